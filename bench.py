@@ -28,7 +28,13 @@ the headline, `records_stay_with_rank` the one with no record exchange at all (a
 travels: hits, sum of t), and --no-gather-records makes the latter the headline.
 value = n x steps / max-over-ranks time.
 
-One JSON line on rank 0, with
+A plain run does only what the headline needs: it sets up, warms up, times --steps steps and prints
+one JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = host clock per
+timed step, config).  --dump-outputs DIR writes, after the timed steps, the hit records rank 0 holds
+from the last step -- a fixed, seeded sample of DUMP_RAYS rays of the dump -- as DIR/<name>.npy.
+
+--full adds everything else: the counted launch and the in-run validation, at N > 1 the other
+readings of the exchange step, and the figures and legs below.
   roofline      the dominant kernel on the headline workload: algorithmic bytes / HIP-event
                 duration vs the 8 TB/s peak.  Its hot set (76 MB) lives in L2 + the 256 MiB
                 Infinity Cache: `residency` says so -- this is NOT an HBM measurement;
@@ -39,7 +45,7 @@ One JSON line on rank 0, with
                 over the ranks, frame gathered to rank 0 (strong scaling);
   pt_render     BASELINE config 4 (plane_sphere, 2048^2, 256 spp);
   cpu_baseline  the compiled reference / the bit-identical port on this box's host cores.
-Every timed launch is validated in-run (`validation`).
+With --full every timed launch is validated in-run (`validation`).
 """
 import argparse
 import ctypes as C
@@ -63,6 +69,49 @@ from benchlegs.ao import ao_frame_leg  # noqa: E402
 from benchlegs.config2 import config2_leg  # noqa: E402
 from benchlegs.pt import pt_frame_leg  # noqa: E402
 from benchlegs.cpu import cpu_baseline  # noqa: E402
+
+DUMP_RAYS = 1 << 20            # --dump-outputs: rays sampled from the dump (5 arrays x 8 bytes x 1 M = 40 MB at most)
+DUMP_SEED = 88172645           # fixed: the same sample in every run with the same arguments
+
+
+def dump_outputs(path, torch, la, mode, dev, nrec, records_of):
+    """--dump-outputs: the records of a fixed, seeded sample of the nrec rays rank 0 holds records of -> path/<name>.npy.
+    records_of(ix) -> tensors of the records of dump rays ix (int64, device); every array is written as float32 / float64"""
+    os.makedirs(path, exist_ok=True)
+    ix = np.arange(nrec) if nrec <= DUMP_RAYS else np.unique(np.random.default_rng(DUMP_SEED).integers(0, nrec, DUMP_RAYS))
+    names = ("prim", "t", "u", "v") if mode == la.MODE_CLOSEST else ("occluded",)
+    arrays = {"ray_index": ix.astype(np.float64)}
+    for name, x in zip(names, records_of(torch.from_numpy(ix).to(dev))):
+        x = x.cpu().numpy()
+        arrays[name] = x.astype(np.float32 if x.dtype in (np.float32, np.uint8) else np.float64)    # prim: int32, exact in float64
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def gathered_records(torch, la, mode, ix, gathered, starts, per, wire_bytes):
+    """N > 1, rank 0: the records of dump rays ix in the gathered slabs (gathered[c][r] = rank r's chunk c; starts[r] = rank r's
+    first ray) -> (prim, t, u, v) or (occluded,); t, u, v are fp32 on the 16-byte wire"""
+    world = len(starts)
+    r = torch.searchsorted(starts, ix, right=True) - 1
+    l = ix - starts[r]
+    c, j = l // per, l % per
+    out = None
+    for c_ in range(len(gathered)):
+        for r_ in range(world):
+            row = gathered[c_][r_]
+            if wire_bytes == 16:
+                rec = row.view(torch.int32).view(per, 4)
+                cols = (rec[:, 0],) + tuple(rec[:, k].view(torch.float32) for k in (1, 2, 3))
+            elif mode == la.MODE_CLOSEST:
+                cols = record_views(torch, row.clone(), per)[:4]       # a row starts at r * per * 28 bytes: not 8-byte aligned in general
+            else:
+                cols = (row[:per],)
+            if out is None:
+                out = [torch.empty(len(ix), dtype=x.dtype, device=ix.device) for x in cols]
+            sel = (r == r_) & (c == c_)
+            for o_, x in zip(out, cols):
+                o_[sel] = x[j[sel]]
+    return out
 
 
 def main():
@@ -108,11 +157,21 @@ def main():
     ap.add_argument("--ao-samples", type=int, default=64)
     ap.add_argument("--ao-tess", type=int, default=8, help="midpoint-subdivision levels of the example scene (4^n x 322 triangles; 8 -> 21.1 M = BASELINE config 5's '>= 10 M', 7 -> 5.3 M)")
     ap.add_argument("--only", choices=["hbm", "ao", "pt", "config2"], default=None,
-                    help="profiling aid: run one secondary leg (the headline shrinks to a 1 M-ray smoke pass)")
+                    help="profiling aid: run one secondary leg (implies --full; the headline shrinks to a 1 M-ray smoke pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the counted launch (roofline), the in-run validation, the other builder's tree, N > 1's other readings "
+                         "of the exchange step, and the legs (cpu_baseline, host_path, roofline_hbm, ao_render, config2, pt_render, gather ceiling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the hit records of the last step (a fixed, seeded sample of the dump's rays) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.only:
-        args.rays = 1_000_000; args.steps = max(1, min(args.steps, 2)); args.no_cpu = True
+        args.full = True
+        args.rays = 1_000_000; args.no_cpu = True
         args.no_hbm = args.only != "hbm"; args.no_ao = args.only != "ao"; args.no_pt = args.only != "pt"; args.no_config2 = args.only != "config2"
+    if not args.full:               # the headline alone: no leg, no comparison launches
+        args.no_cpu = args.no_hbm = args.no_ceiling = args.no_ao = args.no_pt = args.no_config2 = args.no_other_builder = True
 
     import torch
     import lucille_amd as la
@@ -136,7 +195,7 @@ def main():
     b0, b1 = shard.ray_slice(n_total, rank, world)
     n = b1 - b0
     d_org, d_dir, first = upload_rays(scenes, torch, dev, scenes.skip(st_after_tris, 5 * b0), n,
-                                      keep_first=args.cpu_rays if rank == 0 else 0)
+                                      keep_first=args.cpu_rays if rank == 0 and not args.no_cpu else 0)
 
     # ONE host build (rank 0), then the flattened scene into every rank's HBM: ncclBroadcast
     acc = la.HipAccel(local)
@@ -211,13 +270,14 @@ def main():
     one_step(False)                                   # allocations, lazy uploads (untimed)
     torch.cuda.synchronize(dev)
 
-    # ---- algorithmic bytes per ray: counted launch on a sample (untimed) ---------
-    ns = min(n, 4_000_000)
-    cnt_out, cnt = acc.intersect_device(d_org[:ns], d_dir[:ns], mode=mode, variant=args.variant, counters=True)
-    n_nodes = cnt["nodes"] / ns; n_tris = cnt["tris"] / ns
-    b_out = B_OUT if mode == la.MODE_CLOSEST else 4
+    # ---- algorithmic bytes per ray: counted launch on a sample (untimed; --full) ---------
     node_fmt = "f32" if args.variant == 0 else "q16x4"
-    b_ray = B_IN + b_out + B_NODE[node_fmt] * n_nodes + B_TRI * n_tris
+    if args.full:
+        ns = min(n, 4_000_000)
+        cnt_out, cnt = acc.intersect_device(d_org[:ns], d_dir[:ns], mode=mode, variant=args.variant, counters=True)
+        n_nodes = cnt["nodes"] / ns; n_tris = cnt["tris"] / ns
+        b_out = B_OUT if mode == la.MODE_CLOSEST else 4
+        b_ray = B_IN + b_out + B_NODE[node_fmt] * n_nodes + B_TRI * n_tris
 
     # ---- timed region -------------------------------------------------------------
     # ONE exchange step -- the hit-record slices gathered to GPU 0.  At N > 1 that gather is INSIDE the headline's timed
@@ -252,10 +312,21 @@ def main():
     torch.cuda.synchronize(dev); barrier()
     t1 = time.perf_counter()
     elapsed = t1 - t0
+    # what rank 0 holds after the last timed step: at N = 1 the whole dump's records; at N > 1 every rank's gathered records,
+    # or with --no-gather-records those of its own slice
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            dump_outputs(args.dump_outputs, torch, la, mode, dev, n, lambda ix: tuple(x[ix] for x in outs_of(0)[0]))
+        elif not head_gather:
+            dump_outputs(args.dump_outputs, torch, la, mode, dev, n, lambda ix: tuple(x[ix] for x in whole_out))
+        else:
+            starts = torch.tensor([shard.ray_slice(n_total, r_, world)[0] for r_ in range(world)], device=dev)
+            dump_outputs(args.dump_outputs, torch, la, mode, dev, n_total,
+                         lambda ix: gathered_records(torch, la, mode, ix, gathered, starts, per, wire_bytes))
     # N > 1: the other reading of the exchange step (secondary figure); the gathered pass also fills `gathered` for the validation
     other_elapsed = None
     gather_only_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         gsteps = max(1, min(args.steps, 3))
         other_step(False)
         barrier(); torch.cuda.synchronize(dev)
@@ -318,7 +389,7 @@ def main():
             stay_elapsed = elapsed / args.steps
     # ---- per-rank diagnostics (N > 1): every rank says what it did, on stderr and -- collected by rank 0 -- in the line ----
     ranks = None
-    if world > 1:
+    if world > 1 and args.full:
         d_ = shard.dist()
         mine = {"rank": rank, "device": local, "transport": "rccl" if (d_ is not None and d_.transport == la.DIST_RCCL) else "shm",
                 "rccl_status": shard.rccl_status(), "rays": int(n), "launches_per_step": int(launches_per_step),
@@ -328,7 +399,7 @@ def main():
 
     # ---- the digest every rank sends instead of its records: hits and sum of t of its slice ------------------
     digest = None
-    if mode == la.MODE_CLOSEST:
+    if mode == la.MODE_CLOSEST and args.full:
         if not head_gather:
             hp = whole_out[0][:n] != -1; ht = whole_out[1][:n]
             lh_, lt_ = float(hp.sum().item()), float(ht[hp].sum().item())
@@ -343,7 +414,7 @@ def main():
 
     # ---- validation of the timed launches (rank 0) --------------------------------
     validation = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if not head_gather:         # the headline's own launch: one buffer; the gathered chunks are checked against the chunked pass's
             validation = validate_dump(torch, la, args, mode, lambda c: (whole_out, n), [(0, n)], cnt_out, ns, gathered, world, per, n_total, bufs, nchunks, wire_bytes)
         else:
@@ -382,18 +453,6 @@ def main():
 
     if rank == 0:
         value = n_total * args.steps / elapsed / 1e6
-        achieved = b_ray * n / (kernel_ms * 1e-3) / 1e9
-        traffic = traffic_source = traffic_ms = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if os.path.exists(pmc) and world == 1:
-            try:
-                j = json.load(open(pmc))
-                if j.get("rays_per_launch") == n and j.get("mode") == args.mode and j.get("kernel_tag") == node_fmt \
-                        and args.variant in (-1, 4):
-                    traffic = j.get("hbm_bytes_per_launch"); traffic_ms = j.get("kernel_avg_ms_rocprof")
-                    traffic_source = pmc_source("profiles/pmc_latest.json", j)
-            except Exception:
-                traffic = traffic_source = None
         hot_mb = (info["nnodes_traversal"] * 64 + info["ntriangles"] * 48) / 1e6
         res = {
             "metric": "Mrays/s (primary+AO)", "value": round(value, 2), "unit": "Mrays/s",
@@ -414,29 +473,42 @@ def main():
                                "other_builder": other,
                                "nodes": info["nnodes_traversal"], "depth": info["max_depth"], "device_bytes": info["device_bytes"],
                                "build_s": round(info["build_seconds"], 3), "ref_tree_build_s": round(info["ref_build_seconds"], 3)}},
-            "roofline": {"bound": "l2+mall" if hot_mb < 256.0 else "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "traffic_over_algorithmic": None if traffic is None else round(traffic / (b_ray * n), 3),
-                         "traffic_frac_of_peak": None if traffic is None or not traffic_ms else round(traffic / (traffic_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                         "peak_note": "peak = the 8 TB/s HBM datasheet figure, kept as the common denominator; this workload's hot set is cache-resident, "
-                                      "so `frac` is NOT a fraction of a bandwidth the data asked of HBM -- the HBM-bound figure is roofline_hbm.frac",
-                         "formula": "bytes_per_ray = %d + %d + %d x nodes_per_ray + %d x tris_per_ray (SURVEY 8d); achieved = bytes_per_ray x rays_per_launch / kernel_ms; "
-                                    "frac = achieved / peak" % (B_IN, b_out, B_NODE[node_fmt], B_TRI),
-                         "residency": "hot set %.0f MB (4-wide nodes + tri32) < 256 MiB Infinity Cache: served by L2 + MALL, "
-                                      "NOT an HBM measurement; see roofline_hbm" % hot_mb,
-                         "kernel": "k_trace_persist_lane<walk=spec,%s nodes>" % node_fmt if args.variant in (-1, 4) else "k_trace_direct<%s nodes>" % node_fmt,
-                         "node_bytes": B_NODE[node_fmt], "launches_per_step": launches_per_step,
-                         "kernel_ms": round(kernel_ms, 3), "bytes_per_ray": round(b_ray, 1),
-                         "nodes_per_ray": round(n_nodes, 3), "tris_per_ray": round(n_tris, 3)},
-            "validation": validation,
         }
+        if args.full:
+            achieved = b_ray * n / (kernel_ms * 1e-3) / 1e9
+            traffic = traffic_source = traffic_ms = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
+            if os.path.exists(pmc) and world == 1:
+                try:
+                    j = json.load(open(pmc))
+                    if j.get("rays_per_launch") == n and j.get("mode") == args.mode and j.get("kernel_tag") == node_fmt \
+                            and args.variant in (-1, 4):
+                        traffic = j.get("hbm_bytes_per_launch"); traffic_ms = j.get("kernel_avg_ms_rocprof")
+                        traffic_source = pmc_source("profiles/pmc_latest.json", j)
+                except Exception:
+                    traffic = traffic_source = None
+            res["roofline"] = {"bound": "l2+mall" if hot_mb < 256.0 else "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                               "traffic_over_algorithmic": None if traffic is None else round(traffic / (b_ray * n), 3),
+                               "traffic_frac_of_peak": None if traffic is None or not traffic_ms else round(traffic / (traffic_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                               "peak_note": "peak = the 8 TB/s HBM datasheet figure, kept as the common denominator; this workload's hot set is cache-resident, "
+                                            "so `frac` is NOT a fraction of a bandwidth the data asked of HBM -- the HBM-bound figure is roofline_hbm.frac",
+                               "formula": "bytes_per_ray = %d + %d + %d x nodes_per_ray + %d x tris_per_ray (SURVEY 8d); achieved = bytes_per_ray x rays_per_launch / kernel_ms; "
+                                          "frac = achieved / peak" % (B_IN, b_out, B_NODE[node_fmt], B_TRI),
+                               "residency": "hot set %.0f MB (4-wide nodes + tri32) < 256 MiB Infinity Cache: served by L2 + MALL, "
+                                            "NOT an HBM measurement; see roofline_hbm" % hot_mb,
+                               "kernel": "k_trace_persist_lane<walk=spec,%s nodes>" % node_fmt if args.variant in (-1, 4) else "k_trace_direct<%s nodes>" % node_fmt,
+                               "node_bytes": B_NODE[node_fmt], "launches_per_step": launches_per_step,
+                               "kernel_ms": round(kernel_ms, 3), "bytes_per_ray": round(b_ray, 1),
+                               "nodes_per_ray": round(n_nodes, 3), "tris_per_ray": round(n_tris, 3)}
+            res["validation"] = validation
         if digest is not None:
             validation["digest_all_ranks"] = dict(digest, hit_rate=round(digest["hits"] / max(1, n_total), 4))
             validation["ok"] = bool(validation["ok"]) and 0.5 < digest["hits"] / max(1, n_total) < 0.99
         if validation is not None and other is not None and other["records_bit_equal"] is not None:
             validation["records_equal_on_the_other_builders_tree"] = other["records_bit_equal"]       # hit records do not depend on the tree
             validation["ok"] = bool(validation["ok"]) and bool(other["records_bit_equal"])
-        if world > 1:
+        if world > 1 and args.full:
             res["exchange"] = {"headline_includes_record_gather": bool(head_gather),
                                "definition": "SURVEY 8e: hit-record slices gathered to GPU 0 (one exchange step); the gather is inside the headline's timed region "
                                              "unless --no-gather-records.  Rounds 1-2 timed it inside, round 3's headline did not: compare N > 1 values across rounds "

@@ -103,7 +103,7 @@ def test_bench_n2_code_path_on_one_gpu():
     passing validation of the strong-scaling ray dump (rank 0's own records + the gathered slices) and of the legs"""
     env = dict(os.environ)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--backend", "gloo", "--device-override", "0", "--rays", "3000001", "--tris", "200000", "--half-extent", "0.01",
            "--no-cpu", "--no-hbm", "--ao-size", "256", "--ao-tess", "2", "--ao-samples", "16", "--pt-size", "128", "--pt-spp", "8"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
@@ -133,7 +133,7 @@ def test_bench_n2_over_the_rccl_branch_with_a_mock_library():
     from tests.test_gpu_dist_mock import build_mock
     env = dict(os.environ, LH_DIST_TRANSPORT="rccl", LH_RCCL_LIBRARY=build_mock(), MOCK_RCCL_TIMEOUT="120")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--device-override", "0", "--rays", "2000001", "--tris", "100000", "--half-extent", "0.01", "--record-bytes", "28",
            "--no-cpu", "--no-hbm", "--no-pt", "--ao-size", "192", "--ao-tess", "2", "--ao-samples", "16"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
@@ -150,7 +150,7 @@ def test_bench_n2_over_the_rccl_branch_with_a_mock_library():
 def _bench_n8(extra_env, extra_args=()):
     env = dict(os.environ); env.update(extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--steps", "2", "--warmup", "1",
            "--device-override", "0", "--rays", "1600003", "--tris", "60000", "--half-extent", "0.012",
            "--no-cpu", "--no-hbm", "--ao-size", "200", "--ao-tess", "2", "--ao-samples", "16", "--pt-size", "96", "--pt-spp", "4"] + list(extra_args)
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=1500)

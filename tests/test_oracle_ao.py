@@ -9,9 +9,9 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
-from tests.helpers import load_golden
+from tests.helpers import GOLDEN, load_golden
 
-RIB = "/root/reference/examples/ambient_occlusion/ambient_occlusion.rib"
+RIB = os.path.join(GOLDEN, "rib", "ambient_occlusion.rib")     # the reference's example scene (BASELINE config 1), stored as data
 
 
 def oracle_from_fixture(g):
@@ -82,7 +82,7 @@ def test_spiral_visits_every_bucket_once():
             assert pts == {(i, j) for i in range(nx) for j in range(ny)}
 
 
-@pytest.mark.skipif(not po.ref_available() or not os.path.exists(RIB), reason="needs oracle/_ref and /root/reference")
+@pytest.mark.skipif(not po.ref_available(), reason="compiled reference not built")
 @pytest.mark.parametrize("w,h,ns,ps", [(64, 64, 9, 2), (96, 96, 64, 1)])
 def test_ao_live_reference(tmp_path, w, h, ns, ps):
     """other sizes / sample counts than the golden, against a fresh reference render"""

@@ -38,9 +38,16 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
-def _worker(rank, world, port, W, H, T, q):
+def _init_host_rank(rank, world, port):
+    """shard.init_process_group as on a box without a GPU: the gloo group alone.  Where a GPU is visible it would also put
+    rank r on device r (a one-GPU box has no device 1) and bring up lh_dist_* -- the device side, which test_gpu_shard.py covers"""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    r, w, _ = shard.init_process_group(backend="gloo")
+    torch.cuda.is_available = lambda: False          # this spawned process only
+    return shard.init_process_group(backend="gloo")
+
+
+def _worker(rank, world, port, W, H, T, q):
+    r, w, _ = _init_host_rank(rank, world, port)
     assert (r, w) == (rank, world)
     tiles = shard.tile_grid(W, H, T)
     mine = shard.tiles_of_rank(len(tiles), rank, world)
@@ -92,8 +99,7 @@ def test_tile_gather_world2_gloo(W, H, T):
 def _dump_worker(rank, world, port, n, nchunks, q):
     """the strong-scaling ray-dump exchange of bench.py on gloo: every rank produces 'hit records' for its
     slice of one dump (here: a function of the absolute ray id), chunk by chunk, and rank 0 gathers them"""
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    shard.init_process_group(backend="gloo")
+    _init_host_rank(rank, world, port)
     b0, b1 = shard.ray_slice(n, rank, world)
     per = shard.chunk_capacity(n, world, nchunks)
     got = [torch.zeros((world, per * 4), dtype=torch.uint8) for _ in range(nchunks)] if rank == 0 else None
@@ -155,8 +161,7 @@ def test_serpentine_bands_cover_once_and_cancel_a_slope():
 def _band_worker(rank, world, port, W, H, rows, q):
     """the AO frame's exchange step on gloo: every rank fills the slabs of ITS serpentine bands with a function of the frame
     position, one gather, rank 0 places them (render.assemble_shards: the regular fast path and the clipped-last-band path)"""
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    shard.init_process_group(backend="gloo")
+    _init_host_rank(rank, world, port)
     _, y0s = render.bands_for(H, world, rows)
     mine = shard.bands_of_rank(len(y0s), rank, world)
     per = (len(y0s) + world - 1) // world
