@@ -145,14 +145,50 @@ int  lh_accel_intersect_device(lh_accel_t *accel, size_t n, const void *d_org_xy
                                void *d_v, void *d_occluded, int mode, int variant,
                                void *stream);
 
+/* ---- ray and record formats of the batch entry points (lh_accel_intersect_host_ex / _device_ex) ----
+ * LH_RAYS_F64: org_xyz / dir_xyz hold 3 doubles per ray (the format of lh_accel_intersect_host / _device).
+ * LH_RAYS_F32: the same layout with 3 floats per ray.  A float ray is traced as the fp64 ray ((double)org[k], (double)dir[k]):
+ *   its records are bit-equal to what the fp64 entry points return for those widened rays, and the fp64 path's rules (the
+ *   reference's |dir.y| <= 1e-14 exclusions among them) apply to the widened ray.
+ * LH_REC_F64: closest-hit records as SoA arrays prim (u32), t, u, v (f64) -- the format of the fp64 entry points.
+ * LH_REC16: closest-hit records as an array of lh_rec16_t (16-byte aligned): prim unchanged, t, u, v each (float) of the fp64
+ *   record -- exactly the rounding lh_dist_pack_records16 applies to the wire.  A miss is prim = LH_MISS, t = (float)1e38, and
+ *   u, v whatever the fp64 miss record rounds to.
+ * Any-hit mode writes the occluded byte per ray with either ray format; LH_REC16 does not apply to it. */
+#define LH_RAYS_F64 0
+#define LH_RAYS_F32 1
+#define LH_REC_F64  0
+#define LH_REC16    1
+typedef struct lh_rec16 { uint32_t prim; float t, u, v; } lh_rec16_t;
+#ifdef __cplusplus
+static_assert(sizeof(lh_rec16_t) == 16, "lh_rec16_t is 16 bytes");
+#else
+_Static_assert(sizeof(lh_rec16_t) == 16, "lh_rec16_t is 16 bytes");
+#endif
+/* lh_accel_intersect_host / _device with a ray format (LH_RAYS_*) and a record format (LH_REC_*).  prim_or_rec16: the prim
+ * array (LH_REC_F64) or the lh_rec16_t array (LH_REC16); t, u, v: the f64 arrays of LH_REC_F64, NULL with LH_REC16.
+ * The host form is synchronous and moves each format's own bytes over the link (24 bytes per fp32 ray up, 16 per LH_REC16
+ * record down, 1 per any-hit ray; pipelined like lh_accel_intersect_host from 2 M rays on); the device form enqueues the
+ * default variant on `stream` and returns.  -1 (lh_last_error), nothing written: an unknown format or mode, a misaligned
+ * LH_REC16 pointer, LH_REC16 in any-hit mode, non-NULL t / u / v with LH_REC16.  n == 0 returns 0 (the record array is not
+ * looked at, it may be NULL; an unknown format or mode is still refused).  With
+ * lh_accel_trace_statistics on, they count as lh_accel_intersect_host / _device do. */
+int  lh_accel_intersect_host_ex(lh_accel_t *accel, size_t n, const void *org_xyz, const void *dir_xyz, int ray_format,
+                                int record_format, void *prim_or_rec16, double *t, double *u, double *v,
+                                uint8_t *occluded, int mode);
+int  lh_accel_intersect_device_ex(lh_accel_t *accel, size_t n, const void *d_org_xyz, const void *d_dir_xyz, int ray_format,
+                                  int record_format, void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v,
+                                  void *d_occluded, int mode, void *stream);
+
 /* same launch with traversal statistics: counters[4] (host) receives
  * {inner-node visits, triangle tests, fp64 resolves, rays}; synchronous. */
 int  lh_accel_intersect_device_counted(lh_accel_t *accel, size_t n, const void *d_org_xyz,
                                        const void *d_dir_xyz, void *d_prim, void *d_t,
                                        void *d_u, void *d_v, void *d_occluded, int mode,
                                        int variant, uint64_t counters[4]);
-/* rays of the last counted launch that were finished outside the main kernel: the reference-order walk (exact-t ties,
- * fragile hits) and the private-stack walk for rays whose LDS stack column would have overflowed */
+/* rays of the last counted launch (lh_accel_intersect_device_counted, or a host batch -- lh_accel_intersect_host / _host_ex --
+ * with lh_accel_trace_statistics on) that were finished outside the main kernel: the reference-order walk (exact-t ties,
+ * fragile hits), the cooperative walk, and the private-stack walk for rays whose LDS stack column would have overflowed */
 uint64_t lh_accel_last_retraced(const lh_accel_t *accel);
 /* bytes of the node record the ray-dump entry points (lh_accel_intersect_host / _device) walk on this scene: 64 (4-wide
  * 16-bit-grid node), or 128 (8-wide, one cache line) when the scene's hot set does not fit the 256 MiB Infinity Cache --

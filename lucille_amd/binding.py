@@ -19,6 +19,8 @@ MISS = 0xFFFFFFFF
 T_INF = 1.0e38
 MODE_CLOSEST, MODE_ANY = 0, 1
 VARIANT_DEFAULT, VARIANT_DIRECT, VARIANT_SPEC = -1, 0, 4      # the tuned walk (= SPEC), the textbook reference walk
+RAYS_F64, RAYS_F32 = 0, 1           # ray formats of the _ex batch entry points (include/lucille_hip.h)
+REC_F64, REC16 = 0, 1               # record formats: SoA prim / t / u / v, or 16-byte records {prim u32, t, u, v f32}
 
 
 class LucilleHipError(RuntimeError):
@@ -105,7 +107,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 ABI_SYMBOLS = [
     "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
-    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
+    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
     "lh_render_ao_tile", "lh_render_ao_tile_host", "lh_render_ao_bands", "lh_render_scratch", "lh_accel_beam_visibility_host", "lh_accel_beam_visibility_device", "lh_accel_beam_visibility_set_host", "lh_accel_beam_raster_host", "lh_accel_beam_raster_device", "lh_accel_beam_raster_set_host", "lh_render_pt_tile",
     "lh_accel_trace_statistics", "lh_accel_statistics", "lh_accel_slot_statistics",
@@ -154,6 +156,8 @@ def lib():
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.lh_accel_intersect_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32]
     L.lh_accel_intersect_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+    L.lh_accel_intersect_host_ex.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32]
+    L.lh_accel_intersect_device_ex.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.lh_accel_last_retraced.argtypes = [vp]; L.lh_accel_last_retraced.restype = C.c_uint64
     L.lh_accel_dump_node_bytes.argtypes = [vp]
     L.lh_accel_intersect_device_counted.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32,
@@ -222,6 +226,29 @@ def _check(rc, what):
 
 def _np(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
+
+
+def _is_f32(a):
+    """a float32 numpy array or torch tensor (the dtype selects the ray format of the batch entry points)"""
+    dt = getattr(a, "dtype", None)
+    if dt is None:
+        return False
+    if isinstance(dt, np.dtype):
+        return dt == np.float32
+    return str(dt) == "torch.float32"
+
+
+def _rec16_host(n):
+    """an (n, 4) uint32 array whose data is 16-byte aligned (lh_rec16_t records)"""
+    raw = np.empty(4 * n + 4, np.uint32)
+    k = (-raw.ctypes.data % 16) // 4
+    return raw[k:k + 4 * n].reshape(n, 4)
+
+
+def _records_format(records):
+    if records not in ("f64", "rec16"):
+        raise ValueError("records must be 'f64' or 'rec16', not %r" % (records,))
+    return REC16 if records == "rec16" else REC_F64
 
 
 def _dptr(t):
@@ -369,7 +396,32 @@ class HipAccel:
                                                 C.byref(u), C.byref(v)), "lh_accel_intersect1")
         return hit, int(p.value), t.value, u.value, v.value
 
-    def intersect_host(self, org, dr, mode=MODE_CLOSEST):
+    def intersect_host(self, org, dr, mode=MODE_CLOSEST, records="f64"):
+        """org, dr: [n, 3] host rays.  float32 inputs (numpy arrays or CPU torch tensors, both float32) are sent as fp32 rays
+        (traced as the widened fp64 rays: the same records); anything else as fp64.  records="rec16" (closest hit): the records
+        come back as one (n, 4) uint32 array of lh_rec16_t {prim, t, u, v as float32 bits}; else (prim, t, u, v) / occluded."""
+        rf = _records_format(records)
+        f32 = _is_f32(org) and _is_f32(dr)
+        if f32 or rf == REC16:
+            dt = np.float32 if f32 else np.float64
+            o = _np(org, dt).reshape(-1, 3); d = _np(dr, dt).reshape(-1, 3)
+            n = o.shape[0]
+            fmt = RAYS_F32 if f32 else RAYS_F64
+            if mode == MODE_CLOSEST and rf == REC16:
+                rec = _rec16_host(n)
+                _check(self.L.lh_accel_intersect_host_ex(self.h, n, o.ctypes.data, d.ctypes.data, fmt, rf, rec.ctypes.data,
+                                                         None, None, None, None, mode), "lh_accel_intersect_host_ex")
+                return rec
+            if mode == MODE_CLOSEST:
+                prim = np.empty(n, np.uint32); t = np.empty(n); u = np.empty(n); v = np.empty(n)
+                _check(self.L.lh_accel_intersect_host_ex(self.h, n, o.ctypes.data, d.ctypes.data, fmt, rf, prim.ctypes.data,
+                                                         t.ctypes.data, u.ctypes.data, v.ctypes.data, None, mode),
+                       "lh_accel_intersect_host_ex")
+                return prim, t, u, v
+            occ = np.empty(n, np.uint8)
+            _check(self.L.lh_accel_intersect_host_ex(self.h, n, o.ctypes.data, d.ctypes.data, fmt, rf, None, None, None, None,
+                                                     occ.ctypes.data, mode), "lh_accel_intersect_host_ex")
+            return occ
         o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3)
         n = o.shape[0]
         if mode == MODE_CLOSEST:
@@ -384,14 +436,41 @@ class HipAccel:
         return occ
 
     def intersect_device(self, org, dr, out=None, mode=MODE_CLOSEST, variant=VARIANT_DEFAULT, stream=None,
-                         counters=False):
-        """org, dr: CUDA(HIP) float64 tensors [n,3], contiguous.  Enqueues on `stream`
-        (default: torch's current stream) and returns the output tensors."""
+                         counters=False, records="f64"):
+        """org, dr: CUDA(HIP) float64 or float32 tensors [n,3] (both of one dtype: float32 = fp32 rays, traced as the widened
+        fp64 rays), contiguous.  Enqueues on `stream` (default: torch's current stream) and returns the output tensors:
+        (prim, t, u, v), (occluded,), or with records="rec16" (closest hit) (rec,) -- one (n, 4) int32 tensor of lh_rec16_t
+        {prim, t, u, v as float32 bits}.  fp32 rays and rec16 records run the default variant, without counters."""
         import torch
-        assert org.is_cuda and dr.is_cuda and org.dtype == torch.float64 and dr.dtype == torch.float64
+        assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
         assert org.is_contiguous() and dr.is_contiguous()
+        rf = _records_format(records)
         n = org.shape[0]
         dev = org.device
+        if org.dtype == torch.float32 or rf == REC16:
+            if variant != VARIANT_DEFAULT or counters:
+                raise ValueError("fp32 rays / rec16 records run the default variant without counters")
+            fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
+            if out is None:
+                if mode == MODE_CLOSEST and rf == REC16:
+                    out = (torch.empty((n, 4), dtype=torch.int32, device=dev),)
+                elif mode == MODE_CLOSEST:
+                    out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                           torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
+                else:
+                    out = (torch.empty(n, dtype=torch.uint8, device=dev),)
+            if mode == MODE_CLOSEST and rf == REC16:
+                prim, t, u, v, occ = out[0], None, None, None, None
+            elif mode == MODE_CLOSEST:
+                (prim, t, u, v), occ = out, None
+            else:
+                prim = t = u = v = None; occ = out[0]
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(self.L.lh_accel_intersect_device_ex(self.h, n, _dptr(org), _dptr(dr), fmt, rf, _dptr(prim), _dptr(t), _dptr(u),
+                                                       _dptr(v), _dptr(occ), mode, C.c_void_p(stream)),
+                   "lh_accel_intersect_device_ex")
+            return out
         if out is None:
             if mode == MODE_CLOSEST:
                 out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),

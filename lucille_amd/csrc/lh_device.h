@@ -54,6 +54,7 @@ typedef struct lh_dev_scene {
     uint32_t    coop_patience; /* 0 (half a second), or: wall-clock ticks of 10 ns the pass beside a producer waits without progress before it leaves the queue to the sweep (tests) */
     uint32_t    ao_group;  /* fused AO stage: work items in groups of this many hit slots, a group's slots side by side per sample; 0 (the default): a slot's samples side by side */
     uint32_t    top_nodes; /* the first top_nodes 4-wide nodes (level order: the top of the tree) are walked from a copy in the workgroup's LDS; 0: none */
+    uint32_t    io_fmt;    /* ray dumps (ray source 0): LH_IO_* bits -- how the launch reads its rays and writes its records; 0: fp64 rays, SoA fp64 records */
     const void *cam_src;       /* NULL, or: ray source 2 -- the launch's rays are the camera rays of a path-traced pass (PtCamSrc, lh_pt.h), org / dir unused */
     const uint32_t *n_dev;     /* NULL, or: the launch's ray count lives on the device (the path tracer's bounce chain; the host passes an upper bound) */
     uint32_t   *diag_out;      /* NULL, or: four counts per ray of this launch (4-wide node visits, leaf visits, triangle records through the fp32
@@ -105,6 +106,9 @@ enum {
 #define LH_RAY_BUDGET     128u         /* default visit budget of the persistent walk (set_param "ray_budget") */
 #define LH_PRIM_OVERFLOW  0xFFFFFFFDu  /* the LDS stack column was too short for this ray: k_overflow_fix */
 #define LH_OCC_OVERFLOW   4u
+/* lh_dev_scene_t.io_fmt (launch-uniform; the persistent walk branches on it in its refill and its retire only) */
+#define LH_IO_RAYS_F32    1u           /* org / dir hold 3 floats per ray: widened to fp64 as they are read */
+#define LH_IO_REC16       2u           /* closest-hit records go to `prim` as lh_rec16_t (prim, (float) t, u, v); t / u / v unused */
 
 #ifdef __cplusplus
 extern "C" {

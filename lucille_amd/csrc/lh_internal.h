@@ -184,7 +184,8 @@ extern "C" int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, c
 /* lh_query.hip */
 void lh_comb_destroy(lh_accel_t *a);                 /* the single-ray combiner's pinned block and stream (lh_accel_destroy) */
 int  lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim, void *d_t, void *d_u, void *d_v,
-               void *d_occ, int mode, int variant, unsigned long long *d_counters, hipStream_t s, bool dump);
+               void *d_occ, int mode, int variant, unsigned long long *d_counters, hipStream_t s, bool dump,
+               uint32_t io_fmt = 0u);       /* io_fmt: LH_IO_* (lh_device.h) -- ray dumps in fp32 rays / 16-byte records */
 int  lh_aoq_slot(lh_accel_t *a, hipStream_t s);
 int  lh_ensure_stage(lh_accel_t *a, size_t bytes);
 

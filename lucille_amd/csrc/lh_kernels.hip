@@ -336,14 +336,52 @@ __device__ __forceinline__ void traverse_spec8(Lane &L, int &pend, const lh_dev_
 
 /* resolve whatever is still queued; afterwards `best` is the exact answer */
 
-template <bool ANYHIT>
-__device__ __forceinline__ void write_out(size_t i, const Lane &L, const Best &best,
+/* The formats of a ray dump (sc.io_fmt, launch-uniform: a scalar branch).  Rays: 3 doubles per ray, or 3 floats widened to the
+ * fp64 ray they stand for.  Records: SoA prim / t / u / v, or lh_rec16_t in `prim` -- prim, then t, u, v each (float) of the
+ * fp64 record (lh_dist.hip k_pack_records16's rounding).  The fix-up protocol's flags (LH_PRIM_OVERFLOW / LH_PRIM_RETRACE)
+ * live in the prim word of either format; whoever finishes a flagged ray writes its whole record. */
+template <bool IO = true>          /* IO = false: fp64 rays only (the persistent walk's fp64 instantiations: their refill is the fp64 one, bit for bit) */
+__device__ __forceinline__ void dump_ray(const lh_dev_scene_t &sc, size_t i, const double *__restrict__ org, const double *__restrict__ dir,
+                                         double &ox, double &oy, double &oz, double &dx, double &dy, double &dz)
+{
+    if (IO && (sc.io_fmt & LH_IO_RAYS_F32)) {
+        const float *o = (const float *)org + 3 * i, *d = (const float *)dir + 3 * i;
+        ox = (double)o[0]; oy = (double)o[1]; oz = (double)o[2];
+        dx = (double)d[0]; dy = (double)d[1]; dz = (double)d[2];
+    } else {
+        ox = org[3 * i]; oy = org[3 * i + 1]; oz = org[3 * i + 2];
+        dx = dir[3 * i]; dy = dir[3 * i + 1]; dz = dir[3 * i + 2];
+    }
+}
+
+/* FMT = false: a caller whose records are never dumps (the path tracer's camera rays, SRC 2) compiles the SoA stores alone */
+template <bool FMT = true>
+__device__ __forceinline__ uint32_t &rec_prim(const lh_dev_scene_t &sc, uint32_t *prim, size_t i)
+{
+    return prim[(FMT && (sc.io_fmt & LH_IO_REC16)) ? 4 * i : i];
+}
+
+template <bool FMT = true>
+__device__ __forceinline__ void store_rec(const lh_dev_scene_t &sc, size_t i, uint32_t *__restrict__ prim, double *__restrict__ t,
+                                          double *__restrict__ u, double *__restrict__ v, uint32_t p, double tt, double uu, double vv)
+{
+    if (FMT && (sc.io_fmt & LH_IO_REC16)) {
+        uint4 r;
+        r.x = p; r.y = __float_as_uint((float)tt); r.z = __float_as_uint((float)uu); r.w = __float_as_uint((float)vv);
+        ((uint4 *)prim)[i] = r;
+    } else {
+        prim[i] = p; t[i] = tt; u[i] = uu; v[i] = vv;
+    }
+}
+
+template <bool ANYHIT, bool FMT = true>
+__device__ __forceinline__ void write_out(const lh_dev_scene_t &sc, size_t i, const Lane &L, const Best &best,
                                           uint32_t *__restrict__ prim, double *__restrict__ t,
                                           double *__restrict__ u, double *__restrict__ v,
                                           uint8_t *__restrict__ occ, const bool retrace_on)
 {
     if (L.over) {            /* out of visit budget, or the LDS stack was too short for this ray: k_coop_walk redoes it */
-        if (ANYHIT) occ[i] = (uint8_t)LH_OCC_OVERFLOW; else prim[i] = LH_PRIM_OVERFLOW;
+        if (ANYHIT) occ[i] = (uint8_t)LH_OCC_OVERFLOW; else rec_prim<FMT>(sc, prim, i) = LH_PRIM_OVERFLOW;
         return;
     }
     /* a hit the reference may not reach goes through the reference's own walk (k_fixups);
@@ -352,7 +390,7 @@ __device__ __forceinline__ void write_out(size_t i, const Lane &L, const Best &b
     if (ANYHIT) {
         occ[i] = retrace ? (uint8_t)LH_OCC_RETRACE : ((L.certain || best.prim != LH_MISS_PRIM) ? 1 : 0);
     } else {
-        prim[i] = retrace ? LH_PRIM_RETRACE : best.prim; t[i] = best.t; u[i] = best.u; v[i] = best.v;
+        store_rec<FMT>(sc, i, prim, t, u, v, retrace ? LH_PRIM_RETRACE : best.prim, best.t, best.u, best.v);
     }
 }
 
@@ -412,8 +450,8 @@ __global__ __launch_bounds__(LH_BLOCK) void k_trace_direct(
     const int tid = threadIdx.x;
     const size_t i = (size_t)blockIdx.x * LH_BLOCK + tid;
     if (i >= n) return;
-    const double ox = org[3 * i], oy = org[3 * i + 1], oz = org[3 * i + 2];
-    const double dx = dir[3 * i], dy = dir[3 * i + 1], dz = dir[3 * i + 2];
+    double ox, oy, oz, dx, dy, dz;
+    dump_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
     Lane L; Best best = {LH_T_INF, 0.0, 0.0, LH_MISS_PRIM, 0u};
     uint32_t cn = 0, ct = 0, ce = 0;
     lane_init(L, sc, ox, oy, oz, dx, dy, dz);
@@ -421,7 +459,7 @@ __global__ __launch_bounds__(LH_BLOCK) void k_trace_direct(
     if (__builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
     traverse<ANYHIT, COUNT>(L, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce);
     finish<ANYHIT, COUNT>(L, sc, ox, oy, oz, dx, dy, dz, best, ce);
-    write_out<ANYHIT>(i, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL);
+    write_out<ANYHIT>(sc, i, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL);
     if (COUNT) add_counters(counters, cn, ct, ce, 1);
 }
 
@@ -461,13 +499,12 @@ __device__ __forceinline__ void ao_item(const AoSrc &ao, uint32_t i, uint32_t &s
 
 /* ray `i` of the launch.  SRC 0: from the arrays; 1: the AO ray (slot i / N, sample i % N) regenerated from the hit record
  * (selfp: the triangle it starts on, when that cannot occlude it); 2: the camera ray of path i of a path-traced pass */
-template <int SRC>
+template <int SRC, bool IO = true>
 __device__ __forceinline__ void src_ray(const lh_dev_scene_t &sc, uint32_t i, const double *__restrict__ org, const double *__restrict__ dir,
                                         const AoSrc &ao, double &ox, double &oy, double &oz, double &dx, double &dy, double &dz, uint32_t &selfp)
 {
     if (SRC == 0) {
-        ox = org[3 * (size_t)i]; oy = org[3 * (size_t)i + 1]; oz = org[3 * (size_t)i + 2];
-        dx = dir[3 * (size_t)i]; dy = dir[3 * (size_t)i + 1]; dz = dir[3 * (size_t)i + 2];
+        dump_ray<IO>(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
     } else if (SRC == 1) {
         uint32_t slot, r;
         ao_item(ao, i, slot, r);
@@ -486,7 +523,10 @@ constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 #define LH_REFILL_PASSES 2          /* ranges a refill may draw from (1: rounds 1-5: the lanes a range's end did not fill wait for the next regroup) */
 #endif
 
-template <bool ANYHIT, bool COUNT, int WALK, int SRC>
+/* IO (ray source 0 only): the launch's formats (sc.io_fmt) are read in the refill and written in the retire; false: fp64 rays and
+ * SoA fp64 records only.  Two instantiations instead of one branch: the branch in the retire alone cost the fp64 closest-hit walk
+ * five more spilled VGPRs (1 -> 6, 16 -> 32 bytes of scratch a lane), the fp64 launches now run the parent's code unchanged */
+template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false>
 __device__ __forceinline__ void trace_persist_lane(
     const lh_dev_scene_t &sc, const uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
@@ -535,7 +575,7 @@ __device__ __forceinline__ void trace_persist_lane(
             const bool fragile = sc.ref_nodes != NULL && !L.over && best.prim != LH_MISS_PRIM && best.frag != 0u && !(ANYHIT && L.certain);
             bool queued = false;
             if (__builtin_expect(L.over | fragile, 0)) queued = fixq_push(fq, my, L.over ? LH_Q_COOP : LH_Q_REF);
-            if (SRC != 1) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT>(my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
+            if (SRC != 1) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT, SRC == 0 && IO>(sc, my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
             else if (!L.over && !fragile && (L.certain || best.prim != LH_MISS_PRIM)) { uint32_t sl, rr; ao_item(ao, my, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
             if (COUNT) {
                 cr++;
@@ -626,7 +666,7 @@ __device__ __forceinline__ void trace_persist_lane(
         if (newray != kNoRay) {
             const uint32_t i = newray;
             my = i;
-            src_ray<SRC>(sc, i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
+            src_ray<SRC, IO>(sc, i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
             lane_init(L, sc, ox, oy, oz, dx, dy, dz);
             best.t = LH_T_INF; best.u = 0.0; best.v = 0.0; best.prim = LH_MISS_PRIM; best.frag = 0u;
             stk[0][tid] = kDone;
@@ -660,7 +700,7 @@ __device__ __forceinline__ void trace_persist_lane(
     }
 }
 
-template <bool ANYHIT, bool COUNT, int WALK, int SRC>
+template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false>
 __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_lane(
     lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
@@ -676,7 +716,7 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_l
         for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
         __syncthreads();
     }
-    trace_persist_lane<ANYHIT, COUNT, WALK, SRC>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
+    trace_persist_lane<ANYHIT, COUNT, WALK, SRC, IO>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -802,7 +842,7 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
                             const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
                             gb.prim = rh.prim; gb.t = rh.t; gb.u = rh.u; gb.v = rh.v;
                         }
-                        prim[i] = gb.prim; t[i] = gb.t; u[i] = gb.u; v[i] = gb.v;
+                        store_rec<SRC == 0>(sc, i, prim, t, u, v, gb.prim, gb.t, gb.u, gb.v);
                     }
                 }
                 if (SRC == 1 && (lane & 15) == 0) {
@@ -853,7 +893,7 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
                     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
                     if (SRC == 1) { if (rh.prim != LH_MISS_PRIM) { uint32_t sl, rr; ao_item(ao, ri, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); } }
                     else if (ANYHIT) occ[ri] = rh.prim != LH_MISS_PRIM ? 1 : 0;
-                    else { prim[ri] = rh.prim; t[ri] = rh.t; u[ri] = rh.u; v[ri] = rh.v; }
+                    else store_rec<SRC == 0>(sc, ri, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
                 }
                 ns = 0;
                 progress = wall_clock64();
@@ -943,7 +983,7 @@ __device__ __forceinline__ void flagged_ray(const lh_dev_scene_t &sc, size_t i, 
         pt_camera_ray((const PtCamSrc *)sc.cam_src, (uint32_t)i, o, d);
         ox = o[0]; oy = o[1]; oz = o[2]; dx = d[0]; dy = d[1]; dz = d[2];
     } else {
-        ox = org[3 * i]; oy = org[3 * i + 1]; oz = org[3 * i + 2]; dx = dir[3 * i]; dy = dir[3 * i + 1]; dz = dir[3 * i + 2];
+        dump_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
     }
 }
 
@@ -1003,7 +1043,7 @@ __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *
     }
     L.over = false;
     finish<ANYHIT, true>(L, sc, ox, oy, oz, dx, dy, dz, best, ce);
-    write_out<ANYHIT>(i, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL);
+    write_out<ANYHIT>(sc, i, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL);
     if (cnt) { cnt[0] = cn; cnt[1] = cl; cnt[2] = ct; cnt[3] = ce; }
 }
 
@@ -1017,18 +1057,18 @@ __global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, con
     if (!force && qcount[1] == 0u) return;
     if (sc.n_dev && (size_t)*sc.n_dev < n) n = *sc.n_dev;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        if (anyhit ? (occ[i] == LH_OCC_OVERFLOW) : (prim[i] == LH_PRIM_OVERFLOW)) {
+        if (anyhit ? (occ[i] == LH_OCC_OVERFLOW) : (rec_prim(sc, prim, i) == LH_PRIM_OVERFLOW)) {
             if (anyhit) overflow_walk<true>(sc, i, org, dir, prim, t, u, v, occ);
             else overflow_walk<false>(sc, i, org, dir, prim, t, u, v, occ);
             if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
         }
         if (sc.ref_nodes == NULL) continue;
-        if (anyhit ? (occ[i] != LH_OCC_RETRACE) : (prim[i] != LH_PRIM_RETRACE)) continue;
+        if (anyhit ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE)) continue;
         double ox, oy, oz, dx, dy, dz;
         flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
         const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
         if (anyhit) occ[i] = rh.prim != LH_MISS_PRIM ? 1 : 0;
-        else { prim[i] = rh.prim; t[i] = rh.t; u[i] = rh.u; v[i] = rh.v; }
+        else store_rec(sc, i, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
         if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
     }
 }
@@ -1060,12 +1100,12 @@ __global__ __launch_bounds__(64) void k_trace_small(lh_dev_scene_t sc, uint32_t 
     if (sc.diag_out) { uint32_t *d = sc.diag_out + 4 * (size_t)i; d[0] = cnt[0]; d[1] = cnt[1]; d[2] = cnt[2]; d[3] = cnt[3]; }
     if (counters) add_counters(counters, cnt[0], cnt[2], cnt[3], 1);
     if (sc.ref_nodes == NULL) return;
-    if (ANYHIT ? (occ[i] != LH_OCC_RETRACE) : (prim[i] != LH_PRIM_RETRACE)) return;
+    if (ANYHIT ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE)) return;
     double ox, oy, oz, dx, dy, dz;
     flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
     const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
     if (ANYHIT) occ[i] = rh.prim != LH_MISS_PRIM ? 1 : 0;
-    else { prim[i] = rh.prim; t[i] = rh.t; u[i] = rh.u; v[i] = rh.v; }
+    else store_rec(sc, i, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
 }
 
@@ -1107,12 +1147,19 @@ int launch_one(const lh_dev_scene_t &sc, size_t n, const double *org, const doub
                 LH_LAUNCH_PERSIST((k_trace_persist_lane<false, COUNT, 8, 2>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
             else
                 LH_LAUNCH_PERSIST((k_trace_persist_lane<false, COUNT, 3, 2>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+        } else if (sc.io_fmt) {              /* fp32 rays / 16-byte records: the instantiations that read and write them (IO) */
+            if (walk == 7)
+                LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 7, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+            else if (walk == 8)
+                LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 8, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+            else
+                LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 3, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
         } else if (walk == 7)
-            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 7, 0>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 7, 0, false>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
         else if (walk == 8)
-            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 8, 0>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 8, 0, false>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
         else
-            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 3, 0>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 3, 0, false>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1318,9 +1365,13 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double 
     /* the persistent kernel indexes rays with 32 bits: a larger batch is a sequence of launches */
     const size_t kMaxLaunch = (size_t)1 << 30;
     if (n > kMaxLaunch) {
+        /* element offsets in the launch's formats (sc->io_fmt): 3 floats or doubles per ray, 4 words or 1 per record */
+        const size_t ray_b = (sc->io_fmt & LH_IO_RAYS_F32) ? 3 * sizeof(float) : 3 * sizeof(double);
+        const size_t rec_w = (sc->io_fmt & LH_IO_REC16) ? 4 : 1;
         for (size_t off = 0; off < n; off += kMaxLaunch) {
             const size_t m = (n - off < kMaxLaunch) ? n - off : kMaxLaunch;
-            const int rc = lh_launch_trace(sc, m, d_org + 3 * off, d_dir + 3 * off, d_prim ? d_prim + off : NULL, d_t ? d_t + off : NULL,
+            const int rc = lh_launch_trace(sc, m, (const double *)((const char *)d_org + ray_b * off), (const double *)((const char *)d_dir + ray_b * off),
+                                           d_prim ? d_prim + rec_w * off : NULL, d_t ? d_t + off : NULL,
                                            d_u ? d_u + off : NULL, d_v ? d_v + off : NULL, anyhit, d_occluded ? d_occluded + off : NULL,
                                            d_counters, d_workq, variant, grid_blocks, min_active, tri_batch, q, ncus, stream);
             if (rc != 0) return rc;

@@ -13,11 +13,12 @@
 
 #include "lh_internal.h"
 
-/* fill miss results without touching the scene (empty accel) */
-__global__ void k_fill_miss(size_t n, uint32_t *prim, double *t, double *u, double *v, uint8_t *occ)
+/* fill miss results without touching the scene (empty accel); rec16 (or NULL): 16-byte records instead of prim / t / u / v */
+__global__ void k_fill_miss(size_t n, uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, uint4 *rec16)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    if (rec16) { uint4 r; r.x = LH_MISS_PRIM; r.y = __float_as_uint((float)LH_T_INF); r.z = r.w = __float_as_uint(0.0f); rec16[i] = r; }
     if (prim) prim[i] = LH_MISS_PRIM;
     if (t) t[i] = LH_T_INF;
     if (u) u[i] = 0.0;
@@ -91,26 +92,29 @@ static bool q8_available(const lh_accel_t *a)
 
 int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim,
               void *d_t, void *d_u, void *d_v, void *d_occ, int mode, int variant,
-              unsigned long long *d_counters, hipStream_t s, bool dump)
+              unsigned long long *d_counters, hipStream_t s, bool dump, uint32_t io_fmt)
 {
     if (!a || !a->committed) return fail("intersect: accel not committed");
     if (n == 0) return 0;
     if ((!d_org || !d_dir) && !a->dev.cam_src) return fail("intersect: NULL ray arrays");
-    if (mode == LH_MODE_CLOSEST && (!d_prim || !d_t || !d_u || !d_v)) return fail("intersect: closest mode needs prim,t,u,v outputs");
+    const bool rec16 = mode == LH_MODE_CLOSEST && (io_fmt & LH_IO_REC16);
+    if (rec16 && (!d_prim || d_t || d_u || d_v)) return fail("intersect: 16-byte records go to one array (t, u, v must be NULL)");
+    if (mode == LH_MODE_CLOSEST && !rec16 && (!d_prim || !d_t || !d_u || !d_v)) return fail("intersect: closest mode needs prim,t,u,v outputs");
     if (mode == LH_MODE_ANY && !d_occ) return fail("intersect: any mode needs the occluded output");
     if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect: unknown mode %d", mode);
     HIPCHK(hipSetDevice(a->device));
     if (a->hs->bvh.ntris == 0) {
         size_t blocks = (n + 255) / 256;
         hipLaunchKernelGGL(k_fill_miss, dim3((unsigned)blocks), dim3(256), 0, s, n,
-                           mode == LH_MODE_CLOSEST ? (uint32_t *)d_prim : NULL, (double *)(mode == LH_MODE_CLOSEST ? d_t : NULL),
+                           mode == LH_MODE_CLOSEST && !rec16 ? (uint32_t *)d_prim : NULL, (double *)(mode == LH_MODE_CLOSEST ? d_t : NULL),
                            (double *)(mode == LH_MODE_CLOSEST ? d_u : NULL), (double *)(mode == LH_MODE_CLOSEST ? d_v : NULL),
-                           mode == LH_MODE_ANY ? (uint8_t *)d_occ : NULL);
+                           mode == LH_MODE_ANY ? (uint8_t *)d_occ : NULL, rec16 ? (uint4 *)d_prim : NULL);
         HIPCHK(hipGetLastError());
         return 0;
     }
     if (dump && a->poison_outputs) {          /* LH_POISON_OUTPUTS: every answer slot must be written by the launch */
-        if (mode == LH_MODE_CLOSEST) {
+        if (rec16) HIPCHK(hipMemsetAsync(d_prim, 0x77, n * 16, s));
+        else if (mode == LH_MODE_CLOSEST) {
             HIPCHK(hipMemsetAsync(d_prim, 0x77, n * sizeof(uint32_t), s)); HIPCHK(hipMemsetAsync(d_t, 0x77, n * sizeof(double), s));
             HIPCHK(hipMemsetAsync(d_u, 0x77, n * sizeof(double), s)); HIPCHK(hipMemsetAsync(d_v, 0x77, n * sizeof(double), s));
         } else HIPCHK(hipMemsetAsync(d_occ, 0x77, n, s));
@@ -146,12 +150,13 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
      * closest hit, 2 735 -> 2 772 any hit; the 8-wide walk and the AO stage are best where they are) */
     const bool dump4 = dump && !a->dev.prefer_q8 && !a->knobs_user;
     const bool dump8 = dump && a->dev.prefer_q8 && !a->knobs_user;
+    a->dev.io_fmt = io_fmt & (mode == LH_MODE_ANY ? LH_IO_RAYS_F32 : (LH_IO_RAYS_F32 | LH_IO_REC16));
     int rc = lh_launch_trace(&a->dev, n, (const double *)d_org, (const double *)d_dir, (uint32_t *)d_prim,
                              (double *)d_t, (double *)d_u, (double *)d_v, mode == LH_MODE_ANY,
                              (uint8_t *)d_occ, d_counters, (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR)), variant, grid,
                              dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch,
                              &a->aoq[qk].q, a->ncus, (void *)s);
-    a->dev.ray_budget = budget_keep; a->dev.ray_chunk = chunk_keep; a->dev.stack_cap = cap_keep;
+    a->dev.ray_budget = budget_keep; a->dev.ray_chunk = chunk_keep; a->dev.stack_cap = cap_keep; a->dev.io_fmt = 0u;
     if (rc != 0) return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
@@ -331,10 +336,15 @@ static int pipe_init(lh_accel_t *a)
     return 0;
 }
 
-static int intersect_host_pipelined(lh_accel_t *a, size_t n, const double *org, const double *dir,
-                                    uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode)
+/* io_fmt (LH_IO_*): every stage moves the format's own bytes -- RB bytes per ray and array up (24 fp64, 12 fp32), 16 per record
+ * down for LH_IO_REC16 (the walk writes them into the block's device buffer), 28 for SoA fp64 records, 1 per any-hit ray.  The
+ * blocks are allocated for the largest format (fp64 rays and records) and laid out by the batch's own */
+static int intersect_host_pipelined(lh_accel_t *a, size_t n, const void *org, const void *dir,
+                                    uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode, uint32_t io_fmt)
 {
     if (pipe_init(a) != 0) return -1;
+    const size_t RB = (io_fmt & LH_IO_RAYS_F32) ? 3 * sizeof(float) : 3 * sizeof(double);
+    const bool rec16 = mode == LH_MODE_CLOSEST && (io_fmt & LH_IO_REC16);
     /* CAP: rays a staging block holds (the arrays inside it are CAP apart); C: rays per chunk of THIS batch -- a batch of less than four
      * blocks is cut in four, so that its upload, launch and download overlap too (2 / 3 / 6 pieces: no better, tools/hostpath_sizes.py) */
     const size_t CAP = a->pipe.cap, D = (size_t)a->pipe.depth;
@@ -345,7 +355,8 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const double *org, 
     auto unstage = [&](size_t k) {
         const size_t b = k % D, first = k * C, m = (first + C <= n) ? C : n - first;
         const char *ho = (const char *)a->pipe.h_out[b];
-        if (mode == LH_MODE_CLOSEST) {
+        if (rec16) cs.add((char *)prim + 16 * first, ho, 16 * m);
+        else if (mode == LH_MODE_CLOSEST) {
             if (t) cs.add(t + first, ho, sizeof(double) * m);
             if (u) cs.add(u + first, ho + sizeof(double) * CAP, sizeof(double) * m);
             if (v) cs.add(v + first, ho + 2 * sizeof(double) * CAP, sizeof(double) * m);
@@ -365,8 +376,8 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const double *org, 
         while (unstaged < k && (unstaged + D <= k || hipEventQuery(a->pipe.done[unstaged % D]) == hipSuccess)) unstage(unstaged++);
         (void)hipGetLastError();          /* a query that says "not ready" must not be the next launch check's last error */
         char *hi = (char *)a->pipe.h_in[b], *di = (char *)a->pipe.d_in[b], *dout = (char *)a->pipe.d_out[b];
-        cs.add(hi, org + 3 * first, sizeof(double) * 3 * m);
-        cs.add(hi + sizeof(double) * 3 * CAP, dir + 3 * first, sizeof(double) * 3 * m);
+        cs.add(hi, (const char *)org + RB * first, RB * m);
+        cs.add(hi + RB * CAP, (const char *)dir + RB * first, RB * m);
         cs.run();
         double c2 = diag ? now() : 0; t_copy += c2 - c1;
         /* the rays go up on a stream of their own; trace + records down alternate between two more: chunk k + 1's rays cross the link while
@@ -375,18 +386,20 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const double *org, 
          * step (two uploads sharing the link, then two launches sharing the chip, then two downloads) and nothing overlapped:
          * profiles/r06_hostpath.txt */
         hipStream_t s_in = a->pipe.s[0], s_tr = a->pipe.s[1 + (k & 1)];
-        if (m == CAP) HIPCHK(hipMemcpyAsync(di, hi, sizeof(double) * 6 * CAP, hipMemcpyHostToDevice, s_in));
+        if (m == CAP) HIPCHK(hipMemcpyAsync(di, hi, 2 * RB * CAP, hipMemcpyHostToDevice, s_in));
         else {
-            HIPCHK(hipMemcpyAsync(di, hi, sizeof(double) * 3 * m, hipMemcpyHostToDevice, s_in));
-            HIPCHK(hipMemcpyAsync(di + sizeof(double) * 3 * CAP, hi + sizeof(double) * 3 * CAP, sizeof(double) * 3 * m, hipMemcpyHostToDevice, s_in));
+            HIPCHK(hipMemcpyAsync(di, hi, RB * m, hipMemcpyHostToDevice, s_in));
+            HIPCHK(hipMemcpyAsync(di + RB * CAP, hi + RB * CAP, RB * m, hipMemcpyHostToDevice, s_in));
         }
         HIPCHK(hipEventRecord(a->pipe.in_done[b], s_in));
         HIPCHK(hipStreamWaitEvent(s_tr, a->pipe.in_done[b], 0));
         double *d_t = (double *)dout, *d_u = d_t + CAP, *d_v = d_u + CAP; uint32_t *d_prim = (uint32_t *)(d_v + CAP);
-        const int rc = lh_launch(a, m, di, di + sizeof(double) * 3 * CAP, d_prim, d_t, d_u, d_v, (uint8_t *)dout, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true);
+        const int rc = rec16 ? lh_launch(a, m, di, di + RB * CAP, dout, NULL, NULL, NULL, NULL, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, io_fmt)
+                             : lh_launch(a, m, di, di + RB * CAP, d_prim, d_t, d_u, d_v, (uint8_t *)dout, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, io_fmt);
         if (rc != 0) return rc;
         char *ho = (char *)a->pipe.h_out[b];
-        if (mode == LH_MODE_CLOSEST) {
+        if (rec16) HIPCHK(hipMemcpyAsync(ho, dout, 16 * m, hipMemcpyDeviceToHost, s_tr));
+        else if (mode == LH_MODE_CLOSEST) {
             if (t) HIPCHK(hipMemcpyAsync(ho, d_t, sizeof(double) * m, hipMemcpyDeviceToHost, s_tr));
             if (u) HIPCHK(hipMemcpyAsync(ho + sizeof(double) * CAP, d_u, sizeof(double) * m, hipMemcpyDeviceToHost, s_tr));
             if (v) HIPCHK(hipMemcpyAsync(ho + 2 * sizeof(double) * CAP, d_v, sizeof(double) * m, hipMemcpyDeviceToHost, s_tr));
@@ -403,48 +416,51 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const double *org, 
     return 0;
 }
 
-extern "C" int lh_accel_intersect_host(lh_accel_t *a, size_t n, const double *org, const double *dir,
-                                       uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode)
+/* the host batch in the formats io_fmt (LH_IO_*); the caller holds the accelerator's lock and has checked the arguments */
+static int intersect_host_fmt(lh_accel_t *a, size_t n, const void *org, const void *dir,
+                              uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode, uint32_t io_fmt)
 {
-    lh_guard guard(a);
-    if (!a || !a->committed) return fail("intersect: accel not committed");
-    if (n == 0) return 0;
-    if (!org || !dir) return fail("intersect: NULL ray arrays");
-    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect: unknown mode %d", mode);
     HIPCHK(hipSetDevice(a->device));
     static const size_t pipe_min = getenv("LH_PIPE_MIN") && atoll(getenv("LH_PIPE_MIN")) > 0 ? (size_t)atoll(getenv("LH_PIPE_MIN")) : LH_PIPE_MIN;
     if (n >= pipe_min && !a->stat_on && !getenv("LH_HOST_SIMPLE"))
-        return intersect_host_pipelined(a, n, org, dir, prim, t, u, v, occ, mode);
-    /* layout of the staging block: org | dir | t | u | v | prim | occ */
-    const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t total = 2 * b_ray + 3 * b_d + sizeof(uint32_t) * n + n + 64;
+        return intersect_host_pipelined(a, n, org, dir, prim, t, u, v, occ, mode, io_fmt);
+    /* layout of the staging block: org | dir | t | u | v | prim | occ; 16-byte records (io_fmt LH_IO_REC16) start where t does,
+     * rounded up to 16 bytes (fp64 rays: exactly there) */
+    const bool rec16 = mode == LH_MODE_CLOSEST && (io_fmt & LH_IO_REC16);
+    const size_t w = rec16 ? 4 : 1;                                           /* words per record's prim */
+    const size_t b_ray = ((io_fmt & LH_IO_RAYS_F32) ? sizeof(float) : sizeof(double)) * 3 * n, b_d = sizeof(double) * n;
+    const size_t b_out = (2 * b_ray + 15) & ~(size_t)15;
+    const size_t total = b_out + 3 * b_d + sizeof(uint32_t) * n + n + 64;
     if (lh_ensure_stage(a, total) != 0) return -1;
     char *base = (char *)a->d_stage;
-    double *d_org = (double *)base, *d_dir = (double *)(base + b_ray);
-    double *d_t = (double *)(base + 2 * b_ray), *d_u = d_t + n, *d_v = d_u + n;
+    char *d_org = base, *d_dir = base + b_ray;
+    double *d_t = (double *)(base + b_out), *d_u = d_t + n, *d_v = d_u + n;
     uint32_t *d_prim = (uint32_t *)(d_v + n);
     uint8_t *d_occ = (uint8_t *)(d_prim + n);
+    if (rec16) { d_prim = (uint32_t *)d_t; d_t = d_u = d_v = NULL; }
     HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
     HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
     if (a->stat_on) HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, a->stream));
     int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT,
-                    a->stat_on ? a->d_counters : NULL, a->stream, true);
+                    a->stat_on ? a->d_counters : NULL, a->stream, true, io_fmt);
     if (rc != 0) return rc;
     if (a->stat_on) {
         /* hits are counted from the device outputs whatever the caller asked to copy back */
-        std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_N] = {0, 0, 0, 0}, nh = 0;
+        std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV] = {0}, nh = 0;
         if (mode == LH_MODE_CLOSEST) {
-            hp.resize(n); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, a->stream));
+            hp.resize(w * n); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * w * n, hipMemcpyDeviceToHost, a->stream));
         } else {
             ho.resize(n); HIPCHK(hipMemcpyAsync(ho.data(), d_occ, n, hipMemcpyDeviceToHost, a->stream));
         }
         if (a->hs->bvh.ntris) HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost, a->stream));
         HIPCHK(hipStreamSynchronize(a->stream));
-        for (size_t i = 0; i < n; i++) nh += (mode == LH_MODE_CLOSEST) ? (hp[i] != LH_MISS_PRIM) : (ho[i] != 0);
+        for (size_t i = 0; i < n; i++) nh += (mode == LH_MODE_CLOSEST) ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
         a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT];
         a->stat[3] += n; a->stat[4] += nh;
+        a->last_retraced = h[LH_CNT_RETRACED];          /* a counted launch, as lh_accel_intersect_device_counted's */
     }
-    if (mode == LH_MODE_CLOSEST) {
+    if (rec16) HIPCHK(hipMemcpyAsync(prim, d_prim, 16 * n, hipMemcpyDeviceToHost, a->stream));
+    else if (mode == LH_MODE_CLOSEST) {
         if (prim) HIPCHK(hipMemcpyAsync(prim, d_prim, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, a->stream));
         if (t) HIPCHK(hipMemcpyAsync(t, d_t, b_d, hipMemcpyDeviceToHost, a->stream));
         if (u) HIPCHK(hipMemcpyAsync(u, d_u, b_d, hipMemcpyDeviceToHost, a->stream));
@@ -454,6 +470,55 @@ extern "C" int lh_accel_intersect_host(lh_accel_t *a, size_t n, const double *or
     }
     HIPCHK(hipStreamSynchronize(a->stream));
     return 0;
+}
+
+extern "C" int lh_accel_intersect_host(lh_accel_t *a, size_t n, const double *org, const double *dir,
+                                       uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode)
+{
+    lh_guard guard(a);
+    if (!a || !a->committed) return fail("intersect: accel not committed");
+    if (n == 0) return 0;
+    if (!org || !dir) return fail("intersect: NULL ray arrays");
+    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect: unknown mode %d", mode);
+    return intersect_host_fmt(a, n, org, dir, prim, t, u, v, occ, mode, 0u);
+}
+
+/* the formats of an _ex call -> LH_IO_* bits, or -1 (lh_last_error) for a combination the contract refuses (lucille_hip.h).  n == 0
+ * writes nothing: the record array is not looked at then (it may be NULL, as an empty tensor's pointer is) */
+static int ex_formats(const char *what, size_t n, int ray_format, int record_format, int mode, const void *rec, const void *t, const void *u, const void *v)
+{
+    if (ray_format != LH_RAYS_F64 && ray_format != LH_RAYS_F32) return fail("%s: unknown ray format %d", what, ray_format);
+    if (record_format != LH_REC_F64 && record_format != LH_REC16) return fail("%s: unknown record format %d", what, record_format);
+    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("%s: unknown mode %d", what, mode);
+    if (record_format == LH_REC16) {
+        if (mode == LH_MODE_ANY) return fail("%s: LH_REC16 is a closest-hit record format (any-hit writes occluded bytes)", what);
+        if (t || u || v) return fail("%s: LH_REC16 writes whole records to prim_or_rec16: t, u, v must be NULL", what);
+        if (n == 0) return 0;
+        if (!rec) return fail("%s: LH_REC16 needs the record array", what);
+        if (((uintptr_t)rec & 15u) != 0) return fail("%s: the LH_REC16 record array is not 16-byte aligned", what);
+    }
+    return (int)((ray_format == LH_RAYS_F32 ? LH_IO_RAYS_F32 : 0u) | (record_format == LH_REC16 ? LH_IO_REC16 : 0u));
+}
+
+extern "C" int lh_accel_intersect_host_ex(lh_accel_t *a, size_t n, const void *org, const void *dir, int ray_format, int record_format,
+                                          void *prim_or_rec16, double *t, double *u, double *v, uint8_t *occ, int mode)
+{
+    lh_guard guard(a);
+    const int io = ex_formats("lh_accel_intersect_host_ex", n, ray_format, record_format, mode, prim_or_rec16, t, u, v);
+    if (io < 0) return -1;
+    if (!a || !a->committed) return fail("intersect: accel not committed");
+    if (n == 0) return 0;
+    if (!org || !dir) return fail("intersect: NULL ray arrays");
+    return intersect_host_fmt(a, n, org, dir, (uint32_t *)prim_or_rec16, t, u, v, occ, mode, (uint32_t)io);
+}
+
+extern "C" int lh_accel_intersect_device_ex(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, int ray_format, int record_format,
+                                            void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occ, int mode, void *stream)
+{
+    lh_guard guard(a);
+    const int io = ex_formats("lh_accel_intersect_device_ex", n, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
+    if (io < 0) return -1;
+    return lh_launch(a, n, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, (hipStream_t)stream, true, (uint32_t)io);
 }
 
 extern "C" int lh_accel_trace_statistics(lh_accel_t *a, int enable)
