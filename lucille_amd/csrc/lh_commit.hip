@@ -172,6 +172,78 @@ int lh_ensure_buf(lh_buf *b, size_t bytes)
     return 0;
 }
 
+/* the scene's device arrays, a row each: the slot of the accelerator that owns the array, its size, and whether it is there
+ * -- as the image's header h says (a receiver, before it has allocated), else as the slot says.  The first LH_IMAGE_ROWS rows,
+ * in this order, are the scene image: a wire format between ranks (lh_dist.hip) */
+struct scene_row { void **slot; size_t bytes; bool present; };
+#define LH_SCENE_ROWS 15
+#define LH_IMAGE_ROWS 14          /* the 2-wide fp32 nodes (the textbook walk of a host-built scene) are never sent */
+static void scene_rows(lh_accel_t *a, const lh_scene_image_t *h, scene_row r[LH_SCENE_ROWS])
+{
+    const lh_bvh_t *b = &a->hs->bvh;
+    const size_t nt = b->ntris, rn = a->dev.ref_nnodes;
+    int n = 0;
+#define LH_ROW(SLOT, BYTES, IN_IMAGE) do { r[n].slot = &(SLOT); r[n].bytes = (BYTES); r[n].present = h ? (nt && (IN_IMAGE)) : (SLOT) != NULL; n++; } while (0)
+    LH_ROW(a->d_tri32, sizeof(lh_tri32_t) * nt + 64, true);          /* the unified walk reads 16 B past a record */
+    LH_ROW(a->d_tri64, sizeof(lh_tri64_t) * nt, true);
+    LH_ROW(a->d_q4nodes, sizeof(lh_q4node_t) * (size_t)b->nq4nodes, true);
+    LH_ROW(a->d_q8nodes, sizeof(lh_q8node_t) * (size_t)b->nq8nodes, h->nq8);
+    LH_ROW(a->d_ref_lca, sizeof(int) * 4 * rn, h->have_ref);
+    LH_ROW(a->d_prim_leafpos, sizeof(uint32_t) * 2 * nt, h->have_ref);
+    LH_ROW(a->d_ref_nodes, sizeof(lh_refnode_t) * rn, h->have_ref);
+    LH_ROW(a->d_ref_leaf_prims, sizeof(uint32_t) * nt, h->have_ref);
+    LH_ROW(a->d_nrm9, sizeof(double) * 9 * nt, h->has_nrm);
+    for (int k = 0; k < 3; k++) LH_ROW(a->d_attr9[k], sizeof(double) * 9 * nt, h->has_attr[k]);
+    LH_ROW(a->d_st6, sizeof(double) * 6 * nt, h->has_st);
+    LH_ROW(a->d_inside, nt, h->has_inside);
+    LH_ROW(a->d_nodes, sizeof(lh_node_t) * (size_t)b->nnodes, false);
+#undef LH_ROW
+}
+
+/* the resident scene of a->dev and the accelerator's byte count: the arrays from their owners, the rest from the host scene's
+ * header.  Every path that adds, replaces or frees an array ends here; nothing else writes these fields.  (The header of
+ * lucille's own tree is this replica's: publish_ref.) */
+static void publish_scene(lh_accel_t *a)
+{
+    const lh_bvh_t *b = &a->hs->bvh; lh_dev_scene_t *d = &a->dev;
+    d->nodes = a->d_nodes; d->tri32 = a->d_tri32; d->tri64 = a->d_tri64; d->q4nodes = a->d_q4nodes; d->q8nodes = a->d_q8nodes;
+    d->ref_lca = a->d_ref_lca; d->prim_leafpos = a->d_prim_leafpos; d->ref_nodes = a->d_ref_nodes; d->ref_leaf_prims = a->d_ref_leaf_prims;
+    d->ntris = b->ntris; d->nnodes = b->nnodes; d->max_depth = b->max_depth;
+    d->nq4nodes = b->nq4nodes; d->q4_depth = b->q4_depth; d->q4_stack = b->q4_stack;
+    d->nq8nodes = a->d_q8nodes ? b->nq8nodes : 0u; d->q8_depth = a->d_q8nodes ? b->q8_depth : 0u;       /* the host scene's may be another replica's */
+    d->scene_r = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        d->grid_lo[k] = b->grid_lo[k]; d->grid_step[k] = b->grid_step[k];
+        d->scene_r = fmaxf(d->scene_r, fmaxf(fabsf(b->bmin[k]), fabsf(b->bmax[k])));
+    }
+    d->deg_dcap = b->deg_dcap < 3.0e38 ? (float)b->deg_dcap : INFINITY;
+    d->cap_srcs = (d->deg_dcap < 3.0e38f ? 1u : 0u) | (d->deg_dcap < 1.0f ? 6u : 0u);
+    /* lh_accel_info's device_bytes.  A received scene counts the 64 bytes behind its triangle records, an uploaded or
+     * device-built one does not: kept as it was, the figure is compared across versions */
+    scene_row r[LH_SCENE_ROWS];
+    scene_rows(a, NULL, r);
+    a->device_bytes = 0;
+    for (int k = 0; k < LH_SCENE_ROWS; k++) if (r[k].present) a->device_bytes += r[k].bytes;
+    if (a->d_tri32 && !a->hs->received) a->device_bytes -= 64;
+}
+
+/* lucille's own tree is in a->d_ref_*: the header of this replica's copy (built here, the host scene's, or an image's) */
+static void publish_ref(lh_accel_t *a, uint32_t nnodes, int empty, const double bmin[3], const double bmax[3])
+{
+    a->dev.ref_nnodes = nnodes; a->dev.ref_empty = empty;
+    for (int k = 0; k < 3; k++) { a->dev.ref_bmin[k] = bmin[k]; a->dev.ref_bmax[k] = bmax[k]; }
+    publish_scene(a);
+}
+
+/* a host array becomes one of the scene's device arrays (pad: bytes allocated behind it) */
+static int upload_array(lh_accel_t *a, void **slot, const void *src, size_t bytes, size_t pad = 0)
+{
+    HIPCHK(hipMalloc(slot, bytes + pad));
+    HIPCHK(hipMemcpy(*slot, src, bytes, hipMemcpyHostToDevice));
+    publish_scene(a);
+    return 0;
+}
+
 static void release_device(lh_accel_t *a)
 {
     lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_slot, &a->r_hitrec,
@@ -179,28 +251,17 @@ static void release_device(lh_accel_t *a)
                       &a->p_org2, &a->p_dir2, &a->p_path, &a->p_path2, &a->p_thr, &a->p_thr2, &a->p_rad, &a->p_counts};
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); i++) free_buf(bufs[i]);
     if (a->d_total) (void)hipFree(a->d_total);
-    if (a->d_nrm9) (void)hipFree(a->d_nrm9);
-    for (int k = 0; k < 3; k++) { if (a->d_attr9[k]) (void)hipFree(a->d_attr9[k]); a->d_attr9[k] = NULL; }
-    if (a->d_st6) (void)hipFree(a->d_st6);
-    if (a->d_inside) (void)hipFree(a->d_inside);
+    scene_row rows[LH_SCENE_ROWS];
+    scene_rows(a, NULL, rows);
+    for (int k = 0; k < LH_SCENE_ROWS; k++) { if (*rows[k].slot) (void)hipFree(*rows[k].slot); *rows[k].slot = NULL; }
+    publish_scene(a);
     if (a->d_prim_mesh) (void)hipFree(a->d_prim_mesh);
     if (a->d_materials) (void)hipFree(a->d_materials);
     if (a->d_env_map) (void)hipFree(a->d_env_map);
-    a->d_st6 = a->d_inside = a->d_prim_mesh = a->d_materials = a->d_env_map = NULL;
+    a->d_prim_mesh = a->d_materials = a->d_env_map = NULL;
     free_buf(&a->r_state); free_buf(&a->r_uni); free_buf(&a->r_bands); free_buf(&a->r_diag);
     if (a->h_read) { (void)hipHostFree(a->h_read); a->h_read = NULL; }
-    a->d_total = NULL; a->d_nrm9 = NULL;
-    if (a->d_nodes) (void)hipFree(a->d_nodes);
-    if (a->d_tri32) (void)hipFree(a->d_tri32);
-    if (a->d_tri64) (void)hipFree(a->d_tri64);
-    if (a->d_q4nodes) (void)hipFree(a->d_q4nodes);
-    if (a->d_q8nodes) (void)hipFree(a->d_q8nodes);
-    a->d_q4nodes = a->d_q8nodes = NULL; a->dev.q4nodes = NULL; a->dev.q8nodes = NULL; a->dev.nodes = NULL;
-    if (a->d_ref_lca) (void)hipFree(a->d_ref_lca);
-    if (a->d_prim_leafpos) (void)hipFree(a->d_prim_leafpos);
-    if (a->d_ref_nodes) (void)hipFree(a->d_ref_nodes);
-    if (a->d_ref_leaf_prims) (void)hipFree(a->d_ref_leaf_prims);
-    a->d_ref_lca = a->d_prim_leafpos = a->d_ref_nodes = a->d_ref_leaf_prims = NULL;
+    a->d_total = NULL;
     if (a->d_danger) (void)hipFree(a->d_danger);
     a->d_danger = NULL; a->dev.ndanger = LH_DANGER_ALL;
     if (a->d_cursor) (void)hipFree(a->d_cursor);
@@ -224,7 +285,7 @@ static void release_device(lh_accel_t *a)
     }
     if (a->d_stage) (void)hipFree(a->d_stage);
     if (a->stream) (void)hipStreamDestroy(a->stream);
-    a->d_nodes = a->d_tri32 = a->d_tri64 = NULL; a->d_cursor = a->d_counters = NULL;
+    a->d_cursor = a->d_counters = NULL;
     a->d_stage = NULL; a->stage_bytes = 0; a->stream = NULL;
 }
 
@@ -427,7 +488,13 @@ static int device_rebuild_q8(lh_accel_t *a)
     if (q4) (void)hipFree(q4);
     if (t32) (void)hipFree(t32);
     if (rc != 0) { if (q8) (void)hipFree(q8); return -1; }
-    if (q8) { a->d_q8nodes = q8; a->dev.q8nodes = q8; a->dev.nq8nodes = nq8; a->dev.q8_depth = d8; a->device_bytes += sizeof(lh_q8node_t) * (size_t)nq8; }
+    if (q8) {
+        pthread_mutex_lock(&g_scene_mu);
+        hs->bvh.nq8nodes = nq8; hs->bvh.q8_depth = d8;
+        pthread_mutex_unlock(&g_scene_mu);
+        a->d_q8nodes = q8;
+        publish_scene(a);
+    }
     return 0;
 }
 
@@ -526,11 +593,7 @@ static int device_ref_tree(lh_accel_t *a)
         if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: lucille's own tree not built on the device (%s): host thread\n", rerr);
         return 1;
     }
-    a->dev.ref_lca = a->d_ref_lca; a->dev.prim_leafpos = a->d_prim_leafpos;
-    a->dev.ref_nodes = a->d_ref_nodes; a->dev.ref_leaf_prims = a->d_ref_leaf_prims;
-    a->dev.ref_nnodes = rn; a->dev.ref_empty = 0;
-    for (int k = 0; k < 3; k++) { a->dev.ref_bmin[k] = sc6[k]; a->dev.ref_bmax[k] = sc6[3 + k]; }
-    a->device_bytes += sizeof(int) * 4 * (size_t)rn + sizeof(uint32_t) * 3 * (size_t)hs->bvh.ntris + sizeof(lh_refnode_t) * (size_t)rn;
+    publish_ref(a, rn, 0, sc6, sc6 + 3);
     pthread_mutex_lock(&g_scene_mu);
     hs->ref_on_device = 1; hs->ref_build_seconds = now_s() - t0;
     pthread_mutex_unlock(&g_scene_mu);
@@ -547,24 +610,11 @@ int lh_ensure_formats(lh_accel_t *a, int mask)
         const int rc8 = lh_bvh_ensure_q8(&a->hs->bvh);
         pthread_mutex_unlock(&g_scene_mu);
         if (rc8 != 0) return fail("building the 8-wide tree failed (out of memory)");
-        const size_t q8b = sizeof(lh_q8node_t) * (size_t)b->nq8nodes;
-        HIPCHK(hipMalloc(&a->d_q8nodes, q8b));
-        HIPCHK(hipMemcpy(a->d_q8nodes, b->q8nodes, q8b, hipMemcpyHostToDevice));
-        a->dev.q8nodes = a->d_q8nodes; a->dev.nq8nodes = b->nq8nodes; a->dev.q8_depth = b->q8_depth; a->device_bytes += q8b;
+        if (upload_array(a, &a->d_q8nodes, b->q8nodes, sizeof(lh_q8node_t) * (size_t)b->nq8nodes) != 0) return -1;
     }
     if (a->hs->device_built) return 0;         /* the tree exists only as 4-wide nodes on the device */
-    if ((mask & LH_FMT_F32) && !a->d_nodes) {
-        const size_t nb = sizeof(lh_node_t) * (size_t)b->nnodes;
-        HIPCHK(hipMalloc(&a->d_nodes, nb));
-        HIPCHK(hipMemcpy(a->d_nodes, b->nodes, nb, hipMemcpyHostToDevice));
-        a->dev.nodes = a->d_nodes; a->device_bytes += nb;
-    }
-    if ((mask & LH_FMT_Q16X4) && !a->d_q4nodes) {
-        const size_t q4b = sizeof(lh_q4node_t) * (size_t)b->nq4nodes;
-        HIPCHK(hipMalloc(&a->d_q4nodes, q4b));
-        HIPCHK(hipMemcpy(a->d_q4nodes, b->q4nodes, q4b, hipMemcpyHostToDevice));
-        a->dev.q4nodes = a->d_q4nodes; a->device_bytes += q4b;
-    }
+    if ((mask & LH_FMT_F32) && !a->d_nodes && upload_array(a, &a->d_nodes, b->nodes, sizeof(lh_node_t) * (size_t)b->nnodes) != 0) return -1;
+    if ((mask & LH_FMT_Q16X4) && !a->d_q4nodes && upload_array(a, &a->d_q4nodes, b->q4nodes, sizeof(lh_q4node_t) * (size_t)b->nq4nodes) != 0) return -1;
     return 0;
 }
 
@@ -584,23 +634,12 @@ static int attach_ref(lh_accel_t *a)
             lca[4 * i + 2] = hs->ref.nodes[i].axis; lca[4 * i + 3] = hs->ref.nodes[i].child[0];
         }
         for (uint32_t p = 0; p < hs->bvh.ntris; p++) { lp[2 * p] = hs->ref.prim_leaf[p]; lp[2 * p + 1] = hs->ref.prim_pos[p]; }
-        hipError_t e1 = hipMalloc(&a->d_ref_lca, sizeof(int) * 4 * (size_t)rn);
-        hipError_t e2 = hipMalloc(&a->d_prim_leafpos, sizeof(uint32_t) * 2 * (size_t)hs->bvh.ntris);
-        hipError_t e3 = hipMalloc(&a->d_ref_nodes, sizeof(lh_refnode_t) * (size_t)rn);
-        hipError_t e4 = hipMalloc(&a->d_ref_leaf_prims, sizeof(uint32_t) * (size_t)hs->bvh.ntris);
-        if (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && e4 == hipSuccess) {
-            e1 = hipMemcpy(a->d_ref_lca, lca, sizeof(int) * 4 * (size_t)rn, hipMemcpyHostToDevice);
-            e2 = hipMemcpy(a->d_prim_leafpos, lp, sizeof(uint32_t) * 2 * (size_t)hs->bvh.ntris, hipMemcpyHostToDevice);
-            e3 = hipMemcpy(a->d_ref_nodes, hs->ref.nodes, sizeof(lh_refnode_t) * (size_t)rn, hipMemcpyHostToDevice);
-            e4 = hipMemcpy(a->d_ref_leaf_prims, hs->ref.leaf_prims, sizeof(uint32_t) * (size_t)hs->bvh.ntris, hipMemcpyHostToDevice);
-        }
+        const size_t nt = hs->bvh.ntris;
+        const bool ok = upload_array(a, &a->d_ref_lca, lca, sizeof(int) * 4 * (size_t)rn) == 0 && upload_array(a, &a->d_prim_leafpos, lp, sizeof(uint32_t) * 2 * nt) == 0 &&
+                        upload_array(a, &a->d_ref_nodes, hs->ref.nodes, sizeof(lh_refnode_t) * (size_t)rn) == 0 && upload_array(a, &a->d_ref_leaf_prims, hs->ref.leaf_prims, sizeof(uint32_t) * nt) == 0;
         free(lca); free(lp);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) return fail("reference-order tree upload failed");
-        a->dev.ref_lca = a->d_ref_lca; a->dev.prim_leafpos = a->d_prim_leafpos;
-        a->dev.ref_nodes = a->d_ref_nodes; a->dev.ref_leaf_prims = a->d_ref_leaf_prims;
-        a->dev.ref_nnodes = rn; a->dev.ref_empty = hs->ref.empty;
-        for (int k = 0; k < 3; k++) { a->dev.ref_bmin[k] = hs->ref.bmin[k]; a->dev.ref_bmax[k] = hs->ref.bmax[k]; }
-        a->device_bytes += sizeof(int) * 4 * (size_t)rn + sizeof(uint32_t) * 3 * (size_t)hs->bvh.ntris + sizeof(lh_refnode_t) * (size_t)rn;
+        if (!ok) return fail("reference-order tree upload failed");
+        publish_ref(a, rn, hs->ref.empty, hs->ref.bmin, hs->ref.bmax);
     }
     return lh_danger_scan(a);
 }
@@ -637,43 +676,33 @@ static int size_grid(lh_accel_t *a)
     return 0;
 }
 
-/* ---- device replica of the host scene (once per GPU) ---------------------------------------- */
-static int device_upload(lh_accel_t *a)
+/* what an accelerator launches with whatever its scene came from: its stream, the cursor blocks, the counters */
+static int device_begin(lh_accel_t *a)
 {
-    lh_host_scene *hs = a->hs;
     HIPCHK(hipSetDevice(a->device));
-    double t0 = now_s();
     HIPCHK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
     HIPCHK(hipMalloc((void **)&a->d_cursor, sizeof(uint32_t) * LH_CURSOR_WORDS * LH_NCURSOR));
     HIPCHK(hipMalloc((void **)&a->d_counters, sizeof(unsigned long long) * LH_CNT_DEV));
     HIPCHK(hipMalloc((void **)&a->d_total, sizeof(unsigned long long) * 72));      /* the hit count of a batch; then k_ao_resolve's 64 occlusion counters; [64]: the hit count kept for the fused AO stage and the batch's one read-back */
-    a->device_bytes = 0;
-    if (hs->nrm9) {
-        HIPCHK(hipMalloc(&a->d_nrm9, sizeof(double) * 9 * (size_t)hs->bvh.ntris));
-        HIPCHK(hipMemcpy(a->d_nrm9, hs->nrm9, sizeof(double) * 9 * (size_t)hs->bvh.ntris, hipMemcpyHostToDevice));
-        a->device_bytes += sizeof(double) * 9 * (size_t)hs->bvh.ntris;
-    }
-    for (int kind = 0; kind < 3; kind++) if (hs->attr9[kind]) {
-        const size_t b = sizeof(double) * 9 * (size_t)hs->bvh.ntris;
-        HIPCHK(hipMalloc(&a->d_attr9[kind], b));
-        HIPCHK(hipMemcpy(a->d_attr9[kind], hs->attr9[kind], b, hipMemcpyHostToDevice));
-        a->device_bytes += b;
-    }
-    if (hs->st6) {
-        const size_t b = sizeof(double) * 6 * (size_t)hs->bvh.ntris;
-        HIPCHK(hipMalloc(&a->d_st6, b)); HIPCHK(hipMemcpy(a->d_st6, hs->st6, b, hipMemcpyHostToDevice));
-        a->device_bytes += b;
-    }
-    if (hs->inside) {
-        HIPCHK(hipMalloc(&a->d_inside, hs->bvh.ntris)); HIPCHK(hipMemcpy(a->d_inside, hs->inside, hs->bvh.ntris, hipMemcpyHostToDevice));
-        a->device_bytes += hs->bvh.ntris;
-    }
+    return 0;
+}
+
+/* ---- device replica of the host scene (once per GPU) ---------------------------------------- */
+static int device_upload(lh_accel_t *a)
+{
+    lh_host_scene *hs = a->hs;
+    const double t0 = now_s();
+    if (device_begin(a) != 0) return -1;
+    const size_t nt = hs->bvh.ntris;
+    if (hs->nrm9 && upload_array(a, &a->d_nrm9, hs->nrm9, sizeof(double) * 9 * nt) != 0) return -1;
+    for (int kind = 0; kind < 3; kind++)
+        if (hs->attr9[kind] && upload_array(a, &a->d_attr9[kind], hs->attr9[kind], sizeof(double) * 9 * nt) != 0) return -1;
+    if (hs->st6 && upload_array(a, &a->d_st6, hs->st6, sizeof(double) * 6 * nt) != 0) return -1;
+    if (hs->inside && upload_array(a, &a->d_inside, hs->inside, nt) != 0) return -1;
     if (hs->bvh.ntris) {
-        size_t t32 = sizeof(lh_tri32_t) * (size_t)hs->bvh.ntris;
-        size_t t64 = sizeof(lh_tri64_t) * (size_t)hs->bvh.ntris;
+        const size_t t64 = sizeof(lh_tri64_t) * nt;
         const double tu = now_s();
-        HIPCHK(hipMalloc(&a->d_tri64, t64));
-        HIPCHK(hipMemcpy(a->d_tri64, hs->bvh.tri64, t64, hipMemcpyHostToDevice));
+        if (upload_array(a, &a->d_tri64, hs->bvh.tri64, t64) != 0) return -1;
         if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 upload (%.0f MB)      %8.2f ms\n", t64 / 1e6, (now_s() - tu) * 1e3);
         if (hs->device_built) {
             /* the traversal tree is built here, on this device (lh_build.hip): LBVH -> the same 4-wide nodes */
@@ -696,28 +725,14 @@ static int device_upload(lh_accel_t *a)
             pthread_mutex_lock(&g_scene_mu);
             hs->bvh.nq4nodes = nq4; hs->bvh.q4_depth = d4; hs->bvh.q4_stack = st4; hs->bvh.nnodes = nq4; hs->bvh.max_depth = d4; hs->bvh.build_seconds = now_s() - tb;
             hs->bvh.nlive = nlive; hs->bvh.deg_dcap = dcap;
+            if (a->d_q8nodes) { hs->bvh.nq8nodes = nq8; hs->bvh.q8_depth = d8; }
             for (int k = 0; k < 3; k++) { hs->bvh.bmin[k] = bmin[k]; hs->bvh.bmax[k] = bmax[k]; hs->bvh.grid_lo[k] = glo[k]; hs->bvh.grid_step[k] = gst[k]; }
             pthread_mutex_unlock(&g_scene_mu);
-            a->dev.q4nodes = a->d_q4nodes;
-            a->device_bytes += sizeof(lh_q4node_t) * (size_t)nq4;
-            if (a->d_q8nodes) { a->dev.q8nodes = a->d_q8nodes; a->dev.nq8nodes = nq8; a->dev.q8_depth = d8; a->device_bytes += sizeof(lh_q8node_t) * (size_t)nq8; }
+            publish_scene(a);
             if (3 * d4 + 5 > 264) return -3;          /* deeper than k_overflow_fix's private stack: the caller falls back to the host builder */
             if (hs->have_ref && (hs->ref_on_device || hs->ref_state == 1) && device_ref_tree(a) < 0) return -1;
-        } else {
-            HIPCHK(hipMalloc(&a->d_tri32, t32 + 64));   /* the unified walk reads 16 B past a record */
-            HIPCHK(hipMemcpy(a->d_tri32, hs->bvh.tri32, t32, hipMemcpyHostToDevice));
-        }
-        a->device_bytes += t32 + t64;
-        float r = 0.0f;
-        for (int k = 0; k < 3; k++) { r = fmaxf(r, fabsf(hs->bvh.bmin[k])); r = fmaxf(r, fabsf(hs->bvh.bmax[k])); }
-        a->dev.tri32 = a->d_tri32; a->dev.tri64 = a->d_tri64;
-        a->dev.ntris = hs->bvh.ntris; a->dev.nnodes = hs->bvh.nnodes;
-        a->dev.max_depth = hs->bvh.max_depth; a->dev.scene_r = r; a->dev.ray_chunk = a->ray_chunk;
-        a->dev.deg_dcap = hs->bvh.deg_dcap < 3.0e38 ? (float)hs->bvh.deg_dcap : INFINITY;
-        a->dev.cap_srcs = (a->dev.deg_dcap < 3.0e38f ? 1u : 0u) | (a->dev.deg_dcap < 1.0f ? 6u : 0u);
-        for (int k = 0; k < 3; k++) { a->dev.grid_lo[k] = hs->bvh.grid_lo[k]; a->dev.grid_step[k] = hs->bvh.grid_step[k]; }
+        } else if (upload_array(a, &a->d_tri32, hs->bvh.tri32, sizeof(lh_tri32_t) * nt, 64) != 0) return -1;
         if (hs->have_ref && __atomic_load_n(&hs->ref_state, __ATOMIC_ACQUIRE) == 2 && attach_ref(a) != 0) return -1;
-        a->dev.nq4nodes = hs->bvh.nq4nodes; a->dev.q4_depth = hs->bvh.q4_depth; a->dev.q4_stack = hs->bvh.q4_stack;
         /* resident from the start: what the default kernel reads (everything else on first use) */
         if (lh_ensure_formats(a, LH_FMT_Q16X4) != 0) return -1;
     }
@@ -981,22 +996,9 @@ int lh_scene_image_header(lh_accel_t *a, lh_scene_image_t *h)
 int lh_scene_image_arrays(lh_accel_t *a, const lh_scene_image_t *h, void **ptr, size_t *bytes, int cap)
 {
     int n = 0;
-    const size_t nt = h->ntris;
-#define LH_IMG(P, B) do { if (n < cap) { ptr[n] = (P); bytes[n] = (B); } n++; } while (0)
-    if (nt) {
-        LH_IMG(a->d_tri32, sizeof(lh_tri32_t) * nt + 64); LH_IMG(a->d_tri64, sizeof(lh_tri64_t) * nt);
-        LH_IMG(a->d_q4nodes, sizeof(lh_q4node_t) * (size_t)h->nq4);
-        if (h->nq8) LH_IMG(a->d_q8nodes, sizeof(lh_q8node_t) * (size_t)h->nq8);
-        if (h->have_ref) {
-            LH_IMG(a->d_ref_lca, sizeof(int) * 4 * (size_t)h->ref_nnodes); LH_IMG(a->d_prim_leafpos, sizeof(uint32_t) * 2 * nt);
-            LH_IMG(a->d_ref_nodes, sizeof(lh_refnode_t) * (size_t)h->ref_nnodes); LH_IMG(a->d_ref_leaf_prims, sizeof(uint32_t) * nt);
-        }
-        if (h->has_nrm) LH_IMG(a->d_nrm9, sizeof(double) * 9 * nt);
-        for (int k = 0; k < 3; k++) if (h->has_attr[k]) LH_IMG(a->d_attr9[k], sizeof(double) * 9 * nt);
-        if (h->has_st) LH_IMG(a->d_st6, sizeof(double) * 6 * nt);
-        if (h->has_inside) LH_IMG(a->d_inside, nt);
-    }
-#undef LH_IMG
+    scene_row r[LH_SCENE_ROWS];
+    scene_rows(a, h, r);
+    for (int k = 0; k < LH_IMAGE_ROWS; k++) if (r[k].present) { if (n < cap) { ptr[n] = *r[k].slot; bytes[n] = r[k].bytes; } n++; }
     return n;
 }
 
@@ -1012,53 +1014,23 @@ int lh_scene_image_alloc(lh_accel_t *a, const lh_scene_image_t *h)
     lh_guard guard(a);
     lh_host_scene *hs = a->hs;
     a->commit_failed = 1;
-    HIPCHK(hipSetDevice(a->device));
-    HIPCHK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc((void **)&a->d_cursor, sizeof(uint32_t) * LH_CURSOR_WORDS * LH_NCURSOR));
-    HIPCHK(hipMalloc((void **)&a->d_counters, sizeof(unsigned long long) * LH_CNT_DEV));
-    HIPCHK(hipMalloc((void **)&a->d_total, sizeof(unsigned long long) * 72));      /* the hit count of a batch; then k_ao_resolve's 64 occlusion counters; [64]: the hit count kept for the fused AO stage and the batch's one read-back */
+    if (device_begin(a) != 0) return -1;
     hs->received = 1; hs->device_built = 1;              /* no host tree: the walks over other node formats are not available */
     hs->bvh.ntris = h->ntris; hs->bvh.nnodes = h->nnodes; hs->bvh.max_depth = h->max_depth; hs->bvh.nleaves = h->nleaves;
     hs->bvh.nq4nodes = h->nq4; hs->bvh.q4_depth = h->q4_depth; hs->bvh.q4_stack = h->q4_stack; hs->nmeshes = h->nmeshes;
+    hs->bvh.nq8nodes = h->nq8; hs->bvh.q8_depth = h->q8_depth;
     hs->bvh.build_seconds = h->build_seconds; hs->ref_build_seconds = h->ref_build_seconds;
     hs->bvh.nlive = h->nlive; hs->bvh.deg_dcap = h->deg_dcap;
-    a->dev.deg_dcap = h->deg_dcap < 3.0e38 ? (float)h->deg_dcap : INFINITY;
-    a->dev.cap_srcs = (a->dev.deg_dcap < 3.0e38f ? 1u : 0u) | (a->dev.deg_dcap < 1.0f ? 6u : 0u);
     hs->have_ref = h->have_ref; hs->ref_state = h->have_ref ? 2 : 0;
-    float r = 0.0f;
-    for (int k = 0; k < 3; k++) {
-        hs->bvh.bmin[k] = h->bmin[k]; hs->bvh.bmax[k] = h->bmax[k]; hs->bvh.grid_lo[k] = h->grid_lo[k]; hs->bvh.grid_step[k] = h->grid_step[k];
-        a->dev.grid_lo[k] = h->grid_lo[k]; a->dev.grid_step[k] = h->grid_step[k];
-        a->dev.ref_bmin[k] = h->ref_bmin[k]; a->dev.ref_bmax[k] = h->ref_bmax[k];
-        r = fmaxf(r, fabsf(h->bmin[k])); r = fmaxf(r, fabsf(h->bmax[k]));
-    }
-    const size_t nt = h->ntris;
-    a->device_bytes = 0;
-    if (nt) {
-        hs->bvh.prim_geom = (uint32_t *)malloc(sizeof(uint32_t) * nt); hs->bvh.prim_index = (uint32_t *)malloc(sizeof(uint32_t) * nt);
+    for (int k = 0; k < 3; k++) { hs->bvh.bmin[k] = h->bmin[k]; hs->bvh.bmax[k] = h->bmax[k]; hs->bvh.grid_lo[k] = h->grid_lo[k]; hs->bvh.grid_step[k] = h->grid_step[k]; }
+    publish_ref(a, h->ref_nnodes, h->ref_empty, h->ref_bmin, h->ref_bmax);          /* the box of a tree that is no longer on any host: lh_danger_scan reads it */
+    if (h->ntris) {
+        hs->bvh.prim_geom = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)h->ntris); hs->bvh.prim_index = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)h->ntris);
         if (!hs->bvh.prim_geom || !hs->bvh.prim_index) return fail("out of memory");
-        HIPCHK(hipMalloc(&a->d_tri32, sizeof(lh_tri32_t) * nt + 64)); HIPCHK(hipMalloc(&a->d_tri64, sizeof(lh_tri64_t) * nt));
-        HIPCHK(hipMalloc(&a->d_q4nodes, sizeof(lh_q4node_t) * (size_t)h->nq4));
-        if (h->nq8) HIPCHK(hipMalloc(&a->d_q8nodes, sizeof(lh_q8node_t) * (size_t)h->nq8));
-        if (h->have_ref) {
-            HIPCHK(hipMalloc(&a->d_ref_lca, sizeof(int) * 4 * (size_t)h->ref_nnodes)); HIPCHK(hipMalloc(&a->d_prim_leafpos, sizeof(uint32_t) * 2 * nt));
-            HIPCHK(hipMalloc(&a->d_ref_nodes, sizeof(lh_refnode_t) * (size_t)h->ref_nnodes)); HIPCHK(hipMalloc(&a->d_ref_leaf_prims, sizeof(uint32_t) * nt));
-        }
-        if (h->has_nrm) HIPCHK(hipMalloc(&a->d_nrm9, sizeof(double) * 9 * nt));
-        for (int k = 0; k < 3; k++) if (h->has_attr[k]) HIPCHK(hipMalloc(&a->d_attr9[k], sizeof(double) * 9 * nt));
-        if (h->has_st) HIPCHK(hipMalloc(&a->d_st6, sizeof(double) * 6 * nt));
-        if (h->has_inside) HIPCHK(hipMalloc(&a->d_inside, nt));
-        a->dev.tri32 = a->d_tri32; a->dev.tri64 = a->d_tri64; a->dev.q4nodes = a->d_q4nodes;
-        a->dev.q8nodes = a->d_q8nodes; a->dev.nq8nodes = h->nq8; a->dev.q8_depth = h->q8_depth;
-        a->dev.ntris = h->ntris; a->dev.nnodes = h->nnodes; a->dev.max_depth = h->max_depth; a->dev.scene_r = r; a->dev.ray_chunk = a->ray_chunk;
-        a->dev.nq4nodes = h->nq4; a->dev.q4_depth = h->q4_depth; a->dev.q4_stack = h->q4_stack;
-        if (h->have_ref) {
-            a->dev.ref_lca = a->d_ref_lca; a->dev.prim_leafpos = a->d_prim_leafpos; a->dev.ref_nodes = a->d_ref_nodes;
-            a->dev.ref_leaf_prims = a->d_ref_leaf_prims; a->dev.ref_nnodes = h->ref_nnodes; a->dev.ref_empty = h->ref_empty;
-        }
-        void *ptr[32]; size_t bytes[32];
-        const int n = lh_scene_image_arrays(a, h, ptr, bytes, 32);
-        for (int k = 0; k < n; k++) a->device_bytes += bytes[k];
+        scene_row r[LH_SCENE_ROWS];
+        scene_rows(a, h, r);
+        for (int k = 0; k < LH_SCENE_ROWS; k++) if (r[k].present) HIPCHK(hipMalloc(r[k].slot, r[k].bytes));
+        publish_scene(a);
     }
     return 0;
 }
@@ -1075,8 +1047,6 @@ int lh_scene_image_finish(lh_accel_t *a)
     return 0;
 }
 
-
-/* fill miss results without touching the scene (empty accel) */
 extern "C" int lh_accel_add_rib_scene(lh_accel_t *a, const lh_rib_scene_t *scene)
 {
     lh_guard guard(a);

@@ -70,11 +70,12 @@ struct lh_accel {
     /* staged meshes (host copies, packed xyz) */
     lh_mesh_copy *meshes; uint32_t nmeshes;
     lh_host_scene *hs;        /* never NULL after create */
-    void *d_ref_lca, *d_prim_leafpos, *d_ref_nodes, *d_ref_leaf_prims;
+    void *d_ref_lca, *d_prim_leafpos, *d_ref_nodes, *d_ref_leaf_prims;   /* lucille's own tree: owned here, published in dev (lh_commit.hip publish_scene) */
     void *d_danger;                    /* 8 + LH_DANGER_MAX x 6 doubles: the count, then the boxes of lh_dev_scene_t.danger (lh_commit.hip lh_danger_scan) */
     /* device */
-    lh_dev_scene_t dev;
-    void *d_nodes, *d_tri32, *d_tri64, *d_q4nodes, *d_q8nodes;
+    lh_dev_scene_t dev;                /* what the kernels get: the resident scene (written by lh_commit.hip publish_scene only) and the knobs of
+                                          create / set_param; its per-launch fields stay zero here -- a launch sets them in a copy (lh_launch) */
+    void *d_nodes, *d_tri32, *d_tri64, *d_q4nodes, *d_q8nodes;   /* the owners of the scene's arrays (lh_commit.hip scene_rows) */
     int ncus;                          /* compute units of the device */
     int wide8;                         /* ray dumps walk the 8-wide nodes: -1 when the hot set exceeds the Infinity Cache (default), 0 never, 1 always */
     unsigned long long *d_cursor, *d_counters;   /* d_cursor: LH_NCURSOR blocks of LH_CURSOR_WORDS words (a line per cursor + the drained mask), one block per launch in flight */
@@ -183,9 +184,19 @@ int  lh_scene_image_finish(lh_accel_t *a);
 extern "C" int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], uint32_t *prim, double *t, double *u, double *v);
 /* lh_query.hip */
 void lh_comb_destroy(lh_accel_t *a);                 /* the single-ray combiner's pinned block and stream (lh_accel_destroy) */
+/* one batch of rays through the hot path, from a copy of a->dev that carries the launch's own inputs: d_counters (LH_CNT_DEV
+ * statistics counters or NULL), dump (a ray dump: incoherent rays, dump_budget, the 8-wide nodes where they pay; else a tile
+ * pipeline's batch: ray_budget, LH_TILE_CHUNK) and, in lh_launch_opt, what only some callers have */
+struct lh_launch_opt {
+    uint32_t io_fmt = 0u;                      /* LH_IO_* (lh_device.h): ray dumps in fp32 rays / 16-byte records */
+    uint32_t *diag_out = NULL;                 /* four counts per ray (lh_accel_intersect_diag_*) */
+    const uint32_t *n_dev = NULL;              /* the ray count lives on the device, n is its upper bound (the path tracer's bounce chain) */
+    const void *cam_src = NULL;                /* the rays are the camera rays of a path-traced pass: d_org / d_dir may be NULL */
+    unsigned long long *diag_clock = NULL;     /* LH_STAGE_TIMING: start / exit clocks of the launch's waves */
+};
 int  lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim, void *d_t, void *d_u, void *d_v,
                void *d_occ, int mode, int variant, unsigned long long *d_counters, hipStream_t s, bool dump,
-               uint32_t io_fmt = 0u);       /* io_fmt: LH_IO_* (lh_device.h) -- ray dumps in fp32 rays / 16-byte records */
+               const lh_launch_opt &opt = lh_launch_opt());
 int  lh_aoq_slot(lh_accel_t *a, hipStream_t s);
 int  lh_ensure_stage(lh_accel_t *a, size_t bytes);
 

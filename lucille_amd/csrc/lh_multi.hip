@@ -34,8 +34,8 @@
 
 #include "../../include/lucille_hip.h"
 
-extern "C" int lh_accel_commit_replica(lh_accel_t *dst, lh_accel_t *src);      /* lh_api.hip */
-extern "C" void lh_set_error(const char *msg);                                   /* lh_api.hip: lh_last_error of this thread */
+extern "C" int lh_accel_commit_replica(lh_accel_t *dst, lh_accel_t *src);      /* lh_commit.hip */
+extern "C" void lh_set_error(const char *msg);                                   /* lh_commit.hip: lh_last_error of this thread */
 
 struct lh_multi {
     int n;

@@ -90,14 +90,20 @@ static bool q8_available(const lh_accel_t *a)
     return !a->hs->received && a->hs->bvh.nq4nodes > 1;
 }
 
+/* ray dumps of this variant walk the 8-wide nodes on this scene: "wide8" forced, or left to the size of the hot set */
+static bool dump_walks_q8(const lh_accel_t *a, int variant)
+{
+    return variant == LH_VARIANT_SPEC && q8_available(a) && (a->wide8 == 1 || (a->wide8 == -1 && wide8_pays(a)));
+}
+
 int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim,
               void *d_t, void *d_u, void *d_v, void *d_occ, int mode, int variant,
-              unsigned long long *d_counters, hipStream_t s, bool dump, uint32_t io_fmt)
+              unsigned long long *d_counters, hipStream_t s, bool dump, const lh_launch_opt &opt)
 {
     if (!a || !a->committed) return fail("intersect: accel not committed");
     if (n == 0) return 0;
-    if ((!d_org || !d_dir) && !a->dev.cam_src) return fail("intersect: NULL ray arrays");
-    const bool rec16 = mode == LH_MODE_CLOSEST && (io_fmt & LH_IO_REC16);
+    if ((!d_org || !d_dir) && !opt.cam_src) return fail("intersect: NULL ray arrays");
+    const bool rec16 = mode == LH_MODE_CLOSEST && (opt.io_fmt & LH_IO_REC16);
     if (rec16 && (!d_prim || d_t || d_u || d_v)) return fail("intersect: 16-byte records go to one array (t, u, v must be NULL)");
     if (mode == LH_MODE_CLOSEST && !rec16 && (!d_prim || !d_t || !d_u || !d_v)) return fail("intersect: closest mode needs prim,t,u,v outputs");
     if (mode == LH_MODE_ANY && !d_occ) return fail("intersect: any mode needs the occluded output");
@@ -132,31 +138,29 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
     /* ray dumps (incoherent by assumption) over a scene whose hot set does not fit the 256 MiB Infinity Cache walk the 8-wide
      * nodes: each record then costs a 128-byte line of HBM traffic whatever its size, and an 8-wide record uses all of it
      * (S-soup-10M: 57 -> 40 records per ray).  The tile pipelines' coherent rays stay on the 4-wide nodes. */
-    a->dev.prefer_q8 = 0;
-    if (dump && variant == LH_VARIANT_SPEC && q8_available(a) && (a->wide8 == 1 || (a->wide8 == -1 && wide8_pays(a)))) {
-        if (lh_ensure_formats(a, LH_FMT_Q8) != 0) return -1;
-        a->dev.prefer_q8 = 1;
-    }
+    const bool q8 = dump && dump_walks_q8(a, variant);
+    if (q8 && lh_ensure_formats(a, LH_FMT_Q8) != 0) return -1;
+    const int qk = lh_aoq_slot(a, s);             /* the stream's fix-up queue (rays out of visit budget -> the cooperative walk) */
+    if (qk < 0) return -1;
+    /* the launch's own scene: the resident one and what this launch alone is run with */
+    lh_dev_scene_t sc = a->dev;
+    sc.prefer_q8 = q8;
     /* ray dumps are incoherent by assumption: a wave's iterations serve 64 unrelated rays, a ray's age in iterations runs to
      * several times its own steps -- the tile pipelines' budget (128) would send half the batch to the cooperative walk */
-    const uint32_t budget_keep = a->dev.ray_budget, chunk_keep = a->dev.ray_chunk;
-    if (dump) a->dev.ray_budget = a->dump_budget;
-    else if (a->dev.ray_chunk < LH_TILE_CHUNK) a->dev.ray_chunk = LH_TILE_CHUNK;       /* the tile pipelines' batches are coherent in batch order */
-    const uint32_t cap_keep = a->dev.stack_cap; const int grid = a->grid_blocks;
-    const int qk = lh_aoq_slot(a, s);             /* the stream's fix-up queue (rays out of visit budget -> the cooperative walk) */
-    if (qk < 0) { a->dev.ray_budget = budget_keep; a->dev.ray_chunk = chunk_keep; a->dev.stack_cap = cap_keep; return -1; }
+    if (dump) sc.ray_budget = a->dump_budget;
+    else if (sc.ray_chunk < LH_TILE_CHUNK) sc.ray_chunk = LH_TILE_CHUNK;       /* the tile pipelines' batches are coherent in batch order */
+    sc.io_fmt = opt.io_fmt & (mode == LH_MODE_ANY ? LH_IO_RAYS_F32 : (LH_IO_RAYS_F32 | LH_IO_REC16));
+    sc.diag_out = opt.diag_out; sc.n_dev = opt.n_dev; sc.cam_src = opt.cam_src; sc.diag_clock = opt.diag_clock;
     /* a ray dump over the 4-wide nodes regroups a little later and passes over parked leaves a little sooner than the tile
      * pipelines' coherent batches want (tools/experiments/knob_sweep3.py / knob_sweep4.py, r05: S-soup-1M 2 233 -> 2 266 Mrays/s
      * closest hit, 2 735 -> 2 772 any hit; the 8-wide walk and the AO stage are best where they are) */
-    const bool dump4 = dump && !a->dev.prefer_q8 && !a->knobs_user;
-    const bool dump8 = dump && a->dev.prefer_q8 && !a->knobs_user;
-    a->dev.io_fmt = io_fmt & (mode == LH_MODE_ANY ? LH_IO_RAYS_F32 : (LH_IO_RAYS_F32 | LH_IO_REC16));
-    int rc = lh_launch_trace(&a->dev, n, (const double *)d_org, (const double *)d_dir, (uint32_t *)d_prim,
+    const bool dump4 = dump && !q8 && !a->knobs_user;
+    const bool dump8 = dump && q8 && !a->knobs_user;
+    int rc = lh_launch_trace(&sc, n, (const double *)d_org, (const double *)d_dir, (uint32_t *)d_prim,
                              (double *)d_t, (double *)d_u, (double *)d_v, mode == LH_MODE_ANY,
-                             (uint8_t *)d_occ, d_counters, (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR)), variant, grid,
+                             (uint8_t *)d_occ, d_counters, (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR)), variant, a->grid_blocks,
                              dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch,
                              &a->aoq[qk].q, a->ncus, (void *)s);
-    a->dev.ray_budget = budget_keep; a->dev.ray_chunk = chunk_keep; a->dev.stack_cap = cap_keep; a->dev.io_fmt = 0u;
     if (rc != 0) return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
@@ -201,9 +205,7 @@ extern "C" int lh_accel_intersect_device_counted(lh_accel_t *a, size_t n, const 
 extern "C" int lh_accel_dump_node_bytes(const lh_accel_t *a)
 {
     if (!a || !a->committed || a->hs->bvh.ntris == 0) return 0;
-    if (a->default_variant == LH_VARIANT_SPEC && q8_available(a) &&
-        (a->wide8 == 1 || (a->wide8 == -1 && wide8_pays(a)))) return (int)sizeof(lh_q8node_t);
-    return 64;
+    return dump_walks_q8(a, a->default_variant) ? (int)sizeof(lh_q8node_t) : 64;
 }
 
 extern "C" uint64_t lh_accel_last_retraced(const lh_accel_t *a) { return a ? a->last_retraced : 0; }
@@ -394,8 +396,8 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const void *org, co
         HIPCHK(hipEventRecord(a->pipe.in_done[b], s_in));
         HIPCHK(hipStreamWaitEvent(s_tr, a->pipe.in_done[b], 0));
         double *d_t = (double *)dout, *d_u = d_t + CAP, *d_v = d_u + CAP; uint32_t *d_prim = (uint32_t *)(d_v + CAP);
-        const int rc = rec16 ? lh_launch(a, m, di, di + RB * CAP, dout, NULL, NULL, NULL, NULL, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, io_fmt)
-                             : lh_launch(a, m, di, di + RB * CAP, d_prim, d_t, d_u, d_v, (uint8_t *)dout, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, io_fmt);
+        const int rc = rec16 ? lh_launch(a, m, di, di + RB * CAP, dout, NULL, NULL, NULL, NULL, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, lh_launch_opt{io_fmt})
+                             : lh_launch(a, m, di, di + RB * CAP, d_prim, d_t, d_u, d_v, (uint8_t *)dout, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, lh_launch_opt{io_fmt});
         if (rc != 0) return rc;
         char *ho = (char *)a->pipe.h_out[b];
         if (rec16) HIPCHK(hipMemcpyAsync(ho, dout, 16 * m, hipMemcpyDeviceToHost, s_tr));
@@ -442,7 +444,7 @@ static int intersect_host_fmt(lh_accel_t *a, size_t n, const void *org, const vo
     HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
     if (a->stat_on) HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, a->stream));
     int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT,
-                    a->stat_on ? a->d_counters : NULL, a->stream, true, io_fmt);
+                    a->stat_on ? a->d_counters : NULL, a->stream, true, lh_launch_opt{io_fmt});
     if (rc != 0) return rc;
     if (a->stat_on) {
         /* hits are counted from the device outputs whatever the caller asked to copy back */
@@ -518,7 +520,7 @@ extern "C" int lh_accel_intersect_device_ex(lh_accel_t *a, size_t n, const void 
     lh_guard guard(a);
     const int io = ex_formats("lh_accel_intersect_device_ex", n, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
     if (io < 0) return -1;
-    return lh_launch(a, n, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, (hipStream_t)stream, true, (uint32_t)io);
+    return lh_launch(a, n, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, (hipStream_t)stream, true, lh_launch_opt{(uint32_t)io});
 }
 
 extern "C" int lh_accel_trace_statistics(lh_accel_t *a, int enable)
@@ -784,9 +786,8 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
     HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
     HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
     if (a->stat_on) HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, a->stream));
-    a->dev.diag_out = d_diag;
-    const int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, NULL, LH_MODE_CLOSEST, LH_VARIANT_SPEC, a->stat_on ? a->d_counters : NULL, a->stream, true);
-    a->dev.diag_out = NULL;
+    lh_launch_opt opt; opt.diag_out = d_diag;
+    const int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, NULL, LH_MODE_CLOSEST, LH_VARIANT_SPEC, a->stat_on ? a->d_counters : NULL, a->stream, true, opt);
     if (rc != 0) return rc;
     HIPCHK(hipMemcpyAsync(diag, d_diag, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, a->stream));
     std::vector<uint32_t> hp;
@@ -823,10 +824,8 @@ extern "C" int lh_accel_intersect_diag_device(lh_accel_t *a, size_t n, const voi
     if (lh_ensure_stage(a, 3 * b_d + sizeof(uint32_t) * n + n + 64) != 0) return -1;
     double *d_t = (double *)a->d_stage, *d_u = d_t + n, *d_v = d_u + n;
     uint32_t *d_prim = (uint32_t *)(d_v + n); uint8_t *d_occ = (uint8_t *)(d_prim + n);
-    a->dev.diag_out = (uint32_t *)d_diag;
-    const int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_SPEC, NULL, s, true);
-    a->dev.diag_out = NULL;
-    return rc;
+    lh_launch_opt opt; opt.diag_out = (uint32_t *)d_diag;
+    return lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_SPEC, NULL, s, true, opt);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -72,7 +72,7 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     /* ... and the wall clock at which every persistent wave starts and leaves (two launches: closest, AO) */
     const size_t nwaves = (size_t)a->grid_blocks * (LH_BLOCK / 64);
     if (stage_timing) { if (ensure_buf(&a->r_diag, sizeof(unsigned long long) * 6 * nwaves)) return -1; HIPCHK(hipMemsetAsync(a->r_diag.p, 0, sizeof(unsigned long long) * 6 * nwaves, s)); }
-    a->dev.diag_clock = stage_timing ? (unsigned long long *)a->r_diag.p : NULL;
+    lh_launch_opt opt; opt.diag_clock = stage_timing ? (unsigned long long *)a->r_diag.p : NULL;
     /* 1. camera rays */
     if (lh_render_launch_primary_region(cam, x0, w, nbands, band_rows, d_band_y0, y0, cam->height, ps, ps,
                                         (double *)a->r_org.p, (double *)a->r_dir.p, s) != 0)
@@ -80,8 +80,8 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     if (stage_timing) HIPCHK(hipEventRecord(ev[1], s));
     /* 2. closest hit */
     if (lh_launch(a, S, a->r_org.p, a->r_dir.p, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, LH_MODE_CLOSEST,
-               LH_VARIANT_DEFAULT, cnt, s, false) != 0) return -1;
-    if (stage_timing) { HIPCHK(hipEventRecord(ev[2], s)); a->dev.diag_clock = (unsigned long long *)a->r_diag.p + 3 * nwaves; }
+               LH_VARIANT_DEFAULT, cnt, s, false, opt) != 0) return -1;
+    if (stage_timing) { HIPCHK(hipEventRecord(ev[2], s)); opt.diag_clock = (unsigned long long *)a->r_diag.p + 3 * nwaves; }
     /* 3. compaction (deterministic: hits in sample order).  The fused AO stage does not need the total on the host: its buffers are
      * sized for the worst case (every sample hits) and its kernels read the count where the compaction left it -- a batch costs ONE
      * host round trip, at its end (round 5: the two in the middle were ~0.25 ms of a rank's 8.9 ms share of the config-5 frame).
@@ -126,17 +126,17 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         if (ensure_buf(&a->r_occcount, nslots * sizeof(unsigned int))) return -1;
         qslot = lh_aoq_slot(a, s);
         if (qslot < 0) return -1;
-        const uint32_t budget_keep = a->dev.ray_budget;
-        if (a->ao_budget) a->dev.ray_budget = a->ao_budget;
+        lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget, its clocks */
+        sc.diag_clock = opt.diag_clock;
+        if (a->ao_budget) sc.ray_budget = a->ao_budget;
         /* the tail a budget costs a launch is fixed, the queue a low budget sends to the sweep grows with the launch: a launch of
          * 2^27 rays or more doubles the default (config 5: whole frame 57.6 -> 56.7 ms, half of it 30.8 -> 29.9; a quarter and an
          * eighth are best at 384 -- tools/ao_budget_probe.py).  With the count on the device the kernel picks between the two */
         const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;
-        if (!late_count && big && nhit * (unsigned long long)N >= (1ull << 27)) a->dev.ray_budget = big;
-        const int rc_ao = lh_launch_trace_ao(&a->dev, nslots, ntheta, nphi, seed, (const double *)a->r_hitrec.p, (const unsigned long long *)a->r_key.p,
+        if (!late_count && big && nhit * (unsigned long long)N >= (1ull << 27)) sc.ray_budget = big;
+        const int rc_ao = lh_launch_trace_ao(&sc, nslots, ntheta, nphi, seed, (const double *)a->r_hitrec.p, (const unsigned long long *)a->r_key.p,
                                (unsigned int *)a->r_occcount.p, cnt, (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR)), a->grid_blocks,
                                a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, late_count ? d_nhit : NULL, late_count ? big : 0u, (void *)s);
-        a->dev.ray_budget = budget_keep;
         if (rc_ao != 0) return fail("fused AO launch failed: %s", hipGetErrorString(hipGetLastError()));
         if (!late_count) {
             uint32_t qc[2] = {0, 0};
@@ -158,7 +158,7 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
             /* 5. any-hit */
             if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));   /* the abandoned fused pass is not counted (nor are the camera rays then) */
             if (lh_launch(a, nao_m, a->r_aorg.p, a->r_adir.p, NULL, NULL, NULL, NULL, a->r_occ.p, LH_MODE_ANY,
-                       LH_VARIANT_DEFAULT, cnt, s, false) != 0) return -1;
+                       LH_VARIANT_DEFAULT, cnt, s, false, opt) != 0) return -1;
         }
         return 0;
     };
@@ -219,7 +219,6 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
                         d.front(), qq(d, 0.5), qq(d, 0.9), d.back(), g.front(), qq(g, 0.1), qq(g, 0.5), qq(g, 0.9), qq(g, 0.99), g.back(), d.size());
             }
         }
-        a->dev.diag_clock = NULL;
     }
     a->r_nsamples = S; a->r_nslots = (size_t)nhit; a->r_nao = fused ? 0 : nao;
     if (cnt) {
@@ -499,9 +498,8 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
     if (lh_pt_launch_begin(cam, x0, y0, w, h, band_rows, band_stride, spp, s0, seed, d_cam, counts, nbounce + 2, s) != 0) return fail("pt begin launch failed");
     int rc = 0;
     for (int depth = 0; depth < nbounce && rc == 0; depth++) {
-        a->dev.n_dev = counts + depth; a->dev.cam_src = depth == 0 ? d_cam : NULL;
-        rc = lh_launch(a, S, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, LH_MODE_CLOSEST, LH_VARIANT_SPEC, cnt, s, false);
-        a->dev.n_dev = NULL; a->dev.cam_src = NULL;
+        lh_launch_opt opt; opt.n_dev = counts + depth; opt.cam_src = depth == 0 ? d_cam : NULL;
+        rc = lh_launch(a, S, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, LH_MODE_CLOSEST, LH_VARIANT_SPEC, cnt, s, false, opt);
         if (rc != 0) break;
         if (lh_pt_launch_shade(S, &a->dev, (const double *)a->d_nrm9, (const double *)a->d_attr9[0], (const uint32_t *)a->d_prim_mesh,
                                a->d_materials, override_mat, env_rgb, d_env_map, env_w, env_h, (flags & LH_PT_REFERENCE_WEIGHTS) != 0,
