@@ -180,6 +180,46 @@ int  lh_accel_intersect_device_ex(lh_accel_t *accel, size_t n, const void *d_org
                                   int record_format, void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v,
                                   void *d_occluded, int mode, void *stream);
 
+/* ---- indexed ray batches: trace SOME of the rays of a device-resident batch, chosen on the device ----
+ * What a wavefront transport needs between two waves of rays (a shadow pass for the rays that hit, the next bounce for the paths
+ * that survived, a re-trace of a changed subset) without reading records back, gathering rays and scattering records:
+ * d_org_xyz / d_dir_xyz and the record arrays describe n_rays rays exactly as for lh_accel_intersect_device_ex (formats, alignment,
+ * the any-hit byte); d_index holds n_index uint32_t ray ids (device; NULL: the identity list 0 .. n_index-1); d_count (device; NULL: all
+ * n_index entries) is ONE uint32_t, the number of list entries to trace -- min(*d_count, n_index) are traced, and *d_count is read by
+ * the launch on `stream`, not by the host: it may be written by work enqueued on `stream` before this call (lh_accel_compact_device).
+ *   - For every traced entry k the ray id = index[k] is traced and its record written to slot id of the record arrays (not slot k):
+ *     bit-equal to what lh_accel_intersect_device_ex writes for that ray.
+ *   - The records of rays that are not listed are not touched, byte for byte -- whatever they hold.
+ *   - An id >= n_rays is skipped: nothing is read or written for it.  An id may be listed more than once: its record is the ray's answer.
+ *   - Asynchronous on `stream`; the default variant (the tuned walk), whatever "variant" was set to.
+ *   - Every refusal of lh_accel_intersect_device_ex applies and leaves nothing written; so do n_index > 2^30, n_rays >= 2^32 and a list or
+ *     count pointer that is not 4-byte aligned.  n_index == 0 or n_rays == 0 returns 0 and looks at no array.
+ *   - With lh_accel_trace_statistics on, the call counts (node visits, tests, and `rays` advances by the number of rays traced: listed
+ *     entries within the count whose id is < n_rays) and is then synchronous: the count is known on the device alone. */
+int  lh_accel_intersect_device_indexed(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz, int ray_format,
+                                       int record_format, void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occluded,
+                                       int mode, const void *d_index, size_t n_index, const void *d_count, void *stream);
+
+/* the records of a batch -> a list for lh_accel_intersect_device_indexed, on the device.  n records: closest-hit records in
+ * d_prim_or_rec16 (record_format LH_REC_F64: the prim array; LH_REC16: the lh_rec16_t array) for LH_SELECT_HIT (prim != LH_MISS) /
+ * LH_SELECT_MISS, or any-hit bytes in d_occluded for LH_SELECT_OCCLUDED (byte != 0) / LH_SELECT_UNOCCLUDED; the array the selection
+ * does not read may be NULL (record_format is then ignored).  The candidates are the entries of the input list, given as above
+ * (d_index_in / n_index_in / d_count_in; ids >= n are skipped); all three NULL / 0: all n records.  d_index_out (room for as many
+ * entries as there are candidates: n_index_in, or n) receives the selected ids in the order they have in the input list --
+ * ascending for the identity list: the same list for the same records, run after run; d_count_out receives their number (one
+ * uint32_t).  Asynchronous on `stream`, no host synchronisation, no accelerator: it runs on the calling thread's current device.
+ * The output list and count must not alias or overlap the input list and count (the input is read while the output is written): to
+ * compact a list again, alternate between two buffers.
+ * -1 (lh_last_error), nothing written: an unknown select or record format, a missing or misaligned array, more than 2^30 candidates,
+ * an output that aliases an input. */
+#define LH_SELECT_HIT        0
+#define LH_SELECT_MISS       1
+#define LH_SELECT_OCCLUDED   2
+#define LH_SELECT_UNOCCLUDED 3
+int  lh_accel_compact_device(size_t n, int record_format, const void *d_prim_or_rec16, const void *d_occluded, int select,
+                             const void *d_index_in, size_t n_index_in, const void *d_count_in,
+                             void *d_index_out, void *d_count_out, void *stream);
+
 /* same launch with traversal statistics: counters[4] (host) receives
  * {inner-node visits, triangle tests, fp64 resolves, rays}; synchronous. */
 int  lh_accel_intersect_device_counted(lh_accel_t *accel, size_t n, const void *d_org_xyz,

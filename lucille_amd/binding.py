@@ -21,6 +21,7 @@ MODE_CLOSEST, MODE_ANY = 0, 1
 VARIANT_DEFAULT, VARIANT_DIRECT, VARIANT_SPEC = -1, 0, 4      # the tuned walk (= SPEC), the textbook reference walk
 RAYS_F64, RAYS_F32 = 0, 1           # ray formats of the _ex batch entry points (include/lucille_hip.h)
 REC_F64, REC16 = 0, 1               # record formats: SoA prim / t / u / v, or 16-byte records {prim u32, t, u, v f32}
+SELECT_HIT, SELECT_MISS, SELECT_OCCLUDED, SELECT_UNOCCLUDED = 0, 1, 2, 3      # what compact() keeps (LH_SELECT_*)
 
 
 class LucilleHipError(RuntimeError):
@@ -107,7 +108,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 ABI_SYMBOLS = [
     "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
-    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
+    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
     "lh_render_ao_tile", "lh_render_ao_tile_host", "lh_render_ao_bands", "lh_render_scratch", "lh_accel_beam_visibility_host", "lh_accel_beam_visibility_device", "lh_accel_beam_visibility_set_host", "lh_accel_beam_raster_host", "lh_accel_beam_raster_device", "lh_accel_beam_raster_set_host", "lh_render_pt_tile",
     "lh_accel_trace_statistics", "lh_accel_statistics", "lh_accel_slot_statistics",
@@ -158,6 +159,8 @@ def lib():
     L.lh_accel_intersect_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
     L.lh_accel_intersect_host_ex.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32]
     L.lh_accel_intersect_device_ex.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
+    L.lh_accel_intersect_device_indexed.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp, vp]
+    L.lh_accel_compact_device.argtypes = [sz, i32, vp, vp, i32, vp, sz, vp, vp, vp, vp]
     L.lh_accel_last_retraced.argtypes = [vp]; L.lh_accel_last_retraced.restype = C.c_uint64
     L.lh_accel_dump_node_bytes.argtypes = [vp]
     L.lh_accel_intersect_device_counted.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32,
@@ -254,6 +257,73 @@ def _records_format(records):
 def _dptr(t):
     """device pointer of a torch tensor (or None)"""
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _list_args(index, count, what):
+    """(index pointer, entries, count pointer) of a device list: `index` an int32 / uint32 tensor of ray ids (or None), `count` a
+    one-element int32 / uint32 tensor (or None)"""
+    import torch
+    words = (torch.int32, getattr(torch, "uint32", torch.int32))
+    if index is not None and not (index.is_cuda and index.dtype in words and index.dim() == 1 and index.is_contiguous()):
+        raise ValueError("%s: index must be a contiguous 1-d int32 / uint32 device tensor" % what)
+    if count is not None and not (count.is_cuda and count.dtype in words and count.numel() == 1):
+        raise ValueError("%s: count must be a one-element int32 / uint32 device tensor" % what)
+    return _dptr(index), (0 if index is None else int(index.numel())), _dptr(count)
+
+
+def compact(records_or_occluded, select, index=None, count=None, out=None, stream=None):
+    """lh_accel_compact_device: the ids of the records that `select` (SELECT_HIT / SELECT_MISS over closest-hit records -- the prim
+    tensor [n] or the rec16 tensor [n, 4], int32; SELECT_OCCLUDED / SELECT_UNOCCLUDED over the uint8 any-hit bytes [n]) keeps, in the
+    order of the input list (`index` / `count` as for HipAccel.intersect_device; neither: all n records).  Returns (index, count):
+    an int32 tensor with room for every candidate whose first count[0] entries are the list, and the one-element int32 count --
+    both on the device, nothing is read back; pass them to intersect_device(index=..., count=...).  out: such a pair to fill; it
+    must not alias or overlap `index` / `count` (the call refuses: to compact a list again, alternate between two pairs)."""
+    import torch
+    r = records_or_occluded
+    assert r.is_cuda and r.is_contiguous()
+    closest = select in (SELECT_HIT, SELECT_MISS)
+    if closest:
+        if r.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not (r.dim() == 1 or (r.dim() == 2 and r.shape[1] == 4)):
+            raise ValueError("compact: closest-hit records are an int32 prim tensor [n] or a rec16 tensor [n, 4]")
+        rf = REC16 if r.dim() == 2 else REC_F64
+    else:
+        if r.dtype != torch.uint8 or r.dim() != 1:
+            raise ValueError("compact: any-hit records are a uint8 tensor [n]")
+        rf = REC_F64
+    n = int(r.shape[0])
+    ip, ni, cp = _list_args(index, count, "compact")
+    if index is None and count is not None:
+        ni = n
+    cand = ni if (index is not None or count is not None) else n
+    if out is None:
+        out = (torch.empty(cand, dtype=torch.int32, device=r.device), torch.empty(1, dtype=torch.int32, device=r.device))
+    oi, oc = out
+    assert oi.is_cuda and oc.is_cuda and oi.is_contiguous() and oi.numel() >= cand and oc.numel() == 1
+    if stream is None:
+        stream = torch.cuda.current_stream(r.device).cuda_stream
+    with torch.cuda.device(r.device):
+        _check(lib().lh_accel_compact_device(n, rf, _dptr(r) if closest else None, None if closest else _dptr(r), select,
+                                             ip, ni, cp, _dptr(oi), _dptr(oc), C.c_void_p(stream)), "lh_accel_compact_device")
+    return out
+
+
+def _device_out(n, dev, mode, rf, out):
+    """the output tensors of a device batch (allocated when `out` is None) and their places in the C call: (out, prim, t, u, v, occ)"""
+    import torch
+    if out is None:
+        if mode == MODE_CLOSEST and rf == REC16:
+            out = (torch.empty((n, 4), dtype=torch.int32, device=dev),)
+        elif mode == MODE_CLOSEST:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
+                   torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
+        else:
+            out = (torch.empty(n, dtype=torch.uint8, device=dev),)
+    if mode == MODE_CLOSEST and rf == REC16:
+        return out, out[0], None, None, None, None
+    if mode == MODE_CLOSEST:
+        prim, t, u, v = out
+        return out, prim, t, u, v, None
+    return out, None, None, None, None, out[0]
 
 
 _live = weakref.WeakSet()
@@ -435,13 +505,47 @@ class HipAccel:
                                               occ.ctypes.data, mode), "lh_accel_intersect_host")
         return occ
 
+    def intersect_device_indexed(self, org, dr, out=None, mode=MODE_CLOSEST, stream=None, records="f64", index=None, count=None):
+        """lh_accel_intersect_device_indexed: trace the rays of org / dr ([n, 3] device tensors, float64 or float32) that the list
+        names, and write their records to THEIR slots of `out`; every other slot of `out` stays as it is.  index: int32 / uint32
+        device tensor of ray ids (None: 0 .. n-1); count: one-element int32 / uint32 device tensor, the number of list entries to
+        trace (clamped to the list's length; None: all) -- read by the launch on `stream`, not by the host, so it may be what an
+        earlier kernel on that stream is still to write (compact()).  Ids >= n are skipped, an id may appear twice.  out: as for
+        intersect_device; when it is None the tensors are allocated here with torch.empty, and the slots of rays that are not
+        listed are then UNSPECIFIED (whatever the allocator handed over).  Returns out."""
+        import torch
+        assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
+        assert org.is_contiguous() and dr.is_contiguous()
+        rf = _records_format(records)
+        n = org.shape[0]
+        dev = org.device
+        fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
+        out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
+        ip, ni, cp = _list_args(index, count, "intersect_device")
+        if index is None:
+            ni = n
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.L.lh_accel_intersect_device_indexed(self.h, n, _dptr(org), _dptr(dr), fmt, rf, _dptr(prim), _dptr(t), _dptr(u),
+                                                        _dptr(v), _dptr(occ), mode, ip, ni, cp, C.c_void_p(stream)),
+               "lh_accel_intersect_device_indexed")
+        return out
+
     def intersect_device(self, org, dr, out=None, mode=MODE_CLOSEST, variant=VARIANT_DEFAULT, stream=None,
-                         counters=False, records="f64"):
+                         counters=False, records="f64", index=None, count=None):
         """org, dr: CUDA(HIP) float64 or float32 tensors [n,3] (both of one dtype: float32 = fp32 rays, traced as the widened
         fp64 rays), contiguous.  Enqueues on `stream` (default: torch's current stream) and returns the output tensors:
         (prim, t, u, v), (occluded,), or with records="rec16" (closest hit) (rec,) -- one (n, 4) int32 tensor of lh_rec16_t
-        {prim, t, u, v as float32 bits}.  fp32 rays and rec16 records run the default variant, without counters."""
+        {prim, t, u, v as float32 bits}.  fp32 rays and rec16 records run the default variant, without counters.
+        index / count (device tensors: a list of ray ids, the number of its entries to trace): only the listed rays are traced,
+        their records go to their own slots of `out` and no other slot is written (intersect_device_indexed; the default variant,
+        without counters).  With out=None the tensors are freshly allocated and the slots of rays that are not listed are
+        UNSPECIFIED."""
         import torch
+        if index is not None or count is not None:
+            if variant != VARIANT_DEFAULT or counters:
+                raise ValueError("indexed batches run the default variant without counters")
+            return self.intersect_device_indexed(org, dr, out=out, mode=mode, stream=stream, records=records, index=index, count=count)
         assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
         assert org.is_contiguous() and dr.is_contiguous()
         rf = _records_format(records)
@@ -451,36 +555,14 @@ class HipAccel:
             if variant != VARIANT_DEFAULT or counters:
                 raise ValueError("fp32 rays / rec16 records run the default variant without counters")
             fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
-            if out is None:
-                if mode == MODE_CLOSEST and rf == REC16:
-                    out = (torch.empty((n, 4), dtype=torch.int32, device=dev),)
-                elif mode == MODE_CLOSEST:
-                    out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
-                           torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
-                else:
-                    out = (torch.empty(n, dtype=torch.uint8, device=dev),)
-            if mode == MODE_CLOSEST and rf == REC16:
-                prim, t, u, v, occ = out[0], None, None, None, None
-            elif mode == MODE_CLOSEST:
-                (prim, t, u, v), occ = out, None
-            else:
-                prim = t = u = v = None; occ = out[0]
+            out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
             if stream is None:
                 stream = torch.cuda.current_stream(dev).cuda_stream
             _check(self.L.lh_accel_intersect_device_ex(self.h, n, _dptr(org), _dptr(dr), fmt, rf, _dptr(prim), _dptr(t), _dptr(u),
                                                        _dptr(v), _dptr(occ), mode, C.c_void_p(stream)),
                    "lh_accel_intersect_device_ex")
             return out
-        if out is None:
-            if mode == MODE_CLOSEST:
-                out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float64, device=dev),
-                       torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev))
-            else:
-                out = (torch.empty(n, dtype=torch.uint8, device=dev),)
-        if mode == MODE_CLOSEST:
-            prim, t, u, v = out; occ = None
-        else:
-            prim = t = u = v = None; occ = out[0]
+        out, prim, t, u, v, occ = _device_out(n, dev, mode, REC_F64, out)
         if counters:
             torch.cuda.synchronize(dev)
             c = (C.c_uint64 * 4)()

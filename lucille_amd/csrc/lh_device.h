@@ -60,6 +60,11 @@ typedef struct lh_dev_scene {
     uint32_t   *diag_out;      /* NULL, or: four counts per ray of this launch (4-wide node visits, leaf visits, triangle records through the fp32
                                   filter, fp64 tests): the per-ray diagnostics of ri_bvh_intersect's `user` argument (bvh.h:103-110, bvh.c:451-456) */
     unsigned long long *diag_clock;   /* diagnostics (LH_STAGE_TIMING): [2][waves] start / exit wall clock of every persistent wave, or NULL */
+    const uint32_t *index;     /* indexed ray dumps (idx_on): the launch's work items are the entries of this list of ray ids, NULL = the identity list;
+                                  launch-uniform like io_fmt -- read where a ray is loaded (entry -> id), the id is what the lane, the fix-up queue and the
+                                  record stores carry from there on; never read in the node step or the triangle pass */
+    uint32_t    idx_on;        /* 0: work item i is ray i.  1: work item k is ray index[k] (or k), ids >= idx_nrays are skipped */
+    uint32_t    idx_nrays;     /* rays the ray and record arrays of an indexed launch hold */
 } lh_dev_scene_t;
 
 /* traversal statistics accumulated by the COUNT variants (u64 each) */

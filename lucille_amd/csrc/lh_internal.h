@@ -193,6 +193,9 @@ struct lh_launch_opt {
     const uint32_t *n_dev = NULL;              /* the ray count lives on the device, n is its upper bound (the path tracer's bounce chain) */
     const void *cam_src = NULL;                /* the rays are the camera rays of a path-traced pass: d_org / d_dir may be NULL */
     unsigned long long *diag_clock = NULL;     /* LH_STAGE_TIMING: start / exit clocks of the launch's waves */
+    /* an indexed ray dump (lh_accel_intersect_device_indexed): n is the number of list entries, the arrays hold idx_nrays rays; index NULL: the
+     * identity list; n_dev (above): the number of entries to trace, clamped to n */
+    bool indexed = false; const uint32_t *index = NULL; uint32_t idx_nrays = 0u;
 };
 int  lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim, void *d_t, void *d_u, void *d_v,
                void *d_occ, int mode, int variant, unsigned long long *d_counters, hipStream_t s, bool dump,

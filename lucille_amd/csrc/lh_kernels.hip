@@ -526,7 +526,12 @@ constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 /* IO (ray source 0 only): the launch's formats (sc.io_fmt) are read in the refill and written in the retire; false: fp64 rays and
  * SoA fp64 records only.  Two instantiations instead of one branch: the branch in the retire alone cost the fp64 closest-hit walk
  * five more spilled VGPRs (1 -> 6, 16 -> 32 bytes of scratch a lane), the fp64 launches now run the parent's code unchanged */
-template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false>
+/* IDX (ray source 0, with IO): an indexed launch (sc.idx_on) -- the work items the cursors hand out are the entries of a list of ray ids
+ * (sc.index, NULL = the identity list).  The refill turns the entry into the id; from there on the lane carries the id (`my`), as the
+ * fix-up queue and the record stores do: the retire, the cooperative walk and the walk itself never see the list.  An id beyond the
+ * arrays (>= sc.idx_nrays) is skipped: its lane stays idle until the next regroup, nothing is read or written for it.  IDX = false:
+ * the code of every other launch, unchanged */
+template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false, bool IDX = false>
 __device__ __forceinline__ void trace_persist_lane(
     const lh_dev_scene_t &sc, const uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
@@ -575,6 +580,11 @@ __device__ __forceinline__ void trace_persist_lane(
             const bool fragile = sc.ref_nodes != NULL && !L.over && best.prim != LH_MISS_PRIM && best.frag != 0u && !(ANYHIT && L.certain);
             bool queued = false;
             if (__builtin_expect(L.over | fragile, 0)) queued = fixq_push(fq, my, L.over ? LH_Q_COOP : LH_Q_REF);
+            if (IDX && fragile) {
+                /* an id may be listed twice: the lane whose push succeeded has the consumer write the final record while this one, turned away by a
+                 * full queue, flags the slot -- with the flag WORD alone, so that no tentative t, u, v can land among the final record's stores */
+                if (!queued) { if (ANYHIT) occ[my] = (uint8_t)LH_OCC_RETRACE; else rec_prim<true>(sc, prim, my) = LH_PRIM_RETRACE; }
+            } else
             if (SRC != 1) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT, SRC == 0 && IO>(sc, my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
             else if (!L.over && !fragile && (L.certain || best.prim != LH_MISS_PRIM)) { uint32_t sl, rr; ao_item(ao, my, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
             if (COUNT) {
@@ -663,6 +673,10 @@ __device__ __forceinline__ void trace_persist_lane(
                 }
             }
         }
+        if (IDX && newray != kNoRay) {
+            if (sc.index) newray = sc.index[newray];
+            if (newray >= sc.idx_nrays) newray = kNoRay;
+        }
         if (newray != kNoRay) {
             const uint32_t i = newray;
             my = i;
@@ -677,7 +691,7 @@ __device__ __forceinline__ void trace_persist_lane(
             it0 = it;
         }
         const unsigned long long work = __ballot((L.cur != kDone) | (pend != 0));
-        if (work == 0ull) break;
+        if (work == 0ull && (!IDX || exhausted)) break;          /* (an indexed launch: a refill whose entries were all skipped leaves a wave without work, not without rays) */
         /* ---- walk until too few lanes remain active ---------------------- */
         const int thresh = exhausted ? 1 : min_active;
         if (WALK == 3)
@@ -717,6 +731,38 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_l
         __syncthreads();
     }
     trace_persist_lane<ANYHIT, COUNT, WALK, SRC, IO>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
+}
+
+/* the persistent kernel of an indexed ray dump (lh_accel_intersect_device_indexed): n list entries at most, sc.n_dev (or NULL) the
+ * number of them to trace.  A kernel of its own, so that the kernels above keep their names, registers and instruction streams */
+template <bool ANYHIT, bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_indexed(
+    lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
+    uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+    double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters,
+    uint32_t *cursor, int min_active, int tri_batch, const FixQ fq)
+{
+    extern __shared__ int lh_stack_lds[];
+    if (sc.n_dev) { const uint32_t c = *sc.n_dev; if (c < n) n = c; }      /* min(*d_count, n_index) */
+    if (WALK != 7 && sc.top_nodes) {
+        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
+        const uint4 *src = (const uint4 *)sc.q4nodes;
+        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
+        __syncthreads();
+    }
+    trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
+}
+
+/* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
+ * arrays, skipped).  For the cold kernels that enumerate a launch's rays (k_fixups, k_trace_small) */
+__device__ __forceinline__ bool item_ray(const lh_dev_scene_t &sc, size_t k, size_t &i)
+{
+    i = k;
+    if (sc.idx_on) {
+        if (sc.index) i = sc.index[k];
+        if (i >= sc.idx_nrays) return false;
+    }
+    return true;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -992,7 +1038,7 @@ __device__ __forceinline__ void flagged_ray(const lh_dev_scene_t &sc, size_t i, 
 template <bool ANYHIT>
 __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *__restrict__ org, const double *__restrict__ dir,
                               uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
-                              uint8_t *__restrict__ occ, uint32_t *cnt = NULL)
+                              uint8_t *__restrict__ occ, uint32_t *cnt = NULL, bool *fragile_out = NULL)
 {
     double ox, oy, oz, dx, dy, dz;
     flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
@@ -1043,7 +1089,13 @@ __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *
     }
     L.over = false;
     finish<ANYHIT, true>(L, sc, ox, oy, oz, dx, dy, dz, best, ce);
-    write_out<ANYHIT>(sc, i, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL);
+    if (fragile_out) {
+        /* indexed launches: a ray id may be listed twice, and two lanes that flag, re-read and finish ONE slot can interleave their stores --
+         * so nothing tentative is written: the caller is told, and writes the reference walk's record alone (equal bits from every lane) */
+        *fragile_out = sc.ref_nodes != NULL && best.prim != LH_MISS_PRIM && best.frag != 0u && !(ANYHIT && L.certain);
+        if (!*fragile_out) write_out<ANYHIT>(sc, i, L, best, prim, t, u, v, occ, false);
+    } else
+        write_out<ANYHIT>(sc, i, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL);
     if (cnt) { cnt[0] = cn; cnt[1] = cl; cnt[2] = ct; cnt[3] = ce; }
 }
 
@@ -1056,14 +1108,20 @@ __global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, con
     /* nothing was left flagged unless a push found the queue full (or the launch had no queue: force) */
     if (!force && qcount[1] == 0u) return;
     if (sc.n_dev && (size_t)*sc.n_dev < n) n = *sc.n_dev;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    /* an indexed launch looks at the slots of its listed rays only: a stale word in an unlisted record that happens to equal a flag is not ours */
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) {
+        size_t i;
+        if (!item_ray(sc, k, i)) continue;
+        bool fragile = false, walked = false;
         if (anyhit ? (occ[i] == LH_OCC_OVERFLOW) : (rec_prim(sc, prim, i) == LH_PRIM_OVERFLOW)) {
-            if (anyhit) overflow_walk<true>(sc, i, org, dir, prim, t, u, v, occ);
-            else overflow_walk<false>(sc, i, org, dir, prim, t, u, v, occ);
+            bool *fo = sc.idx_on ? &fragile : NULL;
+            if (anyhit) overflow_walk<true>(sc, i, org, dir, prim, t, u, v, occ, NULL, fo);
+            else overflow_walk<false>(sc, i, org, dir, prim, t, u, v, occ, NULL, fo);
             if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
+            walked = sc.idx_on != 0u;
         }
         if (sc.ref_nodes == NULL) continue;
-        if (anyhit ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE)) continue;
+        if (walked ? !fragile : (anyhit ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE))) continue;
         double ox, oy, oz, dx, dy, dz;
         flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
         const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
@@ -1093,14 +1151,17 @@ __global__ __launch_bounds__(64) void k_trace_small(lh_dev_scene_t sc, uint32_t 
     /* ONE RAY PER WAVE: sixty-four unrelated rays in the lanes of one wave walk in lockstep through each other's branches
      * (16 rays: 243 us against 49 us for one, r04); a wave per ray runs them side by side on as many CUs -- the batch takes
      * as long as its longest ray.  63 idle lanes per wave are free here: the batch is tiny and the chip is empty. */
-    const uint32_t i = PER_WAVE ? blockIdx.x : blockIdx.x * 64u + threadIdx.x;
-    if (i >= n || (PER_WAVE && threadIdx.x != 0)) return;
+    const uint32_t k = PER_WAVE ? blockIdx.x : blockIdx.x * 64u + threadIdx.x;
+    if (k >= n || (PER_WAVE && threadIdx.x != 0)) return;
+    size_t i;
+    if (!item_ray(sc, k, i)) return;
     uint32_t cnt[4] = {0u, 0u, 0u, 0u};
-    overflow_walk<ANYHIT>(sc, i, org, dir, prim, t, u, v, occ, cnt);
+    bool fragile = false;
+    overflow_walk<ANYHIT>(sc, i, org, dir, prim, t, u, v, occ, cnt, sc.idx_on ? &fragile : NULL);
     if (sc.diag_out) { uint32_t *d = sc.diag_out + 4 * (size_t)i; d[0] = cnt[0]; d[1] = cnt[1]; d[2] = cnt[2]; d[3] = cnt[3]; }
     if (counters) add_counters(counters, cnt[0], cnt[2], cnt[3], 1);
     if (sc.ref_nodes == NULL) return;
-    if (ANYHIT ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE)) return;
+    if (sc.idx_on ? !fragile : (ANYHIT ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE))) return;
     double ox, oy, oz, dx, dy, dz;
     flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
     const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
@@ -1147,6 +1208,13 @@ int launch_one(const lh_dev_scene_t &sc, size_t n, const double *org, const doub
                 LH_LAUNCH_PERSIST((k_trace_persist_lane<false, COUNT, 8, 2>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
             else
                 LH_LAUNCH_PERSIST((k_trace_persist_lane<false, COUNT, 3, 2>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
+        } else if (sc.idx_on) {              /* an indexed ray dump: the list is read in the refill */
+            if (walk == 7)
+                LH_LAUNCH_PERSIST((k_trace_persist_indexed<ANYHIT, COUNT, 7>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, fq);
+            else if (walk == 8)
+                LH_LAUNCH_PERSIST((k_trace_persist_indexed<ANYHIT, COUNT, 8>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, fq);
+            else
+                LH_LAUNCH_PERSIST((k_trace_persist_indexed<ANYHIT, COUNT, 3>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, fq);
         } else if (sc.io_fmt) {              /* fp32 rays / 16-byte records: the instantiations that read and write them (IO) */
             if (walk == 7)
                 LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 7, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
@@ -1365,6 +1433,7 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double 
     /* the persistent kernel indexes rays with 32 bits: a larger batch is a sequence of launches */
     const size_t kMaxLaunch = (size_t)1 << 30;
     if (n > kMaxLaunch) {
+        if (sc->idx_on) return -1;
         /* element offsets in the launch's formats (sc->io_fmt): 3 floats or doubles per ray, 4 words or 1 per record */
         const size_t ray_b = (sc->io_fmt & LH_IO_RAYS_F32) ? 3 * sizeof(float) : 3 * sizeof(double);
         const size_t rec_w = (sc->io_fmt & LH_IO_REC16) ? 4 : 1;
@@ -1380,7 +1449,8 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double 
     }
     lh_dev_scene_t scl = *sc;
     uint32_t need; int walk; bool guard = false;
-    if ((sc->cam_src || sc->n_dev) && (variant == LH_VARIANT_DIRECT || anyhit || q == NULL)) return -1;      /* the path tracer's chain: default walk, closest hit */
+    if ((sc->cam_src || sc->n_dev) && (variant == LH_VARIANT_DIRECT || (anyhit && !sc->idx_on) || q == NULL)) return -1;      /* the path tracer's chain: default walk, closest hit; an indexed dump's count: either mode */
+    if (sc->idx_on && (variant == LH_VARIANT_DIRECT || sc->cam_src || sc->diag_out || n > kMaxLaunch)) return -1;       /* the list is read by the default walk's kernels only */
     static const bool small_ok = !(getenv("LH_SMALL_BATCH") && atoi(getenv("LH_SMALL_BATCH")) == 0);      /* LH_SMALL_BATCH=0: rounds 1-3's path for a handful of rays (A/B) */
     if (((n <= LH_SMALL_BATCH && small_ok) || sc->diag_out) && variant != LH_VARIANT_DIRECT && !sc->cam_src && !sc->n_dev && (sc->diag_out || !sc->stack_cap) && sc->q4nodes) {      /* the sequential walk has a private stack: a capped LDS stack (tests) does not concern per-ray diagnostics */
         /* a handful of rays (the coalesced one-ray callers): one small launch, a wave per ray, no queue, no cursors.

@@ -26,6 +26,27 @@ __global__ void k_fill_miss(size_t n, uint32_t *prim, double *t, double *u, doub
     if (occ) occ[i] = 0;
 }
 
+/* the listed slots of an indexed launch (lh_accel_intersect_device_indexed): entry k < min(*count, n) -> slot index[k] (or k), ids beyond nrays
+ * skipped.  miss: the records of an empty scene's rays; else: LH_POISON_OUTPUTS' 0x77 bytes -- in the LISTED slots alone, the others are not ours */
+__global__ void k_fill_listed(size_t n, const uint32_t *index, const uint32_t *count, uint32_t nrays, int miss,
+                              uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, uint4 *rec16, unsigned long long *counters)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (count && *count < n) n = *count;
+    if (k >= n) return;
+    const uint32_t i = index ? index[k] : (uint32_t)k;
+    if (i >= nrays) return;
+    const uint32_t w = miss ? LH_MISS_PRIM : 0x77777777u;
+    const unsigned long long d = 0x7777777777777777ull;
+    if (rec16) { uint4 r; r.x = w; r.y = miss ? __float_as_uint((float)LH_T_INF) : w; r.z = r.w = miss ? __float_as_uint(0.0f) : w; rec16[i] = r; }
+    if (prim) prim[i] = w;
+    if (t) t[i] = miss ? LH_T_INF : __longlong_as_double((long long)d);
+    if (u) u[i] = miss ? 0.0 : __longlong_as_double((long long)d);
+    if (v) v[i] = miss ? 0.0 : __longlong_as_double((long long)d);
+    if (occ) occ[i] = miss ? 0 : 0x77;
+    if (counters) atomicAdd(&counters[LH_CNT_RAYS], 1ull);
+}
+
 /* the fix-up queue for launches on `s`: launches on one stream are ordered, so they share a slot (queue, second stream,
  * events); different streams (replicas' tile loops, the pipelined host path) get their own */
 int lh_aoq_slot(lh_accel_t *a, hipStream_t s)
@@ -109,6 +130,15 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
     if (mode == LH_MODE_ANY && !d_occ) return fail("intersect: any mode needs the occluded output");
     if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect: unknown mode %d", mode);
     HIPCHK(hipSetDevice(a->device));
+    const bool closest = mode == LH_MODE_CLOSEST;
+    if (opt.indexed && (a->hs->bvh.ntris == 0 || (dump && a->poison_outputs))) {
+        const int miss = a->hs->bvh.ntris == 0;
+        hipLaunchKernelGGL(k_fill_listed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, opt.index, opt.n_dev, opt.idx_nrays, miss,
+                           closest && !rec16 ? (uint32_t *)d_prim : NULL, (double *)(closest ? d_t : NULL), (double *)(closest ? d_u : NULL),
+                           (double *)(closest ? d_v : NULL), closest ? NULL : (uint8_t *)d_occ, rec16 ? (uint4 *)d_prim : NULL, miss ? d_counters : NULL);
+        HIPCHK(hipGetLastError());
+        if (miss) return 0;
+    }
     if (a->hs->bvh.ntris == 0) {
         size_t blocks = (n + 255) / 256;
         hipLaunchKernelGGL(k_fill_miss, dim3((unsigned)blocks), dim3(256), 0, s, n,
@@ -118,7 +148,7 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
         HIPCHK(hipGetLastError());
         return 0;
     }
-    if (dump && a->poison_outputs) {          /* LH_POISON_OUTPUTS: every answer slot must be written by the launch */
+    if (dump && a->poison_outputs && !opt.indexed) {          /* LH_POISON_OUTPUTS: every answer slot must be written by the launch */
         if (rec16) HIPCHK(hipMemsetAsync(d_prim, 0x77, n * 16, s));
         else if (mode == LH_MODE_CLOSEST) {
             HIPCHK(hipMemsetAsync(d_prim, 0x77, n * sizeof(uint32_t), s)); HIPCHK(hipMemsetAsync(d_t, 0x77, n * sizeof(double), s));
@@ -130,6 +160,7 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
      * at once and attaches the tree when it is ready (until then ties resolve to the larger primitive id) */
     if (a->hs->device_built && !a->d_ref_nodes && lh_sync_ref(a, !a->fast_start) != 0) return -1;
     if (variant == LH_VARIANT_DEFAULT) variant = a->default_variant;
+    if (opt.indexed) variant = LH_VARIANT_SPEC;          /* the list is read by the default walk's kernels */
     if (variant != LH_VARIANT_DIRECT && variant != LH_VARIANT_SPEC)
         return fail("intersect: unknown variant %d (%d: the textbook reference walk, %d: the default)", variant, LH_VARIANT_DIRECT, LH_VARIANT_SPEC);
     /* a tree built on the device exists only as 4-wide nodes: the textbook walk runs as the default walk there */
@@ -151,6 +182,7 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
     else if (sc.ray_chunk < LH_TILE_CHUNK) sc.ray_chunk = LH_TILE_CHUNK;       /* the tile pipelines' batches are coherent in batch order */
     sc.io_fmt = opt.io_fmt & (mode == LH_MODE_ANY ? LH_IO_RAYS_F32 : (LH_IO_RAYS_F32 | LH_IO_REC16));
     sc.diag_out = opt.diag_out; sc.n_dev = opt.n_dev; sc.cam_src = opt.cam_src; sc.diag_clock = opt.diag_clock;
+    sc.idx_on = opt.indexed ? 1u : 0u; sc.index = opt.index; sc.idx_nrays = opt.idx_nrays;
     /* a ray dump over the 4-wide nodes regroups a little later and passes over parked leaves a little sooner than the tile
      * pipelines' coherent batches want (tools/experiments/knob_sweep3.py / knob_sweep4.py, r05: S-soup-1M 2 233 -> 2 266 Mrays/s
      * closest hit, 2 735 -> 2 772 any hit; the 8-wide walk and the AO stage are best where they are) */
@@ -521,6 +553,38 @@ extern "C" int lh_accel_intersect_device_ex(lh_accel_t *a, size_t n, const void 
     const int io = ex_formats("lh_accel_intersect_device_ex", n, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
     if (io < 0) return -1;
     return lh_launch(a, n, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, (hipStream_t)stream, true, lh_launch_opt{(uint32_t)io});
+}
+
+/* rays listed by ids: the records of the listed rays go to THEIR slots, every other slot stays as it is (lucille_hip.h) */
+extern "C" int lh_accel_intersect_device_indexed(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, int ray_format, int record_format,
+                                                 void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occ, int mode,
+                                                 const void *d_index, size_t n_index, const void *d_count, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_intersect_device_indexed";
+    const int io = ex_formats(what, (n_rays && n_index) ? n_rays : 0, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
+    if (io < 0) return -1;
+    if (n_index > ((size_t)1 << 30)) return fail("%s: a list holds 2^30 entries at most (%zu given)", what, n_index);
+    if (n_rays > 0xFFFFFFFFull) return fail("%s: ray ids are 32 bits wide: 2^32 - 1 rays at most (%zu given)", what, n_rays);
+    if ((((uintptr_t)d_index | (uintptr_t)d_count) & 3u) != 0) return fail("%s: the list and its count are 32-bit words: a pointer is not 4-byte aligned", what);
+    if (!a || !a->committed) return fail("intersect: accel not committed");
+    if (n_index == 0 || n_rays == 0) return 0;
+    lh_launch_opt opt;
+    opt.io_fmt = (uint32_t)io; opt.indexed = true; opt.index = (const uint32_t *)d_index; opt.idx_nrays = (uint32_t)n_rays;
+    opt.n_dev = (const uint32_t *)d_count;
+    hipStream_t s = (hipStream_t)stream;
+    if (!a->stat_on)
+        return lh_launch(a, n_index, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, s, true, opt);
+    /* statistics: the counting kernels, and one read-back -- how many rays the launch traced is known on the device alone */
+    HIPCHK(hipSetDevice(a->device));
+    HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+    if (lh_launch(a, n_index, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, a->d_counters, s, true, opt) != 0) return -1;
+    unsigned long long h[LH_CNT_DEV];
+    HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT]; a->stat[3] += h[LH_CNT_RAYS];
+    a->last_retraced = h[LH_CNT_RETRACED];
+    return 0;
 }
 
 extern "C" int lh_accel_trace_statistics(lh_accel_t *a, int enable)
