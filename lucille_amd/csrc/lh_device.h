@@ -129,12 +129,36 @@ typedef struct lh_fixq {
     void     *ev_ready, *ev_done;     /* hipEvent_t: queue reset on the launch stream; consumer finished */
 } lh_fixq_t;
 
-/* launchers implemented in lh_kernels.hip; stream is a hipStream_t */
-int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double *d_org,
-                    const double *d_dir, uint32_t *d_prim, double *d_t,
-                    double *d_u, double *d_v, int anyhit, uint8_t *d_occluded,
-                    unsigned long long *d_counters /* LH_CNT_DEV or NULL */,
-                    unsigned long long *d_workq /* LH_NPART persistent cursors */,
+/* one batch of rays and where its answers go (device addresses): what the launch path hands down, layer by layer, to the kernels'
+ * loose pointers.  The arrays' element types follow the launch's LH_IO_* formats, so they travel untyped */
+typedef struct lh_batch {
+    size_t      n;
+    int         mode;          /* LH_MODE_CLOSEST or LH_MODE_ANY */
+    const void *org, *dir;     /* 3 doubles per ray (LH_IO_RAYS_F32: 3 floats); NULL where the launch has a ray source of its own */
+    void       *prim;          /* closest hit: uint32 ids -- or the lh_rec16_t records (LH_IO_REC16), t / u / v NULL then */
+    void       *t, *u, *v;     /* closest hit: doubles */
+    void       *occ;           /* any hit: a byte per ray */
+    unsigned long long *counters;   /* LH_CNT_DEV statistics counters of a counted launch, or NULL */
+} lh_batch_t;
+
+/* rays [off, off + m) of a batch in the formats io_fmt (LH_IO_*); an array that is not there stays NULL */
+static inline lh_batch_t lh_batch_sub(lh_batch_t b, uint32_t io_fmt, size_t off, size_t m)
+{
+    const size_t ray_b = (io_fmt & LH_IO_RAYS_F32) ? 3 * sizeof(float) : 3 * sizeof(double);
+    const size_t rec_b = (io_fmt & LH_IO_REC16) ? 4 * sizeof(uint32_t) : sizeof(uint32_t);
+    b.n = m;
+    if (b.org) b.org = (const char *)b.org + ray_b * off;
+    if (b.dir) b.dir = (const char *)b.dir + ray_b * off;
+    if (b.prim) b.prim = (char *)b.prim + rec_b * off;
+    if (b.t) b.t = (double *)b.t + off;
+    if (b.u) b.u = (double *)b.u + off;
+    if (b.v) b.v = (double *)b.v + off;
+    if (b.occ) b.occ = (uint8_t *)b.occ + off;
+    return b;
+}
+
+/* launchers implemented in lh_kernels.hip; stream is a hipStream_t.  d_cursor: the launch's LH_NPART persistent cursors */
+int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, unsigned long long *d_cursor,
                     int variant, int grid_blocks, int min_active, int tri_batch,
                     const lh_fixq_t *q, int ncus, void *stream);
 int lh_launch_trace_ao(const lh_dev_scene_t *sc, size_t nslots, int ntheta, int nphi, unsigned long long seed,

@@ -3,7 +3,8 @@
  * scene, error reporting and the launch helpers.  Internal (the public C ABI is include/lucille_hip.h).
  *
  *   lh_commit.hip   lifetime: create / add meshes / commit (host or device build) / replicas / destroy / parameters
- *   lh_query.hip    ray queries: device, host and pipelined host batches, statistics, beam visibility
+ *   lh_query.hip    ray queries: device, host and pipelined host batches, statistics, beam visibility; lh_launch(accel, batch, ...), the
+ *                   one way a batch of rays (lh_batch_t) reaches the kernels' launcher (lh_kernels.hip lh_launch_trace)
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
  */
 #ifndef LH_INTERNAL_H
@@ -184,9 +185,9 @@ int  lh_scene_image_finish(lh_accel_t *a);
 extern "C" int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], uint32_t *prim, double *t, double *u, double *v);
 /* lh_query.hip */
 void lh_comb_destroy(lh_accel_t *a);                 /* the single-ray combiner's pinned block and stream (lh_accel_destroy) */
-/* one batch of rays through the hot path, from a copy of a->dev that carries the launch's own inputs: d_counters (LH_CNT_DEV
- * statistics counters or NULL), dump (a ray dump: incoherent rays, dump_budget, the 8-wide nodes where they pay; else a tile
- * pipeline's batch: ray_budget, LH_TILE_CHUNK) and, in lh_launch_opt, what only some callers have */
+/* one batch of rays (lh_batch_t, lh_device.h: rays, records, the LH_CNT_DEV statistics counters or NULL) through the hot path, from a
+ * copy of a->dev that carries the launch's own inputs: dump (a ray dump: incoherent rays, dump_budget, the 8-wide nodes where they
+ * pay; else a tile pipeline's batch: ray_budget, LH_TILE_CHUNK) and, in lh_launch_opt, what only some callers have */
 struct lh_launch_opt {
     uint32_t io_fmt = 0u;                      /* LH_IO_* (lh_device.h): ray dumps in fp32 rays / 16-byte records */
     uint32_t *diag_out = NULL;                 /* four counts per ray (lh_accel_intersect_diag_*) */
@@ -197,9 +198,12 @@ struct lh_launch_opt {
      * identity list; n_dev (above): the number of entries to trace, clamped to n */
     bool indexed = false; const uint32_t *index = NULL; uint32_t idx_nrays = 0u;
 };
-int  lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim, void *d_t, void *d_u, void *d_v,
-               void *d_occ, int mode, int variant, unsigned long long *d_counters, hipStream_t s, bool dump,
-               const lh_launch_opt &opt = lh_launch_opt());
+int  lh_launch(lh_accel_t *a, const lh_batch_t &batch, int variant, hipStream_t s, bool dump, const lh_launch_opt &opt = lh_launch_opt());
+/* the cursor block of the next persistent launch: LH_NCURSOR of them, taken in turn (one per launch in flight) */
+static inline unsigned long long *lh_next_cursor(lh_accel_t *a)
+{
+    return (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR));
+}
 int  lh_aoq_slot(lh_accel_t *a, hipStream_t s);
 int  lh_ensure_stage(lh_accel_t *a, size_t bytes);
 

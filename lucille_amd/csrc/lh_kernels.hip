@@ -1190,59 +1190,44 @@ static int allow_lds(const void *func, size_t bytes)
 #define LH_LAUNCH_PERSIST(KERNEL, ...) do { if (allow_lds((const void *)(KERNEL), lds_bytes) != 0) return -1; \
                                             hipLaunchKernelGGL((KERNEL), dim3(grid_blocks), dim3(LH_BLOCK), lds_bytes, s, __VA_ARGS__); } while (0)
 
-template <bool ANYHIT, bool COUNT>
-int launch_one(const lh_dev_scene_t &sc, size_t n, const double *org, const double *dir,
-               uint32_t *prim, double *t, double *u, double *v, uint8_t *occ,
-               unsigned long long *counters, unsigned long long *cursor, int walk,
-               int grid_blocks, int min_active, int tri_batch, size_t lds_bytes, const FixQ &fq, hipStream_t s)
-{
-    if (walk == 0) {
-        const size_t blocks = (n + LH_BLOCK - 1) / LH_BLOCK;
-        if (blocks > 0x7fffffffull) return -1;
-        hipLaunchKernelGGL((k_trace_direct<ANYHIT, COUNT>), dim3((unsigned)blocks), dim3(LH_BLOCK), lds_bytes, s,
-                           sc, n, org, dir, prim, t, u, v, occ, counters);
-    } else {
-        if (hipMemsetAsync(cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
-        if (sc.cam_src) {                    /* ray source 2: closest hit over the 4-wide nodes only (lh_launch_trace checks) */
-            if (walk == 8)
-                LH_LAUNCH_PERSIST((k_trace_persist_lane<false, COUNT, 8, 2>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-            else
-                LH_LAUNCH_PERSIST((k_trace_persist_lane<false, COUNT, 3, 2>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-        } else if (sc.idx_on) {              /* an indexed ray dump: the list is read in the refill */
-            if (walk == 7)
-                LH_LAUNCH_PERSIST((k_trace_persist_indexed<ANYHIT, COUNT, 7>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, fq);
-            else if (walk == 8)
-                LH_LAUNCH_PERSIST((k_trace_persist_indexed<ANYHIT, COUNT, 8>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, fq);
-            else
-                LH_LAUNCH_PERSIST((k_trace_persist_indexed<ANYHIT, COUNT, 3>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, fq);
-        } else if (sc.io_fmt) {              /* fp32 rays / 16-byte records: the instantiations that read and write them (IO) */
-            if (walk == 7)
-                LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 7, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-            else if (walk == 8)
-                LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 8, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-            else
-                LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 3, 0, true>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-        } else if (walk == 7)
-            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 7, 0, false>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-        else if (walk == 8)
-            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 8, 0, false>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-        else
-            LH_LAUNCH_PERSIST((k_trace_persist_lane<ANYHIT, COUNT, 3, 0, false>), sc, (uint32_t)n, org, dir, prim, t, u, v, occ, counters, (uint32_t *)cursor, min_active, tri_batch, AoSrc{}, fq);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
+/* a batch's ray and record arrays as the kernels take them: loose typed pointers, in every kernel's order */
+#define LH_BATCH_ARRAYS(B) (const double *)(B).org, (const double *)(B).dir, (uint32_t *)(B).prim, (double *)(B).t, (double *)(B).u, \
+                           (double *)(B).v, (uint8_t *)(B).occ
 
-int launch_walk(const lh_dev_scene_t &sc, size_t n, const double *org, const double *dir,
-                uint32_t *prim, double *t, double *u, double *v, int anyhit, uint8_t *occ,
-                unsigned long long *counters, unsigned long long *cursor, int walk,
+/* the batch's main kernel: walk 0 the textbook walk, 3 / 8 the 4-wide nodes (8: checked pushes), 7 the 8-wide nodes.  The instantiation
+ * follows the batch (any hit, counted) and the launch's scene: camera rays (SRC 2), a list of ray ids, fp32 rays / 16-byte records (IO) */
+int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, unsigned long long *cursor, int walk,
                 int grid_blocks, int min_active, int tri_batch, size_t lds_bytes, const FixQ &fq, hipStream_t s)
 {
-    if (anyhit) {
-        if (counters) return launch_one<true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
-        return launch_one<true, false>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
-    }
-    if (counters) return launch_one<false, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
-    return launch_one<false, false>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
+    auto launch = [&](auto anyhit_c, auto count_c) -> int {
+        constexpr bool ANYHIT = decltype(anyhit_c)::value, COUNT = decltype(count_c)::value;
+        if (walk == 0) {
+            const size_t blocks = (b.n + LH_BLOCK - 1) / LH_BLOCK;
+            if (blocks > 0x7fffffffull) return -1;
+            hipLaunchKernelGGL((k_trace_direct<ANYHIT, COUNT>), dim3((unsigned)blocks), dim3(LH_BLOCK), lds_bytes, s,
+                               sc, b.n, LH_BATCH_ARRAYS(b), b.counters);
+        } else {
+            if (hipMemsetAsync(cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
+            /* the instantiations of this batch, by ray source and by walk (w: 7, 8, 3); the compiler emits the kernels in the order they are first
+             * named here, so a reordering shows up in a comparison of the device code */
+            using lane_t = decltype(&k_trace_persist_lane<ANYHIT, COUNT, 3, 0>);
+            using indexed_t = decltype(&k_trace_persist_indexed<ANYHIT, COUNT, 3>);
+            const int w = walk == 7 ? 0 : walk == 8 ? 1 : 2;
+            const lane_t cam = walk == 8 ? k_trace_persist_lane<false, COUNT, 8, 2> : k_trace_persist_lane<false, COUNT, 3, 2>;      /* ray source 2: closest hit over the 4-wide nodes only (lh_launch_trace checks) */
+            const indexed_t indexed[3] = {k_trace_persist_indexed<ANYHIT, COUNT, 7>, k_trace_persist_indexed<ANYHIT, COUNT, 8>, k_trace_persist_indexed<ANYHIT, COUNT, 3>};
+            const lane_t io[3] = {k_trace_persist_lane<ANYHIT, COUNT, 7, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, 8, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, 3, 0, true>};
+            const lane_t f64[3] = {k_trace_persist_lane<ANYHIT, COUNT, 7, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, 8, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, 3, 0, false>};
+            if (sc.idx_on && !sc.cam_src)        /* an indexed ray dump: the list is read in the refill */
+                LH_LAUNCH_PERSIST(indexed[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor, min_active, tri_batch, fq);
+            else                                 /* io_fmt: fp32 rays / 16-byte records, the instantiations that read and write them (IO) */
+                LH_LAUNCH_PERSIST(sc.cam_src ? cam : sc.io_fmt ? io[w] : f64[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor,
+                                  min_active, tri_batch, AoSrc{}, fq);
+        }
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    };
+    const std::true_type yes; const std::false_type no;
+    if (b.mode == LH_MODE_ANY) return b.counters ? launch(yes, yes) : launch(yes, no);
+    return b.counters ? launch(no, yes) : launch(no, no);
 }
 
 /* LDS stack rows of a 4-wide walk over this scene.  3 * depth + 5 (or the builder's count of the deepest path) covers every
@@ -1322,9 +1307,11 @@ void clamp_chunk(lh_dev_scene_t &scl, size_t n, int grid_blocks)
  * one ray per 16 lanes, restarted from the root -- is hidden behind the bulk of the frame), submitted AFTER it: if the two
  * streams share a hardware queue it simply runs afterwards. */
 template <bool ANYHIT, int SRC>
-int launch_coop(const lh_dev_scene_t &sc, const double *org, const double *dir, uint32_t *prim, double *t, double *u, double *v,
-                uint8_t *occ, const AoSrc &ao, const FixQ &fq, const lh_fixq_t *q, unsigned long long *counters, int ncus, hipStream_t s)
+int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_fixq_t *q, int ncus, hipStream_t s)
 {
+    /* the pass next to the producer (owner_groups 0) and the sweep behind it */
+#define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL((k_coop_walk<ANYHIT, SRC>), dim3(GRID), dim3(64), lds, STREAM, scl, LH_BATCH_ARRAYS(b), \
+                                                                      ao, fq, b.counters, OWNER_GROUPS)
     lh_dev_scene_t scl = sc;
     scl.stack_rows = coop_rows(sc);
     if (scl.stack_rows == 0) return -1;
@@ -1341,7 +1328,7 @@ int launch_coop(const lh_dev_scene_t &sc, const double *org, const double *dir, 
     if (concurrent < 0) { const char *e = getenv("LH_COOP_CONCURRENT"); concurrent = (e && atoi(e) == 0) ? 0 : 1; }
     if (concurrent) {
         if (hipStreamWaitEvent(aux, (hipEvent_t)q->ev_ready, 0) != hipSuccess) return -1;
-        hipLaunchKernelGGL((k_coop_walk<ANYHIT, SRC>), dim3(grid), dim3(64), lds, aux, scl, org, dir, prim, t, u, v, occ, ao, fq, counters, 0u);
+        LH_LAUNCH_COOP(grid, aux, 0u);
         if (hipGetLastError() != hipSuccess) return -1;
         if (hipEventRecord((hipEvent_t)q->ev_done, aux) != hipSuccess) return -1;
         if (hipStreamWaitEvent(s, (hipEvent_t)q->ev_done, 0) != hipSuccess) return -1;
@@ -1349,7 +1336,8 @@ int launch_coop(const lh_dev_scene_t &sc, const double *org, const double *dir, 
     /* the sweep: the same kernel behind the producer, on its stream, sixteen waves per CU -- whatever the concurrent pass did not
      * take (nothing, when it ran next to the producer: the waves read a few words and leave) */
     /* (a sweep of grid x 4 or x 2 workgroups instead of x 16: a rank's share of the config-5 frame 7.35 / 7.80 -> 7.35 / 7.79 and 7.31 / 7.73 ms: nothing.  r06_share_probe.txt) */
-    hipLaunchKernelGGL((k_coop_walk<ANYHIT, SRC>), dim3(grid * 16), dim3(64), lds, s, scl, org, dir, prim, t, u, v, occ, ao, fq, counters, (uint32_t)grid * 4u);
+    LH_LAUNCH_COOP(grid * 16, s, (uint32_t)grid * 4u);
+#undef LH_LAUNCH_COOP
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1401,7 +1389,8 @@ extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, size_t nslots, int n
     else { if (d_counters) LH_AO_LAUNCH(true, 3); else LH_AO_LAUNCH(false, 3); }
 #undef LH_AO_LAUNCH
     if (hipGetLastError() != hipSuccess) return -1;
-    return launch_coop<true, 1>(scl, NULL, NULL, NULL, NULL, NULL, NULL, NULL, ao, fq, q, d_counters, ncus, s);
+    const lh_batch_t none = {n, LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};          /* the rays are made in the kernel, the answers counted per slot */
+    return launch_coop<true, 1>(scl, none, ao, fq, q, ncus, s);
 }
 
 /* the node formats a launch of `variant` reads on this scene (bit mask, LH_FMT_* in lh_internal.h): so that the commit
@@ -1418,31 +1407,26 @@ extern "C" int lh_trace_formats_needed(const lh_dev_scene_t *sc, int variant)
     return variant == LH_VARIANT_DIRECT ? 1 : 4;
 }
 
-/* one batch of rays through the hot path.  variant: LH_VARIANT_SPEC (the default: 4-wide nodes, or the 8-wide nodes when
+/* one batch of rays (lh_batch_t: the rays, where the records go, the counters of a counted launch) through the hot path; d_cursor: the
+ * launch's block of persistent cursors.  variant: LH_VARIANT_SPEC (the default: 4-wide nodes, or the 8-wide nodes when
  * sc->prefer_q8) or LH_VARIANT_DIRECT (the textbook walk over the 2-wide fp32 nodes; needs sc->nodes).  q: the launch's
  * fix-up queue with its second stream, private to the stream. */
-extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double *d_org,
-                               const double *d_dir, uint32_t *d_prim, double *d_t, double *d_u,
-                               double *d_v, int anyhit, uint8_t *d_occluded,
-                               unsigned long long *d_counters, unsigned long long *d_workq,
+extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, unsigned long long *d_cursor,
                                int variant, int grid_blocks, int min_active, int tri_batch,
                                const lh_fixq_t *q, int ncus, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
+    const lh_batch_t &b = *batch;
+    const size_t n = b.n;
+    const bool anyhit = b.mode == LH_MODE_ANY;
     if (n == 0) return 0;
     /* the persistent kernel indexes rays with 32 bits: a larger batch is a sequence of launches */
     const size_t kMaxLaunch = (size_t)1 << 30;
     if (n > kMaxLaunch) {
         if (sc->idx_on) return -1;
-        /* element offsets in the launch's formats (sc->io_fmt): 3 floats or doubles per ray, 4 words or 1 per record */
-        const size_t ray_b = (sc->io_fmt & LH_IO_RAYS_F32) ? 3 * sizeof(float) : 3 * sizeof(double);
-        const size_t rec_w = (sc->io_fmt & LH_IO_REC16) ? 4 : 1;
         for (size_t off = 0; off < n; off += kMaxLaunch) {
-            const size_t m = (n - off < kMaxLaunch) ? n - off : kMaxLaunch;
-            const int rc = lh_launch_trace(sc, m, (const double *)((const char *)d_org + ray_b * off), (const double *)((const char *)d_dir + ray_b * off),
-                                           d_prim ? d_prim + rec_w * off : NULL, d_t ? d_t + off : NULL,
-                                           d_u ? d_u + off : NULL, d_v ? d_v + off : NULL, anyhit, d_occluded ? d_occluded + off : NULL,
-                                           d_counters, d_workq, variant, grid_blocks, min_active, tri_batch, q, ncus, stream);
+            const lh_batch_t part = lh_batch_sub(b, sc->io_fmt, off, (n - off < kMaxLaunch) ? n - off : kMaxLaunch);
+            const int rc = lh_launch_trace(sc, &part, d_cursor, variant, grid_blocks, min_active, tri_batch, q, ncus, stream);
             if (rc != 0) return rc;
         }
         return 0;
@@ -1455,14 +1439,9 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double 
     if (((n <= LH_SMALL_BATCH && small_ok) || sc->diag_out) && variant != LH_VARIANT_DIRECT && !sc->cam_src && !sc->n_dev && (sc->diag_out || !sc->stack_cap) && sc->q4nodes) {      /* the sequential walk has a private stack: a capped LDS stack (tests) does not concern per-ray diagnostics */
         /* a handful of rays (the coalesced one-ray callers): one small launch, a wave per ray, no queue, no cursors.
          * Per-ray diagnostics (diag_out): the same walk for a batch of any size, a lane per ray */
-        if (n <= LH_SMALL_BATCH) {
-            if (anyhit) hipLaunchKernelGGL((k_trace_small<true, true>), dim3((unsigned)n), dim3(64), 0, s, scl, (uint32_t)n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, d_counters);
-            else hipLaunchKernelGGL((k_trace_small<false, true>), dim3((unsigned)n), dim3(64), 0, s, scl, (uint32_t)n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, d_counters);
-        } else {
-            const unsigned blocks = (unsigned)((n + 63) / 64);
-            if (anyhit) hipLaunchKernelGGL((k_trace_small<true, false>), dim3(blocks), dim3(64), 0, s, scl, (uint32_t)n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, d_counters);
-            else hipLaunchKernelGGL((k_trace_small<false, false>), dim3(blocks), dim3(64), 0, s, scl, (uint32_t)n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, d_counters);
-        }
+        const bool per_wave = n <= LH_SMALL_BATCH;
+        auto *k = per_wave ? (anyhit ? k_trace_small<true, true> : k_trace_small<false, true>) : (anyhit ? k_trace_small<true, false> : k_trace_small<false, false>);
+        hipLaunchKernelGGL(k, dim3((unsigned)(per_wave ? n : (n + 63) / 64)), dim3(64), 0, s, scl, (uint32_t)n, LH_BATCH_ARRAYS(b), b.counters);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (sc->diag_out) return -1;                 /* per-ray diagnostics exist for the default walk's nodes only */
@@ -1500,20 +1479,19 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, size_t n, const double 
     if (!coop) scl.ray_budget = 0xFFFFFFFFu;
     if (walk != 0 && q != NULL && fixq_begin(q, s) != 0) return -1;
     if (walk != 0 && q == NULL) return -1;
-    int rc = launch_walk(scl, n, d_org, d_dir, d_prim, d_t, d_u, d_v, anyhit, d_occluded,
-                         d_counters, d_workq, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
+    int rc = launch_walk(scl, b, d_cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
     if (rc != 0) return rc;
     if (coop) {
-        rc = anyhit ? launch_coop<true, 0>(scl, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, AoSrc{}, fq, q, d_counters, ncus, s)
-             : sc->cam_src ? launch_coop<false, 2>(scl, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, AoSrc{}, fq, q, d_counters, ncus, s)
-                    : launch_coop<false, 0>(scl, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occluded, AoSrc{}, fq, q, d_counters, ncus, s);
+        rc = anyhit ? launch_coop<true, 0>(scl, b, AoSrc{}, fq, q, ncus, s)
+             : sc->cam_src ? launch_coop<false, 2>(scl, b, AoSrc{}, fq, q, ncus, s)
+                    : launch_coop<false, 0>(scl, b, AoSrc{}, fq, q, ncus, s);
         if (rc != 0) return rc;
     }
     /* what is still flagged: fragile hits (the reference's own walk), and out-of-budget rays the queue had no room for */
     {
         const size_t blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(k_fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, d_org, d_dir,
-                           d_prim, d_t, d_u, d_v, d_occluded, anyhit, d_counters, q ? q->qcount : NULL, (walk == 0 || q == NULL) ? 1 : 0);
+        hipLaunchKernelGGL(k_fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, LH_BATCH_ARRAYS(b),
+                           anyhit ? 1 : 0, b.counters, q ? q->qcount : NULL, (walk == 0 || q == NULL) ? 1 : 0);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -13,21 +13,10 @@
 
 #include "lh_internal.h"
 
-/* fill miss results without touching the scene (empty accel); rec16 (or NULL): 16-byte records instead of prim / t / u / v */
-__global__ void k_fill_miss(size_t n, uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, uint4 *rec16)
-{
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (rec16) { uint4 r; r.x = LH_MISS_PRIM; r.y = __float_as_uint((float)LH_T_INF); r.z = r.w = __float_as_uint(0.0f); rec16[i] = r; }
-    if (prim) prim[i] = LH_MISS_PRIM;
-    if (t) t[i] = LH_T_INF;
-    if (u) u[i] = 0.0;
-    if (v) v[i] = 0.0;
-    if (occ) occ[i] = 0;
-}
-
-/* the listed slots of an indexed launch (lh_accel_intersect_device_indexed): entry k < min(*count, n) -> slot index[k] (or k), ids beyond nrays
- * skipped.  miss: the records of an empty scene's rays; else: LH_POISON_OUTPUTS' 0x77 bytes -- in the LISTED slots alone, the others are not ours */
+/* fill record slots without touching the scene: entry k < min(*count, n) -> slot index[k] (or k), ids beyond nrays skipped -- the listed slots of
+ * an indexed launch (lh_accel_intersect_device_indexed), or all n of a dense one (index, count NULL, nrays = n).  miss: the records of an empty
+ * scene's rays; else: LH_POISON_OUTPUTS' 0x77 bytes -- in the LISTED slots alone, the others are not ours.  rec16 (or NULL): 16-byte records
+ * instead of prim / t / u / v */
 __global__ void k_fill_listed(size_t n, const uint32_t *index, const uint32_t *count, uint32_t nrays, int miss,
                               uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, uint4 *rec16, unsigned long long *counters)
 {
@@ -117,43 +106,49 @@ static bool dump_walks_q8(const lh_accel_t *a, int variant)
     return variant == LH_VARIANT_SPEC && q8_available(a) && (a->wide8 == 1 || (a->wide8 == -1 && wide8_pays(a)));
 }
 
-int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, void *d_prim,
-              void *d_t, void *d_u, void *d_v, void *d_occ, int mode, int variant,
-              unsigned long long *d_counters, hipStream_t s, bool dump, const lh_launch_opt &opt)
+/* what the batch entry points check first, the same check winning whichever of them is asked: 1 = go on, 0 = no rays (nothing to do),
+ * -1 = refused (lh_last_error: "<what>: ...") */
+static int batch_args(const lh_accel_t *a, const char *what, size_t n, bool have_arrays, const char *arrays, int mode)
 {
-    if (!a || !a->committed) return fail("intersect: accel not committed");
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
     if (n == 0) return 0;
-    if ((!d_org || !d_dir) && !opt.cam_src) return fail("intersect: NULL ray arrays");
-    const bool rec16 = mode == LH_MODE_CLOSEST && (opt.io_fmt & LH_IO_REC16);
-    if (rec16 && (!d_prim || d_t || d_u || d_v)) return fail("intersect: 16-byte records go to one array (t, u, v must be NULL)");
-    if (mode == LH_MODE_CLOSEST && !rec16 && (!d_prim || !d_t || !d_u || !d_v)) return fail("intersect: closest mode needs prim,t,u,v outputs");
-    if (mode == LH_MODE_ANY && !d_occ) return fail("intersect: any mode needs the occluded output");
-    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect: unknown mode %d", mode);
+    if (!have_arrays) return fail("%s: NULL %s", what, arrays);
+    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("%s: unknown mode %d", what, mode);
+    return 1;
+}
+
+int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bool dump, const lh_launch_opt &opt)
+{
+    const int go = batch_args(a, "intersect", b.n, (b.org && b.dir) || opt.cam_src, "ray arrays", b.mode);
+    if (go <= 0) return go;
+    const size_t n = b.n;
+    const bool closest = b.mode == LH_MODE_CLOSEST, rec16 = closest && (opt.io_fmt & LH_IO_REC16);
+    if (rec16 && (!b.prim || b.t || b.u || b.v)) return fail("intersect: 16-byte records go to one array (t, u, v must be NULL)");
+    if (closest && !rec16 && (!b.prim || !b.t || !b.u || !b.v)) return fail("intersect: closest mode needs prim,t,u,v outputs");
+    if (!closest && !b.occ) return fail("intersect: any mode needs the occluded output");
     HIPCHK(hipSetDevice(a->device));
-    const bool closest = mode == LH_MODE_CLOSEST;
-    if (opt.indexed && (a->hs->bvh.ntris == 0 || (dump && a->poison_outputs))) {
-        const int miss = a->hs->bvh.ntris == 0;
-        hipLaunchKernelGGL(k_fill_listed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, opt.index, opt.n_dev, opt.idx_nrays, miss,
-                           closest && !rec16 ? (uint32_t *)d_prim : NULL, (double *)(closest ? d_t : NULL), (double *)(closest ? d_u : NULL),
-                           (double *)(closest ? d_v : NULL), closest ? NULL : (uint8_t *)d_occ, rec16 ? (uint4 *)d_prim : NULL, miss ? d_counters : NULL);
-        HIPCHK(hipGetLastError());
+    /* an empty scene: every ray misses -- all of a dense batch, the listed ones of an indexed batch (which are counted: how many there are is
+     * known on the device alone).  LH_POISON_OUTPUTS: the listed slots alone are the launch's to spoil; a dense batch's arrays take a memset */
+    const bool miss = a->hs->bvh.ntris == 0;
+    if (miss || (opt.indexed && dump && a->poison_outputs)) {
+        const size_t step = (size_t)1 << 30;          /* the fill kernel's slot ids are 32 bits wide (a list holds 2^30 entries at most) */
+        for (size_t off = 0; off < n; off += step) {
+            const lh_batch_t f = lh_batch_sub(b, opt.io_fmt, off, n - off < step ? n - off : step);
+            hipLaunchKernelGGL(k_fill_listed, dim3((unsigned)((f.n + 255) / 256)), dim3(256), 0, s, f.n, opt.indexed ? opt.index : NULL,
+                               opt.indexed ? opt.n_dev : NULL, opt.indexed ? opt.idx_nrays : (uint32_t)f.n, miss ? 1 : 0,
+                               closest && !rec16 ? (uint32_t *)f.prim : NULL, (double *)(closest ? f.t : NULL), (double *)(closest ? f.u : NULL),
+                               (double *)(closest ? f.v : NULL), closest ? NULL : (uint8_t *)f.occ, rec16 ? (uint4 *)f.prim : NULL,
+                               miss && opt.indexed ? f.counters : NULL);
+            HIPCHK(hipGetLastError());
+        }
         if (miss) return 0;
     }
-    if (a->hs->bvh.ntris == 0) {
-        size_t blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(k_fill_miss, dim3((unsigned)blocks), dim3(256), 0, s, n,
-                           mode == LH_MODE_CLOSEST && !rec16 ? (uint32_t *)d_prim : NULL, (double *)(mode == LH_MODE_CLOSEST ? d_t : NULL),
-                           (double *)(mode == LH_MODE_CLOSEST ? d_u : NULL), (double *)(mode == LH_MODE_CLOSEST ? d_v : NULL),
-                           mode == LH_MODE_ANY ? (uint8_t *)d_occ : NULL, rec16 ? (uint4 *)d_prim : NULL);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
     if (dump && a->poison_outputs && !opt.indexed) {          /* LH_POISON_OUTPUTS: every answer slot must be written by the launch */
-        if (rec16) HIPCHK(hipMemsetAsync(d_prim, 0x77, n * 16, s));
-        else if (mode == LH_MODE_CLOSEST) {
-            HIPCHK(hipMemsetAsync(d_prim, 0x77, n * sizeof(uint32_t), s)); HIPCHK(hipMemsetAsync(d_t, 0x77, n * sizeof(double), s));
-            HIPCHK(hipMemsetAsync(d_u, 0x77, n * sizeof(double), s)); HIPCHK(hipMemsetAsync(d_v, 0x77, n * sizeof(double), s));
-        } else HIPCHK(hipMemsetAsync(d_occ, 0x77, n, s));
+        if (rec16) HIPCHK(hipMemsetAsync(b.prim, 0x77, n * 16, s));
+        else if (closest) {
+            HIPCHK(hipMemsetAsync(b.prim, 0x77, n * sizeof(uint32_t), s)); HIPCHK(hipMemsetAsync(b.t, 0x77, n * sizeof(double), s));
+            HIPCHK(hipMemsetAsync(b.u, 0x77, n * sizeof(double), s)); HIPCHK(hipMemsetAsync(b.v, 0x77, n * sizeof(double), s));
+        } else HIPCHK(hipMemsetAsync(b.occ, 0x77, n, s));
     }
     /* a device-built scene: lucille's own tree (exact-t tie winners, fragile hits) is built by a background host thread.
      * Queries are exact by default -- the first launch waits for it; set_param("fast_start", 1) / LH_FAST_START=1 launches
@@ -180,7 +175,7 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
      * several times its own steps -- the tile pipelines' budget (128) would send half the batch to the cooperative walk */
     if (dump) sc.ray_budget = a->dump_budget;
     else if (sc.ray_chunk < LH_TILE_CHUNK) sc.ray_chunk = LH_TILE_CHUNK;       /* the tile pipelines' batches are coherent in batch order */
-    sc.io_fmt = opt.io_fmt & (mode == LH_MODE_ANY ? LH_IO_RAYS_F32 : (LH_IO_RAYS_F32 | LH_IO_REC16));
+    sc.io_fmt = opt.io_fmt & (closest ? (LH_IO_RAYS_F32 | LH_IO_REC16) : LH_IO_RAYS_F32);
     sc.diag_out = opt.diag_out; sc.n_dev = opt.n_dev; sc.cam_src = opt.cam_src; sc.diag_clock = opt.diag_clock;
     sc.idx_on = opt.indexed ? 1u : 0u; sc.index = opt.index; sc.idx_nrays = opt.idx_nrays;
     /* a ray dump over the 4-wide nodes regroups a little later and passes over parked leaves a little sooner than the tile
@@ -188,11 +183,9 @@ int lh_launch(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, voi
      * closest hit, 2 735 -> 2 772 any hit; the 8-wide walk and the AO stage are best where they are) */
     const bool dump4 = dump && !q8 && !a->knobs_user;
     const bool dump8 = dump && q8 && !a->knobs_user;
-    int rc = lh_launch_trace(&sc, n, (const double *)d_org, (const double *)d_dir, (uint32_t *)d_prim,
-                             (double *)d_t, (double *)d_u, (double *)d_v, mode == LH_MODE_ANY,
-                             (uint8_t *)d_occ, d_counters, (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR)), variant, a->grid_blocks,
-                             dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch,
-                             &a->aoq[qk].q, a->ncus, (void *)s);
+    const int rc = lh_launch_trace(&sc, &b, lh_next_cursor(a), variant, a->grid_blocks,
+                                   dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch,
+                                   &a->aoq[qk].q, a->ncus, (void *)s);
     if (rc != 0) return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
@@ -202,7 +195,24 @@ extern "C" int lh_accel_intersect_device(lh_accel_t *a, size_t n, const void *d_
                                          int mode, int variant, void *stream)
 {
     lh_guard guard(a);
-    return lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, variant, NULL, (hipStream_t)stream, true);
+    return lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, NULL}, variant, (hipStream_t)stream, true);
+}
+
+/* a counted launch: a->d_counters zeroed on the launch's stream before it, read back on that stream behind it (waits for the stream).  A caller
+ * that keeps statistics adds what is its own to say: how many rays, how many hits */
+static int counted_begin(lh_accel_t *a, hipStream_t s) { HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, s)); return 0; }
+static int counted_collect(lh_accel_t *a, hipStream_t s, unsigned long long h[LH_CNT_DEV])
+{
+    HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(unsigned long long) * LH_CNT_DEV, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    a->last_retraced = h[LH_CNT_RETRACED];
+    return 0;
+}
+
+static void stat_add(lh_accel_t *a, const unsigned long long *h, unsigned long long rays, unsigned long long hits)
+{
+    a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT];
+    a->stat[3] += rays; a->stat[4] += hits;
 }
 
 extern "C" int lh_accel_intersect_device_counted(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir,
@@ -213,22 +223,20 @@ extern "C" int lh_accel_intersect_device_counted(lh_accel_t *a, size_t n, const 
     if (!a || !a->committed) return fail("intersect: accel not committed");
     if (!counters) return fail("intersect_counted: counters is NULL");
     HIPCHK(hipSetDevice(a->device));
-    HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, a->stream));
+    if (counted_begin(a, a->stream) != 0) return -1;
     HIPCHK(hipDeviceSynchronize());
-    if (a->hs->bvh.ntris == 0) { counters[0] = counters[1] = counters[2] = 0; counters[3] = n; }
-    int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, variant, a->d_counters, a->stream, true);
+    const bool empty = a->hs->bvh.ntris == 0;          /* answered without a walk: nothing is counted on the device */
+    if (empty) { counters[0] = counters[1] = counters[2] = 0; counters[3] = n; }
+    int rc = lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, a->d_counters}, variant, a->stream, true);
     if (rc != 0) return rc;
-    HIPCHK(hipStreamSynchronize(a->stream));
-    if (a->hs->bvh.ntris) {
-        unsigned long long h[LH_CNT_DEV];
-        HIPCHK(hipMemcpy(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost));
-        for (int k = 0; k < LH_CNT_N; k++) counters[k] = h[k];
-        a->last_retraced = h[LH_CNT_RETRACED];
-        if (getenv("LH_DEBUG_COUNTERS"))
-            fprintf(stderr, "[lucille_hip] lane slots: node steps %llu of %llu, triangle steps %llu of %llu, regroup iterations %llu; "
-                            "rays through the reference walk %llu\n",
-                    h[LH_CNT_NODES], h[LH_CNT_NODE_SLOTS], h[LH_CNT_TRIS], h[LH_CNT_TRI_SLOTS], h[LH_CNT_REGROUP_SLOTS], h[LH_CNT_RETRACED]);
-    }
+    if (empty) { HIPCHK(hipStreamSynchronize(a->stream)); return 0; }
+    unsigned long long h[LH_CNT_DEV];
+    if (counted_collect(a, a->stream, h) != 0) return -1;
+    for (int k = 0; k < LH_CNT_N; k++) counters[k] = h[k];
+    if (getenv("LH_DEBUG_COUNTERS"))
+        fprintf(stderr, "[lucille_hip] lane slots: node steps %llu of %llu, triangle steps %llu of %llu, regroup iterations %llu; "
+                        "rays through the reference walk %llu\n",
+                h[LH_CNT_NODES], h[LH_CNT_NODE_SLOTS], h[LH_CNT_TRIS], h[LH_CNT_TRI_SLOTS], h[LH_CNT_REGROUP_SLOTS], h[LH_CNT_RETRACED]);
     return 0;
 }
 
@@ -385,17 +393,21 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const void *org, co
     size_t C = CAP;
     if (n < 4 * CAP) { C = ((n + 3) / 4 + 4095) & ~(size_t)4095; if (C < ((size_t)1 << 16)) C = (size_t)1 << 16; if (C > CAP) C = CAP; }
     const size_t nchunks = (n + C - 1) / C;
+    /* where a block's arrays start (bytes): in: org | dir, out: t | u | v | prim -- CAP rays apart whatever a chunk holds; the 16-byte records
+     * and the occluded bytes start their block.  back: the arrays the caller wants, in the order they come back */
+    const struct { size_t dir, t, u, v, prim; } at = {RB * CAP, 0, sizeof(double) * CAP, 2 * sizeof(double) * CAP, 3 * sizeof(double) * CAP};
+    struct { void *user; size_t at, bytes; } back[4]; int nback = 0;
+    if (rec16) back[nback++] = {prim, 0, 16};
+    else if (mode == LH_MODE_CLOSEST) {
+        if (t) back[nback++] = {t, at.t, sizeof(double)};
+        if (u) back[nback++] = {u, at.u, sizeof(double)};
+        if (v) back[nback++] = {v, at.v, sizeof(double)};
+        if (prim) back[nback++] = {prim, at.prim, sizeof(uint32_t)};
+    } else if (occ) back[nback++] = {occ, 0, 1};
     CopySet cs;
     auto unstage = [&](size_t k) {
         const size_t b = k % D, first = k * C, m = (first + C <= n) ? C : n - first;
-        const char *ho = (const char *)a->pipe.h_out[b];
-        if (rec16) cs.add((char *)prim + 16 * first, ho, 16 * m);
-        else if (mode == LH_MODE_CLOSEST) {
-            if (t) cs.add(t + first, ho, sizeof(double) * m);
-            if (u) cs.add(u + first, ho + sizeof(double) * CAP, sizeof(double) * m);
-            if (v) cs.add(v + first, ho + 2 * sizeof(double) * CAP, sizeof(double) * m);
-            if (prim) cs.add(prim + first, ho + 3 * sizeof(double) * CAP, sizeof(uint32_t) * m);
-        } else if (occ) cs.add(occ + first, ho, m);
+        for (int o = 0; o < nback; o++) cs.add((char *)back[o].user + back[o].bytes * first, (const char *)a->pipe.h_out[b] + back[o].at, back[o].bytes * m);
     };
     size_t unstaged = 0;              /* chunks [0, unstaged) are back in the caller's arrays */
     static const bool diag = getenv("LH_PIPE_DIAG") != NULL;          /* where the calling thread's time goes: waits / copies / enqueues, ms */
@@ -411,7 +423,7 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const void *org, co
         (void)hipGetLastError();          /* a query that says "not ready" must not be the next launch check's last error */
         char *hi = (char *)a->pipe.h_in[b], *di = (char *)a->pipe.d_in[b], *dout = (char *)a->pipe.d_out[b];
         cs.add(hi, (const char *)org + RB * first, RB * m);
-        cs.add(hi + RB * CAP, (const char *)dir + RB * first, RB * m);
+        cs.add(hi + at.dir, (const char *)dir + RB * first, RB * m);
         cs.run();
         double c2 = diag ? now() : 0; t_copy += c2 - c1;
         /* the rays go up on a stream of their own; trace + records down alternate between two more: chunk k + 1's rays cross the link while
@@ -423,22 +435,16 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const void *org, co
         if (m == CAP) HIPCHK(hipMemcpyAsync(di, hi, 2 * RB * CAP, hipMemcpyHostToDevice, s_in));
         else {
             HIPCHK(hipMemcpyAsync(di, hi, RB * m, hipMemcpyHostToDevice, s_in));
-            HIPCHK(hipMemcpyAsync(di + RB * CAP, hi + RB * CAP, RB * m, hipMemcpyHostToDevice, s_in));
+            HIPCHK(hipMemcpyAsync(di + at.dir, hi + at.dir, RB * m, hipMemcpyHostToDevice, s_in));
         }
         HIPCHK(hipEventRecord(a->pipe.in_done[b], s_in));
         HIPCHK(hipStreamWaitEvent(s_tr, a->pipe.in_done[b], 0));
-        double *d_t = (double *)dout, *d_u = d_t + CAP, *d_v = d_u + CAP; uint32_t *d_prim = (uint32_t *)(d_v + CAP);
-        const int rc = rec16 ? lh_launch(a, m, di, di + RB * CAP, dout, NULL, NULL, NULL, NULL, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, lh_launch_opt{io_fmt})
-                             : lh_launch(a, m, di, di + RB * CAP, d_prim, d_t, d_u, d_v, (uint8_t *)dout, mode, LH_VARIANT_DEFAULT, NULL, s_tr, true, lh_launch_opt{io_fmt});
+        const lh_batch_t chunk = rec16 ? lh_batch_t{m, mode, di, di + at.dir, dout, NULL, NULL, NULL, NULL, NULL}
+                                       : lh_batch_t{m, mode, di, di + at.dir, dout + at.prim, dout + at.t, dout + at.u, dout + at.v, dout, NULL};
+        const int rc = lh_launch(a, chunk, LH_VARIANT_DEFAULT, s_tr, true, lh_launch_opt{io_fmt});
         if (rc != 0) return rc;
         char *ho = (char *)a->pipe.h_out[b];
-        if (rec16) HIPCHK(hipMemcpyAsync(ho, dout, 16 * m, hipMemcpyDeviceToHost, s_tr));
-        else if (mode == LH_MODE_CLOSEST) {
-            if (t) HIPCHK(hipMemcpyAsync(ho, d_t, sizeof(double) * m, hipMemcpyDeviceToHost, s_tr));
-            if (u) HIPCHK(hipMemcpyAsync(ho + sizeof(double) * CAP, d_u, sizeof(double) * m, hipMemcpyDeviceToHost, s_tr));
-            if (v) HIPCHK(hipMemcpyAsync(ho + 2 * sizeof(double) * CAP, d_v, sizeof(double) * m, hipMemcpyDeviceToHost, s_tr));
-            if (prim) HIPCHK(hipMemcpyAsync(ho + 3 * sizeof(double) * CAP, d_prim, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s_tr));
-        } else if (occ) HIPCHK(hipMemcpyAsync(ho, dout, m, hipMemcpyDeviceToHost, s_tr));
+        for (int o = 0; o < nback; o++) HIPCHK(hipMemcpyAsync(ho + back[o].at, dout + back[o].at, back[o].bytes * m, hipMemcpyDeviceToHost, s_tr));
         HIPCHK(hipEventRecord(a->pipe.done[b], s_tr));
         if (diag) t_enq += now() - c2;
     }
@@ -474,24 +480,21 @@ static int intersect_host_fmt(lh_accel_t *a, size_t n, const void *org, const vo
     if (rec16) { d_prim = (uint32_t *)d_t; d_t = d_u = d_v = NULL; }
     HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
     HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
-    if (a->stat_on) HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, a->stream));
-    int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT,
-                    a->stat_on ? a->d_counters : NULL, a->stream, true, lh_launch_opt{io_fmt});
+    if (a->stat_on && counted_begin(a, a->stream) != 0) return -1;
+    int rc = lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL},
+                       LH_VARIANT_DEFAULT, a->stream, true, lh_launch_opt{io_fmt});
     if (rc != 0) return rc;
     if (a->stat_on) {
         /* hits are counted from the device outputs whatever the caller asked to copy back */
-        std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV] = {0}, nh = 0;
+        std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV], nh = 0;
         if (mode == LH_MODE_CLOSEST) {
             hp.resize(w * n); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * w * n, hipMemcpyDeviceToHost, a->stream));
         } else {
             ho.resize(n); HIPCHK(hipMemcpyAsync(ho.data(), d_occ, n, hipMemcpyDeviceToHost, a->stream));
         }
-        if (a->hs->bvh.ntris) HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost, a->stream));
-        HIPCHK(hipStreamSynchronize(a->stream));
+        if (counted_collect(a, a->stream, h) != 0) return -1;          /* an empty scene's batch leaves them zero */
         for (size_t i = 0; i < n; i++) nh += (mode == LH_MODE_CLOSEST) ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
-        a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT];
-        a->stat[3] += n; a->stat[4] += nh;
-        a->last_retraced = h[LH_CNT_RETRACED];          /* a counted launch, as lh_accel_intersect_device_counted's */
+        stat_add(a, h, n, nh);
     }
     if (rec16) HIPCHK(hipMemcpyAsync(prim, d_prim, 16 * n, hipMemcpyDeviceToHost, a->stream));
     else if (mode == LH_MODE_CLOSEST) {
@@ -510,10 +513,8 @@ extern "C" int lh_accel_intersect_host(lh_accel_t *a, size_t n, const double *or
                                        uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode)
 {
     lh_guard guard(a);
-    if (!a || !a->committed) return fail("intersect: accel not committed");
-    if (n == 0) return 0;
-    if (!org || !dir) return fail("intersect: NULL ray arrays");
-    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect: unknown mode %d", mode);
+    const int go = batch_args(a, "intersect", n, org && dir, "ray arrays", mode);
+    if (go <= 0) return go;
     return intersect_host_fmt(a, n, org, dir, prim, t, u, v, occ, mode, 0u);
 }
 
@@ -540,9 +541,8 @@ extern "C" int lh_accel_intersect_host_ex(lh_accel_t *a, size_t n, const void *o
     lh_guard guard(a);
     const int io = ex_formats("lh_accel_intersect_host_ex", n, ray_format, record_format, mode, prim_or_rec16, t, u, v);
     if (io < 0) return -1;
-    if (!a || !a->committed) return fail("intersect: accel not committed");
-    if (n == 0) return 0;
-    if (!org || !dir) return fail("intersect: NULL ray arrays");
+    const int go = batch_args(a, "intersect", n, org && dir, "ray arrays", mode);
+    if (go <= 0) return go;
     return intersect_host_fmt(a, n, org, dir, (uint32_t *)prim_or_rec16, t, u, v, occ, mode, (uint32_t)io);
 }
 
@@ -552,7 +552,7 @@ extern "C" int lh_accel_intersect_device_ex(lh_accel_t *a, size_t n, const void 
     lh_guard guard(a);
     const int io = ex_formats("lh_accel_intersect_device_ex", n, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
     if (io < 0) return -1;
-    return lh_launch(a, n, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, (hipStream_t)stream, true, lh_launch_opt{(uint32_t)io});
+    return lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, NULL}, LH_VARIANT_DEFAULT, (hipStream_t)stream, true, lh_launch_opt{(uint32_t)io});
 }
 
 /* rays listed by ids: the records of the listed rays go to THEIR slots, every other slot stays as it is (lucille_hip.h) */
@@ -567,23 +567,20 @@ extern "C" int lh_accel_intersect_device_indexed(lh_accel_t *a, size_t n_rays, c
     if (n_index > ((size_t)1 << 30)) return fail("%s: a list holds 2^30 entries at most (%zu given)", what, n_index);
     if (n_rays > 0xFFFFFFFFull) return fail("%s: ray ids are 32 bits wide: 2^32 - 1 rays at most (%zu given)", what, n_rays);
     if ((((uintptr_t)d_index | (uintptr_t)d_count) & 3u) != 0) return fail("%s: the list and its count are 32-bit words: a pointer is not 4-byte aligned", what);
-    if (!a || !a->committed) return fail("intersect: accel not committed");
-    if (n_index == 0 || n_rays == 0) return 0;
+    const int go = batch_args(a, "intersect", (n_index && n_rays) ? n_index : 0, d_org && d_dir, "ray arrays", mode);
+    if (go <= 0) return go;
     lh_launch_opt opt;
     opt.io_fmt = (uint32_t)io; opt.indexed = true; opt.index = (const uint32_t *)d_index; opt.idx_nrays = (uint32_t)n_rays;
     opt.n_dev = (const uint32_t *)d_count;
     hipStream_t s = (hipStream_t)stream;
-    if (!a->stat_on)
-        return lh_launch(a, n_index, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, NULL, s, true, opt);
+    const lh_batch_t b = {n_index, mode, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL};
     /* statistics: the counting kernels, and one read-back -- how many rays the launch traced is known on the device alone */
-    HIPCHK(hipSetDevice(a->device));
-    HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
-    if (lh_launch(a, n_index, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_DEFAULT, a->d_counters, s, true, opt) != 0) return -1;
+    if (a->stat_on) { HIPCHK(hipSetDevice(a->device)); if (counted_begin(a, s) != 0) return -1; }
+    if (lh_launch(a, b, LH_VARIANT_DEFAULT, s, true, opt) != 0) return -1;
+    if (!a->stat_on) return 0;
     unsigned long long h[LH_CNT_DEV];
-    HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT]; a->stat[3] += h[LH_CNT_RAYS];
-    a->last_retraced = h[LH_CNT_RETRACED];
+    if (counted_collect(a, s, h) != 0) return -1;
+    stat_add(a, h, h[LH_CNT_RAYS], 0);          /* hits are not counted: the records stay on the device */
     return 0;
 }
 
@@ -679,8 +676,8 @@ static int comb_run(lh_accel_t *a, lh_combiner *c, int b, int n)
 {
     lh_guard guard(a);                       /* the accelerator's device state: one launch at a time */
     HIPCHK(hipSetDevice(a->device));
-    if (lh_launch(a, (size_t)n, c->d_org[b], c->d_dir[b], c->d_prim[b], c->d_t[b], c->d_u[b], c->d_v[b], NULL, LH_MODE_CLOSEST,
-                  LH_VARIANT_DEFAULT, NULL, c->stream, true) != 0) return -1;
+    if (lh_launch(a, lh_batch_t{(size_t)n, LH_MODE_CLOSEST, c->d_org[b], c->d_dir[b], c->d_prim[b], c->d_t[b], c->d_u[b], c->d_v[b], NULL, NULL},
+                  LH_VARIANT_DEFAULT, c->stream, true) != 0) return -1;
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
 }
@@ -830,9 +827,8 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
                                             double *t, double *u, double *v, uint32_t *diag)
 {
     lh_guard guard(a);
-    if (!a || !a->committed) return fail("intersect_diag: accel not committed");
-    if (n == 0) return 0;
-    if (!org || !dir || !diag) return fail("intersect_diag: NULL argument");
+    const int go = batch_args(a, "intersect_diag", n, org && dir && diag, "argument", LH_MODE_CLOSEST);
+    if (go <= 0) return go;
     if (n > 0x7fffffffull) return fail("intersect_diag: more than 2^31 rays");
     HIPCHK(hipSetDevice(a->device));
     if (a->hs->bvh.ntris == 0) {
@@ -849,9 +845,9 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
     uint32_t *d_prim = (uint32_t *)(d_v + n), *d_diag = d_prim + n;
     HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
     HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
-    if (a->stat_on) HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long) * LH_CNT_DEV, a->stream));
+    if (a->stat_on && counted_begin(a, a->stream) != 0) return -1;
     lh_launch_opt opt; opt.diag_out = d_diag;
-    const int rc = lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, NULL, LH_MODE_CLOSEST, LH_VARIANT_SPEC, a->stat_on ? a->d_counters : NULL, a->stream, true, opt);
+    const int rc = lh_launch(a, lh_batch_t{n, LH_MODE_CLOSEST, d_org, d_dir, d_prim, d_t, d_u, d_v, NULL, a->stat_on ? a->d_counters : NULL}, LH_VARIANT_SPEC, a->stream, true, opt);
     if (rc != 0) return rc;
     HIPCHK(hipMemcpyAsync(diag, d_diag, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, a->stream));
     std::vector<uint32_t> hp;
@@ -859,14 +855,14 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
     if (t) HIPCHK(hipMemcpyAsync(t, d_t, b_d, hipMemcpyDeviceToHost, a->stream));
     if (u) HIPCHK(hipMemcpyAsync(u, d_u, b_d, hipMemcpyDeviceToHost, a->stream));
     if (v) HIPCHK(hipMemcpyAsync(v, d_v, b_d, hipMemcpyDeviceToHost, a->stream));
-    unsigned long long h[LH_CNT_N] = {0, 0, 0, 0};
+    unsigned long long h[LH_CNT_N] = {0, 0, 0, 0};          /* the totals alone, read with the records: a diagnostic batch does not report retraced rays (counted_collect) */
     if (a->stat_on) HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost, a->stream));
     HIPCHK(hipStreamSynchronize(a->stream));
     if (prim) memcpy(prim, hp.data(), sizeof(uint32_t) * n);
     if (a->stat_on) {
         unsigned long long nh = 0;
         for (size_t i = 0; i < n; i++) nh += hp[i] != LH_MISS_PRIM;
-        a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT]; a->stat[3] += n; a->stat[4] += nh;
+        stat_add(a, h, n, nh);
     }
     return 0;
 }
@@ -876,10 +872,8 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
 extern "C" int lh_accel_intersect_diag_device(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, int mode, void *d_diag, void *stream)
 {
     lh_guard guard(a);
-    if (!a || !a->committed) return fail("intersect_diag_device: accel not committed");
-    if (n == 0) return 0;
-    if (!d_org || !d_dir || !d_diag) return fail("intersect_diag_device: NULL argument");
-    if (mode != LH_MODE_CLOSEST && mode != LH_MODE_ANY) return fail("intersect_diag_device: unknown mode %d", mode);
+    const int go = batch_args(a, "intersect_diag_device", n, d_org && d_dir && d_diag, "argument", mode);
+    if (go <= 0) return go;
     if (n > 0x7fffffffull) return fail("intersect_diag_device: more than 2^31 rays");
     HIPCHK(hipSetDevice(a->device));
     hipStream_t s = (hipStream_t)stream;
@@ -889,7 +883,7 @@ extern "C" int lh_accel_intersect_diag_device(lh_accel_t *a, size_t n, const voi
     double *d_t = (double *)a->d_stage, *d_u = d_t + n, *d_v = d_u + n;
     uint32_t *d_prim = (uint32_t *)(d_v + n); uint8_t *d_occ = (uint8_t *)(d_prim + n);
     lh_launch_opt opt; opt.diag_out = (uint32_t *)d_diag;
-    return lh_launch(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, mode, LH_VARIANT_SPEC, NULL, s, true, opt);
+    return lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, NULL}, LH_VARIANT_SPEC, s, true, opt);
 }
 
 /* ------------------------------------------------------------------------ */

@@ -79,8 +79,8 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         return fail("primary ray kernel launch failed");
     if (stage_timing) HIPCHK(hipEventRecord(ev[1], s));
     /* 2. closest hit */
-    if (lh_launch(a, S, a->r_org.p, a->r_dir.p, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, LH_MODE_CLOSEST,
-               LH_VARIANT_DEFAULT, cnt, s, false, opt) != 0) return -1;
+    if (lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, a->r_org.p, a->r_dir.p, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt},
+                  LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
     if (stage_timing) { HIPCHK(hipEventRecord(ev[2], s)); opt.diag_clock = (unsigned long long *)a->r_diag.p + 3 * nwaves; }
     /* 3. compaction (deterministic: hits in sample order).  The fused AO stage does not need the total on the host: its buffers are
      * sized for the worst case (every sample hits) and its kernels read the count where the compaction left it -- a batch costs ONE
@@ -135,7 +135,7 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;
         if (!late_count && big && nhit * (unsigned long long)N >= (1ull << 27)) sc.ray_budget = big;
         const int rc_ao = lh_launch_trace_ao(&sc, nslots, ntheta, nphi, seed, (const double *)a->r_hitrec.p, (const unsigned long long *)a->r_key.p,
-                               (unsigned int *)a->r_occcount.p, cnt, (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR)), a->grid_blocks,
+                               (unsigned int *)a->r_occcount.p, cnt, lh_next_cursor(a), a->grid_blocks,
                                a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, late_count ? d_nhit : NULL, late_count ? big : 0u, (void *)s);
         if (rc_ao != 0) return fail("fused AO launch failed: %s", hipGetErrorString(hipGetLastError()));
         if (!late_count) {
@@ -157,8 +157,8 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
                 return fail("AO ray kernel launch failed");
             /* 5. any-hit */
             if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));   /* the abandoned fused pass is not counted (nor are the camera rays then) */
-            if (lh_launch(a, nao_m, a->r_aorg.p, a->r_adir.p, NULL, NULL, NULL, NULL, a->r_occ.p, LH_MODE_ANY,
-                       LH_VARIANT_DEFAULT, cnt, s, false, opt) != 0) return -1;
+            if (lh_launch(a, lh_batch_t{nao_m, LH_MODE_ANY, a->r_aorg.p, a->r_adir.p, NULL, NULL, NULL, NULL, a->r_occ.p, cnt},
+                          LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
         }
         return 0;
     };
@@ -499,7 +499,7 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
     int rc = 0;
     for (int depth = 0; depth < nbounce && rc == 0; depth++) {
         lh_launch_opt opt; opt.n_dev = counts + depth; opt.cam_src = depth == 0 ? d_cam : NULL;
-        rc = lh_launch(a, S, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, LH_MODE_CLOSEST, LH_VARIANT_SPEC, cnt, s, false, opt);
+        rc = lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt}, LH_VARIANT_SPEC, s, false, opt);
         if (rc != 0) break;
         if (lh_pt_launch_shade(S, &a->dev, (const double *)a->d_nrm9, (const double *)a->d_attr9[0], (const uint32_t *)a->d_prim_mesh,
                                a->d_materials, override_mat, env_rgb, d_env_map, env_w, env_h, (flags & LH_PT_REFERENCE_WEIGHTS) != 0,

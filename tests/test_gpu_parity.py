@@ -111,6 +111,32 @@ def test_empty_scene_and_empty_batch():
     assert (acc3.intersect_host(org, dr)[0] == la.MISS).all()
 
 
+@pytest.mark.parametrize("case", ["closest", "any", "counted"])
+def test_empty_scene_fills_every_slot(case):
+    """an empty accelerator answers a dense device batch without a walk: every slot of arrays that held something else becomes a
+    miss -- 300 rays: more than one 256-thread block and not a multiple of it.  A counted batch reports its rays and nothing else"""
+    import torch
+    n = 300
+    acc = la.HipAccel(0); acc.commit()
+    o, d = torch_rays(*random_rays(np.random.default_rng(5), n))
+    if case == "any":
+        out = (torch.full((n,), 0x55, dtype=torch.uint8, device="cuda"),)
+        got = acc.intersect_device(o, d, out=out, mode=la.MODE_ANY)
+        torch.cuda.synchronize()
+        assert got[0] is out[0] and (out[0].cpu().numpy() == 0).all()
+    else:
+        out = (torch.full((n,), 7, dtype=torch.int32, device="cuda"),) + tuple(torch.full((n,), 0.25, dtype=torch.float64, device="cuda") for _ in range(3))
+        got = acc.intersect_device(o, d, out=out, counters=case == "counted")
+        if case == "counted":
+            got, cnt = got
+            assert (cnt["nodes"], cnt["tris"], cnt["exact"], cnt["rays"]) == (0, 0, 0, n)
+        torch.cuda.synchronize()
+        assert all(g is x for g, x in zip(got, out))
+        prim, t, u, v = (x.cpu().numpy() for x in out)
+        assert (prim.view(np.uint32) == la.MISS).all() and (t == 1.0e38).all() and (u == 0).all() and (v == 0).all()
+    acc.close()
+
+
 def test_host_batch_and_single_ray_entry_points():
     """lh_accel_intersect_host / lh_accel_intersect1 == accel_intersect_func semantics"""
     P, idx, org, dr = po.soup(3000, 2000, 0.05, 41)

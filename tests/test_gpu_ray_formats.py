@@ -208,6 +208,21 @@ def test_empty_scene_rec16():
     acc.close()
 
 
+def test_empty_scene_rec16_fills_every_slot():
+    """300 records that held something else (more than one 256-thread block, not a multiple of it): all of them become the miss record"""
+    import torch
+    n = 300
+    acc = la.HipAccel(0); acc.commit()
+    o = torch.zeros((n, 3), dtype=torch.float64, device="cuda"); d = torch.ones((n, 3), dtype=torch.float64, device="cuda")
+    rec = torch.full((n, 4), 0x3F000007, dtype=torch.int32, device="cuda")
+    got = acc.intersect_device(o, d, out=(rec,), records="rec16")
+    torch.cuda.synchronize()
+    assert got[0] is rec
+    exp = pack16_np(np.full(n, po.MISS, np.uint32), np.full(n, 1e38), np.zeros(n), np.zeros(n))
+    assert_rec_equal(rec.cpu().numpy().view(np.uint32), exp, "empty scene, pre-filled records")
+    acc.close()
+
+
 def big_batch(n, seed=45):
     P, idx, _, _ = po.soup(20000, 10, 0.01, seed)
     rng = np.random.default_rng(seed)
