@@ -91,6 +91,40 @@ int  lh_accel_commit(lh_accel_t *accel, int build_threads);
  * below; an automatic device build that cannot be done (memory, a degenerate tree) is redone on the host. */
 #define LH_BUILD_ON_HOST (-3)
 #define LH_AUTO_DEVICE_TRIANGLES 1000000ull
+/* ---- meshes that live on the device: lh_accel_add_mesh for vertices a kernel produced (a deformation, a simulation step, a
+ * tessellation, any torch tensor), with no copy to the host, no host flatten and no upload in front of the build.
+ * d_positions / d_indices are device memory of the accelerator's device (hipMalloc; a CUDA torch tensor): npositions vertices of
+ * 3 doubles (LH_POS_F64; stride_bytes >= 24 and a multiple of 8: 32 for ri_vector_t) or 3 floats (LH_POS_F32; stride_bytes >= 12
+ * and a multiple of 4), and nindices uint32_t triangle corners.  An fp32 vertex IS the fp64 vertex (double)x, (double)y, (double)z:
+ * trees, hit records and frames are bit-equal to those of a host mesh holding the widened values.
+ *   - Primitive ids as for lh_accel_add_mesh: meshes in add order, mesh g's triangle i = first_prim[g] + i; the trailing nindices % 3
+ *     indices are ignored; a zero-area triangle keeps its id.  lh_accel_prim_lookup answers from the triangle counts alone.
+ *   - The arrays are read by copies enqueued on `stream` (hipStream_t as void*; NULL = the default stream) before the call returns:
+ *     the library keeps its own device copy, so the caller may overwrite or free them in stream order afterwards.  lh_accel_commit
+ *     waits for those copies through an event per caller stream (no device-wide synchronise).
+ *   - lh_accel_commit accepts build_threads == 0 or LH_BUILD_ON_DEVICE and always takes the device path: ONE kernel flattens every
+ *     mesh straight into the fp64 triangle records, then both device builders run as for LH_BUILD_ON_DEVICE.  No host copy of the
+ *     triangles is made and there is no background host thread; LH_BUILD=host and LH_REF_BUILD=host in the environment do not apply
+ *     to these accelerators.  The one exception: a scene whose trees the device builders cannot make (an LBVH deeper than the walks'
+ *     stacks: exponentially spaced geometry) has its flattened triangles copied to the host once and both trees built there -- what
+ *     commits from host arrays commits from device arrays.
+ *   - Found on the device, reported by lh_accel_commit (-1; the accelerator is then in the failed-commit state, create a new one):
+ *     an index >= npositions ("index I out of range (npositions N)": detected before it addresses anything) and a NaN / infinite /
+ *     > 1e30 coordinate of a REFERENCED vertex (lh_accel_commit's message; an unreferenced vertex may hold anything).
+ *   - An empty scene (no meshes, or only empty ones) commits to the always-miss accelerator.
+ * Refused, -1 with lh_last_error holding the quoted words, nothing enqueued, nothing changed: "unknown position format"; "bad
+ * stride"; "positions not aligned" (to 8 / 4 bytes); "indices not 4-byte aligned"; "NULL array" (with a non-zero count); "not a
+ * device pointer" (what hipPointerGetAttributes does not report as device memory of the accelerator's device -- host memory, another
+ * device's: asked, never dereferenced; "extends past its allocation" where the runtime knows the range); "2^29 triangles" (the
+ * scene's total); "already committed"; "cannot be mixed" (lh_accel_add_mesh and lh_accel_add_mesh_device on one accelerator, in
+ * either order).  On an accelerator with "device meshes" -- each message says so -- also: lh_accel_set_normals and
+ * lh_accel_set_attribute (per-vertex normals and attributes from device arrays are not taken: the hit epilogue and the AO pipeline
+ * use the geometric normal, as for a host mesh without normals), lh_accel_commit with LH_BUILD_ON_HOST or a thread count,
+ * lh_accel_export, lh_accel_commit_replica / lh_multi_commit from it, lh_dist_broadcast_scene from it. */
+#define LH_POS_F64 0      /* 3 doubles per vertex at stride_bytes (>= 24, multiple of 8; 32 for ri_vector_t)   */
+#define LH_POS_F32 1      /* 3 floats per vertex at stride_bytes (>= 12, multiple of 4); vertex = (double)float */
+int  lh_accel_add_mesh_device(lh_accel_t *accel, uint32_t npositions, const void *d_positions, int position_format,
+                              size_t stride_bytes, uint32_t nindices, const void *d_indices /* uint32_t */, void *stream);
 int  lh_accel_wait_exact(lh_accel_t *accel);
 /* lucille's own tree as the kernels read it, for inspection (tests compare the device-built tree with the host-built one):
  * *nnodes nodes of 128 bytes (lh_refbvh.h: two child boxes of 6 doubles, child[2], axis, is_leaf, first, count, parent, depth;

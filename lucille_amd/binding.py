@@ -22,6 +22,7 @@ VARIANT_DEFAULT, VARIANT_DIRECT, VARIANT_SPEC = -1, 0, 4      # the tuned walk (
 RAYS_F64, RAYS_F32 = 0, 1           # ray formats of the _ex batch entry points (include/lucille_hip.h)
 REC_F64, REC16 = 0, 1               # record formats: SoA prim / t / u / v, or 16-byte records {prim u32, t, u, v f32}
 SELECT_HIT, SELECT_MISS, SELECT_OCCLUDED, SELECT_UNOCCLUDED = 0, 1, 2, 3      # what compact() keeps (LH_SELECT_*)
+POS_F64, POS_F32 = 0, 1             # vertex formats of HipAccel.add_mesh_device (LH_POS_*)
 
 
 class LucilleHipError(RuntimeError):
@@ -106,7 +107,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 
 # every symbol include/lucille_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
-    "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
+    "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
     "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
@@ -146,6 +147,7 @@ def lib():
     L.lh_last_error.restype = C.c_char_p
     L.lh_accel_create.argtypes = [C.POINTER(vp), i32]
     L.lh_accel_add_mesh.argtypes = [vp, u32, vp, sz, u32, vp]
+    L.lh_accel_add_mesh_device.argtypes = [vp, u32, vp, i32, sz, u32, vp, vp]
     L.lh_accel_commit.argtypes = [vp, i32]
     L.lh_accel_wait_exact.argtypes = [vp]
     L.lh_accel_ref_tree.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp]
@@ -370,6 +372,36 @@ class HipAccel:
         _check(self.L.lh_accel_add_mesh(self.h, P.shape[0], P.ctypes.data, P.shape[1] * 8, I.shape[0],
                                         I.ctypes.data), "lh_accel_add_mesh")
         self._npos.append(P.shape[0])
+
+    def add_mesh_device(self, positions, indices, stream=None):
+        """lh_accel_add_mesh_device: a mesh whose arrays live on the accelerator's device.  positions: a CUDA tensor (n, 3), or a
+        strided view (n, >= 3) whose rows are the vertices (element stride 1 along a row; the byte stride between rows is taken
+        from the tensor), float64 or float32 -- a float32 vertex is the float64 vertex it widens to; indices: a contiguous CUDA
+        int32 tensor (its bits are read as uint32; uint32 where torch has it), three per triangle.  The arrays are read by copies
+        enqueued on `stream` (a torch.cuda.Stream, a raw stream handle, or None: torch's current stream) before this returns:
+        they may be overwritten or freed in stream order afterwards.  commit() then flattens and builds on the device."""
+        import torch
+        P, I = positions, indices
+        if not (isinstance(P, torch.Tensor) and isinstance(I, torch.Tensor) and P.is_cuda and I.is_cuda):
+            raise ValueError("add_mesh_device: positions and indices must be CUDA torch tensors (host arrays: add_mesh)")
+        if P.device.index != self.device or I.device.index != self.device:
+            raise ValueError("add_mesh_device: the tensors must live on the accelerator's device %d" % self.device)
+        if P.dtype not in (torch.float64, torch.float32):
+            raise ValueError("add_mesh_device: positions must be float64 or float32, not %s" % P.dtype)
+        if P.dim() != 2 or P.shape[1] < 3 or (P.shape[0] > 1 and P.stride(0) < 3) or P.stride(1) != 1:
+            raise ValueError("add_mesh_device: positions must be (n, 3) or a strided view (n, >= 3) with contiguous rows")
+        if I.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not I.is_contiguous():
+            raise ValueError("add_mesh_device: indices must be a contiguous int32 / uint32 tensor")
+        if P.shape[0] >= 1 << 32 or I.numel() >= 1 << 32:
+            raise ValueError("add_mesh_device: vertex and index counts are 32-bit")
+        fmt = POS_F32 if P.dtype == torch.float32 else POS_F64
+        stride = (P.stride(0) if P.shape[0] > 1 else P.shape[1]) * P.element_size()
+        if stream is None:
+            stream = torch.cuda.current_stream(P.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        with torch.cuda.device(P.device):
+            _check(self.L.lh_accel_add_mesh_device(self.h, int(P.shape[0]), _dptr(P) if P.shape[0] else None, fmt, int(stride), int(I.numel()),
+                                                   _dptr(I) if I.numel() else None, C.c_void_p(stream)), "lh_accel_add_mesh_device")
 
     def set_normals(self, mesh, normals, two_side=0):
         N = _np(normals, np.float64) if normals is not None else None

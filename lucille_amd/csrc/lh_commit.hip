@@ -93,6 +93,7 @@ extern "C" int lh_accel_add_mesh(lh_accel_t *a, uint32_t npos, const double *pos
     lh_guard guard(a);
     if (!a) return fail("lh_accel_add_mesh: accel is NULL");
     if (a->committed) return fail("lh_accel_add_mesh: accel already committed");
+    if (a->ndmeshes) return fail("lh_accel_add_mesh: host meshes and device meshes cannot be mixed on one accelerator");
     if ((npos && !pos) || (nidx && !idx)) return fail("lh_accel_add_mesh: NULL array");
     if (stride < 3 * sizeof(double) || (stride % sizeof(double)) != 0) return fail("lh_accel_add_mesh: bad stride %zu", stride);
     for (uint32_t i = 0; i < nidx - (nidx % 3); i++)
@@ -120,6 +121,7 @@ extern "C" int lh_accel_set_normals(lh_accel_t *a, uint32_t mesh, const double *
     lh_guard guard(a);
     if (!a) return fail("lh_accel_set_normals: accel is NULL");
     if (a->committed) return fail("lh_accel_set_normals: accel already committed");
+    if (a->ndmeshes) return fail("lh_accel_set_normals: not available for device meshes (they are shaded with the geometric normal)");
     if (mesh >= a->nmeshes) return fail("lh_accel_set_normals: mesh %u out of range", mesh);
     if (nrm && (stride < 3 * sizeof(double) || (stride % sizeof(double)) != 0)) return fail("lh_accel_set_normals: bad stride");
     lh_mesh_copy *m = &a->meshes[mesh];
@@ -140,6 +142,7 @@ extern "C" int lh_accel_set_attribute(lh_accel_t *a, uint32_t mesh, int kind, co
     lh_guard guard(a);
     if (!a) return fail("lh_accel_set_attribute: accel is NULL");
     if (a->committed) return fail("lh_accel_set_attribute: accel already committed");
+    if (a->ndmeshes) return fail("lh_accel_set_attribute: not available for device meshes");
     if (mesh >= a->nmeshes) return fail("lh_accel_set_attribute: mesh %u out of range", mesh);
     if (kind < LH_ATTR_COLOR || kind > LH_ATTR_TEXCOORD_UNSHARED) return fail("lh_accel_set_attribute: unknown attribute kind %d", kind);
     lh_mesh_copy *m = &a->meshes[mesh];
@@ -157,6 +160,138 @@ extern "C" int lh_accel_set_attribute(lh_accel_t *a, uint32_t mesh, int kind, co
         for (int k = 0; k < ncomp; k++) m->attr[kind][(size_t)ncomp * i + k] = q[k];
     }
     return 0;
+}
+
+/* ---- meshes handed over as device arrays ----------------------------------------------------- */
+static void publish_scene(lh_accel_t *a);
+static void free_dmeshes(lh_accel_t *a)
+{
+    for (uint32_t g = 0; g < a->ndmeshes; g++) if (a->dmeshes[g].block) (void)hipFree(a->dmeshes[g].block);
+    free(a->dmeshes); a->dmeshes = NULL; a->ndmeshes = 0;
+    for (uint32_t k = 0; k < a->ndmesh_events; k++) (void)hipEventDestroy(a->dmesh_events[k].ev);
+    free(a->dmesh_events); a->dmesh_events = NULL; a->ndmesh_events = 0;
+}
+
+/* `bytes` at p are device memory of the accelerator's device, as the runtime knows it: asked, never tried */
+static int device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *what)
+{
+    hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("lh_accel_add_mesh_device: %s is not a device pointer", what); }
+    if (at.type != hipMemoryTypeDevice || at.device != a->device)
+        return fail("lh_accel_add_mesh_device: %s is not a device pointer on device %d (the accelerator's)", what, a->device);
+    void *base = NULL; size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if ((const char *)p + bytes > (const char *)base + size) return fail("lh_accel_add_mesh_device: %s extends past its allocation (%zu bytes needed)", what, bytes);
+    return 0;
+}
+
+extern "C" int lh_accel_add_mesh_device(lh_accel_t *a, uint32_t npos, const void *d_pos, int fmt, size_t stride, uint32_t nidx,
+                                        const void *d_idx, void *stream)
+{
+    lh_guard guard(a);
+    if (!a) return fail("lh_accel_add_mesh_device: accel is NULL");
+    if (a->committed || a->commit_failed) return fail("lh_accel_add_mesh_device: accel already committed");
+    if (a->nmeshes) return fail("lh_accel_add_mesh_device: host meshes and device meshes cannot be mixed on one accelerator");
+    if (fmt != LH_POS_F64 && fmt != LH_POS_F32) return fail("lh_accel_add_mesh_device: unknown position format %d", fmt);
+    const size_t elem = fmt == LH_POS_F32 ? sizeof(float) : sizeof(double);
+    if (stride < 3 * elem || (stride % elem) != 0) return fail("lh_accel_add_mesh_device: bad stride %zu", stride);
+    if ((npos && !d_pos) || (nidx && !d_idx)) return fail("lh_accel_add_mesh_device: NULL array");
+    if (((uintptr_t)d_pos % elem) != 0) return fail("lh_accel_add_mesh_device: positions not aligned to %zu bytes", elem);
+    if (((uintptr_t)d_idx % sizeof(uint32_t)) != 0) return fail("lh_accel_add_mesh_device: indices not 4-byte aligned");
+    const uint32_t ntris = nidx / 3;
+    if (a->dmesh_tris + ntris >= (1ull << 29)) return fail("lh_accel_add_mesh_device: the scene would hold %llu triangles (the limit is 2^29 triangles)", a->dmesh_tris + ntris);
+    if (ntris && npos == 0) return fail("lh_accel_add_mesh_device: index 0 out of range (npositions 0)");         /* every index is: known without reading one */
+    /* what the flatten kernel will read: whole vertices up to the last one's z, whole triangles */
+    const size_t pos_bytes = ntris ? (size_t)(npos - 1) * stride + 3 * elem : 0, idx_bytes = sizeof(uint32_t) * 3 * (size_t)ntris;
+    HIPCHK(hipSetDevice(a->device));
+    if (ntris && (device_array_ok(a, d_pos, pos_bytes, "positions") != 0 || device_array_ok(a, d_idx, idx_bytes, "indices") != 0)) return -1;
+    lh_dmesh *nm = (lh_dmesh *)realloc(a->dmeshes, sizeof(lh_dmesh) * (a->ndmeshes + 1));
+    if (!nm) return fail("out of memory");
+    a->dmeshes = nm;
+    lh_dmesh m; memset(&m, 0, sizeof(m));
+    m.stride = stride; m.npos = npos; m.ntris = ntris; m.fmt = fmt;
+    if (ntris) {
+        hipStream_t s = (hipStream_t)stream;
+        lh_dmesh_event *ev = NULL;
+        for (uint32_t k = 0; k < a->ndmesh_events; k++) if (a->dmesh_events[k].stream == s) ev = &a->dmesh_events[k];
+        if (!ev) {
+            lh_dmesh_event *ne = (lh_dmesh_event *)realloc(a->dmesh_events, sizeof(lh_dmesh_event) * (a->ndmesh_events + 1));
+            if (!ne) return fail("out of memory");
+            a->dmesh_events = ne;
+            HIPCHK(hipEventCreateWithFlags(&ne[a->ndmesh_events].ev, hipEventDisableTiming));
+            ne[a->ndmesh_events].stream = s;
+            ev = &ne[a->ndmesh_events++];
+        }
+        const size_t pos_room = (pos_bytes + 15) & ~(size_t)15;
+        HIPCHK(hipMalloc(&m.block, pos_room + idx_bytes));
+        m.pos = m.block; m.idx = (const uint32_t *)((char *)m.block + pos_room);
+        /* the library's own copy, in the caller's stream order: the caller's arrays are free again once these two have run */
+        if (hipMemcpyAsync(m.block, d_pos, pos_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync((char *)m.block + pos_room, d_idx, idx_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipEventRecord(ev->ev, s) != hipSuccess) {
+            const char *why = hipGetErrorString(hipGetLastError());
+            (void)hipStreamSynchronize(s); (void)hipFree(m.block);
+            return fail("lh_accel_add_mesh_device: copying the mesh failed: %s", why);
+        }
+    }
+    a->dmeshes[a->ndmeshes++] = m;
+    a->dmesh_tris += ntris;
+    return 0;
+}
+
+/* 1 if the accelerator holds, or was committed from, device meshes (lh_multi.hip asks) */
+extern "C" int lh_accel_device_meshes(const lh_accel_t *a) { return a && (a->ndmeshes || a->hs->device_meshes) ? 1 : 0; }
+
+/* running triangle counts of the staged device meshes: first[g] = primitive id of mesh g's triangle 0, first[n] = all */
+static uint32_t *dmesh_first_prim(const lh_accel_t *a)
+{
+    uint32_t *first = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)a->ndmeshes + 1));
+    if (!first) return NULL;
+    first[0] = 0;
+    for (uint32_t g = 0; g < a->ndmeshes; g++) first[g + 1] = first[g] + a->dmeshes[g].ntris;
+    return first;
+}
+
+/* lh_accel_prim_lookup's tables (and the materials' mesh ordinals) from the triangle counts alone */
+static int dmesh_prim_tables(lh_host_scene *hs, const uint32_t *first, uint32_t nmeshes)
+{
+    const uint32_t n = first[nmeshes];
+    free(hs->bvh.prim_geom); free(hs->bvh.prim_index); hs->bvh.prim_geom = hs->bvh.prim_index = NULL;
+    if (n == 0) return 0;
+    hs->bvh.prim_geom = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n); hs->bvh.prim_index = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n);
+    if (!hs->bvh.prim_geom || !hs->bvh.prim_index) return fail("out of memory");
+    for (uint32_t g = 0; g < nmeshes; g++)
+        for (uint32_t p = first[g]; p < first[g + 1]; p++) { hs->bvh.prim_geom[p] = g; hs->bvh.prim_index[p] = 3 * (p - first[g]); }
+    return 0;
+}
+
+/* the staged device meshes -> a->d_tri64, on the accelerator's stream, behind the copies the adds enqueued (an event per caller
+ * stream; no device-wide synchronise).  Returns once the kernel's status word is back: an index out of range fails the commit */
+static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first)
+{
+    const uint32_t nm = a->ndmeshes, nt = first[nm];
+    const double t0 = now_s();
+    HIPCHK(hipMalloc(&a->d_tri64, sizeof(lh_tri64_t) * (size_t)nt));
+    publish_scene(a);
+    for (uint32_t k = 0; k < a->ndmesh_events; k++) HIPCHK(hipStreamWaitEvent(a->stream, a->dmesh_events[k].ev, 0));
+    /* one block: the descriptors, the first_prim table, the status words */
+    const size_t desc_bytes = sizeof(lh_dmesh_desc_t) * (size_t)nm, first_bytes = (sizeof(uint32_t) * ((size_t)nm + 1) + 15) & ~(size_t)15;
+    std::vector<char> h(desc_bytes + first_bytes + 16, 0);
+    lh_dmesh_desc_t *hd = (lh_dmesh_desc_t *)h.data();
+    for (uint32_t g = 0; g < nm; g++) { hd[g].pos = a->dmeshes[g].pos; hd[g].idx = a->dmeshes[g].idx; hd[g].stride = a->dmeshes[g].stride; hd[g].npos = a->dmeshes[g].npos; hd[g].fmt = (uint32_t)a->dmeshes[g].fmt; }
+    memcpy(h.data() + desc_bytes, first, sizeof(uint32_t) * ((size_t)nm + 1));
+    char *d_tab = NULL; uint32_t status[4] = {0, 0, 0, 0};
+    HIPCHK(hipMalloc((void **)&d_tab, h.size()));
+    int rc = 0;
+    if (hipMemcpyAsync(d_tab, h.data(), h.size(), hipMemcpyHostToDevice, a->stream) != hipSuccess) rc = fail("lh_accel_commit: uploading the mesh table failed");
+    if (rc == 0) rc = lh_flatten_launch(nt, nm, (const lh_dmesh_desc_t *)d_tab, (const uint32_t *)(d_tab + desc_bytes), a->d_tri64, (uint32_t *)(d_tab + desc_bytes + first_bytes), a->stream);
+    if (rc == 0 && hipMemcpyAsync(status, d_tab + desc_bytes + first_bytes, sizeof(status), hipMemcpyDeviceToHost, a->stream) != hipSuccess) rc = fail("lh_accel_commit: reading the flatten status failed");
+    const hipError_t es = hipStreamSynchronize(a->stream);
+    (void)hipFree(d_tab);
+    if (rc == 0 && es != hipSuccess) rc = fail("lh_accel_commit: flattening the device meshes failed: %s", hipGetErrorString(es));
+    if (rc == 0 && status[0]) rc = fail("lh_accel_commit: mesh %u: index %u out of range (npositions %u)", status[1], status[2], status[3]);
+    if (rc == 0 && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device flatten (%u meshes, %.0f MB) %8.2f ms\n", nm, sizeof(lh_tri64_t) * (double)nt / 1e6, (now_s() - t0) * 1e3);
+    return rc;
 }
 
 void lh_free_buf(lh_buf *b) { if (b->p) (void)hipFree(b->p); b->p = NULL; b->cap = 0; }
@@ -688,7 +823,7 @@ static int device_begin(lh_accel_t *a)
 }
 
 /* ---- device replica of the host scene (once per GPU) ---------------------------------------- */
-static int device_upload(lh_accel_t *a)
+static int device_upload(lh_accel_t *a, const uint32_t *dmesh_first = NULL)
 {
     lh_host_scene *hs = a->hs;
     const double t0 = now_s();
@@ -702,8 +837,9 @@ static int device_upload(lh_accel_t *a)
     if (hs->bvh.ntris) {
         const size_t t64 = sizeof(lh_tri64_t) * nt;
         const double tu = now_s();
-        if (upload_array(a, &a->d_tri64, hs->bvh.tri64, t64) != 0) return -1;
-        if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 upload (%.0f MB)      %8.2f ms\n", t64 / 1e6, (now_s() - tu) * 1e3);
+        if (dmesh_first) { if (flatten_device_meshes(a, dmesh_first) != 0) return -1; }          /* device meshes: the records are made here, nothing crosses the link */
+        else if (upload_array(a, &a->d_tri64, hs->bvh.tri64, t64) != 0) return -1;
+        if (!dmesh_first && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 upload (%.0f MB)      %8.2f ms\n", t64 / 1e6, (now_s() - tu) * 1e3);
         if (hs->device_built) {
             /* the traversal tree is built here, on this device (lh_build.hip): LBVH -> the same 4-wide nodes */
             char berr[256] = "";
@@ -717,7 +853,7 @@ static int device_upload(lh_accel_t *a)
             const int rcb = lh_device_build(hs->bvh.ntris, (const double *)a->d_tri64, &a->d_q4nodes, &nq4, &d4, &st4, want_q8, &a->d_q8nodes, &nq8, &d8, &a->d_tri32, bmin, bmax, glo, gst,
                                             &nlive, &dcap, (void *)a->stream, berr, sizeof(berr));
             if (rcb == -2) return fail("lh_accel_commit: a vertex coordinate is NaN, infinite or beyond 1e30");
-            if (rcb != 0 && a->build_auto && !hs->ref_on_device) {
+            if (rcb != 0 && ((a->build_auto && !hs->ref_on_device) || dmesh_first)) {
                 if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device build failed (%s): host builders\n", berr);
                 return -3;                              /* nobody asked for the device: the caller builds on the host */
             }
@@ -730,7 +866,11 @@ static int device_upload(lh_accel_t *a)
             pthread_mutex_unlock(&g_scene_mu);
             publish_scene(a);
             if (3 * d4 + 5 > 264) return -3;          /* deeper than k_overflow_fix's private stack: the caller falls back to the host builder */
-            if (hs->have_ref && (hs->ref_on_device || hs->ref_state == 1) && device_ref_tree(a) < 0) return -1;
+            if (hs->have_ref && (hs->ref_on_device || hs->ref_state == 1) && device_ref_tree(a) < 0) {
+                if (!dmesh_first) return -1;
+                if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: %s: host builders\n", lh_last_error());
+                return -3;                              /* device meshes: the flattened triangles are copied out and both trees built on the host */
+            }
         } else if (upload_array(a, &a->d_tri32, hs->bvh.tri32, sizeof(lh_tri32_t) * nt, 64) != 0) return -1;
         if (hs->have_ref && __atomic_load_n(&hs->ref_state, __ATOMIC_ACQUIRE) == 2 && attach_ref(a) != 0) return -1;
         /* resident from the start: what the default kernel reads (everything else on first use) */
@@ -742,12 +882,71 @@ static int device_upload(lh_accel_t *a)
     return 0;
 }
 
+/* a device-mesh scene whose trees the device builders could not make (an LBVH deeper than the walks' stacks, memory): the one case
+ * in which its triangles are copied to the host -- once, as flattened by the kernel -- and both trees are built there from that
+ * copy, handed to the host builders as ONE mesh of 3 n vertices with the identity index list; the scene goes on as a host-built one */
+static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm)
+{
+    lh_host_scene *hs = a->hs;
+    const size_t nt = first[nm];
+    double *tri = (double *)malloc(sizeof(lh_tri64_t) * nt);
+    uint32_t *ident = (uint32_t *)malloc(sizeof(uint32_t) * 3 * nt);
+    lh_mesh_copy *mc = (lh_mesh_copy *)calloc(1, sizeof(lh_mesh_copy));
+    if (!tri || !ident || !mc) { free(tri); free(ident); free(mc); return fail("out of memory"); }
+    const double t0 = now_s();
+    const hipError_t e = hipMemcpy(tri, a->d_tri64, sizeof(lh_tri64_t) * nt, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { free(tri); free(ident); free(mc); return fail("lh_accel_commit: copying the flattened triangles to the host failed: %s", hipGetErrorString(e)); }
+    if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 to the host (%.0f MB)   %8.2f ms\n", sizeof(lh_tri64_t) * (double)nt / 1e6, (now_s() - t0) * 1e3);
+    for (size_t i = 0; i < 3 * nt; i++) ident[i] = (uint32_t)i;
+    free_dmeshes(a);
+    release_device(a);
+    lh_bvh_release(&hs->bvh); lh_refbvh_release(&hs->ref); hs->ref_state = 0; hs->ref_on_device = 0;
+    mc->npos = mc->nidx = (uint32_t)(3 * nt); mc->pos = tri; mc->idx = ident;
+    a->meshes = mc; a->nmeshes = 1;
+    if (host_build(a, 0, false, false) != 0) return -1;
+    hs->nmeshes = nm;
+    if (dmesh_prim_tables(hs, first, nm) != 0) return -1;
+    return device_upload(a) == 0 ? 0 : -1;
+}
+
+/* lh_accel_commit of an accelerator that holds device meshes: always the device path, no host copy of the triangles */
+static int commit_device_meshes(lh_accel_t *a)
+{
+    lh_host_scene *hs = a->hs;
+    const double tc0 = now_s();
+    HIPCHK(hipSetDevice(a->device));
+    const uint32_t nm = a->ndmeshes;
+    uint32_t *first = dmesh_first_prim(a);
+    if (!first) return fail("out of memory");
+    memset(&hs->bvh, 0, sizeof(hs->bvh));
+    hs->bvh.deg_dcap = INFINITY; hs->bvh.ntris = hs->bvh.nlive = first[nm];
+    { const char *e = getenv("LH_REFTREE"); hs->have_ref = !(e && atoi(e) == 0); }
+    hs->nmeshes = nm; hs->device_meshes = 1; hs->device_built = 1; hs->ref_state = 0;
+    hs->ref_on_device = 1;                      /* lucille's own tree is built on the device too: there are no host triangles for a host thread */
+    a->build_auto = 0;
+    int rc = dmesh_prim_tables(hs, first, nm);
+    if (rc == 0) rc = device_upload(a, first);
+    if (rc == -3) rc = dmesh_host_fallback(a, first, nm);
+    free(first);
+    free_dmeshes(a);
+    if (rc != 0) return -1;
+    if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device meshes, %.2f ms in all\n", (now_s() - tc0) * 1e3);
+    a->commit_failed = 0;
+    return 0;
+}
+
 extern "C" int lh_accel_commit(lh_accel_t *a, int build_threads)
 {
     lh_guard guard(a);
     if (!a) return fail("lh_accel_commit: accel is NULL");
     if (a->committed) return fail("lh_accel_commit: already committed");
     if (a->commit_failed) return fail("lh_accel_commit: an earlier commit of this accelerator failed; create a new one");
+    if (a->ndmeshes) {
+        if (build_threads != 0 && build_threads != LH_BUILD_ON_DEVICE)
+            return fail("lh_accel_commit: device meshes are built on the device (build_threads must be 0 or LH_BUILD_ON_DEVICE)");
+        a->commit_failed = 1;
+        return commit_device_meshes(a);
+    }
     a->commit_failed = 1;                       /* cleared on success */
     /* where the trees are built: said by the caller (LH_BUILD_ON_DEVICE, LH_BUILD_ON_HOST, or a thread count = the host), by
      * LH_BUILD in the environment, or -- build_threads == 0 -- by the size of the scene: from LH_AUTO_DEVICE_TRIANGLES on the
@@ -835,8 +1034,9 @@ extern "C" int lh_accel_commit_replica(lh_accel_t *dst, lh_accel_t *src)
 {
     if (!dst || !src || !src->committed) return fail("lh_accel_commit_replica: source not committed");
     if (src->hs->received) return fail("lh_accel_commit_replica: the source scene was received from another rank (no host copy to replicate)");
+    if (src->hs->device_meshes) return fail("lh_accel_commit_replica: the source scene was committed from device meshes (no host copy to replicate)");
     lh_guard guard(dst);
-    if (dst->committed || dst->commit_failed || dst->nmeshes) return fail("lh_accel_commit_replica: destination is not a fresh accelerator");
+    if (dst->committed || dst->commit_failed || dst->nmeshes || dst->ndmeshes) return fail("lh_accel_commit_replica: destination is not a fresh accelerator");
     pthread_mutex_lock(&g_scene_mu);
     lh_host_scene *old = dst->hs;
     dst->hs = src->hs; dst->hs->refs++;
@@ -869,6 +1069,7 @@ extern "C" void lh_accel_destroy(lh_accel_t *a)
 {
     if (!a) return;
     if (a->committed || a->commit_failed) { (void)hipSetDevice(a->device); lh_comb_destroy(a); release_device(a); }
+    if (a->ndmeshes || a->ndmesh_events) { (void)hipSetDevice(a->device); free_dmeshes(a); }
     for (uint32_t g = 0; g < a->nmeshes; g++) {
         free(a->meshes[g].pos); free(a->meshes[g].idx); free(a->meshes[g].nrm);
         for (int k = 0; k < 5; k++) free(a->meshes[g].attr[k]);
@@ -952,6 +1153,7 @@ extern "C" int lh_accel_set_param(lh_accel_t *a, const char *name, int value)
 extern "C" int lh_accel_export(const lh_accel_t *a, void *nodes, void *tri32)
 {
     if (!a || !a->committed) return fail("lh_accel_export: accel not committed");
+    if (a->hs->device_meshes) return fail("lh_accel_export: the scene was committed from device meshes; there is no host copy");
     if (a->hs->device_built) return fail("lh_accel_export: the tree was built on the device; there is no host copy");
     if (nodes && a->hs->bvh.nnodes) memcpy(nodes, a->hs->bvh.nodes, sizeof(lh_node_t) * (size_t)a->hs->bvh.nnodes);
     if (tri32 && a->hs->bvh.ntris) memcpy(tri32, a->hs->bvh.tri32, sizeof(lh_tri32_t) * (size_t)a->hs->bvh.ntris);
@@ -968,6 +1170,7 @@ extern "C" int lh_accel_export(const lh_accel_t *a, void *nodes, void *tri32)
 int lh_scene_image_header(lh_accel_t *a, lh_scene_image_t *h)
 {
     if (!a || !a->committed) return fail("scene image: accel not committed");
+    if (a->hs->device_meshes) return fail("scene image: a scene committed from device meshes is not broadcast");
     if (lh_sync_ref(a, true) != 0) return -1;           /* a device-built scene: lucille's own tree must be attached */
     /* a scene whose ray dumps walk the 8-wide nodes (hot set beyond the Infinity Cache) is sent WITH them: rank 0 builds them
      * lazily on its first dump, a receiver has no host tree to build them from and would walk the slower 4-wide nodes --
@@ -1009,7 +1212,7 @@ uint32_t *lh_scene_image_prim_index(lh_accel_t *a) { return a->hs->bvh.prim_inde
 /* a fresh accelerator becomes the receiving end: device arrays allocated as the header says */
 int lh_scene_image_alloc(lh_accel_t *a, const lh_scene_image_t *h)
 {
-    if (!a || a->committed || a->commit_failed || a->nmeshes) return fail("scene image: the receiver must be a fresh accelerator");
+    if (!a || a->committed || a->commit_failed || a->nmeshes || a->ndmeshes) return fail("scene image: the receiver must be a fresh accelerator");
     if (h->magic != 0x4C48494Du) return fail("scene image: bad header");
     lh_guard guard(a);
     lh_host_scene *hs = a->hs;

@@ -37,6 +37,12 @@ int lh_fail(const char *fmt, ...);
 struct lh_mesh_copy { uint32_t npos, nidx; double *pos; uint32_t *idx; double *nrm; int two_side;
                       double *attr[5]; };
 
+/* a mesh handed over as device arrays (lh_accel_add_mesh_device): the library's own device copy of what the flatten kernel reads --
+ * one block, the vertices in the caller's format and stride, then the indices -- and, for the kernel, its descriptor (lh_flatten.hip) */
+struct lh_dmesh { void *block; const void *pos; const uint32_t *idx; size_t stride; uint32_t npos, ntris; int fmt; };
+typedef struct lh_dmesh_desc { const void *pos; const uint32_t *idx; unsigned long long stride; uint32_t npos, fmt; } lh_dmesh_desc_t;
+struct lh_dmesh_event { hipStream_t stream; hipEvent_t ev; };          /* the last copy enqueued on a caller's stream: the commit waits for it */
+
 struct lh_buf { void *p; size_t cap; };
 #define LH_AOQ_SLOTS 4
 #define LH_PIPE_DEPTH_MAX 8   /* staging blocks of a pipelined host batch (lh_query.hip) */
@@ -59,6 +65,7 @@ struct lh_host_scene {
     int device_built;
     int received;             /* the scene arrived as an image from another rank (lh_dist.hip): device arrays only */
     int ref_on_device;        /* lucille's own tree of a device-built scene was built on the device too (lh_refbuild.hip): no host copy */
+    int device_meshes;        /* the scene came from device arrays (lh_accel_add_mesh_device): no host copy of its triangles, one device, no export */
     int ref_state; pthread_t ref_thread; int ref_thread_live; int ref_threads;
     void **trash; uint32_t ntrash;   /* host blocks the device-side commit no longer needs: freed by the background thread (unmapping 0.5 GB takes 0.1 s) */
 };
@@ -70,6 +77,9 @@ struct lh_accel {
     int commit_failed;        /* a commit that failed half-way: device memory is released by destroy, a retry is refused */
     /* staged meshes (host copies, packed xyz) */
     lh_mesh_copy *meshes; uint32_t nmeshes;
+    /* ... or staged device meshes (never both): device copies until the commit has flattened them */
+    lh_dmesh *dmeshes; uint32_t ndmeshes; unsigned long long dmesh_tris;
+    lh_dmesh_event *dmesh_events; uint32_t ndmesh_events;
     lh_host_scene *hs;        /* never NULL after create */
     void *d_ref_lca, *d_prim_leafpos, *d_ref_nodes, *d_ref_leaf_prims;   /* lucille's own tree: owned here, published in dev (lh_commit.hip publish_scene) */
     void *d_danger;                    /* 8 + LH_DANGER_MAX x 6 doubles: the count, then the boxes of lh_dev_scene_t.danger (lh_commit.hip lh_danger_scan) */
@@ -181,6 +191,9 @@ uint32_t *lh_scene_image_prim_geom(lh_accel_t *a);
 uint32_t *lh_scene_image_prim_index(lh_accel_t *a);
 int  lh_scene_image_alloc(lh_accel_t *a, const lh_scene_image_t *h);
 int  lh_scene_image_finish(lh_accel_t *a);
+/* lh_flatten.hip: the staged device meshes -> lh_tri64_t[ntris] in primitive-id order, one launch */
+int  lh_flatten_launch(uint32_t ntris, uint32_t nmeshes, const lh_dmesh_desc_t *d_desc, const uint32_t *d_first, void *d_tri64,
+                       uint32_t *d_status, hipStream_t stream);
 /* lh_hostwalk.c */
 extern "C" int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], uint32_t *prim, double *t, double *u, double *v);
 /* lh_query.hip */

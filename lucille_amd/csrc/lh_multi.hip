@@ -35,6 +35,7 @@
 #include "../../include/lucille_hip.h"
 
 extern "C" int lh_accel_commit_replica(lh_accel_t *dst, lh_accel_t *src);      /* lh_commit.hip */
+extern "C" int lh_accel_device_meshes(const lh_accel_t *a);                     /* lh_commit.hip: holds, or was committed from, device meshes */
 extern "C" void lh_set_error(const char *msg);                                   /* lh_commit.hip: lh_last_error of this thread */
 
 struct lh_multi {
@@ -137,6 +138,7 @@ extern "C" int lh_multi_commit(lh_multi_t *m, int build_threads)
 {
     if (!m) return mfail("lh_multi_commit: NULL");
     if (m->committed) return mfail("lh_multi_commit: already committed");
+    if (lh_accel_device_meshes(m->acc[0])) return mfail("lh_multi_commit: replica 0 holds device meshes (lh_accel_add_mesh_device): lh_multi_* replicates host meshes only");
     if (lh_accel_commit(m->acc[0], build_threads) != 0) return -1;
     std::vector<int> rc((size_t)m->n, 0);
     std::vector<std::string> err((size_t)m->n);

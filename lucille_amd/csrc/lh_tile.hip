@@ -372,7 +372,7 @@ extern "C" int lh_accel_set_material(lh_accel_t *a, uint32_t mesh, const lh_mate
 {
     lh_guard guard(a);
     if (!a || !mat) return fail("lh_accel_set_material: NULL argument");
-    const uint32_t nm = a->committed ? a->hs->nmeshes : a->nmeshes;
+    const uint32_t nm = a->committed ? a->hs->nmeshes : a->nmeshes + a->ndmeshes;          /* host or device meshes, never both */
     if (mesh != LH_ALL_MESHES && mesh >= nm) return fail("lh_accel_set_material: mesh %u out of range", mesh);
     for (int k = 0; k < 3; k++) {
         if (!(mat->kd[k] >= 0.0f && mat->ks[k] >= 0.0f && mat->kt[k] >= 0.0f)) return fail("lh_accel_set_material: negative or NaN reflectance");
