@@ -357,6 +357,58 @@ int  lh_render_ao_tile_host(lh_accel_t *accel, const lh_camera_t *cam, int x0, i
                             int pixel_samples, int gather_nsamples, uint64_t seed, const double *uniforms,
                             size_t nuniforms, float *rgb, lh_tile_stats_t *stats);
 
+/* ---- the AO stage for a caller's batch of hit records: ri_transport_ambientocclusion's occlusion term per hit ----
+ * What lh_render_ao_tile does after its closest-hit launch, for rays that are not camera samples (the second vertex of a path,
+ * texel or vertex positions of a bake, a transport's own rays): d_org_xyz / d_dir_xyz are n_rays fp64 rays as for
+ * lh_accel_intersect_device, d_prim / d_t / d_u / d_v their LH_REC_F64 closest-hit records -- same generator, slot keys, replay
+ * path and fused any-hit kernel as the tile pipeline.
+ *   - N = floor(sqrt(gather_nsamples))^2 AO rays per hit, ntheta = nphi = floor(sqrt(gather_nsamples)) (ambientocclusion.c:378-380).
+ *   - d_index / n_index / d_count: a list as for lh_accel_intersect_device_indexed (ids, the identity list when d_index is NULL, the
+ *     count read on `stream`); all NULL / 0: every ray.  A traced ray is a listed entry within the count whose id is < n_rays; a traced
+ *     ray with prim != LH_MISS is a hit.  Hit slots number the hits in list order (ray order for the identity list): the tile
+ *     pipeline's deterministic compaction.
+ *   - For a hit: P, Ng, Ns (the accelerator's per-vertex normals where the mesh has them; an accelerator of device meshes has none: the
+ *     geometric normal), the ortho basis and the 1e-6 offset as the tile pipeline computes them, the self-primitive skip of a
+ *     flat-shaded non-degenerate hit included.  d_key (n_rays uint64, or NULL: the key of ray i is i): its low 34 bits key the built-in
+ *     generator, as the absolute sample position does in a frame.  d_uniforms (or NULL: the built-in generator): 2 doubles per AO ray
+ *     in (hit slot, j, i) order, the replay path of lh_render_ao_tile; 2 * N * hits of them are consumed.
+ *   - d_occluded_count[id] (uint32, may be NULL) = the occluded rays among the hit's N, under the any-hit semantics of the pipeline;
+ *     d_radiance[id] (float, may be NULL) = (float)(1.0 * (N - count) / N) in double arithmetic.  A traced miss gets LH_AO_NO_HIT and
+ *     0.0f.  The slots of rays that are not traced are not touched, byte for byte.  An id listed twice gets two slots (with uniforms
+ *     it consumes two sets); its output is that ray's answer.
+ *   - Synchronous on `stream` (the outputs are complete on return; one host read-back, for the fix-up queue's overflow flag).  Fused
+ *     (no AO ray in memory) when "ao_fused" is on, no uniforms are given, the scene is not empty and list entries x N < 2^31; else the
+ *     rays are materialised in HBM and traced in any-hit mode -- also the second try of a fused launch whose queue overflowed.  Both
+ *     give the same bytes.
+ *   - An empty scene: every traced ray is a miss, no record array is read.
+ *   - -1 (lh_last_error), nothing enqueued or written: an uncommitted accelerator, a NULL ray or record array with n_rays > 0,
+ *     gather_nsamples < 1, n_rays >= 2^31, n_index > 2^30, a list / count / output pointer that is not 4-byte aligned or a key /
+ *     uniform pointer that is not 8-byte aligned, both outputs NULL.  n_rays == 0 returns 0 and looks at no array.
+ *   - With lh_accel_trace_statistics on it counts as the tile pipelines' AO stage does: `rays` advances by the AO rays traced (hits x N),
+ *     counters[4] by the occluded rays.
+ *   - Its scratch is its own: lh_render_scratch keeps showing the last tile call. */
+#define LH_AO_NO_HIT 0xFFFFFFFFu
+int  lh_accel_ao_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                        const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                        int gather_nsamples, uint64_t seed, const void *d_key, const void *d_uniforms,
+                        const void *d_index, size_t n_index, const void *d_count,
+                        void *d_occluded_count, void *d_radiance, void *stream);
+/* the same for HOST arrays: copies up, runs lh_accel_ao_device on the accelerator's stream, copies down (every ray is traced).
+ * uniforms (may be NULL): nuniforms must cover the worst case 2 * N * n_rays.  occluded_count or radiance may be NULL, not both. */
+int  lh_accel_ao_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,
+                      const double *t, const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
+                      const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance);
+/* only the AO rays -- what stage 4 of the tile pipeline writes -- of every ray of the batch, for a caller who traces them itself:
+ * d_slot_of_ray[i] (n_rays uint32) = the hit slot of ray i, LH_AO_NO_HIT for a miss; *d_nslots (one uint32) = the number of hits;
+ * ray (slot, r) at element slot * N + r of d_ao_org_xyz / d_ao_dir_xyz (fp64 xyz), the first *d_nslots * N elements written.
+ * Asynchronous on `stream`, nothing is read back: capacity_rays (elements of the two ray arrays) must cover the worst case
+ * n_rays * N, else the call is refused and nothing is enqueued.  Refusals as above, and a NULL or misaligned output.  n_rays == 0
+ * writes *d_nslots = 0 and nothing else. */
+int  lh_accel_ao_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                             const void *d_prim, const void *d_t, const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed,
+                             const void *d_key, const void *d_uniforms, void *d_slot_of_ray, void *d_nslots,
+                             void *d_ao_org_xyz, void *d_ao_dir_xyz, size_t capacity_rays, void *stream);
+
 /* one path-traced tile on the device (BASELINE config 4: the reference's pathtrace.c is dead
  * code; its documented structure -- camera sample, Russian roulette on the reflectance,
  * cosine-sampled diffuse bounces to a vertex limit, environment radiance on escape -- re-expressed

@@ -17,7 +17,7 @@ There is no CPU fallback: loading fails loudly when the library is missing and
 every query fails loudly when no HIP device is visible.
 """
 from .binding import (Camera, HipAccel, LucilleHipError, MISS, MODE_ANY, MODE_CLOSEST, RAYS_F64, RAYS_F32, REC_F64, REC16,  # noqa: F401
-                      SELECT_HIT, SELECT_MISS, SELECT_OCCLUDED, SELECT_UNOCCLUDED, compact, POS_F64, POS_F32,
+                      SELECT_HIT, SELECT_MISS, SELECT_OCCLUDED, SELECT_UNOCCLUDED, compact, POS_F64, POS_F32, AO_NO_HIT,
                       VARIANT_DEFAULT, VARIANT_DIRECT,
                       VARIANT_SPEC, build_library, device_count, library_path,
                       HipMulti, HipDist, DIST_RCCL, DIST_SHM, Material, Environment, ALL_MESHES, PT_REFERENCE_WEIGHTS, ATTR_COLOR, ATTR_TANGENT, ATTR_BINORMAL,

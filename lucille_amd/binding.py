@@ -23,6 +23,7 @@ RAYS_F64, RAYS_F32 = 0, 1           # ray formats of the _ex batch entry points 
 REC_F64, REC16 = 0, 1               # record formats: SoA prim / t / u / v, or 16-byte records {prim u32, t, u, v f32}
 SELECT_HIT, SELECT_MISS, SELECT_OCCLUDED, SELECT_UNOCCLUDED = 0, 1, 2, 3      # what compact() keeps (LH_SELECT_*)
 POS_F64, POS_F32 = 0, 1             # vertex formats of HipAccel.add_mesh_device (LH_POS_*)
+AO_NO_HIT = 0xFFFFFFFF               # occluded count of a traced miss, slot of a miss (LH_AO_NO_HIT)
 
 
 class LucilleHipError(RuntimeError):
@@ -116,7 +117,7 @@ ABI_SYMBOLS = [
     "lh_render_ao_frame_host", "lh_rib_load", "lh_rib_free", "lh_rib_last_error", "lh_rib_info", "lh_rib_messages",
     "lh_rib_mesh", "lh_accel_add_rib_scene", "lh_hdr_write",
     "lh_accel_set_material", "lh_accel_set_environment", "lh_render_pt_tile2", "lh_render_pt_bands", "lh_accel_set_attribute",
-    "lh_accel_state_build_device", "lh_accel_state_build_host",
+    "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
     "lh_multi_add_rib_scene", "lh_multi_commit", "lh_multi_set_material", "lh_multi_set_environment", "lh_multi_intersect_host",
     "lh_multi_render_ao_frame_host", "lh_multi_render_pt_frame_host",
@@ -194,6 +195,9 @@ def lib():
     L.lh_accel_set_attribute.argtypes = [vp, u32, i32, vp, sz, u32]
     L.lh_accel_state_build_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, vp]
     L.lh_accel_state_build_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.lh_accel_ao_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, C.c_uint64, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.lh_accel_ao_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, C.c_uint64, vp, vp, sz, vp, vp]
+    L.lh_accel_ao_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp]
     L.lh_multi_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32)]
     L.lh_multi_destroy.argtypes = [vp]; L.lh_multi_destroy.restype = None
     L.lh_multi_ndevices.argtypes = [vp]
@@ -797,6 +801,124 @@ class HipAccel:
         _check(self.L.lh_accel_state_build_host(self.h, o.shape[0], o.ctypes.data, d.ctypes.data, p.ctypes.data, tt.ctypes.data,
                                                 uu.ctypes.data, vv.ctypes.data, st.ctypes.data), "lh_accel_state_build_host")
         return st
+
+    # ---- the AO stage for a caller's batch of hit records -------------------------------
+    @staticmethod
+    def _ao_batch_in(what, org, dr, records, key, uniforms):
+        """the checks ao_device / ao_rays_device make before they call C: (n, prim, t, u, v)"""
+        import torch
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        keys = (torch.int64, getattr(torch, "uint64", torch.int64))
+        for name, x in (("org", org), ("dr", dr)):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [n, 3]" % (what, name))
+        n = int(org.shape[0])
+        if int(dr.shape[0]) != n:
+            raise ValueError("%s: org and dr differ in length" % what)
+        if not isinstance(records, (tuple, list)) or len(records) != 4:
+            raise ValueError("%s: records must be the (prim, t, u, v) tensors of a closest-hit batch" % what)
+        prim, t, u, v = records
+        if not (isinstance(prim, torch.Tensor) and prim.is_cuda and prim.dtype in words and prim.dim() == 1 and prim.shape[0] == n and prim.is_contiguous()):
+            raise ValueError("%s: prim must be a contiguous int32 / uint32 device tensor [n]" % what)
+        for name, x in (("t", t), ("u", u), ("v", v)):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 1 and x.shape[0] == n and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [n]" % (what, name))
+        if key is not None and not (isinstance(key, torch.Tensor) and key.is_cuda and key.dtype in keys and key.dim() == 1 and key.shape[0] == n and key.is_contiguous()):
+            raise ValueError("%s: key must be a contiguous int64 / uint64 device tensor [n]" % what)
+        if uniforms is not None and not (isinstance(uniforms, torch.Tensor) and uniforms.is_cuda and uniforms.dtype == torch.float64 and uniforms.is_contiguous()):
+            raise ValueError("%s: uniforms must be a contiguous float64 device tensor" % what)
+        return n, prim, t, u, v
+
+    def ao_device(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None, index=None, count=None, out=None,
+                  stream=None):
+        """lh_accel_ao_device: the AO stage of render_ao_tile for a batch of rays and their closest-hit records (`records` = the
+        (prim, t, u, v) tensors intersect_device returned for org / dr, float64 rays).  N = floor(sqrt(gather_nsamples))^2 AO rays
+        per hit.  key: int64 / uint64 device tensor [n] whose low 34 bits key the built-in generator (None: ray i has key i);
+        uniforms: float64 device tensor, 2 per AO ray in (hit slot, j, i) order -- the replay path (None: the built-in generator);
+        index / count: a device list as for intersect_device (only the listed rays are traced, no other slot of `out` is written).
+        Returns (count, radiance): an int32 tensor [n] whose bits are uint32 -- the occluded rays of the hit, AO_NO_HIT for a miss --
+        and the float32 tensor [n] of (N - count) / N (0 for a miss).  out: such a pair to fill (either member may be None, not
+        both); with out=None both are allocated with torch.empty and the slots of rays that are not listed are UNSPECIFIED.
+        Synchronous: the outputs are complete on return."""
+        import torch
+        what = "ao_device"
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
+        dev = org.device
+        ip, ni, cp = _list_args(index, count, what)
+        if index is None and count is not None:
+            ni = n
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
+            raise ValueError("%s: out must be a (count, radiance) pair, at least one of them a tensor" % what)
+        oc, orad = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if oc is not None and not (oc.is_cuda and oc.dtype in words and oc.dim() == 1 and oc.shape[0] == n and oc.is_contiguous()):
+            raise ValueError("%s: the count output must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 1 and orad.shape[0] == n and orad.is_contiguous()):
+            raise ValueError("%s: the radiance output must be a contiguous float32 device tensor [n]" % what)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_ao_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
+                                         int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad), C.c_void_p(stream)),
+               "lh_accel_ao_device")
+        return out
+
+    def ao_rays_device(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None, out=None, stream=None):
+        """lh_accel_ao_rays_device: only the AO rays of the batch's hits, for a caller who traces them itself.  Returns
+        (slot_of_ray int32 [n] -- the hit slot of every ray, AO_NO_HIT (as uint32 bits) for a miss; nslots -- one-element int32
+        tensor, the number of hits; ao_org, ao_dir -- float64 [n * N, 3], ray (slot, r) at row slot * N + r, the first
+        nslots * N rows written).  Everything stays on the device and nothing is read back; out: such a 4-tuple to fill."""
+        import torch
+        what = "ao_rays_device"
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
+        dev = org.device
+        if int(gather_nsamples) < 1:
+            raise ValueError("%s: gather_nsamples must be at least 1" % what)
+        N = int(int(gather_nsamples) ** 0.5) ** 2
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+                   torch.empty((n * N, 3), dtype=torch.float64, device=dev), torch.empty((n * N, 3), dtype=torch.float64, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise ValueError("%s: out must be (slot_of_ray, nslots, ao_org, ao_dir)" % what)
+        so, ns, ao, ad = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
+            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
+            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
+        for name, x in (("ao_org", ao), ("ao_dir", ad)):
+            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
+        cap = min(int(ao.shape[0]), int(ad.shape[0]))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_ao_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
+                                              int(seed), _dptr(key), _dptr(uniforms), _dptr(so), _dptr(ns), _dptr(ao), _dptr(ad), cap,
+                                              C.c_void_p(stream)), "lh_accel_ao_rays_device")
+        return out
+
+    def ao_host(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None):
+        """lh_accel_ao_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v)) -> (count uint32 [n], radiance float32 [n])"""
+        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
+        if d.shape[0] != n or len(records) != 4:
+            raise ValueError("ao_host: org, dr and the (prim, t, u, v) records must describe the same rays")
+        p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
+        u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
+        if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
+            raise ValueError("ao_host: org, dr and the (prim, t, u, v) records must describe the same rays")
+        k = None if key is None else _np(key, np.uint64).reshape(-1)
+        if k is not None and k.shape[0] != n:
+            raise ValueError("ao_host: one key per ray")
+        un = None if uniforms is None else _np(uniforms, np.float64).reshape(-1)
+        cnt = np.empty(n, np.uint32); rad = np.empty(n, np.float32)
+        _check(self.L.lh_accel_ao_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                       int(gather_nsamples), int(seed), None if k is None else k.ctypes.data,
+                                       None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,
+                                       rad.ctypes.data), "lh_accel_ao_host")
+        return cnt, rad
 
     def scratch(self, which, dtype, width):
         """view (copy to host) of a scratch buffer of the last render_ao_tile call"""

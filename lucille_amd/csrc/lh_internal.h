@@ -124,6 +124,10 @@ struct lh_accel {
     void *h_read;                      /* 1 KiB of pinned host memory: the read-backs at the end of an AO batch (occlusion totals, hit count, queue flags) */
     /* tile-render scratch (lh_render_ao_tile) */
     lh_buf r_org, r_dir, r_prim, r_t, r_u, r_v, r_slot, r_hitrec, r_aorg, r_adir, r_occ, r_blocks, r_key, r_frame, r_occcount;
+    /* scratch of the AO stage for a caller's batch (lh_accel_ao_device / _ao_rays_device / _ao_host), apart from the tile's so that
+     * lh_render_scratch keeps showing the last tile call: slot of every list entry, hit records, slot keys, per-slot counts, the
+     * materialised rays and their any-hit bytes, block counts, the totals (hits; 64 occlusion counters), lh_accel_ao_host's staging */
+    lh_buf b_slot, b_hitrec, b_key, b_occcount, b_aorg, b_adir, b_occ, b_blocks, b_tot, b_host;
     uint64_t last_retraced;            /* rays the last counted launch finished outside the main kernel */
     int ao_fused;                      /* AO rays generated inside the any-hit kernel (default); 0: materialised in HBM */
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */

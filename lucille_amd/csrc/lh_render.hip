@@ -147,6 +147,47 @@ __global__ void k_scan_blocks(uint32_t nblocks, uint32_t *__restrict__ block_cou
 
 struct DevNormals { const double *nrm; };   /* 9 doubles per prim (n0 n1 n2), NaN n0.x => none */
 
+/* the hit epilogue of one AO slot, written once for k_ao_setup (a Region's samples) and k_ao_batch_setup (a caller's batch): the
+ * 12-double hit record of `slot` for ray i of the arrays, and the self-primitive bits of the slot's key (its low 34 bits are the caller's) */
+__device__ __forceinline__ void ao_hit_epilogue(const void *tri64, const double *nrm9,
+                                                const double *org, const double *dir,
+                                                const uint32_t *prim, const double *t,
+                                                const double *u, const double *v, size_t i,
+                                                double *hitrec, unsigned long long *slot_key, uint32_t slot)
+{
+    LH_NC
+    /* ri_intersection_state_build (intersection_state.c:99-248): P, Ng, Ns */
+    const uint32_t p = prim[i];
+    const double *tv = (const double *)tri64 + 9 * (size_t)p;
+    const double tt = t[i], uu = u[i], vv = v[i];
+    double P[3], Ng[3], Ns[3], v01[3], v02[3];
+    for (int k = 0; k < 3; k++) P[k] = org[3 * i + k] + dir[3 * i + k] * tt;
+    for (int k = 0; k < 3; k++) { v01[k] = tv[3 + k] - tv[k]; v02[k] = tv[6 + k] - tv[k]; }
+    vcross(Ng, v01, v02); vnormalize(Ng);
+    bool has_n = false;
+    if (nrm9) { const double n0x = nrm9[9 * (size_t)p]; has_n = (n0x == n0x); }
+    if (has_n) {
+        const double *nn = nrm9 + 9 * (size_t)p; const double w = 1.0 - uu - vv;
+        for (int k = 0; k < 3; k++) { const double a = nn[k] * w, b = nn[3 + k] * uu, c = nn[6 + k] * vv; Ns[k] = (a + b) + c; }
+    } else {
+        Ns[0] = Ng[0]; Ns[1] = Ng[1]; Ns[2] = Ng[2];
+    }
+    /* flat-shaded: the origin triangle cannot occlude its own AO rays (lh_ao.h) -- unless it is degenerate (Ng = 0) */
+    const bool noself = !has_n && (Ng[0] != 0.0 || Ng[1] != 0.0 || Ng[2] != 0.0);
+    slot_key[slot] |= (unsigned long long)(noself ? p : LH_SLOT_NOSELF) << LH_SLOTKEY_BITS;
+    /* ri_ortho_basis(basis, Ns) (reflection.c:311-333) and the 1e-6 offset (ambientocclusion.c:65-73) */
+    double b0[3], b1[3] = {0.0, 0.0, 0.0};
+    int ax = 3;
+    for (int k = 0; k < 3; k++) if (Ns[k] < 0.6 && Ns[k] > -0.6) { ax = k; break; }
+    if (ax >= 3) ax = 0;
+    b1[ax] = 1.0;
+    vcross(b0, b1, Ns); vnormalize(b0);
+    vcross(b1, Ns, b0); vnormalize(b1);
+    double *r = hitrec + 12 * (size_t)slot;
+    const double eps = 1.0e-6;
+    for (int k = 0; k < 3; k++) { r[k] = P[k] + Ns[k] * eps; r[3 + k] = b0[k]; r[6 + k] = b1[k]; r[9 + k] = Ns[k]; }
+}
+
 /* one thread per primary sample: slot = exclusive scan of the hit flags; writes the
  * per-hit record {org(3), basis(9)} (12 doubles) and slot_of_sample */
 __global__ void k_ao_setup(size_t n, const lh_dev_scene_t sc, const double *__restrict__ nrm9,
@@ -180,36 +221,7 @@ __global__ void k_ao_setup(size_t n, const lh_dev_scene_t sc, const double *__re
         slot_key[slot] = (py * (unsigned long long)full_width + px) * (unsigned long long)spp + (i32 - ipix * (uint32_t)spp);      /* < 2^34: checked by the caller */
     }
 
-    /* ri_intersection_state_build (intersection_state.c:99-248): P, Ng, Ns */
-    const uint32_t p = prim[i];
-    const double *tv = (const double *)sc.tri64 + 9 * (size_t)p;
-    const double tt = t[i], uu = u[i], vv = v[i];
-    double P[3], Ng[3], Ns[3], v01[3], v02[3];
-    for (int k = 0; k < 3; k++) P[k] = org[3 * i + k] + dir[3 * i + k] * tt;
-    for (int k = 0; k < 3; k++) { v01[k] = tv[3 + k] - tv[k]; v02[k] = tv[6 + k] - tv[k]; }
-    vcross(Ng, v01, v02); vnormalize(Ng);
-    bool has_n = false;
-    if (nrm9) { const double n0x = nrm9[9 * (size_t)p]; has_n = (n0x == n0x); }
-    if (has_n) {
-        const double *nn = nrm9 + 9 * (size_t)p; const double w = 1.0 - uu - vv;
-        for (int k = 0; k < 3; k++) { const double a = nn[k] * w, b = nn[3 + k] * uu, c = nn[6 + k] * vv; Ns[k] = (a + b) + c; }
-    } else {
-        Ns[0] = Ng[0]; Ns[1] = Ng[1]; Ns[2] = Ng[2];
-    }
-    /* flat-shaded: the origin triangle cannot occlude its own AO rays (lh_ao.h) -- unless it is degenerate (Ng = 0) */
-    const bool noself = !has_n && (Ng[0] != 0.0 || Ng[1] != 0.0 || Ng[2] != 0.0);
-    slot_key[slot] |= (unsigned long long)(noself ? p : LH_SLOT_NOSELF) << LH_SLOTKEY_BITS;
-    /* ri_ortho_basis(basis, Ns) (reflection.c:311-333) and the 1e-6 offset (ambientocclusion.c:65-73) */
-    double b0[3], b1[3] = {0.0, 0.0, 0.0};
-    int ax = 3;
-    for (int k = 0; k < 3; k++) if (Ns[k] < 0.6 && Ns[k] > -0.6) { ax = k; break; }
-    if (ax >= 3) ax = 0;
-    b1[ax] = 1.0;
-    vcross(b0, b1, Ns); vnormalize(b0);
-    vcross(b1, Ns, b0); vnormalize(b1);
-    double *r = hitrec + 12 * (size_t)slot;
-    const double eps = 1.0e-6;
-    for (int k = 0; k < 3; k++) { r[k] = P[k] + Ns[k] * eps; r[3 + k] = b0[k]; r[6 + k] = b1[k]; r[9 + k] = Ns[k]; }
+    ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, i, hitrec, slot_key, slot);
 }
 
 /* counter-based uniforms in [0,1) with 32-bit resolution (like randomMT2's y*2^-32): lh_ao.h */
@@ -219,12 +231,11 @@ __device__ __forceinline__ uint32_t mix32(uint64_t x) { return lh_mix32(x); }
  * rnd != NULL: the caller's uniforms (2 per ray), fp64 throughout -- the parity replay of the reference's
  * MT19937 stream.  rnd == NULL: the built-in generator of lh_ao.h -- bit for bit the rays the any-hit kernel
  * generates in its refill when the tile runs fused (this kernel is then only used to show them). */
-__global__ void k_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long long seed,
-                          const double *__restrict__ hitrec, const double *__restrict__ rnd /* 2 per ray or NULL */,
-                          const unsigned long long *__restrict__ slot_key, double *__restrict__ org, double *__restrict__ dir)
+__device__ __forceinline__ void ao_ray_item(size_t id, size_t nslots, int ntheta, int nphi, unsigned long long seed,
+                                            const double *__restrict__ hitrec, const double *__restrict__ rnd /* 2 per ray or NULL */,
+                                            const unsigned long long *__restrict__ slot_key, double *__restrict__ org, double *__restrict__ dir)
 {
     LH_NC
-    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int N = ntheta * nphi;
     if (id >= nslots * (size_t)N) return;
     const size_t slot = id / N; const int r = (int)(id % N);
@@ -248,6 +259,22 @@ __global__ void k_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long lon
         org[3 * id + k] = h[k];
         dir[3 * id + k] = d0 * h[3 + k] + d1 * h[6 + k] + d2 * h[9 + k];
     }
+}
+
+__global__ void k_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long long seed,
+                          const double *__restrict__ hitrec, const double *__restrict__ rnd,
+                          const unsigned long long *__restrict__ slot_key, double *__restrict__ org, double *__restrict__ dir)
+{
+    ao_ray_item((size_t)blockIdx.x * blockDim.x + threadIdx.x, nslots, ntheta, nphi, seed, hitrec, rnd, slot_key, org, dir);
+}
+
+/* the same rays for a slot count that lives on the device (lh_accel_ao_rays_device reads nothing back): the grid covers the worst
+ * case, the threads beyond *nslots_dev x N leave */
+__global__ void k_ao_rays_counted(const unsigned long long *__restrict__ nslots_dev, int ntheta, int nphi, unsigned long long seed,
+                                  const double *__restrict__ hitrec, const double *__restrict__ rnd,
+                                  const unsigned long long *__restrict__ slot_key, double *__restrict__ org, double *__restrict__ dir)
+{
+    ao_ray_item((size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)*nslots_dev, ntheta, nphi, seed, hitrec, rnd, slot_key, org, dir);
 }
 
 /* one thread per pixel: accumulates its sub-samples exactly like subsample()
@@ -299,6 +326,110 @@ __global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N,
             const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
             if (tot) atomicAdd(occ_total + (blockIdx.x & 63u), (unsigned long long)tot);
         }
+    }
+}
+
+/* ---- the AO stage for a caller's batch of hit records (lh_accel_ao_device / lh_accel_ao_rays_device) ----------------
+ * The samples of a Region become the entries of a list (lh_accel_intersect_device_indexed's: ids in `index` or the identity,
+ * `count` on the device or all n_list of them); entry k is traced when k < min(*count, n_list) and its id < n_rays, and is a
+ * hit when prim[id] != LH_MISS.  Hit slots number the hits in list order: the same ballot / block-scan compaction as above. */
+struct BatchList {
+    const uint32_t *index;      /* n_list ids, or NULL: the identity */
+    const uint32_t *count;      /* entries to trace (clamped to n_list), or NULL: all */
+    uint32_t n_list, n_rays;
+};
+
+/* 32-bit index arithmetic: n_list < 2^31 (checked by the callers) */
+__device__ __forceinline__ bool batch_entry(const BatchList &bl, uint32_t k, uint32_t &id)
+{
+    uint32_t lim = bl.n_list;
+    if (bl.count) { const uint32_t c = *bl.count; if (c < lim) lim = c; }
+    if (k >= lim) return false;
+    id = bl.index ? bl.index[k] : k;
+    return id < bl.n_rays;
+}
+
+__global__ void k_ao_batch_count(const BatchList bl, const uint32_t *__restrict__ prim, uint32_t *__restrict__ block_counts)
+{
+    __shared__ uint32_t wsum[4];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    const bool hit = batch_entry(bl, k, id) && (prim[id] != LH_MISS_PRIM);
+    const unsigned long long m = __ballot(hit);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+/* k_ao_setup for a batch: one thread per list entry; slot_of_entry[k] = the entry's hit slot or LH_AO_NO_HIT, the hit record and
+ * the slot key (the caller's key of the ray -- its id when key is NULL -- in the low 34 bits) through the same epilogue.
+ * nslots_out (or NULL): the number of hits as one uint32, for a caller of lh_accel_ao_rays_device */
+__global__ void k_ao_batch_setup(const BatchList bl, const lh_dev_scene_t sc, const double *__restrict__ nrm9,
+                                 const double *__restrict__ org, const double *__restrict__ dir,
+                                 const uint32_t *__restrict__ prim, const double *__restrict__ t,
+                                 const double *__restrict__ u, const double *__restrict__ v,
+                                 const unsigned long long *__restrict__ key,
+                                 const uint32_t *__restrict__ block_offsets, const unsigned long long *__restrict__ total,
+                                 uint32_t *__restrict__ slot_of_entry, double *__restrict__ hitrec,
+                                 unsigned long long *__restrict__ slot_key, uint32_t *__restrict__ nslots_out)
+{
+    LH_NC
+    __shared__ uint32_t wsum[4];
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (nslots_out && k == 0) *nslots_out = (uint32_t)*total;
+    uint32_t id = 0;
+    const bool hit = batch_entry(bl, k, id) && (prim[id] != LH_MISS_PRIM);
+    const unsigned long long m = __ballot(hit);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) wsum[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t woff = 0;
+    for (int j = 0; j < wv; j++) woff += wsum[j];
+    if (k < bl.n_list) slot_of_entry[k] = LH_AO_NO_HIT;
+    if (!hit) return;
+    const uint32_t slot = block_offsets[blockIdx.x] + woff + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    slot_of_entry[k] = slot;
+    slot_key[slot] = (key ? key[id] : (unsigned long long)id) & LH_SLOTKEY_MASK;
+    ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, (size_t)id, hitrec, slot_key, slot);
+}
+
+/* k_ao_resolve for a batch: one thread per list entry, the slot's occluded rays -> occluded_count[id] / radiance[id] (either may
+ * be NULL); a traced miss gets LH_AO_NO_HIT / 0.  slot_of_entry NULL: an empty scene, every traced ray is a miss.  The batch's occluded
+ * total goes to the 64 counters of occ_total, one atomic per workgroup */
+__global__ void k_ao_batch_resolve(const BatchList bl, int N,
+                                   const uint32_t *__restrict__ slot_of_entry, const uint8_t *__restrict__ occ,
+                                   const unsigned int *__restrict__ occ_count, uint32_t *__restrict__ occluded_count,
+                                   float *__restrict__ radiance, unsigned long long *__restrict__ occ_total)
+{
+    LH_NC
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    unsigned int nocc = 0;
+    if (batch_entry(bl, k, id)) {
+        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
+        uint32_t c = LH_AO_NO_HIT;
+        float rad = 0.0f;
+        if (slot != LH_AO_NO_HIT) {
+            if (occ_count) c = occ_count[slot];            /* fused AO stage: occluded rays were counted per slot */
+            else {
+                const uint8_t *o = occ + (size_t)slot * (size_t)N;
+                c = 0;
+                for (int r = 0; r < N; r++) if (o[r]) c++;
+            }
+            nocc = c;
+            const double ns = (double)(uint32_t)N, occlusion = (double)c;
+            rad = (float)(1.0 * (ns - occlusion) / ns);          /* k_ao_resolve's expression */
+        }
+        if (occluded_count) occluded_count[id] = c;
+        if (radiance) radiance[id] = rad;
+    }
+    __shared__ unsigned int wsum[4];
+    for (int off = 32; off > 0; off >>= 1) nocc += (unsigned int)__shfl_xor((int)nocc, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nocc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (tot) atomicAdd(occ_total + (blockIdx.x & 63u), (unsigned long long)tot);
     }
 }
 
@@ -706,6 +837,19 @@ extern "C" int lh_render_launch_ao_rays(size_t nslots, int ntheta, int nphi, uns
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+/* nslots_max: the bound the arrays were sized for; the kernel reads the count at d_nslots */
+extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigned long long *d_nslots, int ntheta, int nphi,
+                                                unsigned long long seed, const double *d_hitrec, const double *d_rnd,
+                                                const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream)
+{
+    const size_t total = nslots_max * (size_t)(ntheta * nphi), nb = (total + 255) / 256;
+    if (total == 0) return 0;
+    if (nb > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_ao_rays_counted, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream,
+                       d_nslots, ntheta, nphi, seed, d_hitrec, d_rnd, d_slot_key, d_org, d_dir);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
                                         const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
                                         unsigned long long *d_occ_total, void *stream)
@@ -714,6 +858,38 @@ extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int
     if (total == 0) return 0;
     hipLaunchKernelGGL(k_ao_resolve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        w, h, band_rows, xs, ys, N, d_slot_of_sample, d_occ, d_occ_count, d_rgb, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the compaction of a batch's hits (list-aware k_hit_count, k_scan_blocks, k_ao_batch_setup); d_total: the number of hits (64 bits,
+ * where lh_launch_trace_ao reads it); d_nslots32 (or NULL): the same as one uint32 */
+extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
+                                              const uint32_t *d_index, const uint32_t *d_count, const double *d_org, const double *d_dir,
+                                              const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
+                                              const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
+                                              double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
+                                              uint32_t *d_nslots32, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (n_list == 0 || n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return n_list == 0 ? 0 : -1;
+    const unsigned nb = (unsigned)((n_list + 255) / 256);
+    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
+    hipLaunchKernelGGL(k_ao_batch_count, dim3(nb), dim3(256), 0, s, bl, d_prim, d_block_counts);
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, nb, d_block_counts, d_total);
+    hipLaunchKernelGGL(k_ao_batch_setup, dim3(nb), dim3(256), 0, s, bl, *sc, d_nrm9, d_org, d_dir, d_prim, d_t, d_u, d_v, d_key,
+                       d_block_counts, d_total, d_slot_of_entry, d_hitrec, d_slot_key, d_nslots32);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
+                                              const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
+                                              uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream)
+{
+    if (n_list == 0) return 0;
+    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
+    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
+    hipLaunchKernelGGL(k_ao_batch_resolve, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       bl, N, d_slot_of_entry, d_occ, d_occ_count, d_occluded_count, d_radiance, d_occ_total);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -303,6 +303,222 @@ extern "C" int lh_render_ao_tile_host(lh_accel_t *a, const lh_camera_t *cam, int
     return 0;
 }
 
+/* ------------------------------------------------------------------------ */
+/* the AO stage for a caller's batch of hit records (ao_region's stages 3-6)  */
+/* ------------------------------------------------------------------------ */
+extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
+                                              const uint32_t *d_index, const uint32_t *d_count, const double *d_org, const double *d_dir,
+                                              const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
+                                              const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
+                                              double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
+                                              uint32_t *d_nslots32, void *stream);
+extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
+                                              const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
+                                              uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream);
+extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigned long long *d_nslots, int ntheta, int nphi,
+                                                unsigned long long seed, const double *d_hitrec, const double *d_rnd,
+                                                const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
+
+/* what the three entry points refuse before they look at the accelerator's scene; 1: go on, 0: nothing to do (n_rays == 0) */
+static int ao_batch_args(const char *what, const lh_accel_t *a, size_t n_rays, bool have_arrays, int gather_nsamples,
+                         const void *key, const void *uniforms, const void *index, size_t n_index, const void *count,
+                         const void *out32_a, const void *out32_b)
+{
+    if (gather_nsamples < 1) return fail("%s: gather_nsamples must be at least 1 (%d given)", what, gather_nsamples);
+    if (n_rays >= ((size_t)1 << 31)) return fail("%s: 2^31 - 1 rays at most in one batch (%zu given)", what, n_rays);
+    if (n_index > ((size_t)1 << 30)) return fail("%s: a list holds 2^30 entries at most (%zu given)", what, n_index);
+    if ((((uintptr_t)index | (uintptr_t)count) & 3u) != 0) return fail("%s: the list and its count are 32-bit words: a pointer is not 4-byte aligned", what);
+    if ((((uintptr_t)key | (uintptr_t)uniforms) & 7u) != 0) return fail("%s: keys and uniforms are 64-bit words: a pointer is not 8-byte aligned", what);
+    if ((((uintptr_t)out32_a | (uintptr_t)out32_b) & 3u) != 0) return fail("%s: the outputs are 32-bit words: a pointer is not 4-byte aligned", what);
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (n_rays == 0) return 0;
+    if (!have_arrays) return fail("%s: NULL ray or record array", what);
+    return 1;
+}
+
+extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                  const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+                                  const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
+                                  void *d_occluded_count, void *d_radiance, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_ao_device";
+    const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, gather_nsamples, d_key, d_uniforms,
+                                 d_index, n_index, d_count, d_occluded_count, d_radiance);
+    if (go <= 0) return go;
+    if (!d_occluded_count && !d_radiance) return fail("%s: both outputs are NULL", what);
+    const size_t L = (d_index || d_count || n_index) ? n_index : n_rays;          /* list entries; all NULL / 0: every ray */
+    if (L == 0) return 0;
+    HIPCHK(hipSetDevice(a->device));
+    hipStream_t s = (hipStream_t)stream;
+    const int nphi = (int)sqrt((double)gather_nsamples), ntheta = nphi, N = nphi * ntheta;   /* ambientocclusion.c:378-380 */
+    const uint32_t *idx = (const uint32_t *)d_index, *cntp = (const uint32_t *)d_count;
+    if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)a->b_tot.p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
+    if (a->hs->bvh.ntris == 0) {          /* an empty scene: every traced ray is a miss, no record array is read */
+        HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
+        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, N, NULL, NULL, NULL, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s) != 0)
+            return fail("%s: resolve kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    }
+    const unsigned nb = (unsigned)((L + 255) / 256);
+    if (ensure_buf(&a->b_blocks, (size_t)nb * 4) || ensure_buf(&a->b_slot, L * 4) || ensure_buf(&a->b_hitrec, L * 96) ||
+        ensure_buf(&a->b_key, L * 8)) return -1;                     /* worst case: every entry hits */
+    unsigned long long *cnt = a->stat_on ? a->d_counters : NULL;          /* lh_accel_trace_statistics: as the tile pipelines' AO stage */
+    if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+    /* 3. compaction: hits in list order, the count stays on the device */
+    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, L, n_rays, idx, cntp, (const double *)d_org, (const double *)d_dir,
+                                       (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
+                                       (const unsigned long long *)d_key, (uint32_t *)a->b_blocks.p, (uint32_t *)a->b_slot.p,
+                                       (double *)a->b_hitrec.p, (unsigned long long *)a->b_key.p, d_nhit, NULL, s) != 0)
+        return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
+    /* fused: the any-hit kernel makes ray (slot, r) in its refill and reads the slot count where the compaction left it (ao_region's
+     * late count); the grouped order (set_param "ao_group") needs the count on the host: materialised */
+    bool fused = a->ao_fused && !d_uniforms && L * (size_t)N < ((size_t)1 << 31) && !a->dev.ao_group;
+    const bool fused_tried = fused;
+    if (!a->h_read) HIPCHK(hipHostMalloc(&a->h_read, 1024, hipHostMallocDefault));
+    unsigned long long *h_nocc64 = (unsigned long long *)a->h_read, *h_nhit = h_nocc64 + 64; uint32_t *h_qc = (uint32_t *)(h_nocc64 + 65);
+    h_qc[0] = h_qc[1] = 0u; *h_nhit = 0;
+    lh_launch_opt opt;
+    auto materialised = [&](unsigned long long nhit) -> int {
+        const size_t nao = (size_t)nhit * N;
+        if (!nao) return 0;
+        if (ensure_buf(&a->b_aorg, nao * 24) || ensure_buf(&a->b_adir, nao * 24) || ensure_buf(&a->b_occ, nao)) return -1;
+        /* 4. AO rays */
+        if (lh_render_launch_ao_rays((size_t)nhit, ntheta, nphi, seed, (const double *)a->b_hitrec.p, (const double *)d_uniforms,
+                                     (const unsigned long long *)a->b_key.p, (double *)a->b_aorg.p, (double *)a->b_adir.p, s) != 0)
+            return fail("%s: AO ray kernel launch failed", what);
+        /* 5. any-hit */
+        if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));   /* the abandoned fused pass is not counted */
+        return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, a->b_aorg.p, a->b_adir.p, NULL, NULL, NULL, NULL, a->b_occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
+    };
+    auto resolve = [&](bool from_counts) -> int {
+        /* 6. per-ray occlusion, scattered to the rays' own slots */
+        HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
+        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, N, (const uint32_t *)a->b_slot.p, (const uint8_t *)a->b_occ.p,
+                                           from_counts ? (const unsigned int *)a->b_occcount.p : NULL, (uint32_t *)d_occluded_count,
+                                           (float *)d_radiance, d_nocc, s) != 0)
+            return fail("%s: resolve kernel launch failed", what);
+        HIPCHK(hipMemcpyAsync(h_nocc64, d_nocc, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost, s));
+        return 0;
+    };
+    if (fused) {
+        if (ensure_buf(&a->b_occcount, L * sizeof(unsigned int))) return -1;
+        const int qslot = lh_aoq_slot(a, s);
+        if (qslot < 0) return -1;
+        lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget */
+        if (a->ao_budget) sc.ray_budget = a->ao_budget;
+        const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;      /* as ao_region: a launch of 2^27 rays or more */
+        if (lh_launch_trace_ao(&sc, L, ntheta, nphi, seed, (const double *)a->b_hitrec.p, (const unsigned long long *)a->b_key.p,
+                               (unsigned int *)a->b_occcount.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
+                               &a->aoq[qslot].q, a->ncus, d_nhit, big, (void *)s) != 0)
+            return fail("%s: fused AO launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+        if (resolve(true) != 0) return -1;
+        /* the call's one round trip: hit count, occlusion totals, the queue's overflow flag */
+        HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(*h_nhit), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_qc, a->aoq[qslot].q.qcount, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (h_qc[1] != 0) {                           /* more than LH_AO_QCAP uncertain AO rays: the stage once more, materialised */
+            fused = false;
+            if (materialised(*h_nhit) != 0 || resolve(false) != 0) return -1;
+            HIPCHK(hipStreamSynchronize(s));
+        }
+    } else {
+        HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(*h_nhit), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (materialised(*h_nhit) != 0 || resolve(false) != 0) return -1;
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    if (cnt) {
+        unsigned long long hc[LH_CNT_DEV], nocc = 0;
+        for (int k = 0; k < 64; k++) nocc += h_nocc64[k];
+        HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+        a->stat[0] += hc[LH_CNT_NODES]; a->stat[1] += hc[LH_CNT_TRIS]; a->stat[2] += hc[LH_CNT_EXACT];
+        a->stat[3] += hc[LH_CNT_RAYS]; a->stat[4] += nocc;
+        a->stat_slots[0] += hc[LH_CNT_NODE_SLOTS]; a->stat_slots[1] += hc[LH_CNT_TRI_SLOTS]; a->stat_slots[2] += hc[LH_CNT_REGROUP_SLOTS];
+    }
+    return 0;
+}
+
+extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                       const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+                                       const void *d_uniforms, void *d_slot_of_ray, void *d_nslots, void *d_ao_org, void *d_ao_dir,
+                                       size_t capacity_rays, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_ao_rays_device";
+    if ((((uintptr_t)d_ao_org | (uintptr_t)d_ao_dir) & 7u) != 0) return fail("%s: the ray arrays are doubles: a pointer is not 8-byte aligned", what);
+    const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, gather_nsamples, d_key, d_uniforms,
+                                 NULL, 0, NULL, d_slot_of_ray, d_nslots);
+    if (go < 0) return go;
+    hipStream_t s = (hipStream_t)stream;
+    if (go == 0) {
+        if (d_nslots) { HIPCHK(hipSetDevice(a->device)); HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s)); }
+        return 0;
+    }
+    if (!d_slot_of_ray || !d_nslots || !d_ao_org || !d_ao_dir) return fail("%s: NULL output array", what);
+    const int nphi = (int)sqrt((double)gather_nsamples), ntheta = nphi, N = nphi * ntheta;
+    if (capacity_rays / (size_t)N < n_rays || capacity_rays < n_rays * (size_t)N)
+        return fail("%s: capacity_rays %zu does not cover the worst case n_rays * N = %zu x %d", what, capacity_rays, n_rays, N);
+    if ((n_rays * (size_t)N + 255) / 256 > 0x7fffffffu) return fail("%s: more than 2^39 AO rays in one call", what);
+    HIPCHK(hipSetDevice(a->device));
+    if (a->hs->bvh.ntris == 0) {
+        HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
+        HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s));
+        return 0;
+    }
+    const unsigned nb = (unsigned)((n_rays + 255) / 256);
+    if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65) || ensure_buf(&a->b_blocks, (size_t)nb * 4) ||
+        ensure_buf(&a->b_hitrec, n_rays * 96) || ensure_buf(&a->b_key, n_rays * 8)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)a->b_tot.p;
+    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
+                                       (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
+                                       (const unsigned long long *)d_key, (uint32_t *)a->b_blocks.p, (uint32_t *)d_slot_of_ray,
+                                       (double *)a->b_hitrec.p, (unsigned long long *)a->b_key.p, d_nhit, (uint32_t *)d_nslots, s) != 0)
+        return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
+    if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, ntheta, nphi, seed, (const double *)a->b_hitrec.p, (const double *)d_uniforms,
+                                         (const unsigned long long *)a->b_key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
+        return fail("%s: AO ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                                const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
+                                const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_ao_host";
+    const int go = ao_batch_args(what, a, n_rays, org && dir && prim && t && u && v, gather_nsamples, NULL, NULL, NULL, 0, NULL, NULL, NULL);
+    if (go <= 0) return go;
+    if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
+    const size_t n = n_rays;
+    const int nphi = (int)sqrt((double)gather_nsamples);
+    const size_t need = uniforms ? (size_t)2 * nphi * nphi * n : 0;          /* worst case: every ray hits */
+    if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
+    HIPCHK(hipSetDevice(a->device));
+    const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
+    if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 3 * sizeof(uint32_t) * n)) return -1;
+    double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
+    double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
+    uint32_t *d_prim = (uint32_t *)(d_uni + need), *d_cnt = d_prim + n; float *d_rad = (float *)(d_cnt + n);
+    hipStream_t s = a->stream;
+    HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_t, t, b_d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_u, u, b_d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_v, v, b_d, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
+    if (key) HIPCHK(hipMemcpyAsync(d_key, key, b_d, hipMemcpyHostToDevice, s));
+    if (need) HIPCHK(hipMemcpyAsync(d_uni, uniforms, need * sizeof(double), hipMemcpyHostToDevice, s));
+    if (lh_accel_ao_device(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, key ? d_key : NULL, need ? d_uni : NULL,
+                           NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s) != 0) return -1;
+    if (occluded_count) HIPCHK(hipMemcpyAsync(occluded_count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+    if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
 extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t *count)
 {
     lh_guard guard(a);

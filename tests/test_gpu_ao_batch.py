@@ -1,0 +1,369 @@
+"""The AO stage for a caller's batch of hit records (lh_accel_ao_device / lh_accel_ao_rays_device / lh_accel_ao_host).
+
+Pinned, bit for bit, to what the suite already pins: the tile pipeline's own scratch (slots, AO rays, any-hit bytes of a frame
+rendered as one tile), the oracle's answer for the materialised rays, and the fused stage against the materialised one."""
+import numpy as np
+import pytest
+
+import lucille_amd as la
+from lucille_amd import binding
+from oracle import pyoracle as po
+from tests.test_gpu_ao import load_case
+
+pytestmark = pytest.mark.gpu
+
+NO_HIT = la.AO_NO_HIT
+POISON32, POISONF = 0x5A5A5A5A, -12345.678
+
+
+@pytest.fixture(scope="module")
+def c1():
+    return load_case("ao_c1")
+
+
+@pytest.fixture(scope="module")
+def ps():
+    return load_case("ao_ps")
+
+
+def dev(a):
+    import torch
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint32:
+        a = a.view(np.int32)
+    if a.dtype == np.uint64:
+        a = a.view(np.int64)
+    return torch.from_numpy(a).cuda()
+
+
+def host(t, dtype=None):
+    a = t.cpu().numpy()
+    if dtype is not None:
+        a = a.view(dtype)
+    return a
+
+
+def ao(acc, o, d, rec, ns, fused=1, **kw):
+    """ao_device with "ao_fused" set for the call -> (count uint32, radiance float32) on the host"""
+    acc.set_param("ao_fused", fused)
+    try:
+        c, r = acc.ao_device(o, d, rec, ns, **kw)
+    finally:
+        acc.set_param("ao_fused", 1)
+    return host(c, np.uint32).copy(), host(r).copy()
+
+
+def ao_rays(acc, o, d, rec, ns, **kw):
+    """ao_rays_device -> (slot_of_ray uint32, nslots, ao_org, ao_dir) on the host, the rays cut to nslots * N"""
+    import torch
+    so, n, ao_o, ao_d = acc.ao_rays_device(o, d, rec, ns, **kw)
+    torch.cuda.synchronize()
+    nslots = int(host(n, np.uint32)[0]); N = int(np.sqrt(ns)) ** 2
+    return host(so, np.uint32).copy(), nslots, host(ao_o)[:nslots * N].copy(), host(ao_d)[:nslots * N].copy()
+
+
+def expected(slot_of_ray, occ_per_ray, N):
+    """per-ray count / radiance from the per-AO-ray occlusion flags of the hits' slots"""
+    n = slot_of_ray.shape[0]
+    hit = slot_of_ray != NO_HIT
+    sums = occ_per_ray.reshape(-1, N).astype(bool).sum(axis=1).astype(np.uint32)
+    cnt = np.full(n, NO_HIT, np.uint32); cnt[hit] = sums[slot_of_ray[hit]]
+    rad = np.zeros(n, np.float32); rad[hit] = np.float32((N - cnt[hit].astype(np.float64)) / N)
+    return cnt, rad
+
+
+def poison(n):
+    import torch
+    return (torch.full((n,), POISON32, dtype=torch.int32, device="cuda"), torch.full((n,), POISONF, dtype=torch.float32, device="cuda"))
+
+
+# ---- 1. equals the tile pipeline, built-in generator -------------------------------------------------------------------
+@pytest.mark.parametrize("which", ["c1", "ps"])
+def test_equals_the_tile_pipeline_builtin_generator(c1, ps, which):
+    import torch
+    case, pxs = (c1, 1) if which == "c1" else (ps, 2)
+    acc, cam, o = case["acc"], case["cam"], case["oracle"]
+    W, H, NS, N = cam.width, cam.height, 16, 16
+    acc.set_param("ao_fused", 0)
+    try:
+        _, st = acc.render_ao_tile(cam, 0, 0, W, H, pxs, NS, seed=5)
+    finally:
+        acc.set_param("ao_fused", 1)
+    s = {k: acc.scratch(k, dt, w) for k, dt, w in ((0, np.float64, 3), (1, np.float64, 3), (2, np.uint32, 1), (3, np.float64, 1),
+                                                    (4, np.float64, 1), (5, np.float64, 1), (6, np.uint32, 1), (8, np.float64, 3),
+                                                    (9, np.float64, 3), (10, np.uint8, 1))}
+    n = s[0].shape[0]
+    assert n == W * H * pxs * pxs and s[8].shape[0] == st["primary_hits"] * N > 0
+    org, dr = dev(s[0]), dev(s[1])
+    rec = (dev(s[2]), dev(s[3]), dev(s[4]), dev(s[5]))
+    slot, nslots, aorg, adir = ao_rays(acc, org, dr, rec, NS, seed=5)
+    assert np.array_equal(slot, s[6]) and nslots == st["primary_hits"]
+    assert np.array_equal(aorg.view(np.uint64), s[8].view(np.uint64)) and np.array_equal(adir.view(np.uint64), s[9].view(np.uint64))
+    ecnt, erad = expected(s[6], s[10], N)
+    ocnt, _ = expected(s[6], o.intersect(aorg, adir, nthreads=8)[0] != po.MISS, N)
+    assert np.array_equal(ecnt, ocnt)
+    for fused in (1, 0):
+        cnt, rad = ao(acc, org, dr, rec, NS, fused, seed=5)
+        assert np.array_equal(cnt, ecnt), (fused, int((cnt != ecnt).sum()))
+        assert np.array_equal(rad.view(np.uint32), erad.view(np.uint32))
+        assert (cnt[s[2] == po.MISS] == NO_HIT).all() and (rad[s[2] == po.MISS] == 0.0).all()
+    # an explicit identity key is the default; a shifted key makes other rays
+    key = torch.arange(n, dtype=torch.int64, device="cuda")
+    cnt_k, rad_k = ao(acc, org, dr, rec, NS, 1, seed=5, key=key)
+    assert np.array_equal(cnt_k, ecnt) and np.array_equal(rad_k.view(np.uint32), erad.view(np.uint32))
+    _, _, aorg_k, adir_k = ao_rays(acc, org, dr, rec, NS, seed=5, key=key)
+    assert np.array_equal(adir_k.view(np.uint64), s[9].view(np.uint64))
+    _, _, aorg_s, adir_s = ao_rays(acc, org, dr, rec, NS, seed=5, key=key + 12345)
+    assert np.array_equal(aorg_s.view(np.uint64), s[8].view(np.uint64)) and not np.array_equal(adir_s, s[9])
+    # the tile's scratch is still the tile's
+    assert np.array_equal(acc.scratch(6, np.uint32, 1), s[6]) and np.array_equal(acc.scratch(10, np.uint8, 1), s[10])
+    assert np.array_equal(acc.scratch(8, np.float64, 3), s[8])
+
+
+# ---- 2. replay ------------------------------------------------------------------------------------------------------
+def test_replay_with_caller_uniforms(c1):
+    acc, cam = c1["acc"], c1["cam"]
+    W = H = 256; N = NS = 16
+    order = np.zeros(2 * 64, np.uint32)
+    nb = po.lib().lo_bucket_order(W, H, 32, order.ctypes.data_as(po.C.POINTER(po.C.c_uint)))
+    mt = np.empty(2 * N * 1024 + 64); po.lib().lo_mt_stream(4357, mt.size, mt.ctypes.data_as(po._dp))
+    uni_h = mt[:2 * N * 1024].copy(); uni = dev(uni_h)
+    st = None
+    for b in range(nb):                                   # the first bucket of the reference's order that hits anything
+        bx, by = int(order[2 * b]) * 32, int(order[2 * b + 1]) * 32
+        _, st = acc.render_ao_tile(cam, bx, by, 32, 32, 1, NS, uniforms=uni)
+        if st["primary_hits"]:
+            break
+    assert st["primary_hits"] > 0
+    s = {k: acc.scratch(k, dt, w) for k, dt, w in ((0, np.float64, 3), (1, np.float64, 3), (2, np.uint32, 1), (3, np.float64, 1),
+                                                    (4, np.float64, 1), (5, np.float64, 1), (6, np.uint32, 1), (8, np.float64, 3),
+                                                    (9, np.float64, 3), (10, np.uint8, 1))}
+    org, dr = dev(s[0]), dev(s[1]); rec = (dev(s[2]), dev(s[3]), dev(s[4]), dev(s[5]))
+    slot, nslots, aorg, adir = ao_rays(acc, org, dr, rec, NS, uniforms=uni)
+    assert np.array_equal(slot, s[6]) and nslots == st["primary_hits"]
+    assert np.array_equal(aorg.view(np.uint64), s[8].view(np.uint64)) and np.array_equal(adir.view(np.uint64), s[9].view(np.uint64))
+    ecnt, erad = expected(s[6], s[10], N)
+    cnt, rad = ao(acc, org, dr, rec, NS, 1, uniforms=uni)
+    assert np.array_equal(cnt, ecnt) and np.array_equal(rad.view(np.uint32), erad.view(np.uint32))
+    hc, hr = acc.ao_host(s[0], s[1], (s[2], s[3], s[4], s[5]), NS, uniforms=uni_h)
+    assert np.array_equal(hc, ecnt) and np.array_equal(hr.view(np.uint32), erad.view(np.uint32))
+    hc, hr = acc.ao_host(s[0], s[1], (s[2], s[3], s[4], s[5]), NS, seed=9)          # and the built-in generator through the host form
+    dc, drad = ao(acc, org, dr, rec, NS, 1, seed=9)
+    assert np.array_equal(hc, dc) and np.array_equal(hr.view(np.uint32), drad.view(np.uint32))
+
+
+# ---- 3. boundaries of the compaction ----------------------------------------------------------------------------------
+SIZES = (1, 63, 64, 65, 255, 256, 257, 262145)          # the last: more than 1024 blocks of 256, k_scan_blocks' carry path
+
+
+@pytest.fixture(scope="module")
+def soup():
+    """po.soup(3000, n, 0.05, 7) for the largest n: the triangles come first in the generator's stream, so the first n rays are
+    po.soup(3000, n, ...)'s for every smaller n; the closest-hit records of all rays, once"""
+    import torch
+    P, idx, org, dr = po.soup(3000, max(SIZES), 0.05, 7)
+    P2, idx2, org2, dr2 = po.soup(3000, 257, 0.05, 7)
+    assert np.array_equal(P, P2) and np.array_equal(org[:257], org2) and np.array_equal(dr[:257], dr2)
+    acc = la.HipAccel(0); acc.add_mesh(P, idx); acc.commit(); acc.wait_exact()
+    o = po.Oracle(); o.add_mesh(P, idx); o.build()
+    to, td = dev(org), dev(dr)
+    rec = acc.intersect_device(to, td); torch.cuda.synchronize()
+    return {"acc": acc, "oracle": o, "P": P, "idx": idx, "org": to, "dr": td, "rec": rec, "prim": host(rec[0], np.uint32).copy()}
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_compaction_boundaries(soup, n):
+    acc, o = soup["acc"], soup["oracle"]
+    org, dr = soup["org"][:n].contiguous(), soup["dr"][:n].contiguous()
+    rec = tuple(x[:n].contiguous() for x in soup["rec"])
+    hit = soup["prim"][:n] != po.MISS
+    scan = np.full(n, NO_HIT, np.uint32); scan[hit] = (np.cumsum(hit) - hit)[hit].astype(np.uint32)
+    for ns in (1, 3, 4, 16):
+        N = int(np.sqrt(ns)) ** 2
+        slot, nslots, aorg, adir = ao_rays(acc, org, dr, rec, ns, seed=3)
+        assert np.array_equal(slot, scan) and nslots == int(hit.sum())
+        occ = o.intersect(aorg, adir, nthreads=8)[0] != po.MISS if nslots else np.zeros(0, bool)
+        ecnt, erad = expected(scan, occ, N)
+        cf, rf = ao(acc, org, dr, rec, ns, 1, seed=3)
+        cm, rm = ao(acc, org, dr, rec, ns, 0, seed=3)
+        assert np.array_equal(cf, ecnt), (ns, int((cf != ecnt).sum()))
+        assert np.array_equal(cm, cf) and np.array_equal(rf.view(np.uint32), rm.view(np.uint32))
+        assert np.array_equal(rf.view(np.uint32), erad.view(np.uint32))
+
+
+def test_all_miss_batch_and_self_primitive_skip(soup):
+    import torch
+    acc = soup["acc"]
+    n = 300
+    org = torch.full((n, 3), 50.0, dtype=torch.float64, device="cuda"); dr = torch.ones((n, 3), dtype=torch.float64, device="cuda")
+    rec = acc.intersect_device(org, dr); torch.cuda.synchronize()
+    assert (host(rec[0], np.uint32) == po.MISS).all()
+    slot, nslots, _, _ = ao_rays(acc, org, dr, rec, 16)
+    assert nslots == 0 and (slot == NO_HIT).all()
+    for fused in (1, 0):
+        cnt, rad = ao(acc, org, dr, rec, 16, fused)
+        assert (cnt == NO_HIT).all() and (rad == 0.0).all()
+    # one triangle, every ray hits it: flat-shaded, so the triangle cannot occlude its own AO rays
+    one = la.HipAccel(0)
+    one.add_mesh(np.array([[-1.0, -1.0, 0.0], [1.0, -1.0, 0.0], [0.0, 1.0, 0.0]]), np.array([0, 1, 2], np.uint32)); one.commit(); one.wait_exact()
+    rng = np.random.default_rng(1)
+    o_h = np.concatenate([rng.uniform(-0.2, 0.2, (n, 2)), np.full((n, 1), 1.0)], axis=1); d_h = np.tile([0.0, 0.0, -1.0], (n, 1))
+    org, dr = dev(o_h), dev(d_h)
+    rec = one.intersect_device(org, dr); torch.cuda.synchronize()
+    assert (host(rec[0], np.uint32) == 0).all()
+    for fused in (1, 0):
+        cnt, rad = ao(one, org, dr, rec, 16, fused)
+        assert (cnt == 0).all() and (rad == 1.0).all()
+    one.close()
+
+
+# ---- 4. lists -------------------------------------------------------------------------------------------------------
+def test_lists_write_the_listed_slots_alone(soup):
+    import torch
+    acc = soup["acc"]; n = 5000; NS = 16
+    org, dr = soup["org"][:n].contiguous(), soup["dr"][:n].contiguous()
+    rec = tuple(x[:n].contiguous() for x in soup["rec"])
+    hit = soup["prim"][:n] != po.MISS
+    full_c, full_r = ao(acc, org, dr, rec, NS, 1, seed=3)
+
+    def check(index, count, listed, fused):
+        out = poison(n)
+        cnt, rad = ao(acc, org, dr, rec, NS, fused, seed=3, index=index, count=count, out=out)
+        assert np.array_equal(cnt[listed], full_c[listed]) and np.array_equal(rad[listed].view(np.uint32), full_r[listed].view(np.uint32))
+        assert (cnt[~listed] == POISON32).all() and (rad[~listed] == np.float32(POISONF)).all()
+
+    idx, cnt = la.compact(rec[0], la.SELECT_HIT)                      # the hits, count on the device
+    for fused in (1, 0):
+        check(idx, cnt, hit, fused)
+    rng = np.random.default_rng(5)
+    lst = rng.permutation(n)[:1500].astype(np.uint32)
+    lst[7] = lst[3]; lst[11] = n + 9; lst[12] = 0xFFFFFFF0            # a duplicate id, two ids >= n
+    listed = np.zeros(n, bool); listed[lst[lst < n]] = True
+    for fused in (1, 0):
+        check(dev(lst), None, listed, fused)
+    part = np.zeros(n, bool); part[lst[:100][lst[:100] < n]] = True   # the count cuts the list
+    check(dev(lst), torch.tensor([100], dtype=torch.int32, device="cuda"), part, 1)
+    check(None, torch.tensor([77], dtype=torch.int32, device="cuda"), np.arange(n) < 77, 1)      # identity list with a count
+    for fused in (1, 0):                                              # count = 0 on the device: nothing is written
+        check(dev(lst), torch.zeros(1, dtype=torch.int32, device="cuda"), np.zeros(n, bool), fused)
+
+
+# ---- 5. device meshes and the empty scene ---------------------------------------------------------------------------------
+def test_device_mesh_accelerator_and_empty_scene(soup):
+    import torch
+    n = 4000; NS = 16
+    org, dr = soup["org"][:n].contiguous(), soup["dr"][:n].contiguous()
+    rec = tuple(x[:n].contiguous() for x in soup["rec"])
+    ref_c, ref_r = ao(soup["acc"], org, dr, rec, NS, 1, seed=3)
+    dm = la.HipAccel(0)
+    dm.add_mesh_device(dev(soup["P"]), dev(soup["idx"])); dm.commit(); dm.wait_exact()
+    rec_d = dm.intersect_device(org, dr); torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(rec_d, rec))
+    for fused in (1, 0):
+        c, r = ao(dm, org, dr, rec_d, NS, fused, seed=3)
+        assert np.array_equal(c, ref_c) and np.array_equal(r.view(np.uint32), ref_r.view(np.uint32))
+    ref_rays = ao_rays(soup["acc"], org, dr, rec, NS, seed=3); got = ao_rays(dm, org, dr, rec_d, NS, seed=3)
+    assert np.array_equal(got[0], ref_rays[0]) and got[1] == ref_rays[1]
+    assert np.array_equal(got[2].view(np.uint64), ref_rays[2].view(np.uint64)) and np.array_equal(got[3].view(np.uint64), ref_rays[3].view(np.uint64))
+    dm.close()
+    empty = la.HipAccel(0); empty.commit()
+    c, r = ao(empty, org, dr, rec, NS, 1)                             # whatever the records say: nothing is there to hit
+    assert (c == NO_HIT).all() and (r == 0.0).all()
+    slot, nslots, _, _ = ao_rays(empty, org, dr, rec, NS)
+    assert nslots == 0 and (slot == NO_HIT).all()
+    empty.close()
+
+
+# ---- 6. refusals and side effects -----------------------------------------------------------------------------------------
+def test_refusals_leave_everything_untouched(soup):
+    import torch
+    acc, L = soup["acc"], binding.lib()
+    n = 64; N = 16
+    org, dr = soup["org"][:n].contiguous(), soup["dr"][:n].contiguous()
+    prim, t, u, v = (x[:n].contiguous() for x in soup["rec"])
+    cnt, rad = poison(n)
+    key = torch.zeros(n + 1, dtype=torch.int64, device="cuda"); idx = torch.zeros(n, dtype=torch.int32, device="cuda")
+    slot = torch.full((n,), POISON32, dtype=torch.int32, device="cuda"); ns = torch.full((1,), POISON32, dtype=torch.int32, device="cuda")
+    aorg = torch.full((n * N, 3), POISONF, dtype=torch.float64, device="cuda"); adir = aorg.clone()
+    O, D, P, T, U, V = (x.data_ptr() for x in (org, dr, prim, t, u, v))
+    CN, R, K, I = cnt.data_ptr(), rad.data_ptr(), key.data_ptr(), idx.data_ptr()
+    raw = la.HipAccel(0)                                                # never committed
+    cases = [
+        (raw.h, (n, O, D, P, T, U, V, 16, 1, None, None, None, 0, None, CN, R, None), "not committed"),
+        (acc.h, (n, None, D, P, T, U, V, 16, 1, None, None, None, 0, None, CN, R, None), "NULL"),
+        (acc.h, (n, O, D, P, None, U, V, 16, 1, None, None, None, 0, None, CN, R, None), "NULL"),
+        (acc.h, (n, O, D, P, T, U, V, 0, 1, None, None, None, 0, None, CN, R, None), "gather_nsamples"),
+        (acc.h, (1 << 31, O, D, P, T, U, V, 16, 1, None, None, None, 0, None, CN, R, None), "2^31"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, None, (1 << 30) + 1, None, CN, R, None), "2^30"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, I + 2, 8, None, CN, R, None), "4-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, I, 8, I + 1, CN, R, None), "4-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, K + 4, None, None, 0, None, CN, R, None), "8-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, None, 0, None, CN + 2, R, None), "4-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, None, 0, None, CN, R + 2, None), "4-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, None, 0, None, None, None, None), "both outputs"),
+    ]
+    for h, args, msg in cases:
+        rc = L.lh_accel_ao_device(h, *args)
+        err = L.lh_last_error().decode()
+        assert rc == -1 and msg in err and "lh_accel_ao_device" in err, (args, err)
+    S, NSL, AO, AD = slot.data_ptr(), ns.data_ptr(), aorg.data_ptr(), adir.data_ptr()
+    rays_cases = [
+        (raw.h, (n, O, D, P, T, U, V, 16, 1, None, None, S, NSL, AO, AD, n * N, None), "not committed"),
+        (acc.h, (n, O, D, None, T, U, V, 16, 1, None, None, S, NSL, AO, AD, n * N, None), "NULL"),
+        (acc.h, (n, O, D, P, T, U, V, 0, 1, None, None, S, NSL, AO, AD, n * N, None), "gather_nsamples"),
+        (acc.h, (1 << 31, O, D, P, T, U, V, 16, 1, None, None, S, NSL, AO, AD, n * N, None), "2^31"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, K + 4, None, S, NSL, AO, AD, n * N, None), "8-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, S + 2, NSL, AO, AD, n * N, None), "4-byte aligned"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, S, NSL, AO, AD, n * N - 1, None), "capacity_rays"),
+        (acc.h, (n, O, D, P, T, U, V, 16, 1, None, None, S, NSL, None, AD, n * N, None), "NULL"),
+    ]
+    for h, args, msg in rays_cases:
+        rc = L.lh_accel_ao_rays_device(h, *args)
+        err = L.lh_last_error().decode()
+        assert rc == -1 and msg in err and "lh_accel_ao_rays_device" in err, (args, err)
+    hc = np.full(n, POISON32, np.uint32); hr = np.full(n, POISONF, np.float32); z = np.zeros((n, 3)); zp = np.zeros(n, np.uint32); zt = np.zeros(n)
+    for h, args, msg in [
+            (raw.h, (n, z.ctypes.data, z.ctypes.data, zp.ctypes.data, zt.ctypes.data, zt.ctypes.data, zt.ctypes.data, 16, 1, None, None, 0,
+                     hc.ctypes.data, hr.ctypes.data), "not committed"),
+            (acc.h, (n, z.ctypes.data, z.ctypes.data, zp.ctypes.data, zt.ctypes.data, zt.ctypes.data, zt.ctypes.data, 16, 1, None,
+                     zt.ctypes.data, n, hc.ctypes.data, hr.ctypes.data), "uniforms"),
+            (acc.h, (n, z.ctypes.data, z.ctypes.data, zp.ctypes.data, zt.ctypes.data, zt.ctypes.data, zt.ctypes.data, 16, 1, None, None, 0,
+                     None, None), "both outputs")]:
+        rc = L.lh_accel_ao_host(h, *args)
+        err = L.lh_last_error().decode()
+        assert rc == -1 and msg in err and "lh_accel_ao_host" in err, (args, err)
+    torch.cuda.synchronize()
+    assert (host(cnt) == POISON32).all() and (host(rad) == np.float32(POISONF)).all()
+    assert (host(slot) == POISON32).all() and (host(ns) == POISON32).all()
+    assert (host(aorg) == POISONF).all() and (host(adir) == POISONF).all()
+    assert (hc == POISON32).all() and (hr == np.float32(POISONF)).all()
+    # zero rays: 0, no array looked at
+    assert L.lh_accel_ao_device(acc.h, 0, None, None, None, None, None, None, 16, 1, None, None, None, 0, None, None, None, None) == 0
+    # the binding refuses wrong dtypes, shapes and strides before it calls C
+    rec = (prim, t, u, v)
+    for bad in (lambda: acc.ao_device(org.float(), dr, rec, 16), lambda: acc.ao_device(org[:, :2], dr, rec, 16),
+                lambda: acc.ao_device(org, dr, (prim, t[:-1], u, v), 16), lambda: acc.ao_device(org, dr, (prim.long(), t, u, v), 16),
+                lambda: acc.ao_device(soup["org"][:2 * n:2], dr, rec, 16), lambda: acc.ao_device(org, dr, rec, 16, key=key[:n].int()),
+                lambda: acc.ao_device(org, dr, rec, 16, out=(cnt.float(), rad)), lambda: acc.ao_device(org, dr, rec, 16, index=idx.long()),
+                lambda: acc.ao_rays_device(org, dr, rec, 16, out=(slot, ns, aorg.float(), adir))):
+        with pytest.raises(ValueError):
+            bad()
+    raw.close()
+
+
+def test_statistics_count_the_ao_rays(soup):
+    acc = soup["acc"]; n = 3000; NS = 16; N = 16
+    org, dr = soup["org"][:n].contiguous(), soup["dr"][:n].contiguous()
+    rec = tuple(x[:n].contiguous() for x in soup["rec"])
+    nslots = int((soup["prim"][:n] != po.MISS).sum())
+    ref = {f: ao(acc, org, dr, rec, NS, f, seed=3) for f in (1, 0)}
+    acc.trace_statistics(True)
+    try:
+        for fused in (1, 0):
+            acc.statistics(clear=True)
+            cnt, rad = ao(acc, org, dr, rec, NS, fused, seed=3)
+            s = acc.statistics(clear=True)
+            assert np.array_equal(cnt, ref[fused][0]) and np.array_equal(rad, ref[fused][1])
+            assert s["rays"] == nslots * N and s["hits"] == int(cnt[cnt != NO_HIT].sum()) and s["nodes"] > 0
+    finally:
+        acc.trace_statistics(False)
