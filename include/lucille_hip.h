@@ -112,14 +112,18 @@ int  lh_accel_commit(lh_accel_t *accel, int build_threads);
  *     an index >= npositions ("index I out of range (npositions N)": detected before it addresses anything) and a NaN / infinite /
  *     > 1e30 coordinate of a REFERENCED vertex (lh_accel_commit's message; an unreferenced vertex may hold anything).
  *   - An empty scene (no meshes, or only empty ones) commits to the always-miss accelerator.
+ *   - Per-vertex normals, colours, tangents, binormals and texture coordinates come from device arrays too:
+ *     lh_accel_set_normals_device and lh_accel_set_attribute_device (below, beside lh_accel_set_attribute).  The commit gathers them
+ *     into the per-primitive arrays of a host scene with ONE more kernel behind the flatten; a scene that falls back to the host
+ *     builders keeps them (the gathered arrays are copied out with the triangles).
  * Refused, -1 with lh_last_error holding the quoted words, nothing enqueued, nothing changed: "unknown position format"; "bad
  * stride"; "positions not aligned" (to 8 / 4 bytes); "indices not 4-byte aligned"; "NULL array" (with a non-zero count); "not a
  * device pointer" (what hipPointerGetAttributes does not report as device memory of the accelerator's device -- host memory, another
  * device's: asked, never dereferenced; "extends past its allocation" where the runtime knows the range); "2^29 triangles" (the
  * scene's total); "already committed"; "cannot be mixed" (lh_accel_add_mesh and lh_accel_add_mesh_device on one accelerator, in
  * either order).  On an accelerator with "device meshes" -- each message says so -- also: lh_accel_set_normals and
- * lh_accel_set_attribute (per-vertex normals and attributes from device arrays are not taken: the hit epilogue and the AO pipeline
- * use the geometric normal, as for a host mesh without normals), lh_accel_commit with LH_BUILD_ON_HOST or a thread count,
+ * lh_accel_set_attribute (the host-pointer setters: device meshes take lh_accel_set_normals_device and
+ * lh_accel_set_attribute_device), lh_accel_commit with LH_BUILD_ON_HOST or a thread count,
  * lh_accel_export, lh_accel_commit_replica / lh_multi_commit from it, lh_dist_broadcast_scene from it. */
 #define LH_POS_F64 0      /* 3 doubles per vertex at stride_bytes (>= 24, multiple of 8; 32 for ri_vector_t)   */
 #define LH_POS_F32 1      /* 3 floats per vertex at stride_bytes (>= 12, multiple of 4); vertex = (double)float */
@@ -367,8 +371,8 @@ int  lh_render_ao_tile_host(lh_accel_t *accel, const lh_camera_t *cam, int x0, i
  *     count read on `stream`); all NULL / 0: every ray.  A traced ray is a listed entry within the count whose id is < n_rays; a traced
  *     ray with prim != LH_MISS is a hit.  Hit slots number the hits in list order (ray order for the identity list): the tile
  *     pipeline's deterministic compaction.
- *   - For a hit: P, Ng, Ns (the accelerator's per-vertex normals where the mesh has them; an accelerator of device meshes has none: the
- *     geometric normal), the ortho basis and the 1e-6 offset as the tile pipeline computes them, the self-primitive skip of a
+ *   - For a hit: P, Ng, Ns (the accelerator's per-vertex normals where the mesh has them -- lh_accel_set_normals, or
+ *     lh_accel_set_normals_device for device meshes -- else the geometric normal), the ortho basis and the 1e-6 offset as the tile pipeline computes them, the self-primitive skip of a
  *     flat-shaded non-degenerate hit included.  d_key (n_rays uint64, or NULL: the key of ray i is i): its low 34 bits key the built-in
  *     generator, as the absolute sample position does in a frame.  d_uniforms (or NULL: the built-in generator): 2 doubles per AO ray
  *     in (hit slot, j, i) order, the replay path of lh_render_ao_tile; 2 * N * hits of them are consumed.
@@ -466,6 +470,27 @@ int  lh_render_pt_bands(lh_accel_t *accel, const lh_camera_t *cam, int y0_first,
 #define LH_ATTR_TEXCOORD_UNSHARED 4
 #define LH_STATE_DOUBLES 24
 int  lh_accel_set_attribute(lh_accel_t *accel, uint32_t mesh, int kind, const double *data, size_t stride_bytes, uint32_t count);
+/* The same for meshes added with lh_accel_add_mesh_device, before commit; mesh = ordinal in add order.  d_normals / d_data are
+ * device memory of the accelerator's device: 3 components per vertex (normals, colours, tangents, binormals), 2 per vertex
+ * (LH_ATTR_TEXCOORD) or 2 per index (LH_ATTR_TEXCOORD_UNSHARED), as doubles (LH_POS_F64: stride_bytes >= 8 x components and a
+ * multiple of 8, pointer 8-byte aligned) or floats (LH_POS_F32: >= 4 x components, a multiple of 4, 4-byte aligned; a value IS
+ * (double)value).  nnormals / count must equal the mesh's npositions (the unshared kind: the nindices given at the add).
+ *   - d_normals == NULL with nnormals == 0 sets two_side alone; a second call for a mesh and kind replaces the first; d_data ==
+ *     NULL with count == 0 removes it.  Shared texture coordinates win over unshared ones, as on the host.
+ *   - The array is read by a copy enqueued on `stream` before the call returns, into a block the library owns (the caller's format
+ *     and stride): the caller may overwrite or free it in stream order afterwards.  lh_accel_commit waits through the per-stream
+ *     events of the mesh copies (no device-wide synchronise) and gathers every mesh and kind with one kernel into the
+ *     per-primitive arrays the hit epilogue, the AO stage and the path tracer read; a mesh lacking a kind another mesh has is
+ *     "absent" there exactly as on the host path.  Values are not validated (a NaN normal means "no normal").  The blocks are freed
+ *     when the commit returns, however it ends, and by lh_accel_destroy.
+ *   - Refused, -1 with lh_last_error, nothing enqueued, nothing changed: "accel is NULL"; "already committed"; an accelerator that
+ *     holds host meshes or none ("for device meshes": the message names the host form); "mesh M out of range"; "unknown attribute
+ *     kind"; "unknown format"; "bad stride"; "not aligned"; "NULL array" (with a non-zero count); "not a device pointer" /
+ *     "extends past its allocation" (asked of the runtime, never dereferenced); "N values given, the mesh needs M". */
+int  lh_accel_set_normals_device(lh_accel_t *accel, uint32_t mesh, uint32_t nnormals, const void *d_normals,
+                                 int format /* LH_POS_F64 | LH_POS_F32 */, size_t stride_bytes, int two_side, void *stream);
+int  lh_accel_set_attribute_device(lh_accel_t *accel, uint32_t mesh, int kind /* LH_ATTR_* */, uint32_t count,
+                                   const void *d_data, int format, size_t stride_bytes, void *stream);
 int  lh_accel_state_build_device(lh_accel_t *accel, size_t n, const void *d_org_xyz, const void *d_dir_xyz, const void *d_prim,
                                  const void *d_t, const void *d_u, const void *d_v, void *d_state, void *stream);
 int  lh_accel_state_build_host(lh_accel_t *accel, size_t n, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,

@@ -116,7 +116,7 @@ ABI_SYMBOLS = [
     "lh_accel_trace_statistics", "lh_accel_statistics", "lh_accel_slot_statistics",
     "lh_render_ao_frame_host", "lh_rib_load", "lh_rib_free", "lh_rib_last_error", "lh_rib_info", "lh_rib_messages",
     "lh_rib_mesh", "lh_accel_add_rib_scene", "lh_hdr_write",
-    "lh_accel_set_material", "lh_accel_set_environment", "lh_render_pt_tile2", "lh_render_pt_bands", "lh_accel_set_attribute",
+    "lh_accel_set_material", "lh_accel_set_environment", "lh_render_pt_tile2", "lh_render_pt_bands", "lh_accel_set_attribute", "lh_accel_set_normals_device", "lh_accel_set_attribute_device",
     "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
     "lh_multi_add_rib_scene", "lh_multi_commit", "lh_multi_set_material", "lh_multi_set_environment", "lh_multi_intersect_host",
@@ -175,6 +175,8 @@ def lib():
     L.lh_accel_slot_statistics.argtypes = [vp, C.POINTER(C.c_uint64), i32]
     L.lh_accel_export.argtypes = [vp, vp, vp]
     L.lh_accel_set_normals.argtypes = [vp, u32, vp, sz, i32]
+    L.lh_accel_set_normals_device.argtypes = [vp, u32, u32, vp, i32, sz, i32, vp]
+    L.lh_accel_set_attribute_device.argtypes = [vp, u32, i32, u32, vp, i32, sz, vp]
     L.lh_render_primary_rays.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, vp, vp, vp]
     L.lh_render_ao_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, C.c_uint64, vp, vp,
                                     C.POINTER(TileStats), vp]
@@ -418,6 +420,50 @@ class HipAccel:
         _check(self.L.lh_accel_set_normals(self.h, int(mesh), N.ctypes.data if N is not None else None,
                                            (N.shape[1] * 8) if N is not None else 24, int(two_side)),
                "lh_accel_set_normals")
+
+    def _device_rows(self, what, T, ncomp):
+        """the checks set_normals_device / set_attribute_device make before they call C: (count, pointer, format, byte stride)"""
+        import torch
+        if T is None:
+            return 0, None, POS_F64, 8 * ncomp
+        if not (isinstance(T, torch.Tensor) and T.is_cuda):
+            raise ValueError("%s: the array must be a CUDA torch tensor, or None to remove it (host arrays: the host form)" % what)
+        if T.device.index != self.device:
+            raise ValueError("%s: the tensor must live on the accelerator's device %d" % (what, self.device))
+        if T.dtype not in (torch.float64, torch.float32):
+            raise ValueError("%s: the tensor must be float64 or float32, not %s" % (what, T.dtype))
+        if T.dim() != 2 or T.shape[1] < ncomp or (T.shape[0] > 1 and T.stride(0) < ncomp) or T.stride(1) != 1:
+            raise ValueError("%s: the tensor must be (n, %d) or a strided view (n, >= %d) with contiguous rows" % (what, ncomp, ncomp))
+        if T.shape[0] >= 1 << 32:
+            raise ValueError("%s: counts are 32-bit" % what)
+        stride = (T.stride(0) if T.shape[0] > 1 else T.shape[1]) * T.element_size()
+        return int(T.shape[0]), (_dptr(T) if T.shape[0] else None), (POS_F32 if T.dtype == torch.float32 else POS_F64), int(stride)
+
+    def _stream_handle(self, stream):
+        import torch
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        return C.c_void_p(getattr(stream, "cuda_stream", stream))
+
+    def set_normals_device(self, mesh, normals, two_side=0, stream=None):
+        """lh_accel_set_normals_device: per-vertex normals of device mesh `mesh` (add order) from a CUDA tensor (n, 3) or a strided
+        view (n, >= 3) with contiguous rows, float64 or float32, one row per vertex; None removes them and sets two_side alone.
+        Read by a copy enqueued on `stream` (as add_mesh_device) before this returns."""
+        import torch
+        n, ptr, fmt, stride = self._device_rows("set_normals_device", normals, 3)
+        with torch.cuda.device(self.device):
+            _check(self.L.lh_accel_set_normals_device(self.h, int(mesh), n, ptr, fmt, stride, int(two_side), self._stream_handle(stream)),
+                   "lh_accel_set_normals_device")
+
+    def set_attribute_device(self, mesh, kind, data, stream=None):
+        """lh_accel_set_attribute_device: colours, tangents, binormals (3 per vertex), texture coordinates (2 per vertex) or
+        unshared texture coordinates (2 per index) of device mesh `mesh` from a CUDA tensor, as set_normals_device; None removes."""
+        import torch
+        ncomp = 2 if int(kind) in (ATTR_TEXCOORD, ATTR_TEXCOORD_UNSHARED) else 3
+        n, ptr, fmt, stride = self._device_rows("set_attribute_device", data, ncomp)
+        with torch.cuda.device(self.device):
+            _check(self.L.lh_accel_set_attribute_device(self.h, int(mesh), int(kind), n, ptr, fmt, stride, self._stream_handle(stream)),
+                   "lh_accel_set_attribute_device")
 
     def commit(self, build_threads=0, on_device=False, build=None):
         """build: "device" (= on_device: both trees on the GPU, LH_BUILD_ON_DEVICE), "host" (LH_BUILD_ON_HOST; a thread count

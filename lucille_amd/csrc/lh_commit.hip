@@ -121,7 +121,7 @@ extern "C" int lh_accel_set_normals(lh_accel_t *a, uint32_t mesh, const double *
     lh_guard guard(a);
     if (!a) return fail("lh_accel_set_normals: accel is NULL");
     if (a->committed) return fail("lh_accel_set_normals: accel already committed");
-    if (a->ndmeshes) return fail("lh_accel_set_normals: not available for device meshes (they are shaded with the geometric normal)");
+    if (a->ndmeshes) return fail("lh_accel_set_normals: host arrays are not taken for device meshes (lh_accel_set_normals_device takes device arrays)");
     if (mesh >= a->nmeshes) return fail("lh_accel_set_normals: mesh %u out of range", mesh);
     if (nrm && (stride < 3 * sizeof(double) || (stride % sizeof(double)) != 0)) return fail("lh_accel_set_normals: bad stride");
     lh_mesh_copy *m = &a->meshes[mesh];
@@ -142,7 +142,7 @@ extern "C" int lh_accel_set_attribute(lh_accel_t *a, uint32_t mesh, int kind, co
     lh_guard guard(a);
     if (!a) return fail("lh_accel_set_attribute: accel is NULL");
     if (a->committed) return fail("lh_accel_set_attribute: accel already committed");
-    if (a->ndmeshes) return fail("lh_accel_set_attribute: not available for device meshes");
+    if (a->ndmeshes) return fail("lh_accel_set_attribute: host arrays are not taken for device meshes (lh_accel_set_attribute_device takes device arrays)");
     if (mesh >= a->nmeshes) return fail("lh_accel_set_attribute: mesh %u out of range", mesh);
     if (kind < LH_ATTR_COLOR || kind > LH_ATTR_TEXCOORD_UNSHARED) return fail("lh_accel_set_attribute: unknown attribute kind %d", kind);
     lh_mesh_copy *m = &a->meshes[mesh];
@@ -166,23 +166,39 @@ extern "C" int lh_accel_set_attribute(lh_accel_t *a, uint32_t mesh, int kind, co
 static void publish_scene(lh_accel_t *a);
 static void free_dmeshes(lh_accel_t *a)
 {
-    for (uint32_t g = 0; g < a->ndmeshes; g++) if (a->dmeshes[g].block) (void)hipFree(a->dmeshes[g].block);
+    for (uint32_t g = 0; g < a->ndmeshes; g++) {
+        if (a->dmeshes[g].block) (void)hipFree(a->dmeshes[g].block);
+        for (int k = 0; k < LH_DATTR_SLOTS; k++) if (a->dmeshes[g].attr[k].block) (void)hipFree(a->dmeshes[g].attr[k].block);
+    }
     free(a->dmeshes); a->dmeshes = NULL; a->ndmeshes = 0;
     for (uint32_t k = 0; k < a->ndmesh_events; k++) (void)hipEventDestroy(a->dmesh_events[k].ev);
     free(a->dmesh_events); a->dmesh_events = NULL; a->ndmesh_events = 0;
 }
 
 /* `bytes` at p are device memory of the accelerator's device, as the runtime knows it: asked, never tried */
-static int device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *what)
+static int device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *who, const char *what)
 {
     hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("lh_accel_add_mesh_device: %s is not a device pointer", what); }
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("%s: %s is not a device pointer", who, what); }
     if (at.type != hipMemoryTypeDevice || at.device != a->device)
-        return fail("lh_accel_add_mesh_device: %s is not a device pointer on device %d (the accelerator's)", what, a->device);
+        return fail("%s: %s is not a device pointer on device %d (the accelerator's)", who, what, a->device);
     void *base = NULL; size_t size = 0;
     if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if ((const char *)p + bytes > (const char *)base + size) return fail("lh_accel_add_mesh_device: %s extends past its allocation (%zu bytes needed)", what, bytes);
+    if ((const char *)p + bytes > (const char *)base + size) return fail("%s: %s extends past its allocation (%zu bytes needed)", who, what, bytes);
     return 0;
+}
+
+/* the event of caller stream s: recorded behind every copy the library enqueues there, waited for by the commit */
+static lh_dmesh_event *dmesh_event_of(lh_accel_t *a, hipStream_t s)
+{
+    for (uint32_t k = 0; k < a->ndmesh_events; k++) if (a->dmesh_events[k].stream == s) return &a->dmesh_events[k];
+    lh_dmesh_event *ne = (lh_dmesh_event *)realloc(a->dmesh_events, sizeof(lh_dmesh_event) * (a->ndmesh_events + 1));
+    if (!ne) { (void)fail("out of memory"); return NULL; }
+    a->dmesh_events = ne;
+    const hipError_t e = hipEventCreateWithFlags(&ne[a->ndmesh_events].ev, hipEventDisableTiming);
+    if (e != hipSuccess) { (void)fail("hipEventCreateWithFlags failed: %s", hipGetErrorString(e)); return NULL; }
+    ne[a->ndmesh_events].stream = s;
+    return &ne[a->ndmesh_events++];
 }
 
 extern "C" int lh_accel_add_mesh_device(lh_accel_t *a, uint32_t npos, const void *d_pos, int fmt, size_t stride, uint32_t nidx,
@@ -204,24 +220,17 @@ extern "C" int lh_accel_add_mesh_device(lh_accel_t *a, uint32_t npos, const void
     /* what the flatten kernel will read: whole vertices up to the last one's z, whole triangles */
     const size_t pos_bytes = ntris ? (size_t)(npos - 1) * stride + 3 * elem : 0, idx_bytes = sizeof(uint32_t) * 3 * (size_t)ntris;
     HIPCHK(hipSetDevice(a->device));
-    if (ntris && (device_array_ok(a, d_pos, pos_bytes, "positions") != 0 || device_array_ok(a, d_idx, idx_bytes, "indices") != 0)) return -1;
+    if (ntris && (device_array_ok(a, d_pos, pos_bytes, "lh_accel_add_mesh_device", "positions") != 0 ||
+                  device_array_ok(a, d_idx, idx_bytes, "lh_accel_add_mesh_device", "indices") != 0)) return -1;
     lh_dmesh *nm = (lh_dmesh *)realloc(a->dmeshes, sizeof(lh_dmesh) * (a->ndmeshes + 1));
     if (!nm) return fail("out of memory");
     a->dmeshes = nm;
     lh_dmesh m; memset(&m, 0, sizeof(m));
-    m.stride = stride; m.npos = npos; m.ntris = ntris; m.fmt = fmt;
+    m.stride = stride; m.npos = npos; m.ntris = ntris; m.fmt = fmt; m.nidx = nidx;
     if (ntris) {
         hipStream_t s = (hipStream_t)stream;
-        lh_dmesh_event *ev = NULL;
-        for (uint32_t k = 0; k < a->ndmesh_events; k++) if (a->dmesh_events[k].stream == s) ev = &a->dmesh_events[k];
-        if (!ev) {
-            lh_dmesh_event *ne = (lh_dmesh_event *)realloc(a->dmesh_events, sizeof(lh_dmesh_event) * (a->ndmesh_events + 1));
-            if (!ne) return fail("out of memory");
-            a->dmesh_events = ne;
-            HIPCHK(hipEventCreateWithFlags(&ne[a->ndmesh_events].ev, hipEventDisableTiming));
-            ne[a->ndmesh_events].stream = s;
-            ev = &ne[a->ndmesh_events++];
-        }
+        lh_dmesh_event *ev = dmesh_event_of(a, s);
+        if (!ev) return -1;
         const size_t pos_room = (pos_bytes + 15) & ~(size_t)15;
         HIPCHK(hipMalloc(&m.block, pos_room + idx_bytes));
         m.pos = m.block; m.idx = (const uint32_t *)((char *)m.block + pos_room);
@@ -241,6 +250,71 @@ extern "C" int lh_accel_add_mesh_device(lh_accel_t *a, uint32_t npos, const void
 
 /* 1 if the accelerator holds, or was committed from, device meshes (lh_multi.hip asks) */
 extern "C" int lh_accel_device_meshes(const lh_accel_t *a) { return a && (a->ndmeshes || a->hs->device_meshes) ? 1 : 0; }
+
+/* lh_accel_set_normals_device / lh_accel_set_attribute_device: slot `slot` of staged device mesh `mesh` becomes the library's own
+ * copy of `count` elements of `ncomp` components (the caller's format and stride), enqueued on `stream`; d == NULL removes it.
+ * Every refusal comes before anything is enqueued or changed */
+static int set_dmesh_attr(lh_accel_t *a, const char *who, uint32_t mesh, int slot, uint32_t count, const void *d, int fmt, size_t stride,
+                          const int *two_side, void *stream)
+{
+    if (a->committed || a->commit_failed) return fail("%s: accel already committed", who);
+    if (!a->ndmeshes) return fail("%s: for device meshes (lh_accel_add_mesh_device); host meshes take %s", who,
+                                  slot == LH_DATTR_NORMAL ? "lh_accel_set_normals" : "lh_accel_set_attribute");
+    if (mesh >= a->ndmeshes) return fail("%s: mesh %u out of range", who, mesh);
+    if (!two_side && (slot < LH_ATTR_COLOR || slot > LH_ATTR_TEXCOORD_UNSHARED)) return fail("%s: unknown attribute kind %d", who, slot);      /* two_side: the normals' call */
+    lh_dmesh *m = &a->dmeshes[mesh];
+    const uint32_t ncomp = (slot == LH_ATTR_TEXCOORD || slot == LH_ATTR_TEXCOORD_UNSHARED) ? 2u : 3u;
+    const uint32_t need = slot == LH_ATTR_TEXCOORD_UNSHARED ? m->nidx : m->npos;
+    size_t bytes = 0;
+    if (d || count) {
+        if (fmt != LH_POS_F64 && fmt != LH_POS_F32) return fail("%s: unknown format %d", who, fmt);
+        const size_t elem = fmt == LH_POS_F32 ? sizeof(float) : sizeof(double);
+        if (stride < ncomp * elem || (stride % elem) != 0) return fail("%s: bad stride %zu", who, stride);
+        if (((uintptr_t)d % elem) != 0) return fail("%s: array not aligned to %zu bytes", who, elem);
+        if (!d) return fail("%s: NULL array", who);
+        bytes = count ? (size_t)(count - 1) * stride + ncomp * elem : 0;
+        HIPCHK(hipSetDevice(a->device));
+        if (bytes && device_array_ok(a, d, bytes, who, "the array") != 0) return -1;
+        if (count != need) return fail("%s: %u values given, the mesh needs %u (one per %s)", who, count, need,
+                                       slot == LH_ATTR_TEXCOORD_UNSHARED ? "index" : "vertex");
+    }
+    lh_dmesh_attr n; memset(&n, 0, sizeof(n));
+    if (d) {
+        n.has = 1; n.fmt = fmt; n.stride = stride;
+        if (m->ntris && bytes) {                        /* a mesh without triangles is never read */
+            hipStream_t s = (hipStream_t)stream;
+            lh_dmesh_event *ev = dmesh_event_of(a, s);
+            if (!ev) return -1;
+            HIPCHK(hipMalloc(&n.block, bytes));
+            /* the library's own copy, in the caller's stream order: the caller's array is free again once it has run */
+            if (hipMemcpyAsync(n.block, d, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess || hipEventRecord(ev->ev, s) != hipSuccess) {
+                const char *why = hipGetErrorString(hipGetLastError());
+                (void)hipStreamSynchronize(s); (void)hipFree(n.block);
+                return fail("%s: copying the array failed: %s", who, why);
+            }
+        }
+    }
+    if (m->attr[slot].block) { (void)hipSetDevice(a->device); (void)hipFree(m->attr[slot].block); }      /* replaced or removed */
+    m->attr[slot] = n;
+    if (two_side) m->two_side = *two_side;
+    return 0;
+}
+
+extern "C" int lh_accel_set_normals_device(lh_accel_t *a, uint32_t mesh, uint32_t nnormals, const void *d_normals, int fmt, size_t stride,
+                                           int two_side, void *stream)
+{
+    lh_guard guard(a);
+    if (!a) return fail("lh_accel_set_normals_device: accel is NULL");
+    return set_dmesh_attr(a, "lh_accel_set_normals_device", mesh, LH_DATTR_NORMAL, nnormals, d_normals, fmt, stride, &two_side, stream);
+}
+
+extern "C" int lh_accel_set_attribute_device(lh_accel_t *a, uint32_t mesh, int kind, uint32_t count, const void *d_data, int fmt, size_t stride,
+                                             void *stream)
+{
+    lh_guard guard(a);
+    if (!a) return fail("lh_accel_set_attribute_device: accel is NULL");
+    return set_dmesh_attr(a, "lh_accel_set_attribute_device", mesh, kind, count, d_data, fmt, stride, NULL, stream);
+}
 
 /* running triangle counts of the staged device meshes: first[g] = primitive id of mesh g's triangle 0, first[n] = all */
 static uint32_t *dmesh_first_prim(const lh_accel_t *a)
@@ -291,6 +365,57 @@ static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first)
     if (rc == 0 && es != hipSuccess) rc = fail("lh_accel_commit: flattening the device meshes failed: %s", hipGetErrorString(es));
     if (rc == 0 && status[0]) rc = fail("lh_accel_commit: mesh %u: index %u out of range (npositions %u)", status[1], status[2], status[3]);
     if (rc == 0 && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device flatten (%u meshes, %.0f MB) %8.2f ms\n", nm, sizeof(lh_tri64_t) * (double)nt / 1e6, (now_s() - t0) * 1e3);
+    return rc;
+}
+
+/* the per-vertex normals and attributes of the staged device meshes -> a->d_nrm9, a->d_attr9[], a->d_st6, a->d_inside, the arrays a
+ * host scene uploads (device_upload): one kernel on the accelerator's stream.  Called behind flatten_device_meshes, which has
+ * waited for the callers' copies and found every index in range; an array no mesh contributes to stays NULL, a scene without
+ * any costs nothing here */
+static int gather_device_attributes(lh_accel_t *a, const uint32_t *first)
+{
+    const uint32_t nm = a->ndmeshes, nt = first[nm];
+    bool any[LH_DATTR_SLOTS] = {false, false, false, false, false, false}, any_two = false, work = false;
+    for (uint32_t g = 0; g < nm; g++) {
+        for (int k = 0; k < LH_DATTR_SLOTS; k++) any[k] = any[k] || a->dmeshes[g].attr[k].has;
+        any_two = any_two || a->dmeshes[g].two_side;
+    }
+    for (int k = 0; k < LH_DATTR_SLOTS; k++) work = work || any[k];
+    if (nt == 0 || !(work || any_two)) return 0;
+    const double t0 = now_s();
+    if (any[LH_DATTR_NORMAL]) HIPCHK(hipMalloc(&a->d_nrm9, sizeof(double) * 9 * (size_t)nt));
+    for (int k = 0; k < 3; k++) if (any[k]) HIPCHK(hipMalloc(&a->d_attr9[k], sizeof(double) * 9 * (size_t)nt));
+    if (any[LH_ATTR_TEXCOORD] || any[LH_ATTR_TEXCOORD_UNSHARED]) HIPCHK(hipMalloc(&a->d_st6, sizeof(double) * 6 * (size_t)nt));
+    if (any_two) HIPCHK(hipMalloc(&a->d_inside, (size_t)nt));
+    publish_scene(a);
+    lh_gather_out_t out;
+    out.nrm9 = (double *)a->d_nrm9; out.st6 = (double *)a->d_st6; out.inside = (uint8_t *)a->d_inside;
+    for (int k = 0; k < 3; k++) out.attr9[k] = (double *)a->d_attr9[k];
+    /* one block: the index descriptors, the attribute descriptors, the first_prim table */
+    const size_t desc_bytes = sizeof(lh_dmesh_desc_t) * (size_t)nm, attr_bytes = sizeof(lh_dmesh_attr_desc_t) * (size_t)nm;
+    std::vector<char> h(desc_bytes + attr_bytes + sizeof(uint32_t) * ((size_t)nm + 1), 0);
+    lh_dmesh_desc_t *hd = (lh_dmesh_desc_t *)h.data();
+    lh_dmesh_attr_desc_t *ha = (lh_dmesh_attr_desc_t *)(h.data() + desc_bytes);
+    for (uint32_t g = 0; g < nm; g++) {
+        const lh_dmesh *m = &a->dmeshes[g];
+        hd[g].pos = m->pos; hd[g].idx = m->idx; hd[g].stride = m->stride; hd[g].npos = m->npos; hd[g].fmt = (uint32_t)m->fmt;
+        for (int k = 0; k < LH_DATTR_SLOTS; k++) {
+            ha[g].data[k] = m->attr[k].block; ha[g].stride[k] = m->attr[k].stride;
+            if (m->attr[k].fmt == LH_POS_F32) ha[g].f32_mask |= 1u << k;
+        }
+        ha[g].two_side = m->two_side ? 1u : 0u; ha[g].nidx = m->nidx;
+    }
+    memcpy(h.data() + desc_bytes + attr_bytes, first, sizeof(uint32_t) * ((size_t)nm + 1));
+    char *d_tab = NULL;
+    HIPCHK(hipMalloc((void **)&d_tab, h.size()));
+    int rc = 0;
+    if (hipMemcpyAsync(d_tab, h.data(), h.size(), hipMemcpyHostToDevice, a->stream) != hipSuccess) rc = fail("lh_accel_commit: uploading the attribute table failed");
+    if (rc == 0) rc = lh_gather_launch(nt, nm, (const lh_dmesh_desc_t *)d_tab, (const lh_dmesh_attr_desc_t *)(d_tab + desc_bytes),
+                                       (const uint32_t *)(d_tab + desc_bytes + attr_bytes), out, a->stream);
+    const hipError_t es = hipStreamSynchronize(a->stream);         /* the table is the host vector's until here */
+    (void)hipFree(d_tab);
+    if (rc == 0 && es != hipSuccess) rc = fail("lh_accel_commit: gathering the device meshes' attributes failed: %s", hipGetErrorString(es));
+    if (rc == 0 && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device attribute gather      %8.2f ms\n", (now_s() - t0) * 1e3);
     return rc;
 }
 
@@ -838,7 +963,7 @@ static int device_upload(lh_accel_t *a, const uint32_t *dmesh_first = NULL)
     if (hs->bvh.ntris) {
         const size_t t64 = sizeof(lh_tri64_t) * nt;
         const double tu = now_s();
-        if (dmesh_first) { if (flatten_device_meshes(a, dmesh_first) != 0) return -1; }          /* device meshes: the records are made here, nothing crosses the link */
+        if (dmesh_first) { if (flatten_device_meshes(a, dmesh_first) != 0 || gather_device_attributes(a, dmesh_first) != 0) return -1; }      /* device meshes: the records are made here, nothing crosses the link */
         else if (upload_array(a, &a->d_tri64, hs->bvh.tri64, t64) != 0) return -1;
         if (!dmesh_first && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 upload (%.0f MB)      %8.2f ms\n", t64 / 1e6, (now_s() - tu) * 1e3);
         if (hs->device_built) {
@@ -899,6 +1024,19 @@ static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm
     if (e != hipSuccess) { free(tri); free(ident); free(mc); return fail("lh_accel_commit: copying the flattened triangles to the host failed: %s", hipGetErrorString(e)); }
     if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 to the host (%.0f MB)   %8.2f ms\n", sizeof(lh_tri64_t) * (double)nt / 1e6, (now_s() - t0) * 1e3);
     for (size_t i = 0; i < 3 * nt; i++) ident[i] = (uint32_t)i;
+    /* the per-primitive attribute arrays the gather made cross the release with the triangles: into the host scene, in the layout
+     * device_upload carries back (host_build below sees one mesh without attributes and leaves them alone) */
+    struct { void *dev; void **host; size_t bytes; } carry[] = {
+        {a->d_nrm9, (void **)&hs->nrm9, sizeof(double) * 9 * nt}, {a->d_attr9[0], (void **)&hs->attr9[0], sizeof(double) * 9 * nt},
+        {a->d_attr9[1], (void **)&hs->attr9[1], sizeof(double) * 9 * nt}, {a->d_attr9[2], (void **)&hs->attr9[2], sizeof(double) * 9 * nt},
+        {a->d_st6, (void **)&hs->st6, sizeof(double) * 6 * nt}, {a->d_inside, (void **)&hs->inside, nt}};
+    for (size_t k = 0; k < sizeof(carry) / sizeof(carry[0]); k++) {
+        if (!carry[k].dev) continue;
+        free(*carry[k].host);
+        *carry[k].host = malloc(carry[k].bytes);                /* the host scene's from here on: freed with it */
+        const hipError_t ec = *carry[k].host ? hipMemcpy(*carry[k].host, carry[k].dev, carry[k].bytes, hipMemcpyDeviceToHost) : hipErrorOutOfMemory;
+        if (ec != hipSuccess) { free(tri); free(ident); free(mc); return fail("lh_accel_commit: copying the gathered attributes to the host failed: %s", hipGetErrorString(ec)); }
+    }
     free_dmeshes(a);
     release_device(a);
     lh_bvh_release(&hs->bvh); lh_refbvh_release(&hs->ref); hs->ref_state = 0; hs->ref_on_device = 0;

@@ -39,8 +39,16 @@ struct lh_mesh_copy { uint32_t npos, nidx; double *pos; uint32_t *idx; double *n
 
 /* a mesh handed over as device arrays (lh_accel_add_mesh_device): the library's own device copy of what the flatten kernel reads --
  * one block, the vertices in the caller's format and stride, then the indices -- and, for the kernel, its descriptor (lh_flatten.hip) */
-struct lh_dmesh { void *block; const void *pos; const uint32_t *idx; size_t stride; uint32_t npos, ntris; int fmt; };
+struct lh_dmesh_attr { void *block; size_t stride; int fmt, has; };          /* has: the mesh carries the attribute (block stays NULL for a mesh without triangles) */
+#define LH_DATTR_NORMAL 5         /* slot of the normals behind the five LH_ATTR_* kinds */
+#define LH_DATTR_SLOTS 6
+struct lh_dmesh { void *block; const void *pos; const uint32_t *idx; size_t stride; uint32_t npos, ntris; int fmt;
+                  uint32_t nidx; int two_side; lh_dmesh_attr attr[LH_DATTR_SLOTS]; };      /* lh_accel_set_normals_device / _set_attribute_device: own copies, caller's format and stride */
 typedef struct lh_dmesh_desc { const void *pos; const uint32_t *idx; unsigned long long stride; uint32_t npos, fmt; } lh_dmesh_desc_t;
+/* what k_gather_attributes reads of a mesh beside its lh_dmesh_desc_t: data[k] NULL = the mesh lacks slot k */
+typedef struct lh_dmesh_attr_desc { const void *data[LH_DATTR_SLOTS]; unsigned long long stride[LH_DATTR_SLOTS]; uint32_t f32_mask, two_side, nidx, pad; } lh_dmesh_attr_desc_t;
+/* the per-primitive arrays the gather fills; NULL = no mesh of the scene has it */
+typedef struct lh_gather_out { double *nrm9, *attr9[3], *st6; uint8_t *inside; } lh_gather_out_t;
 struct lh_dmesh_event { hipStream_t stream; hipEvent_t ev; };          /* the last copy enqueued on a caller's stream: the commit waits for it */
 
 struct lh_buf { void *p; size_t cap; };
@@ -198,6 +206,9 @@ int  lh_scene_image_finish(lh_accel_t *a);
 /* lh_flatten.hip: the staged device meshes -> lh_tri64_t[ntris] in primitive-id order, one launch */
 int  lh_flatten_launch(uint32_t ntris, uint32_t nmeshes, const lh_dmesh_desc_t *d_desc, const uint32_t *d_first, void *d_tri64,
                        uint32_t *d_status, hipStream_t stream);
+/* ... and their per-vertex normals and attributes -> the per-primitive arrays of `out`, one launch, after a clean flatten */
+int  lh_gather_launch(uint32_t ntris, uint32_t nmeshes, const lh_dmesh_desc_t *d_desc, const lh_dmesh_attr_desc_t *d_attr, const uint32_t *d_first,
+                      lh_gather_out_t out, hipStream_t stream);
 /* lh_hostwalk.c */
 extern "C" int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], uint32_t *prim, double *t, double *u, double *v);
 /* lh_query.hip */
