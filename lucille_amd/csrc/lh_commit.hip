@@ -506,11 +506,11 @@ static int upload_array(lh_accel_t *a, void **slot, const void *src, size_t byte
 
 static void release_device(lh_accel_t *a)
 {
-    lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_slot, &a->r_hitrec,
-                      &a->r_aorg, &a->r_adir, &a->r_occ, &a->r_blocks, &a->r_key, &a->r_frame, &a->r_occcount,
-                      &a->b_slot, &a->b_hitrec, &a->b_key, &a->b_occcount, &a->b_aorg, &a->b_adir, &a->b_occ, &a->b_blocks, &a->b_tot, &a->b_host,
+    lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_frame, &a->b_tot, &a->b_host,
                       &a->p_org2, &a->p_dir2, &a->p_path, &a->p_path2, &a->p_thr, &a->p_thr2, &a->p_rad, &a->p_counts};
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); i++) free_buf(bufs[i]);
+    for (lh_ao_scratch *sc : {&a->tile_ao, &a->batch_ao})
+        for (lh_buf *b : {&sc->slot, &sc->hitrec, &sc->key, &sc->occcount, &sc->aorg, &sc->adir, &sc->occ, &sc->blocks}) free_buf(b);
     if (a->d_total) (void)hipFree(a->d_total);
     scene_row rows[LH_SCENE_ROWS];
     scene_rows(a, NULL, rows);

@@ -52,6 +52,9 @@ typedef struct lh_gather_out { double *nrm9, *attr9[3], *st6; uint8_t *inside; }
 struct lh_dmesh_event { hipStream_t stream; hipEvent_t ev; };          /* the last copy enqueued on a caller's stream: the commit waits for it */
 
 struct lh_buf { void *p; size_t cap; };
+/* what the AO stage (lh_tile.hip ao_stage) owns for one kind of caller: slot of every sample / list entry, hit records, slot keys, per-slot
+ * occlusion counts (fused), the materialised rays and their any-hit bytes, the compaction's block counts */
+struct lh_ao_scratch { lh_buf slot, hitrec, key, occcount, aorg, adir, occ, blocks; };
 #define LH_AOQ_SLOTS 4
 #define LH_PIPE_DEPTH_MAX 8   /* staging blocks of a pipelined host batch (lh_query.hip) */
 
@@ -130,12 +133,13 @@ struct lh_accel {
     lh_buf r_diag;                     /* LH_STAGE_TIMING: wave start / exit clocks */
     lh_buf r_bands;                    /* lh_render_ao_bands: first line of every band */
     void *h_read;                      /* 1 KiB of pinned host memory: the read-backs at the end of an AO batch (occlusion totals, hit count, queue flags) */
-    /* tile-render scratch (lh_render_ao_tile) */
-    lh_buf r_org, r_dir, r_prim, r_t, r_u, r_v, r_slot, r_hitrec, r_aorg, r_adir, r_occ, r_blocks, r_key, r_frame, r_occcount;
-    /* scratch of the AO stage for a caller's batch (lh_accel_ao_device / _ao_rays_device / _ao_host), apart from the tile's so that
-     * lh_render_scratch keeps showing the last tile call: slot of every list entry, hit records, slot keys, per-slot counts, the
-     * materialised rays and their any-hit bytes, block counts, the totals (hits; 64 occlusion counters), lh_accel_ao_host's staging */
-    lh_buf b_slot, b_hitrec, b_key, b_occcount, b_aorg, b_adir, b_occ, b_blocks, b_tot, b_host;
+    /* tile-render scratch (lh_render_ao_tile): camera rays and closest-hit records, the frame of the host entry points, the AO stage's */
+    lh_buf r_org, r_dir, r_prim, r_t, r_u, r_v, r_frame;
+    lh_ao_scratch tile_ao;
+    /* the AO stage's scratch for a caller's batch (lh_accel_ao_device / _ao_rays_device / _ao_host), apart from the tile's so that
+     * lh_render_scratch keeps showing the last tile call; the batch's totals (hits; 64 occlusion counters), lh_accel_ao_host's staging */
+    lh_ao_scratch batch_ao;
+    lh_buf b_tot, b_host;
     uint64_t last_retraced;            /* rays the last counted launch finished outside the main kernel */
     int ao_fused;                      /* AO rays generated inside the any-hit kernel (default); 0: materialised in HBM */
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */
@@ -233,6 +237,64 @@ static inline unsigned long long *lh_next_cursor(lh_accel_t *a)
     return (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR));
 }
 int  lh_aoq_slot(lh_accel_t *a, hipStream_t s);
+/* a counted launch's words h (LH_CNT_*) into the accelerator's statistics; the caller says what is its own to say: how many rays, how many
+ * hits.  slots: the lane-slot words too (the tile pipelines' batches; h holds LH_CNT_DEV words then) */
+static inline void lh_stat_add(lh_accel_t *a, const unsigned long long *h, unsigned long long rays, unsigned long long hits, bool slots = false)
+{
+    a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT];
+    a->stat[3] += rays; a->stat[4] += hits;
+    if (slots) { a->stat_slots[0] += h[LH_CNT_NODE_SLOTS]; a->stat_slots[1] += h[LH_CNT_TRI_SLOTS]; a->stat_slots[2] += h[LH_CNT_REGROUP_SLOTS]; }
+}
 int  lh_ensure_stage(lh_accel_t *a, size_t bytes);
+
+/* lh_render.hip: the launchers lh_tile.hip calls (stream is a hipStream_t).  lh_render.hip includes this file too, so a prototype that drifts
+ * from its definition does not compile -- under extern "C" it would still link */
+extern "C" int lh_render_launch_primary(const lh_camera_t *cam, int x0, int y0, int w, int h, int xs, int ys,
+                                        double *d_org, double *d_dir, void *stream);
+extern "C" int lh_render_launch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n, const double *d_org,
+                                        const double *d_dir, const uint32_t *d_prim, const double *d_t,
+                                        const double *d_u, const double *d_v, uint32_t *d_block_counts,
+                                        uint32_t *d_slot_of_sample, double *d_hitrec,
+                                        unsigned long long *d_slot_key, int x0, int w, int nbands, int band_rows,
+                                        const int *d_band_y0, int y0, int spp, int full_width,
+                                        unsigned long long *d_total, void *stream);
+extern "C" int lh_render_launch_primary_region(const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0,
+                                               int y0, int height_limit, int xs, int ys, double *d_org, double *d_dir, void *stream);
+extern "C" int lh_render_launch_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long long seed,
+                                        const double *d_hitrec, const double *d_rnd,
+                                        const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
+extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
+                                        const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
+                                        unsigned long long *d_occ_total, void *stream);
+extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
+                                              const uint32_t *d_index, const uint32_t *d_count, const double *d_org, const double *d_dir,
+                                              const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
+                                              const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
+                                              double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
+                                              uint32_t *d_nslots32, void *stream);
+extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
+                                              const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
+                                              uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream);
+extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigned long long *d_nslots, int ntheta, int nphi,
+                                                unsigned long long seed, const double *d_hitrec, const double *d_rnd,
+                                                const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
+extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
+                                            const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
+                                            const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,
+                                            const double *d_u, const double *d_v, double *d_state, void *stream);
+extern "C" size_t lh_pt_material_bytes(void);
+extern "C" void lh_pt_material_pack(const lh_material_t *m, void *out);
+extern "C" int lh_pt_launch_begin(const lh_camera_t *cam, int x0, int y0, int w, int h, int band_rows, int band_stride, int spp, int s0,
+                                  unsigned long long seed, void *d_cam, uint32_t *d_counts, int ncounts, void *stream);
+extern "C" size_t lh_pt_cam_bytes(void);
+extern "C" int lh_pt_launch_shade(size_t n_max, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
+                                  const uint32_t *d_prim_mesh, const void *d_materials, const lh_material_t *override_mat,
+                                  const float env_rgb[3], const void *d_env_map, int env_w, int env_h, int ref_weights,
+                                  int depth, int max_depth, unsigned long long seed, int s0, int spp, int x0, int y0, int w,
+                                  int band_rows, int band_stride, int full_width, const void *d_cam, uint32_t *d_counts, const double *d_org, const double *d_dir, const uint32_t *d_prim,
+                                  const double *d_t, const double *d_u, const double *d_v, const uint32_t *d_path_of,
+                                  const float *d_thr, unsigned long long *d_accum, double *d_org2, double *d_dir2, uint32_t *d_path_of2,
+                                  float *d_thr2, int ncus, void *stream);
+extern "C" int lh_pt_launch_resolve(int w, int h, int band_rows, float inv_total_spp, unsigned long long *d_accum, float *d_rgb, void *stream);
 
 #endif

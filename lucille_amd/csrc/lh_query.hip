@@ -209,12 +209,6 @@ static int counted_collect(lh_accel_t *a, hipStream_t s, unsigned long long h[LH
     return 0;
 }
 
-static void stat_add(lh_accel_t *a, const unsigned long long *h, unsigned long long rays, unsigned long long hits)
-{
-    a->stat[0] += h[LH_CNT_NODES]; a->stat[1] += h[LH_CNT_TRIS]; a->stat[2] += h[LH_CNT_EXACT];
-    a->stat[3] += rays; a->stat[4] += hits;
-}
-
 extern "C" int lh_accel_intersect_device_counted(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir,
                                                  void *d_prim, void *d_t, void *d_u, void *d_v, void *d_occ,
                                                  int mode, int variant, uint64_t counters[4])
@@ -494,7 +488,7 @@ static int intersect_host_fmt(lh_accel_t *a, size_t n, const void *org, const vo
         }
         if (counted_collect(a, a->stream, h) != 0) return -1;          /* an empty scene's batch leaves them zero */
         for (size_t i = 0; i < n; i++) nh += (mode == LH_MODE_CLOSEST) ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
-        stat_add(a, h, n, nh);
+        lh_stat_add(a, h, n, nh);
     }
     if (rec16) HIPCHK(hipMemcpyAsync(prim, d_prim, 16 * n, hipMemcpyDeviceToHost, a->stream));
     else if (mode == LH_MODE_CLOSEST) {
@@ -580,7 +574,7 @@ extern "C" int lh_accel_intersect_device_indexed(lh_accel_t *a, size_t n_rays, c
     if (!a->stat_on) return 0;
     unsigned long long h[LH_CNT_DEV];
     if (counted_collect(a, s, h) != 0) return -1;
-    stat_add(a, h, h[LH_CNT_RAYS], 0);          /* hits are not counted: the records stay on the device */
+    lh_stat_add(a, h, h[LH_CNT_RAYS], 0);          /* hits are not counted: the records stay on the device */
     return 0;
 }
 
@@ -862,7 +856,7 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
     if (a->stat_on) {
         unsigned long long nh = 0;
         for (size_t i = 0; i < n; i++) nh += hp[i] != LH_MISS_PRIM;
-        stat_add(a, h, n, nh);
+        lh_stat_add(a, h, n, nh);
     }
     return 0;
 }

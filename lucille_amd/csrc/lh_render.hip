@@ -30,7 +30,7 @@
 #include <string.h>
 
 #include "../../include/lucille_hip.h"
-#include "lh_device.h"
+#include "lh_internal.h"
 #include "lh_ao.h"
 
 namespace {

@@ -13,24 +13,6 @@
 
 #define ensure_buf lh_ensure_buf
 
-/* launchers in lh_render.hip */
-extern "C" int lh_render_launch_primary(const lh_camera_t *cam, int x0, int y0, int w, int h, int xs, int ys,
-                                        double *d_org, double *d_dir, void *stream);
-extern "C" int lh_render_launch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n, const double *d_org,
-                                        const double *d_dir, const uint32_t *d_prim, const double *d_t,
-                                        const double *d_u, const double *d_v, uint32_t *d_block_counts,
-                                        uint32_t *d_slot_of_sample, double *d_hitrec,
-                                        unsigned long long *d_slot_key, int x0, int w, int nbands, int band_rows,
-                                        const int *d_band_y0, int y0, int spp, int full_width,
-                                        unsigned long long *d_total, void *stream);
-extern "C" int lh_render_launch_primary_region(const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0,
-                                               int y0, int height_limit, int xs, int ys, double *d_org, double *d_dir, void *stream);
-extern "C" int lh_render_launch_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long long seed,
-                                        const double *d_hitrec, const double *d_rnd,
-                                        const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
-extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
-                                        const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
-                                        unsigned long long *d_occ_total, void *stream);
 
 extern "C" int lh_render_primary_rays(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h,
                                       int ps, void *d_org, void *d_dir, void *stream)
@@ -45,85 +27,93 @@ extern "C" int lh_render_primary_rays(lh_accel_t *a, const lh_camera_t *cam, int
     return 0;
 }
 
-/* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands */
-static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0, int y0,
-                     uint64_t valid_pixels, int ps, int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb,
-                     lh_tile_stats_t *stats, void *stream)
-{
-    const int h = nbands * band_rows;              /* lines of the batch */
-    HIPCHK(hipSetDevice(a->device));
-    hipStream_t s = (hipStream_t)stream;
-    const int nphi = (int)sqrt((double)gather_nsamples), ntheta = nphi, N = nphi * ntheta;   /* ambientocclusion.c:378-380 */
-    const size_t S = (size_t)w * h * ps * ps;
-    if ((unsigned long long)cam->width * (unsigned long long)cam->height * (unsigned long long)(ps * ps) >= (1ull << 34))
-        return fail("AO pipeline: more than 2^34 samples in the frame (slot keys carry 34 bits)");
-    if (S >= ((size_t)1 << 31)) return fail("AO pipeline: more than 2^31 samples in one batch; render the frame in tiles");     /* 32-bit sample indices on the device */
-    const unsigned nb = (unsigned)((S + 255) / 256);
-    if (ensure_buf(&a->r_org, S * 24) || ensure_buf(&a->r_dir, S * 24) || ensure_buf(&a->r_prim, S * 4) ||
-        ensure_buf(&a->r_t, S * 8) || ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8) ||
-        ensure_buf(&a->r_slot, S * 4) || ensure_buf(&a->r_blocks, (size_t)nb * 4)) return -1;
-    /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
-    unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
-    if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
-    /* LH_STAGE_TIMING=1: HIP events between the stages of the batch, printed to stderr (tools/experiments/rank_breakdown.py) */
-    const bool stage_timing = getenv("LH_STAGE_TIMING") != NULL;
+/* the hemisphere's sample grid of a hit: nphi = ntheta = (int)sqrt(gather_nsamples), N = their product AO rays (ambientocclusion.c:378-380) */
+struct ao_grid { int nphi, ntheta, N; };
+static inline ao_grid ao_sample_grid(int gather_nsamples) { const int n = (int)sqrt((double)gather_nsamples); return ao_grid{n, n, n * n}; }
+
+/* LH_STAGE_TIMING=1: HIP events between the stages of a batch, printed to stderr (tools/experiments/rank_breakdown.py); they go with the
+ * scope, whichever way the batch returns */
+struct stage_timer {
     hipEvent_t ev[6] = {NULL, NULL, NULL, NULL, NULL, NULL};
-    if (stage_timing) { for (int k = 0; k < 6; k++) HIPCHK(hipEventCreate(&ev[k])); HIPCHK(hipEventRecord(ev[0], s)); }
-    /* ... and the wall clock at which every persistent wave starts and leaves (two launches: closest, AO) */
-    const size_t nwaves = (size_t)a->grid_blocks * (LH_BLOCK / 64);
-    if (stage_timing) { if (ensure_buf(&a->r_diag, sizeof(unsigned long long) * 6 * nwaves)) return -1; HIPCHK(hipMemsetAsync(a->r_diag.p, 0, sizeof(unsigned long long) * 6 * nwaves, s)); }
-    lh_launch_opt opt; opt.diag_clock = stage_timing ? (unsigned long long *)a->r_diag.p : NULL;
-    /* 1. camera rays */
-    if (lh_render_launch_primary_region(cam, x0, w, nbands, band_rows, d_band_y0, y0, cam->height, ps, ps,
-                                        (double *)a->r_org.p, (double *)a->r_dir.p, s) != 0)
-        return fail("primary ray kernel launch failed");
-    if (stage_timing) HIPCHK(hipEventRecord(ev[1], s));
-    /* 2. closest hit */
-    if (lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, a->r_org.p, a->r_dir.p, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt},
-                  LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
-    if (stage_timing) { HIPCHK(hipEventRecord(ev[2], s)); opt.diag_clock = (unsigned long long *)a->r_diag.p + 3 * nwaves; }
-    /* 3. compaction (deterministic: hits in sample order).  The fused AO stage does not need the total on the host: its buffers are
-     * sized for the worst case (every sample hits) and its kernels read the count where the compaction left it -- a batch costs ONE
-     * host round trip, at its end (round 5: the two in the middle were ~0.25 ms of a rank's 8.9 ms share of the config-5 frame).
-     * The materialised stage (caller uniforms: the parity replay; LH_AO_FUSED=0; a fix-up queue that overflowed) sizes its ray
-     * arrays from the count and reads it first. */
-    unsigned long long nhit = 0, nocc = 0;
-    unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of k_ao_resolve's 64 counters */
-    const size_t nao_max = S * (size_t)N;
-    bool fused = a->ao_fused && !d_uniforms && a->hs->bvh.ntris;
-    const bool late_count = fused && nao_max < ((size_t)1 << 31) && !a->dev.ao_group && !getenv("LH_AO_SYNC");      /* the persistent kernel's 32-bit ray index covers the worst case */
-    if (a->hs->bvh.ntris) {
-        if (ensure_buf(&a->r_hitrec, S * 96) || ensure_buf(&a->r_key, S * 8)) return -1;   /* worst case: every sample hits */
-        if (lh_render_launch_compact(&a->dev, (const double *)a->d_nrm9, S, (const double *)a->r_org.p,
-                                     (const double *)a->r_dir.p, (const uint32_t *)a->r_prim.p, (const double *)a->r_t.p,
-                                     (const double *)a->r_u.p, (const double *)a->r_v.p, (uint32_t *)a->r_blocks.p,
-                                     (uint32_t *)a->r_slot.p, (double *)a->r_hitrec.p, (unsigned long long *)a->r_key.p,
-                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, s) != 0)
-            return fail("compaction kernels failed: %s", hipGetErrorString(hipGetLastError()));
-        HIPCHK(hipMemcpyAsync(d_nhit, a->d_total, sizeof(nhit), hipMemcpyDeviceToDevice, s));
-        if (!late_count) {
-            HIPCHK(hipMemcpyAsync(&nhit, d_nhit, sizeof(nhit), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (nhit * (unsigned long long)N >= (1ull << 31)) fused = false;
+    ~stage_timer() { for (int k = 0; k < 6; k++) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+};
+
+/* ... the report: the stages' times, and the percentiles of the clocks at which the persistent waves of the two launches (closest, AO)
+ * started, found every cursor dry and left (clk: a->r_diag, [2][3][nwaves]) */
+static int stage_report(const stage_timer &tm, const void *d_clk, size_t nwaves, size_t S, unsigned long long nhit, size_t nao)
+{
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < 5; k++) (void)hipEventElapsedTime(&ms[k], tm.ev[k], tm.ev[k + 1]);
+    fprintf(stderr, "[lucille_hip] AO batch stages (ms): primary %.3f closest %.3f compact %.3f ao %.3f resolve %.3f | samples %zu hits %llu ao rays %zu\n",
+            ms[0], ms[1], ms[2], ms[3], ms[4], S, nhit, nao);
+    std::vector<unsigned long long> clk(6 * nwaves);
+    HIPCHK(hipMemcpy(clk.data(), d_clk, sizeof(unsigned long long) * 6 * nwaves, hipMemcpyDeviceToHost));
+    for (int launch = 0; launch < 2; launch++) {
+        const unsigned long long *st = clk.data() + 3 * nwaves * launch, *ex = st + nwaves, *dry = ex + nwaves;
+        unsigned long long t0 = ~0ull; std::vector<double> e;
+        for (size_t w = 0; w < nwaves; w++) if (st[w] && st[w] < t0) t0 = st[w];
+        for (size_t w = 0; w < nwaves; w++) if (ex[w]) e.push_back((double)(ex[w] - t0) * 1e-5);        /* 100 MHz -> ms */
+        if (e.empty()) continue;
+        std::sort(e.begin(), e.end());
+        auto qq = [](std::vector<double> &v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
+        double last_start = 0; for (size_t w = 0; w < nwaves; w++) if (st[w]) last_start = fmax(last_start, (double)(st[w] - t0) * 1e-5);
+        fprintf(stderr, "[lucille_hip]   %s kernel: %zu waves, last start %.3f ms; exits (ms) min %.3f p10 %.3f p50 %.3f p90 %.3f p99 %.3f max %.3f\n",
+                launch ? "AO" : "closest", e.size(), last_start, e.front(), qq(e, 0.10), qq(e, 0.50), qq(e, 0.90), qq(e, 0.99), e.back());
+        /* when a wave found every cursor dry, and how long it went on after that (its last range and its slowest last rays) */
+        std::vector<double> d, g;
+        for (size_t w = 0; w < nwaves; w++) if (dry[w] && ex[w]) { d.push_back((double)(dry[w] - t0) * 1e-5); g.push_back((double)(ex[w] - dry[w]) * 1e-5); }
+        if (!d.empty()) {
+            std::sort(d.begin(), d.end()); std::sort(g.begin(), g.end());
+            fprintf(stderr, "[lucille_hip]     cursors found dry at (ms) min %.3f p50 %.3f p90 %.3f max %.3f; exit - dry (ms) min %.3f p10 %.3f p50 %.3f p90 %.3f p99 %.3f max %.3f (%zu waves)\n",
+                    d.front(), qq(d, 0.5), qq(d, 0.9), d.back(), g.front(), qq(g, 0.1), qq(g, 0.5), qq(g, 0.9), qq(g, 0.99), g.back(), d.size());
         }
-    } else {
-        HIPCHK(hipMemsetAsync(a->r_slot.p, 0xFF, S * 4, s));
-        HIPCHK(hipMemsetAsync(d_nhit, 0, sizeof(nhit), s));
     }
-    if (stage_timing) HIPCHK(hipEventRecord(ev[3], s));
-    /* AO stage.  Fused (default): the any-hit kernel generates ray (slot, r) in its refill (lh_ao.h) and counts
-     * the occluded rays per slot -- nothing per AO ray goes through HBM.  Materialised: caller uniforms (the parity
-     * replay), LH_AO_FUSED=0, or a fix-up queue overflow of the fused launch. */
-    if (fused && !late_count && nhit == 0) fused = false;          /* nothing was hit: nothing to trace, the resolve sees misses only */
-    const bool fused_tried = fused;
-    int qslot = -1;
-    /* the batch's read-backs land in pinned memory: three small copies behind the last kernel, one wait */
+    return 0;
+}
+
+/* The AO stage of the tile pipeline and of a caller's batch alike: from "the compaction has left hit records and keys (in b) and the hit count
+ * (at d_nhit) on the device" to "occlusion totals, hit count and statistics words are on the host".  fused: the any-hit kernel generates ray
+ * (slot, r) in its refill (lh_ao.h) and counts the occluded rays per slot -- nothing per AO ray goes through HBM.  Else, and as the second try
+ * of a fused launch whose fix-up queue overflowed, materialised: AO rays in HBM (from d_uniforms if given: the parity replay), an any-hit batch.
+ * late (with fused only): the count stays on the device -- the buffers are sized for the worst case (nmax slots: every sample / entry hits), the
+ * kernels read it at d_nhit -- and the stage costs ONE host round trip, at its end (round 5: the two in the middle were ~0.25 ms of a rank's
+ * 8.9 ms share of the config-5 frame).  Else the count is read first: it sizes the ray arrays and the launch.  resolve(from_counts) enqueues the
+ * caller's radiance kernel (from the per-slot counts, or from the any-hit bytes), which adds the occluded rays into the 64 counters at d_nocc.
+ * cnt: the LH_CNT_DEV counters or NULL; tm: stage timing or NULL (events 3-5: count known, any-hit done, resolved); prefix: of the messages */
+struct ao_totals { unsigned long long nhit, nocc, cnt[LH_CNT_DEV]; bool fused; };      /* cnt: the words at `cnt`; fused: the stage ended fused (no AO ray in HBM) */
+template <class Resolve>
+static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t nmax, ao_grid g, uint64_t seed, const void *d_uniforms,
+                    const unsigned long long *d_nhit, unsigned long long *d_nocc, unsigned long long *cnt, const lh_launch_opt &opt,
+                    stage_timer *tm, bool fused, bool late, Resolve resolve, hipStream_t s, ao_totals *out)
+{
+    const unsigned long long N = (unsigned long long)g.N;
+    /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
     if (!a->h_read) HIPCHK(hipHostMalloc(&a->h_read, 1024, hipHostMallocDefault));
     unsigned long long *h_nocc64 = (unsigned long long *)a->h_read, *h_nhit = h_nocc64 + 64; uint32_t *h_qc = (uint32_t *)(h_nocc64 + 65);
-    h_qc[0] = h_qc[1] = 0u;
-    if (fused && (late_count || nhit)) {
-        const size_t nslots = late_count ? S : (size_t)nhit;
-        if (ensure_buf(&a->r_occcount, nslots * sizeof(unsigned int))) return -1;
+    unsigned long long nhit = 0;
+    if (!late) {
+        HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(*h_nhit), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        nhit = *h_nhit;
+        /* the persistent kernel's ray index has 32 bits; nothing was hit: nothing to trace, the resolve sees misses only */
+        if (nhit * N >= (1ull << 31) || nhit == 0) fused = false;
+    }
+    if (tm) HIPCHK(hipEventRecord(tm->ev[3], s));
+    const bool fused_tried = fused;
+    uint32_t budget = 0;
+    int qslot = -1;
+    /* the stream's wait behind a fused launch, with the queue's words (and the late count) behind what is enqueued */
+    auto wait_queue = [&]() -> int {
+        if (late) HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(*h_nhit), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_qc, a->aoq[qslot].q.qcount, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        nhit = *h_nhit;
+        if (tm) fprintf(stderr, "[lucille_hip]   fused AO stage: %u rays through the fix-up queue (budget %u)\n", h_qc[0], budget);
+        return 0;
+    };
+    if (fused) {
+        const size_t nslots = late ? nmax : (size_t)nhit;
+        if (ensure_buf(&b->occcount, nslots * sizeof(unsigned int))) return -1;
         qslot = lh_aoq_slot(a, s);
         if (qslot < 0) return -1;
         lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget, its clocks */
@@ -133,108 +123,141 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
          * 2^27 rays or more doubles the default (config 5: whole frame 57.6 -> 56.7 ms, half of it 30.8 -> 29.9; a quarter and an
          * eighth are best at 384 -- tools/ao_budget_probe.py).  With the count on the device the kernel picks between the two */
         const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;
-        if (!late_count && big && nhit * (unsigned long long)N >= (1ull << 27)) sc.ray_budget = big;
-        const int rc_ao = lh_launch_trace_ao(&sc, nslots, ntheta, nphi, seed, (const double *)a->r_hitrec.p, (const unsigned long long *)a->r_key.p,
-                               (unsigned int *)a->r_occcount.p, cnt, lh_next_cursor(a), a->grid_blocks,
-                               a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, late_count ? d_nhit : NULL, late_count ? big : 0u, (void *)s);
-        if (rc_ao != 0) return fail("fused AO launch failed: %s", hipGetErrorString(hipGetLastError()));
-        if (!late_count) {
-            uint32_t qc[2] = {0, 0};
-            HIPCHK(hipMemcpyAsync(qc, a->aoq[qslot].q.qcount, sizeof(qc), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (qc[1] != 0) fused = false;             /* more than LH_AO_QCAP uncertain AO rays: redo the stage materialised */
-            if (stage_timing) fprintf(stderr, "[lucille_hip]   fused AO stage: %u rays through the fix-up queue (budget %u)\n", qc[0], a->dev.ray_budget);
+        if (!late && big && nhit * N >= (1ull << 27)) sc.ray_budget = big;
+        budget = sc.ray_budget;
+        if (lh_launch_trace_ao(&sc, nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                               (unsigned int *)b->occcount.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
+                               &a->aoq[qslot].q, a->ncus, late ? d_nhit : NULL, late ? big : 0u, (void *)s) != 0)
+            return fail("%sfused AO launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
+        if (!late) {
+            if (wait_queue() != 0) return -1;
+            fused = h_qc[1] == 0;             /* more than LH_AO_QCAP uncertain AO rays: redo the stage materialised */
         }
     }
-    /* stages 4-6 with the AO rays in HBM; also the second try of a batch whose fused launch overflowed its queue */
+    /* stages 4-5 with the AO rays in HBM */
     auto materialised = [&]() -> int {
-        const size_t nao_m = (size_t)nhit * N;
-        if (nao_m) {
-            if (ensure_buf(&a->r_aorg, nao_m * 24) || ensure_buf(&a->r_adir, nao_m * 24) || ensure_buf(&a->r_occ, nao_m)) return -1;
-            /* 4. AO rays */
-            if (lh_render_launch_ao_rays(nhit, ntheta, nphi, seed, (const double *)a->r_hitrec.p, (const double *)d_uniforms,
-                                         (const unsigned long long *)a->r_key.p, (double *)a->r_aorg.p, (double *)a->r_adir.p, s) != 0)
-                return fail("AO ray kernel launch failed");
-            /* 5. any-hit */
-            if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));   /* the abandoned fused pass is not counted (nor are the camera rays then) */
-            if (lh_launch(a, lh_batch_t{nao_m, LH_MODE_ANY, a->r_aorg.p, a->r_adir.p, NULL, NULL, NULL, NULL, a->r_occ.p, cnt},
-                          LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
-        }
-        return 0;
+        const size_t nao = (size_t)(nhit * N);
+        if (!nao) return 0;
+        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || ensure_buf(&b->occ, nao)) return -1;
+        /* 4. AO rays */
+        if (lh_render_launch_ao_rays((size_t)nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
+                                     (const unsigned long long *)b->key.p, (double *)b->aorg.p, (double *)b->adir.p, s) != 0)
+            return fail("%sAO ray kernel launch failed", prefix);
+        /* 5. any-hit.  The abandoned fused pass is not counted (nor is what the caller counted before the stage) */
+        if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+        return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, b->aorg.p, b->adir.p, NULL, NULL, NULL, NULL, b->occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
     };
-    auto resolve = [&](bool from_counts) -> int {
-        /* 6. radiance */
-        HIPCHK(hipMemsetAsync(a->d_total, 0, sizeof(unsigned long long) * 64, s));
-        if (lh_render_launch_resolve(w, h, band_rows, ps, ps, N, (const uint32_t *)a->r_slot.p, (const uint8_t *)a->r_occ.p,
-                                     from_counts ? (const unsigned int *)a->r_occcount.p : NULL, (float *)d_rgb, a->d_total, s) != 0)
-            return fail("resolve kernel launch failed");
-        HIPCHK(hipMemcpyAsync(h_nocc64, a->d_total, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost, s));
+    /* 6. radiance, and its occlusion totals on their way to the host */
+    auto resolved = [&](bool from_counts) -> int {
+        HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
+        if (resolve(from_counts) != 0) return -1;
+        HIPCHK(hipMemcpyAsync(h_nocc64, d_nocc, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost, s));
         return 0;
     };
     if (!fused && materialised() != 0) return -1;
-    if (stage_timing) HIPCHK(hipEventRecord(ev[4], s));
-    if (resolve(fused) != 0) return -1;
-    if (stage_timing) HIPCHK(hipEventRecord(ev[5], s));
-    if (late_count) {
-        /* the batch's one round trip: hit count, occlusion totals, the queue's overflow flag */
-        HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(nhit), hipMemcpyDeviceToHost, s));
-        if (qslot >= 0) HIPCHK(hipMemcpyAsync(h_qc, a->aoq[qslot].q.qcount, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        nhit = *h_nhit;
-        if (stage_timing) fprintf(stderr, "[lucille_hip]   fused AO stage: %u rays through the fix-up queue (budget %u)\n", h_qc[0], a->ao_budget ? a->ao_budget : a->dev.ray_budget);
+    if (tm) HIPCHK(hipEventRecord(tm->ev[4], s));
+    if (resolved(fused) != 0) return -1;
+    if (tm) HIPCHK(hipEventRecord(tm->ev[5], s));
+    if (late) {
+        /* the stage's one round trip: hit count, occlusion totals, the queue's overflow flag */
+        if (wait_queue() != 0) return -1;
         if (h_qc[1] != 0) {                           /* more than LH_AO_QCAP uncertain AO rays: the stage once more, materialised */
             fused = false;
-            if (materialised() != 0 || resolve(false) != 0) return -1;
+            if (materialised() != 0 || resolved(false) != 0) return -1;
             HIPCHK(hipStreamSynchronize(s));
         }
     } else HIPCHK(hipStreamSynchronize(s));
-    const size_t nao = (size_t)nhit * N;
-    for (int k = 0; k < 64; k++) nocc += h_nocc64[k];
-    if (stage_timing) {
-        float ms[5] = {0, 0, 0, 0, 0};
-        for (int k = 0; k < 5; k++) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-        fprintf(stderr, "[lucille_hip] AO batch stages (ms): primary %.3f closest %.3f compact %.3f ao %.3f resolve %.3f | samples %zu hits %llu ao rays %zu\n",
-                ms[0], ms[1], ms[2], ms[3], ms[4], S, nhit, nao);
-        for (int k = 0; k < 6; k++) (void)hipEventDestroy(ev[k]);
-        std::vector<unsigned long long> clk(6 * nwaves);
-        HIPCHK(hipMemcpy(clk.data(), a->r_diag.p, sizeof(unsigned long long) * 6 * nwaves, hipMemcpyDeviceToHost));
-        for (int launch = 0; launch < 2; launch++) {
-            const unsigned long long *st = clk.data() + 3 * nwaves * launch, *ex = st + nwaves, *dry = ex + nwaves;
-            unsigned long long t0 = ~0ull; std::vector<double> e;
-            for (size_t w = 0; w < nwaves; w++) if (st[w] && st[w] < t0) t0 = st[w];
-            for (size_t w = 0; w < nwaves; w++) if (ex[w]) e.push_back((double)(ex[w] - t0) * 1e-5);        /* 100 MHz -> ms */
-            if (e.empty()) continue;
-            std::sort(e.begin(), e.end());
-            auto q = [&](double f) { return e[(size_t)(f * (e.size() - 1))]; };
-            double last_start = 0; for (size_t w = 0; w < nwaves; w++) if (st[w]) last_start = fmax(last_start, (double)(st[w] - t0) * 1e-5);
-            fprintf(stderr, "[lucille_hip]   %s kernel: %zu waves, last start %.3f ms; exits (ms) min %.3f p10 %.3f p50 %.3f p90 %.3f p99 %.3f max %.3f\n",
-                    launch ? "AO" : "closest", e.size(), last_start, e.front(), q(0.10), q(0.50), q(0.90), q(0.99), e.back());
-            /* when a wave found every cursor dry, and how long it went on after that (its last range and its slowest last rays) */
-            std::vector<double> d, g;
-            for (size_t w = 0; w < nwaves; w++) if (dry[w] && ex[w]) { d.push_back((double)(dry[w] - t0) * 1e-5); g.push_back((double)(ex[w] - dry[w]) * 1e-5); }
-            if (!d.empty()) {
-                std::sort(d.begin(), d.end()); std::sort(g.begin(), g.end());
-                auto qq = [&](std::vector<double> &v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
-                fprintf(stderr, "[lucille_hip]     cursors found dry at (ms) min %.3f p50 %.3f p90 %.3f max %.3f; exit - dry (ms) min %.3f p10 %.3f p50 %.3f p90 %.3f p99 %.3f max %.3f (%zu waves)\n",
-                        d.front(), qq(d, 0.5), qq(d, 0.9), d.back(), g.front(), qq(g, 0.1), qq(g, 0.5), qq(g, 0.9), qq(g, 0.99), g.back(), d.size());
-            }
-        }
+    out->nhit = nhit; out->nocc = 0; out->fused = fused;
+    for (int k = 0; k < 64; k++) out->nocc += h_nocc64[k];
+    if (cnt) HIPCHK(hipMemcpy(out->cnt, cnt, sizeof(out->cnt), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands */
+static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0, int y0,
+                     uint64_t valid_pixels, int ps, int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb,
+                     lh_tile_stats_t *stats, void *stream)
+{
+    const int h = nbands * band_rows;              /* lines of the batch */
+    HIPCHK(hipSetDevice(a->device));
+    hipStream_t s = (hipStream_t)stream;
+    const ao_grid g = ao_sample_grid(gather_nsamples);
+    const size_t S = (size_t)w * h * ps * ps;
+    if ((unsigned long long)cam->width * (unsigned long long)cam->height * (unsigned long long)(ps * ps) >= (1ull << 34))
+        return fail("AO pipeline: more than 2^34 samples in the frame (slot keys carry 34 bits)");
+    if (S >= ((size_t)1 << 31)) return fail("AO pipeline: more than 2^31 samples in one batch; render the frame in tiles");     /* 32-bit sample indices on the device */
+    const unsigned nb = (unsigned)((S + 255) / 256);
+    lh_ao_scratch *b = &a->tile_ao;
+    if (ensure_buf(&a->r_org, S * 24) || ensure_buf(&a->r_dir, S * 24) || ensure_buf(&a->r_prim, S * 4) ||
+        ensure_buf(&a->r_t, S * 8) || ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8) ||
+        ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
+    /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
+    unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
+    if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+    /* LH_STAGE_TIMING=1: events between the stages, and the wall clock at which every persistent wave starts and leaves (two launches: closest, AO) */
+    stage_timer timer, *tm = getenv("LH_STAGE_TIMING") ? &timer : NULL;
+    const size_t nwaves = (size_t)a->grid_blocks * (LH_BLOCK / 64);
+    lh_launch_opt opt;
+    if (tm) {
+        for (int k = 0; k < 6; k++) HIPCHK(hipEventCreate(&tm->ev[k]));
+        HIPCHK(hipEventRecord(tm->ev[0], s));
+        if (ensure_buf(&a->r_diag, sizeof(unsigned long long) * 6 * nwaves)) return -1;
+        HIPCHK(hipMemsetAsync(a->r_diag.p, 0, sizeof(unsigned long long) * 6 * nwaves, s));
+        opt.diag_clock = (unsigned long long *)a->r_diag.p;
     }
-    a->r_nsamples = S; a->r_nslots = (size_t)nhit; a->r_nao = fused ? 0 : nao;
+    /* 1. camera rays */
+    if (lh_render_launch_primary_region(cam, x0, w, nbands, band_rows, d_band_y0, y0, cam->height, ps, ps,
+                                        (double *)a->r_org.p, (double *)a->r_dir.p, s) != 0)
+        return fail("primary ray kernel launch failed");
+    if (tm) HIPCHK(hipEventRecord(tm->ev[1], s));
+    /* 2. closest hit */
+    if (lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, a->r_org.p, a->r_dir.p, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt},
+                  LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
+    if (tm) { HIPCHK(hipEventRecord(tm->ev[2], s)); opt.diag_clock += 3 * nwaves; }
+    unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of k_ao_resolve's 64 counters */
+    auto resolve = [&](bool from_counts) -> int {
+        if (lh_render_launch_resolve(w, h, band_rows, ps, ps, g.N, (const uint32_t *)b->slot.p, (const uint8_t *)b->occ.p,
+                                     from_counts ? (const unsigned int *)b->occcount.p : NULL, (float *)d_rgb, a->d_total, s) != 0)
+            return fail("resolve kernel launch failed");
+        return 0;
+    };
+    ao_totals tot = {};
+    if (a->hs->bvh.ntris) {
+        /* 3. compaction (deterministic: hits in sample order) */
+        if (ensure_buf(&b->hitrec, S * 96) || ensure_buf(&b->key, S * 8)) return -1;   /* worst case: every sample hits */
+        if (lh_render_launch_compact(&a->dev, (const double *)a->d_nrm9, S, (const double *)a->r_org.p,
+                                     (const double *)a->r_dir.p, (const uint32_t *)a->r_prim.p, (const double *)a->r_t.p,
+                                     (const double *)a->r_u.p, (const double *)a->r_v.p, (uint32_t *)b->blocks.p,
+                                     (uint32_t *)b->slot.p, (double *)b->hitrec.p, (unsigned long long *)b->key.p,
+                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, s) != 0)
+            return fail("compaction kernels failed: %s", hipGetErrorString(hipGetLastError()));
+        HIPCHK(hipMemcpyAsync(d_nhit, a->d_total, sizeof(*d_nhit), hipMemcpyDeviceToDevice, s));
+        /* 4-6.  Late: the persistent kernel's 32-bit ray index covers the worst case; the grouped order ("ao_group") needs the count on the host */
+        const bool fused = a->ao_fused && !d_uniforms;
+        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && !a->dev.ao_group && !getenv("LH_AO_SYNC");
+        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, s, &tot) != 0) return -1;
+    } else {          /* an empty scene: every sample is a miss */
+        HIPCHK(hipMemsetAsync(b->slot.p, 0xFF, S * 4, s));
+        HIPCHK(hipMemsetAsync(d_nhit, 0, sizeof(*d_nhit), s));
+        if (tm) { HIPCHK(hipEventRecord(tm->ev[3], s)); HIPCHK(hipEventRecord(tm->ev[4], s)); }
+        HIPCHK(hipMemsetAsync(a->d_total, 0, sizeof(unsigned long long) * 64, s));
+        if (resolve(false) != 0) return -1;
+        if (tm) HIPCHK(hipEventRecord(tm->ev[5], s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    const size_t nao = (size_t)tot.nhit * g.N;
+    if (tm && stage_report(*tm, a->r_diag.p, nwaves, S, tot.nhit, nao) != 0) return -1;
+    a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao;
     if (cnt) {
-        unsigned long long hc[LH_CNT_DEV];
-        HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-        a->stat[0] += hc[LH_CNT_NODES]; a->stat[1] += hc[LH_CNT_TRIS]; a->stat[2] += hc[LH_CNT_EXACT];
-        a->stat[3] += hc[LH_CNT_RAYS]; a->stat[4] += nhit + nocc;
-        a->stat_slots[0] += hc[LH_CNT_NODE_SLOTS]; a->stat_slots[1] += hc[LH_CNT_TRI_SLOTS]; a->stat_slots[2] += hc[LH_CNT_REGROUP_SLOTS];
+        lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
             fprintf(stderr, "[lucille_hip] AO batch: rays by node visits (bucket b: [2^(b-1), 2^b)):");
-            for (int b = 0; b < 24; b++) fprintf(stderr, " %llu", hc[LH_CNT_HIST + b]);
+            for (int k = 0; k < 24; k++) fprintf(stderr, " %llu", tot.cnt[LH_CNT_HIST + k]);
             fprintf(stderr, "\n");
         }
     }
     if (stats) {
-        stats->primary_rays = valid_pixels * (uint64_t)(ps * ps); stats->primary_hits = nhit; stats->ao_rays = nao; stats->ao_occluded = nocc;
+        stats->primary_rays = valid_pixels * (uint64_t)(ps * ps); stats->primary_hits = tot.nhit; stats->ao_rays = nao; stats->ao_occluded = tot.nocc;
     }
     HIPCHK(hipStreamSynchronize(s));
     return 0;
@@ -290,8 +313,7 @@ extern "C" int lh_render_ao_tile_host(lh_accel_t *a, const lh_camera_t *cam, int
     if (ensure_buf(&a->r_frame, fb)) return -1;
     void *d_uni = NULL;
     if (uniforms) {
-        const int nphi = (int)sqrt((double)gather_nsamples);
-        const size_t need = (size_t)2 * nphi * nphi * w * h * ps * ps;       /* worst case: every sample hits */
+        const size_t need = (size_t)2 * ao_sample_grid(gather_nsamples).N * w * h * ps * ps;       /* worst case: every sample hits */
         if (nuniforms < need) return fail("lh_render_ao_tile_host: %zu uniforms given, the tile may consume %zu", nuniforms, need);
         if (ensure_buf(&a->r_uni, need * sizeof(double))) return -1;
         HIPCHK(hipMemcpyAsync(a->r_uni.p, uniforms, need * sizeof(double), hipMemcpyHostToDevice, a->stream));
@@ -304,20 +326,8 @@ extern "C" int lh_render_ao_tile_host(lh_accel_t *a, const lh_camera_t *cam, int
 }
 
 /* ------------------------------------------------------------------------ */
-/* the AO stage for a caller's batch of hit records (ao_region's stages 3-6)  */
+/* a caller's batch of hit records: its own compaction, then ao_stage         */
 /* ------------------------------------------------------------------------ */
-extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
-                                              const uint32_t *d_index, const uint32_t *d_count, const double *d_org, const double *d_dir,
-                                              const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
-                                              const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
-                                              double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
-                                              uint32_t *d_nslots32, void *stream);
-extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
-                                              const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
-                                              uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream);
-extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigned long long *d_nslots, int ntheta, int nphi,
-                                                unsigned long long seed, const double *d_hitrec, const double *d_rnd,
-                                                const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
 
 /* what the three entry points refuse before they look at the accelerator's scene; 1: go on, 0: nothing to do (n_rays == 0) */
 static int ao_batch_args(const char *what, const lh_accel_t *a, size_t n_rays, bool have_arrays, int gather_nsamples,
@@ -351,93 +361,43 @@ extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_or
     if (L == 0) return 0;
     HIPCHK(hipSetDevice(a->device));
     hipStream_t s = (hipStream_t)stream;
-    const int nphi = (int)sqrt((double)gather_nsamples), ntheta = nphi, N = nphi * ntheta;   /* ambientocclusion.c:378-380 */
+    const ao_grid g = ao_sample_grid(gather_nsamples);
     const uint32_t *idx = (const uint32_t *)d_index, *cntp = (const uint32_t *)d_count;
+    lh_ao_scratch *b = &a->batch_ao;
     if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65)) return -1;
     unsigned long long *d_nhit = (unsigned long long *)a->b_tot.p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
     if (a->hs->bvh.ntris == 0) {          /* an empty scene: every traced ray is a miss, no record array is read */
         HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
-        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, N, NULL, NULL, NULL, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s) != 0)
+        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, g.N, NULL, NULL, NULL, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s) != 0)
             return fail("%s: resolve kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     }
     const unsigned nb = (unsigned)((L + 255) / 256);
-    if (ensure_buf(&a->b_blocks, (size_t)nb * 4) || ensure_buf(&a->b_slot, L * 4) || ensure_buf(&a->b_hitrec, L * 96) ||
-        ensure_buf(&a->b_key, L * 8)) return -1;                     /* worst case: every entry hits */
+    if (ensure_buf(&b->blocks, (size_t)nb * 4) || ensure_buf(&b->slot, L * 4) || ensure_buf(&b->hitrec, L * 96) ||
+        ensure_buf(&b->key, L * 8)) return -1;                     /* worst case: every entry hits */
     unsigned long long *cnt = a->stat_on ? a->d_counters : NULL;          /* lh_accel_trace_statistics: as the tile pipelines' AO stage */
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
     /* 3. compaction: hits in list order, the count stays on the device */
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, L, n_rays, idx, cntp, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
-                                       (const unsigned long long *)d_key, (uint32_t *)a->b_blocks.p, (uint32_t *)a->b_slot.p,
-                                       (double *)a->b_hitrec.p, (unsigned long long *)a->b_key.p, d_nhit, NULL, s) != 0)
+                                       (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)b->slot.p,
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    /* fused: the any-hit kernel makes ray (slot, r) in its refill and reads the slot count where the compaction left it (ao_region's
-     * late count); the grouped order (set_param "ao_group") needs the count on the host: materialised */
-    bool fused = a->ao_fused && !d_uniforms && L * (size_t)N < ((size_t)1 << 31) && !a->dev.ao_group;
-    const bool fused_tried = fused;
-    if (!a->h_read) HIPCHK(hipHostMalloc(&a->h_read, 1024, hipHostMallocDefault));
-    unsigned long long *h_nocc64 = (unsigned long long *)a->h_read, *h_nhit = h_nocc64 + 64; uint32_t *h_qc = (uint32_t *)(h_nocc64 + 65);
-    h_qc[0] = h_qc[1] = 0u; *h_nhit = 0;
-    lh_launch_opt opt;
-    auto materialised = [&](unsigned long long nhit) -> int {
-        const size_t nao = (size_t)nhit * N;
-        if (!nao) return 0;
-        if (ensure_buf(&a->b_aorg, nao * 24) || ensure_buf(&a->b_adir, nao * 24) || ensure_buf(&a->b_occ, nao)) return -1;
-        /* 4. AO rays */
-        if (lh_render_launch_ao_rays((size_t)nhit, ntheta, nphi, seed, (const double *)a->b_hitrec.p, (const double *)d_uniforms,
-                                     (const unsigned long long *)a->b_key.p, (double *)a->b_aorg.p, (double *)a->b_adir.p, s) != 0)
-            return fail("%s: AO ray kernel launch failed", what);
-        /* 5. any-hit */
-        if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));   /* the abandoned fused pass is not counted */
-        return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, a->b_aorg.p, a->b_adir.p, NULL, NULL, NULL, NULL, a->b_occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
-    };
+    /* 4-6.  A fused stage always leaves the count on the device; the grouped order (set_param "ao_group") needs it on the host: materialised */
+    const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && !a->dev.ao_group;
+    /* 6. per-ray occlusion, scattered to the rays' own slots */
     auto resolve = [&](bool from_counts) -> int {
-        /* 6. per-ray occlusion, scattered to the rays' own slots */
-        HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
-        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, N, (const uint32_t *)a->b_slot.p, (const uint8_t *)a->b_occ.p,
-                                           from_counts ? (const unsigned int *)a->b_occcount.p : NULL, (uint32_t *)d_occluded_count,
+        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, g.N, (const uint32_t *)b->slot.p, (const uint8_t *)b->occ.p,
+                                           from_counts ? (const unsigned int *)b->occcount.p : NULL, (uint32_t *)d_occluded_count,
                                            (float *)d_radiance, d_nocc, s) != 0)
             return fail("%s: resolve kernel launch failed", what);
-        HIPCHK(hipMemcpyAsync(h_nocc64, d_nocc, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost, s));
         return 0;
     };
-    if (fused) {
-        if (ensure_buf(&a->b_occcount, L * sizeof(unsigned int))) return -1;
-        const int qslot = lh_aoq_slot(a, s);
-        if (qslot < 0) return -1;
-        lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget */
-        if (a->ao_budget) sc.ray_budget = a->ao_budget;
-        const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;      /* as ao_region: a launch of 2^27 rays or more */
-        if (lh_launch_trace_ao(&sc, L, ntheta, nphi, seed, (const double *)a->b_hitrec.p, (const unsigned long long *)a->b_key.p,
-                               (unsigned int *)a->b_occcount.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
-                               &a->aoq[qslot].q, a->ncus, d_nhit, big, (void *)s) != 0)
-            return fail("%s: fused AO launch failed: %s", what, hipGetErrorString(hipGetLastError()));
-        if (resolve(true) != 0) return -1;
-        /* the call's one round trip: hit count, occlusion totals, the queue's overflow flag */
-        HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(*h_nhit), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h_qc, a->aoq[qslot].q.qcount, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (h_qc[1] != 0) {                           /* more than LH_AO_QCAP uncertain AO rays: the stage once more, materialised */
-            fused = false;
-            if (materialised(*h_nhit) != 0 || resolve(false) != 0) return -1;
-            HIPCHK(hipStreamSynchronize(s));
-        }
-    } else {
-        HIPCHK(hipMemcpyAsync(h_nhit, d_nhit, sizeof(*h_nhit), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (materialised(*h_nhit) != 0 || resolve(false) != 0) return -1;
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    if (cnt) {
-        unsigned long long hc[LH_CNT_DEV], nocc = 0;
-        for (int k = 0; k < 64; k++) nocc += h_nocc64[k];
-        HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-        a->stat[0] += hc[LH_CNT_NODES]; a->stat[1] += hc[LH_CNT_TRIS]; a->stat[2] += hc[LH_CNT_EXACT];
-        a->stat[3] += hc[LH_CNT_RAYS]; a->stat[4] += nocc;
-        a->stat_slots[0] += hc[LH_CNT_NODE_SLOTS]; a->stat_slots[1] += hc[LH_CNT_TRI_SLOTS]; a->stat_slots[2] += hc[LH_CNT_REGROUP_SLOTS];
-    }
+    ao_totals tot;
+    if (ao_stage(a, "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, fused, fused, resolve, s, &tot) != 0)
+        return -1;
+    if (cnt) lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nocc, true);
     return 0;
 }
 
@@ -458,10 +418,10 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
         return 0;
     }
     if (!d_slot_of_ray || !d_nslots || !d_ao_org || !d_ao_dir) return fail("%s: NULL output array", what);
-    const int nphi = (int)sqrt((double)gather_nsamples), ntheta = nphi, N = nphi * ntheta;
-    if (capacity_rays / (size_t)N < n_rays || capacity_rays < n_rays * (size_t)N)
-        return fail("%s: capacity_rays %zu does not cover the worst case n_rays * N = %zu x %d", what, capacity_rays, n_rays, N);
-    if ((n_rays * (size_t)N + 255) / 256 > 0x7fffffffu) return fail("%s: more than 2^39 AO rays in one call", what);
+    const ao_grid g = ao_sample_grid(gather_nsamples);
+    if (capacity_rays / (size_t)g.N < n_rays || capacity_rays < n_rays * (size_t)g.N)
+        return fail("%s: capacity_rays %zu does not cover the worst case n_rays * N = %zu x %d", what, capacity_rays, n_rays, g.N);
+    if ((n_rays * (size_t)g.N + 255) / 256 > 0x7fffffffu) return fail("%s: more than 2^39 AO rays in one call", what);
     HIPCHK(hipSetDevice(a->device));
     if (a->hs->bvh.ntris == 0) {
         HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
@@ -469,16 +429,16 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
         return 0;
     }
     const unsigned nb = (unsigned)((n_rays + 255) / 256);
-    if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65) || ensure_buf(&a->b_blocks, (size_t)nb * 4) ||
-        ensure_buf(&a->b_hitrec, n_rays * 96) || ensure_buf(&a->b_key, n_rays * 8)) return -1;
+    if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65) || ensure_buf(&a->batch_ao.blocks, (size_t)nb * 4) ||
+        ensure_buf(&a->batch_ao.hitrec, n_rays * 96) || ensure_buf(&a->batch_ao.key, n_rays * 8)) return -1;
     unsigned long long *d_nhit = (unsigned long long *)a->b_tot.p;
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
-                                       (const unsigned long long *)d_key, (uint32_t *)a->b_blocks.p, (uint32_t *)d_slot_of_ray,
-                                       (double *)a->b_hitrec.p, (unsigned long long *)a->b_key.p, d_nhit, (uint32_t *)d_nslots, s) != 0)
+                                       (const unsigned long long *)d_key, (uint32_t *)a->batch_ao.blocks.p, (uint32_t *)d_slot_of_ray,
+                                       (double *)a->batch_ao.hitrec.p, (unsigned long long *)a->batch_ao.key.p, d_nhit, (uint32_t *)d_nslots, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, ntheta, nphi, seed, (const double *)a->b_hitrec.p, (const double *)d_uniforms,
-                                         (const unsigned long long *)a->b_key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
+    if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, g.ntheta, g.nphi, seed, (const double *)a->batch_ao.hitrec.p, (const double *)d_uniforms,
+                                         (const unsigned long long *)a->batch_ao.key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
         return fail("%s: AO ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
     return 0;
 }
@@ -493,8 +453,7 @@ extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org,
     if (go <= 0) return go;
     if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
     const size_t n = n_rays;
-    const int nphi = (int)sqrt((double)gather_nsamples);
-    const size_t need = uniforms ? (size_t)2 * nphi * nphi * n : 0;          /* worst case: every ray hits */
+    const size_t need = uniforms ? (size_t)2 * ao_sample_grid(gather_nsamples).N * n : 0;          /* worst case: every ray hits */
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
@@ -523,8 +482,8 @@ extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t 
 {
     lh_guard guard(a);
     if (!a || !a->committed || !d_ptr || !count) return fail("lh_render_scratch: bad argument");
-    lh_buf *b[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_slot, &a->r_hitrec,
-                   &a->r_aorg, &a->r_adir, &a->r_occ};
+    lh_buf *b[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->tile_ao.slot, &a->tile_ao.hitrec,
+                   &a->tile_ao.aorg, &a->tile_ao.adir, &a->tile_ao.occ};
     if (which < 0 || which > 10) return fail("lh_render_scratch: unknown buffer %d", which);
     *d_ptr = b[which]->p;
     *count = which <= 6 ? a->r_nsamples : (which == 7 ? a->r_nslots : a->r_nao);
@@ -534,10 +493,6 @@ extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t 
 /* ------------------------------------------------------------------------ */
 /* hit epilogue for a batch (ri_intersection_state_build)                   */
 /* ------------------------------------------------------------------------ */
-extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
-                                            const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
-                                            const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,
-                                            const double *d_u, const double *d_v, double *d_state, void *stream);
 
 extern "C" int lh_accel_state_build_device(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, const void *d_prim,
                                            const void *d_t, const void *d_u, const void *d_v, void *d_state, void *stream)
@@ -632,9 +587,6 @@ extern "C" int lh_accel_set_environment(lh_accel_t *a, const lh_environment_t *e
     return 0;
 }
 
-extern "C" size_t lh_pt_material_bytes(void);
-extern "C" void lh_pt_material_pack(const lh_material_t *m, void *out);
-
 static int sync_materials(lh_accel_t *a)
 {
     const uint32_t nm = a->hs->nmeshes ? a->hs->nmeshes : 1;
@@ -664,18 +616,6 @@ static int sync_materials(lh_accel_t *a)
 /* ------------------------------------------------------------------------ */
 /* wavefront path tracer (kernels: lh_render.hip, arithmetic: lh_pt.h)       */
 /* ------------------------------------------------------------------------ */
-extern "C" int lh_pt_launch_begin(const lh_camera_t *cam, int x0, int y0, int w, int h, int band_rows, int band_stride, int spp, int s0,
-                                  unsigned long long seed, void *d_cam, uint32_t *d_counts, int ncounts, void *stream);
-extern "C" size_t lh_pt_cam_bytes(void);
-extern "C" int lh_pt_launch_shade(size_t n_max, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
-                                  const uint32_t *d_prim_mesh, const void *d_materials, const lh_material_t *override_mat,
-                                  const float env_rgb[3], const void *d_env_map, int env_w, int env_h, int ref_weights,
-                                  int depth, int max_depth, unsigned long long seed, int s0, int spp, int x0, int y0, int w,
-                                  int band_rows, int band_stride, int full_width, const void *d_cam, uint32_t *d_counts, const double *d_org, const double *d_dir, const uint32_t *d_prim,
-                                  const double *d_t, const double *d_u, const double *d_v, const uint32_t *d_path_of,
-                                  const float *d_thr, unsigned long long *d_accum, double *d_org2, double *d_dir2, uint32_t *d_path_of2,
-                                  float *d_thr2, int ncus, void *stream);
-extern "C" int lh_pt_launch_resolve(int w, int h, int band_rows, float inv_total_spp, unsigned long long *d_accum, float *d_rgb, void *stream);
 
 /* the pass over a w-wide region of h lines = full bands of band_rows lines, band k starting at frame line y0 + k * band_stride
  * (an ordinary tile: band_rows = h) */
@@ -746,7 +686,7 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
     if (cnt) {
         unsigned long long hc[LH_CNT_N];
         HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
-        a->stat[0] += hc[LH_CNT_NODES]; a->stat[1] += hc[LH_CNT_TRIS]; a->stat[2] += hc[LH_CNT_EXACT]; a->stat[3] += hc[LH_CNT_RAYS];
+        lh_stat_add(a, hc, hc[LH_CNT_RAYS], 0);
     }
     if (stats) {
         uint64_t rays = 0, depth = 0;

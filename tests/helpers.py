@@ -307,3 +307,30 @@ RASTER_GOLDEN_CASES = (
     dict(seed=13, ntri=1500, width=48, height=48, nbeams=6, tri_size=0.25),
     dict(seed=17, ntri=300, width=128, height=128, nbeams=6, eye=(-0.4, 0.3, -0.2), fov=60.0),   # two columns per lane on the device
 )
+
+
+# the frame whose fused AO stage overflows its fix-up queue at "ray_budget" 1: golden ao_c1 tessellated three levels, 2 x 2 pixel samples,
+# 16 AO samples (tests/test_gpu_parity.py::test_cooperative_walk_in_the_fused_ao_stage has the measured number of appends)
+AO_OVERFLOW_FRAME = (1280, 960)
+
+
+def ao_overflow_case():
+    """-> (committed accelerator, camera) of that frame"""
+    import lucille_amd as la
+    from lucille_amd import scenes
+    g = load_golden("ao_c1")
+    acc = la.HipAccel(0)
+    for k in range(int(g["ngeoms"])):
+        P, I = scenes.tessellate(g["pos%d" % k], g["idx%d" % k], 3); acc.add_mesh(P, I)
+    acc.commit()
+    c = g["camera"]
+    return acc, la.Camera.make(AO_OVERFLOW_FRAME[0], AO_OVERFLOW_FRAME[1], c[16], c[:16], int(c[19]))
+
+
+def scratch_count(acc, which):
+    """elements of a scratch buffer of the last render_ao_tile call (HipAccel.scratch without the copy to the host); buffer 8, the
+    materialised AO rays: primary hits x N when the AO stage ended materialised, 0 when it ended fused"""
+    p = C.c_void_p(); n = C.c_size_t()
+    assert acc.L.lh_render_scratch(acc.h, which, C.byref(p), C.byref(n)) == 0
+    return n.value
+

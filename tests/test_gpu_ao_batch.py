@@ -120,6 +120,39 @@ def test_equals_the_tile_pipeline_builtin_generator(c1, ps, which):
     assert np.array_equal(acc.scratch(8, np.float64, 3), s[8])
 
 
+# ---- 1b. a fix-up queue that overflows ---------------------------------------------------------------------------------
+def test_queue_overflow_falls_back_to_materialised():
+    """the frame of test_gpu_parity.py::test_cooperative_walk_in_the_fused_ao_stage whose fused stage overflows its queue at
+    "ray_budget" 1: the tile says so (its scratch holds materialised AO rays), the batch's AO rays are the tile's (test 1) through
+    the same stage, and the batch call answers as at budget 256 and as the materialised stage, bit for bit"""
+    from tests.helpers import ao_overflow_case, scratch_count
+    acc, cam = ao_overflow_case()
+    W, H, NS, N = cam.width, cam.height, 16, 16
+    try:
+        acc.set_param("ray_budget", 1)
+        _, st = acc.render_ao_tile(cam, 0, 0, W, H, 2, NS, seed=5)
+        assert scratch_count(acc, 8) == st["primary_hits"] * N > 0            # the tile's fused launch overflowed
+        s = {k: acc.scratch(k, dt, w) for k, dt, w in ((0, np.float64, 3), (1, np.float64, 3), (2, np.uint32, 1), (3, np.float64, 1),
+                                                        (4, np.float64, 1), (5, np.float64, 1))}
+        n = s[0].shape[0]
+        assert n == W * H * 4
+        org, dr = dev(s[0]), dev(s[1])
+        rec = (dev(s[2]), dev(s[3]), dev(s[4]), dev(s[5]))
+        miss = s[2] == po.MISS
+        acc.set_param("ray_budget", 256)
+        ref_c, ref_r = ao(acc, org, dr, rec, NS, 1, seed=5, out=poison(n))
+        assert (ref_c[miss] == NO_HIT).all() and (ref_r[miss] == 0.0).all()
+        assert int((~miss).sum()) == st["primary_hits"] and (ref_c[~miss] <= N).all() and int(ref_c[~miss].sum()) == st["ao_occluded"]
+        acc.set_param("ray_budget", 1)
+        for fused in (1, 0):
+            cnt, rad = ao(acc, org, dr, rec, NS, fused, seed=5, out=poison(n))
+            assert np.array_equal(cnt, ref_c), (fused, int((cnt != ref_c).sum()))
+            assert np.array_equal(rad.view(np.uint32), ref_r.view(np.uint32)), fused
+    finally:
+        acc.set_param("ray_budget", 128); acc.set_param("ao_fused", 1)
+        acc.close()
+
+
 # ---- 2. replay ------------------------------------------------------------------------------------------------------
 def test_replay_with_caller_uniforms(c1):
     acc, cam = c1["acc"], c1["cam"]

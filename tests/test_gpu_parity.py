@@ -529,27 +529,32 @@ def test_cooperative_walk_keeps_every_bit(budget):
 def test_cooperative_walk_in_the_fused_ao_stage():
     """the AO frame must not depend on the visit budget: tiny budgets send most AO rays through the fix-up queue and the
     cooperative walk (SRC 1: rays regenerated from (slot, sample)); a queue that overflows falls back to the materialised
-    stage -- same frame bit for bit"""
+    stage -- same frame bit for bit.
+
+    The overflow frame is the smallest of 800 x 600, 1024 x 768 and 1280 x 960 whose fused launch at "ray_budget" 1 appends at least
+    1.25 x LH_AO_QCAP (4 194 304) entries to the queue (the count depends on wave scheduling: rays that finish before their wave's
+    first regroup are never queued).  Measured on an MI355X (LH_STAGE_TIMING=1, "fused AO stage: N rays through the fix-up queue"):
+    2 728 953 (0.65 x), 4 486 034 (1.07 x), 7 055 207 (1.68 x) of 12.7 M, 20.8 M, 32.5 M AO rays -> 1280 x 960 (tests/helpers.py
+    AO_OVERFLOW_FRAME)"""
     import torch
-    from lucille_amd import render, scenes
-    g = load_golden("ao_c1")
-    acc = la.HipAccel(0)
-    for k in range(int(g["ngeoms"])):
-        P, I = scenes.tessellate(g["pos%d" % k], g["idx%d" % k], 3); acc.add_mesh(P, I)
-    acc.commit()
-    c = g["camera"]; cam = la.Camera.make(200, 150, c[16], c[:16], int(c[19]))
+    from lucille_amd import render
+    from tests.helpers import ao_overflow_case, scratch_count
+    acc, big = ao_overflow_case()
+    c = load_golden("ao_c1")["camera"]; cam = la.Camera.make(200, 150, c[16], c[:16], int(c[19]))
     ref_img, ref_stats = render.render_ao_frame(acc, cam, 2, 16, tile=200, seed=5)
     for budget in (2, 9, 40):
         acc.set_param("ray_budget", budget)
         img, stats = render.render_ao_frame(acc, cam, 2, 16, tile=200, seed=5)
         torch.cuda.synchronize()
         assert stats == ref_stats and torch.equal(img, ref_img), budget
-    acc.set_param("ray_budget", 1)                 # 960 k AO rays, all out of budget: fits the queue (2^20)
-    big = la.Camera.make(400, 300, c[16], c[:16], int(c[19]))
+    # the overflow, rendered as ONE tile so that the tile's scratch tells how the stage ended
+    W, H = big.width, big.height
     acc.set_param("ray_budget", 256)
-    ref_big, st_big = render.render_ao_frame(acc, big, 2, 16, tile=400, seed=5)
-    acc.set_param("ray_budget", 1)                 # ~4 M AO rays out of budget: the queue overflows -> materialised stage
-    img, stats = render.render_ao_frame(acc, big, 2, 16, tile=400, seed=5)
+    ref_big, st_big = acc.render_ao_tile(big, 0, 0, W, H, 2, 16, seed=5)
+    assert scratch_count(acc, 8) == 0                                       # ended fused
+    acc.set_param("ray_budget", 1)                 # every AO ray that outlives its wave's first regroup is queued: more than LH_AO_QCAP (2^22)
+    img, stats = acc.render_ao_tile(big, 0, 0, W, H, 2, 16, seed=5)
     torch.cuda.synchronize()
+    assert scratch_count(acc, 8) == st_big["primary_hits"] * 16 > 0         # ended materialised
     assert stats == st_big and torch.equal(img, ref_big)
     acc.close()
