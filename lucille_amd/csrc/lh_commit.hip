@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "lh_internal.h"
+#include "lh_danger.h"
 
 static thread_local char g_err[512] = "";
 
@@ -476,8 +477,8 @@ static void publish_scene(lh_accel_t *a)
         d->grid_lo[k] = b->grid_lo[k]; d->grid_step[k] = b->grid_step[k];
         d->scene_r = fmaxf(d->scene_r, fmaxf(fabsf(b->bmin[k]), fabsf(b->bmax[k])));
     }
-    d->deg_dcap = b->deg_dcap < 3.0e38 ? (float)b->deg_dcap : INFINITY;
-    d->cap_srcs = (d->deg_dcap < 3.0e38f ? 1u : 0u) | (d->deg_dcap < 1.0f ? 6u : 0u);
+    d->deg_dcap = lh_dcap_device(b->deg_dcap);          /* lh_danger.h: rounded toward zero, never above the double the host walk compares with */
+    d->cap_srcs = lh_dcap_srcs(b->deg_dcap);
     /* lh_accel_info's device_bytes.  A received scene counts the 64 bytes behind its triangle records, an uploaded or
      * device-built one does not: kept as it was, the figure is compared across versions */
     scene_row r[LH_SCENE_ROWS];
@@ -821,19 +822,13 @@ static int lh_danger_scan(lh_accel_t *a)
     }
     pthread_mutex_unlock(&g_scene_mu);
     {   /* the union of the listed boxes on the scene's 16-bit grid, a cell wider on every side (the nodes' own boxes are rounded outward
-         * the same way: lh_bvh.c).  A union that leaves the grid (a leaf that also holds a triangle outside the traversal tree's bounds):
-         * round 5's rule */
+         * the same way: lh_bvh.c).  A union that leaves the grid on any side (a leaf that also holds a triangle outside the traversal
+         * tree's bounds, however little outside): round 5's rule (lh_danger.h lh_danger_pack) */
         double u[6] = {1.0e308, 1.0e308, 1.0e308, -1.0e308, -1.0e308, -1.0e308};
         for (unsigned long long i = 0; i < cnt; i++)
             for (int k = 0; k < 3; k++) { u[k] = fmin(u[k], h[8 + 6 * i + k]); u[3 + k] = fmax(u[3 + k], h[8 + 6 * i + 3 + k]); }
         uint32_t w[3];
-        for (int k = 0; k < 3; k++) {
-            const double g0 = (double)hs->bvh.grid_lo[k], st = (double)hs->bvh.grid_step[k];          /* the host scene's: a->dev's copy is set later in a device-built commit */
-            const double qlo = floor((u[k] - g0) / st) - 1.0, qhi = ceil((u[3 + k] - g0) / st) + 1.0;
-            if (!(st > 0.0) || !(qlo >= -2.0) || !(qhi <= 65537.0)) return 0;          /* (also a NaN) */
-            const uint32_t lo = qlo < 0.0 ? 0u : (uint32_t)qlo, hi = qhi > 65535.0 ? 65535u : (uint32_t)qhi;
-            w[k] = lo | hi << 16;
-        }
+        if (!lh_danger_pack(u, hs->bvh.grid_lo, hs->bvh.grid_step, w)) return 0;          /* the host scene's grid: a->dev's copy is set later in a device-built commit */
         for (int k = 0; k < 3; k++) a->dev.danger[k] = w[k];
     }
     a->dev.ndanger = (uint32_t)cnt;

@@ -24,6 +24,7 @@
 
 #include "lh_bvh.h"
 #include "lh_refbvh.h"
+#include "lh_danger.h"
 
 /* fmaxf / fminf with their IEEE meaning (a NaN operand is ignored), inline: without -ffinite-math-only gcc calls libm for each of
  * the eight in a slab test -- 200 calls per ray, two thirds of this file's time -- and that switch would let the compiler drop the
@@ -106,8 +107,11 @@ static void hw_resolve(const lh_bvh_t *b, const lh_refbvh_t *ref, uint32_t prim,
     }
 }
 
-/* lh_walk.h danger_hit on the host: test_ray_aabb (bvh.c:869-936) against the listed leaf boxes, the same fp64 expressions */
-static int hw_danger_hit(const lh_bvh_t *b, uint32_t nd, const double o[3], const double d[3])
+/* lh_walk.h ray_needs_ref_walk's box test on the host: a superset of test_ray_aabb (bvh.c:869-936) against the listed leaf boxes.  The
+ * same fp64 expressions on every axis the reference divides by; an axis with |d| <= 1e-14, where the reference multiplies by +-DBL_MAX
+ * (bvh.c:473-497: a miss unless the origin lies within the slab, and on one of its two faces), is not asked at all.  External linkage:
+ * tests/cpu_model calls it ray by ray (tests/test_danger_routing_model.py) */
+int lh_danger_hit(const lh_bvh_t *b, uint32_t nd, const double o[3], const double d[3])
 {
     uint32_t i; int k;
     for (i = 0; i < nd; i++) {
@@ -140,7 +144,7 @@ int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double
         const double D = fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2])));
         if (D > b->deg_dcap) {
             const uint32_t nd = __atomic_load_n(&b->ndanger, __ATOMIC_ACQUIRE);
-            refw = (nd == LH_DANGER_ALL || D > LH_DEG_DCAP_ALL) ? 1 : hw_danger_hit(b, nd, o, d);
+            refw = (nd == LH_DANGER_ALL || D > LH_DEG_DCAP_ALL) ? 1 : lh_danger_hit(b, nd, o, d);
         }
     }
     if (!refw) {

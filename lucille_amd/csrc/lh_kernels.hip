@@ -686,8 +686,8 @@ __device__ __forceinline__ void trace_persist_lane(
             stk[0][tid] = kDone;
             /* rays beyond deg_dcap are the reference walk's (lh_walk.h).  cap_srcs (host-set, scalar): can a ray of THIS source exceed it at all --
              * dumps whenever it is finite; camera and AO rays (unit vectors) only where a zero-area triangle of |e1|_1 |e2|_1 > 1 stayed in the
-             * tree.  Every other scene skips the test whole */
-            if ((SRC == 0 ? (sc.cap_srcs & 1u) != 0u : sc.deg_dcap < 1.0f) && __builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
+             * tree: the bit is set from the DOUBLE cap (lh_danger.h lh_dcap_srcs): the float cap of such a scene may be 1.0f.  Every other scene skips the test whole */
+            if ((sc.cap_srcs & (1u << SRC)) != 0u && __builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
             it0 = it;
         }
         const unsigned long long work = __ballot((L.cur != kDone) | (pend != 0));

@@ -18,6 +18,7 @@
 #include "lh_refbvh.h"
 #include "lh_filter.h"
 #include "lh_reftrace.h"
+#include "lh_danger.h"
 
 #define MISS 0xFFFFFFFFu
 #define DONE ((int32_t)0x80000000)
@@ -230,4 +231,45 @@ int lhm_hostwalk(const lh_bvh_t *b, const lh_refbvh_t *ref, size_t n, const doub
     size_t i; int hits = 0;
     for (i = 0; i < n; i++) hits += lh_host_walk_closest(b, ref, org + 3 * i, dir + 3 * i, prim + i, t + i, u + i, v + i) > 0;
     return hits;
+}
+
+/* ---- the routing decision around zero-area triangles that stay in the tree (lh_danger.h, lh_walk.h ray_needs_ref_walk): the PRODUCT's
+ * arithmetic, callable ray by ray (tests/test_danger_routing_model.py) ---- */
+int lhm_danger_pack(const double u[6], const float glo[3], const float gstep[3], uint32_t w[3]) { return lh_danger_pack(u, glo, gstep, w); }
+float lhm_dcap_device(double cap) { return lh_dcap_device(cap); }
+uint32_t lhm_dcap_srcs(double cap) { return lh_dcap_srcs(cap); }
+double lhm_deg_dcap(const lh_bvh_t *b) { return b->deg_dcap; }
+
+/* the box the danger scan lists for primitive p (lh_commit.hip k_danger_scan): its leaf's box in the leaf's parent, or the scene box
+ * where the root is the leaf */
+void lhm_ref_leaf_box(const lh_refbvh_t *r, uint32_t p, double out[6])
+{
+    const int leaf = (int)r->prim_leaf[p], parent = r->nodes[leaf].parent; int q;
+    if (parent < 0) { for (q = 0; q < 3; q++) { out[q] = r->bmin[q]; out[3 + q] = r->bmax[q]; } return; }
+    for (q = 0; q < 6; q++) out[q] = r->nodes[parent].box[r->nodes[parent].child[0] == leaf ? 0 : 1][q];
+}
+
+/* lh_hostwalk.c lh_danger_hit over n rays against nd <= LH_DANGER_MAX boxes (bmin xyz, bmax xyz each) */
+int lhm_danger_hit(size_t n, const double *org, const double *dir, uint32_t nd, const double *boxes, uint8_t *out)
+{
+    static lh_bvh_t tmp; size_t i;
+    if (nd == 0 || nd > LH_DANGER_MAX) return -1;
+    memset(&tmp, 0, sizeof(tmp));
+    memcpy(tmp.danger, boxes, sizeof(double) * 6 * nd); tmp.ndanger = nd;
+    for (i = 0; i < n; i++) out[i] = (uint8_t)lh_danger_hit(&tmp, nd, org + 3 * i, dir + 3 * i);
+    return 0;
+}
+
+/* the device's box test of ray_needs_ref_walk: lane_init (lh_ray_setup + lh_ray_setup_grid with the scene's grid and radius as
+ * lh_commit.hip publish_scene sets them), then lh_slab_w against the packed words under the initial culling bound 1e38 */
+void lhm_device_box_test(const lh_bvh_t *b, size_t n, const double *org, const double *dir, const uint32_t w[3], uint8_t *out)
+{
+    float scene_r = 0.0f; size_t i; int k;
+    for (k = 0; k < 3; k++) { scene_r = fmaxf(scene_r, fabsf(b->bmin[k])); scene_r = fmaxf(scene_r, fabsf(b->bmax[k])); }
+    for (i = 0; i < n; i++) {
+        const double *o = org + 3 * i, *d = dir + 3 * i; lh_ray32_t r; float tn;
+        lh_ray_setup(&r, o[0], o[1], o[2], d[0], d[1], d[2], scene_r);
+        lh_ray_setup_grid(&r, b->grid_lo, b->grid_step, scene_r);
+        out[i] = (uint8_t)lh_slab_w(&r, w[0], w[1], w[2], 1.0e38f, &tn);
+    }
 }

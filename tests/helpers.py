@@ -28,7 +28,7 @@ def build_model():
     srcs = [os.path.join(MODEL_DIR, "lh_model.c"), os.path.join(CSRC, "lh_bvh.c"), os.path.join(CSRC, "lh_refbvh.c"),
             os.path.join(CSRC, "lh_hostwalk.c"),           # the product's one-ray host walk, as it is (lhm_hostwalk)
             os.path.join(CSRC, "lh_bvh.h"), os.path.join(CSRC, "lh_filter.h"), os.path.join(CSRC, "lh_refbvh.h"),
-            os.path.join(CSRC, "lh_reftrace.h")]
+            os.path.join(CSRC, "lh_reftrace.h"), os.path.join(CSRC, "lh_danger.h")]
     if (not os.path.exists(so)) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         tmp = "%s.%d.tmp" % (so, os.getpid())              # pytest-xdist workers build at once: link aside, rename whole
         subprocess.check_call(["gcc", "-O2", "-std=gnu11", "-ffp-contract=off", "-fPIC", "-shared"] + _fma_flag() +
@@ -93,6 +93,12 @@ class Model:
 
     def ref_bbox(self):
         b = np.empty(6); self.lib().lhm_ref_bbox(self.ref, b.ctypes.data_as(_dp)); return b[:3], b[3:]
+
+    def ref_leaf_box(self, prim):
+        """the box of primitive `prim`'s leaf in lucille's own tree as its parent holds it (the scene box where the root is the
+        leaf): what lh_commit.hip's danger scan lists -> (lo[3], hi[3])"""
+        L = self.lib(); L.lhm_ref_leaf_box.argtypes = [C.c_void_p, C.c_uint32, _dp]
+        b = np.empty(6); L.lhm_ref_leaf_box(self.ref, int(prim), b.ctypes.data_as(_dp)); return b[:3], b[3:]
 
     @classmethod
     def ref_off(cls):
@@ -171,6 +177,54 @@ class Model:
         L.lhm_hostwalk(self.h, self.ref if (use_ref and getattr(self, "ref", None)) else None, n, org.ctypes.data_as(_dp), dr.ctypes.data_as(_dp),
                        prim.ctypes.data_as(_u32p), t.ctypes.data_as(_dp), u.ctypes.data_as(_dp), v.ctypes.data_as(_dp))
         return prim, t, u, v
+
+    # ---- the routing decision around zero-area triangles that stay in the tree (lh_danger.h) --------------------
+    @classmethod
+    def danger_pack(cls, box_lo, box_hi, grid_lo, grid_step):
+        """lh_danger_pack: the union box on the grid (float32 grid_lo / grid_step) -> uint32 [3] words (lo | hi << 16), or None:
+        "every ray" (LH_DANGER_ALL)"""
+        L = cls.lib(); fp = C.POINTER(C.c_float)
+        L.lhm_danger_pack.argtypes = [_dp, fp, fp, _u32p]
+        u = np.ascontiguousarray(np.concatenate([box_lo, box_hi]), np.float64)
+        g = np.ascontiguousarray(grid_lo, np.float32); st = np.ascontiguousarray(grid_step, np.float32); w = np.zeros(3, np.uint32)
+        ok = L.lhm_danger_pack(u.ctypes.data_as(_dp), g.ctypes.data_as(fp), st.ctypes.data_as(fp), w.ctypes.data_as(_u32p))
+        return w if ok else None
+
+    @classmethod
+    def dcap_device(cls, cap):
+        """lh_dcap_device: the float the device compares a ray's largest direction component with, as a Python float"""
+        L = cls.lib(); L.lhm_dcap_device.restype = C.c_float; L.lhm_dcap_device.argtypes = [C.c_double]
+        return float(L.lhm_dcap_device(float(cap)))
+
+    @classmethod
+    def dcap_srcs(cls, cap):
+        """lh_dcap_srcs: lh_dev_scene_t.cap_srcs of a (double) cap"""
+        L = cls.lib(); L.lhm_dcap_srcs.restype = C.c_uint32; L.lhm_dcap_srcs.argtypes = [C.c_double]
+        return int(L.lhm_dcap_srcs(float(cap)))
+
+    def deg_dcap(self):
+        L = self.lib(); L.lhm_deg_dcap.restype = C.c_double; L.lhm_deg_dcap.argtypes = [C.c_void_p]
+        return float(L.lhm_deg_dcap(self.h))
+
+    @classmethod
+    def danger_hit(cls, org, dr, boxes):
+        """lh_hostwalk.c lh_danger_hit per ray against boxes [nd, 6] (bmin xyz, bmax xyz) -> bool [n]"""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3); dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 3)
+        bx = np.ascontiguousarray(boxes, np.float64).reshape(-1, 6); out = np.zeros(org.shape[0], np.uint8)
+        L = cls.lib(); L.lhm_danger_hit.argtypes = [C.c_size_t, _dp, _dp, C.c_uint32, _dp, C.POINTER(C.c_uint8)]
+        assert L.lhm_danger_hit(org.shape[0], org.ctypes.data_as(_dp), dr.ctypes.data_as(_dp), bx.shape[0], bx.ctypes.data_as(_dp),
+                                out.ctypes.data_as(C.POINTER(C.c_uint8))) == 0
+        return out.astype(bool)
+
+    def device_box_test(self, org, dr, words):
+        """the device's box test per ray (lane_init's lh_ray_setup + lh_ray_setup_grid on this scene's grid, lh_slab_w with
+        tb = 1e38) against packed words -> bool [n]"""
+        org = np.ascontiguousarray(org, np.float64).reshape(-1, 3); dr = np.ascontiguousarray(dr, np.float64).reshape(-1, 3)
+        w = np.ascontiguousarray(words, np.uint32).reshape(3); out = np.zeros(org.shape[0], np.uint8)
+        L = self.lib(); L.lhm_device_box_test.argtypes = [C.c_void_p, C.c_size_t, _dp, _dp, _u32p, C.POINTER(C.c_uint8)]
+        L.lhm_device_box_test(self.h, org.shape[0], org.ctypes.data_as(_dp), dr.ctypes.data_as(_dp), w.ctypes.data_as(_u32p),
+                              out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return out.astype(bool)
 
     def trace_diag(self, org, dr, qnodes=2):
         """closest-hit walk with PER-RAY counts -> ((prim, t, u, v), uint32 [n, 4]: node visits, leaf visits, triangle records
