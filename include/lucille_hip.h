@@ -258,6 +258,43 @@ int  lh_accel_compact_device(size_t n, int record_format, const void *d_prim_or_
                              const void *d_index_in, size_t n_index_in, const void *d_count_in,
                              void *d_index_out, void *d_count_out, void *stream);
 
+/* ---- per-ray maximum distance (tmax): "only up to here", for closest- and any-hit batches ----
+ * Shadow rays toward a point on a light, distance-limited occlusion, visibility between two path vertices, proximity queries.  The
+ * bound prunes the walk; it is not a filter behind an unbounded launch.
+ * The contract is a filter on what the library already guarantees.  For a ray and a bound tmax (the unit of t: multiples of |dir|) let
+ * R = (prim, t, u, v) be the record the unbounded entry points (lh_accel_intersect_device_ex / _indexed / _host_ex) return -- the
+ * reference's, bit for bit.
+ *   - Closest hit: the answer is R if R.prim != LH_MISS and R.t < tmax, the comparison made in fp64; otherwise the miss record of the
+ *     unbounded call (LH_MISS, 1e38, 0.0, 0.0).  LH_REC16: the same record through the same rounding.
+ *   - Any hit: occluded = (R.prim != LH_MISS && R.t < tmax) ? 1 : 0.
+ *   - The comparison is strict, and IEEE's: a NaN, zero or negative tmax gives a miss; +inf, and any value above every t, gives
+ *     exactly the unbounded answer.
+ *   - LH_RAYS_F32: the bounds are floats and a bound IS (double)tmax; LH_RAYS_F64: they are doubles.
+ *   (It is NOT "the reference's walk started with t_best = tmax": the reference has no such parameter -- ri_ray_t.max_t is ignored --
+ *   and that walk culls boxes against t_best.)
+ * The device form.  Rays, records, formats and alignment as for lh_accel_intersect_device_ex.  d_tmax holds n_rays bounds of the ray
+ * format's type, one per ray id (an indexed call addresses it by id, not by list position).  d_index == NULL && n_index == 0 &&
+ * d_count == NULL: every ray is traced and every record slot written.  Otherwise the list has exactly the semantics of
+ * lh_accel_intersect_device_indexed (NULL d_index with n_index > 0: the identity list; min(*d_count, n_index) read on the stream; ids >=
+ * n_rays skipped; duplicates allowed; unlisted slots untouched, byte for byte).  d_tmax == NULL forwards to lh_accel_intersect_device_ex
+ * (no list) or lh_accel_intersect_device_indexed: the unbounded call by construction.  Asynchronous on `stream`; the default variant; over
+ * the 4-wide or the 8-wide nodes as ray dumps are.
+ *   - -1 (lh_last_error), nothing written or enqueued: everything those two refuse, with their message under this entry point's name; a
+ *     d_tmax that is not aligned to its element size ("tmax not aligned"); n_rays > 2^30 ("2^30 rays").  n_rays == 0 returns 0.  On the
+ *     empty scene every traced ray gets the miss record / 0.
+ *   - With lh_accel_trace_statistics on, the call counts as lh_accel_intersect_device_indexed does (and is then synchronous), and
+ *     counters[4] (hits) advances by the traced rays whose answer is a hit after the bound.
+ * The host form is synchronous and correct for every n.  It takes the plain path -- pageable copies through the staging block, one
+ * bounded launch -- in chunks of 2^21 rays, whatever n is: the bounds do not travel through the pinned ring lh_accel_intersect_host_ex
+ * uses from 2 M rays on.  tmax == NULL forwards to lh_accel_intersect_host_ex.  The same refusals (no 2^30 limit). */
+int  lh_accel_intersect_device_tmax(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                                    const void *d_tmax, int ray_format, int record_format,
+                                    void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occluded, int mode,
+                                    const void *d_index, size_t n_index, const void *d_count, void *stream);
+int  lh_accel_intersect_host_tmax(lh_accel_t *accel, size_t n, const void *org_xyz, const void *dir_xyz, const void *tmax,
+                                  int ray_format, int record_format, void *prim_or_rec16, double *t, double *u, double *v,
+                                  uint8_t *occluded, int mode);
+
 /* same launch with traversal statistics: counters[4] (host) receives
  * {inner-node visits, triangle tests, fp64 resolves, rays}; synchronous. */
 int  lh_accel_intersect_device_counted(lh_accel_t *accel, size_t n, const void *d_org_xyz,

@@ -110,7 +110,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 ABI_SYMBOLS = [
     "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
-    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
+    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_intersect_device_tmax", "lh_accel_intersect_host_tmax", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
     "lh_render_ao_tile", "lh_render_ao_tile_host", "lh_render_ao_bands", "lh_render_scratch", "lh_accel_beam_visibility_host", "lh_accel_beam_visibility_device", "lh_accel_beam_visibility_set_host", "lh_accel_beam_raster_host", "lh_accel_beam_raster_device", "lh_accel_beam_raster_set_host", "lh_render_pt_tile",
     "lh_accel_trace_statistics", "lh_accel_statistics", "lh_accel_slot_statistics",
@@ -164,6 +164,8 @@ def lib():
     L.lh_accel_intersect_device_ex.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp]
     L.lh_accel_intersect_device_indexed.argtypes = [vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp, vp]
     L.lh_accel_compact_device.argtypes = [sz, i32, vp, vp, i32, vp, sz, vp, vp, vp, vp]
+    L.lh_accel_intersect_device_tmax.argtypes = [vp, sz, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, sz, vp, vp]
+    L.lh_accel_intersect_host_tmax.argtypes = [vp, sz, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32]
     L.lh_accel_last_retraced.argtypes = [vp]; L.lh_accel_last_retraced.restype = C.c_uint64
     L.lh_accel_dump_node_bytes.argtypes = [vp]
     L.lh_accel_intersect_device_counted.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32,
@@ -277,6 +279,14 @@ def _list_args(index, count, what):
     if count is not None and not (count.is_cuda and count.dtype in words and count.numel() == 1):
         raise ValueError("%s: count must be a one-element int32 / uint32 device tensor" % what)
     return _dptr(index), (0 if index is None else int(index.numel())), _dptr(count)
+
+
+def _tmax_device(tmax, org, what):
+    """a per-ray bound tensor of a device batch: the rays' dtype and device, shape [n], contiguous"""
+    if not (hasattr(tmax, "is_cuda") and tmax.is_cuda and tmax.device == org.device and tmax.dtype == org.dtype
+            and tmax.dim() == 1 and tmax.shape[0] == org.shape[0] and tmax.is_contiguous()):
+        raise ValueError("%s: tmax must be a contiguous device tensor of the rays' dtype and shape [n]" % what)
+    return tmax
 
 
 def compact(records_or_occluded, select, index=None, count=None, out=None, stream=None):
@@ -548,12 +558,42 @@ class HipAccel:
                                                 C.byref(u), C.byref(v)), "lh_accel_intersect1")
         return hit, int(p.value), t.value, u.value, v.value
 
-    def intersect_host(self, org, dr, mode=MODE_CLOSEST, records="f64"):
-        """org, dr: [n, 3] host rays.  float32 inputs (numpy arrays or CPU torch tensors, both float32) are sent as fp32 rays
-        (traced as the widened fp64 rays: the same records); anything else as fp64.  records="rec16" (closest hit): the records
-        come back as one (n, 4) uint32 array of lh_rec16_t {prim, t, u, v as float32 bits}; else (prim, t, u, v) / occluded."""
+    def intersect_host_tmax(self, org, dr, tmax, mode=MODE_CLOSEST, records="f64"):
+        """lh_accel_intersect_host_tmax: intersect_host under a maximum distance per ray -- tmax: n bounds, taken in the rays' precision
+        (float32 rays: float32 bounds).  A ray's answer is the unbounded record if that is a hit with t < tmax, else a miss.  What
+        intersect_host(..., tmax=...) calls."""
         rf = _records_format(records)
         f32 = _is_f32(org) and _is_f32(dr)
+        dt = np.float32 if f32 else np.float64
+        o = _np(org, dt).reshape(-1, 3); d = _np(dr, dt).reshape(-1, 3); tm = _np(tmax, dt).reshape(-1)
+        n = o.shape[0]
+        if tm.shape[0] != n:
+            raise ValueError("intersect_host: tmax must hold one bound per ray (%d for %d rays)" % (tm.shape[0], n))
+        fmt = RAYS_F32 if f32 else RAYS_F64
+        call = lambda rec, t, u, v, occ: _check(self.L.lh_accel_intersect_host_tmax(
+            self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data, fmt, rf, rec, t, u, v, occ, mode), "lh_accel_intersect_host_tmax")
+        if mode == MODE_CLOSEST and rf == REC16:
+            rec = _rec16_host(n)
+            call(rec.ctypes.data, None, None, None, None)
+            return rec
+        if mode == MODE_CLOSEST:
+            prim = np.empty(n, np.uint32); t = np.empty(n); u = np.empty(n); v = np.empty(n)
+            call(prim.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data, None)
+            return prim, t, u, v
+        occ = np.empty(n, np.uint8)
+        call(None, None, None, None, occ.ctypes.data)
+        return occ
+
+    def intersect_host(self, org, dr, mode=MODE_CLOSEST, records="f64", tmax=None):
+        """org, dr: [n, 3] host rays.  float32 inputs (numpy arrays or CPU torch tensors, both float32) are sent as fp32 rays
+        (traced as the widened fp64 rays: the same records); anything else as fp64.  records="rec16" (closest hit): the records
+        come back as one (n, 4) uint32 array of lh_rec16_t {prim, t, u, v as float32 bits}; else (prim, t, u, v) / occluded.
+        tmax (an array of n bounds, taken in the rays' precision; None: unbounded, today's paths): a ray's answer is the unbounded
+        record if that is a hit with t < tmax, else a miss (lh_accel_intersect_host_tmax)."""
+        rf = _records_format(records)
+        f32 = _is_f32(org) and _is_f32(dr)
+        if tmax is not None:
+            return self.intersect_host_tmax(org, dr, tmax, mode=mode, records=records)
         if f32 or rf == REC16:
             dt = np.float32 if f32 else np.float64
             o = _np(org, dt).reshape(-1, 3); d = _np(dr, dt).reshape(-1, 3)
@@ -587,14 +627,16 @@ class HipAccel:
                                               occ.ctypes.data, mode), "lh_accel_intersect_host")
         return occ
 
-    def intersect_device_indexed(self, org, dr, out=None, mode=MODE_CLOSEST, stream=None, records="f64", index=None, count=None):
+    def intersect_device_indexed(self, org, dr, out=None, mode=MODE_CLOSEST, stream=None, records="f64", index=None, count=None, tmax=None):
         """lh_accel_intersect_device_indexed: trace the rays of org / dr ([n, 3] device tensors, float64 or float32) that the list
         names, and write their records to THEIR slots of `out`; every other slot of `out` stays as it is.  index: int32 / uint32
         device tensor of ray ids (None: 0 .. n-1); count: one-element int32 / uint32 device tensor, the number of list entries to
         trace (clamped to the list's length; None: all) -- read by the launch on `stream`, not by the host, so it may be what an
         earlier kernel on that stream is still to write (compact()).  Ids >= n are skipped, an id may appear twice.  out: as for
         intersect_device; when it is None the tensors are allocated here with torch.empty, and the slots of rays that are not
-        listed are then UNSPECIFIED (whatever the allocator handed over).  Returns out."""
+        listed are then UNSPECIFIED (whatever the allocator handed over).  tmax: None, or a device tensor of the rays' dtype and
+        shape [n] -- a bound per ray ID (not per list position): the listed rays' answers under lh_accel_intersect_device_tmax's
+        contract.  Returns out."""
         import torch
         assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
         assert org.is_contiguous() and dr.is_contiguous()
@@ -608,13 +650,18 @@ class HipAccel:
             ni = n
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
+        if tmax is not None:
+            _check(self.L.lh_accel_intersect_device_tmax(self.h, n, _dptr(org), _dptr(dr), _dptr(_tmax_device(tmax, org, "intersect_device_indexed")),
+                                                         fmt, rf, _dptr(prim), _dptr(t), _dptr(u), _dptr(v), _dptr(occ), mode, ip, ni, cp,
+                                                         C.c_void_p(stream)), "lh_accel_intersect_device_tmax")
+            return out
         _check(self.L.lh_accel_intersect_device_indexed(self.h, n, _dptr(org), _dptr(dr), fmt, rf, _dptr(prim), _dptr(t), _dptr(u),
                                                         _dptr(v), _dptr(occ), mode, ip, ni, cp, C.c_void_p(stream)),
                "lh_accel_intersect_device_indexed")
         return out
 
     def intersect_device(self, org, dr, out=None, mode=MODE_CLOSEST, variant=VARIANT_DEFAULT, stream=None,
-                         counters=False, records="f64", index=None, count=None):
+                         counters=False, records="f64", index=None, count=None, tmax=None):
         """org, dr: CUDA(HIP) float64 or float32 tensors [n,3] (both of one dtype: float32 = fp32 rays, traced as the widened
         fp64 rays), contiguous.  Enqueues on `stream` (default: torch's current stream) and returns the output tensors:
         (prim, t, u, v), (occluded,), or with records="rec16" (closest hit) (rec,) -- one (n, 4) int32 tensor of lh_rec16_t
@@ -622,17 +669,31 @@ class HipAccel:
         index / count (device tensors: a list of ray ids, the number of its entries to trace): only the listed rays are traced,
         their records go to their own slots of `out` and no other slot is written (intersect_device_indexed; the default variant,
         without counters).  With out=None the tensors are freshly allocated and the slots of rays that are not listed are
-        UNSPECIFIED."""
+        UNSPECIFIED.
+        tmax (a device tensor of the rays' dtype, shape [n]; None: unbounded, today's paths): a per-ray maximum distance -- a ray's
+        answer is the unbounded record if that is a hit with t < tmax (strict; NaN, 0 and negatives: a miss; +inf: unbounded), else a
+        miss (lh_accel_intersect_device_tmax; the default variant, without counters)."""
         import torch
+        if tmax is not None and (variant != VARIANT_DEFAULT or counters):
+            raise ValueError("bounded batches (tmax) run the default variant without counters")
         if index is not None or count is not None:
             if variant != VARIANT_DEFAULT or counters:
                 raise ValueError("indexed batches run the default variant without counters")
-            return self.intersect_device_indexed(org, dr, out=out, mode=mode, stream=stream, records=records, index=index, count=count)
+            return self.intersect_device_indexed(org, dr, out=out, mode=mode, stream=stream, records=records, index=index, count=count, tmax=tmax)
         assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
         assert org.is_contiguous() and dr.is_contiguous()
         rf = _records_format(records)
         n = org.shape[0]
         dev = org.device
+        if tmax is not None:
+            fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
+            out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
+            if stream is None:
+                stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(self.L.lh_accel_intersect_device_tmax(self.h, n, _dptr(org), _dptr(dr), _dptr(_tmax_device(tmax, org, "intersect_device")), fmt, rf,
+                                                         _dptr(prim), _dptr(t), _dptr(u), _dptr(v), _dptr(occ), mode, None, 0, None,
+                                                         C.c_void_p(stream)), "lh_accel_intersect_device_tmax")
+            return out
         if org.dtype == torch.float32 or rf == REC16:
             if variant != VARIANT_DEFAULT or counters:
                 raise ValueError("fp32 rays / rec16 records run the default variant without counters")

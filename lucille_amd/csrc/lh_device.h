@@ -22,6 +22,9 @@ typedef struct lh_dev_scene {
     const void *q4nodes;      /* lh_q4node_t[nq4nodes] (64 B each): what the default walk reads   */
     uint32_t    nq4nodes, q4_depth;
     uint32_t    q4_stack;  /* rows the 4-wide walk needs (lh_bvh_t); 0: 3 x q4_depth + 5 */
+    uint32_t    idx_nrays; /* indexed ray dumps (`index` below): rays the ray and record arrays of the launch hold, > 0; 0: not an indexed launch -- work item i is
+                              ray i.  (Here, in the four bytes the alignment of q8nodes leaves free: the struct is as large as it was before `tmax` joined it --
+                              the cold kernels keep a copy of it in scratch for their out-of-line walks) */
     const void *q8nodes;      /* lh_q8node_t[nq8nodes] (128 B each), or NULL                       */
     uint32_t    nq8nodes, q8_depth;
     int         prefer_q8;    /* this launch walks the 8-wide nodes (ray dumps over scenes larger than the Infinity Cache) */
@@ -60,11 +63,13 @@ typedef struct lh_dev_scene {
     uint32_t   *diag_out;      /* NULL, or: four counts per ray of this launch (4-wide node visits, leaf visits, triangle records through the fp32
                                   filter, fp64 tests): the per-ray diagnostics of ri_bvh_intersect's `user` argument (bvh.h:103-110, bvh.c:451-456) */
     unsigned long long *diag_clock;   /* diagnostics (LH_STAGE_TIMING): [2][waves] start / exit wall clock of every persistent wave, or NULL */
-    const uint32_t *index;     /* indexed ray dumps (idx_on): the launch's work items are the entries of this list of ray ids, NULL = the identity list;
+    const uint32_t *index;     /* indexed ray dumps (idx_nrays > 0): the launch's work items are the entries of this list of ray ids, NULL = the identity list;
                                   launch-uniform like io_fmt -- read where a ray is loaded (entry -> id), the id is what the lane, the fix-up queue and the
-                                  record stores carry from there on; never read in the node step or the triangle pass */
-    uint32_t    idx_on;        /* 0: work item i is ray i.  1: work item k is ray index[k] (or k), ids >= idx_nrays are skipped */
-    uint32_t    idx_nrays;     /* rays the ray and record arrays of an indexed launch hold */
+                                  record stores carry from there on; never read in the node step or the triangle pass.
+                                  Work item k is ray index[k] (or k), ids >= idx_nrays are skipped */
+    const void *tmax;          /* NULL, or: a bounded launch (lh_accel_intersect_device_tmax; always an indexed one) -- idx_nrays bounds by ray id, doubles, or floats
+                                  with LH_IO_RAYS_F32 (lh_tmax.h).  Read where a ray is loaded and where it retires, by the kernels of their own that such a
+                                  launch runs (k_trace_persist_tmax, k_coop_walk_tmax, k_fixups_tmax, k_trace_small_tmax): no other kernel looks at it */
 } lh_dev_scene_t;
 
 /* traversal statistics accumulated by the COUNT variants (u64 each) */

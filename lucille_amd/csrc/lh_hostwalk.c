@@ -15,6 +15,9 @@
  *   exact-t ties by lucille's own tree (lh_refbvh_tie_winner), fragile hits and rays beyond deg_dcap by the reference's
  *   own walk on that tree (lh_ref_trace) -- as k_fixups / k_coop_walk do on the device.
  *
+ * lh_host_walk_tmax is the same walk under a per-ray maximum distance (lh_tmax.h), closest and any hit: the rule of the bounded device
+ * launches (lh_accel_intersect_device_tmax) in host C, which is how the not-gpu suite checks it (tests/test_tmax_model.py).
+ *
  * Used by lh_accel_intersect1 (lh_query.hip) for scenes whose trees live on the host (host-built commits).  The records
  * equal the device path's bit for bit (tests/test_gpu_single_ray.py compares both with the oracle).
  */
@@ -35,6 +38,7 @@ static inline float hw_minf(float a, float b) { return (a <= b || b != b) ? a : 
 #define fminf(a, b) hw_minf((a), (b))
 #include "lh_filter.h"
 #include "lh_reftrace.h"
+#include "lh_tmax.h"
 
 #if defined(__SSE2__) && defined(__FMA__)
 #include <immintrin.h>
@@ -199,6 +203,93 @@ int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double
         *prim = hit ? p : HW_MISS; *t = tt; *u = uu; *v = vv;
         return hit;
     }
+    *prim = best.prim; *t = best.t; *u = best.u; *v = best.v;
+    return best.prim != HW_MISS;
+}
+
+/* One ray under a maximum distance: closest hit (anyhit 0: the record of lh_host_walk_closest if it is a hit with t < tmax, else the miss record) or
+ * any hit (anyhit 1: returns whether that record is such a hit; the outputs hold the miss record).  The walk above with lh_tmax.h's rule, step for step
+ * as the bounded kernels apply it (lh_walk.h tmax_start / tri_step_g / tmax_retire): the culling bound starts at the fp32 bound, best.t at min(tmax, 1e38);
+ * an any-hit ray ends at a certain fp32 hit only below lh_tmax_sure_below; an accepted hit near the bound is fragile; the reference's own walk runs
+ * unbounded and its record goes through lh_tmax_accept.  Returns 1 / 0, or -2 like lh_host_walk_closest. */
+int lh_host_walk_tmax(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], double tmax, int anyhit,
+                      uint32_t *prim, double *t, double *u, double *v)
+{
+    hw_best_t best = { HW_T_INF, 0.0, 0.0, HW_MISS, 0u };
+    int certain = 0;
+    *prim = HW_MISS; *t = HW_T_INF; *u = 0.0; *v = 0.0;
+    if (b->ntris == 0) return 0;
+    int refw = 0;
+    if (ref) {                                    /* asked without the bound: a superset of the rays the unbounded walk hands to the reference's */
+        const double D = fmax(fabs(d[0]), fmax(fabs(d[1]), fabs(d[2])));
+        if (D > b->deg_dcap) {
+            const uint32_t nd = __atomic_load_n(&b->ndanger, __ATOMIC_ACQUIRE);
+            refw = (nd == LH_DANGER_ALL || D > LH_DEG_DCAP_ALL) ? 1 : lh_danger_hit(b, nd, o, d);
+        }
+    }
+    if (lh_tmax_dead(tmax)) return 0;             /* no t is below it (on the device such a ray fails every box of the root and retires as a miss) */
+    if (!refw) {
+        lh_ray32_t r; float tb = lh_tmax_tb(tmax), scene_r = 0.0f;
+        int32_t stack[HW_STACK]; int sp = 0, k; int32_t cur = 0;
+        uint32_t pend[4]; int np = 0, ovf = 0, done = 0;
+        best.t = lh_tmax_best0(tmax);
+        for (k = 0; k < 3; k++) { scene_r = fmaxf(scene_r, fabsf(b->bmin[k])); scene_r = fmaxf(scene_r, fabsf(b->bmax[k])); }
+        lh_ray_setup(&r, o[0], o[1], o[2], d[0], d[1], d[2], scene_r);
+        lh_ray_setup_grid(&r, b->grid_lo, b->grid_step, scene_r);
+        while (!done) {
+            if (cur >= 0) {
+                const lh_q4node_t *n = &b->q4nodes[cur];
+                uint32_t key[4]; int slot[4], nh = 0, c, m; float tn4[4];
+                const int hitmask = hw_node4(&r, n, tb, tn4);
+                for (c = 0; c < 4; c++) {
+                    union { float f; uint32_t w; } cv;
+                    if (!(hitmask >> c & 1)) continue;
+                    cv.f = tn4[c];
+                    const uint32_t kc = (cv.w & ~3u) | (uint32_t)c;
+                    for (m = nh; m > 0 && key[m - 1] > kc; m--) { key[m] = key[m - 1]; slot[m] = slot[m - 1]; }
+                    key[m] = kc; slot[m] = c; nh++;
+                }
+                for (m = nh - 1; m >= 1; m--) { if (sp < HW_STACK) stack[sp++] = n->ref[slot[m]]; else ovf = 1; }
+                if (nh) cur = n->ref[slot[0]];
+                else if (sp) cur = stack[--sp];
+                else break;
+            } else {
+                const uint32_t x = ~(uint32_t)cur, first = x >> 2, cnt = (x & 3u) + 1u; uint32_t q;
+                for (q = 0; q < cnt && !done; q++) {
+                    const lh_tri32_t *T = &b->tri32[first + q]; float t_hi;
+                    const int cls = lh_tri_filter(&r, T->v0[0], T->v0[1], T->v0[2], T->e1x, T->e1y, T->e1z, T->e2x, T->e2y, T->e2z, T->ne1, T->ne2, tb, &t_hi);
+                    if (cls == LH_TRI_REJECT) continue;
+                    if (anyhit) {
+                        /* a certain hit provably below the bound ends the ray; any other is a candidate for the fp64 test (the bound never moves) */
+                        if (cls == LH_TRI_CERTAIN && t_hi < lh_tmax_sure_below(tb)) { certain = 1; done = 1; break; }
+                    } else if (cls == LH_TRI_CERTAIN) tb = fminf(tb, t_hi);
+                    if (np == 4) {
+                        for (k = 0; k < 4; k++) hw_resolve(b, ref, pend[k], o, d, &best);
+                        np = 0;
+                        if (anyhit && best.prim != HW_MISS) { done = 1; break; }
+                    }
+                    pend[np++] = T->prim;
+                }
+                if (done || !sp) break;
+                cur = stack[--sp];
+            }
+        }
+        if (!(anyhit && (certain || best.prim != HW_MISS))) for (k = 0; k < np; k++) hw_resolve(b, ref, pend[k], o, d, &best);
+        /* retire: an accepted hit near the bound is fragile (its partner beyond the bound was not taken); a miss carries the miss record's t */
+        if (best.prim != HW_MISS) { if (lh_tmax_near(best.t, tmax)) best.frag |= 2u; }
+        else best.t = HW_T_INF;
+        refw = ref && best.prim != HW_MISS && best.frag != 0u && !(anyhit && certain);
+        if (ovf) { if (ref) refw = 1; else return -2; }
+    }
+    if (refw) {
+        uint32_t p; double tt, uu, vv;
+        const int hit = lh_ref_trace(ref->nodes, ref->leaf_prims, &b->tri64[0].v[0][0], ref->empty, ref->bmin, ref->bmax,
+                                     o[0], o[1], o[2], d[0], d[1], d[2], &p, &tt, &uu, &vv);
+        if (!(hit && lh_tmax_accept(tt, tmax))) return 0;              /* the outputs hold the miss record */
+        if (!anyhit) { *prim = p; *t = tt; *u = uu; *v = vv; }
+        return 1;
+    }
+    if (anyhit) return certain || best.prim != HW_MISS;
     *prim = best.prim; *t = best.t; *u = best.u; *v = best.v;
     return best.prim != HW_MISS;
 }

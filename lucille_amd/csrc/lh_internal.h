@@ -215,6 +215,10 @@ int  lh_gather_launch(uint32_t ntris, uint32_t nmeshes, const lh_dmesh_desc_t *d
                       lh_gather_out_t out, hipStream_t stream);
 /* lh_hostwalk.c */
 extern "C" int lh_host_walk_closest(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], uint32_t *prim, double *t, double *u, double *v);
+/* ... and its bounded variant (lh_tmax.h), closest or any hit: the record of lh_host_walk_closest if it is a hit with t < tmax, else the miss record --
+ * by a walk the bound prunes.  How the rule of the bounded launches is checked without a device (tests/cpu_model/lh_tmax_model.c) */
+extern "C" int lh_host_walk_tmax(const lh_bvh_t *b, const lh_refbvh_t *ref, const double o[3], const double d[3], double tmax, int anyhit,
+                                 uint32_t *prim, double *t, double *u, double *v);
 /* lh_query.hip */
 void lh_comb_destroy(lh_accel_t *a);                 /* the single-ray combiner's pinned block and stream (lh_accel_destroy) */
 /* one batch of rays (lh_batch_t, lh_device.h: rays, records, the LH_CNT_DEV statistics counters or NULL) through the hot path, from a
@@ -229,6 +233,8 @@ struct lh_launch_opt {
     /* an indexed ray dump (lh_accel_intersect_device_indexed): n is the number of list entries, the arrays hold idx_nrays rays; index NULL: the
      * identity list; n_dev (above): the number of entries to trace, clamped to n */
     bool indexed = false; const uint32_t *index = NULL; uint32_t idx_nrays = 0u;
+    /* a bounded ray dump (lh_accel_intersect_device_tmax; with indexed): idx_nrays bounds by ray id, in the rays' type (lh_tmax.h) */
+    const void *tmax = NULL;
 };
 int  lh_launch(lh_accel_t *a, const lh_batch_t &batch, int variant, hipStream_t s, bool dump, const lh_launch_opt &opt = lh_launch_opt());
 /* the cursor block of the next persistent launch: LH_NCURSOR of them, taken in turn (one per launch in flight) */

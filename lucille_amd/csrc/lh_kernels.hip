@@ -53,6 +53,7 @@
 #include "lh_device.h"
 #include "lh_filter.h"
 #include "lh_reftrace.h"
+#include "lh_tmax.h"
 #include "lh_ao.h"
 
 namespace {
@@ -197,7 +198,7 @@ __device__ __forceinline__ void node_step4(Lane &L, int &pend, const lh_dev_scen
 }
 
 /* one triangle of the parked leaf of every lane that holds one */
-template <bool ANYHIT, bool COUNT, int STRIDE, bool RING>
+template <bool ANYHIT, bool COUNT, int STRIDE, bool RING, bool TMAX = false>
 __device__ __forceinline__ void tri_pass(Lane &L, int &pend, const lh_dev_scene_t &sc, int (*stk)[STRIDE], const int tid,
                                          double ox, double oy, double oz, double dx, double dy, double dz, Best &best,
                                          uint32_t &c_tris, uint32_t &c_exact, const int ring_mask = 0)
@@ -208,7 +209,7 @@ __device__ __forceinline__ void tri_pass(Lane &L, int &pend, const lh_dev_scene_
         const float4 *tp = tris + 3 * (size_t)(x >> 2);
         const float4 ta = tp[0], tb_ = tp[1], tc = tp[2];
         if (COUNT) c_tris++;
-        const bool finished = tri_step<ANYHIT, COUNT>(L, sc, ta.x, ta.y, ta.z, ta.w, tb_.x, tb_.y, tb_.z, tb_.w, tc.x, tc.z, tc.w, __float_as_uint(tc.y), ox, oy, oz, dx, dy, dz, best, c_exact);
+        const bool finished = tri_step<ANYHIT, COUNT, TMAX>(L, sc, ta.x, ta.y, ta.z, ta.w, tb_.x, tb_.y, tb_.z, tb_.w, tc.x, tc.z, tc.w, __float_as_uint(tc.y), ox, oy, oz, dx, dy, dz, best, c_exact);
         if (finished) { L.cur = kDone; pend = kNoLeaf; }
         else if (x & 3u) pend = (int)~(((x >> 2) + 1u) << 2 | ((x & 3u) - 1u));
         else {
@@ -221,7 +222,7 @@ __device__ __forceinline__ void tri_pass(Lane &L, int &pend, const lh_dev_scene_
 #undef LH_ROW
 }
 
-template <bool ANYHIT, bool COUNT, bool GUARD, bool SORTED = true>
+template <bool ANYHIT, bool COUNT, bool GUARD, bool SORTED = true, bool TMAX = false>
 __device__ __forceinline__ void traverse_spec4(Lane &L, int &pend, const lh_dev_scene_t &sc,
                                                int (*stk)[LH_BLOCK], const int tid,
                                                double ox, double oy, double oz,
@@ -251,7 +252,7 @@ __device__ __forceinline__ void traverse_spec4(Lane &L, int &pend, const lh_dev_
         const unsigned long long m_pend = __ballot(pend != kNoLeaf);
         if (m_pend != 0ull && (__popcll(m_pend) >= tri_batch || m_node == 0ull)) {
             if (COUNT) c_tslots++;
-            tri_pass<ANYHIT, COUNT, LH_BLOCK, false>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, c_tris, c_exact);
+            tri_pass<ANYHIT, COUNT, LH_BLOCK, false, TMAX>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, c_tris, c_exact);
         }
         const unsigned long long m_work = __ballot((L.cur != kDone) | (pend != kNoLeaf));
         if (__popcll(m_work) < min_active || (++it & kRegroupMask) == 0u) break;      /* at least every 64 iterations: the visit budget is checked at regroup points */
@@ -263,7 +264,7 @@ __device__ __forceinline__ void traverse_spec4(Lane &L, int &pend, const lh_dev_
  * a hit child's stack slot is its rank among the hits in priority order (popcount of the nearer hits), nearest on top;
  * misses write to a scratch row.  For ray dumps over scenes that do not fit the Infinity Cache: there every record costs a
  * 128-byte line of HBM traffic, and this node uses all of it (S-soup-10M: 40 records per ray instead of 57). */
-template <bool ANYHIT, bool COUNT>
+template <bool ANYHIT, bool COUNT, bool TMAX = false>
 __device__ __forceinline__ void traverse_spec8(Lane &L, int &pend, const lh_dev_scene_t &sc,
                                                int (*stk)[LH_BLOCK], const int tid,
                                                double ox, double oy, double oz,
@@ -319,7 +320,7 @@ __device__ __forceinline__ void traverse_spec8(Lane &L, int &pend, const lh_dev_
                 const float4 *tp = tris + 3 * (size_t)(x >> 2);
                 const float4 ta = tp[0], tb_ = tp[1], tc = tp[2];
                 if (COUNT) c_tris++;
-                const bool finished = tri_step<ANYHIT, COUNT>(L, sc, ta.x, ta.y, ta.z, ta.w, tb_.x, tb_.y, tb_.z, tb_.w, tc.x, tc.z, tc.w, __float_as_uint(tc.y), ox, oy, oz, dx, dy, dz, best, c_exact);
+                const bool finished = tri_step<ANYHIT, COUNT, TMAX>(L, sc, ta.x, ta.y, ta.z, ta.w, tb_.x, tb_.y, tb_.z, tb_.w, tc.x, tc.z, tc.w, __float_as_uint(tc.y), ox, oy, oz, dx, dy, dz, best, c_exact);
                 if (finished) { L.cur = kDone; pend = kNoLeaf; }
                 else if (x & 3u) pend = (int)~(((x >> 2) + 1u) << 2 | ((x & 3u) - 1u));
                 else {
@@ -526,12 +527,15 @@ constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 /* IO (ray source 0 only): the launch's formats (sc.io_fmt) are read in the refill and written in the retire; false: fp64 rays and
  * SoA fp64 records only.  Two instantiations instead of one branch: the branch in the retire alone cost the fp64 closest-hit walk
  * five more spilled VGPRs (1 -> 6, 16 -> 32 bytes of scratch a lane), the fp64 launches now run the parent's code unchanged */
-/* IDX (ray source 0, with IO): an indexed launch (sc.idx_on) -- the work items the cursors hand out are the entries of a list of ray ids
+/* IDX (ray source 0, with IO): an indexed launch (sc.idx_nrays > 0) -- the work items the cursors hand out are the entries of a list of ray ids
  * (sc.index, NULL = the identity list).  The refill turns the entry into the id; from there on the lane carries the id (`my`), as the
  * fix-up queue and the record stores do: the retire, the cooperative walk and the walk itself never see the list.  An id beyond the
  * arrays (>= sc.idx_nrays) is skipped: its lane stays idle until the next regroup, nothing is read or written for it.  IDX = false:
  * the code of every other launch, unchanged */
-template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false, bool IDX = false>
+/* TMAX (with IDX): a bounded launch (sc.tmax: a bound per ray id, lh_tmax.h).  The refill starts the lane's culling bound and best.t at the ray's bound
+ * instead of at 1e38, the retire reads the bound once more (no register stays live for it across the walk) to mark a hit near it fragile and to give a
+ * miss its record's t; the triangle step lets a certain any-hit end the ray only below the bound.  TMAX = false: the code of every other launch, unchanged */
+template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false, bool IDX = false, bool TMAX = false>
 __device__ __forceinline__ void trace_persist_lane(
     const lh_dev_scene_t &sc, const uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
@@ -573,6 +577,7 @@ __device__ __forceinline__ void trace_persist_lane(
         if (COUNT) crs++;
         if (idle && my != kNoRay) {
             if (!L.over) finish<ANYHIT, COUNT>(L, sc, ox, oy, oz, dx, dy, dz, best, ce, SRC == 1 ? selfp : LH_MISS_PRIM);
+            if (TMAX && !L.over) tmax_retire(best, ray_tmax(sc, my));
             /* rays the persistent walk does not finish go through the fix-up queue to the concurrent consumer: out of budget /
              * stack rows -> the cooperative walk; a hit the reference may not reach (fragile; a certain fp32 hit is strictly
              * inside its triangle, hence inside every box: never fragile) -> the reference's own walk.  A full queue (ray dumps:
@@ -687,6 +692,11 @@ __device__ __forceinline__ void trace_persist_lane(
             /* rays beyond deg_dcap are the reference walk's (lh_walk.h).  cap_srcs (host-set, scalar): can a ray of THIS source exceed it at all --
              * dumps whenever it is finite; camera and AO rays (unit vectors) only where a zero-area triangle of |e1|_1 |e2|_1 > 1 stayed in the
              * tree: the bit is set from the DOUBLE cap (lh_danger.h lh_dcap_srcs): the float cap of such a scene may be 1.0f.  Every other scene skips the test whole */
+            if (TMAX) {
+                const bool refw = (sc.cap_srcs & (1u << SRC)) != 0u && ray_needs_ref_walk(sc, L, dx, dy, dz);      /* asked under the unbounded 1e38f */
+                tmax_start(L, best, ray_tmax(sc, i));
+                if (__builtin_expect(refw, 0)) LH_FORCE_REF_WALK(L, best);
+            } else
             if ((sc.cap_srcs & (1u << SRC)) != 0u && __builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
             it0 = it;
         }
@@ -695,11 +705,11 @@ __device__ __forceinline__ void trace_persist_lane(
         /* ---- walk until too few lanes remain active ---------------------- */
         const int thresh = exhausted ? 1 : min_active;
         if (WALK == 3)
-            traverse_spec4<ANYHIT, COUNT, false, !(ANYHIT && LH_AO_UNSORTED)>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce, thresh, tri_batch, cns, cts, it);
+            traverse_spec4<ANYHIT, COUNT, false, !(ANYHIT && LH_AO_UNSORTED), TMAX>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce, thresh, tri_batch, cns, cts, it);
         else if (WALK == 8)          /* the same with the stack check: trees whose worst case the LDS rows do not cover */
-            traverse_spec4<ANYHIT, COUNT, true, !(ANYHIT && LH_AO_UNSORTED)>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce, thresh, tri_batch, cns, cts, it);
+            traverse_spec4<ANYHIT, COUNT, true, !(ANYHIT && LH_AO_UNSORTED), TMAX>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce, thresh, tri_batch, cns, cts, it);
         else
-            traverse_spec8<ANYHIT, COUNT>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce, thresh, tri_batch, cns, cts, it);
+            traverse_spec8<ANYHIT, COUNT, TMAX>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, cn, ct, ce, thresh, tri_batch, cns, cts, it);
     }
 #ifdef LH_DIAG_CLOCK
     if (sc.diag_clock && (tid & 63) == 0) sc.diag_clock[(size_t)(gridDim.x + blockIdx.x) * (LH_BLOCK / 64) + (tid >> 6)] = wall_clock64();
@@ -753,12 +763,32 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_i
     trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
 }
 
+/* the persistent kernel of a bounded ray dump (lh_accel_intersect_device_tmax): an indexed launch -- a dense call is the identity list over its rays --
+ * whose rays carry a bound each (sc.tmax).  Again a kernel of its own: every launch without bounds runs the kernels above, unchanged */
+template <bool ANYHIT, bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_tmax(
+    lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
+    uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+    double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters,
+    uint32_t *cursor, int min_active, int tri_batch, const FixQ fq)
+{
+    extern __shared__ int lh_stack_lds[];
+    if (sc.n_dev) { const uint32_t c = *sc.n_dev; if (c < n) n = c; }      /* min(*d_count, n_index) */
+    if (WALK != 7 && sc.top_nodes) {
+        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
+        const uint4 *src = (const uint4 *)sc.q4nodes;
+        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
+        __syncthreads();
+    }
+    trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
+}
+
 /* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
  * arrays, skipped).  For the cold kernels that enumerate a launch's rays (k_fixups, k_trace_small) */
 __device__ __forceinline__ bool item_ray(const lh_dev_scene_t &sc, size_t k, size_t &i)
 {
     i = k;
-    if (sc.idx_on) {
+    if (sc.idx_nrays) {
         if (sc.index) i = sc.index[k];
         if (i >= sc.idx_nrays) return false;
     }
@@ -809,11 +839,14 @@ __device__ __noinline__ RefHit ref_trace_one(const lh_dev_scene_t &sc, double ox
  * SRC 0: rays from org / dir, results into prim / t / u / v / occ.
  * SRC 1: AO rays regenerated from (slot, sample), occluded rays counted per slot; LH_Q_REF entries (and fragile results)
  * are decided by the reference's own walk, by the group's first lane. */
-template <bool ANYHIT, int SRC>
-__global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
-                                                  uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                  double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
-                                                  unsigned long long *counters, const uint32_t owner_groups)
+/* TMAX: the rays of a bounded launch (sc.tmax, lh_tmax.h) -- every lane of a group starts with the ray's bound, the group's merged best retires like a
+ * lane's (tmax_retire), the reference walk's records go through the final accept.  The body is shared; the kernels are k_coop_walk (every launch without
+ * bounds: TMAX = false, the code it always was) and k_coop_walk_tmax */
+template <bool ANYHIT, int SRC, bool TMAX>
+__device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                               uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                               double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc &ao, const FixQ &fq,
+                                               unsigned long long *counters, const uint32_t owner_groups)
 {
     /* owner_groups == 0: the pass that runs NEXT TO the producer (second stream; few waves: it must not take the CUs from it).
      * Group g owns the queue entries g, g + groups, ...; where it stopped is left in fq.heads[g].  If the two streams turn out to
@@ -866,13 +899,15 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
                 /* every lane's candidates through the fp64 test, then the merge over the group */
                 bool need_ref = false, hit = false;
                 finish<ANYHIT, false>(L, sc, ox, oy, oz, dx, dy, dz, best, ce, selfp);
+                const double tmx = TMAX ? ray_tmax(sc, i) : 0.0;
+                if (TMAX && ANYHIT) tmax_retire(best, tmx);          /* any hit: each lane's own hit decides by itself whether it is fragile */
                 if (ANYHIT) {
                     const bool exact = best.prim != LH_MISS_PRIM;
                     const bool sure = (__ballot(L.certain || (exact && best.frag == 0u)) & gmask) != 0ull;
                     hit = sure;
                     if (!sure && (__ballot(exact) & gmask) != 0ull) { need_ref = sc.ref_nodes != NULL; hit = true; }   /* only fragile hits: the reference walk decides */
                     if (SRC != 1 && (lane & 15) == 0) {
-                        if (need_ref) hit = ref_trace_one(sc, ox, oy, oz, dx, dy, dz).prim != LH_MISS_PRIM;
+                        if (need_ref) { RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz); if (TMAX) LH_TMAX_FILTER_REF(rh, tmx); hit = rh.prim != LH_MISS_PRIM; }
                         occ[i] = (uint8_t)(hit ? 1 : 0);
                     }
                 } else {
@@ -884,8 +919,10 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
                         merge_best(sc, gb, b, dx, dy, dz);
                     }
                     if ((lane & 15) == 0) {
+                        if (TMAX) tmax_retire(gb, tmx);
                         if (sc.ref_nodes != NULL && gb.prim != LH_MISS_PRIM && gb.frag != 0u) {        /* a fragile hit: the reference walk decides */
-                            const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
+                            RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
+                            if (TMAX) LH_TMAX_FILTER_REF(rh, tmx);
                             gb.prim = rh.prim; gb.t = rh.t; gb.u = rh.u; gb.v = rh.v;
                         }
                         store_rec<SRC == 0>(sc, i, prim, t, u, v, gb.prim, gb.t, gb.u, gb.v);
@@ -922,6 +959,7 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
                     src_ray<SRC>(sc, (uint32_t)i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
                     lane_init(L, sc, ox, oy, oz, dx, dy, dz);
                     best.t = LH_T_INF; best.u = 0.0; best.v = 0.0; best.prim = LH_MISS_PRIM; best.frag = 0u;
+                    if (TMAX) tmax_start(L, best, ray_tmax(sc, i));
                     pend = kNoLeaf; floor_ = 1; stk[0][lane] = kDone;
                     L.cur = (lane & 15) == 0 ? 0 : kDone;
                     have = true;
@@ -935,7 +973,8 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
                     const uint32_t ri = stash[lane & 15];
                     double rox, roy, roz, rdx, rdy, rdz; uint32_t rself = LH_MISS_PRIM;
                     src_ray<SRC>(sc, ri, org, dir, ao, rox, roy, roz, rdx, rdy, rdz, rself);
-                    const RefHit rh = ref_trace_one(sc, rox, roy, roz, rdx, rdy, rdz);
+                    RefHit rh = ref_trace_one(sc, rox, roy, roz, rdx, rdy, rdz);
+                    if (TMAX) LH_TMAX_FILTER_REF(rh, ray_tmax(sc, ri));
                     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
                     if (SRC == 1) { if (rh.prim != LH_MISS_PRIM) { uint32_t sl, rr; ao_item(ao, ri, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); } }
                     else if (ANYHIT) occ[ri] = rh.prim != LH_MISS_PRIM ? 1 : 0;
@@ -982,7 +1021,7 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
         const unsigned long long m_node = __ballot(L.cur >= 0);
         const unsigned long long m_pend = __ballot(pend != kNoLeaf);
         if (m_pend != 0ull && (__popcll(m_pend) >= 8 || m_node == 0ull))
-            tri_pass<ANYHIT, false, 64, true>(L, pend, sc, stk, lane, ox, oy, oz, dx, dy, dz, best, ct, ce, rmask);
+            tri_pass<ANYHIT, false, 64, true, TMAX>(L, pend, sc, stk, lane, ox, oy, oz, dx, dy, dz, best, ct, ce, rmask);
         if (ANYHIT) {                                    /* a certain hit ends the group's ray */
             if ((__ballot(L.certain) & gmask) != 0ull) { L.cur = kDone; pend = kNoLeaf; }
         }
@@ -1014,6 +1053,25 @@ __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const doubl
     if (owner_groups == 0u && (lane & 15) == 0) fq.heads[gid] = e;          /* where the sweep goes on */
 }
 
+template <bool ANYHIT, int SRC>
+__global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                                  uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                  double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
+                                                  unsigned long long *counters, const uint32_t owner_groups)
+{
+    coop_walk_body<ANYHIT, SRC, false>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+}
+
+/* the cooperative walk of a bounded ray dump (ray source 0) */
+template <bool ANYHIT>
+__global__ __launch_bounds__(64) void k_coop_walk_tmax(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                                       uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                       double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
+                                                       unsigned long long *counters, const uint32_t owner_groups)
+{
+    coop_walk_body<ANYHIT, 0, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+}
+
 /* ------------------------------------------------------------------------ */
 /* one scan over the outputs of a ray dump: what is still flagged            */
 /* ------------------------------------------------------------------------ */
@@ -1035,7 +1093,7 @@ __device__ __forceinline__ void flagged_ray(const lh_dev_scene_t &sc, size_t i, 
 
 /* cnt (or NULL): this ray's 4-wide node visits, leaf visits, triangle records through the fp32 filter, fp64 tests -- the walk
  * is sequential (nearest child first, a leaf's triangles in order), so the counts are the host model's (tests/cpu_model) */
-template <bool ANYHIT>
+template <bool ANYHIT, bool TMAX = false>
 __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *__restrict__ org, const double *__restrict__ dir,
                               uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
                               uint8_t *__restrict__ occ, uint32_t *cnt = NULL, bool *fragile_out = NULL)
@@ -1049,6 +1107,7 @@ __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *
     lane_init(L, sc, ox, oy, oz, dx, dy, dz);
     int cur = 0;
     const bool refw = ray_needs_ref_walk(sc, L, dx, dy, dz);          /* the reference's own walk decides (lh_walk.h) */
+    if (TMAX) tmax_start(L, best, ray_tmax(sc, i));
     if (refw) { best.prim = 0u; best.frag = 1u; }
     else for (;;) {
         if (cur >= 0) {
@@ -1080,7 +1139,7 @@ __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *
                 const float4 *tp = tris + 3 * (size_t)(first + k);
                 const float4 ta = tp[0], tb_ = tp[1], tc = tp[2];
                 ct++;
-                finished = tri_step<ANYHIT, true>(L, sc, ta.x, ta.y, ta.z, ta.w, tb_.x, tb_.y, tb_.z, tb_.w, tc.x, tc.z, tc.w,
+                finished = tri_step<ANYHIT, true, TMAX>(L, sc, ta.x, ta.y, ta.z, ta.w, tb_.x, tb_.y, tb_.z, tb_.w, tc.x, tc.z, tc.w,
                                                   __float_as_uint(tc.y), ox, oy, oz, dx, dy, dz, best, ce);
             }
             if (finished || sp == 0) break;
@@ -1089,6 +1148,7 @@ __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *
     }
     L.over = false;
     finish<ANYHIT, true>(L, sc, ox, oy, oz, dx, dy, dz, best, ce);
+    if (TMAX) tmax_retire(best, ray_tmax(sc, i));
     if (fragile_out) {
         /* indexed launches: a ray id may be listed twice, and two lanes that flag, re-read and finish ONE slot can interleave their stores --
          * so nothing tentative is written: the caller is told, and writes the reference walk's record alone (equal bits from every lane) */
@@ -1099,11 +1159,12 @@ __device__ void overflow_walk(const lh_dev_scene_t &sc, size_t i, const double *
     if (cnt) { cnt[0] = cn; cnt[1] = cl; cnt[2] = ct; cnt[3] = ce; }
 }
 
-__global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, const double *__restrict__ org,
-                                                const double *__restrict__ dir, uint32_t *__restrict__ prim,
-                                                double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
-                                                uint8_t *__restrict__ occ, int anyhit, unsigned long long *counters,
-                                                const uint32_t *qcount, int force)
+template <bool TMAX>
+__device__ __forceinline__ void fixups_body(const lh_dev_scene_t &sc, size_t n, const double *__restrict__ org,
+                                            const double *__restrict__ dir, uint32_t *__restrict__ prim,
+                                            double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
+                                            uint8_t *__restrict__ occ, int anyhit, unsigned long long *counters,
+                                            const uint32_t *qcount, int force)
 {
     /* nothing was left flagged unless a push found the queue full (or the launch had no queue: force) */
     if (!force && qcount[1] == 0u) return;
@@ -1114,21 +1175,41 @@ __global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, con
         if (!item_ray(sc, k, i)) continue;
         bool fragile = false, walked = false;
         if (anyhit ? (occ[i] == LH_OCC_OVERFLOW) : (rec_prim(sc, prim, i) == LH_PRIM_OVERFLOW)) {
-            bool *fo = sc.idx_on ? &fragile : NULL;
-            if (anyhit) overflow_walk<true>(sc, i, org, dir, prim, t, u, v, occ, NULL, fo);
-            else overflow_walk<false>(sc, i, org, dir, prim, t, u, v, occ, NULL, fo);
+            bool *fo = sc.idx_nrays ? &fragile : NULL;
+            if (anyhit) overflow_walk<true, TMAX>(sc, i, org, dir, prim, t, u, v, occ, NULL, fo);
+            else overflow_walk<false, TMAX>(sc, i, org, dir, prim, t, u, v, occ, NULL, fo);
             if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
-            walked = sc.idx_on != 0u;
+            walked = sc.idx_nrays != 0u;
         }
         if (sc.ref_nodes == NULL) continue;
         if (walked ? !fragile : (anyhit ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE))) continue;
         double ox, oy, oz, dx, dy, dz;
         flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
-        const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
+        RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
+        if (TMAX) LH_TMAX_FILTER_REF(rh, ray_tmax(sc, i));
         if (anyhit) occ[i] = rh.prim != LH_MISS_PRIM ? 1 : 0;
         else store_rec(sc, i, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
         if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
     }
+}
+
+__global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, const double *__restrict__ org,
+                                                const double *__restrict__ dir, uint32_t *__restrict__ prim,
+                                                double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
+                                                uint8_t *__restrict__ occ, int anyhit, unsigned long long *counters,
+                                                const uint32_t *qcount, int force)
+{
+    fixups_body<false>(sc, n, org, dir, prim, t, u, v, occ, anyhit, counters, qcount, force);
+}
+
+/* the same scan behind a bounded launch (sc.tmax) */
+__global__ __launch_bounds__(256) void k_fixups_tmax(lh_dev_scene_t sc, size_t n, const double *__restrict__ org,
+                                                     const double *__restrict__ dir, uint32_t *__restrict__ prim,
+                                                     double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
+                                                     uint8_t *__restrict__ occ, int anyhit, unsigned long long *counters,
+                                                     const uint32_t *qcount, int force)
+{
+    fixups_body<true>(sc, n, org, dir, prim, t, u, v, occ, anyhit, counters, qcount, force);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1143,10 +1224,10 @@ __global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, con
 #define LH_SMALL_BATCH 64u
 /* PER_WAVE: one ray per wave (lane 0), else one per lane.  counters (or NULL): the launch's totals (LH_CNT_*); sc.diag_out (or
  * NULL): four counts per ray -- ri_bvh_diag_t's numbers (bvh.h:103-110) for this build's tree */
-template <bool ANYHIT, bool PER_WAVE>
-__global__ __launch_bounds__(64) void k_trace_small(lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
-                                                    uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                    double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters)
+template <bool ANYHIT, bool PER_WAVE, bool TMAX>
+__device__ __forceinline__ void trace_small_body(const lh_dev_scene_t &sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
+                                                 uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                 double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters)
 {
     /* ONE RAY PER WAVE: sixty-four unrelated rays in the lanes of one wave walk in lockstep through each other's branches
      * (16 rays: 243 us against 49 us for one, r04); a wave per ray runs them side by side on as many CUs -- the batch takes
@@ -1157,17 +1238,35 @@ __global__ __launch_bounds__(64) void k_trace_small(lh_dev_scene_t sc, uint32_t 
     if (!item_ray(sc, k, i)) return;
     uint32_t cnt[4] = {0u, 0u, 0u, 0u};
     bool fragile = false;
-    overflow_walk<ANYHIT>(sc, i, org, dir, prim, t, u, v, occ, cnt, sc.idx_on ? &fragile : NULL);
+    overflow_walk<ANYHIT, TMAX>(sc, i, org, dir, prim, t, u, v, occ, cnt, sc.idx_nrays ? &fragile : NULL);
     if (sc.diag_out) { uint32_t *d = sc.diag_out + 4 * (size_t)i; d[0] = cnt[0]; d[1] = cnt[1]; d[2] = cnt[2]; d[3] = cnt[3]; }
     if (counters) add_counters(counters, cnt[0], cnt[2], cnt[3], 1);
     if (sc.ref_nodes == NULL) return;
-    if (sc.idx_on ? !fragile : (ANYHIT ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE))) return;
+    if (sc.idx_nrays ? !fragile : (ANYHIT ? (occ[i] != LH_OCC_RETRACE) : (rec_prim(sc, prim, i) != LH_PRIM_RETRACE))) return;
     double ox, oy, oz, dx, dy, dz;
     flagged_ray(sc, i, org, dir, ox, oy, oz, dx, dy, dz);
-    const RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
+    RefHit rh = ref_trace_one(sc, ox, oy, oz, dx, dy, dz);
+    if (TMAX) LH_TMAX_FILTER_REF(rh, ray_tmax(sc, i));
     if (ANYHIT) occ[i] = rh.prim != LH_MISS_PRIM ? 1 : 0;
     else store_rec(sc, i, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
+}
+
+template <bool ANYHIT, bool PER_WAVE>
+__global__ __launch_bounds__(64) void k_trace_small(lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
+                                                    uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                    double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters)
+{
+    trace_small_body<ANYHIT, PER_WAVE, false>(sc, n, org, dir, prim, t, u, v, occ, counters);
+}
+
+/* a handful of rays of a bounded call (sc.tmax; a wave per ray) */
+template <bool ANYHIT>
+__global__ __launch_bounds__(64) void k_trace_small_tmax(lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
+                                                         uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                         double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters)
+{
+    trace_small_body<ANYHIT, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters);
 }
 
 /* a workgroup's LDS stack beyond 64 KiB (trees deeper than 19 four-wide levels: up to LH_ROWS_UNCHECKED rows) has to be
@@ -1217,7 +1316,12 @@ int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, unsigned long lon
             const indexed_t indexed[3] = {k_trace_persist_indexed<ANYHIT, COUNT, 7>, k_trace_persist_indexed<ANYHIT, COUNT, 8>, k_trace_persist_indexed<ANYHIT, COUNT, 3>};
             const lane_t io[3] = {k_trace_persist_lane<ANYHIT, COUNT, 7, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, 8, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, 3, 0, true>};
             const lane_t f64[3] = {k_trace_persist_lane<ANYHIT, COUNT, 7, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, 8, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, 3, 0, false>};
-            if (sc.idx_on && !sc.cam_src)        /* an indexed ray dump: the list is read in the refill */
+            if (sc.tmax) {                       /* a bounded ray dump: an indexed launch whose rays carry a bound each (named last: the kernels above keep their order) */
+                const indexed_t bounded[3] = {k_trace_persist_tmax<ANYHIT, COUNT, 7>, k_trace_persist_tmax<ANYHIT, COUNT, 8>, k_trace_persist_tmax<ANYHIT, COUNT, 3>};
+                if (!sc.idx_nrays || sc.cam_src) return -1;
+                LH_LAUNCH_PERSIST(bounded[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor, min_active, tri_batch, fq);
+            } else
+            if (sc.idx_nrays && !sc.cam_src)        /* an indexed ray dump: the list is read in the refill */
                 LH_LAUNCH_PERSIST(indexed[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor, min_active, tri_batch, fq);
             else                                 /* io_fmt: fp32 rays / 16-byte records, the instantiations that read and write them (IO) */
                 LH_LAUNCH_PERSIST(sc.cam_src ? cam : sc.io_fmt ? io[w] : f64[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor,
@@ -1306,20 +1410,22 @@ void clamp_chunk(lh_dev_scene_t &scl, size_t n, int grid_blocks)
  * stream, CONCURRENTLY with that launch (a few small workgroups per CU next to the persistent ones: its low efficiency --
  * one ray per 16 lanes, restarted from the root -- is hidden behind the bulk of the frame), submitted AFTER it: if the two
  * streams share a hardware queue it simply runs afterwards. */
-template <bool ANYHIT, int SRC>
+template <bool ANYHIT, int SRC, bool TMAX = false>
 int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_fixq_t *q, int ncus, hipStream_t s)
 {
     /* the pass next to the producer (owner_groups 0) and the sweep behind it */
-#define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL((k_coop_walk<ANYHIT, SRC>), dim3(GRID), dim3(64), lds, STREAM, scl, LH_BATCH_ARRAYS(b), \
+#define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL(kern, dim3(GRID), dim3(64), lds, STREAM, scl, LH_BATCH_ARRAYS(b), \
                                                                       ao, fq, b.counters, OWNER_GROUPS)
+    auto *kern = k_coop_walk<ANYHIT, SRC>;
+    if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
     lh_dev_scene_t scl = sc;
     scl.stack_rows = coop_rows(sc);
     if (scl.stack_rows == 0) return -1;
     const size_t lds = ((size_t)scl.stack_rows * 64 + 128 + 64) * sizeof(int);          /* the stack ring, 2 x 64 exchange words, 4 x 16 stashed reference-walk entries */
-    static bool attr_set[2][3] = {{false, false, false}, {false, false, false}};
-    if (lds > 64 * 1024 && !attr_set[ANYHIT][SRC]) {
-        if (hipFuncSetAttribute((const void *)k_coop_walk<ANYHIT, SRC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        attr_set[ANYHIT][SRC] = true;
+    static bool attr_set[2][4] = {{false, false, false, false}, {false, false, false, false}};          /* [3]: the bounded launches' kernel */
+    if (lds > 64 * 1024 && !attr_set[ANYHIT][TMAX ? 3 : SRC]) {
+        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+        attr_set[ANYHIT][TMAX ? 3 : SRC] = true;
     }
     hipStream_t aux = (hipStream_t)q->aux_stream;
     int grid = ncus > 0 ? ncus : 256;                      /* one wave per workgroup and CU, 4 rays per wave */
@@ -1423,7 +1529,7 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
     /* the persistent kernel indexes rays with 32 bits: a larger batch is a sequence of launches */
     const size_t kMaxLaunch = (size_t)1 << 30;
     if (n > kMaxLaunch) {
-        if (sc->idx_on) return -1;
+        if (sc->idx_nrays) return -1;
         for (size_t off = 0; off < n; off += kMaxLaunch) {
             const lh_batch_t part = lh_batch_sub(b, sc->io_fmt, off, (n - off < kMaxLaunch) ? n - off : kMaxLaunch);
             const int rc = lh_launch_trace(sc, &part, d_cursor, variant, grid_blocks, min_active, tri_batch, q, ncus, stream);
@@ -1433,14 +1539,16 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
     }
     lh_dev_scene_t scl = *sc;
     uint32_t need; int walk; bool guard = false;
-    if ((sc->cam_src || sc->n_dev) && (variant == LH_VARIANT_DIRECT || (anyhit && !sc->idx_on) || q == NULL)) return -1;      /* the path tracer's chain: default walk, closest hit; an indexed dump's count: either mode */
-    if (sc->idx_on && (variant == LH_VARIANT_DIRECT || sc->cam_src || sc->diag_out || n > kMaxLaunch)) return -1;       /* the list is read by the default walk's kernels only */
+    if ((sc->cam_src || sc->n_dev) && (variant == LH_VARIANT_DIRECT || (anyhit && !sc->idx_nrays) || q == NULL)) return -1;      /* the path tracer's chain: default walk, closest hit; an indexed dump's count: either mode */
+    if (sc->tmax && !sc->idx_nrays) return -1;          /* a bounded launch is an indexed one (a dense call: the identity list) */
+    if (sc->idx_nrays && (variant == LH_VARIANT_DIRECT || sc->cam_src || sc->diag_out || n > kMaxLaunch)) return -1;       /* the list is read by the default walk's kernels only */
     static const bool small_ok = !(getenv("LH_SMALL_BATCH") && atoi(getenv("LH_SMALL_BATCH")) == 0);      /* LH_SMALL_BATCH=0: rounds 1-3's path for a handful of rays (A/B) */
     if (((n <= LH_SMALL_BATCH && small_ok) || sc->diag_out) && variant != LH_VARIANT_DIRECT && !sc->cam_src && !sc->n_dev && (sc->diag_out || !sc->stack_cap) && sc->q4nodes) {      /* the sequential walk has a private stack: a capped LDS stack (tests) does not concern per-ray diagnostics */
         /* a handful of rays (the coalesced one-ray callers): one small launch, a wave per ray, no queue, no cursors.
          * Per-ray diagnostics (diag_out): the same walk for a batch of any size, a lane per ray */
         const bool per_wave = n <= LH_SMALL_BATCH;
         auto *k = per_wave ? (anyhit ? k_trace_small<true, true> : k_trace_small<false, true>) : (anyhit ? k_trace_small<true, false> : k_trace_small<false, false>);
+        if (sc->tmax) { if (!per_wave) return -1; k = anyhit ? k_trace_small_tmax<true> : k_trace_small_tmax<false>; }
         hipLaunchKernelGGL(k, dim3((unsigned)(per_wave ? n : (n + 63) / 64)), dim3(64), 0, s, scl, (uint32_t)n, LH_BATCH_ARRAYS(b), b.counters);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
@@ -1482,7 +1590,8 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
     int rc = launch_walk(scl, b, d_cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
     if (rc != 0) return rc;
     if (coop) {
-        rc = anyhit ? launch_coop<true, 0>(scl, b, AoSrc{}, fq, q, ncus, s)
+        rc = sc->tmax ? (anyhit ? launch_coop<true, 0, true>(scl, b, AoSrc{}, fq, q, ncus, s) : launch_coop<false, 0, true>(scl, b, AoSrc{}, fq, q, ncus, s))
+             : anyhit ? launch_coop<true, 0>(scl, b, AoSrc{}, fq, q, ncus, s)
              : sc->cam_src ? launch_coop<false, 2>(scl, b, AoSrc{}, fq, q, ncus, s)
                     : launch_coop<false, 0>(scl, b, AoSrc{}, fq, q, ncus, s);
         if (rc != 0) return rc;
@@ -1490,7 +1599,7 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
     /* what is still flagged: fragile hits (the reference's own walk), and out-of-budget rays the queue had no room for */
     {
         const size_t blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(k_fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, LH_BATCH_ARRAYS(b),
+        hipLaunchKernelGGL(sc->tmax ? k_fixups_tmax : k_fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, LH_BATCH_ARRAYS(b),
                            anyhit ? 1 : 0, b.counters, q ? q->qcount : NULL, (walk == 0 || q == NULL) ? 1 : 0);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;

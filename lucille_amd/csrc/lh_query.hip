@@ -177,7 +177,9 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
     else if (sc.ray_chunk < LH_TILE_CHUNK) sc.ray_chunk = LH_TILE_CHUNK;       /* the tile pipelines' batches are coherent in batch order */
     sc.io_fmt = opt.io_fmt & (closest ? (LH_IO_RAYS_F32 | LH_IO_REC16) : LH_IO_RAYS_F32);
     sc.diag_out = opt.diag_out; sc.n_dev = opt.n_dev; sc.cam_src = opt.cam_src; sc.diag_clock = opt.diag_clock;
-    sc.idx_on = opt.indexed ? 1u : 0u; sc.index = opt.index; sc.idx_nrays = opt.idx_nrays;
+    sc.index = opt.indexed ? opt.index : NULL; sc.idx_nrays = opt.indexed ? opt.idx_nrays : 0u;          /* idx_nrays > 0 (the entry points return before a launch without rays): what makes the launch an indexed one */
+    if (opt.tmax && (!opt.indexed || !dump || variant != LH_VARIANT_SPEC)) return fail("intersect: per-ray bounds are read by the default walk's indexed ray dumps only");
+    sc.tmax = opt.tmax;
     /* a ray dump over the 4-wide nodes regroups a little later and passes over parked leaves a little sooner than the tile
      * pipelines' coherent batches want (tools/experiments/knob_sweep3.py / knob_sweep4.py, r05: S-soup-1M 2 233 -> 2 266 Mrays/s
      * closest hit, 2 735 -> 2 772 any hit; the 8-wide walk and the AO stage are best where they are) */
@@ -575,6 +577,132 @@ extern "C" int lh_accel_intersect_device_indexed(lh_accel_t *a, size_t n_rays, c
     unsigned long long h[LH_CNT_DEV];
     if (counted_collect(a, s, h) != 0) return -1;
     lh_stat_add(a, h, h[LH_CNT_RAYS], 0);          /* hits are not counted: the records stay on the device */
+    return 0;
+}
+
+/* ---- per-ray maximum distance (lucille_hip.h; the rule: lh_tmax.h) ---- */
+/* hits among the listed records of a bounded launch, for the statistics: entry k < min(*count, n) -> slot index[k] (or k), ids beyond nrays skipped,
+ * as the launch enumerated them (an id listed twice counts twice, as its ray does).  prim: the records' first words, `stride` words apart */
+__global__ void k_count_listed_hits(size_t n, const uint32_t *index, const uint32_t *count, uint32_t nrays, const uint32_t *prim, uint32_t stride,
+                                    const uint8_t *occ, unsigned long long *out)
+{
+    const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (count && *count < n) n = *count;
+    bool hit = false;
+    if (k < n) {
+        const uint32_t i = index ? index[k] : (uint32_t)k;
+        if (i < nrays) hit = prim ? prim[(size_t)stride * i] != LH_MISS_PRIM : occ[i] != 0;
+    }
+    const unsigned long long m = __ballot(hit);
+    if (m != 0ull && (threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)__popcll(m));
+}
+
+/* the checks of a bounded call that need no device, after ex_formats': -1 (lh_last_error) or 0 */
+static int tmax_args(const char *what, size_t n_rays, const void *tmax, int ray_format, bool device)
+{
+    if (device && n_rays > ((size_t)1 << 30)) return fail("%s: a bounded call holds 2^30 rays at most (%zu given)", what, n_rays);
+    const uintptr_t el = ray_format == LH_RAYS_F32 ? sizeof(float) : sizeof(double);
+    if (((uintptr_t)tmax & (el - 1u)) != 0) return fail("%s: tmax not aligned to its %zu-byte elements", what, (size_t)el);
+    return 0;
+}
+
+extern "C" int lh_accel_intersect_device_tmax(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_tmax,
+                                              int ray_format, int record_format, void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v,
+                                              void *d_occ, int mode, const void *d_index, size_t n_index, const void *d_count, void *stream)
+{
+    const bool dense = d_index == NULL && n_index == 0 && d_count == NULL;
+    /* no bounds: the unbounded entry point itself */
+    if (!d_tmax)
+        return dense ? lh_accel_intersect_device_ex(a, n_rays, d_org, d_dir, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, stream)
+                     : lh_accel_intersect_device_indexed(a, n_rays, d_org, d_dir, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode,
+                                                         d_index, n_index, d_count, stream);
+    lh_guard guard(a);
+    const char *what = "lh_accel_intersect_device_tmax";
+    const size_t n_list = dense ? n_rays : n_index;          /* a dense call is the identity list over its rays */
+    const int io = ex_formats(what, (n_rays && n_list) ? n_rays : 0, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
+    if (io < 0) return -1;
+    if (n_index > ((size_t)1 << 30)) return fail("%s: a list holds 2^30 entries at most (%zu given)", what, n_index);
+    if (tmax_args(what, n_rays, d_tmax, ray_format, true) != 0) return -1;
+    if ((((uintptr_t)d_index | (uintptr_t)d_count) & 3u) != 0) return fail("%s: the list and its count are 32-bit words: a pointer is not 4-byte aligned", what);
+    const int go = batch_args(a, "intersect", (n_list && n_rays) ? n_list : 0, d_org && d_dir, "ray arrays", mode);
+    if (go <= 0) return go;
+    lh_launch_opt opt;
+    opt.io_fmt = (uint32_t)io; opt.indexed = true; opt.index = (const uint32_t *)d_index; opt.idx_nrays = (uint32_t)n_rays;
+    opt.n_dev = (const uint32_t *)d_count; opt.tmax = d_tmax;
+    hipStream_t s = (hipStream_t)stream;
+    const lh_batch_t b = {n_list, mode, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL};
+    if (a->stat_on) { HIPCHK(hipSetDevice(a->device)); if (counted_begin(a, s) != 0) return -1; }
+    if (lh_launch(a, b, LH_VARIANT_DEFAULT, s, true, opt) != 0) return -1;
+    if (!a->stat_on) return 0;
+    /* statistics: as the indexed call counts, and the hits that are left after the bound, counted from the records on the device */
+    unsigned long long h[LH_CNT_DEV], nh = 0;
+    if (counted_collect(a, s, h) != 0) return -1;
+    const bool closest = mode == LH_MODE_CLOSEST;
+    HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_count_listed_hits, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, s, n_list, opt.index, opt.n_dev, opt.idx_nrays,
+                       closest ? (const uint32_t *)d_prim_or_rec16 : NULL, (io & LH_IO_REC16) ? 4u : 1u, closest ? NULL : (const uint8_t *)d_occ, a->d_counters);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&nh, a->d_counters, sizeof(nh), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    lh_stat_add(a, h, h[LH_CNT_RAYS], nh);
+    return 0;
+}
+
+/* the host form: the plain path (pageable copies through the staging block, one bounded launch) in chunks of LH_TMAX_HOST_CHUNK rays, whatever n is --
+ * the bounds do not travel through the pinned ring of the pipelined host path */
+#define LH_TMAX_HOST_CHUNK ((size_t)1 << 21)
+extern "C" int lh_accel_intersect_host_tmax(lh_accel_t *a, size_t n, const void *org, const void *dir, const void *tmax, int ray_format, int record_format,
+                                            void *prim_or_rec16, double *t, double *u, double *v, uint8_t *occ, int mode)
+{
+    if (!tmax) return lh_accel_intersect_host_ex(a, n, org, dir, ray_format, record_format, prim_or_rec16, t, u, v, occ, mode);
+    lh_guard guard(a);
+    const char *what = "lh_accel_intersect_host_tmax";
+    const int io = ex_formats(what, n, ray_format, record_format, mode, prim_or_rec16, t, u, v);
+    if (io < 0) return -1;
+    if (tmax_args(what, n, tmax, ray_format, false) != 0) return -1;
+    const int go = batch_args(a, "intersect", n, org && dir, "ray arrays", mode);
+    if (go <= 0) return go;
+    HIPCHK(hipSetDevice(a->device));
+    const bool closest = mode == LH_MODE_CLOSEST, rec16 = closest && (io & LH_IO_REC16);
+    const size_t el = (io & LH_IO_RAYS_F32) ? sizeof(float) : sizeof(double), w = rec16 ? 4 : 1;
+    for (size_t off = 0; off < n; off += LH_TMAX_HOST_CHUNK) {
+        const size_t m = n - off < LH_TMAX_HOST_CHUNK ? n - off : LH_TMAX_HOST_CHUNK;
+        /* the staging block: org | dir | tmax | (16-byte aligned) t | u | v | prim | occ; 16-byte records start where t does */
+        const size_t b_ray = el * 3 * m, b_tm = el * m, b_d = sizeof(double) * m;
+        const size_t b_out = (2 * b_ray + b_tm + 15) & ~(size_t)15;
+        if (lh_ensure_stage(a, b_out + 3 * b_d + sizeof(uint32_t) * m + m + 64) != 0) return -1;
+        char *base = (char *)a->d_stage;
+        char *d_org = base, *d_dir = base + b_ray, *d_tm = base + 2 * b_ray;
+        double *d_t = (double *)(base + b_out), *d_u = d_t + m, *d_v = d_u + m;
+        uint32_t *d_prim = (uint32_t *)(d_v + m);
+        uint8_t *d_occ = (uint8_t *)(d_prim + m);
+        if (rec16) { d_prim = (uint32_t *)d_t; d_t = d_u = d_v = NULL; }
+        HIPCHK(hipMemcpyAsync(d_org, (const char *)org + el * 3 * off, b_ray, hipMemcpyHostToDevice, a->stream));
+        HIPCHK(hipMemcpyAsync(d_dir, (const char *)dir + el * 3 * off, b_ray, hipMemcpyHostToDevice, a->stream));
+        HIPCHK(hipMemcpyAsync(d_tm, (const char *)tmax + el * off, b_tm, hipMemcpyHostToDevice, a->stream));
+        if (a->stat_on && counted_begin(a, a->stream) != 0) return -1;
+        lh_launch_opt opt;
+        opt.io_fmt = (uint32_t)io; opt.indexed = true; opt.idx_nrays = (uint32_t)m; opt.tmax = d_tm;
+        const int rc = lh_launch(a, lh_batch_t{m, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL},
+                                 LH_VARIANT_DEFAULT, a->stream, true, opt);
+        if (rc != 0) return rc;
+        if (a->stat_on) {
+            std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV], nh = 0;
+            if (closest) { hp.resize(w * m); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * w * m, hipMemcpyDeviceToHost, a->stream)); }
+            else { ho.resize(m); HIPCHK(hipMemcpyAsync(ho.data(), d_occ, m, hipMemcpyDeviceToHost, a->stream)); }
+            if (counted_collect(a, a->stream, h) != 0) return -1;
+            for (size_t i = 0; i < m; i++) nh += closest ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
+            lh_stat_add(a, h, m, nh);
+        }
+        if (rec16) HIPCHK(hipMemcpyAsync((char *)prim_or_rec16 + 16 * off, d_prim, 16 * m, hipMemcpyDeviceToHost, a->stream));
+        else if (closest) {
+            if (prim_or_rec16) HIPCHK(hipMemcpyAsync((uint32_t *)prim_or_rec16 + off, d_prim, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, a->stream));
+            if (t) HIPCHK(hipMemcpyAsync(t + off, d_t, b_d, hipMemcpyDeviceToHost, a->stream));
+            if (u) HIPCHK(hipMemcpyAsync(u + off, d_u, b_d, hipMemcpyDeviceToHost, a->stream));
+            if (v) HIPCHK(hipMemcpyAsync(v + off, d_v, b_d, hipMemcpyDeviceToHost, a->stream));
+        } else if (occ) HIPCHK(hipMemcpyAsync(occ + off, d_occ, m, hipMemcpyDeviceToHost, a->stream));
+        HIPCHK(hipStreamSynchronize(a->stream));          /* the next chunk reuses the staging block */
+    }
     return 0;
 }
 

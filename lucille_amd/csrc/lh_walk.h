@@ -117,6 +117,27 @@ __device__ __forceinline__ bool ray_needs_ref_walk(const lh_dev_scene_t &sc, con
  * dump kernel 80 bytes of scratch per lane) -- and retires as a fragile hit */
 #define LH_FORCE_REF_WALK(L, best) do { (L).tb = -1.0f; (best).prim = 0u; (best).frag = 1u; } while (0)
 
+/* ---- a bounded launch (sc.tmax, lh_tmax.h): what every kernel that starts or finishes one of its rays does ---- */
+__device__ __forceinline__ double ray_tmax(const lh_dev_scene_t &sc, size_t id)
+{
+    return (sc.io_fmt & LH_IO_RAYS_F32) ? (double)((const float *)sc.tmax)[id] : ((const double *)sc.tmax)[id];
+}
+/* the start values, right after lane_init (and after ray_needs_ref_walk has asked its box under the unbounded 1e38f: the rays it sends to the
+ * reference walk stay a superset of the unbounded launch's) */
+__device__ __forceinline__ void tmax_start(Lane &L, Best &best, const double tmax)
+{
+    L.tb = lh_tmax_tb(tmax); best.t = lh_tmax_best0(tmax);
+}
+/* the end of a bounded ray's walk, after finish(): an accepted hit near the bound is fragile (a partner beyond the bound went unseen), a miss
+ * carries the miss record's t, not the bound */
+__device__ __forceinline__ void tmax_retire(Best &best, const double tmax)
+{
+    if (best.prim != LH_MISS_PRIM) { if (lh_tmax_near(best.t, tmax)) best.frag |= 2u; }
+    else best.t = LH_T_INF;
+}
+/* the reference walk's record (always unbounded) through the final accept */
+#define LH_TMAX_FILTER_REF(rh, tmax) do { if (!((rh).prim != LH_MISS_PRIM && lh_tmax_accept((rh).t, (tmax)))) { (rh).prim = LH_MISS_PRIM; (rh).t = LH_T_INF; (rh).u = 0.0; (rh).v = 0.0; } } while (0)
+
 /* lh_slab_w (lh_filter.h) written for the VALU: per axis one rotate (v_alignbit_b32 by 0 or 16)
  * puts (near, far) into the (low, high) halves, two SDWA converts, two FMAs: 136 VALU ops per
  * 4-wide node step instead of 161 with per-plane selects.  Measured (A/B, 50 M rays): +1.5 %;
@@ -140,7 +161,9 @@ __device__ __forceinline__ bool slab_w(const Lane &L, uint32_t wx, uint32_t wy, 
  * Rejected: nothing.  Certain hit: ends an any-hit ray at once, shrinks the closest-hit culling bound.
  * Anything not rejected joins the pending list (resolved in fp64 now if the list is full).
  * Returns true when the ray is finished (any-hit only). */
-template <bool ANYHIT, bool COUNT, class RayLoad>
+/* TMAX (a bounded launch, lh_tmax.h): L.tb started at the ray's fp32 bound and an any-hit walk never moves it -- a certain hit ends the
+ * ray only where its t_hi is provably below the bound, else it is a candidate for the fp64 test like any other */
+template <bool ANYHIT, bool COUNT, class RayLoad, bool TMAX = false>
 __device__ __forceinline__ bool tri_step_g(Lane &L, const lh_dev_scene_t &sc, float v0x, float v0y, float v0z,
                                            float e1x, float e1y, float e1z, float e2x, float e2y, float e2z,
                                            float ne1, float ne2, uint32_t prim, RayLoad ray, Best &best, uint32_t &c_exact)
@@ -148,7 +171,7 @@ __device__ __forceinline__ bool tri_step_g(Lane &L, const lh_dev_scene_t &sc, fl
     float t_hi;
     const int cls = lh_tri_filter(&L.r, v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z, ne1, ne2, L.tb, &t_hi);
     if (cls == LH_TRI_REJECT) return false;
-    const bool sure = (cls == LH_TRI_CERTAIN);
+    const bool sure = (cls == LH_TRI_CERTAIN) && (!(TMAX && ANYHIT) || t_hi < lh_tmax_sure_below(L.tb));
     if (ANYHIT && sure) { L.certain = true; return true; }
     if (sure) L.tb = fminf(L.tb, t_hi);
     if (L.np == kPend) {
@@ -168,16 +191,15 @@ __device__ __forceinline__ bool tri_step_g(Lane &L, const lh_dev_scene_t &sc, fl
 }
 
 /* the same with the fp64 ray held in registers (the lane walks) */
-template <bool ANYHIT, bool COUNT>
+template <bool ANYHIT, bool COUNT, bool TMAX = false>
 __device__ __forceinline__ bool tri_step(Lane &L, const lh_dev_scene_t &sc, float v0x, float v0y, float v0z,
                                          float e1x, float e1y, float e1z, float e2x, float e2y, float e2z,
                                          float ne1, float ne2, uint32_t prim,
                                          double ox, double oy, double oz, double dx, double dy, double dz,
                                          Best &best, uint32_t &c_exact)
 {
-    return tri_step_g<ANYHIT, COUNT>(L, sc, v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z, ne1, ne2, prim,
-                                     [=](double &a, double &b, double &c, double &d, double &e, double &f) { a = ox; b = oy; c = oz; d = dx; e = dy; f = dz; },
-                                     best, c_exact);
+    auto ray = [=](double &a, double &b, double &c, double &d, double &e, double &f) { a = ox; b = oy; c = oz; d = dx; e = dy; f = dz; };
+    return tri_step_g<ANYHIT, COUNT, decltype(ray), TMAX>(L, sc, v0x, v0y, v0z, e1x, e1y, e1z, e2x, e2y, e2z, ne1, ne2, prim, ray, best, c_exact);
 }
 
 /* (Round 5 also tried ONE candidate per regroup in the persistent walk -- a lane with more stays idle, unretired, and takes its next
