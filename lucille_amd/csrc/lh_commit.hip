@@ -3,6 +3,7 @@
  * device build, the device replica of the scene, parameters.  Reference: accel_build_func / accel_free_func
  * (src/render/accel.h:24-28), ri_bvh_build (src/render/bvh.c:276-379), ri_bvh_free (bvh.c:381-387).
  */
+#include <assert.h>
 #include <thread>
 #include <vector>
 
@@ -471,6 +472,7 @@ static void publish_scene(lh_accel_t *a)
     d->ref_lca = a->d_ref_lca; d->prim_leafpos = a->d_prim_leafpos; d->ref_nodes = a->d_ref_nodes; d->ref_leaf_prims = a->d_ref_leaf_prims;
     d->ntris = b->ntris; d->nnodes = b->nnodes; d->max_depth = b->max_depth;
     d->nq4nodes = b->nq4nodes; d->q4_depth = b->q4_depth; d->q4_stack = b->q4_stack;
+    assert((uint64_t)b->nq4nodes * sizeof(lh_q4node_t) < (1ull << 32));      /* node_step4 (lh_kernels.hip) addresses a node by a 32-bit byte offset from q4nodes */
     d->nq8nodes = a->d_q8nodes ? b->nq8nodes : 0u; d->q8_depth = a->d_q8nodes ? b->q8_depth : 0u;       /* the host scene's may be another replica's */
     d->scene_r = 0.0f;
     for (int k = 0; k < 3; k++) {

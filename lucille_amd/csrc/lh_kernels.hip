@@ -130,6 +130,9 @@ __device__ __forceinline__ void traverse(Lane &L, const lh_dev_scene_t &sc,
  * budget x latency instead of by its longest ray (profiles/README.md r03: 3-6 ms per launch on a
  * rank's share of the frame).  STRIDE: lanes per LDS stack row (LH_BLOCK, or 64 in k_coop_walk). */
 constexpr int kNoLeaf = 0;       /* never a valid leaf reference (leaf refs are negative) */
+#define LH_AS_LDS    __attribute__((address_space(3)))
+#define LH_AS_GLOBAL __attribute__((address_space(1)))
+typedef uint32_t lh_u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kRegroupMask = 63u;   /* the walk returns to the regroup point at least every 64 iterations */
 
 /* RING: stack positions are taken modulo ring_mask + 1 rows (k_coop_walk: a lane that gives entries away from the bottom of
@@ -149,13 +152,17 @@ __device__ __forceinline__ void node_step4(Lane &L, int &pend, const lh_dev_scen
 {
 #define LH_ROW(x) (RING ? ((x) & ring_mask) : (x))
     /* the first ntop nodes (level order: the top of the tree, which every ray walks) are read from the workgroup's copy in LDS:
-     * no request leaves the CU for them */
-    uint4 a, b, c, r;
+     * no request leaves the CU for them.  Two typed pointers and a divergent branch, on purpose: through one generic pointer the
+     * two sides become a select of addresses and four FLAT loads -- every node of every lane down both the LDS and the texture
+     * path, one wait on both counters, seven VALU for the address.  As written: ds_read_b128 x 4 for the lanes inside the top,
+     * global_load_dwordx4 x 4 from the scene's base plus a 32-bit byte offset (nq4nodes * 64 < 2^32: lh_commit.hip
+     * publish_scene) for the others */
+    lh_u32x4 a, b, c, r;          /* the compiler's own vector type: a uint4 is copied through a generic reference, and the loads with it */
     if (!RING && (uint32_t)L.cur < ntop) {
-        const uint4 *lp = top + 4 * (uint32_t)L.cur;
+        const LH_AS_LDS lh_u32x4 *lp = (const LH_AS_LDS lh_u32x4 *)top + 4 * (uint32_t)L.cur;
         a = lp[0]; b = lp[1]; c = lp[2]; r = lp[3];
     } else {
-        const uint4 *p = (const uint4 *)sc.q4nodes + 4 * (size_t)L.cur;
+        const LH_AS_GLOBAL lh_u32x4 *p = (const LH_AS_GLOBAL lh_u32x4 *)((const LH_AS_GLOBAL char *)sc.q4nodes + (size_t)((uint32_t)L.cur << 6));
         a = p[0]; b = p[1]; c = p[2]; r = p[3];
     }
     if (COUNT) c_nodes++;
@@ -166,30 +173,45 @@ __device__ __forceinline__ void node_step4(Lane &L, int &pend, const lh_dev_scen
     const bool h3 = slab_w(L, c.y, c.z, c.w, t3) & ((int)r.w != kDone);
     const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
     const int base = L.sp + nh - 1;
+    /* d0..d3: a hit's row below `base` (its rank among the hits, nearest = 0), counted DOWN (0, -1, -2, -3).  Every miss goes to
+     * row base + 1, the row above the new top: free space (writes reach sp + 3 at most, as they always did) */
+    int d0, d1, d2, d3;
     if (SORTED) {
-        /* entry distances are >= 0, so their bit patterns order like unsigned integers */
-        const uint32_t k0 = h0 ? ((__float_as_uint(t0) & ~3u) | 0u) : 0xFFFFFFFCu;
-        const uint32_t k1 = h1 ? ((__float_as_uint(t1) & ~3u) | 1u) : 0xFFFFFFFDu;
-        const uint32_t k2 = h2 ? ((__float_as_uint(t2) & ~3u) | 2u) : 0xFFFFFFFEu;
-        const uint32_t k3 = h3 ? ((__float_as_uint(t3) & ~3u) | 3u) : 0xFFFFFFFFu;
-        const int b10 = k1 < k0, b20 = k2 < k0, b30 = k3 < k0, b21 = k2 < k1, b31 = k3 < k1, b32 = k3 < k2;
-        const int rk0 = b10 + b20 + b30, rk1 = (1 - b10) + b21 + b31;
-        const int rk2 = (2 - b20 - b21) + b32, rk3 = 3 - b30 - b31 - b32;
-        stk[LH_ROW(h0 ? base - rk0 : L.sp + rk0)][tid] = (int)r.x;
-        stk[LH_ROW(h1 ? base - rk1 : L.sp + rk1)][tid] = (int)r.y;
-        stk[LH_ROW(h2 ? base - rk2 : L.sp + rk2)][tid] = (int)r.z;
-        stk[LH_ROW(h3 ? base - rk3 : L.sp + rk3)][tid] = (int)r.w;
+        /* entry distances are >= 0, so their bit patterns order like unsigned integers.  A key is the distance's bits with the slot
+         * number in the two low bits; a miss's is all ones above its slot number.  Written as one select of constants and one
+         * and-or per child: or-ing a miss with 0xFFFFFFFC | slot gives exactly that */
+        const uint32_t k0 = (__float_as_uint(t0) & ~3u) | (h0 ? 0u : 0xFFFFFFFCu);
+        const uint32_t k1 = (__float_as_uint(t1) & ~3u) | (h1 ? 1u : 0xFFFFFFFDu);
+        const uint32_t k2 = (__float_as_uint(t2) & ~3u) | (h2 ? 2u : 0xFFFFFFFEu);
+        const uint32_t k3 = (__float_as_uint(t3) & ~3u) | (h3 ? 3u : 0xFFFFFFFFu);
+        const int b10 = -(int)(k1 < k0), b20 = -(int)(k2 < k0), b30 = -(int)(k3 < k0), b21 = -(int)(k2 < k1), b31 = -(int)(k3 < k1), b32 = -(int)(k3 < k2);
+        d0 = b10 + b20 + b30; d1 = (-1 - b10) + b21 + b31;
+        d2 = (-2 - b20 - b21) + b32; d3 = -3 - b30 - b31 - b32;
     } else {
-        /* hit c sits below the hits before it (slot 0 ends on top); every miss goes to the row above the new top: free space */
-        const int a1 = (int)h0, a2 = a1 + (int)h1, a3 = a2 + (int)h2;
-        stk[LH_ROW(h0 ? base : base + 1)][tid] = (int)r.x;
-        stk[LH_ROW(h1 ? base - a1 : base + 1)][tid] = (int)r.y;
-        stk[LH_ROW(h2 ? base - a2 : base + 1)][tid] = (int)r.z;
-        stk[LH_ROW(h3 ? base - a3 : base + 1)][tid] = (int)r.w;
+        /* hit c sits below the hits before it (slot 0 ends on top) */
+        d0 = 0; d1 = -(int)h0; d2 = d1 - (int)h1; d3 = d2 - (int)h2;
+    }
+    int nxt, popped2;
+    if (RING) {
+        stk[LH_ROW(h0 ? base + d0 : base + 1)][tid] = (int)r.x;
+        stk[LH_ROW(h1 ? base + d1 : base + 1)][tid] = (int)r.y;
+        stk[LH_ROW(h2 ? base + d2 : base + 1)][tid] = (int)r.z;
+        stk[LH_ROW(h3 ? base + d3 : base + 1)][tid] = (int)r.w;
+        nxt = stk[LH_ROW(base)][tid];
+        popped2 = stk[LH_ROW(base - 1)][tid];
+    } else {
+        /* through the address of the lane's entry in row `base`: a hit's is that minus its rank's rows (one shift-add), the
+         * miss row and the two reads (the new top, the entry under it) are constant offsets from it */
+        LH_AS_LDS int *const pb = (LH_AS_LDS int *)&stk[0][tid] + base * STRIDE;
+        LH_AS_LDS int *const pm = pb + STRIDE;
+        *(h0 ? pb + d0 * STRIDE : pm) = (int)r.x;
+        *(h1 ? pb + d1 * STRIDE : pm) = (int)r.y;
+        *(h2 ? pb + d2 * STRIDE : pm) = (int)r.z;
+        *(h3 ? pb + d3 * STRIDE : pm) = (int)r.w;
+        nxt = *pb;
+        popped2 = *(pb - STRIDE);
     }
     L.sp = base;
-    const int nxt = stk[LH_ROW(base)][tid];
-    const int popped2 = stk[LH_ROW(L.sp - 1)][tid];
     const bool is_leaf = (nxt < 0) & (nxt != kDone);
     const bool park = is_leaf & (pend == kNoLeaf);
     pend = park ? nxt : pend;
@@ -234,8 +256,13 @@ __device__ __forceinline__ void traverse_spec4(Lane &L, int &pend, const lh_dev_
     const int rows = (int)sc.stack_rows;
     const uint4 *top = (const uint4 *)(&stk[rows][0]);        /* the workgroup's copy of the first sc.top_nodes nodes, behind the stack rows */
     const uint32_t ntop = sc.top_nodes;
+    /* the loop's wave-uniform state in scalar registers.  The compiler cannot see that the caller's threshold is uniform (it hangs
+     * on `exhausted`, first set from the wave's number), and with a divergent exit test the iteration counter, the threshold and
+     * the batch size all lived in VGPRs: an add, an and and three compares on the VALU per iteration */
+    const int s_min = __builtin_amdgcn_readfirstlane(min_active), s_batch = __builtin_amdgcn_readfirstlane(tri_batch);
+    uint32_t s_it = (uint32_t)__builtin_amdgcn_readfirstlane((int)it);
     for (;;) {
-        if (COUNT) { if (__ballot(L.cur >= 0) != 0ull) c_nslots++; }
+        if (COUNT) { if (__builtin_amdgcn_ballot_w64(L.cur >= 0) != 0ull) c_nslots++; }
         /* the step below writes up to slot sp + 3.  rows = 3 * depth + 5 covers every ray of a tree that deep; a deeper
          * tree (an LBVH built on the device over a degenerate distribution) gets 64 rows and a ray that would overrun them
          * is finished by k_coop_walk -- same arithmetic, same answer */
@@ -244,19 +271,22 @@ __device__ __forceinline__ void traverse_spec4(Lane &L, int &pend, const lh_dev_
              * an inner node in the triangle pass and steps with a stack pointer one below the one that was never checked -- the
              * write landed one row past the stack (dropped by the LDS until round 4 put the top of the tree there).  One compare
              * and a scalar branch per iteration */
-            const bool ov = (L.cur >= 0) & (L.sp + 4 > rows);
-            if (__builtin_expect(__ballot(ov) != 0ull, 0)) { if (ov) { L.over = true; L.cur = kDone; pend = kNoLeaf; } }
+            const bool ov = (L.cur >= 0) & (L.sp > rows - 4);
+            if (__builtin_expect(__builtin_amdgcn_ballot_w64(ov) != 0ull, 0)) { if (ov) { L.over = true; L.cur = kDone; pend = kNoLeaf; } }
         }
         if (L.cur >= 0) node_step4<COUNT, LH_BLOCK, false, SORTED>(L, pend, sc, stk, tid, c_nodes, 0, top, ntop);
-        const unsigned long long m_node = __ballot(L.cur >= 0);
-        const unsigned long long m_pend = __ballot(pend != kNoLeaf);
-        if (m_pend != 0ull && (__popcll(m_pend) >= tri_batch || m_node == 0ull)) {
+        /* the ballots of the conditions themselves (__ballot takes an int: a 0/1 copy of the condition, compared once more) */
+        const unsigned long long m_node = __builtin_amdgcn_ballot_w64(L.cur >= 0);
+        const unsigned long long m_pend = __builtin_amdgcn_ballot_w64(pend != kNoLeaf);
+        if (m_pend != 0ull && (__popcll(m_pend) >= s_batch || m_node == 0ull)) {
             if (COUNT) c_tslots++;
             tri_pass<ANYHIT, COUNT, LH_BLOCK, false, TMAX>(L, pend, sc, stk, tid, ox, oy, oz, dx, dy, dz, best, c_tris, c_exact);
         }
-        const unsigned long long m_work = __ballot((L.cur != kDone) | (pend != kNoLeaf));
-        if (__popcll(m_work) < min_active || (++it & kRegroupMask) == 0u) break;      /* at least every 64 iterations: the visit budget is checked at regroup points */
+        /* two ballots and a scalar or: the ballot of the or of two conditions goes through a 0/1 copy in a VGPR and one more compare */
+        const unsigned long long m_work = __builtin_amdgcn_ballot_w64(L.cur != kDone) | __builtin_amdgcn_ballot_w64(pend != kNoLeaf);
+        if (__popcll(m_work) < s_min || (++s_it & kRegroupMask) == 0u) break;      /* at least every 64 iterations: the visit budget is checked at regroup points */
     }
+    it = s_it;
 }
 
 /* The same walk over the 8-wide 16-bit-grid nodes (lh_q8node_t): one 128-byte record -- one cache line -- decides eight

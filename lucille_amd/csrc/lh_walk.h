@@ -144,6 +144,12 @@ __device__ __forceinline__ void tmax_retire(Best &best, const double tmax)
  * v_pk_fma_f32 for the two FMAs is 2 % SLOWER, reading the stack top before the slab tests
  * instead of after the pushes changes nothing -- the step is not VALU- or LDS-latency-bound
  * (profiles/README.md, r01d). */
+/* L.tb is never a NaN: it starts at 1e38f (lane_init), at a bounded ray's finite fp32 bound (tmax_start) or at -1
+ * (LH_FORCE_REF_WALK), and tri_step_g only lowers it, through fminf, to a certain hit's finite t_hi.  The compiler cannot follow
+ * that around the walk's loop, so the fminf below quiets L.tb first: one v_max_f32 v, tb, tb per node step, shared by the four
+ * children.  It stays: the minimumNumber builtin gets the same quieting, relaxed floating point cannot be had for one
+ * operation on this target (#pragma float_control is ignored), for the file it would reach the fp64 resolve, and an integer
+ * minimum of the bit patterns goes wrong where a far plane is -0 under a negative bound. */
 __device__ __forceinline__ bool slab_w(const Lane &L, uint32_t wx, uint32_t wy, uint32_t wz, float &tn_out)
 {
     const uint32_t sx = __builtin_amdgcn_alignbit(wx, wx, L.sh[0]);
