@@ -450,6 +450,44 @@ int  lh_accel_ao_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_org
                              const void *d_key, const void *d_uniforms, void *d_slot_of_ray, void *d_nslots,
                              void *d_ao_org_xyz, void *d_ao_dir_xyz, size_t capacity_rays, void *stream);
 
+/* ---- the dirtmap transport: range-limited, distance-weighted occlusion (ri_transport_dirtmap, src/transport/dirtmap.c:84-292) ----
+ * "AO with a range": the same stratified cosine hemisphere about Ns and the same ortho basis as the AO stage, the origin P + eps Ns,
+ * and for every gather ray its CLOSEST hit, weighted by where that hit lies between a near and a far clip; beyond the far clip a hit
+ * counts as no hit.  R is the record the bounded closest-hit contract of lh_accel_intersect_device_tmax gives the gather ray with
+ * tmax = far_clip: a hit only if the unbounded record is a hit with t < far_clip (fp64, strict).
+ *   weight c of one gather ray:  R is a miss -> 1;  R.t <= near_clip -> 0;  else a = R.t - near_clip, b = far_clip - near_clip,
+ *     q = a / b, x = 1 - q, p = x clamped to [0, 1], c = 1 - p -- fp64, in this order (the reference's base colour 1, dirt colour 0 and
+ *     gain 1 are not parameters: its pow(x, 1 / gain) is x).
+ *   value of one hit: with N = floor(sqrt(gather_nsamples))^2 rays, sum = 0; for r = 0 .. N - 1 (r = j * ntheta + i): sum = sum + c_r;
+ *     value = sum / N, in fp64.  The order is part of the contract.
+ *   parameters: all finite, 0 <= near_clip < far_clip <= 1e38, eps >= 0; NULL: LH_DIRT_DEFAULTS.  Anything else, NaN included, is
+ *     refused ("bad dirt parameters").  The self-primitive skip of a flat-shaded hit is applied only when eps >= 1e-6.
+ * lh_accel_dirt_device: as lh_accel_ao_device, word for word -- list, count and key semantics, hit slots in list order, the uniforms
+ *   replay (2 doubles per gather ray in (slot, j, i) order), untouched slots of rays that are not traced, synchronous on `stream`, the
+ *   empty scene, scratch of its own (lh_render_scratch keeps showing the last AO tile), its refusals.  d_near_hits[id] (uint32, may
+ *   be NULL) = the hit's gather rays whose bounded record is a hit; d_value[id] (float, may be NULL) = (float)value.  A traced miss
+ *   gets LH_AO_NO_HIT and 0.0f.  Fused when "ao_fused" is on, no uniforms are given, the scene is not empty and list entries x N
+ *   < 2^31: a closest-hit kernel makes the gather rays itself, walks them under the one bound far_clip and keeps one double per ray
+ *   (the bounded record's t); else, and as the second try of a fused launch whose queue overflowed, the rays are materialised in HBM
+ *   and traced by one bounded closest-hit launch whose bounds are all far_clip.  Both give the same bytes.  With
+ *   lh_accel_trace_statistics on, `rays` advances by hits x N and counters[4] by the bounded hits.
+ * lh_render_dirt_tile: ri_transport_dirtmap per camera sample, without the texture multiply -- a miss gives 0, a hit its value;
+ *   sub-samples accumulated and written as lh_render_ao_tile does, keys are the absolute sample position (a frame does not depend on
+ *   its tiling); stats->ao_rays = hits x N, stats->ao_occluded = the sum of the hits' near_hits. */
+typedef struct lh_dirt_params { double near_clip, far_clip, eps; } lh_dirt_params_t;
+#define LH_DIRT_DEFAULTS { 0.1, 0.5, 1.0e-5 }          /* dirtmap.c:98,110-111 */
+int  lh_accel_dirt_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                          const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                          int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed, const void *d_key, const void *d_uniforms,
+                          const void *d_index, size_t n_index, const void *d_count,
+                          void *d_near_hits, void *d_value, void *stream);
+int  lh_accel_dirt_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,
+                        const double *t, const double *u, const double *v, int gather_nsamples, const lh_dirt_params_t *params,
+                        uint64_t seed, const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *near_hits, float *value);
+int  lh_render_dirt_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
+                         int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed,
+                         const void *d_uniforms, void *d_rgb, lh_tile_stats_t *stats, void *stream);
+
 /* one path-traced tile on the device (BASELINE config 4: the reference's pathtrace.c is dead
  * code; its documented structure -- camera sample, Russian roulette on the reflectance,
  * cosine-sampled diffuse bounces to a vertex limit, environment radiance on escape -- re-expressed

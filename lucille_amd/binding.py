@@ -102,6 +102,14 @@ class TileStats(C.Structure):
                 ("ao_occluded", C.c_uint64)]
 
 
+class DirtParams(C.Structure):
+    """lh_dirt_params_t: near clip, far clip and origin offset of the dirtmap transport (defaults: LH_DIRT_DEFAULTS)"""
+    _fields_ = [("near_clip", C.c_double), ("far_clip", C.c_double), ("eps", C.c_double)]
+
+    def __init__(self, near_clip=0.1, far_clip=0.5, eps=1.0e-5):
+        super().__init__(float(near_clip), float(far_clip), float(eps))
+
+
 # lh_beam_set_t (include/lucille_hip.h): a beam as lucille's ri_beam_set leaves it -- 232 bytes
 BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)), ("normal", np.float64, (4, 3)),
                            ("dominant_axis", np.int32), ("dirsign", np.int32, (3,))])
@@ -118,6 +126,7 @@ ABI_SYMBOLS = [
     "lh_rib_mesh", "lh_accel_add_rib_scene", "lh_hdr_write",
     "lh_accel_set_material", "lh_accel_set_environment", "lh_render_pt_tile2", "lh_render_pt_bands", "lh_accel_set_attribute", "lh_accel_set_normals_device", "lh_accel_set_attribute_device",
     "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
+    "lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
     "lh_multi_add_rib_scene", "lh_multi_commit", "lh_multi_set_material", "lh_multi_set_environment", "lh_multi_intersect_host",
     "lh_multi_render_ao_frame_host", "lh_multi_render_pt_frame_host",
@@ -202,6 +211,11 @@ def lib():
     L.lh_accel_ao_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, C.c_uint64, vp, vp, vp, sz, vp, vp, vp, vp]
     L.lh_accel_ao_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, C.c_uint64, vp, vp, sz, vp, vp]
     L.lh_accel_ao_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, C.c_uint64, vp, vp, vp, vp, vp, vp, sz, vp]
+    dpp = C.POINTER(DirtParams)
+    L.lh_accel_dirt_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, dpp, C.c_uint64, vp, vp, vp, sz, vp, vp, vp, vp]
+    L.lh_accel_dirt_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, dpp, C.c_uint64, vp, vp, sz, vp, vp]
+    L.lh_render_dirt_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, dpp, C.c_uint64, vp, vp,
+                                      C.POINTER(TileStats), vp]
     L.lh_multi_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32)]
     L.lh_multi_destroy.argtypes = [vp]; L.lh_multi_destroy.restype = None
     L.lh_multi_ndevices.argtypes = [vp]
@@ -801,6 +815,22 @@ class HipAccel:
                "lh_render_ao_tile")
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    def render_dirt_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, params=None, seed=1, uniforms=None, out=None,
+                         stream=None):
+        """lh_render_dirt_tile: the dirtmap transport's tile (params: a DirtParams, None: the defaults) ->
+        (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x N, ao_occluded = the bounded hits)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = TileStats()
+        _check(self.L.lh_render_dirt_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples,
+                                          None if params is None else C.byref(params), int(seed), _dptr(uniforms), _dptr(out),
+                                          C.byref(st), C.c_void_p(stream)), "lh_render_dirt_tile")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     def render_ao_frame_host(self, cam, pixel_samples, gather_nsamples, seed=1, tile=0):
         """lh_render_ao_frame_host: the whole frame into host memory -> (float32 [H, W, 3] numpy, top row first; stats)"""
         rgb = np.empty((cam.height, cam.width, 3), np.float32)
@@ -947,8 +977,25 @@ class HipAccel:
         and the float32 tensor [n] of (N - count) / N (0 for a miss).  out: such a pair to fill (either member may be None, not
         both); with out=None both are allocated with torch.empty and the slots of rays that are not listed are UNSPECIFIED.
         Synchronous: the outputs are complete on return."""
+        return self._batch_stage_device("ao_device", None, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
+
+    def dirt_device(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None, index=None, count=None,
+                    out=None, stream=None):
+        """lh_accel_dirt_device: the dirtmap transport's stage -- range-limited, distance-weighted occlusion -- for a batch of rays
+        and their closest-hit records; arguments as ao_device, and params: a DirtParams (None: near 0.1, far 0.5, eps 1e-5).
+        Returns (near_hits, value): an int32 tensor [n] whose bits are uint32 -- the hit's gather rays with a closest hit below
+        the far clip, AO_NO_HIT for a miss -- and the float32 tensor [n] of the mean weight (0 for a miss).  out: such a pair to
+        fill (either member may be None, not both); with out=None the slots of rays that are not listed are UNSPECIFIED.
+        Synchronous: the outputs are complete on return."""
+        if params is None:
+            params = DirtParams()
+        if not isinstance(params, DirtParams):
+            raise ValueError("dirt_device: params must be a DirtParams")
+        return self._batch_stage_device("dirt_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
+
+    def _batch_stage_device(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream):
+        """ao_device (dirt None) / dirt_device (dirt: its DirtParams): the checks and the call"""
         import torch
-        what = "ao_device"
         n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
         dev = org.device
         ip, ni, cp = _list_args(index, count, what)
@@ -967,6 +1014,11 @@ class HipAccel:
         if stream is None:
             stream = torch.cuda.current_stream(dev)
         stream = getattr(stream, "cuda_stream", stream)
+        if dirt is not None:
+            _check(self.L.lh_accel_dirt_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
+                                               C.byref(dirt), int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad),
+                                               C.c_void_p(stream)), "lh_accel_dirt_device")
+            return out
         _check(self.L.lh_accel_ao_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
                                          int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad), C.c_void_p(stream)),
                "lh_accel_ao_device")
@@ -1009,18 +1061,35 @@ class HipAccel:
 
     def ao_host(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None):
         """lh_accel_ao_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v)) -> (count uint32 [n], radiance float32 [n])"""
+        return self._batch_stage_host("ao_host", None, org, dr, records, gather_nsamples, seed, key, uniforms)
+
+    def dirt_host(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None):
+        """lh_accel_dirt_host: host arrays as ao_host, params as dirt_device -> (near_hits uint32 [n], value float32 [n])"""
+        if params is None:
+            params = DirtParams()
+        if not isinstance(params, DirtParams):
+            raise ValueError("dirt_host: params must be a DirtParams")
+        return self._batch_stage_host("dirt_host", params, org, dr, records, gather_nsamples, seed, key, uniforms)
+
+    def _batch_stage_host(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms):
         o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
         if d.shape[0] != n or len(records) != 4:
-            raise ValueError("ao_host: org, dr and the (prim, t, u, v) records must describe the same rays")
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
         p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
         u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
         if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
-            raise ValueError("ao_host: org, dr and the (prim, t, u, v) records must describe the same rays")
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
         k = None if key is None else _np(key, np.uint64).reshape(-1)
         if k is not None and k.shape[0] != n:
-            raise ValueError("ao_host: one key per ray")
+            raise ValueError("%s: one key per ray" % what)
         un = None if uniforms is None else _np(uniforms, np.float64).reshape(-1)
         cnt = np.empty(n, np.uint32); rad = np.empty(n, np.float32)
+        if dirt is not None:
+            _check(self.L.lh_accel_dirt_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                             int(gather_nsamples), C.byref(dirt), int(seed), None if k is None else k.ctypes.data,
+                                             None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,
+                                             rad.ctypes.data), "lh_accel_dirt_host")
+            return cnt, rad
         _check(self.L.lh_accel_ao_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
                                        int(gather_nsamples), int(seed), None if k is None else k.ctypes.data,
                                        None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,

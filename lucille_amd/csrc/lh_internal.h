@@ -55,6 +55,9 @@ struct lh_buf { void *p; size_t cap; };
 /* what the AO stage (lh_tile.hip ao_stage) owns for one kind of caller: slot of every sample / list entry, hit records, slot keys, per-slot
  * occlusion counts (fused), the materialised rays and their any-hit bytes, the compaction's block counts */
 struct lh_ao_scratch { lh_buf slot, hitrec, key, occcount, aorg, adir, occ, blocks; };
+/* ... and what the dirt stage adds for its gather rays (lh_dirt.h): the t of the bounded closest-hit records, and for a materialised stage the bounds and
+ * the rest of the records (prim; u and v) */
+struct lh_dirt_scratch { lh_buf t, bound, prim, uv; };
 #define LH_AOQ_SLOTS 4
 #define LH_PIPE_DEPTH_MAX 8   /* staging blocks of a pipelined host batch (lh_query.hip) */
 
@@ -140,6 +143,11 @@ struct lh_accel {
      * lh_render_scratch keeps showing the last tile call; the batch's totals (hits; 64 occlusion counters), lh_accel_ao_host's staging */
     lh_ao_scratch batch_ao;
     lh_buf b_tot, b_host;
+    /* the dirt stage (lh_render_dirt_tile, lh_accel_dirt_device / _host): scratch of its own for the tile and for a batch, so that lh_render_scratch
+     * keeps showing the last AO tile */
+    lh_ao_scratch tile_dirt, batch_dirt;
+    lh_dirt_scratch tile_dirt_t, batch_dirt_t;
+    lh_buf d_tot, d_rays;              /* a batch's totals; the tile's camera rays and their closest-hit records */
     uint64_t last_retraced;            /* rays the last counted launch finished outside the main kernel */
     int ao_fused;                      /* AO rays generated inside the any-hit kernel (default); 0: materialised in HBM */
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */
@@ -263,7 +271,7 @@ extern "C" int lh_render_launch_compact(const lh_dev_scene_t *sc, const double *
                                         uint32_t *d_slot_of_sample, double *d_hitrec,
                                         unsigned long long *d_slot_key, int x0, int w, int nbands, int band_rows,
                                         const int *d_band_y0, int y0, int spp, int full_width,
-                                        unsigned long long *d_total, void *stream);
+                                        unsigned long long *d_total, double eps, void *stream);
 extern "C" int lh_render_launch_primary_region(const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0,
                                                int y0, int height_limit, int xs, int ys, double *d_org, double *d_dir, void *stream);
 extern "C" int lh_render_launch_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long long seed,
@@ -277,13 +285,20 @@ extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const do
                                               const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
                                               const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
                                               double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
-                                              uint32_t *d_nslots32, void *stream);
+                                              uint32_t *d_nslots32, double eps, void *stream);
 extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
                                               const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
                                               uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream);
 extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigned long long *d_nslots, int ntheta, int nphi,
                                                 unsigned long long seed, const double *d_hitrec, const double *d_rnd,
                                                 const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
+extern "C" int lh_render_launch_dirt_bounds(size_t n, double far_clip, double *d_bound, void *stream);
+extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
+                                             const uint32_t *d_slot_of_sample, const double *d_t, float *d_rgb,
+                                             unsigned long long *d_hit_total, void *stream);
+extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
+                                                   double near_clip, double far_clip, const uint32_t *d_slot_of_entry, const double *d_t,
+                                                   uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream);
 extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
                                             const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
                                             const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,

@@ -511,7 +511,20 @@ struct AoSrc {
     const unsigned long long *nslots_dev; /* NULL, or: the slot count lives on the device (the compaction's total: the host launches this stage without reading
                                              it back; nslots is then its upper bound) */
     uint32_t budget_big;                  /* 0, or: the visit budget of a launch that turns out to hold 2^27 rays or more (lh_tile.hip) */
+    /* the dirt stage (closest hit, TMAX; lh_dirt.h): the bound of every ray of the launch, and where the t of ray (slot, r)'s bounded record goes --
+     * element slot * N + r, 1e38 for a miss; no kernel of the AO stage looks at either */
+    double far_clip; double *dirt_t;
 };
+
+/* the bound of ray `id` of a bounded launch: its element of sc.tmax -- or, for the rays a kernel makes itself (SRC 1: the dirt stage), the launch's one bound */
+template <int SRC>
+__device__ __forceinline__ double lane_tmax(const lh_dev_scene_t &sc, const AoSrc &ao, size_t id)
+{
+    return SRC == 1 ? ao.far_clip : ray_tmax(sc, id);
+}
+
+/* the dirt stage's one store per gather ray: the t of its bounded record (no atomic; the ray and the rest of the record stay in registers) */
+__device__ __forceinline__ void dirt_store(const AoSrc &ao, uint32_t i, double t);
 
 /* Work item i of a fused AO stage -> (hit slot, sample).  The plain order -- a slot's N samples side by side -- puts the N
  * directions of ONE hemisphere into the lanes of a wave: one origin, sixty-four directions, and one address for their
@@ -526,6 +539,13 @@ __device__ __forceinline__ void ao_item(const AoSrc &ao, uint32_t i, uint32_t &s
     const uint32_t G = (uint32_t)ao.group, per = G * N, blk = i / per, q = i - blk * per;
     const uint32_t left = ao.nslots - blk * G, m = left < G ? left : G;      /* the last group may be short */
     r = q / m; slot = blk * G + (q - r * m);
+}
+
+__device__ __forceinline__ void dirt_store(const AoSrc &ao, uint32_t i, double t)
+{
+    uint32_t sl, rr;
+    ao_item(ao, i, sl, rr);
+    ao.dirt_t[(size_t)sl * (size_t)(ao.ntheta * ao.nphi) + rr] = t;
 }
 
 /* ray `i` of the launch.  SRC 0: from the arrays; 1: the AO ray (slot i / N, sample i % N) regenerated from the hit record
@@ -607,7 +627,7 @@ __device__ __forceinline__ void trace_persist_lane(
         if (COUNT) crs++;
         if (idle && my != kNoRay) {
             if (!L.over) finish<ANYHIT, COUNT>(L, sc, ox, oy, oz, dx, dy, dz, best, ce, SRC == 1 ? selfp : LH_MISS_PRIM);
-            if (TMAX && !L.over) tmax_retire(best, ray_tmax(sc, my));
+            if (TMAX && !L.over) tmax_retire(best, lane_tmax<SRC>(sc, ao, my));
             /* rays the persistent walk does not finish go through the fix-up queue to the concurrent consumer: out of budget /
              * stack rows -> the cooperative walk; a hit the reference may not reach (fragile; a certain fp32 hit is strictly
              * inside its triangle, hence inside every box: never fragile) -> the reference's own walk.  A full queue (ray dumps:
@@ -621,6 +641,7 @@ __device__ __forceinline__ void trace_persist_lane(
                 if (!queued) { if (ANYHIT) occ[my] = (uint8_t)LH_OCC_RETRACE; else rec_prim<true>(sc, prim, my) = LH_PRIM_RETRACE; }
             } else
             if (SRC != 1) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT, SRC == 0 && IO>(sc, my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
+            else if (!ANYHIT) { if (!L.over && !fragile) dirt_store(ao, my, best.t); }          /* the dirt stage: a queued ray's word is the consumer's to store */
             else if (!L.over && !fragile && (L.certain || best.prim != LH_MISS_PRIM)) { uint32_t sl, rr; ao_item(ao, my, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
             if (COUNT) {
                 cr++;
@@ -724,7 +745,7 @@ __device__ __forceinline__ void trace_persist_lane(
              * tree: the bit is set from the DOUBLE cap (lh_danger.h lh_dcap_srcs): the float cap of such a scene may be 1.0f.  Every other scene skips the test whole */
             if (TMAX) {
                 const bool refw = (sc.cap_srcs & (1u << SRC)) != 0u && ray_needs_ref_walk(sc, L, dx, dy, dz);      /* asked under the unbounded 1e38f */
-                tmax_start(L, best, ray_tmax(sc, i));
+                tmax_start(L, best, lane_tmax<SRC>(sc, ao, i));
                 if (__builtin_expect(refw, 0)) LH_FORCE_REF_WALK(L, best);
             } else
             if ((sc.cap_srcs & (1u << SRC)) != 0u && __builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
@@ -811,6 +832,23 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_t
         __syncthreads();
     }
     trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
+}
+
+/* the persistent kernel of the fused dirt stage (lh_launch_trace_dirt): the gather rays of ao.nslots hits, made in the refill (SRC 1), walked to their
+ * CLOSEST hit under the launch's one bound ao.far_clip (TMAX); the retire stores the bounded record's t.  A kernel of its own once more */
+template <bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_dirt(
+    lh_dev_scene_t sc, uint32_t n, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao, const FixQ fq)
+{
+    extern __shared__ int lh_stack_lds[];
+    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
+    if (sc.top_nodes) {
+        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
+        const uint4 *src = (const uint4 *)sc.q4nodes;
+        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
+        __syncthreads();
+    }
+    trace_persist_lane<false, COUNT, WALK, 1, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
 /* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
@@ -929,7 +967,7 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
                 /* every lane's candidates through the fp64 test, then the merge over the group */
                 bool need_ref = false, hit = false;
                 finish<ANYHIT, false>(L, sc, ox, oy, oz, dx, dy, dz, best, ce, selfp);
-                const double tmx = TMAX ? ray_tmax(sc, i) : 0.0;
+                const double tmx = TMAX ? lane_tmax<SRC>(sc, ao, i) : 0.0;
                 if (TMAX && ANYHIT) tmax_retire(best, tmx);          /* any hit: each lane's own hit decides by itself whether it is fragile */
                 if (ANYHIT) {
                     const bool exact = best.prim != LH_MISS_PRIM;
@@ -955,10 +993,11 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
                             if (TMAX) LH_TMAX_FILTER_REF(rh, tmx);
                             gb.prim = rh.prim; gb.t = rh.t; gb.u = rh.u; gb.v = rh.v;
                         }
-                        store_rec<SRC == 0>(sc, i, prim, t, u, v, gb.prim, gb.t, gb.u, gb.v);
+                        if (SRC == 1) dirt_store(ao, (uint32_t)i, gb.t);          /* the dirt stage keeps the record's t alone */
+                        else store_rec<SRC == 0>(sc, i, prim, t, u, v, gb.prim, gb.t, gb.u, gb.v);
                     }
                 }
-                if (SRC == 1 && (lane & 15) == 0) {
+                if (SRC == 1 && ANYHIT && (lane & 15) == 0) {
                     if (need_ref) hit = ref_trace_one(sc, ox, oy, oz, dx, dy, dz).prim != LH_MISS_PRIM;
                     if (hit) { uint32_t sl, rr; ao_item(ao, (uint32_t)i, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
                 }
@@ -989,7 +1028,7 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
                     src_ray<SRC>(sc, (uint32_t)i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
                     lane_init(L, sc, ox, oy, oz, dx, dy, dz);
                     best.t = LH_T_INF; best.u = 0.0; best.v = 0.0; best.prim = LH_MISS_PRIM; best.frag = 0u;
-                    if (TMAX) tmax_start(L, best, ray_tmax(sc, i));
+                    if (TMAX) tmax_start(L, best, lane_tmax<SRC>(sc, ao, i));
                     pend = kNoLeaf; floor_ = 1; stk[0][lane] = kDone;
                     L.cur = (lane & 15) == 0 ? 0 : kDone;
                     have = true;
@@ -1004,9 +1043,10 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
                     double rox, roy, roz, rdx, rdy, rdz; uint32_t rself = LH_MISS_PRIM;
                     src_ray<SRC>(sc, ri, org, dir, ao, rox, roy, roz, rdx, rdy, rdz, rself);
                     RefHit rh = ref_trace_one(sc, rox, roy, roz, rdx, rdy, rdz);
-                    if (TMAX) LH_TMAX_FILTER_REF(rh, ray_tmax(sc, ri));
+                    if (TMAX) LH_TMAX_FILTER_REF(rh, lane_tmax<SRC>(sc, ao, ri));
                     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
-                    if (SRC == 1) { if (rh.prim != LH_MISS_PRIM) { uint32_t sl, rr; ao_item(ao, ri, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); } }
+                    if (SRC == 1 && !ANYHIT) dirt_store(ao, ri, rh.t);
+                    else if (SRC == 1) { if (rh.prim != LH_MISS_PRIM) { uint32_t sl, rr; ao_item(ao, ri, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); } }
                     else if (ANYHIT) occ[ri] = rh.prim != LH_MISS_PRIM ? 1 : 0;
                     else store_rec<SRC == 0>(sc, ri, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
                 }
@@ -1100,6 +1140,15 @@ __global__ __launch_bounds__(64) void k_coop_walk_tmax(lh_dev_scene_t sc, const 
                                                        unsigned long long *counters, const uint32_t owner_groups)
 {
     coop_walk_body<ANYHIT, 0, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+}
+
+/* the cooperative walk of the fused dirt stage (ray source 1, closest hit, the launch's one bound) */
+__global__ __launch_bounds__(64) void k_coop_walk_dirt(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                                       uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                       double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
+                                                       unsigned long long *counters, const uint32_t owner_groups)
+{
+    coop_walk_body<false, 1, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1446,16 +1495,18 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
     /* the pass next to the producer (owner_groups 0) and the sweep behind it */
 #define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL(kern, dim3(GRID), dim3(64), lds, STREAM, scl, LH_BATCH_ARRAYS(b), \
                                                                       ao, fq, b.counters, OWNER_GROUPS)
-    auto *kern = k_coop_walk<ANYHIT, SRC>;
+    constexpr bool DIRT = TMAX && SRC == 1 && !ANYHIT;          /* the fused dirt stage */
+    auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
     if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
+    if (DIRT) kern = k_coop_walk_dirt;
     lh_dev_scene_t scl = sc;
     scl.stack_rows = coop_rows(sc);
     if (scl.stack_rows == 0) return -1;
     const size_t lds = ((size_t)scl.stack_rows * 64 + 128 + 64) * sizeof(int);          /* the stack ring, 2 x 64 exchange words, 4 x 16 stashed reference-walk entries */
-    static bool attr_set[2][4] = {{false, false, false, false}, {false, false, false, false}};          /* [3]: the bounded launches' kernel */
-    if (lds > 64 * 1024 && !attr_set[ANYHIT][TMAX ? 3 : SRC]) {
+    static bool attr_set[2][5] = {{false, false, false, false, false}, {false, false, false, false, false}};          /* [3]: the bounded launches' kernel, [4]: the dirt stage's */
+    if (lds > 64 * 1024 && !attr_set[ANYHIT][DIRT ? 4 : TMAX ? 3 : SRC]) {
         if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        attr_set[ANYHIT][TMAX ? 3 : SRC] = true;
+        attr_set[ANYHIT][DIRT ? 4 : TMAX ? 3 : SRC] = true;
     }
     hipStream_t aux = (hipStream_t)q->aux_stream;
     int grid = ncus > 0 ? ncus : 256;                      /* one wave per workgroup and CU, 4 rays per wave */
@@ -1527,6 +1578,42 @@ extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, size_t nslots, int n
     if (hipGetLastError() != hipSuccess) return -1;
     const lh_batch_t none = {n, LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};          /* the rays are made in the kernel, the answers counted per slot */
     return launch_coop<true, 1>(scl, none, ao, fq, q, ncus, s);
+}
+
+/* the dirt stage (lh_dirt.h) the same way: the gather rays of nslots hits made inside a CLOSEST-hit kernel that walks them under the one bound
+ * far_clip (lh_tmax.h) and stores the t of every ray's bounded record -- 1e38 for a miss -- at element slot * N + r of d_t; nothing else per ray
+ * goes through HBM.  Rays the persistent kernel does not finish go through the queue as above: out of budget or stack rows to the cooperative walk,
+ * fragile hits (the mark of a hit near the bound among them) to the reference's own walk, whose unbounded record is filtered by t < far_clip; both
+ * store the same word.  A queue overflow leaves words unwritten: the caller redoes the stage materialised */
+extern "C" int lh_launch_trace_dirt(const lh_dev_scene_t *sc, size_t nslots, int ntheta, int nphi, unsigned long long seed,
+                                    const double *d_hitrec, const unsigned long long *d_slot_key, double far_clip, double *d_t,
+                                    unsigned long long *d_counters, unsigned long long *d_cursor, int grid_blocks, int min_active,
+                                    int tri_batch, const lh_fixq_t *q, int ncus, const unsigned long long *d_nslots, uint32_t budget_big, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = nslots * (size_t)(ntheta * nphi);
+    if (n == 0) return 0;
+    if (n >= ((size_t)1 << 31) || !d_t) return -1;
+    lh_dev_scene_t scl = *sc;
+    bool guard = false;
+    scl.stack_rows = rows4(*sc, &guard, n >= 65536);
+    scl.stack_guard = guard ? 1 : 0;
+    scl.top_nodes = top_nodes_for(*sc, scl.stack_rows);
+    const size_t lds_bytes = (size_t)scl.stack_rows * LH_BLOCK * sizeof(int) + (size_t)scl.top_nodes * 64u;
+    scl.ray_chunk = LH_TILE_CHUNK;          /* the gather rays of a slot are coherent, as AO rays are */
+    clamp_chunk(scl, n, grid_blocks);
+    /* the plain item order (slot, sample): the grouped order is the AO stage's experiment */
+    AoSrc ao = {d_hitrec, d_slot_key, NULL, seed, ntheta, nphi, (uint32_t)nslots, 0, d_nslots, budget_big, far_clip, d_t};
+    FixQ fq = {(unsigned long long *)q->queue, q->qcount, q->qcap, (uint32_t)grid_blocks * (LH_BLOCK / 64), q->qcount + 4};
+    if (hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
+    if (fixq_begin(q, s) != 0) return -1;
+#define LH_DIRT_LAUNCH(CNT, W) LH_LAUNCH_PERSIST((k_trace_persist_dirt<CNT, W>), scl, (uint32_t)n, d_counters, (uint32_t *)d_cursor, min_active, tri_batch, ao, fq)
+    if (guard) { if (d_counters) LH_DIRT_LAUNCH(true, 8); else LH_DIRT_LAUNCH(false, 8); }
+    else { if (d_counters) LH_DIRT_LAUNCH(true, 3); else LH_DIRT_LAUNCH(false, 3); }
+#undef LH_DIRT_LAUNCH
+    if (hipGetLastError() != hipSuccess) return -1;
+    const lh_batch_t none = {n, LH_MODE_CLOSEST, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};          /* the rays are made in the kernel, their t stored through ao */
+    return launch_coop<false, 1, true>(scl, none, ao, fq, q, ncus, s);
 }
 
 /* the node formats a launch of `variant` reads on this scene (bit mask, LH_FMT_* in lh_internal.h): so that the commit

@@ -32,6 +32,7 @@
 #include "../../include/lucille_hip.h"
 #include "lh_internal.h"
 #include "lh_ao.h"
+#include "lh_dirt.h"
 
 namespace {
 
@@ -148,12 +149,13 @@ __global__ void k_scan_blocks(uint32_t nblocks, uint32_t *__restrict__ block_cou
 struct DevNormals { const double *nrm; };   /* 9 doubles per prim (n0 n1 n2), NaN n0.x => none */
 
 /* the hit epilogue of one AO slot, written once for k_ao_setup (a Region's samples) and k_ao_batch_setup (a caller's batch): the
- * 12-double hit record of `slot` for ray i of the arrays, and the self-primitive bits of the slot's key (its low 34 bits are the caller's) */
+ * 12-double hit record of `slot` for ray i of the arrays, and the self-primitive bits of the slot's key (its low 34 bits are the caller's).
+ * eps: the origin's offset along Ns -- 1e-6 for ambient occlusion (ambientocclusion.c:65-73), the dirt stage's own (lh_dirt.h) */
 __device__ __forceinline__ void ao_hit_epilogue(const void *tri64, const double *nrm9,
                                                 const double *org, const double *dir,
                                                 const uint32_t *prim, const double *t,
                                                 const double *u, const double *v, size_t i,
-                                                double *hitrec, unsigned long long *slot_key, uint32_t slot)
+                                                double *hitrec, unsigned long long *slot_key, uint32_t slot, const double eps)
 {
     LH_NC
     /* ri_intersection_state_build (intersection_state.c:99-248): P, Ng, Ns */
@@ -172,10 +174,11 @@ __device__ __forceinline__ void ao_hit_epilogue(const void *tri64, const double 
     } else {
         Ns[0] = Ng[0]; Ns[1] = Ng[1]; Ns[2] = Ng[2];
     }
-    /* flat-shaded: the origin triangle cannot occlude its own AO rays (lh_ao.h) -- unless it is degenerate (Ng = 0) */
-    const bool noself = !has_n && (Ng[0] != 0.0 || Ng[1] != 0.0 || Ng[2] != 0.0);
+    /* flat-shaded: the origin triangle cannot occlude its own AO rays (lh_ao.h) -- unless it is degenerate (Ng = 0), or the offset is
+     * smaller than the one that argument rests on */
+    const bool noself = !has_n && (Ng[0] != 0.0 || Ng[1] != 0.0 || Ng[2] != 0.0) && lh_dirt_selfskip(eps);
     slot_key[slot] |= (unsigned long long)(noself ? p : LH_SLOT_NOSELF) << LH_SLOTKEY_BITS;
-    /* ri_ortho_basis(basis, Ns) (reflection.c:311-333) and the 1e-6 offset (ambientocclusion.c:65-73) */
+    /* ri_ortho_basis(basis, Ns) (reflection.c:311-333) and the offset (ambientocclusion.c:65-73: 1e-6; dirtmap.c:98: 1e-5) */
     double b0[3], b1[3] = {0.0, 0.0, 0.0};
     int ax = 3;
     for (int k = 0; k < 3; k++) if (Ns[k] < 0.6 && Ns[k] > -0.6) { ax = k; break; }
@@ -184,19 +187,20 @@ __device__ __forceinline__ void ao_hit_epilogue(const void *tri64, const double 
     vcross(b0, b1, Ns); vnormalize(b0);
     vcross(b1, Ns, b0); vnormalize(b1);
     double *r = hitrec + 12 * (size_t)slot;
-    const double eps = 1.0e-6;
     for (int k = 0; k < 3; k++) { r[k] = P[k] + Ns[k] * eps; r[3 + k] = b0[k]; r[6 + k] = b1[k]; r[9 + k] = Ns[k]; }
 }
 
 /* one thread per primary sample: slot = exclusive scan of the hit flags; writes the
- * per-hit record {org(3), basis(9)} (12 doubles) and slot_of_sample */
+ * per-hit record {org(3), basis(9)} (12 doubles) and slot_of_sample.  EPS: the offset is the argument (the dirt stage); false: AO's
+ * constant 1e-6, the kernel the AO pipeline always ran (the argument cost it two VGPRs) */
+template <bool EPS>
 __global__ void k_ao_setup(size_t n, const lh_dev_scene_t sc, const double *__restrict__ nrm9,
                            const double *__restrict__ org, const double *__restrict__ dir,
                            const uint32_t *__restrict__ prim, const double *__restrict__ t,
                            const double *__restrict__ u, const double *__restrict__ v,
                            const uint32_t *__restrict__ block_offsets, uint32_t *__restrict__ slot_of_sample,
                            double *__restrict__ hitrec, unsigned long long *__restrict__ slot_key,
-                           const Region rg, int spp, int full_width)
+                           const Region rg, int spp, int full_width, const double eps)
 {
     LH_NC
     __shared__ uint32_t wsum[4];
@@ -221,7 +225,7 @@ __global__ void k_ao_setup(size_t n, const lh_dev_scene_t sc, const double *__re
         slot_key[slot] = (py * (unsigned long long)full_width + px) * (unsigned long long)spp + (i32 - ipix * (uint32_t)spp);      /* < 2^34: checked by the caller */
     }
 
-    ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, i, hitrec, slot_key, slot);
+    ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, i, hitrec, slot_key, slot, EPS ? eps : 1.0e-6);
 }
 
 /* counter-based uniforms in [0,1) with 32-bit resolution (like randomMT2's y*2^-32): lh_ao.h */
@@ -363,7 +367,8 @@ __global__ void k_ao_batch_count(const BatchList bl, const uint32_t *__restrict_
 
 /* k_ao_setup for a batch: one thread per list entry; slot_of_entry[k] = the entry's hit slot or LH_AO_NO_HIT, the hit record and
  * the slot key (the caller's key of the ray -- its id when key is NULL -- in the low 34 bits) through the same epilogue.
- * nslots_out (or NULL): the number of hits as one uint32, for a caller of lh_accel_ao_rays_device */
+ * nslots_out (or NULL): the number of hits as one uint32, for a caller of lh_accel_ao_rays_device.  EPS: as for k_ao_setup */
+template <bool EPS>
 __global__ void k_ao_batch_setup(const BatchList bl, const lh_dev_scene_t sc, const double *__restrict__ nrm9,
                                  const double *__restrict__ org, const double *__restrict__ dir,
                                  const uint32_t *__restrict__ prim, const double *__restrict__ t,
@@ -371,7 +376,7 @@ __global__ void k_ao_batch_setup(const BatchList bl, const lh_dev_scene_t sc, co
                                  const unsigned long long *__restrict__ key,
                                  const uint32_t *__restrict__ block_offsets, const unsigned long long *__restrict__ total,
                                  uint32_t *__restrict__ slot_of_entry, double *__restrict__ hitrec,
-                                 unsigned long long *__restrict__ slot_key, uint32_t *__restrict__ nslots_out)
+                                 unsigned long long *__restrict__ slot_key, uint32_t *__restrict__ nslots_out, const double eps)
 {
     LH_NC
     __shared__ uint32_t wsum[4];
@@ -390,7 +395,7 @@ __global__ void k_ao_batch_setup(const BatchList bl, const lh_dev_scene_t sc, co
     const uint32_t slot = block_offsets[blockIdx.x] + woff + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
     slot_of_entry[k] = slot;
     slot_key[slot] = (key ? key[id] : (unsigned long long)id) & LH_SLOTKEY_MASK;
-    ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, (size_t)id, hitrec, slot_key, slot);
+    ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, (size_t)id, hitrec, slot_key, slot, EPS ? eps : 1.0e-6);
 }
 
 /* k_ao_resolve for a batch: one thread per list entry, the slot's occluded rays -> occluded_count[id] / radiance[id] (either may
@@ -431,6 +436,85 @@ __global__ void k_ao_batch_resolve(const BatchList bl, int N,
         const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
         if (tot) atomicAdd(occ_total + (blockIdx.x & 63u), (unsigned long long)tot);
     }
+}
+
+/* ---- the dirt stage (lh_dirt.h): the resolves read one double per gather ray -- the t of its bounded closest-hit record, at element
+ * slot * N + r -- and apply the rule in r order; whoever traced the rays wrote that array and nothing else ------------------------ */
+
+/* the bound of every gather ray of a materialised dirt stage: far_clip, where the bounded launch reads a bound per ray id */
+__global__ void k_dirt_bounds(size_t n, double far_clip, double *__restrict__ bound)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) bound[i] = far_clip;
+}
+
+/* a workgroup's bounded hits into one of the 64 counters, one atomic per workgroup (k_ao_resolve has the numbers) */
+__device__ __forceinline__ void dirt_total(unsigned int nh, unsigned long long *__restrict__ total)
+{
+    __shared__ unsigned int wsum[4];
+    for (int off = 32; off > 0; off >>= 1) nh += (unsigned int)__shfl_xor((int)nh, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nh;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (tot) atomicAdd(total + (blockIdx.x & 63u), (unsigned long long)tot);
+    }
+}
+
+/* k_ao_resolve for the dirt tile: a miss gives 0, a hit its value (ri_transport_dirtmap, dirtmap.c:234-292, without the texture) */
+__global__ void k_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
+                               const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
+                               float *__restrict__ rgb, unsigned long long *__restrict__ hit_total)
+{
+    LH_NC
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool inside = pix < (size_t)w * h;
+    const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
+    double accum = 0.0;
+    unsigned int nh = 0;
+    const int S = inside ? xs * ys : 0;
+    for (int s = 0; s < S; s++) {
+        const uint32_t slot = slot_of_sample[pix * S + s];
+        double val = 0.0;
+        if (slot != LH_MISS_PRIM) {
+            uint32_t c;
+            val = lh_dirt_value(tg + (size_t)slot * (size_t)N, N, near_clip, far_clip, &c);
+            nh += c;
+        }
+        accum = accum + val;
+    }
+    if (inside) {
+        const double val = accum * ((double)1.0 / (xs * ys));
+        float f = (float)val;
+        if (f < 0.0f) f = 0.0f;
+        float *o = rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx);
+        o[0] = f; o[1] = f; o[2] = f;
+    }
+    dirt_total(nh, hit_total);
+}
+
+/* k_ao_batch_resolve for the dirt stage: near_hits[id] / value[id] (either may be NULL); a traced miss gets LH_AO_NO_HIT / 0.
+ * slot_of_entry NULL: an empty scene, every traced ray is a miss */
+__global__ void k_dirt_batch_resolve(const BatchList bl, int N, double near_clip, double far_clip,
+                                     const uint32_t *__restrict__ slot_of_entry, const double *__restrict__ tg,
+                                     uint32_t *__restrict__ near_hits, float *__restrict__ value, unsigned long long *__restrict__ hit_total)
+{
+    LH_NC
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    unsigned int nh = 0;
+    if (batch_entry(bl, k, id)) {
+        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
+        uint32_t c = LH_AO_NO_HIT;
+        float val = 0.0f;
+        if (slot != LH_AO_NO_HIT) {
+            val = (float)lh_dirt_value(tg + (size_t)slot * (size_t)N, N, near_clip, far_clip, &c);
+            nh = c;
+        }
+        if (near_hits) near_hits[id] = c;
+        if (value) value[id] = val;
+    }
+    dirt_total(nh, hit_total);
 }
 
 
@@ -813,16 +897,16 @@ extern "C" int lh_render_launch_compact(const lh_dev_scene_t *sc, const double *
                                         uint32_t *d_slot_of_sample, double *d_hitrec,
                                         unsigned long long *d_slot_key, int x0, int w, int nbands, int band_rows,
                                         const int *d_band_y0, int y0, int spp, int full_width,
-                                        unsigned long long *d_total, void *stream)
+                                        unsigned long long *d_total, double eps, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) return 0;
     const unsigned nb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_hit_count, dim3(nb), dim3(256), 0, s, n, d_prim, d_block_counts);
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, nb, d_block_counts, d_total);
-    hipLaunchKernelGGL(k_ao_setup, dim3(nb), dim3(256), 0, s, n, *sc, d_nrm9, d_org, d_dir, d_prim, d_t, d_u, d_v,
+    hipLaunchKernelGGL(eps == 1.0e-6 ? k_ao_setup<false> : k_ao_setup<true>, dim3(nb), dim3(256), 0, s, n, *sc, d_nrm9, d_org, d_dir, d_prim, d_t, d_u, d_v,
                        d_block_counts, d_slot_of_sample, d_hitrec, d_slot_key,
-                       make_region(x0, w, nbands, band_rows, d_band_y0, y0, 0x7fffffff), spp, full_width);
+                       make_region(x0, w, nbands, band_rows, d_band_y0, y0, 0x7fffffff), spp, full_width, eps);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -868,7 +952,7 @@ extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const do
                                               const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
                                               const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
                                               double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
-                                              uint32_t *d_nslots32, void *stream)
+                                              uint32_t *d_nslots32, double eps, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     if (n_list == 0 || n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return n_list == 0 ? 0 : -1;
@@ -876,8 +960,8 @@ extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const do
     const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
     hipLaunchKernelGGL(k_ao_batch_count, dim3(nb), dim3(256), 0, s, bl, d_prim, d_block_counts);
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, nb, d_block_counts, d_total);
-    hipLaunchKernelGGL(k_ao_batch_setup, dim3(nb), dim3(256), 0, s, bl, *sc, d_nrm9, d_org, d_dir, d_prim, d_t, d_u, d_v, d_key,
-                       d_block_counts, d_total, d_slot_of_entry, d_hitrec, d_slot_key, d_nslots32);
+    hipLaunchKernelGGL(eps == 1.0e-6 ? k_ao_batch_setup<false> : k_ao_batch_setup<true>, dim3(nb), dim3(256), 0, s, bl, *sc, d_nrm9, d_org, d_dir, d_prim, d_t, d_u, d_v, d_key,
+                       d_block_counts, d_total, d_slot_of_entry, d_hitrec, d_slot_key, d_nslots32, eps);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -890,6 +974,38 @@ extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, cons
     const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
     hipLaunchKernelGGL(k_ao_batch_resolve, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        bl, N, d_slot_of_entry, d_occ, d_occ_count, d_occluded_count, d_radiance, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the dirt stage's launchers (kernels above): the bounds of a materialised stage, the two resolves */
+extern "C" int lh_render_launch_dirt_bounds(size_t n, double far_clip, double *d_bound, void *stream)
+{
+    if (n == 0) return 0;
+    if ((n + 255) / 256 > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_dirt_bounds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, far_clip, d_bound);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
+                                             const uint32_t *d_slot_of_sample, const double *d_t, float *d_rgb,
+                                             unsigned long long *d_hit_total, void *stream)
+{
+    const size_t total = (size_t)w * h;
+    if (total == 0) return 0;
+    hipLaunchKernelGGL(k_dirt_resolve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       w, h, band_rows, xs, ys, N, near_clip, far_clip, d_slot_of_sample, d_t, d_rgb, d_hit_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
+                                                   double near_clip, double far_clip, const uint32_t *d_slot_of_entry, const double *d_t,
+                                                   uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream)
+{
+    if (n_list == 0) return 0;
+    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
+    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
+    hipLaunchKernelGGL(k_dirt_batch_resolve, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       bl, N, near_clip, far_clip, d_slot_of_entry, d_t, d_near_hits, d_value, d_hit_total);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "lh_internal.h"
+#include "lh_dirt.h"
 
 #define ensure_buf lh_ensure_buf
 
@@ -81,10 +82,18 @@ static int stage_report(const stage_timer &tm, const void *d_clk, size_t nwaves,
  * caller's radiance kernel (from the per-slot counts, or from the any-hit bytes), which adds the occluded rays into the 64 counters at d_nocc.
  * cnt: the LH_CNT_DEV counters or NULL; tm: stage timing or NULL (events 3-5: count known, any-hit done, resolved); prefix: of the messages */
 struct ao_totals { unsigned long long nhit, nocc, cnt[LH_CNT_DEV]; bool fused; };      /* cnt: the words at `cnt`; fused: the stage ended fused (no AO ray in HBM) */
+/* dirt (or NULL: ambient occlusion, the code above as it always ran): the stage of the dirtmap transport (lh_dirt.h) -- the hit records were built with
+ * the dirt origin; what the stage leaves is the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), one double at
+ * element slot * N + r of dirt->ts->t, for the caller's resolve: fused and materialised differ only in who wrote it.  fused: the closest-hit kernel
+ * generates the ray in its refill and stores that word at its retire (lh_launch_trace_dirt).  Materialised: gather rays in HBM, ONE bounded
+ * closest-hit launch through the ray dumps' kernels with a bound array filled with far_clip.  nocc then totals the bounded hits */
+struct dirt_stage { lh_dirt_params_t p; lh_dirt_scratch *ts; };
+#define LH_DIRT_CHUNK ((size_t)1 << 30)          /* rays of one bounded launch at most (a list holds 2^30 entries) */
+#define LH_DIRT_LATE_MAX ((size_t)1 << 27)       /* gather rays (1 GiB of t) up to which a stage is sized for its worst case, the count left on the device */
 template <class Resolve>
 static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t nmax, ao_grid g, uint64_t seed, const void *d_uniforms,
                     const unsigned long long *d_nhit, unsigned long long *d_nocc, unsigned long long *cnt, const lh_launch_opt &opt,
-                    stage_timer *tm, bool fused, bool late, Resolve resolve, hipStream_t s, ao_totals *out)
+                    stage_timer *tm, bool fused, bool late, Resolve resolve, const dirt_stage *dirt, hipStream_t s, ao_totals *out)
 {
     const unsigned long long N = (unsigned long long)g.N;
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
@@ -113,7 +122,7 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
     };
     if (fused) {
         const size_t nslots = late ? nmax : (size_t)nhit;
-        if (ensure_buf(&b->occcount, nslots * sizeof(unsigned int))) return -1;
+        if (dirt ? ensure_buf(&dirt->ts->t, nslots * (size_t)N * 8) : ensure_buf(&b->occcount, nslots * sizeof(unsigned int))) return -1;
         qslot = lh_aoq_slot(a, s);
         if (qslot < 0) return -1;
         lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget, its clocks */
@@ -125,6 +134,12 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
         const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;
         if (!late && big && nhit * N >= (1ull << 27)) sc.ray_budget = big;
         budget = sc.ray_budget;
+        if (dirt) {
+            if (lh_launch_trace_dirt(&sc, nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                                     dirt->p.far_clip, (double *)dirt->ts->t.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
+                                     &a->aoq[qslot].q, a->ncus, late ? d_nhit : NULL, late ? big : 0u, (void *)s) != 0)
+                return fail("%sfused dirt launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
+        } else
         if (lh_launch_trace_ao(&sc, nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
                                (unsigned int *)b->occcount.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
                                &a->aoq[qslot].q, a->ncus, late ? d_nhit : NULL, late ? big : 0u, (void *)s) != 0)
@@ -138,13 +153,28 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
     auto materialised = [&]() -> int {
         const size_t nao = (size_t)(nhit * N);
         if (!nao) return 0;
-        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || ensure_buf(&b->occ, nao)) return -1;
+        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!dirt && ensure_buf(&b->occ, nao))) return -1;
         /* 4. AO rays */
         if (lh_render_launch_ao_rays((size_t)nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
                                      (const unsigned long long *)b->key.p, (double *)b->aorg.p, (double *)b->adir.p, s) != 0)
             return fail("%sAO ray kernel launch failed", prefix);
         /* 5. any-hit.  The abandoned fused pass is not counted (nor is what the caller counted before the stage) */
         if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+        if (dirt) {          /* 5. the dirt stage: closest hit under the bound far_clip, the records' t kept */
+            lh_dirt_scratch *ts = dirt->ts;
+            const size_t nb = nao < LH_DIRT_CHUNK ? nao : LH_DIRT_CHUNK;
+            if (ensure_buf(&ts->t, nao * 8) || ensure_buf(&ts->bound, nb * 8) || ensure_buf(&ts->prim, nb * 4) || ensure_buf(&ts->uv, nb * 16)) return -1;
+            if (lh_render_launch_dirt_bounds(nb, dirt->p.far_clip, (double *)ts->bound.p, s) != 0) return fail("%sbound kernel launch failed", prefix);
+            for (size_t off = 0; off < nao; off += LH_DIRT_CHUNK) {
+                const size_t m = nao - off < LH_DIRT_CHUNK ? nao - off : LH_DIRT_CHUNK;
+                lh_launch_opt o = opt;
+                o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = ts->bound.p;
+                const lh_batch_t rays = {m, LH_MODE_CLOSEST, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, ts->prim.p,
+                                         (double *)ts->t.p + off, ts->uv.p, (double *)ts->uv.p + m, NULL, cnt};
+                if (lh_launch(a, rays, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
+            }
+            return 0;
+        }
         return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, b->aorg.p, b->adir.p, NULL, NULL, NULL, NULL, b->occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
     };
     /* 6. radiance, and its occlusion totals on their way to the host */
@@ -173,10 +203,22 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
     return 0;
 }
 
-/* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands */
+/* NULL: the defaults (dirtmap.c:98,110-111); else the caller's, if lh_dirt.h accepts them */
+static int dirt_params(const char *what, const lh_dirt_params_t *params, lh_dirt_params_t *out)
+{
+    const lh_dirt_params_t def = LH_DIRT_DEFAULTS;
+    *out = params ? *params : def;
+    if (!lh_dirt_params_ok(out->near_clip, out->far_clip, out->eps))
+        return fail("%s: bad dirt parameters (near_clip %g, far_clip %g, eps %g: all finite, 0 <= near_clip < far_clip <= 1e38, eps >= 0)", what,
+                    out->near_clip, out->far_clip, out->eps);
+    return 0;
+}
+
+/* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands.  dirt (or NULL): the dirtmap
+ * transport's tile -- the same pipeline with the dirt origin, the dirt stage and its resolve, in scratch of its own */
 static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0, int y0,
                      uint64_t valid_pixels, int ps, int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb,
-                     lh_tile_stats_t *stats, void *stream)
+                     lh_tile_stats_t *stats, void *stream, const lh_dirt_params_t *dirt = NULL)
 {
     const int h = nbands * band_rows;              /* lines of the batch */
     HIPCHK(hipSetDevice(a->device));
@@ -187,10 +229,19 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         return fail("AO pipeline: more than 2^34 samples in the frame (slot keys carry 34 bits)");
     if (S >= ((size_t)1 << 31)) return fail("AO pipeline: more than 2^31 samples in one batch; render the frame in tiles");     /* 32-bit sample indices on the device */
     const unsigned nb = (unsigned)((S + 255) / 256);
-    lh_ao_scratch *b = &a->tile_ao;
-    if (ensure_buf(&a->r_org, S * 24) || ensure_buf(&a->r_dir, S * 24) || ensure_buf(&a->r_prim, S * 4) ||
-        ensure_buf(&a->r_t, S * 8) || ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8) ||
-        ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
+    lh_ao_scratch *b = dirt ? &a->tile_dirt : &a->tile_ao;
+    void *r_org, *r_dir, *r_prim, *r_t, *r_u, *r_v;          /* camera rays and their closest-hit records */
+    if (dirt) {          /* one block of its own (org | dir | t | u | v | prim): lh_render_scratch keeps showing the last AO tile */
+        if (ensure_buf(&a->d_rays, S * 76)) return -1;
+        double *base = (double *)a->d_rays.p;
+        r_org = base; r_dir = base + 3 * S; r_t = base + 6 * S; r_u = base + 7 * S; r_v = base + 8 * S; r_prim = base + 9 * S;
+    } else {
+        if (ensure_buf(&a->r_org, S * 24) || ensure_buf(&a->r_dir, S * 24) || ensure_buf(&a->r_prim, S * 4) ||
+            ensure_buf(&a->r_t, S * 8) || ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8)) return -1;
+        r_org = a->r_org.p; r_dir = a->r_dir.p; r_prim = a->r_prim.p; r_t = a->r_t.p; r_u = a->r_u.p; r_v = a->r_v.p;
+    }
+    if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
+    const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->tile_dirt_t};
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
@@ -207,15 +258,21 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     }
     /* 1. camera rays */
     if (lh_render_launch_primary_region(cam, x0, w, nbands, band_rows, d_band_y0, y0, cam->height, ps, ps,
-                                        (double *)a->r_org.p, (double *)a->r_dir.p, s) != 0)
+                                        (double *)r_org, (double *)r_dir, s) != 0)
         return fail("primary ray kernel launch failed");
     if (tm) HIPCHK(hipEventRecord(tm->ev[1], s));
     /* 2. closest hit */
-    if (lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, a->r_org.p, a->r_dir.p, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt},
+    if (lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, r_org, r_dir, r_prim, r_t, r_u, r_v, NULL, cnt},
                   LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
     if (tm) { HIPCHK(hipEventRecord(tm->ev[2], s)); opt.diag_clock += 3 * nwaves; }
     unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of k_ao_resolve's 64 counters */
     auto resolve = [&](bool from_counts) -> int {
+        if (dirt) {
+            if (lh_render_launch_dirt_resolve(w, h, band_rows, ps, ps, g.N, dirt->near_clip, dirt->far_clip, (const uint32_t *)b->slot.p,
+                                              (const double *)dstage.ts->t.p, (float *)d_rgb, a->d_total, s) != 0)
+                return fail("dirt resolve kernel launch failed");
+            return 0;
+        }
         if (lh_render_launch_resolve(w, h, band_rows, ps, ps, g.N, (const uint32_t *)b->slot.p, (const uint8_t *)b->occ.p,
                                      from_counts ? (const unsigned int *)b->occcount.p : NULL, (float *)d_rgb, a->d_total, s) != 0)
             return fail("resolve kernel launch failed");
@@ -225,17 +282,18 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     if (a->hs->bvh.ntris) {
         /* 3. compaction (deterministic: hits in sample order) */
         if (ensure_buf(&b->hitrec, S * 96) || ensure_buf(&b->key, S * 8)) return -1;   /* worst case: every sample hits */
-        if (lh_render_launch_compact(&a->dev, (const double *)a->d_nrm9, S, (const double *)a->r_org.p,
-                                     (const double *)a->r_dir.p, (const uint32_t *)a->r_prim.p, (const double *)a->r_t.p,
-                                     (const double *)a->r_u.p, (const double *)a->r_v.p, (uint32_t *)b->blocks.p,
+        if (lh_render_launch_compact(&a->dev, (const double *)a->d_nrm9, S, (const double *)r_org,
+                                     (const double *)r_dir, (const uint32_t *)r_prim, (const double *)r_t,
+                                     (const double *)r_u, (const double *)r_v, (uint32_t *)b->blocks.p,
                                      (uint32_t *)b->slot.p, (double *)b->hitrec.p, (unsigned long long *)b->key.p,
-                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, s) != 0)
+                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, dirt ? dirt->eps : 1.0e-6, s) != 0)
             return fail("compaction kernels failed: %s", hipGetErrorString(hipGetLastError()));
         HIPCHK(hipMemcpyAsync(d_nhit, a->d_total, sizeof(*d_nhit), hipMemcpyDeviceToDevice, s));
         /* 4-6.  Late: the persistent kernel's 32-bit ray index covers the worst case; the grouped order ("ao_group") needs the count on the host */
         const bool fused = a->ao_fused && !d_uniforms;
-        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && !a->dev.ao_group && !getenv("LH_AO_SYNC");
-        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, s, &tot) != 0) return -1;
+        /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; it has no grouped order) */
+        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && (dirt ? S * (size_t)g.N <= LH_DIRT_LATE_MAX : !a->dev.ao_group) && !getenv("LH_AO_SYNC");
+        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, dirt ? &dstage : NULL, s, &tot) != 0) return -1;
     } else {          /* an empty scene: every sample is a miss */
         HIPCHK(hipMemsetAsync(b->slot.p, 0xFF, S * 4, s));
         HIPCHK(hipMemsetAsync(d_nhit, 0, sizeof(*d_nhit), s));
@@ -247,7 +305,7 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     }
     const size_t nao = (size_t)tot.nhit * g.N;
     if (tm && stage_report(*tm, a->r_diag.p, nwaves, S, tot.nhit, nao) != 0) return -1;
-    a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao;
+    if (!dirt) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
     if (cnt) {
         lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
@@ -272,6 +330,20 @@ extern "C" int lh_render_ao_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, 
     if (!cam || !d_rgb) return fail("lh_render_ao_tile: NULL argument");
     if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_ao_tile: bad tile/sample counts");
     return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
+}
+
+/* ri_transport_dirtmap per camera sample (dirtmap.c:234-292, without the texture multiply): a miss gives 0, a hit its dirt value */
+extern "C" int lh_render_dirt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, int gather_nsamples,
+                                   const lh_dirt_params_t *params, uint64_t seed, const void *d_uniforms, void *d_rgb,
+                                   lh_tile_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);
+    lh_dirt_params_t p;
+    if (dirt_params("lh_render_dirt_tile", params, &p) != 0) return -1;
+    if (!a || !a->committed) return fail("lh_render_dirt_tile: accel not committed");
+    if (!cam || !d_rgb) return fail("lh_render_dirt_tile: NULL argument");
+    if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_dirt_tile: bad tile/sample counts");
+    return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream, &p);
 }
 
 /* nbands full-width bands of band_rows lines (band b = frame lines band_y0[b] ...; a band that runs past the frame is
@@ -346,13 +418,13 @@ static int ao_batch_args(const char *what, const lh_accel_t *a, size_t n_rays, b
     return 1;
 }
 
-extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
-                                  const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
-                                  const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
-                                  void *d_occluded_count, void *d_radiance, void *stream)
+/* lh_accel_ao_device, and with dirt (checked parameters) lh_accel_dirt_device: the same list, compaction and stage; the dirt call has the dirt
+ * origin, scratch of its own and its resolve (d_occluded_count / d_radiance are then near_hits / value) */
+static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                           const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+                           const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
+                           void *d_occluded_count, void *d_radiance, void *stream, const lh_dirt_params_t *dirt)
 {
-    lh_guard guard(a);
-    const char *what = "lh_accel_ao_device";
     const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, gather_nsamples, d_key, d_uniforms,
                                  d_index, n_index, d_count, d_occluded_count, d_radiance);
     if (go <= 0) return go;
@@ -363,12 +435,23 @@ extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_or
     hipStream_t s = (hipStream_t)stream;
     const ao_grid g = ao_sample_grid(gather_nsamples);
     const uint32_t *idx = (const uint32_t *)d_index, *cntp = (const uint32_t *)d_count;
-    lh_ao_scratch *b = &a->batch_ao;
-    if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65)) return -1;
-    unsigned long long *d_nhit = (unsigned long long *)a->b_tot.p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
+    lh_ao_scratch *b = dirt ? &a->batch_dirt : &a->batch_ao;
+    lh_buf *totals = dirt ? &a->d_tot : &a->b_tot;
+    if (ensure_buf(totals, sizeof(unsigned long long) * 65)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)totals->p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
+    const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->batch_dirt_t};
+    /* 6. per-ray occlusion (dirt: bounded hits and value), scattered to the rays' own slots; slot NULL: an empty scene */
+    auto resolve_with = [&](const uint32_t *slot, bool from_counts) -> int {
+        if (dirt)
+            return lh_render_launch_dirt_batch_resolve(L, n_rays, idx, cntp, g.N, dirt->near_clip, dirt->far_clip, slot, (const double *)dstage.ts->t.p,
+                                                       (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
+        return lh_render_launch_batch_resolve(L, n_rays, idx, cntp, g.N, slot, slot ? (const uint8_t *)b->occ.p : NULL,
+                                              from_counts ? (const unsigned int *)b->occcount.p : NULL, (uint32_t *)d_occluded_count,
+                                              (float *)d_radiance, d_nocc, s);
+    };
     if (a->hs->bvh.ntris == 0) {          /* an empty scene: every traced ray is a miss, no record array is read */
         HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
-        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, g.N, NULL, NULL, NULL, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s) != 0)
+        if (resolve_with(NULL, false) != 0)
             return fail("%s: resolve kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
@@ -382,23 +465,45 @@ extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_or
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, L, n_rays, idx, cntp, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
                                        (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)b->slot.p,
-                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, s) != 0)
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, dirt ? dirt->eps : 1.0e-6, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
     /* 4-6.  A fused stage always leaves the count on the device; the grouped order (set_param "ao_group") needs it on the host: materialised */
-    const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && !a->dev.ao_group;
-    /* 6. per-ray occlusion, scattered to the rays' own slots */
+    const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && (dirt || !a->dev.ao_group);
+    /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; beyond that the count is read first) */
+    const bool late = fused && (!dirt || L * (size_t)g.N <= LH_DIRT_LATE_MAX);
     auto resolve = [&](bool from_counts) -> int {
-        if (lh_render_launch_batch_resolve(L, n_rays, idx, cntp, g.N, (const uint32_t *)b->slot.p, (const uint8_t *)b->occ.p,
-                                           from_counts ? (const unsigned int *)b->occcount.p : NULL, (uint32_t *)d_occluded_count,
-                                           (float *)d_radiance, d_nocc, s) != 0)
-            return fail("%s: resolve kernel launch failed", what);
+        if (resolve_with((const uint32_t *)b->slot.p, from_counts) != 0) return fail("%s: resolve kernel launch failed", what);
         return 0;
     };
     ao_totals tot;
-    if (ao_stage(a, "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, fused, fused, resolve, s, &tot) != 0)
+    if (ao_stage(a, dirt ? "lh_accel_dirt_device: " : "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, fused,
+                 late, resolve, dirt ? &dstage : NULL, s, &tot) != 0)
         return -1;
     if (cnt) lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nocc, true);
+    if (cnt && dirt) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
     return 0;
+}
+
+extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                  const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+                                  const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
+                                  void *d_occluded_count, void *d_radiance, void *stream)
+{
+    lh_guard guard(a);
+    return ao_batch_device("lh_accel_ao_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
+                           d_count, d_occluded_count, d_radiance, stream, NULL);
+}
+
+extern "C" int lh_accel_dirt_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                    const void *d_u, const void *d_v, int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed,
+                                    const void *d_key, const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
+                                    void *d_near_hits, void *d_value, void *stream)
+{
+    lh_guard guard(a);
+    lh_dirt_params_t p;
+    if (dirt_params("lh_accel_dirt_device", params, &p) != 0) return -1;
+    return ao_batch_device("lh_accel_dirt_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
+                           d_count, d_near_hits, d_value, stream, &p);
 }
 
 extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
@@ -435,7 +540,7 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
                                        (const unsigned long long *)d_key, (uint32_t *)a->batch_ao.blocks.p, (uint32_t *)d_slot_of_ray,
-                                       (double *)a->batch_ao.hitrec.p, (unsigned long long *)a->batch_ao.key.p, d_nhit, (uint32_t *)d_nslots, s) != 0)
+                                       (double *)a->batch_ao.hitrec.p, (unsigned long long *)a->batch_ao.key.p, d_nhit, (uint32_t *)d_nslots, 1.0e-6, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
     if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, g.ntheta, g.nphi, seed, (const double *)a->batch_ao.hitrec.p, (const double *)d_uniforms,
                                          (const unsigned long long *)a->batch_ao.key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
@@ -443,12 +548,11 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
     return 0;
 }
 
-extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
-                                const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
-                                const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance)
+/* lh_accel_ao_host, and with dirt (checked parameters) lh_accel_dirt_host */
+static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                         const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
+                         const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance, const lh_dirt_params_t *dirt)
 {
-    lh_guard guard(a);
-    const char *what = "lh_accel_ao_host";
     const int go = ao_batch_args(what, a, n_rays, org && dir && prim && t && u && v, gather_nsamples, NULL, NULL, NULL, 0, NULL, NULL, NULL);
     if (go <= 0) return go;
     if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
@@ -470,12 +574,30 @@ extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org,
     HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
     if (key) HIPCHK(hipMemcpyAsync(d_key, key, b_d, hipMemcpyHostToDevice, s));
     if (need) HIPCHK(hipMemcpyAsync(d_uni, uniforms, need * sizeof(double), hipMemcpyHostToDevice, s));
-    if (lh_accel_ao_device(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, key ? d_key : NULL, need ? d_uni : NULL,
-                           NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s) != 0) return -1;
+    if (ao_batch_device(dirt ? "lh_accel_dirt_device" : "lh_accel_ao_device", a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
+                        key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s, dirt) != 0) return -1;
     if (occluded_count) HIPCHK(hipMemcpyAsync(occluded_count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * n, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
+}
+
+extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                                const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
+                                const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance)
+{
+    lh_guard guard(a);
+    return ao_batch_host("lh_accel_ao_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, occluded_count, radiance, NULL);
+}
+
+extern "C" int lh_accel_dirt_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                                  const double *u, const double *v, int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed,
+                                  const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *near_hits, float *value)
+{
+    lh_guard guard(a);
+    lh_dirt_params_t p;
+    if (dirt_params("lh_accel_dirt_host", params, &p) != 0) return -1;
+    return ao_batch_host("lh_accel_dirt_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, near_hits, value, &p);
 }
 
 extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t *count)
