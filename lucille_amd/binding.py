@@ -358,6 +358,18 @@ def _device_out(n, dev, mode, rf, out):
     return out, None, None, None, None, out[0]
 
 
+def _host_out(n, mode, rf):
+    """the output arrays of a host batch, allocated here, and their places in the C call: (what the method returns, prim, t, u, v, occ)"""
+    if mode == MODE_CLOSEST and rf == REC16:
+        rec = _rec16_host(n)
+        return rec, rec.ctypes.data, None, None, None, None
+    if mode == MODE_CLOSEST:
+        out = (np.empty(n, np.uint32), np.empty(n), np.empty(n), np.empty(n))
+        return (out,) + tuple(x.ctypes.data for x in out) + (None,)
+    occ = np.empty(n, np.uint8)
+    return occ, None, None, None, None, occ.ctypes.data
+
+
 _live = weakref.WeakSet()
 
 
@@ -576,27 +588,7 @@ class HipAccel:
         """lh_accel_intersect_host_tmax: intersect_host under a maximum distance per ray -- tmax: n bounds, taken in the rays' precision
         (float32 rays: float32 bounds).  A ray's answer is the unbounded record if that is a hit with t < tmax, else a miss.  What
         intersect_host(..., tmax=...) calls."""
-        rf = _records_format(records)
-        f32 = _is_f32(org) and _is_f32(dr)
-        dt = np.float32 if f32 else np.float64
-        o = _np(org, dt).reshape(-1, 3); d = _np(dr, dt).reshape(-1, 3); tm = _np(tmax, dt).reshape(-1)
-        n = o.shape[0]
-        if tm.shape[0] != n:
-            raise ValueError("intersect_host: tmax must hold one bound per ray (%d for %d rays)" % (tm.shape[0], n))
-        fmt = RAYS_F32 if f32 else RAYS_F64
-        call = lambda rec, t, u, v, occ: _check(self.L.lh_accel_intersect_host_tmax(
-            self.h, n, o.ctypes.data, d.ctypes.data, tm.ctypes.data, fmt, rf, rec, t, u, v, occ, mode), "lh_accel_intersect_host_tmax")
-        if mode == MODE_CLOSEST and rf == REC16:
-            rec = _rec16_host(n)
-            call(rec.ctypes.data, None, None, None, None)
-            return rec
-        if mode == MODE_CLOSEST:
-            prim = np.empty(n, np.uint32); t = np.empty(n); u = np.empty(n); v = np.empty(n)
-            call(prim.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data, None)
-            return prim, t, u, v
-        occ = np.empty(n, np.uint8)
-        call(None, None, None, None, occ.ctypes.data)
-        return occ
+        return self._intersect_host(org, dr, tmax, mode, records)
 
     def intersect_host(self, org, dr, mode=MODE_CLOSEST, records="f64", tmax=None):
         """org, dr: [n, 3] host rays.  float32 inputs (numpy arrays or CPU torch tensors, both float32) are sent as fp32 rays
@@ -604,42 +596,28 @@ class HipAccel:
         come back as one (n, 4) uint32 array of lh_rec16_t {prim, t, u, v as float32 bits}; else (prim, t, u, v) / occluded.
         tmax (an array of n bounds, taken in the rays' precision; None: unbounded, today's paths): a ray's answer is the unbounded
         record if that is a hit with t < tmax, else a miss (lh_accel_intersect_host_tmax)."""
+        return self._intersect_host(org, dr, tmax, mode, records)
+
+    def _intersect_host(self, org, dr, tmax, mode, records):
+        """intersect_host / intersect_host_tmax: plain fp64 batches go to lh_accel_intersect_host, fp32 rays or rec16 records to _ex, bounds to _tmax"""
         rf = _records_format(records)
         f32 = _is_f32(org) and _is_f32(dr)
-        if tmax is not None:
-            return self.intersect_host_tmax(org, dr, tmax, mode=mode, records=records)
-        if f32 or rf == REC16:
-            dt = np.float32 if f32 else np.float64
-            o = _np(org, dt).reshape(-1, 3); d = _np(dr, dt).reshape(-1, 3)
-            n = o.shape[0]
-            fmt = RAYS_F32 if f32 else RAYS_F64
-            if mode == MODE_CLOSEST and rf == REC16:
-                rec = _rec16_host(n)
-                _check(self.L.lh_accel_intersect_host_ex(self.h, n, o.ctypes.data, d.ctypes.data, fmt, rf, rec.ctypes.data,
-                                                         None, None, None, None, mode), "lh_accel_intersect_host_ex")
-                return rec
-            if mode == MODE_CLOSEST:
-                prim = np.empty(n, np.uint32); t = np.empty(n); u = np.empty(n); v = np.empty(n)
-                _check(self.L.lh_accel_intersect_host_ex(self.h, n, o.ctypes.data, d.ctypes.data, fmt, rf, prim.ctypes.data,
-                                                         t.ctypes.data, u.ctypes.data, v.ctypes.data, None, mode),
-                       "lh_accel_intersect_host_ex")
-                return prim, t, u, v
-            occ = np.empty(n, np.uint8)
-            _check(self.L.lh_accel_intersect_host_ex(self.h, n, o.ctypes.data, d.ctypes.data, fmt, rf, None, None, None, None,
-                                                     occ.ctypes.data, mode), "lh_accel_intersect_host_ex")
-            return occ
-        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3)
+        dt = np.float32 if f32 else np.float64
+        o = _np(org, dt).reshape(-1, 3); d = _np(dr, dt).reshape(-1, 3)
         n = o.shape[0]
-        if mode == MODE_CLOSEST:
-            prim = np.empty(n, np.uint32); t = np.empty(n); u = np.empty(n); v = np.empty(n)
-            _check(self.L.lh_accel_intersect_host(self.h, n, o.ctypes.data, d.ctypes.data, prim.ctypes.data,
-                                                  t.ctypes.data, u.ctypes.data, v.ctypes.data, None, mode),
-                   "lh_accel_intersect_host")
-            return prim, t, u, v
-        occ = np.empty(n, np.uint8)
-        _check(self.L.lh_accel_intersect_host(self.h, n, o.ctypes.data, d.ctypes.data, None, None, None, None,
-                                              occ.ctypes.data, mode), "lh_accel_intersect_host")
-        return occ
+        fmt = (RAYS_F32 if f32 else RAYS_F64, rf)
+        if tmax is not None:
+            tm = _np(tmax, dt).reshape(-1)
+            if tm.shape[0] != n:
+                raise ValueError("intersect_host: tmax must hold one bound per ray (%d for %d rays)" % (tm.shape[0], n))
+            name, head = "lh_accel_intersect_host_tmax", (tm.ctypes.data,) + fmt
+        elif f32 or rf == REC16:
+            name, head = "lh_accel_intersect_host_ex", fmt
+        else:
+            name, head = "lh_accel_intersect_host", ()
+        ret, prim, t, u, v, occ = _host_out(n, mode, rf)
+        _check(getattr(self.L, name)(self.h, n, o.ctypes.data, d.ctypes.data, *head, prim, t, u, v, occ, mode), name)
+        return ret
 
     def intersect_device_indexed(self, org, dr, out=None, mode=MODE_CLOSEST, stream=None, records="f64", index=None, count=None, tmax=None):
         """lh_accel_intersect_device_indexed: trace the rays of org / dr ([n, 3] device tensors, float64 or float32) that the list
@@ -651,28 +629,7 @@ class HipAccel:
         listed are then UNSPECIFIED (whatever the allocator handed over).  tmax: None, or a device tensor of the rays' dtype and
         shape [n] -- a bound per ray ID (not per list position): the listed rays' answers under lh_accel_intersect_device_tmax's
         contract.  Returns out."""
-        import torch
-        assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
-        assert org.is_contiguous() and dr.is_contiguous()
-        rf = _records_format(records)
-        n = org.shape[0]
-        dev = org.device
-        fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
-        out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
-        ip, ni, cp = _list_args(index, count, "intersect_device")
-        if index is None:
-            ni = n
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        if tmax is not None:
-            _check(self.L.lh_accel_intersect_device_tmax(self.h, n, _dptr(org), _dptr(dr), _dptr(_tmax_device(tmax, org, "intersect_device_indexed")),
-                                                         fmt, rf, _dptr(prim), _dptr(t), _dptr(u), _dptr(v), _dptr(occ), mode, ip, ni, cp,
-                                                         C.c_void_p(stream)), "lh_accel_intersect_device_tmax")
-            return out
-        _check(self.L.lh_accel_intersect_device_indexed(self.h, n, _dptr(org), _dptr(dr), fmt, rf, _dptr(prim), _dptr(t), _dptr(u),
-                                                        _dptr(v), _dptr(occ), mode, ip, ni, cp, C.c_void_p(stream)),
-               "lh_accel_intersect_device_indexed")
-        return out
+        return self._intersect_device("intersect_device_indexed", org, dr, out, mode, VARIANT_DEFAULT, stream, False, records, (index, count), tmax)
 
     def intersect_device(self, org, dr, out=None, mode=MODE_CLOSEST, variant=VARIANT_DEFAULT, stream=None,
                          counters=False, records="f64", index=None, count=None, tmax=None):
@@ -687,52 +644,50 @@ class HipAccel:
         tmax (a device tensor of the rays' dtype, shape [n]; None: unbounded, today's paths): a per-ray maximum distance -- a ray's
         answer is the unbounded record if that is a hit with t < tmax (strict; NaN, 0 and negatives: a miss; +inf: unbounded), else a
         miss (lh_accel_intersect_device_tmax; the default variant, without counters)."""
-        import torch
         if tmax is not None and (variant != VARIANT_DEFAULT or counters):
             raise ValueError("bounded batches (tmax) run the default variant without counters")
         if index is not None or count is not None:
             if variant != VARIANT_DEFAULT or counters:
                 raise ValueError("indexed batches run the default variant without counters")
             return self.intersect_device_indexed(org, dr, out=out, mode=mode, stream=stream, records=records, index=index, count=count, tmax=tmax)
+        return self._intersect_device("intersect_device", org, dr, out, mode, variant, stream, counters, records, None, tmax)
+
+    def _intersect_device(self, what, org, dr, out, mode, variant, stream, counters, records, lst, tmax):
+        """intersect_device / intersect_device_indexed behind their own refusals.  lst: None (a dense batch) or (index, count).  Bounds go to
+        lh_accel_intersect_device_tmax (a dense batch with the list (NULL, 0, NULL)), a list to _indexed, fp32 rays or rec16 records to _ex,
+        counters to _counted, the rest to lh_accel_intersect_device"""
+        import torch
         assert org.is_cuda and dr.is_cuda and org.dtype == dr.dtype and org.dtype in (torch.float64, torch.float32)
         assert org.is_contiguous() and dr.is_contiguous()
         rf = _records_format(records)
-        n = org.shape[0]
-        dev = org.device
-        if tmax is not None:
-            fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
-            out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(self.L.lh_accel_intersect_device_tmax(self.h, n, _dptr(org), _dptr(dr), _dptr(_tmax_device(tmax, org, "intersect_device")), fmt, rf,
-                                                         _dptr(prim), _dptr(t), _dptr(u), _dptr(v), _dptr(occ), mode, None, 0, None,
-                                                         C.c_void_p(stream)), "lh_accel_intersect_device_tmax")
-            return out
-        if org.dtype == torch.float32 or rf == REC16:
-            if variant != VARIANT_DEFAULT or counters:
-                raise ValueError("fp32 rays / rec16 records run the default variant without counters")
-            fmt = RAYS_F32 if org.dtype == torch.float32 else RAYS_F64
-            out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
-            if stream is None:
-                stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(self.L.lh_accel_intersect_device_ex(self.h, n, _dptr(org), _dptr(dr), fmt, rf, _dptr(prim), _dptr(t), _dptr(u),
-                                                       _dptr(v), _dptr(occ), mode, C.c_void_p(stream)),
-                   "lh_accel_intersect_device_ex")
-            return out
-        out, prim, t, u, v, occ = _device_out(n, dev, mode, REC_F64, out)
-        if counters:
+        n, dev, f32 = org.shape[0], org.device, org.dtype == torch.float32
+        ex = lst is None and tmax is None and (f32 or rf == REC16)
+        if ex and (variant != VARIANT_DEFAULT or counters):
+            raise ValueError("fp32 rays / rec16 records run the default variant without counters")
+        out, prim, t, u, v, occ = _device_out(n, dev, mode, rf, out)
+        rays = (self.h, n, _dptr(org), _dptr(dr))
+        recs = (_dptr(prim), _dptr(t), _dptr(u), _dptr(v), _dptr(occ), mode)
+        if counters:                  # a dense, unbounded fp64 batch: the others were refused
             torch.cuda.synchronize(dev)
             c = (C.c_uint64 * 4)()
-            _check(self.L.lh_accel_intersect_device_counted(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t),
-                                                            _dptr(u), _dptr(v), _dptr(occ), mode, variant, c),
-                   "lh_accel_intersect_device_counted")
+            _check(self.L.lh_accel_intersect_device_counted(*rays, *recs, variant, c), "lh_accel_intersect_device_counted")
             return out, {"nodes": int(c[0]), "tris": int(c[1]), "exact": int(c[2]), "rays": int(c[3]),
                          "retraced": int(self.L.lh_accel_last_retraced(self.h))}
+        ip, ni, cp = (None, 0, None) if lst is None else _list_args(lst[0], lst[1], "intersect_device")
+        if lst is not None and lst[0] is None:
+            ni = n
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self.L.lh_accel_intersect_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u),
-                                                _dptr(v), _dptr(occ), mode, variant, C.c_void_p(stream)),
-               "lh_accel_intersect_device")
+        fmt = (RAYS_F32 if f32 else RAYS_F64, rf)
+        if tmax is not None:
+            name, args = "lh_accel_intersect_device_tmax", rays + (_dptr(_tmax_device(tmax, org, what)),) + fmt + recs + (ip, ni, cp)
+        elif lst is not None:
+            name, args = "lh_accel_intersect_device_indexed", rays + fmt + recs + (ip, ni, cp)
+        elif ex:
+            name, args = "lh_accel_intersect_device_ex", rays + fmt + recs
+        else:
+            name, args = "lh_accel_intersect_device", rays + recs + (variant,)
+        _check(getattr(self.L, name)(*args, C.c_void_p(stream)), name)
         return out
 
     def trace_statistics(self, enable=True):

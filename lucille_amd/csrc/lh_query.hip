@@ -452,7 +452,70 @@ static int intersect_host_pipelined(lh_accel_t *a, size_t n, const void *org, co
     return 0;
 }
 
-/* the host batch in the formats io_fmt (LH_IO_*); the caller holds the accelerator's lock and has checked the arguments */
+/* the staging block of a host batch of m rays, as device pointers: org | dir | [tmax] | (16-byte aligned) t | u | v | prim | [diag] | occ.  16-byte
+ * records (rec16) start where t does -- fp64 rays without bounds: exactly behind the rays -- and t, u, v are NULL then */
+struct lh_staged { char *org, *dir, *tmax; double *t, *u, *v; uint32_t *prim, *diag; uint8_t *occ; };
+static int staged_block(lh_accel_t *a, size_t m, size_t el, bool rec16, bool bounded, bool diag, lh_staged *d)
+{
+    const size_t b_ray = el * 3 * m, b_out = (2 * b_ray + (bounded ? el * m : 0) + 15) & ~(size_t)15, b_diag = diag ? sizeof(uint32_t) * 4 * m : 0;
+    if (lh_ensure_stage(a, b_out + 3 * sizeof(double) * m + sizeof(uint32_t) * m + b_diag + m + 64) != 0) return -1;
+    char *base = (char *)a->d_stage;
+    d->org = base; d->dir = base + b_ray; d->tmax = bounded ? base + 2 * b_ray : NULL;
+    d->t = (double *)(base + b_out); d->u = d->t + m; d->v = d->u + m;
+    d->prim = (uint32_t *)(d->v + m); d->diag = diag ? d->prim + m : NULL;
+    d->occ = (uint8_t *)(d->prim + m) + b_diag;
+    if (rec16) { d->prim = (uint32_t *)d->t; d->t = d->u = d->v = NULL; }
+    return 0;
+}
+
+/* rays [off, off + m) of a host batch's arrays in the formats io_fmt (LH_IO_*): pageable copies through the staging block, one launch on the accelerator's
+ * stream, the records into those of the caller's arrays that are not NULL; returns when they are there.  tmax (or NULL): the batch's bounds -- the launch is
+ * then the identity list over the chunk's rays (per-ray bounds are read by indexed ray dumps), else a dense one.  diag (or NULL): four counts per ray from the
+ * sequential walk (lh_accel_intersect_diag_host).  The caller holds the accelerator's lock, has checked the arguments and set the device */
+static int host_chunk(lh_accel_t *a, size_t off, size_t m, const void *org, const void *dir, const void *tmax, uint32_t io_fmt,
+                      void *prim, double *t, double *u, double *v, uint8_t *occ, int mode, uint32_t *diag = NULL)
+{
+    const bool closest = mode == LH_MODE_CLOSEST, rec16 = closest && (io_fmt & LH_IO_REC16);
+    const size_t el = (io_fmt & LH_IO_RAYS_F32) ? sizeof(float) : sizeof(double), w = rec16 ? 4 : 1;          /* w: words per record's prim */
+    hipStream_t s = a->stream;
+    lh_staged d;
+    if (staged_block(a, m, el, rec16, tmax != NULL, diag != NULL, &d) != 0) return -1;
+    HIPCHK(hipMemcpyAsync(d.org, (const char *)org + el * 3 * off, el * 3 * m, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d.dir, (const char *)dir + el * 3 * off, el * 3 * m, hipMemcpyHostToDevice, s));
+    if (tmax) HIPCHK(hipMemcpyAsync(d.tmax, (const char *)tmax + el * off, el * m, hipMemcpyHostToDevice, s));
+    if (a->stat_on && counted_begin(a, s) != 0) return -1;
+    lh_launch_opt opt{io_fmt};
+    opt.diag_out = d.diag;
+    if (tmax) { opt.indexed = true; opt.idx_nrays = (uint32_t)m; opt.tmax = d.tmax; }
+    const int rc = lh_launch(a, lh_batch_t{m, mode, d.org, d.dir, d.prim, d.t, d.u, d.v, d.occ, a->stat_on ? a->d_counters : NULL},
+                             diag ? LH_VARIANT_SPEC : LH_VARIANT_DEFAULT, s, true, opt);
+    if (rc != 0) return rc;
+    if (a->stat_on) {
+        /* hits are counted from the device outputs whatever the caller asked to copy back */
+        std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV] = {0}, nh = 0;
+        if (closest) { hp.resize(w * m); HIPCHK(hipMemcpyAsync(hp.data(), d.prim, sizeof(uint32_t) * w * m, hipMemcpyDeviceToHost, s)); }
+        else { ho.resize(m); HIPCHK(hipMemcpyAsync(ho.data(), d.occ, m, hipMemcpyDeviceToHost, s)); }
+        if (diag) {          /* the totals alone: a diagnostic batch does not report retraced rays (counted_collect) */
+            HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(unsigned long long) * LH_CNT_N, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        } else if (counted_collect(a, s, h) != 0) return -1;          /* an empty scene's batch leaves them zero */
+        for (size_t i = 0; i < m; i++) nh += closest ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
+        lh_stat_add(a, h, m, nh);
+    }
+    if (diag) HIPCHK(hipMemcpyAsync(diag + 4 * off, d.diag, sizeof(uint32_t) * 4 * m, hipMemcpyDeviceToHost, s));
+    if (rec16) HIPCHK(hipMemcpyAsync((char *)prim + 16 * off, d.prim, 16 * m, hipMemcpyDeviceToHost, s));
+    else if (closest) {
+        if (prim) HIPCHK(hipMemcpyAsync((uint32_t *)prim + off, d.prim, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, s));
+        if (t) HIPCHK(hipMemcpyAsync(t + off, d.t, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        if (u) HIPCHK(hipMemcpyAsync(u + off, d.u, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        if (v) HIPCHK(hipMemcpyAsync(v + off, d.v, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    } else if (occ) HIPCHK(hipMemcpyAsync(occ + off, d.occ, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));          /* a next chunk reuses the staging block */
+    return 0;
+}
+
+/* the host batch in the formats io_fmt (LH_IO_*): pipelined from LH_PIPE_MIN rays on, else the plain path -- one chunk, one dense launch.  The caller holds
+ * the accelerator's lock and has checked the arguments */
 static int intersect_host_fmt(lh_accel_t *a, size_t n, const void *org, const void *dir,
                               uint32_t *prim, double *t, double *u, double *v, uint8_t *occ, int mode, uint32_t io_fmt)
 {
@@ -460,49 +523,7 @@ static int intersect_host_fmt(lh_accel_t *a, size_t n, const void *org, const vo
     static const size_t pipe_min = getenv("LH_PIPE_MIN") && atoll(getenv("LH_PIPE_MIN")) > 0 ? (size_t)atoll(getenv("LH_PIPE_MIN")) : LH_PIPE_MIN;
     if (n >= pipe_min && !a->stat_on && !getenv("LH_HOST_SIMPLE"))
         return intersect_host_pipelined(a, n, org, dir, prim, t, u, v, occ, mode, io_fmt);
-    /* layout of the staging block: org | dir | t | u | v | prim | occ; 16-byte records (io_fmt LH_IO_REC16) start where t does,
-     * rounded up to 16 bytes (fp64 rays: exactly there) */
-    const bool rec16 = mode == LH_MODE_CLOSEST && (io_fmt & LH_IO_REC16);
-    const size_t w = rec16 ? 4 : 1;                                           /* words per record's prim */
-    const size_t b_ray = ((io_fmt & LH_IO_RAYS_F32) ? sizeof(float) : sizeof(double)) * 3 * n, b_d = sizeof(double) * n;
-    const size_t b_out = (2 * b_ray + 15) & ~(size_t)15;
-    const size_t total = b_out + 3 * b_d + sizeof(uint32_t) * n + n + 64;
-    if (lh_ensure_stage(a, total) != 0) return -1;
-    char *base = (char *)a->d_stage;
-    char *d_org = base, *d_dir = base + b_ray;
-    double *d_t = (double *)(base + b_out), *d_u = d_t + n, *d_v = d_u + n;
-    uint32_t *d_prim = (uint32_t *)(d_v + n);
-    uint8_t *d_occ = (uint8_t *)(d_prim + n);
-    if (rec16) { d_prim = (uint32_t *)d_t; d_t = d_u = d_v = NULL; }
-    HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
-    if (a->stat_on && counted_begin(a, a->stream) != 0) return -1;
-    int rc = lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL},
-                       LH_VARIANT_DEFAULT, a->stream, true, lh_launch_opt{io_fmt});
-    if (rc != 0) return rc;
-    if (a->stat_on) {
-        /* hits are counted from the device outputs whatever the caller asked to copy back */
-        std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV], nh = 0;
-        if (mode == LH_MODE_CLOSEST) {
-            hp.resize(w * n); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * w * n, hipMemcpyDeviceToHost, a->stream));
-        } else {
-            ho.resize(n); HIPCHK(hipMemcpyAsync(ho.data(), d_occ, n, hipMemcpyDeviceToHost, a->stream));
-        }
-        if (counted_collect(a, a->stream, h) != 0) return -1;          /* an empty scene's batch leaves them zero */
-        for (size_t i = 0; i < n; i++) nh += (mode == LH_MODE_CLOSEST) ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
-        lh_stat_add(a, h, n, nh);
-    }
-    if (rec16) HIPCHK(hipMemcpyAsync(prim, d_prim, 16 * n, hipMemcpyDeviceToHost, a->stream));
-    else if (mode == LH_MODE_CLOSEST) {
-        if (prim) HIPCHK(hipMemcpyAsync(prim, d_prim, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, a->stream));
-        if (t) HIPCHK(hipMemcpyAsync(t, d_t, b_d, hipMemcpyDeviceToHost, a->stream));
-        if (u) HIPCHK(hipMemcpyAsync(u, d_u, b_d, hipMemcpyDeviceToHost, a->stream));
-        if (v) HIPCHK(hipMemcpyAsync(v, d_v, b_d, hipMemcpyDeviceToHost, a->stream));
-    } else {
-        if (occ) HIPCHK(hipMemcpyAsync(occ, d_occ, n, hipMemcpyDeviceToHost, a->stream));
-    }
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    return host_chunk(a, 0, n, org, dir, NULL, io_fmt, prim, t, u, v, occ, mode);
 }
 
 extern "C" int lh_accel_intersect_host(lh_accel_t *a, size_t n, const double *org, const double *dir,
@@ -531,15 +552,48 @@ static int ex_formats(const char *what, size_t n, int ray_format, int record_for
     return (int)((ray_format == LH_RAYS_F32 ? LH_IO_RAYS_F32 : 0u) | (record_format == LH_REC16 ? LH_IO_REC16 : 0u));
 }
 
+/* per-ray maximum distance (lucille_hip.h; the rule: lh_tmax.h): the checks of a bounded call that need no device, after ex_formats':
+ * -1 (lh_last_error) or 0 */
+static int tmax_args(const char *what, size_t n_rays, const void *tmax, int ray_format, bool device)
+{
+    if (device && n_rays > ((size_t)1 << 30)) return fail("%s: a bounded call holds 2^30 rays at most (%zu given)", what, n_rays);
+    const uintptr_t el = ray_format == LH_RAYS_F32 ? sizeof(float) : sizeof(double);
+    if (((uintptr_t)tmax & (el - 1u)) != 0) return fail("%s: tmax not aligned to its %zu-byte elements", what, (size_t)el);
+    return 0;
+}
+
+/* lh_accel_intersect_host_ex (tmax NULL) and the bounded lh_accel_intersect_host_tmax.  The bounded form is the plain path (host_chunk) in chunks of
+ * LH_TMAX_HOST_CHUNK rays, whatever n is -- the bounds do not travel through the pinned ring of the pipelined host path */
+#define LH_TMAX_HOST_CHUNK ((size_t)1 << 21)
+static int host_batch(lh_accel_t *a, const char *what, size_t n, const void *org, const void *dir, const void *tmax, int ray_format, int record_format,
+                      void *prim_or_rec16, double *t, double *u, double *v, uint8_t *occ, int mode)
+{
+    lh_guard guard(a);
+    const int io = ex_formats(what, n, ray_format, record_format, mode, prim_or_rec16, t, u, v);
+    if (io < 0) return -1;
+    if (tmax && tmax_args(what, n, tmax, ray_format, false) != 0) return -1;
+    const int go = batch_args(a, "intersect", n, org && dir, "ray arrays", mode);
+    if (go <= 0) return go;
+    if (!tmax) return intersect_host_fmt(a, n, org, dir, (uint32_t *)prim_or_rec16, t, u, v, occ, mode, (uint32_t)io);
+    HIPCHK(hipSetDevice(a->device));
+    for (size_t off = 0; off < n; off += LH_TMAX_HOST_CHUNK) {
+        const int rc = host_chunk(a, off, n - off < LH_TMAX_HOST_CHUNK ? n - off : LH_TMAX_HOST_CHUNK, org, dir, tmax, (uint32_t)io, prim_or_rec16, t, u, v, occ, mode);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 extern "C" int lh_accel_intersect_host_ex(lh_accel_t *a, size_t n, const void *org, const void *dir, int ray_format, int record_format,
                                           void *prim_or_rec16, double *t, double *u, double *v, uint8_t *occ, int mode)
 {
-    lh_guard guard(a);
-    const int io = ex_formats("lh_accel_intersect_host_ex", n, ray_format, record_format, mode, prim_or_rec16, t, u, v);
-    if (io < 0) return -1;
-    const int go = batch_args(a, "intersect", n, org && dir, "ray arrays", mode);
-    if (go <= 0) return go;
-    return intersect_host_fmt(a, n, org, dir, (uint32_t *)prim_or_rec16, t, u, v, occ, mode, (uint32_t)io);
+    return host_batch(a, "lh_accel_intersect_host_ex", n, org, dir, NULL, ray_format, record_format, prim_or_rec16, t, u, v, occ, mode);
+}
+
+extern "C" int lh_accel_intersect_host_tmax(lh_accel_t *a, size_t n, const void *org, const void *dir, const void *tmax, int ray_format, int record_format,
+                                            void *prim_or_rec16, double *t, double *u, double *v, uint8_t *occ, int mode)
+{
+    if (!tmax) return lh_accel_intersect_host_ex(a, n, org, dir, ray_format, record_format, prim_or_rec16, t, u, v, occ, mode);          /* no bounds: the unbounded entry point itself */
+    return host_batch(a, "lh_accel_intersect_host_tmax", n, org, dir, tmax, ray_format, record_format, prim_or_rec16, t, u, v, occ, mode);
 }
 
 extern "C" int lh_accel_intersect_device_ex(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, int ray_format, int record_format,
@@ -551,36 +605,6 @@ extern "C" int lh_accel_intersect_device_ex(lh_accel_t *a, size_t n, const void 
     return lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, NULL}, LH_VARIANT_DEFAULT, (hipStream_t)stream, true, lh_launch_opt{(uint32_t)io});
 }
 
-/* rays listed by ids: the records of the listed rays go to THEIR slots, every other slot stays as it is (lucille_hip.h) */
-extern "C" int lh_accel_intersect_device_indexed(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, int ray_format, int record_format,
-                                                 void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occ, int mode,
-                                                 const void *d_index, size_t n_index, const void *d_count, void *stream)
-{
-    lh_guard guard(a);
-    const char *what = "lh_accel_intersect_device_indexed";
-    const int io = ex_formats(what, (n_rays && n_index) ? n_rays : 0, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
-    if (io < 0) return -1;
-    if (n_index > ((size_t)1 << 30)) return fail("%s: a list holds 2^30 entries at most (%zu given)", what, n_index);
-    if (n_rays > 0xFFFFFFFFull) return fail("%s: ray ids are 32 bits wide: 2^32 - 1 rays at most (%zu given)", what, n_rays);
-    if ((((uintptr_t)d_index | (uintptr_t)d_count) & 3u) != 0) return fail("%s: the list and its count are 32-bit words: a pointer is not 4-byte aligned", what);
-    const int go = batch_args(a, "intersect", (n_index && n_rays) ? n_index : 0, d_org && d_dir, "ray arrays", mode);
-    if (go <= 0) return go;
-    lh_launch_opt opt;
-    opt.io_fmt = (uint32_t)io; opt.indexed = true; opt.index = (const uint32_t *)d_index; opt.idx_nrays = (uint32_t)n_rays;
-    opt.n_dev = (const uint32_t *)d_count;
-    hipStream_t s = (hipStream_t)stream;
-    const lh_batch_t b = {n_index, mode, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL};
-    /* statistics: the counting kernels, and one read-back -- how many rays the launch traced is known on the device alone */
-    if (a->stat_on) { HIPCHK(hipSetDevice(a->device)); if (counted_begin(a, s) != 0) return -1; }
-    if (lh_launch(a, b, LH_VARIANT_DEFAULT, s, true, opt) != 0) return -1;
-    if (!a->stat_on) return 0;
-    unsigned long long h[LH_CNT_DEV];
-    if (counted_collect(a, s, h) != 0) return -1;
-    lh_stat_add(a, h, h[LH_CNT_RAYS], 0);          /* hits are not counted: the records stay on the device */
-    return 0;
-}
-
-/* ---- per-ray maximum distance (lucille_hip.h; the rule: lh_tmax.h) ---- */
 /* hits among the listed records of a bounded launch, for the statistics: entry k < min(*count, n) -> slot index[k] (or k), ids beyond nrays skipped,
  * as the launch enumerated them (an id listed twice counts twice, as its ray does).  prim: the records' first words, `stride` words apart */
 __global__ void k_count_listed_hits(size_t n, const uint32_t *index, const uint32_t *count, uint32_t nrays, const uint32_t *prim, uint32_t stride,
@@ -597,32 +621,18 @@ __global__ void k_count_listed_hits(size_t n, const uint32_t *index, const uint3
     if (m != 0ull && (threadIdx.x & 63) == 0) atomicAdd(out, (unsigned long long)__popcll(m));
 }
 
-/* the checks of a bounded call that need no device, after ex_formats': -1 (lh_last_error) or 0 */
-static int tmax_args(const char *what, size_t n_rays, const void *tmax, int ray_format, bool device)
+/* rays listed by ids: the records of the listed rays go to THEIR slots, every other slot stays as it is (lucille_hip.h) -- lh_accel_intersect_device_indexed
+ * (d_tmax NULL) and the bounded lh_accel_intersect_device_tmax, whose dense call (no list, no count) is the identity list over its rays */
+static int listed_launch(lh_accel_t *a, const char *what, size_t n_rays, const void *d_org, const void *d_dir, const void *d_tmax, int ray_format, int record_format,
+                         void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occ, int mode, const void *d_index, size_t n_index, const void *d_count, void *stream)
 {
-    if (device && n_rays > ((size_t)1 << 30)) return fail("%s: a bounded call holds 2^30 rays at most (%zu given)", what, n_rays);
-    const uintptr_t el = ray_format == LH_RAYS_F32 ? sizeof(float) : sizeof(double);
-    if (((uintptr_t)tmax & (el - 1u)) != 0) return fail("%s: tmax not aligned to its %zu-byte elements", what, (size_t)el);
-    return 0;
-}
-
-extern "C" int lh_accel_intersect_device_tmax(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_tmax,
-                                              int ray_format, int record_format, void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v,
-                                              void *d_occ, int mode, const void *d_index, size_t n_index, const void *d_count, void *stream)
-{
-    const bool dense = d_index == NULL && n_index == 0 && d_count == NULL;
-    /* no bounds: the unbounded entry point itself */
-    if (!d_tmax)
-        return dense ? lh_accel_intersect_device_ex(a, n_rays, d_org, d_dir, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, stream)
-                     : lh_accel_intersect_device_indexed(a, n_rays, d_org, d_dir, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode,
-                                                         d_index, n_index, d_count, stream);
     lh_guard guard(a);
-    const char *what = "lh_accel_intersect_device_tmax";
-    const size_t n_list = dense ? n_rays : n_index;          /* a dense call is the identity list over its rays */
+    const size_t n_list = (d_tmax && d_index == NULL && n_index == 0 && d_count == NULL) ? n_rays : n_index;
     const int io = ex_formats(what, (n_rays && n_list) ? n_rays : 0, ray_format, record_format, mode, d_prim_or_rec16, d_t, d_u, d_v);
     if (io < 0) return -1;
     if (n_index > ((size_t)1 << 30)) return fail("%s: a list holds 2^30 entries at most (%zu given)", what, n_index);
-    if (tmax_args(what, n_rays, d_tmax, ray_format, true) != 0) return -1;
+    if (d_tmax) { if (tmax_args(what, n_rays, d_tmax, ray_format, true) != 0) return -1; }
+    else if (n_rays > 0xFFFFFFFFull) return fail("%s: ray ids are 32 bits wide: 2^32 - 1 rays at most (%zu given)", what, n_rays);
     if ((((uintptr_t)d_index | (uintptr_t)d_count) & 3u) != 0) return fail("%s: the list and its count are 32-bit words: a pointer is not 4-byte aligned", what);
     const int go = batch_args(a, "intersect", (n_list && n_rays) ? n_list : 0, d_org && d_dir, "ray arrays", mode);
     if (go <= 0) return go;
@@ -631,79 +641,47 @@ extern "C" int lh_accel_intersect_device_tmax(lh_accel_t *a, size_t n_rays, cons
     opt.n_dev = (const uint32_t *)d_count; opt.tmax = d_tmax;
     hipStream_t s = (hipStream_t)stream;
     const lh_batch_t b = {n_list, mode, d_org, d_dir, d_prim_or_rec16, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL};
+    /* statistics: the counting kernels, and one read-back -- how many rays the launch traced is known on the device alone */
     if (a->stat_on) { HIPCHK(hipSetDevice(a->device)); if (counted_begin(a, s) != 0) return -1; }
     if (lh_launch(a, b, LH_VARIANT_DEFAULT, s, true, opt) != 0) return -1;
     if (!a->stat_on) return 0;
-    /* statistics: as the indexed call counts, and the hits that are left after the bound, counted from the records on the device */
     unsigned long long h[LH_CNT_DEV], nh = 0;
     if (counted_collect(a, s, h) != 0) return -1;
-    const bool closest = mode == LH_MODE_CLOSEST;
-    HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_count_listed_hits, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, s, n_list, opt.index, opt.n_dev, opt.idx_nrays,
-                       closest ? (const uint32_t *)d_prim_or_rec16 : NULL, (io & LH_IO_REC16) ? 4u : 1u, closest ? NULL : (const uint8_t *)d_occ, a->d_counters);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&nh, a->d_counters, sizeof(nh), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    /* hits: an unbounded call's are not counted (the records stay on the device); a bounded call's are those that are left after the bound, counted from
+     * the records on the device */
+    if (d_tmax) {
+        const bool closest = mode == LH_MODE_CLOSEST;
+        HIPCHK(hipMemsetAsync(a->d_counters, 0, sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(k_count_listed_hits, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, s, n_list, opt.index, opt.n_dev, opt.idx_nrays,
+                           closest ? (const uint32_t *)d_prim_or_rec16 : NULL, (io & LH_IO_REC16) ? 4u : 1u, closest ? NULL : (const uint8_t *)d_occ, a->d_counters);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&nh, a->d_counters, sizeof(nh), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+    }
     lh_stat_add(a, h, h[LH_CNT_RAYS], nh);
     return 0;
 }
 
-/* the host form: the plain path (pageable copies through the staging block, one bounded launch) in chunks of LH_TMAX_HOST_CHUNK rays, whatever n is --
- * the bounds do not travel through the pinned ring of the pipelined host path */
-#define LH_TMAX_HOST_CHUNK ((size_t)1 << 21)
-extern "C" int lh_accel_intersect_host_tmax(lh_accel_t *a, size_t n, const void *org, const void *dir, const void *tmax, int ray_format, int record_format,
-                                            void *prim_or_rec16, double *t, double *u, double *v, uint8_t *occ, int mode)
+extern "C" int lh_accel_intersect_device_indexed(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, int ray_format, int record_format,
+                                                 void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v, void *d_occ, int mode,
+                                                 const void *d_index, size_t n_index, const void *d_count, void *stream)
 {
-    if (!tmax) return lh_accel_intersect_host_ex(a, n, org, dir, ray_format, record_format, prim_or_rec16, t, u, v, occ, mode);
-    lh_guard guard(a);
-    const char *what = "lh_accel_intersect_host_tmax";
-    const int io = ex_formats(what, n, ray_format, record_format, mode, prim_or_rec16, t, u, v);
-    if (io < 0) return -1;
-    if (tmax_args(what, n, tmax, ray_format, false) != 0) return -1;
-    const int go = batch_args(a, "intersect", n, org && dir, "ray arrays", mode);
-    if (go <= 0) return go;
-    HIPCHK(hipSetDevice(a->device));
-    const bool closest = mode == LH_MODE_CLOSEST, rec16 = closest && (io & LH_IO_REC16);
-    const size_t el = (io & LH_IO_RAYS_F32) ? sizeof(float) : sizeof(double), w = rec16 ? 4 : 1;
-    for (size_t off = 0; off < n; off += LH_TMAX_HOST_CHUNK) {
-        const size_t m = n - off < LH_TMAX_HOST_CHUNK ? n - off : LH_TMAX_HOST_CHUNK;
-        /* the staging block: org | dir | tmax | (16-byte aligned) t | u | v | prim | occ; 16-byte records start where t does */
-        const size_t b_ray = el * 3 * m, b_tm = el * m, b_d = sizeof(double) * m;
-        const size_t b_out = (2 * b_ray + b_tm + 15) & ~(size_t)15;
-        if (lh_ensure_stage(a, b_out + 3 * b_d + sizeof(uint32_t) * m + m + 64) != 0) return -1;
-        char *base = (char *)a->d_stage;
-        char *d_org = base, *d_dir = base + b_ray, *d_tm = base + 2 * b_ray;
-        double *d_t = (double *)(base + b_out), *d_u = d_t + m, *d_v = d_u + m;
-        uint32_t *d_prim = (uint32_t *)(d_v + m);
-        uint8_t *d_occ = (uint8_t *)(d_prim + m);
-        if (rec16) { d_prim = (uint32_t *)d_t; d_t = d_u = d_v = NULL; }
-        HIPCHK(hipMemcpyAsync(d_org, (const char *)org + el * 3 * off, b_ray, hipMemcpyHostToDevice, a->stream));
-        HIPCHK(hipMemcpyAsync(d_dir, (const char *)dir + el * 3 * off, b_ray, hipMemcpyHostToDevice, a->stream));
-        HIPCHK(hipMemcpyAsync(d_tm, (const char *)tmax + el * off, b_tm, hipMemcpyHostToDevice, a->stream));
-        if (a->stat_on && counted_begin(a, a->stream) != 0) return -1;
-        lh_launch_opt opt;
-        opt.io_fmt = (uint32_t)io; opt.indexed = true; opt.idx_nrays = (uint32_t)m; opt.tmax = d_tm;
-        const int rc = lh_launch(a, lh_batch_t{m, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, a->stat_on ? a->d_counters : NULL},
-                                 LH_VARIANT_DEFAULT, a->stream, true, opt);
-        if (rc != 0) return rc;
-        if (a->stat_on) {
-            std::vector<uint32_t> hp; std::vector<uint8_t> ho; unsigned long long h[LH_CNT_DEV], nh = 0;
-            if (closest) { hp.resize(w * m); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * w * m, hipMemcpyDeviceToHost, a->stream)); }
-            else { ho.resize(m); HIPCHK(hipMemcpyAsync(ho.data(), d_occ, m, hipMemcpyDeviceToHost, a->stream)); }
-            if (counted_collect(a, a->stream, h) != 0) return -1;
-            for (size_t i = 0; i < m; i++) nh += closest ? (hp[w * i] != LH_MISS_PRIM) : (ho[i] != 0);
-            lh_stat_add(a, h, m, nh);
-        }
-        if (rec16) HIPCHK(hipMemcpyAsync((char *)prim_or_rec16 + 16 * off, d_prim, 16 * m, hipMemcpyDeviceToHost, a->stream));
-        else if (closest) {
-            if (prim_or_rec16) HIPCHK(hipMemcpyAsync((uint32_t *)prim_or_rec16 + off, d_prim, sizeof(uint32_t) * m, hipMemcpyDeviceToHost, a->stream));
-            if (t) HIPCHK(hipMemcpyAsync(t + off, d_t, b_d, hipMemcpyDeviceToHost, a->stream));
-            if (u) HIPCHK(hipMemcpyAsync(u + off, d_u, b_d, hipMemcpyDeviceToHost, a->stream));
-            if (v) HIPCHK(hipMemcpyAsync(v + off, d_v, b_d, hipMemcpyDeviceToHost, a->stream));
-        } else if (occ) HIPCHK(hipMemcpyAsync(occ + off, d_occ, m, hipMemcpyDeviceToHost, a->stream));
-        HIPCHK(hipStreamSynchronize(a->stream));          /* the next chunk reuses the staging block */
-    }
-    return 0;
+    return listed_launch(a, "lh_accel_intersect_device_indexed", n_rays, d_org, d_dir, NULL, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode,
+                         d_index, n_index, d_count, stream);
+}
+
+extern "C" int lh_accel_intersect_device_tmax(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_tmax,
+                                              int ray_format, int record_format, void *d_prim_or_rec16, void *d_t, void *d_u, void *d_v,
+                                              void *d_occ, int mode, const void *d_index, size_t n_index, const void *d_count, void *stream)
+{
+    /* no bounds: the unbounded entry point itself */
+    if (!d_tmax)
+        return d_index == NULL && n_index == 0 && d_count == NULL
+                   ? lh_accel_intersect_device_ex(a, n_rays, d_org, d_dir, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode, stream)
+                   : lh_accel_intersect_device_indexed(a, n_rays, d_org, d_dir, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode,
+                                                       d_index, n_index, d_count, stream);
+    return listed_launch(a, "lh_accel_intersect_device_tmax", n_rays, d_org, d_dir, d_tmax, ray_format, record_format, d_prim_or_rec16, d_t, d_u, d_v, d_occ, mode,
+                         d_index, n_index, d_count, stream);
 }
 
 extern "C" int lh_accel_trace_statistics(lh_accel_t *a, int enable)
@@ -958,35 +936,7 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
         for (size_t i = 0; i < n; i++) { if (prim) prim[i] = LH_MISS_PRIM; if (t) t[i] = LH_T_INF; if (u) u[i] = 0.0; if (v) v[i] = 0.0; }
         return 0;
     }
-    const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t total = 2 * b_ray + 3 * b_d + sizeof(uint32_t) * n + sizeof(uint32_t) * 4 * n + 64;
-    if (lh_ensure_stage(a, total) != 0) return -1;
-    char *base = (char *)a->d_stage;
-    double *d_org = (double *)base, *d_dir = (double *)(base + b_ray);
-    double *d_t = (double *)(base + 2 * b_ray), *d_u = d_t + n, *d_v = d_u + n;
-    uint32_t *d_prim = (uint32_t *)(d_v + n), *d_diag = d_prim + n;
-    HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
-    if (a->stat_on && counted_begin(a, a->stream) != 0) return -1;
-    lh_launch_opt opt; opt.diag_out = d_diag;
-    const int rc = lh_launch(a, lh_batch_t{n, LH_MODE_CLOSEST, d_org, d_dir, d_prim, d_t, d_u, d_v, NULL, a->stat_on ? a->d_counters : NULL}, LH_VARIANT_SPEC, a->stream, true, opt);
-    if (rc != 0) return rc;
-    HIPCHK(hipMemcpyAsync(diag, d_diag, sizeof(uint32_t) * 4 * n, hipMemcpyDeviceToHost, a->stream));
-    std::vector<uint32_t> hp;
-    if (a->stat_on || prim) { hp.resize(n); HIPCHK(hipMemcpyAsync(hp.data(), d_prim, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, a->stream)); }
-    if (t) HIPCHK(hipMemcpyAsync(t, d_t, b_d, hipMemcpyDeviceToHost, a->stream));
-    if (u) HIPCHK(hipMemcpyAsync(u, d_u, b_d, hipMemcpyDeviceToHost, a->stream));
-    if (v) HIPCHK(hipMemcpyAsync(v, d_v, b_d, hipMemcpyDeviceToHost, a->stream));
-    unsigned long long h[LH_CNT_N] = {0, 0, 0, 0};          /* the totals alone, read with the records: a diagnostic batch does not report retraced rays (counted_collect) */
-    if (a->stat_on) HIPCHK(hipMemcpyAsync(h, a->d_counters, sizeof(h), hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    if (prim) memcpy(prim, hp.data(), sizeof(uint32_t) * n);
-    if (a->stat_on) {
-        unsigned long long nh = 0;
-        for (size_t i = 0; i < n; i++) nh += hp[i] != LH_MISS_PRIM;
-        lh_stat_add(a, h, n, nh);
-    }
-    return 0;
+    return host_chunk(a, 0, n, org, dir, NULL, 0u, prim, t, u, v, NULL, LH_MODE_CLOSEST, diag);
 }
 
 /* the same for rays resident on the device, closest- or any-hit: d_diag n x 4 u32 (see lh_accel_intersect_diag_host); the hit

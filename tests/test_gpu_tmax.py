@@ -411,6 +411,20 @@ def test_host_form():
     assert acc.L.lh_accel_intersect_host_tmax(acc.h, 8, o8.ctypes.data, d8.ctypes.data, None, binding.RAYS_F64, binding.REC_F64, prim.ctypes.data,
                                               t.ctypes.data, u.ctypes.data, v.ctypes.data, None, la.MODE_CLOSEST) == 0
     assert_hits_equal((prim, t, u, v), tuple(x[:8] for x in c["exp"]), "host, NULL bound")
+    # statistics on: the bounded host form counts its rays and the hits that are left after the bound, the unbounded one the oracle's hits
+    n = c["org"].shape[0]
+    acc.trace_statistics(True); acc.statistics(clear=True)
+    for mode in (la.MODE_CLOSEST, la.MODE_ANY):
+        host(acc, c["org"], c["dr"], tmax, binding.RAYS_F64, binding.REC_F64, mode)
+        s = acc.statistics(clear=True)
+        assert s["rays"] == n and s["hits"] == int(occ.sum()) and s["nodes"] > 0, (mode, s, int(occ.sum()))
+    rec = binding._rec16_host(n)
+    assert acc.L.lh_accel_intersect_host_ex(acc.h, n, c["org"].ctypes.data, c["dr"].ctypes.data, binding.RAYS_F64, binding.REC16, rec.ctypes.data,
+                                            None, None, None, None, la.MODE_CLOSEST) == 0, acc.L.lh_last_error()
+    s = acc.statistics(clear=True)
+    acc.trace_statistics(False)
+    assert s["rays"] == n and s["hits"] == tc.SCENES["soup20k"][2] == 13568 and s["nodes"] > 0, s
+    assert_rec16(rec, pack16(c["exp"]), "host_ex, counted, rec16")
     acc.close()
 
 
@@ -429,6 +443,11 @@ def test_host_form_two_chunks(monkeypatch):
     assert (exp[0] != po.MISS).sum() > 10000
     assert_rec16(host(acc, o32, d32, t32, binding.RAYS_F32, binding.REC16), pack16(exp), "two chunks, fp32 rays, rec16")
     assert_occ(host(acc, o32, d32, t32, binding.RAYS_F32, binding.REC_F64, la.MODE_ANY), occ, "two chunks, any hit")
+    acc.trace_statistics(True); acc.statistics(clear=True)          # statistics add up over the chunks
+    assert_occ(host(acc, o32, d32, t32, binding.RAYS_F32, binding.REC_F64, la.MODE_ANY), occ, "two chunks, any hit, counted")
+    s = acc.statistics(clear=True)
+    acc.trace_statistics(False)
+    assert s["rays"] == n and s["hits"] == int(occ.sum()), (s, n, int(occ.sum()))
     acc.close()
 
 
