@@ -309,6 +309,17 @@ uint64_t lh_accel_last_retraced(const lh_accel_t *accel);
  * 16-bit-grid node), or 128 (8-wide, one cache line) when the scene's hot set does not fit the 256 MiB Infinity Cache --
  * there every record fetched costs a 128-byte line of HBM traffic.  lh_accel_set_param("wide8", -1 auto / 0 / 1). */
 int lh_accel_dump_node_bytes(const lh_accel_t *accel);
+/* Large plain ray dumps (lh_accel_intersect_device / _device_counted: fp64 rays on 16-byte boundaries, fp64 records or any-hit bytes, the default
+ * walk) are traced from a copy in bin order -- the Morton code of the origin's cell on the scene's bounds -- and their
+ * records copied back to the caller's slots: incoherent rays then meet each XCD's L2 one region of the scene at a time.  Records do not change.
+ * The copy lives in a workspace per stream (82 bytes a ray: 8.2 GB for 100 M rays; sized by the largest dump the stream has seen, never shrunk, freed with
+ * the accelerator; up to four streams keep one each; growing it waits for the device; "dump_order_max_mb" caps it); a dump whose workspace cannot be had
+ * is traced as given.  lh_accel_set_param: "dump_order" 1 (default) / 0 -- a caller whose dumps are coherent already (camera rays in pixel order, rays
+ * sorted upstream) switches it off: the passes cost what an incoherent dump wins; "dump_order_min": rays of the smallest dump that is ordered;
+ * "dump_order_bits": the key, 64 bins either way -- 2 (default): the cell at two bits per axis, 1: one bit per axis under the direction octant; "dump_order_max_mb": 0 (no cap) or the largest workspace in MiB.  LH_DUMP_ORDER=0: off.
+ * fp32 rays, 16-byte records, indexed and bounded dumps, host batches' chunks below "dump_order_min" and the tile pipelines are traced as given.
+ * out[0]: dumps traced in bin order so far (a dump of more than 2^30 rays counts once per part), out[1]: their rays */
+int lh_accel_order_statistics(lh_accel_t *accel, uint64_t out[2], int clear);
 
 /* ---- traversal statistics: ri_bvh_clear_stat_traversal / ri_bvh_report_stat_traversal ----
  * reference: src/render/bvh.c:669-706 (globals filled under -DRI_BVH_TRACE_STATISTICS,

@@ -118,7 +118,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 ABI_SYMBOLS = [
     "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
-    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_intersect_device_tmax", "lh_accel_intersect_host_tmax", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes",
+    "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_intersect_device_tmax", "lh_accel_intersect_host_tmax", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes", "lh_accel_order_statistics",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
     "lh_render_ao_tile", "lh_render_ao_tile_host", "lh_render_ao_bands", "lh_render_scratch", "lh_accel_beam_visibility_host", "lh_accel_beam_visibility_device", "lh_accel_beam_visibility_set_host", "lh_accel_beam_raster_host", "lh_accel_beam_raster_device", "lh_accel_beam_raster_set_host", "lh_render_pt_tile",
     "lh_accel_trace_statistics", "lh_accel_statistics", "lh_accel_slot_statistics",
@@ -177,6 +177,8 @@ def lib():
     L.lh_accel_intersect_host_tmax.argtypes = [vp, sz, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32]
     L.lh_accel_last_retraced.argtypes = [vp]; L.lh_accel_last_retraced.restype = C.c_uint64
     L.lh_accel_dump_node_bytes.argtypes = [vp]
+    if hasattr(L, "lh_accel_order_statistics"):          # an older library under LH_LIBRARY (A/B runs in tools/) has no ordered dumps
+        L.lh_accel_order_statistics.argtypes = [vp, C.POINTER(C.c_uint64), i32]
     L.lh_accel_intersect_device_counted.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp, i32, i32,
                                                     C.POINTER(C.c_uint64)]
     L.lh_accel_set_grid.argtypes = [vp, i32]
@@ -704,6 +706,12 @@ class HipAccel:
         c = (C.c_uint64 * 3)()
         _check(self.L.lh_accel_slot_statistics(self.h, c, 1 if clear else 0), "lh_accel_slot_statistics")
         return dict(zip(("node_slots", "tri_slots", "regroups"), (int(x) for x in c)))
+
+    def order_statistics(self, clear=False):
+        """ray dumps traced from a copy in bin order so far ("dump_order"), and their rays"""
+        c = (C.c_uint64 * 2)()
+        _check(self.L.lh_accel_order_statistics(self.h, c, 1 if clear else 0), "lh_accel_order_statistics")
+        return {"dumps": int(c[0]), "rays": int(c[1])}
 
     def dump_node_bytes(self):
         """64: ray dumps walk the 4-wide nodes; 128: the 8-wide nodes (scene larger than the Infinity Cache, or wide8 = 1)"""

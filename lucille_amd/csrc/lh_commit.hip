@@ -77,6 +77,10 @@ extern "C" int lh_accel_create(lh_accel_t **out, int device)
     if (env && atoi(env) > 0) a->dump_budget = (uint32_t)atoi(env);
     env = getenv("LH_RAY_BUDGET");
     if (env && atoi(env) > 0) a->dev.ray_budget = (uint32_t)atoi(env);
+    /* ray dumps in bin order (lh_order.h): on from LH_DUMP_ORDER_MIN rays, LH_DUMP_ORDER_BITS cell bits per axis under the octant, no cap on the workspace */
+    a->dump_order = 1; a->dump_order_min = LH_DUMP_ORDER_MIN; a->dump_order_bits = LH_DUMP_ORDER_BITS; a->dump_order_max_mb = 0;
+    env = getenv("LH_DUMP_ORDER");
+    if (env) a->dump_order = atoi(env) != 0;
     a->dev.top_nodes = LH_TOP_AUTO;
     a->dev.deg_dcap = INFINITY; a->dev.cap_srcs = 0u; a->dev.ndanger = LH_DANGER_ALL;
     a->dev.coop_patience = 0;
@@ -540,6 +544,7 @@ static void release_device(lh_accel_t *a)
             (void)hipStreamDestroy((hipStream_t)q->aux_stream); (void)hipEventDestroy((hipEvent_t)q->ev_ready); (void)hipEventDestroy((hipEvent_t)q->ev_done);
         }
         memset(q, 0, sizeof(*q)); a->aoq[k].used = 0;
+        free_buf(&a->aoq[k].order_ws);
     }
     if (a->pipe.ready) {
         for (int b = 0; b < a->pipe.depth; b++) {
@@ -1263,7 +1268,9 @@ extern "C" int lh_accel_set_grid(lh_accel_t *a, int blocks)
 /* tuning knobs of the traversal kernel (sweeps, tools/): "grid" persistent workgroups, "min_active" regroup threshold,
  * "tri_batch" parked leaves per triangle pass, "ray_chunk" rays per cursor atomic, "variant" default kernel variant,
  * "ao_fused", "wide8" (-1 auto / 0 / 1), "stack_cap" (tests of the overflow path),
- * "coop_patience" (10 ns ticks the pass beside a launch waits for progress; 0: half a second) */
+ * "coop_patience" (10 ns ticks the pass beside a launch waits for progress; 0: half a second),
+ * "dump_order" (1 / 0: large ray dumps are traced from a copy in bin order, lh_order.h), "dump_order_min" (rays of the smallest dump that is),
+ * "dump_order_bits" (the key, 64 bins either way: 2 = the origin's cell at two bits per axis, 1 = one bit per axis under the direction octant), "dump_order_max_mb" (0: no cap; else a dump whose workspace would be larger is traced as given) */
 extern "C" int lh_accel_set_param(lh_accel_t *a, const char *name, int value)
 {
     lh_guard guard(a);
@@ -1284,6 +1291,10 @@ extern "C" int lh_accel_set_param(lh_accel_t *a, const char *name, int value)
     else if (!strcmp(name, "fast_start")) a->fast_start = value != 0;
     else if (!strcmp(name, "wide8") && value >= -1 && value <= 1) a->wide8 = value;
     else if (!strcmp(name, "top_nodes") && value >= -1 && value <= (int)LH_TOP_NODES_MAX) a->dev.top_nodes = value < 0 ? LH_TOP_AUTO : (uint32_t)value;
+    else if (!strcmp(name, "dump_order")) a->dump_order = value != 0;
+    else if (!strcmp(name, "dump_order_min") && value > 0) a->dump_order_min = (size_t)value;
+    else if (!strcmp(name, "dump_order_bits") && (value == 1 || value == 2)) a->dump_order_bits = (uint32_t)value;
+    else if (!strcmp(name, "dump_order_max_mb") && value >= 0) a->dump_order_max_mb = (size_t)value;
     else if (!strcmp(name, "stack_cap") && (value == 0 || (value >= 8 && value <= 64 && value % 2 == 0))) a->dev.stack_cap = (uint32_t)value;
     else return fail("lh_accel_set_param: unknown parameter or bad value: %s = %d", name, value);
     return 0;

@@ -25,6 +25,7 @@
 #include "lh_bvh.h"
 #include "lh_refbvh.h"
 #include "lh_device.h"
+#include "lh_order.h"
 
 /* lh_last_error() of the calling thread; lh_fail formats it and returns -1 */
 int lh_fail(const char *fmt, ...);
@@ -120,7 +121,7 @@ struct lh_accel {
     int knobs_user;                    /* min_active / tri_batch were set by the caller (set_param, LH_MIN_ACTIVE, LH_TRI_BATCH): ray dumps do not pick their own */
     int default_variant;
     /* per-stream fix-up queues of the persistent launches (rays out of visit budget / stack rows, fragile AO hits) */
-    struct { hipStream_t stream; int used; lh_fixq_t q; } aoq[LH_AOQ_SLOTS];
+    struct { hipStream_t stream; int used; lh_fixq_t q; lh_buf order_ws; } aoq[LH_AOQ_SLOTS];      /* order_ws: the stream's workspace for dumps traced in bin order (lh_order.h) */
     /* staging for host batches */
     void *d_stage; size_t stage_bytes;
     /* pipelined host batches: a ring of pinned in/out staging blocks and their device twins; rays up on s[0]; trace + records down alternate between s[1] and s[2] */
@@ -153,6 +154,10 @@ struct lh_accel {
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */
     int ao_budget_user;                /* set by the caller (set_param / LH_AO_BUDGET / "ray_budget"): taken as it is, whatever the launch's size */
     uint32_t dump_budget;              /* visit budget of ray-dump launches (the tile pipelines': dev.ray_budget) */
+    /* ray dumps traced from a copy in bin order (lh_order.h, lh_query.hip lh_launch): "dump_order" 1 / 0; "dump_order_min": the smallest dump that is ordered;
+     * "dump_order_bits": cell bits per axis of the key (2: the cell alone, 1: under the direction octant); "dump_order_max_mb": 0, or the largest workspace a stream may hold -- a dump that needs more is traced as given */
+    int dump_order; size_t dump_order_min; uint32_t dump_order_bits; size_t dump_order_max_mb;
+    unsigned long long order_stat[2];  /* dumps (parts of 2^30 rays at most) traced in bin order, and their rays (lh_accel_order_statistics) */
     int build_auto;                    /* the commit chose the builders by the size of the scene: a failing device build falls back to the host */
     int poison_outputs;                /* LH_POISON_OUTPUTS=1 (tests, tools/fuzz_*): a ray dump's output arrays are filled with 0x77 before the launch -- an answer slot that nobody
                                           writes shows up as a wrong record instead of as whatever the buffer held (the lost any-hit rays of r05 hid behind recycled buffers) */
@@ -251,6 +256,9 @@ static inline unsigned long long *lh_next_cursor(lh_accel_t *a)
     return (unsigned long long *)((uint32_t *)a->d_cursor + (size_t)LH_CURSOR_WORDS * (a->cursor_next++ % LH_NCURSOR));
 }
 int  lh_aoq_slot(lh_accel_t *a, hipStream_t s);
+/* lh_order.hip: a dump's rays into bin order (passes 1 and 2), its records back into the caller's order (pass 3); the walk between them is the caller's */
+int  lh_order_run(const lh_order_plan_t *p, const lh_order_grid_t *g, const void *d_org, const void *d_dir, void *d_ws, hipStream_t stream);
+int  lh_order_back(const lh_order_plan_t *p, int closest, const void *d_ws, void *d_prim, void *d_t, void *d_u, void *d_v, void *d_occ, hipStream_t stream);
 /* a counted launch's words h (LH_CNT_*) into the accelerator's statistics; the caller says what is its own to say: how many rays, how many
  * hits.  slots: the lane-slot words too (the tile pipelines' batches; h holds LH_CNT_DEV words then) */
 static inline void lh_stat_add(lh_accel_t *a, const unsigned long long *h, unsigned long long rays, unsigned long long hits, bool slots = false)

@@ -2,6 +2,10 @@
  * lh_query.hip -- the ray queries of the C ABI: accel_intersect_func (src/render/accel.h:30-34) as device-resident, host
  * and pipelined host batches, one synchronous ray, traversal statistics (src/render/bvh.c:669-706) and beam visibility
  * (ri_bvh_intersect_beam_visibility, bvh.c:612-667).  The kernels are in lh_kernels.hip / lh_beam.hip.
+ *
+ * Large plain device dumps are traced from a copy in bin order (lh_launch; the passes are in lh_order.hip, the order in lh_order.h): fp64 rays with
+ * fp64 records or any-hit bytes, the default walk, "dump_order_min" rays or more.  Every other call -- fp32 rays, 16-byte records, indexed and bounded
+ * dumps, per-ray diagnostics, the tile pipelines' batches, smaller dumps -- takes the path it always took, unchanged.
  */
 #include <atomic>
 #include <chrono>
@@ -117,6 +121,19 @@ static int batch_args(const lh_accel_t *a, const char *what, size_t n, bool have
     return 1;
 }
 
+/* the workspace of the stream of slot qk for a dump in bin order (lh_order.h), grown on demand and kept; NULL: the dump is traced as given -- its
+ * workspace would exceed "dump_order_max_mb", or the memory is not to be had */
+static void *order_workspace(lh_accel_t *a, int qk, const lh_order_plan_t &p)
+{
+    lh_buf *w = &a->aoq[qk].order_ws;
+    if (a->dump_order_max_mb && p.bytes > (a->dump_order_max_mb << 20)) return NULL;
+    if (w->p && w->cap >= p.bytes) return w->p;
+    lh_free_buf(w);          /* hipFree waits for the launches that still read it */
+    if (hipMalloc(&w->p, p.bytes) != hipSuccess) { (void)hipGetLastError(); w->p = NULL; return NULL; }
+    w->cap = p.bytes;
+    return w->p;
+}
+
 int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bool dump, const lh_launch_opt &opt)
 {
     const int go = batch_args(a, "intersect", b.n, (b.org && b.dir) || opt.cam_src, "ray arrays", b.mode);
@@ -185,9 +202,35 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
      * closest hit, 2 735 -> 2 772 any hit; the 8-wide walk and the AO stage are best where they are) */
     const bool dump4 = dump && !q8 && !a->knobs_user;
     const bool dump8 = dump && q8 && !a->knobs_user;
-    const int rc = lh_launch_trace(&sc, &b, lh_next_cursor(a), variant, a->grid_blocks,
-                                   dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch,
-                                   &a->aoq[qk].q, a->ncus, (void *)s);
+    const int min_active = dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, tri_batch = dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch;
+    /* a large plain dump is traced from a copy in bin order (lh_order.h): each XCD's L2 then sees one region of the scene at a time.  Plain: fp64 rays
+     * (on 16-byte boundaries: the count's loads; a dump that starts on an odd multiple of 8 bytes is traced as given) with fp64 records or any-hit bytes, the default walk, every ray of the arrays, no bound, no count on the device, no
+     * diagnostics.  Everything else -- fp32 rays, 16-byte records, indexed and bounded dumps, the tile pipelines -- is traced as given, and so is a dump
+     * whose workspace cannot be had.  On the caller's stream, without a host synchronisation once the workspace is large enough (growing it frees the old
+     * one, and hipFree waits for the device): count, scan, copy; the walk, with its fix-up queue, its
+     * cooperative walk and k_fixups, on a batch that names the workspace's arrays; the records back.  More than 2^30 rays: part by part, each ordered by itself */
+    const bool ordered = dump && a->dump_order && n >= a->dump_order_min && variant == LH_VARIANT_SPEC && sc.io_fmt == 0u && !opt.indexed && !opt.tmax &&
+                         !opt.cam_src && !opt.n_dev && !opt.diag_out && !opt.diag_clock && !(((uintptr_t)b.org | (uintptr_t)b.dir) & 15u);
+    if (ordered) {
+        const size_t step = (size_t)1 << 30;
+        const uint32_t octant = a->dump_order_bits == 1u;          /* the two 6-bit keys: one bit per axis under the octant, two bits per axis alone */
+        char *ws = (char *)order_workspace(a, qk, lh_order_plan(n < step ? n : step, a->dump_order_bits, octant, closest));
+        const lh_order_grid_t g = lh_order_grid(sc.grid_lo, sc.grid_step, a->dump_order_bits, octant);
+        for (size_t off = 0; ws && off < n; off += step) {
+            const lh_batch_t part = lh_batch_sub(b, 0u, off, n - off < step ? n - off : step);
+            const lh_order_plan_t p = lh_order_plan(part.n, a->dump_order_bits, octant, closest);
+            if (a->poison_outputs) HIPCHK(hipMemsetAsync(ws + (closest ? p.t : p.occ), 0x77, p.dest - (closest ? p.t : p.occ), s));          /* the ordered records too: the walk writes every one */
+            if (lh_order_run(&p, &g, part.org, part.dir, ws, s) != 0) return fail("ordering a ray dump failed: %s", hipGetErrorString(hipGetLastError()));
+            const lh_batch_t o = {part.n, b.mode, ws + p.org, ws + p.dir, closest ? ws + p.prim : NULL, closest ? ws + p.t : NULL, closest ? ws + p.u : NULL,
+                                  closest ? ws + p.v : NULL, closest ? NULL : ws + p.occ, b.counters};
+            if (lh_launch_trace(&sc, &o, lh_next_cursor(a), variant, a->grid_blocks, min_active, tri_batch, &a->aoq[qk].q, a->ncus, (void *)s) != 0 ||
+                lh_order_back(&p, closest ? 1 : 0, ws, part.prim, part.t, part.u, part.v, part.occ, s) != 0)
+                return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+            a->order_stat[0]++; a->order_stat[1] += part.n;
+        }
+        if (ws) return 0;
+    }
+    const int rc = lh_launch_trace(&sc, &b, lh_next_cursor(a), variant, a->grid_blocks, min_active, tri_batch, &a->aoq[qk].q, a->ncus, (void *)s);
     if (rc != 0) return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
@@ -245,6 +288,15 @@ extern "C" int lh_accel_dump_node_bytes(const lh_accel_t *a)
 }
 
 extern "C" uint64_t lh_accel_last_retraced(const lh_accel_t *a) { return a ? a->last_retraced : 0; }
+
+extern "C" int lh_accel_order_statistics(lh_accel_t *a, uint64_t out[2], int clear)
+{
+    lh_guard guard(a);
+    if (!a || !out) return fail("lh_accel_order_statistics: NULL argument");
+    out[0] = a->order_stat[0]; out[1] = a->order_stat[1];
+    if (clear) a->order_stat[0] = a->order_stat[1] = 0;
+    return 0;
+}
 
 int lh_ensure_stage(lh_accel_t *a, size_t bytes)
 {
