@@ -383,7 +383,8 @@ int  lh_render_primary_rays(lh_accel_t *accel, const lh_camera_t *cam, int x0, i
                             int pixel_samples, void *d_org_xyz, void *d_dir_xyz, void *stream);
 
 /* one AO tile entirely on the device: camera rays -> closest hit -> hit epilogue ->
- * gather_nsamples AO rays per hit -> any-hit -> radiance.  d_rgb: float[h][w][3] in image
+ * gather_nsamples AO rays per hit -> any-hit -> radiance, times the texture of the hit's mesh
+ * where it has one (lh_accel_set_texture; else the three channels are equal).  d_rgb: float[h][w][3] in image
  * orientation (row 0 = the tile's TOP row of the output image, as bucket_write flips y).
  * d_uniforms: NULL for the built-in counter-based RNG (seed), or 2 doubles per AO ray in
  * (hit slot, j, i) order -- how a caller replays the reference's MT19937 stream.
@@ -482,8 +483,8 @@ int  lh_accel_ao_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_org
  *   (the bounded record's t); else, and as the second try of a fused launch whose queue overflowed, the rays are materialised in HBM
  *   and traced by one bounded closest-hit launch whose bounds are all far_clip.  Both give the same bytes.  With
  *   lh_accel_trace_statistics on, `rays` advances by hits x N and counters[4] by the bounded hits.
- * lh_render_dirt_tile: ri_transport_dirtmap per camera sample, without the texture multiply -- a miss gives 0, a hit its value;
- *   sub-samples accumulated and written as lh_render_ao_tile does, keys are the absolute sample position (a frame does not depend on
+ * lh_render_dirt_tile: ri_transport_dirtmap per camera sample -- a miss gives 0, a hit its value, times the texture of its mesh where it
+ *   has one (lh_accel_set_texture below; lh_accel_dirt_device / _host return the value alone); sub-samples accumulated and written as lh_render_ao_tile does, keys are the absolute sample position (a frame does not depend on
  *   its tiling); stats->ao_rays = hits x N, stats->ao_occluded = the sum of the hits' near_hits. */
 typedef struct lh_dirt_params { double near_clip, far_clip, eps; } lh_dirt_params_t;
 #define LH_DIRT_DEFAULTS { 0.1, 0.5, 1.0e-5 }          /* dirtmap.c:98,110-111 */
@@ -498,6 +499,51 @@ int  lh_accel_dirt_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz,
 int  lh_render_dirt_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
                          int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed,
                          const void *d_uniforms, void *d_rgb, lh_tile_stats_t *stats, void *stream);
+
+/* ---- material textures: the multiply both occlusion transports end with (src/transport/ambientocclusion.c:393-401, dirtmap.c:273-281) ----
+ * Where the hit's mesh has a texture: ri_texture_fetch(texcol, texture, s, t); radiance[k] *= texcol[k].
+ *   texture: height rows of width texels, 4 floats (RGBA) each, row 0 first (ri_texture_t.data, src/render/texture.h:21-29), no flip.
+ *   fetch(s, t) = ri_texture_fetch (src/render/texture.c:86-235, the scanline branch), fp64 in this order, no contraction:
+ *     u = s - floor(s), v = t - floor(t); each clamped: < 0 -> 0, >= 1 -> 1; px = u * (width - 1), py = v * (height - 1);
+ *     x = (int)px, y = (int)py; dx = px - x, dy = py - y; w0 = (1-dx)(1-dy), w1 = (1-dx)dy, w2 = dx(1-dy), w3 = dx dy over the texels
+ *     (x,y), (x,y+1), (x+1,y), (x+1,y+1) widened to double, a neighbour outside the image counting as 0.0 (the reference's edge rule);
+ *     out[i] = ((w0 e0[i] + w1 e1[i]) + w2 e2[i]) + w3 e3[i] for the four channels.
+ *   s, t: doubles 18 and 19 of lh_accel_state_build_* for the hit (lerp_uv; 0, 0 for a mesh without texture coordinates).  A non-finite
+ *     s or t (undefined in the reference) gives an unspecified colour; the texel index stays inside the image.
+ *   per camera sample: rad_k = rad * texcol[k] (k = 0, 1, 2) where the hit's mesh has a texture, else rad_k = rad, with rad the double the
+ *     tile computes without textures; sub-samples accumulate per channel in the same order, then the same scale, (float) conversion and
+ *     clamp of negatives to 0, per channel.  A miss contributes 0.
+ * lh_render_ao_tile / _bands / _tile_host, lh_render_ao_frame_host, lh_render_dirt_tile, lh_multi_render_ao_frame_host and
+ *   lh_dist_render_ao_frame_host multiply as soon as the accelerator holds at least one texture; with none they launch the kernels
+ *   they always launched, with the same arguments.  Tile statistics, the replay uniforms and the fused / materialised stages do not
+ *   depend on textures.  Not covered: the sun-and-sky branch, mip-maps, textures in the path tracer (lh_render_pt_*), and
+ *   `Surface "texture"` in the RIB reader (it needs the reference's image loaders).
+ * lh_accel_set_texture: rgba is HOST memory (width x height x 4 floats) and is copied.  Allowed for any mesh already added, before or
+ *   after commit (trees do not depend on it; no device is touched before the first call that needs the texture there).  rgba == NULL
+ *   with width == height == 0 removes the texture; a second call replaces the first and takes effect for calls made after it returns.
+ *   A block that is replaced or removed is released only after every launch enqueued earlier that may read it has finished.  Texel
+ *   values are not validated.  With LH_ALL_MESHES the meshes share one block.
+ * lh_accel_set_texture_device: the same for an array in the memory of the accelerator's device; it is read by a copy enqueued on
+ *   `stream` before the call returns, into a block the library owns: the caller may overwrite or free it in stream order afterwards.
+ * Both refuse, -1 with lh_last_error, nothing changed: "accel is NULL"; "mesh M out of range"; "bad texture size" (width or height
+ *   outside [1, 65536]); "NULL array" (with a non-zero size); "not 4-byte aligned"; the device form: "not a device pointer" /
+ *   "extends past its allocation" (asked of the runtime, never dereferenced), as lh_accel_add_mesh_device. */
+int  lh_accel_set_texture(lh_accel_t *accel, uint32_t mesh /* or LH_ALL_MESHES */, const float *rgba, int width, int height);
+int  lh_accel_set_texture_device(lh_accel_t *accel, uint32_t mesh /* or LH_ALL_MESHES */, const void *d_rgba, int width, int height,
+                                 void *stream);
+/* the fetch alone for a caller's batch of hit records (a bake, a transport of the caller's own): d_prim / d_u / d_v are the LH_REC_F64
+ * closest-hit records of n_rays rays; d_index / n_index / d_count: a list as for lh_accel_ao_device (ids, the identity list when
+ * d_index is NULL, the count read on `stream`; all NULL / 0: every ray; a traced ray is a listed entry within the count whose id is
+ * < n_rays).  d_rgba_out[4 * id ..] (doubles) = fetch(s, t) of the hit, or 1, 1, 1, 1 where its mesh has no texture; a traced miss
+ * (LH_MISS, or an id beyond the scene's primitives) gets four zeros.  The slots of rays that are not traced are not touched, byte for
+ * byte; an id listed twice is written twice with the same values.  Asynchronous on `stream`, nothing is read back.  An empty scene:
+ * every traced ray is a miss, no record array is read.  -1 (lh_last_error), nothing enqueued or written: an uncommitted accelerator,
+ * a NULL record or output array with n_rays > 0, n_rays >= 2^31, n_index > 2^30, a list / count / id pointer that is not 4-byte
+ * aligned or a u / v / output pointer that is not 8-byte aligned.  n_rays == 0 returns 0 and looks at no array. */
+int  lh_accel_texture_device(lh_accel_t *accel, size_t n_rays, const void *d_prim, const void *d_u, const void *d_v,
+                             const void *d_index, size_t n_index, const void *d_count, void *d_rgba_out, void *stream);
+/* the same for HOST arrays: copies up, runs lh_accel_texture_device on the accelerator's stream, copies down (every ray is traced) */
+int  lh_accel_texture_host(lh_accel_t *accel, size_t n_rays, const uint32_t *prim, const double *u, const double *v, double *rgba_out);
 
 /* one path-traced tile on the device (BASELINE config 4: the reference's pathtrace.c is dead
  * code; its documented structure -- camera sample, Russian roulette on the reflectance,
@@ -602,6 +648,8 @@ int  lh_multi_add_rib_scene(lh_multi_t *multi, const lh_rib_scene_t *scene);
 int  lh_multi_commit(lh_multi_t *multi, int build_threads);
 int  lh_multi_set_material(lh_multi_t *multi, uint32_t mesh, const lh_material_t *material);
 int  lh_multi_set_environment(lh_multi_t *multi, const lh_environment_t *environment);
+/* lh_accel_set_texture on every replica (after lh_multi_commit, as the materials): lh_multi_render_ao_frame_host then renders textured frames */
+int  lh_multi_set_texture(lh_multi_t *multi, uint32_t mesh /* or LH_ALL_MESHES */, const float *rgba, int width, int height);
 int  lh_multi_intersect_host(lh_multi_t *multi, size_t n, const double *org_xyz, const double *dir_xyz, uint32_t *prim,
                              double *t, double *u, double *v, uint8_t *occluded, int mode);
 int  lh_multi_render_ao_frame_host(lh_multi_t *multi, const lh_camera_t *cam, int pixel_samples, int gather_nsamples,
@@ -644,7 +692,8 @@ int  lh_dist_gather(lh_dist_t *dist, const void *d_send, size_t bytes, void *d_r
  * 6e-8 relative of them (north_star: 1e-5); a miss keeps prim 0xFFFFFFFF and t = 1e38.  No communicator needed. */
 int  lh_dist_pack_records16(size_t n, const void *d_prim, const void *d_t, const void *d_u, const void *d_v, void *d_rec16, void *stream);
 /* rank 0: a committed accelerator; the others: a fresh one (lh_accel_create), committed on return -- no build, no host
- * copy of the tree on those ranks (lh_accel_export and replicas of it are refused) */
+ * copy of the tree on those ranks (lh_accel_export and replicas of it are refused).  The image does not carry material textures:
+ * every rank calls lh_accel_set_texture on its own accelerator after the broadcast (the setter is allowed after commit) */
 int  lh_dist_broadcast_scene(lh_dist_t *dist, lh_accel_t *accel);
 /* the AO frame sharded over the ranks: bands of band_rows lines (<= 0: 16), dealt out in serpentine order (groups of `world`
  * bands, even groups in rank order, odd groups reversed: a steady change of cost down the image cancels); rgb (rank 0 only): height

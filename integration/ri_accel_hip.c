@@ -105,6 +105,9 @@ void *ri_hipbvh_build(const void *data)
             if (geom->binormals) bad |= lh_accel_set_attribute(h->lh, m, LH_ATTR_BINORMAL, (const double *)geom->binormals, sizeof(ri_vector_t), geom->nbinormals);
             if (geom->texcoords) bad |= lh_accel_set_attribute(h->lh, m, LH_ATTR_TEXCOORD, geom->texcoords, 2 * sizeof(ri_float_t), geom->npositions);
             else if (geom->texcoords_unshared) bad |= lh_accel_set_attribute(h->lh, m, LH_ATTR_TEXCOORD_UNSHARED, geom->texcoords_unshared, 2 * sizeof(ri_float_t), geom->nindices);
+            /* the texture both occlusion transports multiply with (ambientocclusion.c:393-401, dirtmap.c:273-281): fp32 RGBA rows, copied */
+            if (geom->material && geom->material->texture)
+                bad |= lh_accel_set_texture(h->lh, m, geom->material->texture->data, geom->material->texture->width, geom->material->texture->height);
             if (bad) {
                 ri_log(LOG_ERROR, "(HIPBVH) geom %u: %s", m, lh_last_error());
                 lh_accel_destroy(h->lh); free(h->geoms); free(h);

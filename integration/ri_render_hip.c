@@ -24,8 +24,9 @@
  *                        stream exactly as its single-threaded render consumes it: reproduces the CPU frame
  *                        (up to the <= 20 / 65 536 pixels where device and glibc sin/cos differ);
  *   "rays"               the CPU controller: every ray through ri_raytrace -> accel->intersect (one launch per ray).
- * Anything the tile pipeline does not cover (sunsky light, xsamples != ysamples, a material texture on a geom)
- * falls back to the CPU controller, which still traces through the HIP accelerator.
+ * Anything the tile pipeline does not cover (sunsky light, xsamples != ysamples) falls back to the CPU controller,
+ * which still traces through the HIP accelerator.  A material texture on a geom is covered: ri_accel_hip.c hands it
+ * to the accelerator and the tile pipeline multiplies (ambientocclusion.c:393-401).
  */
 #include <stdint.h>
 #include <pthread.h>
@@ -52,15 +53,10 @@ extern lh_accel_t *ri_hipbvh_handle(void *accel);                         /* int
 static int hip_frame_supported(ri_render_t *render, int *ps_out)
 {
     ri_display_t *disp = ri_option_get_curr_display(render->context->option);
-    ri_list_t    *itr;
     const int xs = (int)disp->sampling_rates[0], ys = (int)disp->sampling_rates[1];
     if (!render->scene || !render->scene->accel || !render->scene->accel->data) return 0;
     if (render->scene->sunsky_light) return 0;                               /* gather_sunsky (ambientocclusion.c:369-374) */
     if (xs != ys || xs < 1) return 0;
-    for (itr = ri_list_first(render->scene->geom_list); itr != NULL; itr = ri_list_next(itr)) {
-        ri_geom_t *g = (ri_geom_t *)itr->data;
-        if (g->material && g->material->texture) return 0;                   /* texture multiply (ambientocclusion.c:393-401) */
-    }
     *ps_out = xs;
     return 1;
 }

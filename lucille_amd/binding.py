@@ -127,6 +127,7 @@ ABI_SYMBOLS = [
     "lh_accel_set_material", "lh_accel_set_environment", "lh_render_pt_tile2", "lh_render_pt_bands", "lh_accel_set_attribute", "lh_accel_set_normals_device", "lh_accel_set_attribute_device",
     "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
     "lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile",
+    "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
     "lh_multi_add_rib_scene", "lh_multi_commit", "lh_multi_set_material", "lh_multi_set_environment", "lh_multi_intersect_host",
     "lh_multi_render_ao_frame_host", "lh_multi_render_pt_frame_host",
@@ -218,6 +219,12 @@ def lib():
     L.lh_accel_dirt_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, dpp, C.c_uint64, vp, vp, sz, vp, vp]
     L.lh_render_dirt_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, dpp, C.c_uint64, vp, vp,
                                       C.POINTER(TileStats), vp]
+    if hasattr(L, "lh_accel_set_texture"):               # an older library under LH_LIBRARY (the parent's build in tools/tex_frames.py) has no textures
+        L.lh_accel_set_texture.argtypes = [vp, u32, vp, i32, i32]
+        L.lh_accel_set_texture_device.argtypes = [vp, u32, vp, i32, i32, vp]
+        L.lh_accel_texture_device.argtypes = [vp, sz, vp, vp, vp, vp, sz, vp, vp, vp]
+        L.lh_accel_texture_host.argtypes = [vp, sz, vp, vp, vp, vp]
+        L.lh_multi_set_texture.argtypes = [vp, u32, vp, i32, i32]
     L.lh_multi_create.argtypes = [C.POINTER(vp), i32, C.POINTER(i32)]
     L.lh_multi_destroy.argtypes = [vp]; L.lh_multi_destroy.restype = None
     L.lh_multi_ndevices.argtypes = [vp]
@@ -868,6 +875,70 @@ class HipAccel:
     def set_material(self, mesh, material):
         _check(self.L.lh_accel_set_material(self.h, int(mesh), C.byref(material)), "lh_accel_set_material")
 
+    def set_texture(self, mesh, texels, stream=None):
+        """lh_accel_set_texture / lh_accel_set_texture_device: the material texture of mesh `mesh` (or ALL_MESHES) that the AO and
+        dirt tiles multiply a hit's radiance with.  texels: [h, w, 4] float32 -- a numpy array (copied), or a contiguous CUDA
+        torch tensor (the device form: read by a copy enqueued on `stream`, None: the current one); None removes the texture.
+        Allowed before and after commit."""
+        if texels is None:
+            _check(self.L.lh_accel_set_texture(self.h, int(mesh), None, 0, 0), "lh_accel_set_texture")
+            return
+        if hasattr(texels, "is_cuda"):
+            import torch
+            if not (texels.is_cuda and texels.dtype == torch.float32 and texels.dim() == 3 and texels.shape[2] == 4 and texels.is_contiguous()):
+                raise ValueError("set_texture: a tensor must be a contiguous float32 device tensor [h, w, 4]")
+            if stream is None:
+                stream = torch.cuda.current_stream(texels.device)
+            stream = getattr(stream, "cuda_stream", stream)
+            _check(self.L.lh_accel_set_texture_device(self.h, int(mesh), _dptr(texels), int(texels.shape[1]), int(texels.shape[0]),
+                                                      C.c_void_p(stream)), "lh_accel_set_texture_device")
+            return
+        T = _np(texels, np.float32)
+        if T.ndim != 3 or T.shape[2] != 4:
+            raise ValueError("set_texture: texels must be [h, w, 4]")
+        _check(self.L.lh_accel_set_texture(self.h, int(mesh), T.ctypes.data, int(T.shape[1]), int(T.shape[0])), "lh_accel_set_texture")
+
+    def texture_device(self, records, index=None, count=None, out=None, stream=None):
+        """lh_accel_texture_device: the texture fetch alone for a batch of closest-hit records -- `records` = the (prim, t, u, v)
+        device tensors of intersect_device (t is not read).  index / count: a device list as for ao_device.  Returns the float64
+        tensor [n, 4]: the filtered RGBA at the hit, 1 1 1 1 where its mesh has no texture, zeros for a traced miss.  out: such a
+        tensor to fill; with out=None it is allocated with torch.empty and the rows of rays that are not listed are UNSPECIFIED.
+        Asynchronous on `stream`."""
+        import torch
+        what = "texture_device"
+        if not isinstance(records, (tuple, list)) or len(records) != 4:
+            raise ValueError("%s: records must be the (prim, t, u, v) tensors of a closest-hit batch" % what)
+        prim, _, u, v = records
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (isinstance(prim, torch.Tensor) and prim.is_cuda and prim.dtype in words and prim.dim() == 1 and prim.is_contiguous()):
+            raise ValueError("%s: prim must be a contiguous int32 / uint32 device tensor [n]" % what)
+        n = int(prim.shape[0])
+        for name, x in (("u", u), ("v", v)):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and x.dim() == 1 and x.shape[0] == n and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [n]" % (what, name))
+        ip, ni, cp = _list_args(index, count, what)
+        if index is None and count is not None:
+            ni = n
+        if out is None:
+            out = torch.empty((n, 4), dtype=torch.float64, device=prim.device)
+        if not (out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and tuple(out.shape) == (n, 4) and out.is_contiguous()):
+            raise ValueError("%s: out must be a contiguous float64 device tensor [n, 4]" % what)
+        if stream is None:
+            stream = torch.cuda.current_stream(prim.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_texture_device(self.h, n, _dptr(prim), _dptr(u), _dptr(v), ip, ni, cp, _dptr(out), C.c_void_p(stream)),
+               "lh_accel_texture_device")
+        return out
+
+    def texture_host(self, prim, u, v):
+        """lh_accel_texture_host: host arrays of closest-hit records -> float64 [n, 4] as texture_device (every ray is traced)"""
+        p = _np(prim, np.uint32).reshape(-1); uu = _np(u, np.float64).reshape(-1); vv = _np(v, np.float64).reshape(-1)
+        if not (p.shape[0] == uu.shape[0] == vv.shape[0]):
+            raise ValueError("texture_host: prim, u and v must describe the same rays")
+        out = np.zeros((p.shape[0], 4))
+        _check(self.L.lh_accel_texture_host(self.h, p.shape[0], p.ctypes.data, uu.ctypes.data, vv.ctypes.data, out.ctypes.data), "lh_accel_texture_host")
+        return out
+
     def reset_environment(self):
         """back to the default environment of the path tracer (constant white)"""
         _check(self.L.lh_accel_set_environment(self.h, None), "lh_accel_set_environment")
@@ -1126,6 +1197,16 @@ class HipMulti:
 
     def set_material(self, mesh, material):
         _check(self.L.lh_multi_set_material(self.h, int(mesh), C.byref(material)), "lh_multi_set_material")
+
+    def set_texture(self, mesh, texels):
+        """lh_multi_set_texture: every replica gets the texture ([h, w, 4] float32 numpy; None removes it), after commit"""
+        if texels is None:
+            _check(self.L.lh_multi_set_texture(self.h, int(mesh), None, 0, 0), "lh_multi_set_texture")
+            return
+        T = _np(texels, np.float32)
+        if T.ndim != 3 or T.shape[2] != 4:
+            raise ValueError("set_texture: texels must be [h, w, 4]")
+        _check(self.L.lh_multi_set_texture(self.h, int(mesh), T.ctypes.data, int(T.shape[1]), int(T.shape[0])), "lh_multi_set_texture")
 
     def set_environment(self, rgb=(1.0, 1.0, 1.0), envmap=None):
         e = Environment()

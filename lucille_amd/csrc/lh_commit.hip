@@ -182,7 +182,7 @@ static void free_dmeshes(lh_accel_t *a)
 }
 
 /* `bytes` at p are device memory of the accelerator's device, as the runtime knows it: asked, never tried */
-static int device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *who, const char *what)
+int lh_device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *who, const char *what)
 {
     hipPointerAttribute_t at; memset(&at, 0, sizeof(at));
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail("%s: %s is not a device pointer", who, what); }
@@ -226,8 +226,8 @@ extern "C" int lh_accel_add_mesh_device(lh_accel_t *a, uint32_t npos, const void
     /* what the flatten kernel will read: whole vertices up to the last one's z, whole triangles */
     const size_t pos_bytes = ntris ? (size_t)(npos - 1) * stride + 3 * elem : 0, idx_bytes = sizeof(uint32_t) * 3 * (size_t)ntris;
     HIPCHK(hipSetDevice(a->device));
-    if (ntris && (device_array_ok(a, d_pos, pos_bytes, "lh_accel_add_mesh_device", "positions") != 0 ||
-                  device_array_ok(a, d_idx, idx_bytes, "lh_accel_add_mesh_device", "indices") != 0)) return -1;
+    if (ntris && (lh_device_array_ok(a, d_pos, pos_bytes, "lh_accel_add_mesh_device", "positions") != 0 ||
+                  lh_device_array_ok(a, d_idx, idx_bytes, "lh_accel_add_mesh_device", "indices") != 0)) return -1;
     lh_dmesh *nm = (lh_dmesh *)realloc(a->dmeshes, sizeof(lh_dmesh) * (a->ndmeshes + 1));
     if (!nm) return fail("out of memory");
     a->dmeshes = nm;
@@ -280,7 +280,7 @@ static int set_dmesh_attr(lh_accel_t *a, const char *who, uint32_t mesh, int slo
         if (!d) return fail("%s: NULL array", who);
         bytes = count ? (size_t)(count - 1) * stride + ncomp * elem : 0;
         HIPCHK(hipSetDevice(a->device));
-        if (bytes && device_array_ok(a, d, bytes, who, "the array") != 0) return -1;
+        if (bytes && lh_device_array_ok(a, d, bytes, who, "the array") != 0) return -1;
         if (count != need) return fail("%s: %u values given, the mesh needs %u (one per %s)", who, count, need,
                                        slot == LH_ATTR_TEXCOORD_UNSHARED ? "index" : "vertex");
     }
@@ -1212,6 +1212,7 @@ extern "C" int lh_accel_ref_tree(lh_accel_t *a, uint32_t *nnodes, void *nodes_ou
 extern "C" void lh_accel_destroy(lh_accel_t *a)
 {
     if (!a) return;
+    lh_tex_release(a);
     if (a->committed || a->commit_failed) { (void)hipSetDevice(a->device); lh_comb_destroy(a); release_device(a); }
     if (a->ndmeshes || a->ndmesh_events) { (void)hipSetDevice(a->device); free_dmeshes(a); }
     for (uint32_t g = 0; g < a->nmeshes; g++) {

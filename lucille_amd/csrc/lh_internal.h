@@ -26,6 +26,7 @@
 #include "lh_refbvh.h"
 #include "lh_device.h"
 #include "lh_order.h"
+#include "lh_tex.h"
 
 /* lh_last_error() of the calling thread; lh_fail formats it and returns -1 */
 int lh_fail(const char *fmt, ...);
@@ -53,6 +54,13 @@ typedef struct lh_gather_out { double *nrm9, *attr9[3], *st6; uint8_t *inside; }
 struct lh_dmesh_event { hipStream_t stream; hipEvent_t ev; };          /* the last copy enqueued on a caller's stream: the commit waits for it */
 
 struct lh_buf { void *p; size_t cap; };
+/* material textures (lh_tex.h, lh_tex.hip).  A block of texels, shared by the meshes one setter call gave it to: a host copy until the first call
+ * that needs it on the device (lh_accel_set_texture works without a device, before commit), or the device copy lh_accel_set_texture_device
+ * enqueued on the caller's stream (ev: recorded behind that copy, waited for once) */
+struct lh_tex_block { int refs, width, height; float *host; void *dev; hipEvent_t ev; int ev_live; };
+/* what a textured resolve and k_tex_batch read beside the per-sample slots: the closest-hit records by sample / ray id, the texture coordinates
+ * per primitive (NULL: no mesh has any), the mesh ordinal per primitive, the per-mesh descriptor table */
+typedef struct lh_tex_args { const uint32_t *prim; const double *u, *v, *st6; const uint32_t *prim_mesh; const lh_tex_desc_t *table; } lh_tex_args_t;
 /* what the AO stage (lh_tile.hip ao_stage) owns for one kind of caller: slot of every sample / list entry, hit records, slot keys, per-slot
  * occlusion counts (fused), the materialised rays and their any-hit bytes, the compaction's block counts */
 struct lh_ao_scratch { lh_buf slot, hitrec, key, occcount, aorg, adir, occ, blocks; };
@@ -131,6 +139,8 @@ struct lh_accel {
     void *d_attr9[3], *d_st6, *d_inside;            /* colour / tangent / binormal, st, inside flags (uploaded at commit if present) */
     void *d_prim_mesh;                 /* mesh ordinal per primitive (materials; uploaded on first use) */
     lh_material_t *materials; uint32_t nmaterials; void *d_materials; int materials_dirty;
+    lh_tex_block **tex; uint32_t ntex_slots, ntex;      /* per mesh (NULL: none), and how many meshes have one: > 0 makes the AO and dirt tiles multiply */
+    void *d_tex_table; uint32_t tex_table_n; int tex_dirty;     /* lh_tex_desc_t per mesh on the device, rebuilt by lh_tex_sync after a setter */
     lh_environment_t env; void *d_env_map; int env_set;      /* env_set: lh_accel_set_environment was called (else the path tracer's environment is constant white) */
     lh_buf r_state;                    /* lh_accel_state_build_host staging */
     lh_buf r_uni;                      /* lh_render_ao_tile_host: caller uniforms on the device */
@@ -205,6 +215,19 @@ enum { LH_FMT_F32 = 1, LH_FMT_Q16X4 = 4, LH_FMT_Q8 = 32 };
 int  lh_ensure_formats(lh_accel_t *a, int mask);
 int  lh_sync_ref(lh_accel_t *a, bool wait);          /* attach the background-built reference-order tree (wait: block for it) */
 int  lh_ensure_buf(lh_buf *b, size_t bytes);
+int  lh_device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *who, const char *what);      /* `bytes` at p are memory of the accelerator's device: asked of the runtime */
+/* lh_tex.hip */
+void lh_tex_release(lh_accel_t *a);                  /* every texture block and the table (lh_accel_destroy) */
+int  lh_tex_sync(lh_accel_t *a);                     /* pending textures onto the device, the descriptor table, d_prim_mesh; a committed accelerator, its device current */
+int  lh_ensure_prim_mesh(lh_accel_t *a);             /* d_prim_mesh, uploaded on first use (materials, textures) */
+/* the arguments of a textured resolve over records prim / u / v, or NULL when no mesh has a texture (after lh_tex_sync) */
+static inline const lh_tex_args_t *lh_tex_args(const lh_accel_t *a, const void *prim, const void *u, const void *v, lh_tex_args_t *out)
+{
+    if (!a->ntex) return NULL;
+    *out = lh_tex_args_t{(const uint32_t *)prim, (const double *)u, (const double *)v, (const double *)a->d_st6, (const uint32_t *)a->d_prim_mesh,
+                         (const lh_tex_desc_t *)a->d_tex_table};
+    return out;
+}
 void lh_free_buf(lh_buf *b);
 /* the scene image (lh_commit.hip): one rank's committed scene handed to the others (lh_dist.hip) */
 typedef struct lh_scene_image {
@@ -287,7 +310,9 @@ extern "C" int lh_render_launch_ao_rays(size_t nslots, int ntheta, int nphi, uns
                                         const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
 extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
                                         const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
-                                        unsigned long long *d_occ_total, void *stream);
+                                        unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream);
+extern "C" int lh_render_launch_tex_batch(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count,
+                                          const lh_tex_args_t *tex, uint32_t ntris, double *d_rgba, void *stream);
 extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
                                               const uint32_t *d_index, const uint32_t *d_count, const double *d_org, const double *d_dir,
                                               const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
@@ -303,7 +328,7 @@ extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigne
 extern "C" int lh_render_launch_dirt_bounds(size_t n, double far_clip, double *d_bound, void *stream);
 extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
                                              const uint32_t *d_slot_of_sample, const double *d_t, float *d_rgb,
-                                             unsigned long long *d_hit_total, void *stream);
+                                             unsigned long long *d_hit_total, const lh_tex_args_t *tex, void *stream);
 extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
                                                    double near_clip, double far_clip, const uint32_t *d_slot_of_entry, const double *d_t,
                                                    uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream);

@@ -311,6 +311,14 @@ extern "C" int lh_multi_set_material(lh_multi_t *m, uint32_t mesh, const lh_mate
     return 0;
 }
 
+extern "C" int lh_multi_set_texture(lh_multi_t *m, uint32_t mesh, const float *rgba, int width, int height)
+{
+    /* textures live on the replicas, as the materials do */
+    if (!m || !m->committed) return mfail("lh_multi_set_texture: not committed (set textures after lh_multi_commit)");
+    for (int k = 0; k < m->n; k++) if (lh_accel_set_texture(m->acc[k], mesh, rgba, width, height) != 0) return -1;
+    return 0;
+}
+
 extern "C" int lh_multi_set_environment(lh_multi_t *m, const lh_environment_t *environment)
 {
     if (!m || !m->committed) return mfail("lh_multi_set_environment: not committed");

@@ -33,6 +33,7 @@
 #include "lh_internal.h"
 #include "lh_ao.h"
 #include "lh_dirt.h"
+#include "lh_tex.h"
 
 namespace {
 
@@ -281,18 +282,39 @@ __global__ void k_ao_rays_counted(const unsigned long long *__restrict__ nslots_
     ao_ray_item((size_t)blockIdx.x * blockDim.x + threadIdx.x, (size_t)*nslots_dev, ntheta, nphi, seed, hitrec, rnd, slot_key, org, dir);
 }
 
+/* ---- the material texture of a hit (lh_tex.h) ---- */
+typedef lh_tex_args_t TexArgs;          /* lh_internal.h: what the textured resolves and k_tex_batch read; the launchers' callers fill it */
+
+/* texcol of record i (a hit): false = its mesh has no texture (c is not written).  s, t: doubles 18 and 19 of k_state_build */
+__device__ __forceinline__ bool tex_color(const TexArgs &tx, size_t i, double c[4])
+{
+    LH_NC
+    const uint32_t p = tx.prim[i];
+    const lh_tex_desc_t d = tx.table[tx.prim_mesh[p]];
+    if (!d.texels) return false;
+    double s = 0.0, t = 0.0;
+    if (tx.st6) {
+        const double *q = tx.st6 + 6 * (size_t)p;
+        if (q[0] == q[0]) lh_tex_st(q, tx.u[i], tx.v[i], &s, &t);
+    }
+    lh_tex_fetch(d.texels, d.width, d.height, s, t, c);
+    return true;
+}
+
 /* one thread per pixel: accumulates its sub-samples exactly like subsample()
- * (render.c:749-822) and bucket_write (:962-975): rgb[(h-1-ly)*w + lx] */
-__global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
-                             const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
-                             float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
+ * (render.c:749-822) and bucket_write (:962-975): rgb[(h-1-ly)*w + lx].  TEX: radiance[k] *= texcol[k] where the hit's mesh has a
+ * texture (ambientocclusion.c:393-401), accumulated per channel; false: the kernel the AO pipeline always ran */
+template <bool TEX>
+__device__ __forceinline__ void ao_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
+                                           const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
+                                           float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs *tx)
 {
     LH_NC
     const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool inside = pix < (size_t)w * h;
     /* h = all lines of the batch (nbands * band_rows); every band is flipped within itself, as a tile is */
     const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
-    double accum = 0.0;
+    double accum = 0.0, accum1 = 0.0, accum2 = 0.0;      /* (channels 1 and 2: TEX only) */
     unsigned int nocc = 0;
     const int S = inside ? xs * ys : 0;
     for (int s = 0; s < S; s++) {
@@ -310,6 +332,11 @@ __global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N,
             const double ns = (double)(uint32_t)N;
             rad = 1.0 * (ns - occlusion) / ns;
         }
+        if (TEX) {
+            double c[4];
+            if (slot != LH_MISS_PRIM && tex_color(*tx, pix * S + s, c)) { accum = accum + rad * c[0]; accum1 = accum1 + rad * c[1]; accum2 = accum2 + rad * c[2]; }
+            else { accum = accum + rad; accum1 = accum1 + rad; accum2 = accum2 + rad; }
+        } else
         accum = accum + rad;
     }
     if (inside) {
@@ -318,6 +345,12 @@ __global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N,
         if (f < 0.0f) f = 0.0f;
         float *o = rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx);
         o[0] = f; o[1] = f; o[2] = f;
+        if (TEX) {
+            float f1 = (float)(accum1 * ((double)1.0 / (xs * ys))), f2 = (float)(accum2 * ((double)1.0 / (xs * ys)));
+            if (f1 < 0.0f) f1 = 0.0f;
+            if (f2 < 0.0f) f2 = 0.0f;
+            o[1] = f1; o[2] = f2;
+        }
     }
     if (occ_total) {
         /* one atomic per WORKGROUP on one of 64 counters: atomics on one address are served one after the other (~5 ns each) --
@@ -331,6 +364,20 @@ __global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N,
             if (tot) atomicAdd(occ_total + (blockIdx.x & 63u), (unsigned long long)tot);
         }
     }
+}
+
+__global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
+                             const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
+                             float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
+{
+    ao_resolve<false>(w, h, band_rows, xs, ys, N, slot_of_sample, occ, occ_count, rgb, occ_total, NULL);
+}
+
+__global__ void k_ao_resolve_tex(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
+                                 const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
+                                 float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs tx)
+{
+    ao_resolve<true>(w, h, band_rows, xs, ys, N, slot_of_sample, occ, occ_count, rgb, occ_total, &tx);
 }
 
 /* ---- the AO stage for a caller's batch of hit records (lh_accel_ao_device / lh_accel_ao_rays_device) ----------------
@@ -461,16 +508,18 @@ __device__ __forceinline__ void dirt_total(unsigned int nh, unsigned long long *
     }
 }
 
-/* k_ao_resolve for the dirt tile: a miss gives 0, a hit its value (ri_transport_dirtmap, dirtmap.c:234-292, without the texture) */
-__global__ void k_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
-                               const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
-                               float *__restrict__ rgb, unsigned long long *__restrict__ hit_total)
+/* k_ao_resolve for the dirt tile: a miss gives 0, a hit its value (ri_transport_dirtmap, dirtmap.c:234-292).  TEX: with the texture
+ * multiply of :273-281, as ao_resolve; false: the kernel the dirt tile always ran */
+template <bool TEX>
+__device__ __forceinline__ void dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
+                                             const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
+                                             float *__restrict__ rgb, unsigned long long *__restrict__ hit_total, const TexArgs *tx)
 {
     LH_NC
     const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool inside = pix < (size_t)w * h;
     const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
-    double accum = 0.0;
+    double accum = 0.0, accum1 = 0.0, accum2 = 0.0;      /* (channels 1 and 2: TEX only) */
     unsigned int nh = 0;
     const int S = inside ? xs * ys : 0;
     for (int s = 0; s < S; s++) {
@@ -481,6 +530,11 @@ __global__ void k_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int 
             val = lh_dirt_value(tg + (size_t)slot * (size_t)N, N, near_clip, far_clip, &c);
             nh += c;
         }
+        if (TEX) {
+            double c[4];
+            if (slot != LH_MISS_PRIM && tex_color(*tx, pix * S + s, c)) { accum = accum + val * c[0]; accum1 = accum1 + val * c[1]; accum2 = accum2 + val * c[2]; }
+            else { accum = accum + val; accum1 = accum1 + val; accum2 = accum2 + val; }
+        } else
         accum = accum + val;
     }
     if (inside) {
@@ -489,8 +543,44 @@ __global__ void k_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int 
         if (f < 0.0f) f = 0.0f;
         float *o = rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx);
         o[0] = f; o[1] = f; o[2] = f;
+        if (TEX) {
+            float f1 = (float)(accum1 * ((double)1.0 / (xs * ys))), f2 = (float)(accum2 * ((double)1.0 / (xs * ys)));
+            if (f1 < 0.0f) f1 = 0.0f;
+            if (f2 < 0.0f) f2 = 0.0f;
+            o[1] = f1; o[2] = f2;
+        }
     }
     dirt_total(nh, hit_total);
+}
+
+__global__ void k_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
+                               const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
+                               float *__restrict__ rgb, unsigned long long *__restrict__ hit_total)
+{
+    dirt_resolve<false>(w, h, band_rows, xs, ys, N, near_clip, far_clip, slot_of_sample, tg, rgb, hit_total, NULL);
+}
+
+__global__ void k_dirt_resolve_tex(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
+                                   const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
+                                   float *__restrict__ rgb, unsigned long long *__restrict__ hit_total, const TexArgs tx)
+{
+    dirt_resolve<true>(w, h, band_rows, xs, ys, N, near_clip, far_clip, slot_of_sample, tg, rgb, hit_total, &tx);
+}
+
+/* the fetch alone for a batch of hit records (lh_accel_texture_device): one thread per list entry, 4 doubles at rgba[4 * id] -- texcol, or
+ * 1 1 1 1 where the hit's mesh has no texture, or four zeros for a traced miss.  tx.prim NULL: an empty scene, every traced ray is a
+ * miss; a primitive id beyond the scene's counts as a miss too */
+__global__ void k_tex_batch(const BatchList bl, const TexArgs tx, uint32_t ntris, double *__restrict__ rgba)
+{
+    LH_NC
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    if (!batch_entry(bl, k, id)) return;
+    double c[4] = {0.0, 0.0, 0.0, 0.0};
+    const uint32_t p = tx.prim ? tx.prim[id] : LH_MISS_PRIM;
+    if (p < ntris && !tex_color(tx, (size_t)id, c)) { c[0] = 1.0; c[1] = 1.0; c[2] = 1.0; c[3] = 1.0; }
+    double *o = rgba + 4 * (size_t)id;
+    o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
 }
 
 /* k_ao_batch_resolve for the dirt stage: near_hits[id] / value[id] (either may be NULL); a traced miss gets LH_AO_NO_HIT / 0.
@@ -934,14 +1024,29 @@ extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigne
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+/* tex (or NULL: no mesh has a texture -- the kernel and the arguments of every frame before textures): the textured resolve */
 extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
                                         const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
-                                        unsigned long long *d_occ_total, void *stream)
+                                        unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream)
 {
     const size_t total = (size_t)w * h;
     if (total == 0) return 0;
+    if (tex)
+        hipLaunchKernelGGL(k_ao_resolve_tex, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           w, h, band_rows, xs, ys, N, d_slot_of_sample, d_occ, d_occ_count, d_rgb, d_occ_total, *tex);
+    else
     hipLaunchKernelGGL(k_ao_resolve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        w, h, band_rows, xs, ys, N, d_slot_of_sample, d_occ, d_occ_count, d_rgb, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_tex_batch(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count,
+                                          const lh_tex_args_t *tex, uint32_t ntris, double *d_rgba, void *stream)
+{
+    if (n_list == 0) return 0;
+    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
+    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
+    hipLaunchKernelGGL(k_tex_batch, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bl, *tex, ntris, d_rgba);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -988,10 +1093,14 @@ extern "C" int lh_render_launch_dirt_bounds(size_t n, double far_clip, double *d
 
 extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
                                              const uint32_t *d_slot_of_sample, const double *d_t, float *d_rgb,
-                                             unsigned long long *d_hit_total, void *stream)
+                                             unsigned long long *d_hit_total, const lh_tex_args_t *tex, void *stream)
 {
     const size_t total = (size_t)w * h;
     if (total == 0) return 0;
+    if (tex)
+        hipLaunchKernelGGL(k_dirt_resolve_tex, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           w, h, band_rows, xs, ys, N, near_clip, far_clip, d_slot_of_sample, d_t, d_rgb, d_hit_total, *tex);
+    else
     hipLaunchKernelGGL(k_dirt_resolve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        w, h, band_rows, xs, ys, N, near_clip, far_clip, d_slot_of_sample, d_t, d_rgb, d_hit_total);
     return hipGetLastError() == hipSuccess ? 0 : -1;

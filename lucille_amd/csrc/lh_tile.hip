@@ -242,6 +242,10 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     }
     if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
     const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->tile_dirt_t};
+    /* material textures (lh_tex.h): with at least one set, the resolve multiplies; with none, tex is NULL and the launch is the one it always was */
+    if (a->ntex && lh_tex_sync(a) != 0) return -1;
+    lh_tex_args_t tex_store;
+    const lh_tex_args_t *tex = lh_tex_args(a, r_prim, r_u, r_v, &tex_store);
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
@@ -269,12 +273,12 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     auto resolve = [&](bool from_counts) -> int {
         if (dirt) {
             if (lh_render_launch_dirt_resolve(w, h, band_rows, ps, ps, g.N, dirt->near_clip, dirt->far_clip, (const uint32_t *)b->slot.p,
-                                              (const double *)dstage.ts->t.p, (float *)d_rgb, a->d_total, s) != 0)
+                                              (const double *)dstage.ts->t.p, (float *)d_rgb, a->d_total, tex, s) != 0)
                 return fail("dirt resolve kernel launch failed");
             return 0;
         }
         if (lh_render_launch_resolve(w, h, band_rows, ps, ps, g.N, (const uint32_t *)b->slot.p, (const uint8_t *)b->occ.p,
-                                     from_counts ? (const unsigned int *)b->occcount.p : NULL, (float *)d_rgb, a->d_total, s) != 0)
+                                     from_counts ? (const unsigned int *)b->occcount.p : NULL, (float *)d_rgb, a->d_total, tex, s) != 0)
             return fail("resolve kernel launch failed");
         return 0;
     };
@@ -332,7 +336,7 @@ extern "C" int lh_render_ao_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, 
     return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
 }
 
-/* ri_transport_dirtmap per camera sample (dirtmap.c:234-292, without the texture multiply): a miss gives 0, a hit its dirt value */
+/* ri_transport_dirtmap per camera sample (dirtmap.c:234-292): a miss gives 0, a hit its dirt value, times the texture of its mesh where it has one */
 extern "C" int lh_render_dirt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, int gather_nsamples,
                                    const lh_dirt_params_t *params, uint64_t seed, const void *d_uniforms, void *d_rgb,
                                    lh_tile_stats_t *stats, void *stream)
@@ -728,6 +732,11 @@ static int sync_materials(lh_accel_t *a)
         HIPCHK(hipMemcpy(a->d_materials, packed.data(), packed.size(), hipMemcpyHostToDevice));
         a->materials_dirty = 0;
     }
+    return lh_ensure_prim_mesh(a);
+}
+
+int lh_ensure_prim_mesh(lh_accel_t *a)
+{
     if (!a->d_prim_mesh && a->hs->bvh.ntris) {
         HIPCHK(hipMalloc(&a->d_prim_mesh, sizeof(uint32_t) * (size_t)a->hs->bvh.ntris));
         HIPCHK(hipMemcpy(a->d_prim_mesh, a->hs->bvh.prim_geom, sizeof(uint32_t) * (size_t)a->hs->bvh.ntris, hipMemcpyHostToDevice));
