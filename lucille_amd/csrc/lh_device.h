@@ -103,6 +103,11 @@ enum {
 #define LH_DUMP_BUDGET    2048u        /* ... of ray-dump launches (incoherent rays: ages run to several times the steps) */
 #define LH_DUMP_MIN_ACTIVE 24           /* ray dumps over the 4-wide nodes: regroup below this many working lanes ... */
 #define LH_DUMP_TRI_BATCH  8            /* ... and pass over the parked leaves once this many lanes hold one (lh_query.hip lh_launch) */
+#define LH_ORDERED_MIN_ACTIVE 40        /* the ordered copy of a large plain dump over the 4-wide nodes (lh_order.h; closest and any hit): with its nodes coming from L2 the walk waits less and
+                                         * issues more of the time, and fuller node steps and triangle passes pay where the emptier ones of 24 / 8 did not -- S-soup-1M, 100 M rays, dump and passes:
+                                         * closest hit 40.42 -> 37.23 ms, any hit 33.29 -> 30.67 ms; the grid 24 .. 56 x 8 .. 24 is flat around this pair (tools/ordered_knob_sweep.py,
+                                         * profiles/ordered_walk.md).  A dump traced as given keeps 24 / 8 */
+#define LH_ORDERED_TRI_BATCH  20
 #define LH_DUMP8_MIN_ACTIVE 40          /* ray dumps over the 8-wide nodes (scenes beyond the Infinity Cache): S-soup-10M, 50 M rays, 1 787 -> 1 821 Mrays/s closest hit, 2 796 -> 2 875 any hit
                                          * against 32 / 12 (tools/experiments/knob_sweep7.py, r05); 24 / 8, the 4-wide dumps' pair, loses 2 % here */
 #define LH_DUMP8_TRI_BATCH  20

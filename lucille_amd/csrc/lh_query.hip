@@ -216,6 +216,8 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
         const uint32_t octant = a->dump_order_bits == 1u;          /* the two 6-bit keys: one bit per axis under the octant, two bits per axis alone */
         char *ws = (char *)order_workspace(a, qk, lh_order_plan(n < step ? n : step, a->dump_order_bits, octant, closest));
         const lh_order_grid_t g = lh_order_grid(sc.grid_lo, sc.grid_step, a->dump_order_bits, octant);
+        /* the ordered copy over the 4-wide nodes has thresholds of its own (lh_device.h); a caller's knobs hold here as everywhere */
+        const int o_min_active = dump4 ? LH_ORDERED_MIN_ACTIVE : min_active, o_tri_batch = dump4 ? LH_ORDERED_TRI_BATCH : tri_batch;
         for (size_t off = 0; ws && off < n; off += step) {
             const lh_batch_t part = lh_batch_sub(b, 0u, off, n - off < step ? n - off : step);
             const lh_order_plan_t p = lh_order_plan(part.n, a->dump_order_bits, octant, closest);
@@ -223,7 +225,7 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
             if (lh_order_run(&p, &g, part.org, part.dir, ws, s) != 0) return fail("ordering a ray dump failed: %s", hipGetErrorString(hipGetLastError()));
             const lh_batch_t o = {part.n, b.mode, ws + p.org, ws + p.dir, closest ? ws + p.prim : NULL, closest ? ws + p.t : NULL, closest ? ws + p.u : NULL,
                                   closest ? ws + p.v : NULL, closest ? NULL : ws + p.occ, b.counters};
-            if (lh_launch_trace(&sc, &o, lh_next_cursor(a), variant, a->grid_blocks, min_active, tri_batch, &a->aoq[qk].q, a->ncus, (void *)s) != 0 ||
+            if (lh_launch_trace(&sc, &o, lh_next_cursor(a), variant, a->grid_blocks, o_min_active, o_tri_batch, &a->aoq[qk].q, a->ncus, (void *)s) != 0 ||
                 lh_order_back(&p, closest ? 1 : 0, ws, part.prim, part.t, part.u, part.v, part.occ, s) != 0)
                 return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
             a->order_stat[0]++; a->order_stat[1] += part.n;
