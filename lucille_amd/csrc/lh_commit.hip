@@ -9,6 +9,7 @@
 
 #include "lh_internal.h"
 #include "lh_danger.h"
+#include "lh_plan.h"
 
 static thread_local char g_err[512] = "";
 
@@ -932,10 +933,7 @@ static int size_grid(lh_accel_t *a)
 {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, a->device));
-    const uint32_t stack = (uint32_t)lh_trace_rows(&a->dev);
-    int per_cu = (int)(160u / stack);                     /* LDS: stack KiB per 256-thread workgroup */
-    if (per_cu > 4) per_cu = 4;
-    if (per_cu < 1) per_cu = 1;
+    const int per_cu = (int)lh_plan_wgs_per_cu((uint32_t)lh_trace_rows(&a->dev));          /* lh_plan.h: what the top-of-tree copy counts on; at least 2 (64 rows at most) */
     a->grid_blocks = prop.multiProcessorCount * per_cu; a->ncus = prop.multiProcessorCount;
     const char *env = getenv("LH_GRID_BLOCKS");
     if (env && atoi(env) > 0) { a->grid_blocks = atoi(env); a->grid_user = 1; }

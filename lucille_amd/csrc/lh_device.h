@@ -94,7 +94,7 @@ enum {
 #define LH_TOP_AUTO       0xFFFFFFFFu  /* lh_dev_scene_t.top_nodes: as many as the CU's LDS leaves over beside the stack rows (the default) */
 #define LH_TOP_NODES_MAX  512u         /* 4-wide nodes a workgroup may keep in LDS behind its stack rows (32 KiB) */
 #define LH_ROWS_CHECKED   34u          /* ... of the checked walk: four workgroups per CU (4 x 34 KiB) and the cooperative walk's 17 KiB beside them; what every
-                                         launch of 65536 rays or more walks when its tree asks for more (rows4 in lh_kernels.hip) */
+                                         launch of 65536 rays or more walks when its tree asks for more (lh_plan_rows4 in lh_plan.h) */
 #define LH_NPART          8            /* cursor partitions of a persistent launch: one per XCD (each with its own L2) */
 #define LH_CURSOR_STRIDE  32           /* 32-bit words between two cursors: a 128-byte line each (device-scope atomics on one line serialise like atomics on
                                          one address) */
@@ -167,21 +167,39 @@ static inline lh_batch_t lh_batch_sub(lh_batch_t b, uint32_t io_fmt, size_t off,
     return b;
 }
 
-/* launchers implemented in lh_kernels.hip; stream is a hipStream_t.  d_cursor: the launch's LH_NPART persistent cursors */
-int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, unsigned long long *d_cursor,
-                    int variant, int grid_blocks, int min_active, int tri_batch,
-                    const lh_fixq_t *q, int ncus, void *stream);
-int lh_launch_trace_ao(const lh_dev_scene_t *sc, size_t nslots, int ntheta, int nphi, unsigned long long seed,
-                       const double *d_hitrec, const unsigned long long *d_slot_key, unsigned int *d_occ_count,
-                       unsigned long long *d_counters, unsigned long long *d_cursor, int grid_blocks, int min_active,
-                       int tri_batch, const lh_fixq_t *q, int ncus, const unsigned long long *d_nslots, uint32_t budget_big, void *stream);
+/* what every persistent launch is handed beside its scene and its rays: the launch's block of LH_NPART persistent cursors, the grid, the walk's knobs,
+ * the stream's fix-up queue (NULL: none) and the stream (a hipStream_t) */
+typedef struct lh_launch_ctx {
+    unsigned long long *d_cursor;
+    int         grid_blocks, min_active, tri_batch;
+    const lh_fixq_t *q;
+    int         ncus;
+    void       *stream;
+} lh_launch_ctx_t;
+
+/* the rays a fused stage makes in its kernel: ntheta x nphi gather rays of each of nslots hit records.  d_nslots (or NULL): the slot count on the
+ * device -- nslots is then its upper bound (the samples of the batch), the buffers are sized for it and the kernels read the count themselves: no
+ * host round trip between the compaction and the stage; budget_big: 0, or the visit budget of a launch that turns out to hold 2^27 rays or more */
+typedef struct lh_gather_src {
+    size_t      nslots;
+    int         ntheta, nphi;
+    unsigned long long seed;
+    const double *d_hitrec;
+    const unsigned long long *d_slot_key;
+    const unsigned long long *d_nslots;
+    uint32_t    budget_big;
+} lh_gather_src_t;
+
+/* launchers implemented in lh_kernels.hip; their geometry: lh_plan.h */
+int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, int variant, const lh_launch_ctx_t *ctx);
+/* the fused AO stage: occluded rays counted per slot in d_occ_count */
+int lh_launch_trace_ao(const lh_dev_scene_t *sc, const lh_gather_src_t *src, unsigned int *d_occ_count, unsigned long long *d_counters,
+                       const lh_launch_ctx_t *ctx);
 /* ... and the dirt stage's: closest hit under the one bound far_clip, the t of ray (slot, r)'s bounded record at element slot * N + r of d_t */
-int lh_launch_trace_dirt(const lh_dev_scene_t *sc, size_t nslots, int ntheta, int nphi, unsigned long long seed,
-                         const double *d_hitrec, const unsigned long long *d_slot_key, double far_clip, double *d_t,
-                         unsigned long long *d_counters, unsigned long long *d_cursor, int grid_blocks, int min_active,
-                         int tri_batch, const lh_fixq_t *q, int ncus, const unsigned long long *d_nslots, uint32_t budget_big, void *stream);
-int lh_trace_formats_needed(const lh_dev_scene_t *sc, int variant);
-int lh_trace_rows(const lh_dev_scene_t *sc);        /* LDS stack rows the default walk launches with on this scene */
+int lh_launch_trace_dirt(const lh_dev_scene_t *sc, const lh_gather_src_t *src, double far_clip, double *d_t, unsigned long long *d_counters,
+                         const lh_launch_ctx_t *ctx);
+int lh_trace_formats_needed(int variant);
+int lh_trace_rows(const lh_dev_scene_t *sc);        /* LDS stack rows the default walk launches with on this scene (lh_plan.h) */
 
 #ifdef __cplusplus
 }

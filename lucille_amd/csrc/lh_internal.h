@@ -5,6 +5,8 @@
  *   lh_commit.hip   lifetime: create / add meshes / commit (host or device build) / replicas / destroy / parameters
  *   lh_query.hip    ray queries: device, host and pipelined host batches, statistics, beam visibility; lh_launch(accel, batch, ...), the
  *                   one way a batch of rays (lh_batch_t) reaches the kernels' launcher (lh_kernels.hip lh_launch_trace)
+ *   lh_plan.h       the geometry of a persistent launch (rows, checked pushes, the top of the tree in LDS, workgroups per CU, the cooperative
+ *                   walk beside it, the cursor chunk): plain C, read by the launchers, by size_grid and by tests/cpu_model/lh_plan_check.c
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
  */
 #ifndef LH_INTERNAL_H

@@ -51,6 +51,7 @@
 
 #include "../../include/lucille_hip.h"
 #include "lh_device.h"
+#include "lh_plan.h"
 #include "lh_filter.h"
 #include "lh_reftrace.h"
 #include "lh_tmax.h"
@@ -775,6 +776,17 @@ __device__ __forceinline__ void trace_persist_lane(
     }
 }
 
+/* the workgroup's copy of the top of the tree (the first sc.top_nodes 4-wide nodes; lh_plan.h) behind its stack rows, before the walk begins */
+__device__ __forceinline__ void copy_tree_top(const lh_dev_scene_t &sc, int *lh_stack_lds)
+{
+    if (sc.top_nodes) {
+        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
+        const uint4 *src = (const uint4 *)sc.q4nodes;
+        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
+        __syncthreads();
+    }
+}
+
 template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false>
 __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_lane(
     lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
@@ -785,12 +797,7 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_l
     extern __shared__ int lh_stack_lds[];          /* [stack entries][LH_BLOCK], sized at launch; then the top of the tree (sc.top_nodes x 64 bytes) */
     if (SRC != 1 && sc.n_dev) n = *sc.n_dev;       /* the path tracer's bounce chain: the count the previous shading pass left */
     if (SRC == 1 && ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* the fused AO stage behind a compaction nobody read back (<= the host's bound < 2^31) */
-    if (WALK != 7 && sc.top_nodes) {
-        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
-        const uint4 *src = (const uint4 *)sc.q4nodes;
-        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
-        __syncthreads();
-    }
+    if (WALK != 7) copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<ANYHIT, COUNT, WALK, SRC, IO>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
@@ -805,12 +812,7 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_i
 {
     extern __shared__ int lh_stack_lds[];
     if (sc.n_dev) { const uint32_t c = *sc.n_dev; if (c < n) n = c; }      /* min(*d_count, n_index) */
-    if (WALK != 7 && sc.top_nodes) {
-        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
-        const uint4 *src = (const uint4 *)sc.q4nodes;
-        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
-        __syncthreads();
-    }
+    if (WALK != 7) copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
 }
 
@@ -825,12 +827,7 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_t
 {
     extern __shared__ int lh_stack_lds[];
     if (sc.n_dev) { const uint32_t c = *sc.n_dev; if (c < n) n = c; }      /* min(*d_count, n_index) */
-    if (WALK != 7 && sc.top_nodes) {
-        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
-        const uint4 *src = (const uint4 *)sc.q4nodes;
-        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
-        __syncthreads();
-    }
+    if (WALK != 7) copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
 }
 
@@ -842,12 +839,7 @@ __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_dirt(
 {
     extern __shared__ int lh_stack_lds[];
     if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
-    if (sc.top_nodes) {
-        uint4 *dst = (uint4 *)(lh_stack_lds + (size_t)sc.stack_rows * LH_BLOCK);
-        const uint4 *src = (const uint4 *)sc.q4nodes;
-        for (uint32_t k = threadIdx.x; k < sc.top_nodes * 4u; k += LH_BLOCK) dst[k] = src[k];
-        __syncthreads();
-    }
+    copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<false, COUNT, WALK, 1, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
@@ -1348,63 +1340,88 @@ __global__ __launch_bounds__(64) void k_trace_small_tmax(lh_dev_scene_t sc, uint
     trace_small_body<ANYHIT, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters);
 }
 
-/* a workgroup's LDS stack beyond 64 KiB (trees deeper than 19 four-wide levels: up to LH_ROWS_UNCHECKED rows) has to be
- * allowed per kernel function, once */
-static int allow_lds(const void *func, size_t bytes)
+/* ---- launchers: what is launched with how many rows, how much of the tree's top, which chunk is lh_plan.h's to say ---------------- */
+
+/* a kernel's dynamic LDS beyond 64 KiB has to be allowed per kernel function, on the device it is launched on: raised to the bytes asked for, once per
+ * (current device, function).  Only the cooperative walk asks (a ring of 256 or 512 rows: trees deeper than 40 four-wide levels): no plan gives a
+ * persistent workgroup more than 64 KiB (tests/test_launch_plan.py) */
+int allow_lds(const void *func, size_t bytes)
 {
-    static const void *done[64]; static int ndone = 0; static pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
-    if (bytes <= 64 * 1024) return 0;
+    static struct { int dev; const void *func; size_t bytes; } done[256];
+    static int ndone = 0; static pthread_mutex_t mu = PTHREAD_MUTEX_INITIALIZER;
+    if (bytes <= LH_WG_LDS_BYTES) return 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
     pthread_mutex_lock(&mu);
-    bool have = false;
-    for (int k = 0; k < ndone; k++) have = have || done[k] == func;
-    int rc = 0;
-    if (!have) {
-        rc = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LH_ROWS_UNCHECKED * LH_BLOCK * sizeof(int) + LH_TOP_NODES_MAX * 64u)) == hipSuccess ? 0 : -1;
-        if (rc == 0 && ndone < 64) done[ndone++] = func;
+    int k = 0, rc = 0;
+    while (k < ndone && (done[k].dev != dev || done[k].func != func)) k++;
+    if (k == ndone || done[k].bytes < bytes) {
+        rc = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
+        if (rc == 0 && k < 256) { done[k].dev = dev; done[k].func = func; done[k].bytes = bytes; if (k == ndone) ndone++; }      /* a full table: set again next time */
     }
     pthread_mutex_unlock(&mu);
     return rc;
 }
-#define LH_LAUNCH_PERSIST(KERNEL, ...) do { if (allow_lds((const void *)(KERNEL), lds_bytes) != 0) return -1; \
-                                            hipLaunchKernelGGL((KERNEL), dim3(grid_blocks), dim3(LH_BLOCK), lds_bytes, s, __VA_ARGS__); } while (0)
+#define LH_LAUNCH_PERSIST(KERNEL, ...) hipLaunchKernelGGL((KERNEL), dim3(c.grid_blocks), dim3(LH_BLOCK), p.lds_bytes, s, __VA_ARGS__)
 
 /* a batch's ray and record arrays as the kernels take them: loose typed pointers, in every kernel's order */
 #define LH_BATCH_ARRAYS(B) (const double *)(B).org, (const double *)(B).dir, (uint32_t *)(B).prim, (double *)(B).t, (double *)(B).u, \
                            (double *)(B).v, (uint8_t *)(B).occ
 
-/* the batch's main kernel: walk 0 the textbook walk, 3 / 8 the 4-wide nodes (8: checked pushes), 7 the 8-wide nodes.  The instantiation
+/* the plan onto the launch's own scene copy; -1: a launch the plan refuses */
+int apply_plan(lh_dev_scene_t &scl, const lh_plan_t &p)
+{
+    if (p.err != LH_PLAN_OK) return -1;
+    scl.stack_rows = p.rows; scl.stack_guard = p.guard; scl.top_nodes = p.top_nodes;
+    scl.ray_chunk = p.ray_chunk; scl.ray_budget = p.ray_budget;
+    if (p.walk == LH_WALK_Q4 || p.walk == LH_WALK_Q4_CHECKED) scl.prefer_q8 = 0;
+    return 0;
+}
+
+/* what every persistent launch does before its main kernel: the cursors to zero, the kernels' view of the stream's fix-up queue -- which takes rays
+ * only where the cooperative walk runs beside the launch (coop) -- the queue back to empty (stream-ordered), and the point the consumer's stream waits for */
+int persist_begin(const lh_launch_ctx_t &c, bool coop, FixQ *fq, hipStream_t s)
+{
+    const lh_fixq_t *q = c.q;
+    *fq = FixQ{coop ? (unsigned long long *)q->queue : NULL, q->qcount, coop ? q->qcap : 0u, (uint32_t)c.grid_blocks * (LH_BLOCK / 64), q->qcount + 4};
+    if (hipMemsetAsync(c.d_cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_fixq_reset, dim3(1), dim3(256), 0, s, (unsigned long long *)q->queue, q->qcount, q->qcap);
+    if (hipGetLastError() != hipSuccess) return -1;
+    return hipEventRecord((hipEvent_t)q->ev_ready, s) == hipSuccess ? 0 : -1;
+}
+
+/* the batch's main kernel by the plan's walk: the textbook walk, the 4-wide nodes (with or without checked pushes), the 8-wide nodes.  The instantiation
  * follows the batch (any hit, counted) and the launch's scene: camera rays (SRC 2), a list of ray ids, fp32 rays / 16-byte records (IO) */
-int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, unsigned long long *cursor, int walk,
-                int grid_blocks, int min_active, int tri_batch, size_t lds_bytes, const FixQ &fq, hipStream_t s)
+int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, const lh_plan_t &p, const lh_launch_ctx_t &c, const FixQ &fq, hipStream_t s)
 {
     auto launch = [&](auto anyhit_c, auto count_c) -> int {
         constexpr bool ANYHIT = decltype(anyhit_c)::value, COUNT = decltype(count_c)::value;
-        if (walk == 0) {
+        if (p.walk == LH_WALK_DIRECT) {
             const size_t blocks = (b.n + LH_BLOCK - 1) / LH_BLOCK;
             if (blocks > 0x7fffffffull) return -1;
-            hipLaunchKernelGGL((k_trace_direct<ANYHIT, COUNT>), dim3((unsigned)blocks), dim3(LH_BLOCK), lds_bytes, s,
+            hipLaunchKernelGGL((k_trace_direct<ANYHIT, COUNT>), dim3((unsigned)blocks), dim3(LH_BLOCK), p.lds_bytes, s,
                                sc, b.n, LH_BATCH_ARRAYS(b), b.counters);
         } else {
-            if (hipMemsetAsync(cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
-            /* the instantiations of this batch, by ray source and by walk (w: 7, 8, 3); the compiler emits the kernels in the order they are first
+            /* the instantiations of this batch, by ray source and by walk (w: 8-wide, checked, 4-wide); the compiler emits the kernels in the order they are first
              * named here, so a reordering shows up in a comparison of the device code */
-            using lane_t = decltype(&k_trace_persist_lane<ANYHIT, COUNT, 3, 0>);
-            using indexed_t = decltype(&k_trace_persist_indexed<ANYHIT, COUNT, 3>);
-            const int w = walk == 7 ? 0 : walk == 8 ? 1 : 2;
-            const lane_t cam = walk == 8 ? k_trace_persist_lane<false, COUNT, 8, 2> : k_trace_persist_lane<false, COUNT, 3, 2>;      /* ray source 2: closest hit over the 4-wide nodes only (lh_launch_trace checks) */
-            const indexed_t indexed[3] = {k_trace_persist_indexed<ANYHIT, COUNT, 7>, k_trace_persist_indexed<ANYHIT, COUNT, 8>, k_trace_persist_indexed<ANYHIT, COUNT, 3>};
-            const lane_t io[3] = {k_trace_persist_lane<ANYHIT, COUNT, 7, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, 8, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, 3, 0, true>};
-            const lane_t f64[3] = {k_trace_persist_lane<ANYHIT, COUNT, 7, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, 8, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, 3, 0, false>};
+            using lane_t = decltype(&k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4, 0>);
+            using indexed_t = decltype(&k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q4>);
+            const int w = p.walk == LH_WALK_Q8 ? 0 : p.walk == LH_WALK_Q4_CHECKED ? 1 : 2;
+            const lane_t cam = p.walk == LH_WALK_Q4_CHECKED ? k_trace_persist_lane<false, COUNT, LH_WALK_Q4_CHECKED, 2> : k_trace_persist_lane<false, COUNT, LH_WALK_Q4, 2>;      /* ray source 2: closest hit over the 4-wide nodes only (lh_launch_trace checks) */
+            const indexed_t indexed[3] = {k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q8>, k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q4_CHECKED>, k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q4>};
+            const lane_t io[3] = {k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q8, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4_CHECKED, 0, true>, k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4, 0, true>};
+            const lane_t f64[3] = {k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q8, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4_CHECKED, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4, 0, false>};
+            uint32_t *cursor = (uint32_t *)c.d_cursor;
             if (sc.tmax) {                       /* a bounded ray dump: an indexed launch whose rays carry a bound each (named last: the kernels above keep their order) */
-                const indexed_t bounded[3] = {k_trace_persist_tmax<ANYHIT, COUNT, 7>, k_trace_persist_tmax<ANYHIT, COUNT, 8>, k_trace_persist_tmax<ANYHIT, COUNT, 3>};
+                const indexed_t bounded[3] = {k_trace_persist_tmax<ANYHIT, COUNT, LH_WALK_Q8>, k_trace_persist_tmax<ANYHIT, COUNT, LH_WALK_Q4_CHECKED>, k_trace_persist_tmax<ANYHIT, COUNT, LH_WALK_Q4>};
                 if (!sc.idx_nrays || sc.cam_src) return -1;
-                LH_LAUNCH_PERSIST(bounded[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor, min_active, tri_batch, fq);
+                LH_LAUNCH_PERSIST(bounded[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, cursor, c.min_active, c.tri_batch, fq);
             } else
             if (sc.idx_nrays && !sc.cam_src)        /* an indexed ray dump: the list is read in the refill */
-                LH_LAUNCH_PERSIST(indexed[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor, min_active, tri_batch, fq);
+                LH_LAUNCH_PERSIST(indexed[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, cursor, c.min_active, c.tri_batch, fq);
             else                                 /* io_fmt: fp32 rays / 16-byte records, the instantiations that read and write them (IO) */
-                LH_LAUNCH_PERSIST(sc.cam_src ? cam : sc.io_fmt ? io[w] : f64[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, (uint32_t *)cursor,
-                                  min_active, tri_batch, AoSrc{}, fq);
+                LH_LAUNCH_PERSIST(sc.cam_src ? cam : sc.io_fmt ? io[w] : f64[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, cursor,
+                                  c.min_active, c.tri_batch, AoSrc{}, fq);
         }
         return hipGetLastError() == hipSuccess ? 0 : -1;
     };
@@ -1413,103 +1430,26 @@ int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, unsigned long lon
     return b.counters ? launch(no, yes) : launch(no, no);
 }
 
-/* LDS stack rows of a 4-wide walk over this scene.  3 * depth + 5 (or the builder's count of the deepest path) covers every
- * ray, but a launch that fills the chip is bound by rays in flight, and 128 VGPRs allow FOUR workgroups per CU: so a big launch
- * (`dense`) walks at most LH_ROWS_CHECKED rows -- four workgroups and the cooperative walk's in a CU's 160 KiB -- with a check
- * before every push, and the rare ray that would overrun its column goes to the cooperative walk.  Config-5 frame (the tree
- * asks for 59 rows: two workgroups per CU): 85.6 ms unchecked, 61.9 at 34 checked rows; S-soup-1M dump (44 rows: three) 2 234 ->
- * 2 278 Mrays/s.  (Rounds 2-3 measured the opposite for the frame -- 91 against 87 ms -- because the cooperative pass beside
- * the launch, which cannot be resident next to four 128-VGPR workgroups, kept its share of the queue after the launch had ended:
- * k_coop_walk.)  Small batches keep unchecked rows (up to 64): a handful of waves fills nothing, and without a queue an
- * overrunning ray would be left to k_fixups' sequential walk.  "stack_cap" forces a cap (8 .. 64). */
-uint32_t rows4(const lh_dev_scene_t &sc, bool *guard, bool dense = true)
-{
-    uint32_t need = sc.q4_stack ? sc.q4_stack : 3 * sc.q4_depth + 5;      /* the builder's own count of the deepest path, or the bound of any tree that deep */
-    const uint32_t cap = (sc.stack_cap >= 8 && sc.stack_cap <= LH_ROWS_UNCHECKED) ? sc.stack_cap
-                       : ((dense || need > LH_ROWS_UNCHECKED) ? LH_ROWS_CHECKED : LH_ROWS_UNCHECKED);
-    *guard = need > cap;
-    if (need > cap) need = cap;
-    need = (need + 1u) & ~1u;
-    if (need < 16 && !*guard) need = 16;
-    return need;
-}
-
-/* the cooperative walk's ring of stack rows: a power of two covering the tree's worst case (3 per level + sentinel + the
- * step's scratch slots); 0: the tree is deeper than any builder hands over */
-uint32_t coop_rows(const lh_dev_scene_t &sc)
-{
-    const uint32_t need = 3 * sc.q4_depth + 6;
-    uint32_t r = 16;
-    while (r < need) r <<= 1;
-    return r <= 512 ? r : 0;
-}
-
-/* nodes of the top of the tree a workgroup keeps in LDS behind its `rows` stack rows (node_step4): what the CU's 160 KiB leave
- * over once the workgroups its stack rows allow are resident -- never a workgroup fewer for it.  Measured (tools/top_probe.py,
- * r04): S-soup-1M 2 228 -> 2 249 Mrays/s on the host builder's tree, 2 212 -> 2 233 on the device builder's (144 nodes = 6.3 of a
- * ray's 42.5 node visits), config-5 AO frame 86.8 -> 86.2 ms: the requests that leave the CU for the hot top levels are not what
- * bounds the walk (profiles/README.md r04), so the gain is small; it is free.  sc.top_nodes: LH_TOP_AUTO, 0 (off), or a count. */
-uint32_t top_nodes_for(const lh_dev_scene_t &sc, uint32_t rows)
-{
-    uint32_t want = sc.top_nodes;
-    if (want == 0u) return 0u;
-    /* the CU's 160 KiB also hold the workgroup of the cooperative walk that runs NEXT TO this launch (k_coop_walk: one wave,
-     * a ring of coop_rows x 64 entries): its stream has the higher priority, so it is placed first -- a persistent workgroup
-     * that no longer fits beside it is one workgroup per CU fewer for the whole launch (r04: 2 240 -> 1 680 Mrays/s, the
-     * config-5 frame 85 -> 128 ms with every spare byte given to the top of the tree).  A count set by the caller is held to
-     * the same room (512 nodes beside 34 dense rows made 4 x 43 KiB and silently dropped a workgroup per CU) */
-    const uint32_t crows = coop_rows(sc);
-    const uint32_t coop = crows ? (crows * 64u + 128u) * (uint32_t)sizeof(int) + 1024u : 0u;
-    const uint32_t cu = 160u * 1024u - coop, stack = rows * LH_BLOCK * (uint32_t)sizeof(int);
-    uint32_t wgs = (160u * 1024u) / stack;      /* what size_grid() launches per CU */
-    if (wgs > 4u) wgs = 4u;                     /* 128 VGPRs: four workgroups per CU at most */
-    if (wgs == 0u || cu < wgs * stack) return 0u;
-    uint32_t spare = (cu / wgs - stack) / 64u;
-    /* a workgroup above 64 KiB of LDS halves what a CU holds (lh_device.h): the copy never takes a launch across that line (the
-     * small launches' up to 64 unchecked rows are 64 KiB by themselves: no copy there) */
-    if (stack <= 64u * 1024u) { const uint32_t room = (64u * 1024u - stack) / 64u; if (spare > room) spare = room; }
-    if (spare > LH_TOP_NODES_MAX) spare = LH_TOP_NODES_MAX;
-    if (want == LH_TOP_AUTO || want > spare) want = spare;
-    want &= ~15u;
-    return want < sc.nq4nodes ? want : sc.nq4nodes;
-}
-
-/* rays per cursor atomic: the scene's setting, but never so large that a wave gets fewer than
- * ~4 ranges of a small batch (tail imbalance: late path-tracing bounces, small tiles) */
-void clamp_chunk(lh_dev_scene_t &scl, size_t n, int grid_blocks)
-{
-    const size_t waves = (size_t)(grid_blocks > 0 ? grid_blocks : 1) * (LH_BLOCK / 64);
-    size_t c = n / (waves * 4);
-    if (c < 64) c = 64;
-    if (c < scl.ray_chunk) scl.ray_chunk = (uint32_t)c;
-    if (scl.ray_chunk == 0) scl.ray_chunk = 64;
-}
-
 /* the cooperative walk over the fix-up queue of the persistent launch just enqueued on s.  It runs on the queue's second
  * stream, CONCURRENTLY with that launch (a few small workgroups per CU next to the persistent ones: its low efficiency --
  * one ray per 16 lanes, restarted from the root -- is hidden behind the bulk of the frame), submitted AFTER it: if the two
  * streams share a hardware queue it simply runs afterwards. */
 template <bool ANYHIT, int SRC, bool TMAX = false>
-int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_fixq_t *q, int ncus, hipStream_t s)
+int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p, const lh_launch_ctx_t &c, hipStream_t s)
 {
     /* the pass next to the producer (owner_groups 0) and the sweep behind it */
-#define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL(kern, dim3(GRID), dim3(64), lds, STREAM, scl, LH_BATCH_ARRAYS(b), \
+#define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL(kern, dim3(GRID), dim3(64), p.coop_lds_bytes, STREAM, scl, LH_BATCH_ARRAYS(b), \
                                                                       ao, fq, b.counters, OWNER_GROUPS)
     constexpr bool DIRT = TMAX && SRC == 1 && !ANYHIT;          /* the fused dirt stage */
     auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
     if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
     if (DIRT) kern = k_coop_walk_dirt;
     lh_dev_scene_t scl = sc;
-    scl.stack_rows = coop_rows(sc);
-    if (scl.stack_rows == 0) return -1;
-    const size_t lds = ((size_t)scl.stack_rows * 64 + 128 + 64) * sizeof(int);          /* the stack ring, 2 x 64 exchange words, 4 x 16 stashed reference-walk entries */
-    static bool attr_set[2][5] = {{false, false, false, false, false}, {false, false, false, false, false}};          /* [3]: the bounded launches' kernel, [4]: the dirt stage's */
-    if (lds > 64 * 1024 && !attr_set[ANYHIT][DIRT ? 4 : TMAX ? 3 : SRC]) {
-        if (hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        attr_set[ANYHIT][DIRT ? 4 : TMAX ? 3 : SRC] = true;
-    }
+    scl.stack_rows = p.coop_rows;
+    if (allow_lds((const void *)kern, p.coop_lds_bytes) != 0) return -1;
+    const lh_fixq_t *q = c.q;
     hipStream_t aux = (hipStream_t)q->aux_stream;
-    int grid = ncus > 0 ? ncus : 256;                      /* one wave per workgroup and CU, 4 rays per wave */
+    int grid = c.ncus > 0 ? c.ncus : 256;                      /* one wave per workgroup and CU, 4 rays per wave */
     if (grid * 4 > (int)LH_Q_GROUPS) grid = (int)LH_Q_GROUPS / 4;
     static int concurrent = -1;
     if (concurrent < 0) { const char *e = getenv("LH_COOP_CONCURRENT"); concurrent = (e && atoi(e) == 0) ? 0 : 1; }
@@ -1528,56 +1468,56 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-/* the queue back to empty (stream-ordered), and the point the consumer's stream waits for */
-int fixq_begin(const lh_fixq_t *q, hipStream_t s)
+/* what the two fused stages differ in beside their kernels: the chunk before the clamp and the tail of AoSrc */
+struct FusedStage { bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; };
+
+/* a fused stage: the gather rays of g.nslots hits, N = ntheta * nphi each, made inside the persistent kernel (SRC 1).  Rays that kernel does not
+ * finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative walk) -- go through the stream's
+ * fix-up queue (2 words per entry, count + overflow flag in qcount[0..1]) to k_coop_walk */
+int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const FusedStage &st, unsigned long long *d_counters, const lh_launch_ctx_t &c)
 {
-    hipLaunchKernelGGL(k_fixq_reset, dim3(1), dim3(256), 0, s, (unsigned long long *)q->queue, q->qcount, q->qcap);
+    hipStream_t s = (hipStream_t)c.stream;
+    const size_t n = g.nslots * (size_t)(g.ntheta * g.nphi);
+    if (n == 0) return 0;
+    if (n >= ((size_t)1 << 31) || (st.dirt && !st.dirt_t)) return -1;
+    if (g.d_nslots && st.group) return -1;            /* the grouped order needs the exact count on the host */
+    lh_dev_scene_t scl = *sc;
+    scl.ray_chunk = st.chunk;
+    const lh_plan_t p = lh_plan_launch(&scl, n, st.dirt ? LH_PLAN_DIRT : LH_PLAN_AO, LH_VARIANT_SPEC, c.grid_blocks, 1);
+    const AoSrc ao = {g.d_hitrec, g.d_slot_key, st.occ_count, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, st.group, g.d_nslots, g.budget_big, st.far_clip, st.dirt_t};
+    FixQ fq;
+    if (apply_plan(scl, p) != 0) return -1;
+    if (st.occ_count && hipMemsetAsync(st.occ_count, 0, sizeof(unsigned int) * g.nslots, s) != hipSuccess) return -1;      /* with the cursors' memset, before the stream's first kernel */
+    if (persist_begin(c, true, &fq, s) != 0) return -1;
+    /* the rays are made in the kernel; the answers counted per slot (AO), their t stored through ao (dirt) */
+    const lh_batch_t none = {n, st.dirt ? LH_MODE_CLOSEST : LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};
+    const int w = p.guard ? 0 : 1, k = d_counters ? 0 : 1;          /* the kernels below: checked pushes first, counted first */
+    if (!st.dirt) {
+        using ao_t = decltype(&k_trace_persist_lane<true, true, LH_WALK_Q4, 1>);
+        const ao_t kern[2][2] = {{k_trace_persist_lane<true, true, LH_WALK_Q4_CHECKED, 1>, k_trace_persist_lane<true, false, LH_WALK_Q4_CHECKED, 1>},
+                                 {k_trace_persist_lane<true, true, LH_WALK_Q4, 1>, k_trace_persist_lane<true, false, LH_WALK_Q4, 1>}};
+        LH_LAUNCH_PERSIST(kern[w][k], scl, (uint32_t)n, LH_BATCH_ARRAYS(none), d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
+        if (hipGetLastError() != hipSuccess) return -1;
+        return launch_coop<true, 1>(scl, none, ao, fq, p, c, s);
+    }
+    using dirt_t = decltype(&k_trace_persist_dirt<true, LH_WALK_Q4>);
+    const dirt_t kern[2][2] = {{k_trace_persist_dirt<true, LH_WALK_Q4_CHECKED>, k_trace_persist_dirt<false, LH_WALK_Q4_CHECKED>},
+                               {k_trace_persist_dirt<true, LH_WALK_Q4>, k_trace_persist_dirt<false, LH_WALK_Q4>}};
+    LH_LAUNCH_PERSIST(kern[w][k], scl, (uint32_t)n, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
     if (hipGetLastError() != hipSuccess) return -1;
-    return hipEventRecord((hipEvent_t)q->ev_ready, s) == hipSuccess ? 0 : -1;
+    return launch_coop<false, 1, true>(scl, none, ao, fq, p, c, s);
 }
 
 } /* namespace */
 
-/* the AO stage of a tile with the rays generated inside the any-hit kernel (SRC 1 above): nslots primary hits,
- * N = ntheta * nphi rays each, occluded rays counted per slot in d_occ_count (zeroed here).  Rays the persistent kernel
- * does not finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative
- * walk) -- go through d_queue (2 words per entry, count + overflow flag in d_qcount[0..1]) to k_coop_walk. */
-extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, size_t nslots, int ntheta, int nphi, unsigned long long seed,
-                                  const double *d_hitrec, const unsigned long long *d_slot_key, unsigned int *d_occ_count,
-                                  unsigned long long *d_counters, unsigned long long *d_cursor, int grid_blocks, int min_active,
-                                  int tri_batch, const lh_fixq_t *q, int ncus, const unsigned long long *d_nslots, uint32_t budget_big, void *stream)
+/* the AO stage of a tile with the rays generated inside the any-hit kernel (SRC 1 above): occluded rays counted per slot in d_occ_count (zeroed here) */
+extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, const lh_gather_src_t *src, unsigned int *d_occ_count, unsigned long long *d_counters,
+                                  const lh_launch_ctx_t *ctx)
 {
-    /* d_nslots (or NULL): the slot count on the device -- nslots is then its upper bound (the samples of the batch), the buffers
-     * are sized for it and the kernels read the count themselves: no host round trip between the compaction and this stage */
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n = nslots * (size_t)(ntheta * nphi);
-    if (n == 0) return 0;
-    if (n >= ((size_t)1 << 31)) return -1;
-    lh_dev_scene_t scl = *sc;
-    bool guard = false;
-    scl.stack_rows = rows4(*sc, &guard, n >= 65536);
-    scl.stack_guard = guard ? 1 : 0;
-    scl.top_nodes = top_nodes_for(*sc, scl.stack_rows);
-    const size_t lds_bytes = (size_t)scl.stack_rows * LH_BLOCK * sizeof(int) + (size_t)scl.top_nodes * 64u;
     static uint32_t ao_chunk = 0;
     if (!ao_chunk) { const char *e = getenv("LH_AO_CHUNK"); ao_chunk = (e && atoi(e) >= 64 && atoi(e) <= 65536) ? (uint32_t)atoi(e) : LH_TILE_CHUNK; }
-    scl.ray_chunk = ao_chunk;                                               /* AO rays of a slot are coherent: longer ranges per wave (LH_AO_CHUNK) */
-    clamp_chunk(scl, n, grid_blocks);
-    AoSrc ao = {d_hitrec, d_slot_key, d_occ_count, seed, ntheta, nphi, (uint32_t)nslots, (int)sc->ao_group, d_nslots, budget_big};
-    if (d_nslots && sc->ao_group) return -1;            /* the grouped order needs the exact count on the host */
-    FixQ fq = {(unsigned long long *)q->queue, q->qcount, q->qcap, (uint32_t)grid_blocks * (LH_BLOCK / 64), q->qcount + 4};
-    if (hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
-    if (hipMemsetAsync(d_occ_count, 0, sizeof(unsigned int) * nslots, s) != hipSuccess) return -1;
-    if (fixq_begin(q, s) != 0) return -1;
-#define LH_AO_LAUNCH(CNT, W) LH_LAUNCH_PERSIST((k_trace_persist_lane<true, CNT, W, 1>), \
-                           scl, (uint32_t)n, (const double *)NULL, (const double *)NULL, (uint32_t *)NULL, (double *)NULL, (double *)NULL, \
-                           (double *)NULL, (uint8_t *)NULL, d_counters, (uint32_t *)d_cursor, min_active, tri_batch, ao, fq)
-    if (guard) { if (d_counters) LH_AO_LAUNCH(true, 8); else LH_AO_LAUNCH(false, 8); }
-    else { if (d_counters) LH_AO_LAUNCH(true, 3); else LH_AO_LAUNCH(false, 3); }
-#undef LH_AO_LAUNCH
-    if (hipGetLastError() != hipSuccess) return -1;
-    const lh_batch_t none = {n, LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};          /* the rays are made in the kernel, the answers counted per slot */
-    return launch_coop<true, 1>(scl, none, ao, fq, q, ncus, s);
+    /* AO rays of a slot are coherent: longer ranges per wave (LH_AO_CHUNK) */
+    return launch_fused(sc, *src, FusedStage{false, ao_chunk, d_occ_count, (int)sc->ao_group, 0.0, NULL}, d_counters, *ctx);
 }
 
 /* the dirt stage (lh_dirt.h) the same way: the gather rays of nslots hits made inside a CLOSEST-hit kernel that walks them under the one bound
@@ -1585,60 +1525,33 @@ extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, size_t nslots, int n
  * goes through HBM.  Rays the persistent kernel does not finish go through the queue as above: out of budget or stack rows to the cooperative walk,
  * fragile hits (the mark of a hit near the bound among them) to the reference's own walk, whose unbounded record is filtered by t < far_clip; both
  * store the same word.  A queue overflow leaves words unwritten: the caller redoes the stage materialised */
-extern "C" int lh_launch_trace_dirt(const lh_dev_scene_t *sc, size_t nslots, int ntheta, int nphi, unsigned long long seed,
-                                    const double *d_hitrec, const unsigned long long *d_slot_key, double far_clip, double *d_t,
-                                    unsigned long long *d_counters, unsigned long long *d_cursor, int grid_blocks, int min_active,
-                                    int tri_batch, const lh_fixq_t *q, int ncus, const unsigned long long *d_nslots, uint32_t budget_big, void *stream)
+extern "C" int lh_launch_trace_dirt(const lh_dev_scene_t *sc, const lh_gather_src_t *src, double far_clip, double *d_t, unsigned long long *d_counters,
+                                    const lh_launch_ctx_t *ctx)
 {
-    hipStream_t s = (hipStream_t)stream;
-    const size_t n = nslots * (size_t)(ntheta * nphi);
-    if (n == 0) return 0;
-    if (n >= ((size_t)1 << 31) || !d_t) return -1;
-    lh_dev_scene_t scl = *sc;
-    bool guard = false;
-    scl.stack_rows = rows4(*sc, &guard, n >= 65536);
-    scl.stack_guard = guard ? 1 : 0;
-    scl.top_nodes = top_nodes_for(*sc, scl.stack_rows);
-    const size_t lds_bytes = (size_t)scl.stack_rows * LH_BLOCK * sizeof(int) + (size_t)scl.top_nodes * 64u;
-    scl.ray_chunk = LH_TILE_CHUNK;          /* the gather rays of a slot are coherent, as AO rays are */
-    clamp_chunk(scl, n, grid_blocks);
-    /* the plain item order (slot, sample): the grouped order is the AO stage's experiment */
-    AoSrc ao = {d_hitrec, d_slot_key, NULL, seed, ntheta, nphi, (uint32_t)nslots, 0, d_nslots, budget_big, far_clip, d_t};
-    FixQ fq = {(unsigned long long *)q->queue, q->qcount, q->qcap, (uint32_t)grid_blocks * (LH_BLOCK / 64), q->qcount + 4};
-    if (hipMemsetAsync(d_cursor, 0, sizeof(uint32_t) * LH_CURSOR_WORDS, s) != hipSuccess) return -1;
-    if (fixq_begin(q, s) != 0) return -1;
-#define LH_DIRT_LAUNCH(CNT, W) LH_LAUNCH_PERSIST((k_trace_persist_dirt<CNT, W>), scl, (uint32_t)n, d_counters, (uint32_t *)d_cursor, min_active, tri_batch, ao, fq)
-    if (guard) { if (d_counters) LH_DIRT_LAUNCH(true, 8); else LH_DIRT_LAUNCH(false, 8); }
-    else { if (d_counters) LH_DIRT_LAUNCH(true, 3); else LH_DIRT_LAUNCH(false, 3); }
-#undef LH_DIRT_LAUNCH
-    if (hipGetLastError() != hipSuccess) return -1;
-    const lh_batch_t none = {n, LH_MODE_CLOSEST, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};          /* the rays are made in the kernel, their t stored through ao */
-    return launch_coop<false, 1, true>(scl, none, ao, fq, q, ncus, s);
+    /* the gather rays of a slot are coherent, as AO rays are; the plain item order (slot, sample): the grouped order is the AO stage's experiment */
+    return launch_fused(sc, *src, FusedStage{true, LH_TILE_CHUNK, NULL, 0, far_clip, d_t}, d_counters, *ctx);
 }
 
-/* the node formats a launch of `variant` reads on this scene (bit mask, LH_FMT_* in lh_internal.h): so that the commit
- * code can upload a format the first time a variant asks for it */
 extern "C" int lh_trace_rows(const lh_dev_scene_t *sc)
 {
-    bool guard = false;
-    return (int)rows4(*sc, &guard);
+    return (int)lh_plan_trace_rows(sc);
 }
 
-extern "C" int lh_trace_formats_needed(const lh_dev_scene_t *sc, int variant)
+/* the node formats a launch of `variant` reads (bit mask, LH_FMT_* in lh_internal.h): so that the commit
+ * code can upload a format the first time a variant asks for it */
+extern "C" int lh_trace_formats_needed(int variant)
 {
-    (void)sc;
     return variant == LH_VARIANT_DIRECT ? 1 : 4;
 }
 
-/* one batch of rays (lh_batch_t: the rays, where the records go, the counters of a counted launch) through the hot path; d_cursor: the
+/* one batch of rays (lh_batch_t: the rays, where the records go, the counters of a counted launch) through the hot path; ctx->d_cursor: the
  * launch's block of persistent cursors.  variant: LH_VARIANT_SPEC (the default: 4-wide nodes, or the 8-wide nodes when
- * sc->prefer_q8) or LH_VARIANT_DIRECT (the textbook walk over the 2-wide fp32 nodes; needs sc->nodes).  q: the launch's
+ * sc->prefer_q8) or LH_VARIANT_DIRECT (the textbook walk over the 2-wide fp32 nodes; needs sc->nodes).  ctx->q: the launch's
  * fix-up queue with its second stream, private to the stream. */
-extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, unsigned long long *d_cursor,
-                               int variant, int grid_blocks, int min_active, int tri_batch,
-                               const lh_fixq_t *q, int ncus, void *stream)
+extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, int variant, const lh_launch_ctx_t *ctx)
 {
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)ctx->stream;
+    const lh_fixq_t *q = ctx->q;
     const lh_batch_t &b = *batch;
     const size_t n = b.n;
     const bool anyhit = b.mode == LH_MODE_ANY;
@@ -1649,13 +1562,12 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
         if (sc->idx_nrays) return -1;
         for (size_t off = 0; off < n; off += kMaxLaunch) {
             const lh_batch_t part = lh_batch_sub(b, sc->io_fmt, off, (n - off < kMaxLaunch) ? n - off : kMaxLaunch);
-            const int rc = lh_launch_trace(sc, &part, d_cursor, variant, grid_blocks, min_active, tri_batch, q, ncus, stream);
+            const int rc = lh_launch_trace(sc, &part, variant, ctx);
             if (rc != 0) return rc;
         }
         return 0;
     }
     lh_dev_scene_t scl = *sc;
-    uint32_t need; int walk; bool guard = false;
     if ((sc->cam_src || sc->n_dev) && (variant == LH_VARIANT_DIRECT || (anyhit && !sc->idx_nrays) || q == NULL)) return -1;      /* the path tracer's chain: default walk, closest hit; an indexed dump's count: either mode */
     if (sc->tmax && !sc->idx_nrays) return -1;          /* a bounded launch is an indexed one (a dense call: the identity list) */
     if (sc->idx_nrays && (variant == LH_VARIANT_DIRECT || sc->cam_src || sc->diag_out || n > kMaxLaunch)) return -1;       /* the list is read by the default walk's kernels only */
@@ -1670,54 +1582,27 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
     if (sc->diag_out) return -1;                 /* per-ray diagnostics exist for the default walk's nodes only */
-    if (variant == LH_VARIANT_DIRECT) {
-        if (!sc->nodes) return -1;
-        need = sc->max_depth + 2; walk = 0;          /* 2-wide: one push per level + the sentinel */
-        need = (need + 1u) & ~1u;
-        if (need < 16) need = 16;
-    } else if (scl.prefer_q8 && sc->q8nodes) {
-        /* the 8-wide walk pushes up to 7 per level and keeps a scratch row; beyond 48 rows (three workgroups per CU) the rare
-         * ray that needs them is finished by the cooperative walk over the 4-wide nodes (always resident) */
-        need = 7 * sc->q8_depth + 10; walk = 7;
-        const uint32_t cap = (sc->stack_cap >= 16 && sc->stack_cap < 64) ? sc->stack_cap : 48;
-        if (need > cap) { need = cap; guard = true; }
-        need = (need + 1u) & ~1u;
-        if (need < 16 && !guard) need = 16;
-        scl.stack_guard = guard ? 1 : 0;
-    } else {
-        /* a launch that fills the chip walks at most LH_ROWS_CHECKED rows (four workgroups per CU), a ray that would overrun
-         * them is finished by the cooperative walk; so does a very deep tree (chains of nested geometry, an LBVH over a
-         * degenerate distribution) whose worst case does not fit 64 rows -- rows4 */
-        scl.prefer_q8 = 0;
-        need = rows4(*sc, &guard, n >= 65536 || sc->n_dev != NULL); walk = guard ? 8 : 3;
-        scl.stack_guard = guard ? 1 : 0;
-    }
-    if (need > LH_ROWS_UNCHECKED) return -1;
-    scl.stack_rows = need;
-    scl.top_nodes = (walk == 0 || walk == 7) ? 0u : top_nodes_for(*sc, need);
-    const size_t lds_bytes = (size_t)need * LH_BLOCK * sizeof(int) + (size_t)scl.top_nodes * 64u;
-    clamp_chunk(scl, n, grid_blocks);
-    /* small batches (one synchronous ray, a bucket of lucille's renderer): no visit budget, no second stream -- a ray the walk
-     * cannot finish (LDS rows) stays flagged for k_fixups */
-    const bool coop = walk != 0 && q != NULL && (n >= 65536 || sc->n_dev != NULL);
-    FixQ fq = {coop ? (unsigned long long *)q->queue : NULL, q ? q->qcount : NULL, coop ? q->qcap : 0u, (uint32_t)grid_blocks * (LH_BLOCK / 64), q ? q->qcount + 4 : NULL};
-    if (!coop) scl.ray_budget = 0xFFFFFFFFu;
-    if (walk != 0 && q != NULL && fixq_begin(q, s) != 0) return -1;
-    if (walk != 0 && q == NULL) return -1;
-    int rc = launch_walk(scl, b, d_cursor, walk, grid_blocks, min_active, tri_batch, lds_bytes, fq, s);
+    if (variant == LH_VARIANT_DIRECT && !sc->nodes) return -1;
+    const lh_plan_t p = lh_plan_launch(sc, n, LH_PLAN_BATCH, variant, ctx->grid_blocks, q != NULL);
+    if (apply_plan(scl, p) != 0) return -1;
+    /* the textbook walk has neither cursors nor a queue; the persistent walks need the stream's */
+    FixQ fq = {};
+    if (p.walk != LH_WALK_DIRECT && (q == NULL || persist_begin(*ctx, p.coop != 0, &fq, s) != 0)) return -1;
+    int rc = launch_walk(scl, b, p, *ctx, fq, s);
     if (rc != 0) return rc;
-    if (coop) {
-        rc = sc->tmax ? (anyhit ? launch_coop<true, 0, true>(scl, b, AoSrc{}, fq, q, ncus, s) : launch_coop<false, 0, true>(scl, b, AoSrc{}, fq, q, ncus, s))
-             : anyhit ? launch_coop<true, 0>(scl, b, AoSrc{}, fq, q, ncus, s)
-             : sc->cam_src ? launch_coop<false, 2>(scl, b, AoSrc{}, fq, q, ncus, s)
-                    : launch_coop<false, 0>(scl, b, AoSrc{}, fq, q, ncus, s);
+    if (p.coop) {
+        rc = sc->tmax ? (anyhit ? launch_coop<true, 0, true>(scl, b, AoSrc{}, fq, p, *ctx, s) : launch_coop<false, 0, true>(scl, b, AoSrc{}, fq, p, *ctx, s))
+             : anyhit ? launch_coop<true, 0>(scl, b, AoSrc{}, fq, p, *ctx, s)
+             : sc->cam_src ? launch_coop<false, 2>(scl, b, AoSrc{}, fq, p, *ctx, s)
+                    : launch_coop<false, 0>(scl, b, AoSrc{}, fq, p, *ctx, s);
         if (rc != 0) return rc;
     }
     /* what is still flagged: fragile hits (the reference's own walk), and out-of-budget rays the queue had no room for */
     {
         const size_t blocks = (n + 255) / 256;
         hipLaunchKernelGGL(sc->tmax ? k_fixups_tmax : k_fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, LH_BATCH_ARRAYS(b),
-                           anyhit ? 1 : 0, b.counters, q ? q->qcount : NULL, (walk == 0 || q == NULL) ? 1 : 0);
+                           anyhit ? 1 : 0, b.counters, q ? q->qcount : NULL, (p.walk == LH_WALK_DIRECT || q == NULL) ? 1 : 0);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+

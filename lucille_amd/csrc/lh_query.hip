@@ -177,7 +177,7 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
         return fail("intersect: unknown variant %d (%d: the textbook reference walk, %d: the default)", variant, LH_VARIANT_DIRECT, LH_VARIANT_SPEC);
     /* a tree built on the device exists only as 4-wide nodes: the textbook walk runs as the default walk there */
     if (a->hs->device_built) variant = LH_VARIANT_SPEC;
-    if (lh_ensure_formats(a, lh_trace_formats_needed(&a->dev, variant)) != 0) return -1;     /* the textbook walk's nodes: uploaded on first use */
+    if (lh_ensure_formats(a, lh_trace_formats_needed(variant)) != 0) return -1;     /* the textbook walk's nodes: uploaded on first use */
     /* ray dumps (incoherent by assumption) over a scene whose hot set does not fit the 256 MiB Infinity Cache walk the 8-wide
      * nodes: each record then costs a 128-byte line of HBM traffic whatever its size, and an 8-wide record uses all of it
      * (S-soup-10M: 57 -> 40 records per ray).  The tile pipelines' coherent rays stay on the 4-wide nodes. */
@@ -203,6 +203,7 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
     const bool dump4 = dump && !q8 && !a->knobs_user;
     const bool dump8 = dump && q8 && !a->knobs_user;
     const int min_active = dump4 ? LH_DUMP_MIN_ACTIVE : dump8 ? LH_DUMP8_MIN_ACTIVE : a->min_active, tri_batch = dump4 ? LH_DUMP_TRI_BATCH : dump8 ? LH_DUMP8_TRI_BATCH : a->tri_batch;
+    lh_launch_ctx_t ctx = {NULL, a->grid_blocks, min_active, tri_batch, &a->aoq[qk].q, a->ncus, (void *)s};          /* d_cursor: a block of its own per launch */
     /* a large plain dump is traced from a copy in bin order (lh_order.h): each XCD's L2 then sees one region of the scene at a time.  Plain: fp64 rays
      * (on 16-byte boundaries: the count's loads; a dump that starts on an odd multiple of 8 bytes is traced as given) with fp64 records or any-hit bytes, the default walk, every ray of the arrays, no bound, no count on the device, no
      * diagnostics.  Everything else -- fp32 rays, 16-byte records, indexed and bounded dumps, the tile pipelines -- is traced as given, and so is a dump
@@ -217,7 +218,8 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
         char *ws = (char *)order_workspace(a, qk, lh_order_plan(n < step ? n : step, a->dump_order_bits, octant, closest));
         const lh_order_grid_t g = lh_order_grid(sc.grid_lo, sc.grid_step, a->dump_order_bits, octant);
         /* the ordered copy over the 4-wide nodes has thresholds of its own (lh_device.h); a caller's knobs hold here as everywhere */
-        const int o_min_active = dump4 ? LH_ORDERED_MIN_ACTIVE : min_active, o_tri_batch = dump4 ? LH_ORDERED_TRI_BATCH : tri_batch;
+        lh_launch_ctx_t octx = ctx;
+        if (dump4) { octx.min_active = LH_ORDERED_MIN_ACTIVE; octx.tri_batch = LH_ORDERED_TRI_BATCH; }
         for (size_t off = 0; ws && off < n; off += step) {
             const lh_batch_t part = lh_batch_sub(b, 0u, off, n - off < step ? n - off : step);
             const lh_order_plan_t p = lh_order_plan(part.n, a->dump_order_bits, octant, closest);
@@ -225,15 +227,16 @@ int lh_launch(lh_accel_t *a, const lh_batch_t &b, int variant, hipStream_t s, bo
             if (lh_order_run(&p, &g, part.org, part.dir, ws, s) != 0) return fail("ordering a ray dump failed: %s", hipGetErrorString(hipGetLastError()));
             const lh_batch_t o = {part.n, b.mode, ws + p.org, ws + p.dir, closest ? ws + p.prim : NULL, closest ? ws + p.t : NULL, closest ? ws + p.u : NULL,
                                   closest ? ws + p.v : NULL, closest ? NULL : ws + p.occ, b.counters};
-            if (lh_launch_trace(&sc, &o, lh_next_cursor(a), variant, a->grid_blocks, o_min_active, o_tri_batch, &a->aoq[qk].q, a->ncus, (void *)s) != 0 ||
+            octx.d_cursor = lh_next_cursor(a);
+            if (lh_launch_trace(&sc, &o, variant, &octx) != 0 ||
                 lh_order_back(&p, closest ? 1 : 0, ws, part.prim, part.t, part.u, part.v, part.occ, s) != 0)
                 return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
             a->order_stat[0]++; a->order_stat[1] += part.n;
         }
         if (ws) return 0;
     }
-    const int rc = lh_launch_trace(&sc, &b, lh_next_cursor(a), variant, a->grid_blocks, min_active, tri_batch, &a->aoq[qk].q, a->ncus, (void *)s);
-    if (rc != 0) return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    ctx.d_cursor = lh_next_cursor(a);
+    if (lh_launch_trace(&sc, &b, variant, &ctx) != 0) return fail("kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     return 0;
 }
 

@@ -134,15 +134,14 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
         const uint32_t big = (a->ao_budget && !a->ao_budget_user) ? 2u * a->ao_budget : 0u;
         if (!late && big && nhit * N >= (1ull << 27)) sc.ray_budget = big;
         budget = sc.ray_budget;
+        const lh_gather_src_t src = {nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                                     late ? d_nhit : NULL, late ? big : 0u};
+        const lh_launch_ctx_t ctx = {lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, (void *)s};
         if (dirt) {
-            if (lh_launch_trace_dirt(&sc, nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                                     dirt->p.far_clip, (double *)dirt->ts->t.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
-                                     &a->aoq[qslot].q, a->ncus, late ? d_nhit : NULL, late ? big : 0u, (void *)s) != 0)
+            if (lh_launch_trace_dirt(&sc, &src, dirt->p.far_clip, (double *)dirt->ts->t.p, cnt, &ctx) != 0)
                 return fail("%sfused dirt launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
         } else
-        if (lh_launch_trace_ao(&sc, nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                               (unsigned int *)b->occcount.p, cnt, lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch,
-                               &a->aoq[qslot].q, a->ncus, late ? d_nhit : NULL, late ? big : 0u, (void *)s) != 0)
+        if (lh_launch_trace_ao(&sc, &src, (unsigned int *)b->occcount.p, cnt, &ctx) != 0)
             return fail("%sfused AO launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
         if (!late) {
             if (wait_queue() != 0) return -1;

@@ -1,5 +1,5 @@
 """Round 4's launch policy: every launch of 65 536 rays or more walks at most 34 CHECKED LDS stack rows (four workgroups per CU;
-rows4 in lh_kernels.hip) -- a ray that would overrun them is finished by the cooperative walk -- and the fused AO stage has a
+lh_plan_rows4 in lh_plan.h) -- a ray that would overrun them is finished by the cooperative walk -- and the fused AO stage has a
 visit budget of its own ("ao_budget").  Neither may change a bit: records and frames with the policy (the default) must equal
 those of the unchecked walk of rounds 1-3 ("stack_cap" 64) and those of a stack capped far below what the tree asks for, on trees
 that ask for more than 34 rows (a deep chain of nested boxes; the device builder's tree over an exponentially spaced line)."""
@@ -53,6 +53,36 @@ def test_big_dumps_walk_checked_rows_and_keep_every_bit(build):
     acc.set_param("stack_cap", 0)
     small = _records(acc, d_org[:3000], d_dir[:3000])
     assert all(torch.equal(a, b[:3000]) for a, b in zip(small, base))
+    acc.close()
+
+
+def test_a_cooperative_ring_beyond_64_kib_keeps_every_bit():
+    """a tree of 41 four-wide levels or more gives the cooperative walk a ring of 256 rows: 65 KiB of LDS, the one launch whose kernel needs its
+    LDS limit raised (lh_plan.h; allow_lds in lh_kernels.hip).  65 536 rays -- the fewest that run it beside the launch -- at the default's 34
+    checked rows and at a cap of 8, which sends most deep rays through it: records bit-equal to the 64 rows of "stack_cap" 64"""
+    import ctypes as C
+    import torch
+    from tests.helpers import Model, vertex_aimed_rays
+    P, idx = chain_scene(400, 0.85)
+    m = Model(P, idx); d4 = (C.c_uint32 * 2)()          # the host builder's tree, as commit(build="host") builds it
+    Model.lib().lhm_info4.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]; Model.lib().lhm_info4(m.h, d4)
+    assert d4[1] >= 41 and 3 * d4[1] + 6 <= 512          # a ring of 256 or 512 rows
+    rng = np.random.default_rng(43)
+    org, dr = random_rays(rng, 32768, lo=-1.0, hi=2.0)
+    org2, dr2 = vertex_aimed_rays(rng, P, idx, 32768)          # rays at every level of the chain
+    org, dr = np.concatenate([org, org2]), np.concatenate([dr, dr2])
+    acc = la.HipAccel(0); acc.add_mesh(P, idx); info = acc.commit(build="host")
+    assert info["max_depth"] == m.max_depth
+    d_org = torch.from_numpy(np.ascontiguousarray(org)).cuda(); d_dir = torch.from_numpy(np.ascontiguousarray(dr)).cuda()
+    acc.set_param("stack_cap", 64)
+    base = _records(acc, d_org, d_dir)
+    # neither all hits nor all misses: one aimed ray in five goes through a centroid (6 554), a quarter of those at one of the 100 largest triangles
+    # (0.85^100 = 9e-8 and more: nine orders above the rounding of a direction) and hits it or a nearer one -- 1 600 expected, +- 35
+    assert 1000 < int((base[0].cpu().numpy().view(np.uint32) != la.MISS).sum()) < 65536 - 1000
+    for cap in (0, 8):
+        acc.set_param("stack_cap", cap)
+        got = _records(acc, d_org, d_dir)
+        assert all(torch.equal(a, b) for a, b in zip(got, base)), (cap, int(d4[1]))
     acc.close()
 
 
