@@ -500,6 +500,55 @@ int  lh_render_dirt_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int 
                          int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed,
                          const void *d_uniforms, void *d_rgb, lh_tile_stats_t *stats, void *stream);
 
+/* ---- the environment-lit gather: sky light through the AO stage (gather_sunsky's loop, src/transport/ambientocclusion.c:206-324, and
+ *      ri_ibl_sample_cosweight, src/render/ibl.c:52-227, with ri_texture_ibl_fetch as the radiance of a miss) ----
+ * AO with a colour: the same stratified cosine hemisphere about Ns and the same ortho basis as the AO stage, the origin P + eps Ns, an
+ * any-hit answer per gather ray; a ray that is not occluded sees the accelerator's environment (lh_accel_set_environment below: the
+ * angular map scaled by rgb, or the constant rgb; constant white if none was set) in its direction, an occluded ray sees nothing.
+ *   input of gather ray r:  occ_r, its any-hit answer under the pipeline's semantics (the reference's);  rad_r[k] (k = 0, 1, 2), three
+ *     floats: ri_texture_ibl_fetch of the ray's unnormalised fp64 direction, with the environment as it stands when the call is made.
+ *   value of one hit: with N = floor(sqrt(gather_nsamples))^2 rays, per channel sum_k = 0; for r = 0 .. N - 1 (r = j * ntheta + i):
+ *     if (!occ_r) sum_k = sum_k + (double)rad_r[k]; value_k = (float)((scale * sum_k) / N), in fp64.  count = the occluded rays.  The
+ *     order is part of the contract.
+ *   parameters: eps, the origin's offset along Ns (gather_sunsky: 1e-5, ibl.c: 1e-4); scale, the reference's m (0.3183098861837907 is
+ *     gather_sunsky's 1 / M_PI, 1.0 is ri_ibl_sample_cosweight's pi * (1 / pi)).  Both finite, eps >= 0, scale >= 0; NULL:
+ *     LH_ENV_DEFAULTS.  Anything else, NaN included, is refused ("bad environment-gather parameters").  The self-primitive skip of a
+ *     flat-shaded hit is applied only when eps >= 1e-6.
+ * lh_accel_env_device: as lh_accel_dirt_device, word for word -- list, count and key semantics, hit slots in list order, the uniforms
+ *   replay (2 doubles per gather ray in (slot, j, i) order), untouched slots of rays that are not traced (12 bytes per ray of d_rgb),
+ *   an id listed twice, synchronous on `stream`, the empty scene, scratch of its own, its refusals.  d_occluded_count[id] (uint32, may
+ *   be NULL) = count; d_rgb[3 id ..] (3 floats, may be NULL) = value.  A traced miss gets LH_AO_NO_HIT and three 0.0f.  The value
+ *   alone: no texture multiply.  Fused when "ao_fused" is on, no uniforms are given, the scene is not empty and list entries x N < 2^31:
+ *   the AO stage's any-hit kernel makes the gather rays itself and whoever finishes a ray stores its answer as one byte; else, and as
+ *   the second try of a fused launch whose queue overflowed, the rays are materialised in HBM and traced by one any-hit launch.  A
+ *   resolve with a group of lanes per hit then fetches the colours of the rays that are not occluded and adds them in r order.  Both
+ *   give the same bytes.  With lh_accel_trace_statistics on, `rays` advances by hits x N and counters[4] by the occluded rays.
+ * lh_render_env_tile: per camera sample -- a miss gives 0 (ambientocclusion.c:407-411), a hit its value_k (the float), times the texture
+ *   of its mesh where it has one, per channel as the AO and dirt tiles multiply; sub-samples accumulated and written as
+ *   lh_render_ao_tile does, keys are the absolute sample position (a frame does not depend on its tiling); stats->ao_rays = hits x N,
+ *   stats->ao_occluded = the sum of the hits' counts.  lh_render_scratch keeps showing the last AO tile.
+ * lh_accel_environment_device: the fetch alone for n fp64 directions (3 doubles each, need not be unit vectors), 3 floats each to
+ *   d_rgb_out: what a caller needs to light a camera miss.  Asynchronous on `stream`, nothing is read back.  A zero or non-finite
+ *   direction gives an unspecified colour; the texel index stays inside the map.  -1: an uncommitted accelerator, a NULL or misaligned
+ *   array with n > 0.  lh_accel_environment_host: the same for HOST arrays (copies up, the device call, copies down).
+ * Not part of this: the Preetham sky of sunsky.c and the sun's shadow ray (contribution_from_sunlight) -- another radiance source for
+ *   the same stage -- and the qmc branch of ibl.c. */
+typedef struct lh_env_params { double eps, scale; } lh_env_params_t;
+#define LH_ENV_DEFAULTS { 1.0e-5, 1.0 }
+int  lh_accel_env_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                         const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                         int gather_nsamples, const lh_env_params_t *params, uint64_t seed, const void *d_key, const void *d_uniforms,
+                         const void *d_index, size_t n_index, const void *d_count,
+                         void *d_occluded_count, void *d_rgb, void *stream);
+int  lh_accel_env_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,
+                       const double *t, const double *u, const double *v, int gather_nsamples, const lh_env_params_t *params,
+                       uint64_t seed, const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *rgb);
+int  lh_render_env_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
+                        int gather_nsamples, const lh_env_params_t *params, uint64_t seed,
+                        const void *d_uniforms, void *d_rgb, lh_tile_stats_t *stats, void *stream);
+int  lh_accel_environment_device(lh_accel_t *accel, size_t n, const void *d_dir_xyz, void *d_rgb_out, void *stream);
+int  lh_accel_environment_host(lh_accel_t *accel, size_t n, const double *dir_xyz, float *rgb_out);
+
 /* ---- material textures: the multiply both occlusion transports end with (src/transport/ambientocclusion.c:393-401, dirtmap.c:273-281) ----
  * Where the hit's mesh has a texture: ri_texture_fetch(texcol, texture, s, t); radiance[k] *= texcol[k].
  *   texture: height rows of width texels, 4 floats (RGBA) each, row 0 first (ri_texture_t.data, src/render/texture.h:21-29), no flip.
@@ -513,7 +562,7 @@ int  lh_render_dirt_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int 
  *   per camera sample: rad_k = rad * texcol[k] (k = 0, 1, 2) where the hit's mesh has a texture, else rad_k = rad, with rad the double the
  *     tile computes without textures; sub-samples accumulate per channel in the same order, then the same scale, (float) conversion and
  *     clamp of negatives to 0, per channel.  A miss contributes 0.
- * lh_render_ao_tile / _bands / _tile_host, lh_render_ao_frame_host, lh_render_dirt_tile, lh_multi_render_ao_frame_host and
+ * lh_render_ao_tile / _bands / _tile_host, lh_render_ao_frame_host, lh_render_dirt_tile, lh_render_env_tile, lh_multi_render_ao_frame_host and
  *   lh_dist_render_ao_frame_host multiply as soon as the accelerator holds at least one texture; with none they launch the kernels
  *   they always launched, with the same arguments.  Tile statistics, the replay uniforms and the fused / materialised stages do not
  *   depend on textures.  Not covered: the sun-and-sky branch, mip-maps, textures in the path tracer (lh_render_pt_*), and

@@ -110,6 +110,15 @@ class DirtParams(C.Structure):
         super().__init__(float(near_clip), float(far_clip), float(eps))
 
 
+class EnvParams(C.Structure):
+    """lh_env_params_t: origin offset and scale of the environment-lit gather (defaults: LH_ENV_DEFAULTS; scale 0.3183098861837907 is
+    gather_sunsky's 1 / pi, 1.0 is ri_ibl_sample_cosweight's)"""
+    _fields_ = [("eps", C.c_double), ("scale", C.c_double)]
+
+    def __init__(self, eps=1.0e-5, scale=1.0):
+        super().__init__(float(eps), float(scale))
+
+
 # lh_beam_set_t (include/lucille_hip.h): a beam as lucille's ri_beam_set leaves it -- 232 bytes
 BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)), ("normal", np.float64, (4, 3)),
                            ("dominant_axis", np.int32), ("dirsign", np.int32, (3,))])
@@ -127,6 +136,7 @@ ABI_SYMBOLS = [
     "lh_accel_set_material", "lh_accel_set_environment", "lh_render_pt_tile2", "lh_render_pt_bands", "lh_accel_set_attribute", "lh_accel_set_normals_device", "lh_accel_set_attribute_device",
     "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
     "lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile",
+    "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
     "lh_multi_add_rib_scene", "lh_multi_commit", "lh_multi_set_material", "lh_multi_set_environment", "lh_multi_intersect_host",
@@ -219,6 +229,14 @@ def lib():
     L.lh_accel_dirt_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, dpp, C.c_uint64, vp, vp, sz, vp, vp]
     L.lh_render_dirt_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, dpp, C.c_uint64, vp, vp,
                                       C.POINTER(TileStats), vp]
+    if hasattr(L, "lh_accel_env_device"):                # an older library under LH_LIBRARY (A/B runs in tools/) has no environment gather
+        epp = C.POINTER(EnvParams)
+        L.lh_accel_env_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, epp, C.c_uint64, vp, vp, vp, sz, vp, vp, vp, vp]
+        L.lh_accel_env_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, i32, epp, C.c_uint64, vp, vp, sz, vp, vp]
+        L.lh_render_env_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, epp, C.c_uint64, vp, vp,
+                                         C.POINTER(TileStats), vp]
+        L.lh_accel_environment_device.argtypes = [vp, sz, vp, vp, vp]
+        L.lh_accel_environment_host.argtypes = [vp, sz, vp, vp]
     if hasattr(L, "lh_accel_set_texture"):               # an older library under LH_LIBRARY (the parent's build in tools/tex_frames.py) has no textures
         L.lh_accel_set_texture.argtypes = [vp, u32, vp, i32, i32]
         L.lh_accel_set_texture_device.argtypes = [vp, u32, vp, i32, i32, vp]
@@ -801,6 +819,22 @@ class HipAccel:
                                           C.byref(st), C.c_void_p(stream)), "lh_render_dirt_tile")
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    def render_env_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, params=None, seed=1, uniforms=None, out=None,
+                        stream=None):
+        """lh_render_env_tile: the environment-lit gather's tile (params: an EnvParams, None: the defaults) ->
+        (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x N, ao_occluded = the occluded rays)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = TileStats()
+        _check(self.L.lh_render_env_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples,
+                                         None if params is None else C.byref(params), int(seed), _dptr(uniforms), _dptr(out),
+                                         C.byref(st), C.c_void_p(stream)), "lh_render_env_tile")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     def render_ao_frame_host(self, cam, pixel_samples, gather_nsamples, seed=1, tile=0):
         """lh_render_ao_frame_host: the whole frame into host memory -> (float32 [H, W, 3] numpy, top row first; stats)"""
         rgb = np.empty((cam.height, cam.width, 3), np.float32)
@@ -1027,27 +1061,49 @@ class HipAccel:
             raise ValueError("dirt_device: params must be a DirtParams")
         return self._batch_stage_device("dirt_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
 
+    def env_device(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None, index=None, count=None,
+                   out=None, stream=None):
+        """lh_accel_env_device: the environment-lit gather -- sky light with visibility -- for a batch of rays and their closest-hit
+        records; arguments as ao_device, and params: an EnvParams (None: eps 1e-5, scale 1).  Returns (count, rgb): an int32 tensor
+        [n] whose bits are uint32 -- the hit's occluded gather rays, AO_NO_HIT for a miss -- and the float32 tensor [n, 3] of the
+        gathered colour (zeros for a miss), the accelerator's environment (set_environment) seen by the rays that are not occluded.
+        out: such a pair to fill (either member may be None, not both); with out=None the slots of rays that are not listed are
+        UNSPECIFIED.  Synchronous: the outputs are complete on return."""
+        if params is None:
+            params = EnvParams()
+        if not isinstance(params, EnvParams):
+            raise ValueError("env_device: params must be an EnvParams")
+        return self._batch_stage_device("env_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
+
     def _batch_stage_device(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream):
-        """ao_device (dirt None) / dirt_device (dirt: its DirtParams): the checks and the call"""
+        """ao_device (dirt None) / dirt_device (dirt: its DirtParams) / env_device (dirt: its EnvParams; radiance [n, 3]): the checks and the call"""
         import torch
         n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
         dev = org.device
         ip, ni, cp = _list_args(index, count, what)
         if index is None and count is not None:
             ni = n
+        env = isinstance(dirt, EnvParams)
         if out is None:
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.float32, device=dev))
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3) if env else n, dtype=torch.float32, device=dev))
         if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
             raise ValueError("%s: out must be a (count, radiance) pair, at least one of them a tensor" % what)
         oc, orad = out
         words = (torch.int32, getattr(torch, "uint32", torch.int32))
         if oc is not None and not (oc.is_cuda and oc.dtype in words and oc.dim() == 1 and oc.shape[0] == n and oc.is_contiguous()):
             raise ValueError("%s: the count output must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 1 and orad.shape[0] == n and orad.is_contiguous()):
+        if env and orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 2 and tuple(orad.shape) == (n, 3) and orad.is_contiguous()):
+            raise ValueError("%s: the colour output must be a contiguous float32 device tensor [n, 3]" % what)
+        if not env and orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 1 and orad.shape[0] == n and orad.is_contiguous()):
             raise ValueError("%s: the radiance output must be a contiguous float32 device tensor [n]" % what)
         if stream is None:
             stream = torch.cuda.current_stream(dev)
         stream = getattr(stream, "cuda_stream", stream)
+        if env:
+            _check(self.L.lh_accel_env_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
+                                              C.byref(dirt), int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad),
+                                              C.c_void_p(stream)), "lh_accel_env_device")
+            return out
         if dirt is not None:
             _check(self.L.lh_accel_dirt_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
                                                C.byref(dirt), int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad),
@@ -1105,6 +1161,39 @@ class HipAccel:
             raise ValueError("dirt_host: params must be a DirtParams")
         return self._batch_stage_host("dirt_host", params, org, dr, records, gather_nsamples, seed, key, uniforms)
 
+    def env_host(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None):
+        """lh_accel_env_host: host arrays as ao_host, params as env_device -> (count uint32 [n], rgb float32 [n, 3])"""
+        if params is None:
+            params = EnvParams()
+        if not isinstance(params, EnvParams):
+            raise ValueError("env_host: params must be an EnvParams")
+        return self._batch_stage_host("env_host", params, org, dr, records, gather_nsamples, seed, key, uniforms)
+
+    def environment_device(self, dirs, out=None, stream=None):
+        """lh_accel_environment_device: the accelerator's environment (set_environment; constant white if none was set) seen in each of
+        the directions `dirs` (contiguous float64 device tensor [n, 3], need not be unit vectors) -> float32 device tensor [n, 3].
+        Asynchronous on the stream; a zero or non-finite direction gives an unspecified colour."""
+        import torch
+        if not (isinstance(dirs, torch.Tensor) and dirs.is_cuda and dirs.dtype == torch.float64 and dirs.dim() == 2 and dirs.shape[1] == 3 and dirs.is_contiguous()):
+            raise ValueError("environment_device: dirs must be a contiguous float64 device tensor [n, 3]")
+        n = int(dirs.shape[0])
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=dirs.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 3) and out.is_contiguous()):
+            raise ValueError("environment_device: out must be a contiguous float32 device tensor [n, 3]")
+        if stream is None:
+            stream = torch.cuda.current_stream(dirs.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_environment_device(self.h, n, _dptr(dirs), _dptr(out), C.c_void_p(stream)), "lh_accel_environment_device")
+        return out
+
+    def environment_host(self, dirs):
+        """lh_accel_environment_host: host directions [n, 3] -> float32 [n, 3]"""
+        d = _np(dirs, np.float64).reshape(-1, 3)
+        rgb = np.empty((d.shape[0], 3), np.float32)
+        _check(self.L.lh_accel_environment_host(self.h, d.shape[0], d.ctypes.data, rgb.ctypes.data), "lh_accel_environment_host")
+        return rgb
+
     def _batch_stage_host(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms):
         o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
         if d.shape[0] != n or len(records) != 4:
@@ -1118,6 +1207,13 @@ class HipAccel:
             raise ValueError("%s: one key per ray" % what)
         un = None if uniforms is None else _np(uniforms, np.float64).reshape(-1)
         cnt = np.empty(n, np.uint32); rad = np.empty(n, np.float32)
+        if isinstance(dirt, EnvParams):
+            rad = np.empty((n, 3), np.float32)
+            _check(self.L.lh_accel_env_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                            int(gather_nsamples), C.byref(dirt), int(seed), None if k is None else k.ctypes.data,
+                                            None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,
+                                            rad.ctypes.data), "lh_accel_env_host")
+            return cnt, rad
         if dirt is not None:
             _check(self.L.lh_accel_dirt_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
                                              int(gather_nsamples), C.byref(dirt), int(seed), None if k is None else k.ctypes.data,

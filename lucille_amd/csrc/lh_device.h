@@ -198,6 +198,9 @@ int lh_launch_trace_ao(const lh_dev_scene_t *sc, const lh_gather_src_t *src, uns
 /* ... and the dirt stage's: closest hit under the one bound far_clip, the t of ray (slot, r)'s bounded record at element slot * N + r of d_t */
 int lh_launch_trace_dirt(const lh_dev_scene_t *sc, const lh_gather_src_t *src, double far_clip, double *d_t, unsigned long long *d_counters,
                          const lh_launch_ctx_t *ctx);
+/* ... and the environment gather's (lh_env.h): the AO stage's any-hit walk, the answer of ray (slot, r) as a byte, 0 or 1, at element slot * N + r of d_occ */
+int lh_launch_trace_env(const lh_dev_scene_t *sc, const lh_gather_src_t *src, uint8_t *d_occ, unsigned long long *d_counters,
+                        const lh_launch_ctx_t *ctx);
 int lh_trace_formats_needed(int variant);
 int lh_trace_rows(const lh_dev_scene_t *sc);        /* LDS stack rows the default walk launches with on this scene (lh_plan.h) */
 

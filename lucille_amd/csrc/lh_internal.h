@@ -161,6 +161,10 @@ struct lh_accel {
     lh_ao_scratch tile_dirt, batch_dirt;
     lh_dirt_scratch tile_dirt_t, batch_dirt_t;
     lh_buf d_tot, d_rays;              /* a batch's totals; the tile's camera rays and their closest-hit records */
+    /* the environment gather (lh_render_env_tile, lh_accel_env_device / _host; lh_env.h): scratch of its own once more -- its any-hit bytes are the
+     * `occ` of these, fused or materialised -- a batch's totals, the tile's camera rays and records, lh_accel_environment_host's staging */
+    lh_ao_scratch tile_env, batch_env;
+    lh_buf e_tot, e_rays, e_host;
     uint64_t last_retraced;            /* rays the last counted launch finished outside the main kernel */
     int ao_fused;                      /* AO rays generated inside the any-hit kernel (default); 0: materialised in HBM */
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */
@@ -334,6 +338,18 @@ extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs
 extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
                                                    double near_clip, double far_clip, const uint32_t *d_slot_of_entry, const double *d_t,
                                                    uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream);
+/* the accelerator's environment as the launchers take it (lh_accel_set_environment; never set: constant white) */
+typedef struct lh_env_src { float rgb[3]; const void *map; int w, h; } lh_env_src_t;
+extern "C" int lh_render_launch_env_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
+                                            const lh_env_src_t *env, const uint32_t *d_slot_of_sample, const double *d_hitrec,
+                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
+                                            unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream);
+extern "C" int lh_render_launch_env_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
+                                                  unsigned long long seed, double scale, const lh_env_src_t *env, const uint32_t *d_slot_of_entry,
+                                                  const double *d_hitrec, const unsigned long long *d_slot_key, const double *d_adir,
+                                                  const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
+                                                  unsigned long long *d_occ_total, void *stream);
+extern "C" int lh_render_launch_env_fetch(size_t n, const lh_env_src_t *env, const double *d_dir, float *d_rgb, void *stream);
 extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
                                             const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
                                             const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,

@@ -586,7 +586,10 @@ constexpr uint32_t kNoRay = 0xFFFFFFFFu;
 /* TMAX (with IDX): a bounded launch (sc.tmax: a bound per ray id, lh_tmax.h).  The refill starts the lane's culling bound and best.t at the ray's bound
  * instead of at 1e38, the retire reads the bound once more (no register stays live for it across the walk) to mark a hit near it fragile and to give a
  * miss its record's t; the triangle step lets a certain any-hit end the ray only below the bound.  TMAX = false: the code of every other launch, unchanged */
-template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false, bool IDX = false, bool TMAX = false>
+/* ENV (any hit, ray source 1): the environment gather's stage (lh_env.h) -- the lane that retires ray i stores its any-hit answer, 0 or 1, at occ[i]
+ * (the plain item order: i = slot * N + r) instead of counting it into its slot: the resolve needs to know WHICH rays were occluded.  A queued ray's
+ * byte is the consumer's to store.  ENV = false: the code of every other launch, unchanged */
+template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false, bool IDX = false, bool TMAX = false, bool ENV = false>
 __device__ __forceinline__ void trace_persist_lane(
     const lh_dev_scene_t &sc, const uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
@@ -643,6 +646,7 @@ __device__ __forceinline__ void trace_persist_lane(
             } else
             if (SRC != 1) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT, SRC == 0 && IO>(sc, my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
             else if (!ANYHIT) { if (!L.over && !fragile) dirt_store(ao, my, best.t); }          /* the dirt stage: a queued ray's word is the consumer's to store */
+            else if (ENV) { if (!L.over && !fragile) occ[my] = (uint8_t)((L.certain || best.prim != LH_MISS_PRIM) ? 1 : 0); }      /* the environment gather: so is its byte */
             else if (!L.over && !fragile && (L.certain || best.prim != LH_MISS_PRIM)) { uint32_t sl, rr; ao_item(ao, my, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
             if (COUNT) {
                 cr++;
@@ -843,6 +847,18 @@ __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_dirt(
     trace_persist_lane<false, COUNT, WALK, 1, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
+/* the persistent kernel of the fused environment gather (lh_launch_trace_env): the AO stage's any-hit walk over the gather rays of ao.nslots hits
+ * (SRC 1), whose retire stores the ray's answer as a byte at occ[slot * N + r] (ENV).  A kernel of its own once more */
+template <bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_env(
+    lh_dev_scene_t sc, uint32_t n, uint8_t *__restrict__ occ, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao, const FixQ fq)
+{
+    extern __shared__ int lh_stack_lds[];
+    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
+    copy_tree_top(sc, lh_stack_lds);
+    trace_persist_lane<true, COUNT, WALK, 1, false, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
+}
+
 /* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
  * arrays, skipped).  For the cold kernels that enumerate a launch's rays (k_fixups, k_trace_small) */
 __device__ __forceinline__ bool item_ray(const lh_dev_scene_t &sc, size_t k, size_t &i)
@@ -902,7 +918,8 @@ __device__ __noinline__ RefHit ref_trace_one(const lh_dev_scene_t &sc, double ox
 /* TMAX: the rays of a bounded launch (sc.tmax, lh_tmax.h) -- every lane of a group starts with the ray's bound, the group's merged best retires like a
  * lane's (tmax_retire), the reference walk's records go through the final accept.  The body is shared; the kernels are k_coop_walk (every launch without
  * bounds: TMAX = false, the code it always was) and k_coop_walk_tmax */
-template <bool ANYHIT, int SRC, bool TMAX>
+/* ENV (any hit, ray source 1): the environment gather's rays -- the group's answer goes to occ[i] as a byte, 0 or 1, instead of into the slot's count */
+template <bool ANYHIT, int SRC, bool TMAX, bool ENV = false>
 __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const double *__restrict__ org, const double *__restrict__ dir,
                                                uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
                                                double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc &ao, const FixQ &fq,
@@ -991,7 +1008,8 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
                 }
                 if (SRC == 1 && ANYHIT && (lane & 15) == 0) {
                     if (need_ref) hit = ref_trace_one(sc, ox, oy, oz, dx, dy, dz).prim != LH_MISS_PRIM;
-                    if (hit) { uint32_t sl, rr; ao_item(ao, (uint32_t)i, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
+                    if (ENV) occ[i] = (uint8_t)(hit ? 1 : 0);
+                    else if (hit) { uint32_t sl, rr; ao_item(ao, (uint32_t)i, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
                 }
                 if (counters && (lane & 15) == 0) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
                 have = false;
@@ -1038,6 +1056,7 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
                     if (TMAX) LH_TMAX_FILTER_REF(rh, lane_tmax<SRC>(sc, ao, ri));
                     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
                     if (SRC == 1 && !ANYHIT) dirt_store(ao, ri, rh.t);
+                    else if (SRC == 1 && ENV) occ[ri] = rh.prim != LH_MISS_PRIM ? 1 : 0;
                     else if (SRC == 1) { if (rh.prim != LH_MISS_PRIM) { uint32_t sl, rr; ao_item(ao, ri, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); } }
                     else if (ANYHIT) occ[ri] = rh.prim != LH_MISS_PRIM ? 1 : 0;
                     else store_rec<SRC == 0>(sc, ri, prim, t, u, v, rh.prim, rh.t, rh.u, rh.v);
@@ -1141,6 +1160,15 @@ __global__ __launch_bounds__(64) void k_coop_walk_dirt(lh_dev_scene_t sc, const 
                                                        unsigned long long *counters, const uint32_t owner_groups)
 {
     coop_walk_body<false, 1, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+}
+
+/* the cooperative walk of the fused environment gather (ray source 1, any hit, a byte per ray) */
+__global__ __launch_bounds__(64) void k_coop_walk_env(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                                      uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                      double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
+                                                      unsigned long long *counters, const uint32_t owner_groups)
+{
+    coop_walk_body<true, 1, false, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1434,7 +1462,7 @@ int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, const lh_plan_t &
  * stream, CONCURRENTLY with that launch (a few small workgroups per CU next to the persistent ones: its low efficiency --
  * one ray per 16 lanes, restarted from the root -- is hidden behind the bulk of the frame), submitted AFTER it: if the two
  * streams share a hardware queue it simply runs afterwards. */
-template <bool ANYHIT, int SRC, bool TMAX = false>
+template <bool ANYHIT, int SRC, bool TMAX = false, bool ENV = false>
 int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p, const lh_launch_ctx_t &c, hipStream_t s)
 {
     /* the pass next to the producer (owner_groups 0) and the sweep behind it */
@@ -1444,6 +1472,7 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
     auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
     if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
     if (DIRT) kern = k_coop_walk_dirt;
+    if (ENV) kern = k_coop_walk_env;          /* the fused environment gather */
     lh_dev_scene_t scl = sc;
     scl.stack_rows = p.coop_rows;
     if (allow_lds((const void *)kern, p.coop_lds_bytes) != 0) return -1;
@@ -1469,7 +1498,7 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
 }
 
 /* what the two fused stages differ in beside their kernels: the chunk before the clamp and the tail of AoSrc */
-struct FusedStage { bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; };
+struct FusedStage { bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; uint8_t *env_occ; };
 
 /* a fused stage: the gather rays of g.nslots hits, N = ntheta * nphi each, made inside the persistent kernel (SRC 1).  Rays that kernel does not
  * finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative walk) -- go through the stream's
@@ -1489,10 +1518,10 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
     if (apply_plan(scl, p) != 0) return -1;
     if (st.occ_count && hipMemsetAsync(st.occ_count, 0, sizeof(unsigned int) * g.nslots, s) != hipSuccess) return -1;      /* with the cursors' memset, before the stream's first kernel */
     if (persist_begin(c, true, &fq, s) != 0) return -1;
-    /* the rays are made in the kernel; the answers counted per slot (AO), their t stored through ao (dirt) */
-    const lh_batch_t none = {n, st.dirt ? LH_MODE_CLOSEST : LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, NULL, d_counters};
+    /* the rays are made in the kernel; the answers counted per slot (AO), their t stored through ao (dirt), a byte per ray at `occ` (the environment gather) */
+    const lh_batch_t none = {n, st.dirt ? LH_MODE_CLOSEST : LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, st.env_occ, d_counters};
     const int w = p.guard ? 0 : 1, k = d_counters ? 0 : 1;          /* the kernels below: checked pushes first, counted first */
-    if (!st.dirt) {
+    if (!st.dirt && !st.env_occ) {
         using ao_t = decltype(&k_trace_persist_lane<true, true, LH_WALK_Q4, 1>);
         const ao_t kern[2][2] = {{k_trace_persist_lane<true, true, LH_WALK_Q4_CHECKED, 1>, k_trace_persist_lane<true, false, LH_WALK_Q4_CHECKED, 1>},
                                  {k_trace_persist_lane<true, true, LH_WALK_Q4, 1>, k_trace_persist_lane<true, false, LH_WALK_Q4, 1>}};
@@ -1503,9 +1532,18 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
     using dirt_t = decltype(&k_trace_persist_dirt<true, LH_WALK_Q4>);
     const dirt_t kern[2][2] = {{k_trace_persist_dirt<true, LH_WALK_Q4_CHECKED>, k_trace_persist_dirt<false, LH_WALK_Q4_CHECKED>},
                                {k_trace_persist_dirt<true, LH_WALK_Q4>, k_trace_persist_dirt<false, LH_WALK_Q4>}};
-    LH_LAUNCH_PERSIST(kern[w][k], scl, (uint32_t)n, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
+    if (st.dirt) {
+        LH_LAUNCH_PERSIST(kern[w][k], scl, (uint32_t)n, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
+        if (hipGetLastError() != hipSuccess) return -1;
+        return launch_coop<false, 1, true>(scl, none, ao, fq, p, c, s);
+    }
+    /* the environment gather (named last: the kernels above keep their order) */
+    using env_t = decltype(&k_trace_persist_env<true, LH_WALK_Q4>);
+    const env_t ekern[2][2] = {{k_trace_persist_env<true, LH_WALK_Q4_CHECKED>, k_trace_persist_env<false, LH_WALK_Q4_CHECKED>},
+                               {k_trace_persist_env<true, LH_WALK_Q4>, k_trace_persist_env<false, LH_WALK_Q4>}};
+    LH_LAUNCH_PERSIST(ekern[w][k], scl, (uint32_t)n, st.env_occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
     if (hipGetLastError() != hipSuccess) return -1;
-    return launch_coop<false, 1, true>(scl, none, ao, fq, p, c, s);
+    return launch_coop<true, 1, false, true>(scl, none, ao, fq, p, c, s);
 }
 
 } /* namespace */
@@ -1517,7 +1555,7 @@ extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, const lh_gather_src_
     static uint32_t ao_chunk = 0;
     if (!ao_chunk) { const char *e = getenv("LH_AO_CHUNK"); ao_chunk = (e && atoi(e) >= 64 && atoi(e) <= 65536) ? (uint32_t)atoi(e) : LH_TILE_CHUNK; }
     /* AO rays of a slot are coherent: longer ranges per wave (LH_AO_CHUNK) */
-    return launch_fused(sc, *src, FusedStage{false, ao_chunk, d_occ_count, (int)sc->ao_group, 0.0, NULL}, d_counters, *ctx);
+    return launch_fused(sc, *src, FusedStage{false, ao_chunk, d_occ_count, (int)sc->ao_group, 0.0, NULL, NULL}, d_counters, *ctx);
 }
 
 /* the dirt stage (lh_dirt.h) the same way: the gather rays of nslots hits made inside a CLOSEST-hit kernel that walks them under the one bound
@@ -1529,7 +1567,18 @@ extern "C" int lh_launch_trace_dirt(const lh_dev_scene_t *sc, const lh_gather_sr
                                     const lh_launch_ctx_t *ctx)
 {
     /* the gather rays of a slot are coherent, as AO rays are; the plain item order (slot, sample): the grouped order is the AO stage's experiment */
-    return launch_fused(sc, *src, FusedStage{true, LH_TILE_CHUNK, NULL, 0, far_clip, d_t}, d_counters, *ctx);
+    return launch_fused(sc, *src, FusedStage{true, LH_TILE_CHUNK, NULL, 0, far_clip, d_t, NULL}, d_counters, *ctx);
+}
+
+/* the environment gather (lh_env.h) the same way: the AO stage's rays and its any-hit walk, with the launch geometry of the AO stage (LH_PLAN_AO);
+ * instead of a count per slot the answer of ray (slot, r), 0 or 1, is stored at byte slot * N + r of d_occ by whoever finishes the ray -- the lane
+ * that retires it, the cooperative walk, the reference's own walk for a fragile hit.  Every byte of the first nslots * N is written exactly once
+ * (no memset, no atomic) unless the queue overflows: the caller then redoes the stage materialised.  The plain item order (slot, sample) */
+extern "C" int lh_launch_trace_env(const lh_dev_scene_t *sc, const lh_gather_src_t *src, uint8_t *d_occ, unsigned long long *d_counters,
+                                   const lh_launch_ctx_t *ctx)
+{
+    if (!d_occ) return -1;
+    return launch_fused(sc, *src, FusedStage{false, LH_TILE_CHUNK, NULL, 0, 0.0, NULL, d_occ}, d_counters, *ctx);
 }
 
 extern "C" int lh_trace_rows(const lh_dev_scene_t *sc)

@@ -33,6 +33,7 @@
 #include "lh_internal.h"
 #include "lh_ao.h"
 #include "lh_dirt.h"
+#include "lh_env.h"
 #include "lh_tex.h"
 
 namespace {
@@ -607,6 +608,160 @@ __global__ void k_dirt_batch_resolve(const BatchList bl, int N, double near_clip
     dirt_total(nh, hit_total);
 }
 
+/* ---- the environment-lit gather (lh_env.h): the resolves read one byte per gather ray -- its any-hit answer, at element slot * N + r --
+ * and, for the rays that are not occluded, fetch the environment in the ray's direction; whoever traced the rays wrote that array -------- */
+
+/* the accelerator's environment as a kernel argument */
+__device__ __host__ inline DevEnv env_of(const lh_env_src_t &e)
+{
+    DevEnv d;
+    d.rgb[0] = e.rgb[0]; d.rgb[1] = e.rgb[1]; d.rgb[2] = e.rgb[2];
+    d.map = (const float4 *)e.map; d.w = e.w; d.h = e.h;
+    return d;
+}
+
+/* env_fetch for a direction nobody checked: a component that is not finite would reach the texel index as a NaN; such a direction (its colour is
+ * unspecified) is looked up as +z.  Every finite direction goes to env_fetch as it is: a zero vector or one whose norm under- or overflows
+ * ends at u = v = 1/2 by env_fetch's own arithmetic */
+__device__ __forceinline__ void env_lookup(const DevEnv &e, double dx, double dy, double dz, float out[3])
+{
+    if (!(isfinite(dx) && isfinite(dy) && isfinite(dz))) { dx = 0.0; dy = 0.0; dz = 1.0; }
+    env_fetch(e, dx, dy, dz, out);
+}
+
+/* what the two resolves share beside their slots: the grid of the hemisphere, the generator's seed, the hit records and keys (the fused stage: the
+ * directions are made again by lh_ao_ray_builtin) or the materialised directions (adir != NULL: the same doubles, or the replay's), the bytes */
+struct EnvGather {
+    int ntheta, nphi; unsigned long long seed;
+    const double *hitrec; const unsigned long long *slot_key; const double *adir; const uint8_t *occ;
+    double scale; DevEnv env;
+};
+
+/* The feature's hot loop, LH_ENV_GROUP lanes per hit slot: lane l takes the rays r = l, l + G, ... of the slot; an open ray costs a generator call
+ * (sincos, two square roots), env_fetch's acos and normalisation and four 16-byte texel gathers, an occluded one nothing.  A pass of G rays parks
+ * its colours in LDS (12 bytes a lane: component k of lane l is dword 3 l + k, a store banks by 32 dwords per half-wave and 3 is odd, so the 32 lanes
+ * of a half hit 32 different banks; 3 KiB a workgroup); lanes
+ * 0, 1, 2 of the group then take one channel each and add the pass's open rays in r order -- the order of lh_env_value -- from the group's ballot.
+ * Control flow is uniform over the workgroup (N and the sample count are launch constants; a group without a slot runs the passes idle), the LDS
+ * hand-over is inside a wave (a group never straddles one): a fence and a wave barrier, no __syncthreads.
+ * Returns (lanes 0-2) the channel's sum and (every lane of the group) the occluded count */
+#ifndef LH_ENV_GROUP
+#define LH_ENV_GROUP 4           /* a power of two from 4 (three channel lanes) to 64; why 4: DESIGN.md 10.0d */
+#endif
+__device__ __forceinline__ double env_slot_sum(const EnvGather &gx, bool have, uint32_t slot, float (*park)[3], unsigned int &count)
+{
+    LH_NC
+    const int N = gx.ntheta * gx.nphi;
+    const int lane = threadIdx.x & 63, gl = lane & (LH_ENV_GROUP - 1), gshift = lane & ~(LH_ENV_GROUP - 1);
+    float (*mine)[3] = park + (threadIdx.x & ~(LH_ENV_GROUP - 1));          /* the group's G entries */
+    double sum = 0.0;
+    count = 0;
+    for (int base = 0; base < N; base += LH_ENV_GROUP) {
+        const int r = base + gl;
+        const bool valid = have && r < N;
+        const size_t ray = (size_t)slot * (size_t)N + (size_t)r;
+        const bool blocked = valid && gx.occ[ray] != 0;
+        const bool open = valid && !blocked;
+        if (open) {
+            double ox, oy, oz, dx, dy, dz;
+            if (gx.adir) { dx = gx.adir[3 * ray]; dy = gx.adir[3 * ray + 1]; dz = gx.adir[3 * ray + 2]; }
+            else lh_ao_ray_builtin(gx.hitrec + LH_HITREC_DOUBLES * (size_t)slot, gx.slot_key[slot], gx.seed, gx.ntheta, gx.nphi, r, ox, oy, oz, dx, dy, dz);
+            float c[3];
+            env_lookup(gx.env, dx, dy, dz, c);
+            mine[gl][0] = c[0]; mine[gl][1] = c[1]; mine[gl][2] = c[2];
+        }
+        const unsigned long long gmask = LH_ENV_GROUP >= 64 ? ~0ull : ((1ull << (LH_ENV_GROUP & 63)) - 1ull);
+        const unsigned long long m_open = (__ballot(open) >> gshift) & gmask;
+        count += (unsigned int)__popcll((__ballot(blocked) >> gshift) & gmask);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        if (gl < 3) for (unsigned long long m = m_open; m != 0ull; m &= m - 1ull) sum = lh_env_add(sum, mine[__ffsll(m) - 1][gl]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    return sum;
+}
+
+/* k_ao_resolve for the environment gather's tile, a group of lanes per pixel: a miss gives 0 (ambientocclusion.c:407-411), a hit the three floats of
+ * lh_env_value; sub-samples accumulate per channel and are written as ao_resolve does.  TEX: times the texture of the hit's mesh, as ao_resolve */
+template <bool TEX>
+__device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather &gx, const uint32_t *__restrict__ slot_of_sample,
+                                            float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs *tx)
+{
+    LH_NC
+    __shared__ float park[256][3];
+    const size_t pix = (size_t)blockIdx.x * (256 / LH_ENV_GROUP) + (threadIdx.x / LH_ENV_GROUP);
+    const int gl = threadIdx.x & (LH_ENV_GROUP - 1);
+    const bool inside = pix < (size_t)w * h;
+    const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
+    const int S = xs * ys, N = gx.ntheta * gx.nphi;
+    double accum = 0.0;          /* lanes 0-2: the pixel's channel */
+    unsigned int nocc = 0;
+    for (int s = 0; s < S; s++) {
+        const uint32_t slot = inside ? slot_of_sample[pix * S + s] : LH_MISS_PRIM;
+        const bool hit = slot != LH_MISS_PRIM;
+        unsigned int c;
+        const double sum = env_slot_sum(gx, hit, slot, park, c);
+        if (gl == 0) nocc += c;
+        double val = 0.0;
+        if (hit && gl < 3) val = (double)lh_env_finish(gx.scale, sum, N);
+        if (TEX) {
+            double tc[4];
+            if (hit && gl < 3 && tex_color(*tx, pix * S + s, tc)) val = val * (gl == 0 ? tc[0] : (gl == 1 ? tc[1] : tc[2]));
+        }
+        accum = accum + val;
+    }
+    if (inside && gl < 3) {
+        float f = (float)(accum * ((double)1.0 / (xs * ys)));
+        if (f < 0.0f) f = 0.0f;
+        rgb[3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx) + gl] = f;
+    }
+    dirt_total(nocc, occ_total);
+}
+
+__global__ __launch_bounds__(256) void k_env_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather gx, const uint32_t *__restrict__ slot_of_sample,
+                                                     float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
+{
+    env_resolve<false>(w, h, band_rows, xs, ys, gx, slot_of_sample, rgb, occ_total, NULL);
+}
+
+__global__ __launch_bounds__(256) void k_env_resolve_tex(int w, int h, int band_rows, int xs, int ys, const EnvGather gx, const uint32_t *__restrict__ slot_of_sample,
+                                                         float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs tx)
+{
+    env_resolve<true>(w, h, band_rows, xs, ys, gx, slot_of_sample, rgb, occ_total, &tx);
+}
+
+/* k_ao_batch_resolve for the environment gather, a group of lanes per list entry: occluded_count[id] / rgb[3 id ..] (either may be NULL); a traced
+ * miss gets LH_AO_NO_HIT and three zeros.  slot_of_entry NULL: an empty scene, every traced ray is a miss */
+__global__ __launch_bounds__(256) void k_env_batch_resolve(const BatchList bl, const EnvGather gx, const uint32_t *__restrict__ slot_of_entry,
+                                                           uint32_t *__restrict__ occluded_count, float *__restrict__ rgb,
+                                                           unsigned long long *__restrict__ occ_total)
+{
+    LH_NC
+    __shared__ float park[256][3];
+    const uint32_t k = blockIdx.x * (256u / LH_ENV_GROUP) + threadIdx.x / LH_ENV_GROUP;
+    const int gl = threadIdx.x & (LH_ENV_GROUP - 1);
+    uint32_t id = 0;
+    const bool traced = batch_entry(bl, k, id);
+    const uint32_t slot = (traced && slot_of_entry) ? slot_of_entry[k] : LH_AO_NO_HIT;
+    const bool hit = slot != LH_AO_NO_HIT;
+    unsigned int c;
+    const double sum = env_slot_sum(gx, hit, slot, park, c);
+    if (traced) {
+        if (occluded_count && gl == 0) occluded_count[id] = hit ? c : LH_AO_NO_HIT;
+        if (rgb && gl < 3) rgb[3 * (size_t)id + gl] = hit ? lh_env_finish(gx.scale, sum, gx.ntheta * gx.nphi) : 0.0f;
+    }
+    dirt_total((hit && gl == 0) ? c : 0u, occ_total);
+}
+
+/* the fetch alone (lh_accel_environment_device): one thread per direction */
+__global__ void k_env_batch(size_t n, const DevEnv env, const double *__restrict__ dir, float *__restrict__ rgb)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float c[3];
+    env_lookup(env, dir[3 * i], dir[3 * i + 1], dir[3 * i + 2], c);
+    rgb[3 * i] = c[0]; rgb[3 * i + 1] = c[1]; rgb[3 * i + 2] = c[2];
+}
+
 
 /* ---- the whole hit epilogue for a batch of hit records --------------------------------------
  * ri_intersection_state_build (intersection_state.c:99-248), every member a shader reads: P, Ng, Ns, tangent,
@@ -1115,6 +1270,58 @@ extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays,
     const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
     hipLaunchKernelGGL(k_dirt_batch_resolve, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        bl, N, near_clip, far_clip, d_slot_of_entry, d_t, d_near_hits, d_value, d_hit_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the environment gather's launchers (kernels above): the two resolves -- a group of LH_ENV_GROUP lanes per pixel / list entry -- and the fetch alone.
+ * d_adir: the materialised directions, or NULL: the fused stage (the directions are made again from the hit records and keys) */
+static EnvGather env_gather(int ntheta, int nphi, unsigned long long seed, double scale, const lh_env_src_t *env, const double *d_hitrec,
+                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ)
+{
+    EnvGather gx;
+    gx.ntheta = ntheta; gx.nphi = nphi; gx.seed = seed; gx.hitrec = d_hitrec; gx.slot_key = d_slot_key; gx.adir = d_adir; gx.occ = d_occ;
+    gx.scale = scale; gx.env = env_of(*env);
+    return gx;
+}
+
+extern "C" int lh_render_launch_env_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
+                                            const lh_env_src_t *env, const uint32_t *d_slot_of_sample, const double *d_hitrec,
+                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
+                                            unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream)
+{
+    const size_t total = (size_t)w * h, per = 256 / LH_ENV_GROUP, nb = (total + per - 1) / per;
+    if (total == 0) return 0;
+    if (nb > 0x7fffffffu) return -1;
+    const EnvGather gx = env_gather(ntheta, nphi, seed, scale, env, d_hitrec, d_slot_key, d_adir, d_occ);
+    if (tex)
+        hipLaunchKernelGGL(k_env_resolve_tex, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, h, band_rows, xs, ys, gx, d_slot_of_sample, d_rgb,
+                           d_occ_total, *tex);
+    else
+        hipLaunchKernelGGL(k_env_resolve, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, h, band_rows, xs, ys, gx, d_slot_of_sample, d_rgb,
+                           d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_env_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
+                                                  unsigned long long seed, double scale, const lh_env_src_t *env, const uint32_t *d_slot_of_entry,
+                                                  const double *d_hitrec, const unsigned long long *d_slot_key, const double *d_adir,
+                                                  const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
+                                                  unsigned long long *d_occ_total, void *stream)
+{
+    if (n_list == 0) return 0;
+    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
+    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
+    const size_t per = 256 / LH_ENV_GROUP;
+    hipLaunchKernelGGL(k_env_batch_resolve, dim3((unsigned)((n_list + per - 1) / per)), dim3(256), 0, (hipStream_t)stream, bl,
+                       env_gather(ntheta, nphi, seed, scale, env, d_hitrec, d_slot_key, d_adir, d_occ), d_slot_of_entry, d_occluded_count, d_rgb, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_env_fetch(size_t n, const lh_env_src_t *env, const double *d_dir, float *d_rgb, void *stream)
+{
+    if (n == 0) return 0;
+    if ((n + 255) / 256 > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_env_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, env_of(*env), d_dir, d_rgb);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

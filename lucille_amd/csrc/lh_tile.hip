@@ -11,6 +11,7 @@
 
 #include "lh_internal.h"
 #include "lh_dirt.h"
+#include "lh_env.h"
 
 #define ensure_buf lh_ensure_buf
 
@@ -88,12 +89,17 @@ struct ao_totals { unsigned long long nhit, nocc, cnt[LH_CNT_DEV]; bool fused; }
  * generates the ray in its refill and stores that word at its retire (lh_launch_trace_dirt).  Materialised: gather rays in HBM, ONE bounded
  * closest-hit launch through the ray dumps' kernels with a bound array filled with far_clip.  nocc then totals the bounded hits */
 struct dirt_stage { lh_dirt_params_t p; lh_dirt_scratch *ts; };
+/* env: the stage of the environment gather (lh_env.h) -- the AO stage's rays (the hit records were built with the gather's origin) and its any-hit
+ * answers, but one per RAY: what the stage leaves is a byte, 0 or 1, at element slot * N + r of b->occ, for the caller's colour resolve; fused and
+ * materialised differ only in who wrote it.  fused: the any-hit kernel stores the byte where the AO stage counts (lh_launch_trace_env).  Materialised:
+ * the AO stage's own path, whose any-hit launch writes that array.  nocc totals the occluded rays, as for AO */
+#define LH_ENV_LATE_MAX ((size_t)1 << 28)        /* gather rays (256 MiB of bytes) up to which a stage is sized for its worst case, the count left on the device */
 #define LH_DIRT_CHUNK ((size_t)1 << 30)          /* rays of one bounded launch at most (a list holds 2^30 entries) */
 #define LH_DIRT_LATE_MAX ((size_t)1 << 27)       /* gather rays (1 GiB of t) up to which a stage is sized for its worst case, the count left on the device */
 template <class Resolve>
 static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t nmax, ao_grid g, uint64_t seed, const void *d_uniforms,
                     const unsigned long long *d_nhit, unsigned long long *d_nocc, unsigned long long *cnt, const lh_launch_opt &opt,
-                    stage_timer *tm, bool fused, bool late, Resolve resolve, const dirt_stage *dirt, hipStream_t s, ao_totals *out)
+                    stage_timer *tm, bool fused, bool late, Resolve resolve, const dirt_stage *dirt, bool env, hipStream_t s, ao_totals *out)
 {
     const unsigned long long N = (unsigned long long)g.N;
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
@@ -122,7 +128,7 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
     };
     if (fused) {
         const size_t nslots = late ? nmax : (size_t)nhit;
-        if (dirt ? ensure_buf(&dirt->ts->t, nslots * (size_t)N * 8) : ensure_buf(&b->occcount, nslots * sizeof(unsigned int))) return -1;
+        if (dirt ? ensure_buf(&dirt->ts->t, nslots * (size_t)N * 8) : env ? ensure_buf(&b->occ, nslots * (size_t)N) : ensure_buf(&b->occcount, nslots * sizeof(unsigned int))) return -1;
         qslot = lh_aoq_slot(a, s);
         if (qslot < 0) return -1;
         lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget, its clocks */
@@ -140,6 +146,10 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
         if (dirt) {
             if (lh_launch_trace_dirt(&sc, &src, dirt->p.far_clip, (double *)dirt->ts->t.p, cnt, &ctx) != 0)
                 return fail("%sfused dirt launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
+        } else
+        if (env) {
+            if (lh_launch_trace_env(&sc, &src, (uint8_t *)b->occ.p, cnt, &ctx) != 0)
+                return fail("%sfused environment-gather launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
         } else
         if (lh_launch_trace_ao(&sc, &src, (unsigned int *)b->occcount.p, cnt, &ctx) != 0)
             return fail("%sfused AO launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
@@ -213,11 +223,30 @@ static int dirt_params(const char *what, const lh_dirt_params_t *params, lh_dirt
     return 0;
 }
 
+/* NULL: the defaults (gather_sunsky's offset, ri_ibl_sample_cosweight's scale); else the caller's, if lh_env.h accepts them */
+static int env_params(const char *what, const lh_env_params_t *params, lh_env_params_t *out)
+{
+    const lh_env_params_t def = LH_ENV_DEFAULTS;
+    *out = params ? *params : def;
+    if (!lh_env_params_ok(out->eps, out->scale))
+        return fail("%s: bad environment-gather parameters (eps %g, scale %g: both finite, eps >= 0, scale >= 0)", what, out->eps, out->scale);
+    return 0;
+}
+
+/* the accelerator's environment as it stands now (never set: constant white; an explicit black environment stays black) */
+static lh_env_src_t env_source(const lh_accel_t *a)
+{
+    lh_env_src_t e;
+    for (int k = 0; k < 3; k++) e.rgb[k] = a->env_set ? a->env.rgb[k] : 1.0f;
+    e.map = a->d_env_map; e.w = a->env.width; e.h = a->env.height;
+    return e;
+}
+
 /* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands.  dirt (or NULL): the dirtmap
  * transport's tile -- the same pipeline with the dirt origin, the dirt stage and its resolve, in scratch of its own */
 static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0, int y0,
                      uint64_t valid_pixels, int ps, int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb,
-                     lh_tile_stats_t *stats, void *stream, const lh_dirt_params_t *dirt = NULL)
+                     lh_tile_stats_t *stats, void *stream, const lh_dirt_params_t *dirt = NULL, const lh_env_params_t *env = NULL)
 {
     const int h = nbands * band_rows;              /* lines of the batch */
     HIPCHK(hipSetDevice(a->device));
@@ -228,11 +257,14 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         return fail("AO pipeline: more than 2^34 samples in the frame (slot keys carry 34 bits)");
     if (S >= ((size_t)1 << 31)) return fail("AO pipeline: more than 2^31 samples in one batch; render the frame in tiles");     /* 32-bit sample indices on the device */
     const unsigned nb = (unsigned)((S + 255) / 256);
-    lh_ao_scratch *b = dirt ? &a->tile_dirt : &a->tile_ao;
+    lh_ao_scratch *b = dirt ? &a->tile_dirt : env ? &a->tile_env : &a->tile_ao;
+    const double eps = dirt ? dirt->eps : env ? env->eps : 1.0e-6;          /* the gather rays' offset along Ns */
+    const lh_env_src_t esrc = env_source(a);
     void *r_org, *r_dir, *r_prim, *r_t, *r_u, *r_v;          /* camera rays and their closest-hit records */
-    if (dirt) {          /* one block of its own (org | dir | t | u | v | prim): lh_render_scratch keeps showing the last AO tile */
-        if (ensure_buf(&a->d_rays, S * 76)) return -1;
-        double *base = (double *)a->d_rays.p;
+    if (dirt || env) {          /* one block of its own (org | dir | t | u | v | prim): lh_render_scratch keeps showing the last AO tile */
+        lh_buf *rays = dirt ? &a->d_rays : &a->e_rays;
+        if (ensure_buf(rays, S * 76)) return -1;
+        double *base = (double *)rays->p;
         r_org = base; r_dir = base + 3 * S; r_t = base + 6 * S; r_u = base + 7 * S; r_v = base + 8 * S; r_prim = base + 9 * S;
     } else {
         if (ensure_buf(&a->r_org, S * 24) || ensure_buf(&a->r_dir, S * 24) || ensure_buf(&a->r_prim, S * 4) ||
@@ -270,6 +302,13 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     if (tm) { HIPCHK(hipEventRecord(tm->ev[2], s)); opt.diag_clock += 3 * nwaves; }
     unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of k_ao_resolve's 64 counters */
     auto resolve = [&](bool from_counts) -> int {
+        if (env) {          /* from_counts: the stage ended fused -- no direction in memory, the resolve makes them again */
+            if (lh_render_launch_env_resolve(w, h, band_rows, ps, ps, g.ntheta, g.nphi, seed, env->scale, &esrc, (const uint32_t *)b->slot.p,
+                                             (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                                             from_counts ? NULL : (const double *)b->adir.p, (const uint8_t *)b->occ.p, (float *)d_rgb, a->d_total, tex, s) != 0)
+                return fail("environment-gather resolve kernel launch failed");
+            return 0;
+        }
         if (dirt) {
             if (lh_render_launch_dirt_resolve(w, h, band_rows, ps, ps, g.N, dirt->near_clip, dirt->far_clip, (const uint32_t *)b->slot.p,
                                               (const double *)dstage.ts->t.p, (float *)d_rgb, a->d_total, tex, s) != 0)
@@ -289,14 +328,15 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
                                      (const double *)r_dir, (const uint32_t *)r_prim, (const double *)r_t,
                                      (const double *)r_u, (const double *)r_v, (uint32_t *)b->blocks.p,
                                      (uint32_t *)b->slot.p, (double *)b->hitrec.p, (unsigned long long *)b->key.p,
-                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, dirt ? dirt->eps : 1.0e-6, s) != 0)
+                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, eps, s) != 0)
             return fail("compaction kernels failed: %s", hipGetErrorString(hipGetLastError()));
         HIPCHK(hipMemcpyAsync(d_nhit, a->d_total, sizeof(*d_nhit), hipMemcpyDeviceToDevice, s));
         /* 4-6.  Late: the persistent kernel's 32-bit ray index covers the worst case; the grouped order ("ao_group") needs the count on the host */
         const bool fused = a->ao_fused && !d_uniforms;
         /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; it has no grouped order) */
-        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && (dirt ? S * (size_t)g.N <= LH_DIRT_LATE_MAX : !a->dev.ao_group) && !getenv("LH_AO_SYNC");
-        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, dirt ? &dstage : NULL, s, &tot) != 0) return -1;
+        /* (so does the environment gather, a byte per ray) */
+        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && (dirt ? S * (size_t)g.N <= LH_DIRT_LATE_MAX : env ? S * (size_t)g.N <= LH_ENV_LATE_MAX : !a->dev.ao_group) && !getenv("LH_AO_SYNC");
+        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot) != 0) return -1;
     } else {          /* an empty scene: every sample is a miss */
         HIPCHK(hipMemsetAsync(b->slot.p, 0xFF, S * 4, s));
         HIPCHK(hipMemsetAsync(d_nhit, 0, sizeof(*d_nhit), s));
@@ -308,7 +348,7 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     }
     const size_t nao = (size_t)tot.nhit * g.N;
     if (tm && stage_report(*tm, a->r_diag.p, nwaves, S, tot.nhit, nao) != 0) return -1;
-    if (!dirt) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
+    if (!dirt && !env) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
     if (cnt) {
         lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
@@ -347,6 +387,21 @@ extern "C" int lh_render_dirt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0
     if (!cam || !d_rgb) return fail("lh_render_dirt_tile: NULL argument");
     if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_dirt_tile: bad tile/sample counts");
     return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream, &p);
+}
+
+/* the environment-lit gather per camera sample (gather_sunsky's loop with ri_texture_ibl_fetch as its sky, ambientocclusion.c:206-324,407-411): a
+ * miss gives 0, a hit the three floats of lh_env_value, times the texture of its mesh where it has one */
+extern "C" int lh_render_env_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, int gather_nsamples,
+                                  const lh_env_params_t *params, uint64_t seed, const void *d_uniforms, void *d_rgb,
+                                  lh_tile_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);
+    lh_env_params_t p;
+    if (env_params("lh_render_env_tile", params, &p) != 0) return -1;
+    if (!a || !a->committed) return fail("lh_render_env_tile: accel not committed");
+    if (!cam || !d_rgb) return fail("lh_render_env_tile: NULL argument");
+    if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_env_tile: bad tile/sample counts");
+    return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream, NULL, &p);
 }
 
 /* nbands full-width bands of band_rows lines (band b = frame lines band_y0[b] ...; a band that runs past the frame is
@@ -426,7 +481,7 @@ static int ao_batch_args(const char *what, const lh_accel_t *a, size_t n_rays, b
 static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
                            const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
                            const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
-                           void *d_occluded_count, void *d_radiance, void *stream, const lh_dirt_params_t *dirt)
+                           void *d_occluded_count, void *d_radiance, void *stream, const lh_dirt_params_t *dirt, const lh_env_params_t *env = NULL)
 {
     const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, gather_nsamples, d_key, d_uniforms,
                                  d_index, n_index, d_count, d_occluded_count, d_radiance);
@@ -438,13 +493,19 @@ static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const
     hipStream_t s = (hipStream_t)stream;
     const ao_grid g = ao_sample_grid(gather_nsamples);
     const uint32_t *idx = (const uint32_t *)d_index, *cntp = (const uint32_t *)d_count;
-    lh_ao_scratch *b = dirt ? &a->batch_dirt : &a->batch_ao;
-    lh_buf *totals = dirt ? &a->d_tot : &a->b_tot;
+    /* env (checked parameters): lh_accel_env_device -- the environment gather's origin, scratch and resolve (d_radiance is then float[3 n_rays]) */
+    lh_ao_scratch *b = dirt ? &a->batch_dirt : env ? &a->batch_env : &a->batch_ao;
+    lh_buf *totals = dirt ? &a->d_tot : env ? &a->e_tot : &a->b_tot;
+    const lh_env_src_t esrc = env_source(a);
     if (ensure_buf(totals, sizeof(unsigned long long) * 65)) return -1;
     unsigned long long *d_nhit = (unsigned long long *)totals->p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
     const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->batch_dirt_t};
     /* 6. per-ray occlusion (dirt: bounded hits and value), scattered to the rays' own slots; slot NULL: an empty scene */
     auto resolve_with = [&](const uint32_t *slot, bool from_counts) -> int {
+        if (env)          /* from_counts: the stage ended fused -- no direction in memory, the resolve makes them again */
+            return lh_render_launch_env_batch_resolve(L, n_rays, idx, cntp, g.ntheta, g.nphi, seed, env->scale, &esrc, slot, (const double *)b->hitrec.p,
+                                                      (const unsigned long long *)b->key.p, from_counts ? NULL : (const double *)b->adir.p,
+                                                      (const uint8_t *)b->occ.p, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
         if (dirt)
             return lh_render_launch_dirt_batch_resolve(L, n_rays, idx, cntp, g.N, dirt->near_clip, dirt->far_clip, slot, (const double *)dstage.ts->t.p,
                                                        (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
@@ -468,22 +529,22 @@ static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, L, n_rays, idx, cntp, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
                                        (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)b->slot.p,
-                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, dirt ? dirt->eps : 1.0e-6, s) != 0)
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, dirt ? dirt->eps : env ? env->eps : 1.0e-6, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
     /* 4-6.  A fused stage always leaves the count on the device; the grouped order (set_param "ao_group") needs it on the host: materialised */
-    const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && (dirt || !a->dev.ao_group);
+    const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && (dirt || env || !a->dev.ao_group);
     /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; beyond that the count is read first) */
-    const bool late = fused && (!dirt || L * (size_t)g.N <= LH_DIRT_LATE_MAX);
+    const bool late = fused && (!dirt || L * (size_t)g.N <= LH_DIRT_LATE_MAX) && (!env || L * (size_t)g.N <= LH_ENV_LATE_MAX);
     auto resolve = [&](bool from_counts) -> int {
         if (resolve_with((const uint32_t *)b->slot.p, from_counts) != 0) return fail("%s: resolve kernel launch failed", what);
         return 0;
     };
     ao_totals tot;
-    if (ao_stage(a, dirt ? "lh_accel_dirt_device: " : "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, fused,
-                 late, resolve, dirt ? &dstage : NULL, s, &tot) != 0)
+    if (ao_stage(a, dirt ? "lh_accel_dirt_device: " : env ? "lh_accel_env_device: " : "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt,
+                 lh_launch_opt(), NULL, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot) != 0)
         return -1;
     if (cnt) lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nocc, true);
-    if (cnt && dirt) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
+    if (cnt && (dirt || env)) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
     return 0;
 }
 
@@ -507,6 +568,18 @@ extern "C" int lh_accel_dirt_device(lh_accel_t *a, size_t n_rays, const void *d_
     if (dirt_params("lh_accel_dirt_device", params, &p) != 0) return -1;
     return ao_batch_device("lh_accel_dirt_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
                            d_count, d_near_hits, d_value, stream, &p);
+}
+
+extern "C" int lh_accel_env_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                   const void *d_u, const void *d_v, int gather_nsamples, const lh_env_params_t *params, uint64_t seed,
+                                   const void *d_key, const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
+                                   void *d_occluded_count, void *d_rgb, void *stream)
+{
+    lh_guard guard(a);
+    lh_env_params_t p;
+    if (env_params("lh_accel_env_device", params, &p) != 0) return -1;
+    return ao_batch_device("lh_accel_env_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
+                           d_count, d_occluded_count, d_rgb, stream, NULL, &p);
 }
 
 extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
@@ -551,10 +624,11 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
     return 0;
 }
 
-/* lh_accel_ao_host, and with dirt (checked parameters) lh_accel_dirt_host */
+/* lh_accel_ao_host, and with dirt (checked parameters) lh_accel_dirt_host, with env lh_accel_env_host (radiance: 3 floats per ray) */
 static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
                          const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
-                         const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance, const lh_dirt_params_t *dirt)
+                         const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance, const lh_dirt_params_t *dirt,
+                         const lh_env_params_t *env = NULL)
 {
     const int go = ao_batch_args(what, a, n_rays, org && dir && prim && t && u && v, gather_nsamples, NULL, NULL, NULL, 0, NULL, NULL, NULL);
     if (go <= 0) return go;
@@ -564,7 +638,8 @@ static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const d
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 3 * sizeof(uint32_t) * n)) return -1;
+    const size_t nrad = env ? 3 * n : n;          /* floats of `radiance` */
+    if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 2 * sizeof(uint32_t) * n + sizeof(float) * nrad)) return -1;
     double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
     double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
     uint32_t *d_prim = (uint32_t *)(d_uni + need), *d_cnt = d_prim + n; float *d_rad = (float *)(d_cnt + n);
@@ -577,10 +652,10 @@ static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const d
     HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
     if (key) HIPCHK(hipMemcpyAsync(d_key, key, b_d, hipMemcpyHostToDevice, s));
     if (need) HIPCHK(hipMemcpyAsync(d_uni, uniforms, need * sizeof(double), hipMemcpyHostToDevice, s));
-    if (ao_batch_device(dirt ? "lh_accel_dirt_device" : "lh_accel_ao_device", a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
-                        key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s, dirt) != 0) return -1;
+    if (ao_batch_device(dirt ? "lh_accel_dirt_device" : env ? "lh_accel_env_device" : "lh_accel_ao_device", a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
+                        key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s, dirt, env) != 0) return -1;
     if (occluded_count) HIPCHK(hipMemcpyAsync(occluded_count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * n, hipMemcpyDeviceToHost, s));
+    if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * nrad, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
@@ -601,6 +676,53 @@ extern "C" int lh_accel_dirt_host(lh_accel_t *a, size_t n_rays, const double *or
     lh_dirt_params_t p;
     if (dirt_params("lh_accel_dirt_host", params, &p) != 0) return -1;
     return ao_batch_host("lh_accel_dirt_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, near_hits, value, &p);
+}
+
+extern "C" int lh_accel_env_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                                 const double *u, const double *v, int gather_nsamples, const lh_env_params_t *params, uint64_t seed,
+                                 const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *rgb)
+{
+    lh_guard guard(a);
+    lh_env_params_t p;
+    if (env_params("lh_accel_env_host", params, &p) != 0) return -1;
+    return ao_batch_host("lh_accel_env_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, occluded_count, rgb, NULL, &p);
+}
+
+/* the fetch alone: ri_texture_ibl_fetch (env_fetch, lh_pt.h) of the accelerator's environment for n directions.  Asynchronous, nothing read back */
+extern "C" int lh_accel_environment_device(lh_accel_t *a, size_t n, const void *d_dir, void *d_rgb, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_environment_device";
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (n == 0) return 0;
+    if (!d_dir || !d_rgb) return fail("%s: NULL array", what);
+    if (((uintptr_t)d_dir & 7u) != 0) return fail("%s: directions are doubles: the pointer is not 8-byte aligned", what);
+    if (((uintptr_t)d_rgb & 3u) != 0) return fail("%s: the output holds floats: the pointer is not 4-byte aligned", what);
+    if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
+    HIPCHK(hipSetDevice(a->device));
+    const lh_env_src_t esrc = env_source(a);
+    if (lh_render_launch_env_fetch(n, &esrc, (const double *)d_dir, (float *)d_rgb, stream) != 0)
+        return fail("%s: kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+/* the same for HOST arrays: copies up, the device call on the accelerator's stream, copies down */
+extern "C" int lh_accel_environment_host(lh_accel_t *a, size_t n, const double *dir, float *rgb)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_environment_host";
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (n == 0) return 0;
+    if (!dir || !rgb) return fail("%s: NULL array", what);
+    if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
+    HIPCHK(hipSetDevice(a->device));
+    if (ensure_buf(&a->e_host, n * (3 * sizeof(double) + 3 * sizeof(float)))) return -1;
+    double *d_dir = (double *)a->e_host.p; float *d_rgb = (float *)(d_dir + 3 * n);
+    HIPCHK(hipMemcpyAsync(d_dir, dir, sizeof(double) * 3 * n, hipMemcpyHostToDevice, a->stream));
+    if (lh_accel_environment_device(a, n, d_dir, d_rgb, a->stream) != 0) return -1;
+    HIPCHK(hipMemcpyAsync(rgb, d_rgb, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    return 0;
 }
 
 extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t *count)
