@@ -549,6 +549,61 @@ int  lh_render_env_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y
 int  lh_accel_environment_device(lh_accel_t *accel, size_t n, const void *d_dir_xyz, void *d_rgb_out, void *stream);
 int  lh_accel_environment_host(lh_accel_t *accel, size_t n, const double *dir_xyz, float *rgb_out);
 
+/* ---- the refraction chain: the reference's Whitted transport (trace_whitted, src/transport/whitted.c:32-151; ri_refract and
+ *      ri_reflect, src/render/reflection.c:26-128) ----
+ * No random number anywhere: a hit sends ONE ray on -- the refraction of the incoming direction at the interpolated normal, or its
+ * mirror image where the refraction does not exist -- and what that ray hits sends the next, max_depth rays at most; the chain's
+ * value is the accelerator's environment (lh_accel_set_environment: the angular map scaled by rgb, or the constant rgb; constant
+ * white if none was set -- the reference's "no environment map: black" is a constant black environment) seen by the ray that leaves
+ * the scene.
+ *   one bounce, from the hit's state as lh_accel_state_build_device gives it (P: doubles 0-2; n = Ns: doubles 6-8, not normalised
+ *     when it is interpolated; I: doubles 20-22), fp64 in this order, nothing contracted:
+ *       cos1 = (I0 n0 + I1 n1) + I2 n2;  cos1 < 0: c = -cos1, e = 1 / eta, N = n;  else: c = cos1, e = eta, N = -n
+ *       coeff = 1 - (e e) (1 - c c)
+ *       coeff <= 0 (total internal reflection): s = (double)(2.0f * (float)cos1), R = I - n s;  else q = e c - sqrt(coeff), R = q N + e I
+ *       n2 = (R0 R0 + R1 R1) + R2 R2;  n2 > (double)1.0e-17f: R = R * (1 / sqrt(n2))
+ *       next ray: org = P + eps R, dir = R
+ *   the chain of one hit record (state 0), d = 1 .. max_depth: ray d is the bounce of state d - 1, a closest-hit ray under the
+ *     pipeline's semantics (no self-primitive skip).  A miss: the chain escapes -- bounces = d, value = the three floats
+ *     lh_accel_environment_device gives for the direction of ray d.  A hit with d == max_depth: the chain is cut -- bounces =
+ *     d | LH_WHITTED_CUT, value = 0, 0, 0.  Any other hit: state d, from ray d and its record.  max_depth 0: bounces = LH_WHITTED_CUT.
+ *   parameters: eps finite and >= 0, eta finite and > 0, 0 <= max_depth <= 64, reserved == 0; NULL: LH_WHITTED_DEFAULTS.  Anything
+ *     else, NaN included, is refused ("bad refraction parameters").
+ * lh_accel_whitted_rays_device: the bounce alone for a caller's closest-hit records (LH_REC_F64) -- the next ray of every traced hit,
+ *   three doubles each into d_org_out / d_dir_out by ray id; the slots of misses and of rays that are not traced stay as they are.
+ *   Asynchronous on `stream`, nothing is read back.  List and count as for lh_accel_ao_device.
+ * lh_accel_whitted_device: the whole chain, list and count as for lh_accel_ao_device (an id listed twice gets that ray's answer
+ *   twice).  d_bounces[id] (uint32) = LH_AO_NO_HIT for a traced record that is a miss, else as above; d_end_org / d_end_dir[3 id ..]
+ *   (doubles) = the last ray traced for the id -- a miss record, and a hit with max_depth == 0, leave them as they are; d_rgb[3 id ..]
+ *   (floats) = value, three 0.0f for a miss record.  Any of the four may be NULL.  A record whose primitive id is not one of the
+ *   scene's counts as a miss: in an empty scene every record does, no chain starts.  Synchronous on `stream`: one launch pair per
+ *   depth over lists that stay on the device, one read-back at the end.  With lh_accel_trace_statistics on, `rays` advances by the
+ *   chain rays traced.  Scratch of its own, sized by list entries.
+ *   -1 (lh_last_error), nothing enqueued or written: bad parameters, n_rays >= 2^31, n_index > 2^30, a list / count / bounces / rgb
+ *   pointer that is not 4-byte aligned, a ray / record / end-ray pointer that is not 8-byte aligned (prim: 4), an uncommitted
+ *   accelerator, a NULL ray or record array with n_rays > 0.  n_rays == 0 returns 0 and looks at no array.
+ * lh_accel_whitted_host: the same for HOST arrays (copies up, the device call on the accelerator's stream, copies down; every ray
+ *   is traced).
+ * lh_render_whitted_tile: ri_transport_whitted per camera sample (the samples of lh_render_primary_rays) -- a camera miss gives the
+ *   environment in the camera ray's direction (whitted.c:135-139), a hit its chain's value; no texture multiply (whitted.c has
+ *   none); sub-samples are widened to double, added per channel in sample order, scaled, converted, clamped and written in image
+ *   orientation as lh_render_env_tile does.  stats->paths = camera samples, stats->rays = camera rays + chain rays,
+ *   stats->max_depth_reached = the largest d traced.  A frame does not depend on its tiling. */
+typedef struct lh_whitted_params { double eps, eta; int max_depth, reserved; } lh_whitted_params_t;
+#define LH_WHITTED_DEFAULTS { 1.0e-7, 1.33, 8, 0 }   /* whitted.c:38,46,24 */
+#define LH_WHITTED_CUT 0x80000000u
+int  lh_accel_whitted_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                                  const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                                  const lh_whitted_params_t *params, const void *d_index, size_t n_index, const void *d_count,
+                                  void *d_org_out, void *d_dir_out, void *stream);
+int  lh_accel_whitted_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                             const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                             const lh_whitted_params_t *params, const void *d_index, size_t n_index, const void *d_count,
+                             void *d_bounces, void *d_end_org, void *d_end_dir, void *d_rgb, void *stream);
+int  lh_accel_whitted_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,
+                           const double *t, const double *u, const double *v, const lh_whitted_params_t *params,
+                           uint32_t *bounces, double *end_org, double *end_dir, float *rgb);
+
 /* ---- material textures: the multiply both occlusion transports end with (src/transport/ambientocclusion.c:393-401, dirtmap.c:273-281) ----
  * Where the hit's mesh has a texture: ri_texture_fetch(texcol, texture, s, t); radiance[k] *= texcol[k].
  *   texture: height rows of width texels, 4 floats (RGBA) each, row 0 first (ri_texture_t.data, src/render/texture.h:21-29), no flip.
@@ -610,6 +665,9 @@ int  lh_render_pt_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0
                        int spp_begin, int spp_count, int spp_total, int max_path_vertices,
                        float kd, const float env_rgb[3], uint64_t seed, void *d_rgb,
                        lh_pt_stats_t *stats, void *stream);
+/* the refraction chain's tile (described with lh_accel_whitted_device above; its statistics are this struct's) */
+int  lh_render_whitted_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
+                            const lh_whitted_params_t *params, void *d_rgb, lh_pt_stats_t *stats, void *stream);
 
 /* ---- path tracer with the reference's three reflection types (src/transport/pathtrace.c:189-314,407-537) ----
  * Per-mesh material = ri_material_t (src/render/material.h:21-30; defaults of ri_material_new: kd 1, ks 0, kt 0,

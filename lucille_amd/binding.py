@@ -119,6 +119,17 @@ class EnvParams(C.Structure):
         super().__init__(float(eps), float(scale))
 
 
+class WhittedParams(C.Structure):
+    """lh_whitted_params_t: origin offset, relative refractive index and depth limit of the refraction chain (defaults:
+    LH_WHITTED_DEFAULTS, the constants of whitted.c); reserved must stay 0"""
+    _fields_ = [("eps", C.c_double), ("eta", C.c_double), ("max_depth", C.c_int), ("reserved", C.c_int)]
+
+    def __init__(self, eps=1.0e-7, eta=1.33, max_depth=8, reserved=0):
+        super().__init__(float(eps), float(eta), int(max_depth), int(reserved))
+
+
+WHITTED_CUT = 0x80000000          # LH_WHITTED_CUT: the chain was cut at the depth limit (the low bits: that depth)
+
 # lh_beam_set_t (include/lucille_hip.h): a beam as lucille's ri_beam_set leaves it -- 232 bytes
 BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)), ("normal", np.float64, (4, 3)),
                            ("dominant_axis", np.int32), ("dirsign", np.int32, (3,))])
@@ -137,6 +148,7 @@ ABI_SYMBOLS = [
     "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
     "lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile",
     "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
+    "lh_accel_whitted_rays_device", "lh_accel_whitted_device", "lh_accel_whitted_host", "lh_render_whitted_tile",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
     "lh_multi_add_rib_scene", "lh_multi_commit", "lh_multi_set_material", "lh_multi_set_environment", "lh_multi_intersect_host",
@@ -237,6 +249,12 @@ def lib():
                                          C.POINTER(TileStats), vp]
         L.lh_accel_environment_device.argtypes = [vp, sz, vp, vp, vp]
         L.lh_accel_environment_host.argtypes = [vp, sz, vp, vp]
+    if hasattr(L, "lh_accel_whitted_device"):            # an older library under LH_LIBRARY (A/B runs in tools/) has no refraction chain
+        wpp = C.POINTER(WhittedParams)
+        L.lh_accel_whitted_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, wpp, vp, sz, vp, vp, vp, vp]
+        L.lh_accel_whitted_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, wpp, vp, sz, vp, vp, vp, vp, vp, vp]
+        L.lh_accel_whitted_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, wpp, vp, vp, vp, vp]
+        L.lh_render_whitted_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, wpp, vp, C.POINTER(PtStats), vp]
     if hasattr(L, "lh_accel_set_texture"):               # an older library under LH_LIBRARY (the parent's build in tools/tex_frames.py) has no textures
         L.lh_accel_set_texture.argtypes = [vp, u32, vp, i32, i32]
         L.lh_accel_set_texture_device.argtypes = [vp, u32, vp, i32, i32, vp]
@@ -835,6 +853,21 @@ class HipAccel:
                                          C.byref(st), C.c_void_p(stream)), "lh_render_env_tile")
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
+    def render_whitted_tile(self, cam, x0, y0, w, h, pixel_samples, params=None, out=None, stream=None):
+        """lh_render_whitted_tile: the refraction chain's tile (params: a WhittedParams, None: the defaults) -- a camera miss sees the
+        environment, a hit what its chain of refraction rays ends in -> (rgb float32 [h,w,3] CUDA tensor in image orientation, stats
+        dict: paths = camera samples, rays = camera + chain rays, max_depth_reached = the deepest chain ray traced)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = PtStats()
+        _check(self.L.lh_render_whitted_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, None if params is None else C.byref(params),
+                                             _dptr(out), C.byref(st), C.c_void_p(stream)), "lh_render_whitted_tile")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
     def render_ao_frame_host(self, cam, pixel_samples, gather_nsamples, seed=1, tile=0):
         """lh_render_ao_frame_host: the whole frame into host memory -> (float32 [H, W, 3] numpy, top row first; stats)"""
         rgb = np.empty((cam.height, cam.width, 3), np.float32)
@@ -1193,6 +1226,96 @@ class HipAccel:
         rgb = np.empty((d.shape[0], 3), np.float32)
         _check(self.L.lh_accel_environment_host(self.h, d.shape[0], d.ctypes.data, rgb.ctypes.data), "lh_accel_environment_host")
         return rgb
+
+    # ---- the refraction chain for a caller's batch of hit records (lh_whitted.h) --------
+    def whitted_rays_device(self, org, dr, records, params=None, index=None, count=None, out=None, stream=None):
+        """lh_accel_whitted_rays_device: the bounce alone -- the refraction ray (or its mirror image, at a total internal reflection)
+        every traced hit of the batch sends on; arguments as whitted_device.  Returns (org_out, dir_out), float64 [n, 3]: row id is
+        written for a traced hit and stays as it is for a miss or a ray that is not listed (out=None: torch.empty, UNSPECIFIED there).
+        Asynchronous on the stream, nothing is read back."""
+        import torch
+        what = "whitted_rays_device"
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, None, None)
+        params = self._whitted_params(what, params)
+        ip, ni, cp = _list_args(index, count, what)
+        if index is None and count is not None:
+            ni = n
+        if out is None:
+            out = (torch.empty((n, 3), dtype=torch.float64, device=org.device), torch.empty((n, 3), dtype=torch.float64, device=org.device))
+        if not isinstance(out, (tuple, list)) or len(out) != 2:
+            raise ValueError("%s: out must be an (org_out, dir_out) pair" % what)
+        for name, x in (("org_out", out[0]), ("dir_out", out[1])):
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float64 and tuple(x.shape) == (n, 3) and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [n, 3]" % (what, name))
+        if stream is None:
+            stream = torch.cuda.current_stream(org.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_whitted_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), C.byref(params),
+                                                   ip, ni, cp, _dptr(out[0]), _dptr(out[1]), C.c_void_p(stream)), "lh_accel_whitted_rays_device")
+        return out
+
+    def whitted_device(self, org, dr, records, params=None, index=None, count=None, out=None, stream=None):
+        """lh_accel_whitted_device: the reference's Whitted transport for a batch of rays and their closest-hit records (`records` = the
+        (prim, t, u, v) tensors intersect_device returned for org / dr, float64 rays): every hit sends a chain of up to
+        params.max_depth refraction rays on, which ends in the accelerator's environment (set_environment) or at the depth limit.
+        params: a WhittedParams (None: eps 1e-7, eta 1.33, max_depth 8); index / count: a device list as for ao_device.  Returns
+        (bounces, end_org, end_dir, rgb): an int32 tensor [n] whose bits are uint32 -- AO_NO_HIT for a miss record, d for a chain whose
+        ray d left the scene, d | WHITTED_CUT for a chain cut at the limit --, the last ray traced for the id (float64 [n, 3] each;
+        untouched for a miss record and with max_depth 0) and the float32 [n, 3] colour (the environment seen by the escaping ray, zeros
+        for a cut chain and for a miss record).  out: such a 4-tuple to fill, any member None; with out=None all four are allocated
+        with torch.empty and what the call does not write is UNSPECIFIED.  Synchronous: the outputs are complete on return."""
+        import torch
+        what = "whitted_device"
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, None, None)
+        params = self._whitted_params(what, params)
+        dev = org.device
+        ip, ni, cp = _list_args(index, count, what)
+        if index is None and count is not None:
+            ni = n
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float64, device=dev),
+                   torch.empty((n, 3), dtype=torch.float64, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 4:
+            raise ValueError("%s: out must be a (bounces, end_org, end_dir, rgb) 4-tuple (any member may be None)" % what)
+        ob, oeo, oed, orgb = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if ob is not None and not (isinstance(ob, torch.Tensor) and ob.is_cuda and ob.dtype in words and ob.dim() == 1 and ob.shape[0] == n and ob.is_contiguous()):
+            raise ValueError("%s: bounces must be a contiguous int32 / uint32 device tensor [n]" % what)
+        for name, x, dt in (("end_org", oeo, torch.float64), ("end_dir", oed, torch.float64), ("rgb", orgb, torch.float32)):
+            if x is not None and not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dt and tuple(x.shape) == (n, 3) and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous %s device tensor [n, 3]" % (what, name, "float64" if dt == torch.float64 else "float32"))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_whitted_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), C.byref(params),
+                                              ip, ni, cp, _dptr(ob), _dptr(oeo), _dptr(oed), _dptr(orgb), C.c_void_p(stream)), "lh_accel_whitted_device")
+        return out
+
+    def whitted_host(self, org, dr, records, params=None):
+        """lh_accel_whitted_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v)), params as whitted_device ->
+        (bounces uint32 [n], end_org float64 [n, 3], end_dir float64 [n, 3], rgb float32 [n, 3]); the end rays of a miss record (and
+        of every record with max_depth 0) are zeros"""
+        what = "whitted_host"
+        params = self._whitted_params(what, params)
+        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
+        if d.shape[0] != n or len(records) != 4:
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
+        p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
+        u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
+        if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
+        b = np.empty(n, np.uint32); eo = np.zeros((n, 3)); ed = np.zeros((n, 3)); rgb = np.empty((n, 3), np.float32)
+        _check(self.L.lh_accel_whitted_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                            C.byref(params), b.ctypes.data, eo.ctypes.data, ed.ctypes.data, rgb.ctypes.data), "lh_accel_whitted_host")
+        return b, eo, ed, rgb
+
+    @staticmethod
+    def _whitted_params(what, params):
+        if params is None:
+            params = WhittedParams()
+        if not isinstance(params, WhittedParams):
+            raise ValueError("%s: params must be a WhittedParams" % what)
+        return params
 
     def _batch_stage_host(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms):
         o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]

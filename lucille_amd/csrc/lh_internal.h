@@ -8,6 +8,7 @@
  *   lh_plan.h       the geometry of a persistent launch (rows, checked pushes, the top of the tree in LDS, workgroups per CU, the cooperative
  *                   walk beside it, the cursor chunk): plain C, read by the launchers, by size_grid and by tests/cpu_model/lh_plan_check.c
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
+ *   lh_whitted.hip  the refraction chain (the reference's Whitted transport): its bounce kernel, its wavefront loop, its entry points
  */
 #ifndef LH_INTERNAL_H
 #define LH_INTERNAL_H
@@ -165,6 +166,9 @@ struct lh_accel {
      * `occ` of these, fused or materialised -- a batch's totals, the tile's camera rays and records, lh_accel_environment_host's staging */
     lh_ao_scratch tile_env, batch_env;
     lh_buf e_tot, e_rays, e_host;
+    /* the refraction chain (lh_whitted.hip; lh_whitted.h): the chain's compacted rays, ids and records, sized by list entries; its counts (one per depth);
+     * the tile's camera rays, their records and the samples' colours; lh_accel_whitted_host's staging */
+    lh_buf w_chain, w_counts, w_tile, w_host;
     uint64_t last_retraced;            /* rays the last counted launch finished outside the main kernel */
     int ao_fused;                      /* AO rays generated inside the any-hit kernel (default); 0: materialised in HBM */
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */
@@ -340,6 +344,14 @@ extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays,
                                                    uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream);
 /* the accelerator's environment as the launchers take it (lh_accel_set_environment; never set: constant white) */
 typedef struct lh_env_src { float rgb[3]; const void *map; int w, h; } lh_env_src_t;
+/* ... as it stands now (never set: constant white; an explicit black environment stays black) */
+static inline lh_env_src_t lh_env_source(const lh_accel_t *a)
+{
+    lh_env_src_t e;
+    for (int k = 0; k < 3; k++) e.rgb[k] = a->env_set ? a->env.rgb[k] : 1.0f;
+    e.map = a->d_env_map; e.w = a->env.width; e.h = a->env.height;
+    return e;
+}
 extern "C" int lh_render_launch_env_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
                                             const lh_env_src_t *env, const uint32_t *d_slot_of_sample, const double *d_hitrec,
                                             const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,

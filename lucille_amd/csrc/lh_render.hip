@@ -39,6 +39,7 @@
 namespace {
 
 #include "lh_pt.h"
+#include "lh_shade.h"
 
 /* the pixels of one device batch: nbands full-rows-of-w bands of band_rows lines each, band b starting at frame line
  * band_y0[b] (or y0 when there is a single band: a plain rectangle).  Pixel index p of the batch: band = p / (w * band_rows),
@@ -611,23 +612,7 @@ __global__ void k_dirt_batch_resolve(const BatchList bl, int N, double near_clip
 /* ---- the environment-lit gather (lh_env.h): the resolves read one byte per gather ray -- its any-hit answer, at element slot * N + r --
  * and, for the rays that are not occluded, fetch the environment in the ray's direction; whoever traced the rays wrote that array -------- */
 
-/* the accelerator's environment as a kernel argument */
-__device__ __host__ inline DevEnv env_of(const lh_env_src_t &e)
-{
-    DevEnv d;
-    d.rgb[0] = e.rgb[0]; d.rgb[1] = e.rgb[1]; d.rgb[2] = e.rgb[2];
-    d.map = (const float4 *)e.map; d.w = e.w; d.h = e.h;
-    return d;
-}
-
-/* env_fetch for a direction nobody checked: a component that is not finite would reach the texel index as a NaN; such a direction (its colour is
- * unspecified) is looked up as +z.  Every finite direction goes to env_fetch as it is: a zero vector or one whose norm under- or overflows
- * ends at u = v = 1/2 by env_fetch's own arithmetic */
-__device__ __forceinline__ void env_lookup(const DevEnv &e, double dx, double dy, double dz, float out[3])
-{
-    if (!(isfinite(dx) && isfinite(dy) && isfinite(dz))) { dx = 0.0; dy = 0.0; dz = 1.0; }
-    env_fetch(e, dx, dy, dz, out);
-}
+/* (the environment as a kernel argument, and env_lookup -- env_fetch for a direction nobody checked: lh_shade.h) */
 
 /* what the two resolves share beside their slots: the grid of the hemisphere, the generator's seed, the hit records and keys (the fused stage: the
  * directions are made again by lh_ao_ray_builtin) or the materialised directions (adir != NULL: the same doubles, or the replay's), the bytes */
@@ -780,21 +765,16 @@ __global__ void k_state_build(size_t n, const lh_dev_scene_t sc, const double *_
     if (i >= n) return;
     const uint32_t p = prim[i];
     if (p == LH_MISS_PRIM) return;
-    const double *tv = (const double *)sc.tri64 + 9 * (size_t)p;
     const double tt = t[i], uu = u[i], vv = v[i], w = 1.0 - uu - vv;
     double *o = state + LH_STATE_DOUBLES * i;
-    double Ng[3], v01[3], v02[3], I[3];
-    for (int k = 0; k < 3; k++) { o[k] = org[3 * i + k] + dir[3 * i + k] * tt; I[k] = dir[3 * i + k]; }
-    vnormalize(I);
-    for (int k = 0; k < 3; k++) { v01[k] = tv[3 + k] - tv[k]; v02[k] = tv[6 + k] - tv[k]; }
-    vcross(Ng, v01, v02); vnormalize(Ng);
-    bool has_n = false, has_tb = false;
-    if (nrm9) { const double x = nrm9[9 * (size_t)p]; has_n = (x == x); }
+    double P[3], Ng[3], Ns[3], I[3];
+    /* P, Ng, Ns, I: the part a transport of its own shares (lh_shade.h; k_whitted_bounce) */
+    const bool has_n = state_core<true>(sc.tri64, nrm9, p, org + 3 * i, dir + 3 * i, tt, uu, vv, P, Ng, Ns, I);
+    bool has_tb = false;
     if (has_n && tan9 && bin9) { const double x = tan9[9 * (size_t)p], y = bin9[9 * (size_t)p]; has_tb = (x == x) && (y == y); }
 #define LH_LERP9(A, dst) { const double *q_ = (A) + 9 * (size_t)p; \
         for (int k = 0; k < 3; k++) { const double a_ = q_[k] * w, b_ = q_[3 + k] * uu, c_ = q_[6 + k] * vv; (dst)[k] = (a_ + b_) + c_; } }
-    for (int k = 0; k < 3; k++) o[3 + k] = Ng[k];
-    if (has_n) LH_LERP9(nrm9, o + 6) else for (int k = 0; k < 3; k++) o[6 + k] = Ng[k];
+    for (int k = 0; k < 3; k++) { o[k] = P[k]; o[3 + k] = Ng[k]; o[6 + k] = Ns[k]; }
     if (has_tb) { LH_LERP9(tan9, o + 9) LH_LERP9(bin9, o + 12) }
     else {
         /* ri_ortho_basis(tmpbasis, Ng) (reflection.c:311-333) */

@@ -233,14 +233,7 @@ static int env_params(const char *what, const lh_env_params_t *params, lh_env_pa
     return 0;
 }
 
-/* the accelerator's environment as it stands now (never set: constant white; an explicit black environment stays black) */
-static lh_env_src_t env_source(const lh_accel_t *a)
-{
-    lh_env_src_t e;
-    for (int k = 0; k < 3; k++) e.rgb[k] = a->env_set ? a->env.rgb[k] : 1.0f;
-    e.map = a->d_env_map; e.w = a->env.width; e.h = a->env.height;
-    return e;
-}
+#define env_source lh_env_source          /* lh_internal.h */
 
 /* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands.  dirt (or NULL): the dirtmap
  * transport's tile -- the same pipeline with the dirt origin, the dirt stage and its resolve, in scratch of its own */
