@@ -531,8 +531,8 @@ int  lh_render_dirt_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int 
  *   d_rgb_out: what a caller needs to light a camera miss.  Asynchronous on `stream`, nothing is read back.  A zero or non-finite
  *   direction gives an unspecified colour; the texel index stays inside the map.  -1: an uncommitted accelerator, a NULL or misaligned
  *   array with n > 0.  lh_accel_environment_host: the same for HOST arrays (copies up, the device call, copies down).
- * Not part of this: the Preetham sky of sunsky.c and the sun's shadow ray (contribution_from_sunlight) -- another radiance source for
- *   the same stage -- and the qmc branch of ibl.c. */
+ * The Preetham sky of sunsky.c and the sun's shadow ray (contribution_from_sunlight) are another radiance source for the same stage:
+ *   the sun-and-sky light below (lh_accel_set_sky).  Not built: the qmc branch of ibl.c. */
 typedef struct lh_env_params { double eps, scale; } lh_env_params_t;
 #define LH_ENV_DEFAULTS { 1.0e-5, 1.0 }
 int  lh_accel_env_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
@@ -548,6 +548,54 @@ int  lh_render_env_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y
                         const void *d_uniforms, void *d_rgb, lh_tile_stats_t *stats, void *stream);
 int  lh_accel_environment_device(lh_accel_t *accel, size_t n, const void *d_dir_xyz, void *d_rgb_out, void *stream);
 int  lh_accel_environment_host(lh_accel_t *accel, size_t n, const double *dir_xyz, float *rgb_out);
+
+/* ---- the sun-and-sky light of the gather above (gather_sunsky with a sunsky light: ri_sunsky_get_sky_rgb, src/render/sunsky.c:329-415,
+ *      and contribution_from_sunlight, src/transport/ambientocclusion.c:153-199,312-321; the rule: lucille_amd/csrc/lh_sky.h) ----
+ * While a sky is set (lh_accel_set_sky), lh_accel_env_device, lh_accel_env_host and lh_render_env_tile read it in place of the
+ * environment:
+ *   rad_r = the analytic Preetham sky in the direction of gather ray r, rounded to float first: y and z swapped, zero below the horizon,
+ *     a direction within 0.001 of it pulled up and normalised, theta / phi / gamma and the three Perez functions in the reference's float
+ *     order, M1 and M2 from the chromaticity; from there rgb_k = Y (C0_k + M1 C1_k + M2 C2_k) / (L0 + M1 L1 + M2 L2) with C_j =
+ *     basis_rgb[j], L_j = basis_y[j]: the caller's colour pipeline's rgb and CIE y of the daylight basis spectra S0, S1, S2 (the
+ *     reference's 41-sample sum is linear in them).  The collapsed sum rounds differently from the reference's: the sky stays within
+ *     a measured bound of ri_sunsky_get_sky_rgb (|got - ref| <= 7.12e-6 max_k |ref_k|: four times the largest seen, tests/test_sky_rule.py), everything built on
+ *     its colours is bit for bit.  A direction that is not of unit length gives an unspecified colour (NaN possibly), never a fault.
+ *   with LH_SKY_SUN in flags, every hit traces one more any-hit ray from the gather's origin P + eps Ns along sun_dir, answered by a
+ *     plain any-hit launch (the semantics of lh_accel_intersect_device: no self-primitive skip -- a sun behind the surface is
+ *     shadowed by the hit's own triangle, as in the reference); where it is not occluded, sum_k = sum_k + (double)sun_rgb[k] after
+ *     the N gather rays, before value_k = (float)((scale * sum_k) / N).  The sun's ray draws nothing (the uniforms replay is
+ *     unchanged) and is not counted: count, stats->ao_rays, stats->ao_occluded and the trace statistics stay those of the N rays.
+ *   the tile does not multiply by the material texture (the reference's sunsky branch fetches none, ambientocclusion.c:369-375).
+ *   the reference's own call: gather_nsamples 64, eps 1e-5, scale 1 / pi.
+ * The path tracer and the refraction chain keep reading the environment.  With no sky set the three calls launch what they always did.
+ * Layout (168 bytes, 8-byte aligned; fixed): sun_theta 0, sun_phi 4, perez_x 8, perez_y 28, perez_Y 48, zenith_x 68, zenith_y 72,
+ *   zenith_Y 76, basis_rgb 80 ([j][k]: channel k of S_j), basis_y 116, sun_rgb 128, flags 140, sun_dir 144.
+ * lh_sky_from_site: the parts of ri_sunsky_init / init_sun_theta_phi that need no table, for a site (degrees; standard_meridian in hours,
+ *   as the reference multiplies it by 15), a day of the year, a time of day (hours) and a turbidity: the angles, the fifteen Perez
+ *   coefficients, the three zenith values and sun_dir in the reference's light convention (y and z swapped, lightsource.c:156-158).
+ *   basis_rgb, basis_y, sun_rgb and flags are left alone.  Host only, no accelerator.  -1: NULL or a non-finite argument.
+ * lh_accel_set_sky: after commit, as lh_accel_set_environment; the struct is copied; NULL removes the sky.  A struct with a non-finite
+ *   field or an undefined flag is refused ("bad sky parameters").
+ * lh_accel_sky_device / _host: the fetch alone, shaped like lh_accel_environment_device / _host; -1 with a message when no sky is set.
+ * Not built: the sky as a source of the path tracer and the refraction chain, create_sunsky_image, the RIB reader's
+ *   AreaLightSource "sunsky", and the glue's frame controller, which still declines a sunsky light. */
+#define LH_SKY_SUN   1u          /* trace the sun's shadow ray */
+#define LH_SKY_FLAGS 1u          /* the defined bits */
+typedef struct lh_sky {
+    float sun_theta, sun_phi;
+    float perez_x[5], perez_y[5], perez_Y[5];
+    float zenith_x, zenith_y, zenith_Y;
+    float basis_rgb[3][3];   /* the caller's colour pipeline's rgb of S0, S1, S2 */
+    float basis_y[3];        /* its CIE y of the same */
+    float sun_rgb[3];
+    uint32_t flags;          /* LH_SKY_SUN: trace the sun's shadow ray */
+    double sun_dir[3];       /* world space, as the reference's light->direction */
+} lh_sky_t;
+int  lh_sky_from_site(lh_sky_t *sky, float latitude, float longitude, float standard_meridian, int julian_day, float time_of_day,
+                      float turbidity);
+int  lh_accel_set_sky(lh_accel_t *accel, const lh_sky_t *sky);
+int  lh_accel_sky_device(lh_accel_t *accel, size_t n, const void *d_dir_xyz, void *d_rgb_out, void *stream);
+int  lh_accel_sky_host(lh_accel_t *accel, size_t n, const double *dir_xyz, float *rgb_out);
 
 /* ---- the refraction chain: the reference's Whitted transport (trace_whitted, src/transport/whitted.c:32-151; ri_refract and
  *      ri_reflect, src/render/reflection.c:26-128) ----
@@ -620,7 +668,8 @@ int  lh_accel_whitted_host(lh_accel_t *accel, size_t n_rays, const double *org_x
  * lh_render_ao_tile / _bands / _tile_host, lh_render_ao_frame_host, lh_render_dirt_tile, lh_render_env_tile, lh_multi_render_ao_frame_host and
  *   lh_dist_render_ao_frame_host multiply as soon as the accelerator holds at least one texture; with none they launch the kernels
  *   they always launched, with the same arguments.  Tile statistics, the replay uniforms and the fused / materialised stages do not
- *   depend on textures.  Not covered: the sun-and-sky branch, mip-maps, textures in the path tracer (lh_render_pt_*), and
+ *   depend on textures.  The sun-and-sky branch is built and, as in the reference, fetches no texture: lh_render_env_tile does not
+ *   multiply while a sky is set (lh_accel_set_sky).  Not covered: mip-maps, textures in the path tracer (lh_render_pt_*), and
  *   `Surface "texture"` in the RIB reader (it needs the reference's image loaders).
  * lh_accel_set_texture: rgba is HOST memory (width x height x 4 floats) and is copied.  Allowed for any mesh already added, before or
  *   after commit (trees do not depend on it; no device is touched before the first call that needs the texture there).  rgba == NULL

@@ -21,4 +21,4 @@ from .binding import (Camera, HipAccel, LucilleHipError, MISS, MODE_ANY, MODE_CL
                       VARIANT_DEFAULT, VARIANT_DIRECT,
                       VARIANT_SPEC, build_library, device_count, library_path,
                       HipMulti, HipDist, DIST_RCCL, DIST_SHM, Material, Environment, ALL_MESHES, PT_REFERENCE_WEIGHTS, ATTR_COLOR, ATTR_TANGENT, ATTR_BINORMAL,
-                      ATTR_TEXCOORD, ATTR_TEXCOORD_UNSHARED, STATE_DOUBLES, DirtParams, EnvParams, WhittedParams, WHITTED_CUT)
+                      ATTR_TEXCOORD, ATTR_TEXCOORD_UNSHARED, STATE_DOUBLES, DirtParams, EnvParams, WhittedParams, WHITTED_CUT, Sky, SKY_SUN)

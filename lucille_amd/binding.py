@@ -119,6 +119,38 @@ class EnvParams(C.Structure):
         super().__init__(float(eps), float(scale))
 
 
+SKY_SUN = 1                       # LH_SKY_SUN: trace the sun's shadow ray
+
+
+class Sky(C.Structure):
+    """lh_sky_t: the sun-and-sky light of the environment-lit gather (lh_sky.h) -- the Preetham sky's angles, Perez coefficients and
+    zenith values (from_site), the caller's colour pipeline's rgb and CIE y of the daylight basis spectra S0, S1, S2 (basis_rgb[j][k]:
+    channel k of S_j; basis_y[j]), the sun's colour and world-space direction, and flags (SKY_SUN: trace the sun's shadow ray)"""
+    _fields_ = [("sun_theta", C.c_float), ("sun_phi", C.c_float), ("perez_x", C.c_float * 5), ("perez_y", C.c_float * 5),
+                ("perez_Y", C.c_float * 5), ("zenith_x", C.c_float), ("zenith_y", C.c_float), ("zenith_Y", C.c_float),
+                ("basis_rgb", (C.c_float * 3) * 3), ("basis_y", C.c_float * 3), ("sun_rgb", C.c_float * 3), ("flags", C.c_uint32),
+                ("sun_dir", C.c_double * 3)]
+
+    @classmethod
+    def from_site(cls, latitude, longitude, standard_meridian, julian_day, time_of_day, turbidity, basis_rgb=None, basis_y=None,
+                  sun_rgb=(0.0, 0.0, 0.0), flags=0):
+        """lh_sky_from_site: what ri_sunsky_init leaves for a site (degrees; standard_meridian in hours), a day of the year, a time of
+        day (hours) and a turbidity; basis_rgb [3][3], basis_y [3], sun_rgb and flags are the caller's (zeros if not given)"""
+        s = cls()
+        if lib().lh_sky_from_site(C.byref(s), float(latitude), float(longitude), float(standard_meridian), int(julian_day),
+                                  float(time_of_day), float(turbidity)) != 0:
+            raise ValueError("Sky.from_site: a non-finite argument")
+        if basis_rgb is not None:
+            b = np.asarray(basis_rgb, np.float32).reshape(3, 3)
+            for j in range(3):
+                s.basis_rgb[j][:] = [float(x) for x in b[j]]
+        if basis_y is not None:
+            s.basis_y[:] = [float(x) for x in np.asarray(basis_y, np.float32).reshape(3)]
+        s.sun_rgb[:] = [float(x) for x in sun_rgb]
+        s.flags = int(flags)
+        return s
+
+
 class WhittedParams(C.Structure):
     """lh_whitted_params_t: origin offset, relative refractive index and depth limit of the refraction chain (defaults:
     LH_WHITTED_DEFAULTS, the constants of whitted.c); reserved must stay 0"""
@@ -148,6 +180,7 @@ ABI_SYMBOLS = [
     "lh_accel_state_build_device", "lh_accel_state_build_host", "lh_accel_ao_device", "lh_accel_ao_host", "lh_accel_ao_rays_device",
     "lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile",
     "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
+    "lh_sky_from_site", "lh_accel_set_sky", "lh_accel_sky_device", "lh_accel_sky_host",
     "lh_accel_whitted_rays_device", "lh_accel_whitted_device", "lh_accel_whitted_host", "lh_render_whitted_tile",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
@@ -249,6 +282,11 @@ def lib():
                                          C.POINTER(TileStats), vp]
         L.lh_accel_environment_device.argtypes = [vp, sz, vp, vp, vp]
         L.lh_accel_environment_host.argtypes = [vp, sz, vp, vp]
+    if hasattr(L, "lh_accel_set_sky"):                   # an older library under LH_LIBRARY (A/B runs in tools/) has no sun-and-sky light
+        L.lh_sky_from_site.argtypes = [C.POINTER(Sky), C.c_float, C.c_float, C.c_float, i32, C.c_float, C.c_float]
+        L.lh_accel_set_sky.argtypes = [vp, C.POINTER(Sky)]
+        L.lh_accel_sky_device.argtypes = [vp, sz, vp, vp, vp]
+        L.lh_accel_sky_host.argtypes = [vp, sz, vp, vp]
     if hasattr(L, "lh_accel_whitted_device"):            # an older library under LH_LIBRARY (A/B runs in tools/) has no refraction chain
         wpp = C.POINTER(WhittedParams)
         L.lh_accel_whitted_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, wpp, vp, sz, vp, vp, vp, vp]
@@ -1225,6 +1263,43 @@ class HipAccel:
         d = _np(dirs, np.float64).reshape(-1, 3)
         rgb = np.empty((d.shape[0], 3), np.float32)
         _check(self.L.lh_accel_environment_host(self.h, d.shape[0], d.ctypes.data, rgb.ctypes.data), "lh_accel_environment_host")
+        return rgb
+
+    # ---- the sun-and-sky light of the environment-lit gather (lh_sky.h) --------
+    def set_sky(self, sky):
+        """lh_accel_set_sky: from now on env_device / env_host / render_env_tile read this Sky in place of the environment -- the
+        Preetham sky as the radiance of an open gather ray and, with SKY_SUN in its flags, the sun's shadow ray per hit.  After commit;
+        the struct is copied.  A non-finite field or an undefined flag is refused."""
+        if not isinstance(sky, Sky):
+            raise ValueError("set_sky: sky must be a Sky")
+        _check(self.L.lh_accel_set_sky(self.h, C.byref(sky)), "lh_accel_set_sky")
+
+    def reset_sky(self):
+        """no sky: the gather reads the environment again"""
+        _check(self.L.lh_accel_set_sky(self.h, None), "lh_accel_set_sky")
+
+    def sky_device(self, dirs, out=None, stream=None):
+        """lh_accel_sky_device: the accelerator's sky (set_sky) seen in each of the directions `dirs` (contiguous float64 device tensor
+        [n, 3]; unit vectors: any other length gives an unspecified colour) -> float32 device tensor [n, 3].  Asynchronous on the stream."""
+        import torch
+        if not (isinstance(dirs, torch.Tensor) and dirs.is_cuda and dirs.dtype == torch.float64 and dirs.dim() == 2 and dirs.shape[1] == 3 and dirs.is_contiguous()):
+            raise ValueError("sky_device: dirs must be a contiguous float64 device tensor [n, 3]")
+        n = int(dirs.shape[0])
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=dirs.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 3) and out.is_contiguous()):
+            raise ValueError("sky_device: out must be a contiguous float32 device tensor [n, 3]")
+        if stream is None:
+            stream = torch.cuda.current_stream(dirs.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_sky_device(self.h, n, _dptr(dirs), _dptr(out), C.c_void_p(stream)), "lh_accel_sky_device")
+        return out
+
+    def sky_host(self, dirs):
+        """lh_accel_sky_host: host directions [n, 3] -> float32 [n, 3]"""
+        d = _np(dirs, np.float64).reshape(-1, 3)
+        rgb = np.empty((d.shape[0], 3), np.float32)
+        _check(self.L.lh_accel_sky_host(self.h, d.shape[0], d.ctypes.data, rgb.ctypes.data), "lh_accel_sky_host")
         return rgb
 
     # ---- the refraction chain for a caller's batch of hit records (lh_whitted.h) --------

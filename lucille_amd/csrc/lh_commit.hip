@@ -521,7 +521,7 @@ static void release_device(lh_accel_t *a)
         for (lh_buf *b : {&sc->slot, &sc->hitrec, &sc->key, &sc->occcount, &sc->aorg, &sc->adir, &sc->occ, &sc->blocks}) free_buf(b);
     for (lh_dirt_scratch *sc : {&a->tile_dirt_t, &a->batch_dirt_t})
         for (lh_buf *b : {&sc->t, &sc->bound, &sc->prim, &sc->uv}) free_buf(b);
-    for (lh_buf *b : {&a->d_tot, &a->d_rays, &a->e_tot, &a->e_rays, &a->e_host, &a->w_chain, &a->w_counts, &a->w_tile, &a->w_host}) free_buf(b);
+    for (lh_buf *b : {&a->d_tot, &a->d_rays, &a->e_tot, &a->e_rays, &a->e_host, &a->s_tile, &a->s_batch, &a->w_chain, &a->w_counts, &a->w_tile, &a->w_host}) free_buf(b);
     if (a->d_total) (void)hipFree(a->d_total);
     scene_row rows[LH_SCENE_ROWS];
     scene_rows(a, NULL, rows);

@@ -10,7 +10,8 @@
  *
  * `scale` is the reference's m: 1 / M_PI in gather_sunsky (Lo = m * col / nsamples), pi * (1 / pi) = 1 in ri_ibl_sample_cosweight.
  * Every operation is a single fp64 add, multiply or divide in the order written; the one product feeds a quotient, not a sum: nothing a
- * compiler could contract.  The Preetham sky and the sun's shadow ray are not part of this rule: another radiance source for the same sum.
+ * compiler could contract.  The Preetham sky and the sun's shadow ray are another radiance source for the same sum: lh_sky.h states them (the sky's
+ * colour of a direction, and the sun's term, which enters the sum after the N rays and before lh_env_finish); the sum itself stays here.
  *
  * DESIGN.md 10.0d has the stage built on it; tests/test_gpu_envgather.py pins it to the oracle.
  */

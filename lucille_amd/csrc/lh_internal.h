@@ -57,6 +57,9 @@ typedef struct lh_gather_out { double *nrm9, *attr9[3], *st6; uint8_t *inside; }
 struct lh_dmesh_event { hipStream_t stream; hipEvent_t ev; };          /* the last copy enqueued on a caller's stream: the commit waits for it */
 
 struct lh_buf { void *p; size_t cap; };
+/* the accelerator's sun-and-sky light as the launchers take it (lh_accel_set_sky; lh_sky.h): the caller's struct and the three Perez denominators,
+ * which depend on the sky alone and are made once, on the host, when it is set */
+typedef struct lh_sky_src { lh_sky_t sky; float den[3]; } lh_sky_src_t;
 /* material textures (lh_tex.h, lh_tex.hip).  A block of texels, shared by the meshes one setter call gave it to: a host copy until the first call
  * that needs it on the device (lh_accel_set_texture works without a device, before commit), or the device copy lh_accel_set_texture_device
  * enqueued on the caller's stream (ev: recorded behind that copy, waited for once) */
@@ -166,6 +169,10 @@ struct lh_accel {
      * `occ` of these, fused or materialised -- a batch's totals, the tile's camera rays and records, lh_accel_environment_host's staging */
     lh_ao_scratch tile_env, batch_env;
     lh_buf e_tot, e_rays, e_host;
+    /* the sun-and-sky light (lh_accel_set_sky; lh_sky.h): sky_set 0 = none, the gather reads the environment; the sun's rays of a tile / a batch and
+     * their any-hit bytes (per hit slot: org | dir | occ) */
+    lh_sky_src_t sky; int sky_set;
+    lh_buf s_tile, s_batch;
     /* the refraction chain (lh_whitted.hip; lh_whitted.h): the chain's compacted rays, ids and records, sized by list entries; its counts (one per depth);
      * the tile's camera rays, their records and the samples' colours; lh_accel_whitted_host's staging */
     lh_buf w_chain, w_counts, w_tile, w_host;
@@ -362,6 +369,20 @@ extern "C" int lh_render_launch_env_batch_resolve(size_t n_list, size_t n_rays, 
                                                   const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
                                                   unsigned long long *d_occ_total, void *stream);
 extern "C" int lh_render_launch_env_fetch(size_t n, const lh_env_src_t *env, const double *d_dir, float *d_rgb, void *stream);
+/* ... under the sun-and-sky light (lh_sky_src_t, above) */
+extern "C" int lh_render_launch_sky_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
+                                            const lh_sky_src_t *sky, const uint8_t *d_sun_occ, const uint32_t *d_slot_of_sample, const double *d_hitrec,
+                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
+                                            unsigned long long *d_occ_total, void *stream);
+extern "C" int lh_render_launch_sky_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
+                                                  unsigned long long seed, double scale, const lh_sky_src_t *sky, const uint8_t *d_sun_occ,
+                                                  const uint32_t *d_slot_of_entry, const double *d_hitrec, const unsigned long long *d_slot_key,
+                                                  const double *d_adir, const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
+                                                  unsigned long long *d_occ_total, void *stream);
+extern "C" int lh_render_launch_sky_fetch(size_t n, const lh_sky_src_t *sky, const double *d_dir, float *d_rgb, void *stream);
+/* one ray per hit slot from the slot's hit record along sun_dir (d_nslots or NULL: the slot count on the device, nslots its upper bound) */
+extern "C" int lh_render_launch_sun_rays(size_t nslots, const unsigned long long *d_nslots, const double *d_hitrec, const double sun_dir[3],
+                                         double *d_org, double *d_dir, void *stream);
 extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
                                             const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
                                             const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,

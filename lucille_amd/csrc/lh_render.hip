@@ -34,6 +34,7 @@
 #include "lh_ao.h"
 #include "lh_dirt.h"
 #include "lh_env.h"
+#include "lh_sky.h"
 #include "lh_tex.h"
 
 namespace {
@@ -633,7 +634,25 @@ struct EnvGather {
 #ifndef LH_ENV_GROUP
 #define LH_ENV_GROUP 4           /* a power of two from 4 (three channel lanes) to 64; why 4: DESIGN.md 10.0d */
 #endif
-__device__ __forceinline__ double env_slot_sum(const EnvGather &gx, bool have, uint32_t slot, float (*park)[3], unsigned int &count)
+/* the radiance of an open gather ray, the resolves' one difference and so their template parameter: the accelerator's environment, or the
+ * sun-and-sky light (lh_sky.h) -- the sky and its Perez denominators by value in the kernel's arguments (uniform over the launch:
+ * scalar loads, nothing to allocate), and one byte per slot, the any-hit answer of the sun's ray (NULL: no sun) */
+struct RadEnv {
+    const DevEnv &env;
+    __device__ __forceinline__ void operator()(double dx, double dy, double dz, float c[3]) const { env_lookup(env, dx, dy, dz, c); }
+};
+struct RadSky {
+    const lh_sky_src_t &s;
+    __device__ __forceinline__ void operator()(double dx, double dy, double dz, float c[3]) const { lh_sky_rgb_den(&s.sky, s.den, dx, dy, dz, c); }
+};
+/* the sun's term of channel lane gl (0-2) of a hit slot: after the last pass, before lh_env_finish */
+__device__ __forceinline__ double sky_sun_term(const lh_sky_src_t &s, const uint8_t *__restrict__ sun_occ, uint32_t slot, int gl, double sum)
+{
+    const float c = gl == 0 ? s.sky.sun_rgb[0] : (gl == 1 ? s.sky.sun_rgb[1] : s.sky.sun_rgb[2]);
+    return lh_sky_add_sun(sum, sun_occ[slot] != 0, c);
+}
+template <class Rad>
+__device__ __forceinline__ double env_slot_sum(const EnvGather &gx, const Rad &rad, bool have, uint32_t slot, float (*park)[3], unsigned int &count)
 {
     LH_NC
     const int N = gx.ntheta * gx.nphi;
@@ -652,7 +671,7 @@ __device__ __forceinline__ double env_slot_sum(const EnvGather &gx, bool have, u
             if (gx.adir) { dx = gx.adir[3 * ray]; dy = gx.adir[3 * ray + 1]; dz = gx.adir[3 * ray + 2]; }
             else lh_ao_ray_builtin(gx.hitrec + LH_HITREC_DOUBLES * (size_t)slot, gx.slot_key[slot], gx.seed, gx.ntheta, gx.nphi, r, ox, oy, oz, dx, dy, dz);
             float c[3];
-            env_lookup(gx.env, dx, dy, dz, c);
+            rad(dx, dy, dz, c);
             mine[gl][0] = c[0]; mine[gl][1] = c[1]; mine[gl][2] = c[2];
         }
         const unsigned long long gmask = LH_ENV_GROUP >= 64 ? ~0ull : ((1ull << (LH_ENV_GROUP & 63)) - 1ull);
@@ -667,9 +686,10 @@ __device__ __forceinline__ double env_slot_sum(const EnvGather &gx, bool have, u
 
 /* k_ao_resolve for the environment gather's tile, a group of lanes per pixel: a miss gives 0 (ambientocclusion.c:407-411), a hit the three floats of
  * lh_env_value; sub-samples accumulate per channel and are written as ao_resolve does.  TEX: times the texture of the hit's mesh, as ao_resolve */
-template <bool TEX>
-__device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather &gx, const uint32_t *__restrict__ slot_of_sample,
-                                            float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs *tx)
+template <bool TEX, class Rad>
+__device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather &gx, const Rad &rad, const uint32_t *__restrict__ slot_of_sample,
+                                            float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs *tx,
+                                            const lh_sky_src_t *sky = NULL, const uint8_t *__restrict__ sun_occ = NULL)
 {
     LH_NC
     __shared__ float park[256][3];
@@ -684,9 +704,10 @@ __device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs,
         const uint32_t slot = inside ? slot_of_sample[pix * S + s] : LH_MISS_PRIM;
         const bool hit = slot != LH_MISS_PRIM;
         unsigned int c;
-        const double sum = env_slot_sum(gx, hit, slot, park, c);
+        double sum = env_slot_sum(gx, rad, hit, slot, park, c);
         if (gl == 0) nocc += c;
         double val = 0.0;
+        if (sun_occ && hit && gl < 3) sum = sky_sun_term(*sky, sun_occ, slot, gl, sum);
         if (hit && gl < 3) val = (double)lh_env_finish(gx.scale, sum, N);
         if (TEX) {
             double tc[4];
@@ -705,20 +726,30 @@ __device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs,
 __global__ __launch_bounds__(256) void k_env_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather gx, const uint32_t *__restrict__ slot_of_sample,
                                                      float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
 {
-    env_resolve<false>(w, h, band_rows, xs, ys, gx, slot_of_sample, rgb, occ_total, NULL);
+    env_resolve<false>(w, h, band_rows, xs, ys, gx, RadEnv{gx.env}, slot_of_sample, rgb, occ_total, NULL);
+}
+
+/* ... under the sun-and-sky light: no texture multiply (ambientocclusion.c:369-375) */
+__global__ __launch_bounds__(256) void k_sky_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather gx, const lh_sky_src_t sky,
+                                                     const uint8_t *__restrict__ sun_occ, const uint32_t *__restrict__ slot_of_sample,
+                                                     float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
+{
+    env_resolve<false>(w, h, band_rows, xs, ys, gx, RadSky{sky}, slot_of_sample, rgb, occ_total, NULL, &sky, sun_occ);
 }
 
 __global__ __launch_bounds__(256) void k_env_resolve_tex(int w, int h, int band_rows, int xs, int ys, const EnvGather gx, const uint32_t *__restrict__ slot_of_sample,
                                                          float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs tx)
 {
-    env_resolve<true>(w, h, band_rows, xs, ys, gx, slot_of_sample, rgb, occ_total, &tx);
+    env_resolve<true>(w, h, band_rows, xs, ys, gx, RadEnv{gx.env}, slot_of_sample, rgb, occ_total, &tx);
 }
 
 /* k_ao_batch_resolve for the environment gather, a group of lanes per list entry: occluded_count[id] / rgb[3 id ..] (either may be NULL); a traced
  * miss gets LH_AO_NO_HIT and three zeros.  slot_of_entry NULL: an empty scene, every traced ray is a miss */
-__global__ __launch_bounds__(256) void k_env_batch_resolve(const BatchList bl, const EnvGather gx, const uint32_t *__restrict__ slot_of_entry,
-                                                           uint32_t *__restrict__ occluded_count, float *__restrict__ rgb,
-                                                           unsigned long long *__restrict__ occ_total)
+template <class Rad>
+__device__ __forceinline__ void env_batch_resolve(const BatchList &bl, const EnvGather &gx, const Rad &rad, const uint32_t *__restrict__ slot_of_entry,
+                                                  uint32_t *__restrict__ occluded_count, float *__restrict__ rgb,
+                                                  unsigned long long *__restrict__ occ_total, const lh_sky_src_t *sky = NULL,
+                                                  const uint8_t *__restrict__ sun_occ = NULL)
 {
     LH_NC
     __shared__ float park[256][3];
@@ -729,12 +760,27 @@ __global__ __launch_bounds__(256) void k_env_batch_resolve(const BatchList bl, c
     const uint32_t slot = (traced && slot_of_entry) ? slot_of_entry[k] : LH_AO_NO_HIT;
     const bool hit = slot != LH_AO_NO_HIT;
     unsigned int c;
-    const double sum = env_slot_sum(gx, hit, slot, park, c);
+    double sum = env_slot_sum(gx, rad, hit, slot, park, c);
+    if (sun_occ && hit && gl < 3) sum = sky_sun_term(*sky, sun_occ, slot, gl, sum);
     if (traced) {
         if (occluded_count && gl == 0) occluded_count[id] = hit ? c : LH_AO_NO_HIT;
         if (rgb && gl < 3) rgb[3 * (size_t)id + gl] = hit ? lh_env_finish(gx.scale, sum, gx.ntheta * gx.nphi) : 0.0f;
     }
     dirt_total((hit && gl == 0) ? c : 0u, occ_total);
+}
+
+__global__ __launch_bounds__(256) void k_env_batch_resolve(const BatchList bl, const EnvGather gx, const uint32_t *__restrict__ slot_of_entry,
+                                                           uint32_t *__restrict__ occluded_count, float *__restrict__ rgb,
+                                                           unsigned long long *__restrict__ occ_total)
+{
+    env_batch_resolve(bl, gx, RadEnv{gx.env}, slot_of_entry, occluded_count, rgb, occ_total);
+}
+
+__global__ __launch_bounds__(256) void k_sky_batch_resolve(const BatchList bl, const EnvGather gx, const lh_sky_src_t sky, const uint8_t *__restrict__ sun_occ,
+                                                           const uint32_t *__restrict__ slot_of_entry, uint32_t *__restrict__ occluded_count,
+                                                           float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
+{
+    env_batch_resolve(bl, gx, RadSky{sky}, slot_of_entry, occluded_count, rgb, occ_total, &sky, sun_occ);
 }
 
 /* the fetch alone (lh_accel_environment_device): one thread per direction */
@@ -745,6 +791,31 @@ __global__ void k_env_batch(size_t n, const DevEnv env, const double *__restrict
     float c[3];
     env_lookup(env, dir[3 * i], dir[3 * i + 1], dir[3 * i + 2], c);
     rgb[3 * i] = c[0]; rgb[3 * i + 1] = c[1]; rgb[3 * i + 2] = c[2];
+}
+
+/* ... of the sky (lh_accel_sky_device): no index is made of a direction, so whatever it holds reaches a colour, not an address */
+__global__ void k_sky_batch(size_t n, const lh_sky_src_t sky, const double *__restrict__ dir, float *__restrict__ rgb)
+{
+    LH_NC
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float c[3];
+    lh_sky_rgb_den(&sky.sky, sky.den, dir[3 * i], dir[3 * i + 1], dir[3 * i + 2], c);
+    rgb[3 * i] = c[0]; rgb[3 * i + 1] = c[1]; rgb[3 * i + 2] = c[2];
+}
+
+/* the sun's shadow rays, one per hit slot: the gather's origin P + eps Ns (the hit record's first three doubles) along the light's direction.
+ * nslots_dev (or NULL): the slot count where it lives on the device, nslots then its upper bound.  A plain any-hit launch answers them: no slot
+ * key, no self-primitive skip -- a sun behind the surface meets the hit's own triangle, and the reference counts that as shadow */
+__global__ void k_sun_rays(size_t nslots, const unsigned long long *__restrict__ nslots_dev, const double *__restrict__ hitrec,
+                           double sx, double sy, double sz, double *__restrict__ org, double *__restrict__ dir)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (nslots_dev && (size_t)*nslots_dev < nslots) nslots = (size_t)*nslots_dev;
+    if (i >= nslots) return;
+    const double *h = hitrec + LH_HITREC_DOUBLES * i;
+    org[3 * i] = h[0]; org[3 * i + 1] = h[1]; org[3 * i + 2] = h[2];
+    dir[3 * i] = sx; dir[3 * i + 1] = sy; dir[3 * i + 2] = sz;
 }
 
 
@@ -1294,6 +1365,56 @@ extern "C" int lh_render_launch_env_batch_resolve(size_t n_list, size_t n_rays, 
     const size_t per = 256 / LH_ENV_GROUP;
     hipLaunchKernelGGL(k_env_batch_resolve, dim3((unsigned)((n_list + per - 1) / per)), dim3(256), 0, (hipStream_t)stream, bl,
                        env_gather(ntheta, nphi, seed, scale, env, d_hitrec, d_slot_key, d_adir, d_occ), d_slot_of_entry, d_occluded_count, d_rgb, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* ... and under the sun-and-sky light: the resolves' sky instantiations (d_sun_occ: a byte per slot, or NULL: no sun), the fetch alone, the sun's rays */
+extern "C" int lh_render_launch_sky_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
+                                            const lh_sky_src_t *sky, const uint8_t *d_sun_occ, const uint32_t *d_slot_of_sample, const double *d_hitrec,
+                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
+                                            unsigned long long *d_occ_total, void *stream)
+{
+    const size_t total = (size_t)w * h, per = 256 / LH_ENV_GROUP, nb = (total + per - 1) / per;
+    const lh_env_src_t none = {{0.0f, 0.0f, 0.0f}, NULL, 0, 0};
+    if (total == 0) return 0;
+    if (nb > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_sky_resolve, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, h, band_rows, xs, ys,
+                       env_gather(ntheta, nphi, seed, scale, &none, d_hitrec, d_slot_key, d_adir, d_occ), *sky, d_sun_occ, d_slot_of_sample, d_rgb, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_sky_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
+                                                  unsigned long long seed, double scale, const lh_sky_src_t *sky, const uint8_t *d_sun_occ,
+                                                  const uint32_t *d_slot_of_entry, const double *d_hitrec, const unsigned long long *d_slot_key,
+                                                  const double *d_adir, const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
+                                                  unsigned long long *d_occ_total, void *stream)
+{
+    if (n_list == 0) return 0;
+    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
+    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
+    const lh_env_src_t none = {{0.0f, 0.0f, 0.0f}, NULL, 0, 0};
+    const size_t per = 256 / LH_ENV_GROUP;
+    hipLaunchKernelGGL(k_sky_batch_resolve, dim3((unsigned)((n_list + per - 1) / per)), dim3(256), 0, (hipStream_t)stream, bl,
+                       env_gather(ntheta, nphi, seed, scale, &none, d_hitrec, d_slot_key, d_adir, d_occ), *sky, d_sun_occ, d_slot_of_entry,
+                       d_occluded_count, d_rgb, d_occ_total);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_sky_fetch(size_t n, const lh_sky_src_t *sky, const double *d_dir, float *d_rgb, void *stream)
+{
+    if (n == 0) return 0;
+    if ((n + 255) / 256 > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_sky_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, *sky, d_dir, d_rgb);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+extern "C" int lh_render_launch_sun_rays(size_t nslots, const unsigned long long *d_nslots, const double *d_hitrec, const double sun_dir[3],
+                                         double *d_org, double *d_dir, void *stream)
+{
+    if (nslots == 0) return 0;
+    if ((nslots + 255) / 256 > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_sun_rays, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nslots, d_nslots, d_hitrec,
+                       sun_dir[0], sun_dir[1], sun_dir[2], d_org, d_dir);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -12,6 +12,7 @@
 #include "lh_internal.h"
 #include "lh_dirt.h"
 #include "lh_env.h"
+#include "lh_sky.h"
 
 #define ensure_buf lh_ensure_buf
 
@@ -93,13 +94,22 @@ struct dirt_stage { lh_dirt_params_t p; lh_dirt_scratch *ts; };
  * answers, but one per RAY: what the stage leaves is a byte, 0 or 1, at element slot * N + r of b->occ, for the caller's colour resolve; fused and
  * materialised differ only in who wrote it.  fused: the any-hit kernel stores the byte where the AO stage counts (lh_launch_trace_env).  Materialised:
  * the AO stage's own path, whose any-hit launch writes that array.  nocc totals the occluded rays, as for AO */
+/* sun (or NULL; with env only): the sun's shadow ray of the sun-and-sky light (lh_sky.h) -- one more ray per hit slot from the slot's origin along
+ * the light's direction, written by k_sun_rays and answered by ONE plain any-hit launch, a ray dump as lh_accel_intersect_device traces it: no slot
+ * key, so no self-primitive skip (a sun behind the surface is shadowed by the hit's own triangle).  What it leaves is a byte per slot at sun->occ,
+ * for the caller's resolve, the same whether the N gather rays are then traced fused or materialised.  It runs BEFORE them: a launch resets the
+ * stream's fix-up queue, whose words a late stage reads at its end.  late: the slot count is on the device, the launch is the identity list's with
+ * its count there (lh_launch_opt::n_dev).  Not counted: cnt and the totals stay the gather rays' */
+struct sun_stage { const double *dir; lh_buf *buf; const uint8_t *occ; };
+#define LH_SUN_LATE_MAX ((size_t)1 << 30)        /* slots up to which the sun's launch can take its count from the device (a list holds 2^30 entries) */
 #define LH_ENV_LATE_MAX ((size_t)1 << 28)        /* gather rays (256 MiB of bytes) up to which a stage is sized for its worst case, the count left on the device */
 #define LH_DIRT_CHUNK ((size_t)1 << 30)          /* rays of one bounded launch at most (a list holds 2^30 entries) */
 #define LH_DIRT_LATE_MAX ((size_t)1 << 27)       /* gather rays (1 GiB of t) up to which a stage is sized for its worst case, the count left on the device */
 template <class Resolve>
 static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t nmax, ao_grid g, uint64_t seed, const void *d_uniforms,
                     const unsigned long long *d_nhit, unsigned long long *d_nocc, unsigned long long *cnt, const lh_launch_opt &opt,
-                    stage_timer *tm, bool fused, bool late, Resolve resolve, const dirt_stage *dirt, bool env, hipStream_t s, ao_totals *out)
+                    stage_timer *tm, bool fused, bool late, Resolve resolve, const dirt_stage *dirt, bool env, hipStream_t s, ao_totals *out,
+                    sun_stage *sun = NULL)
 {
     const unsigned long long N = (unsigned long long)g.N;
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
@@ -112,6 +122,21 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
         nhit = *h_nhit;
         /* the persistent kernel's ray index has 32 bits; nothing was hit: nothing to trace, the resolve sees misses only */
         if (nhit * N >= (1ull << 31) || nhit == 0) fused = false;
+    }
+    if (sun) {
+        const size_t ns = late ? nmax : (size_t)nhit;
+        sun->occ = NULL;
+        if (ns) {
+            if (ensure_buf(sun->buf, ns * 49)) return -1;          /* org | dir | occ */
+            double *sorg = (double *)sun->buf->p, *sdir = sorg + 3 * ns;
+            uint8_t *socc = (uint8_t *)(sdir + 3 * ns);
+            if (lh_render_launch_sun_rays(ns, late ? d_nhit : NULL, (const double *)b->hitrec.p, sun->dir, sorg, sdir, s) != 0)
+                return fail("%ssun ray kernel launch failed", prefix);
+            lh_launch_opt o;
+            if (late) { o.indexed = true; o.index = NULL; o.idx_nrays = (uint32_t)ns; o.n_dev = (const uint32_t *)d_nhit; }          /* the count's low word: it is below 2^31 */
+            if (lh_launch(a, lh_batch_t{ns, LH_MODE_ANY, sorg, sdir, NULL, NULL, NULL, NULL, socc, NULL}, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
+            sun->occ = socc;
+        }
     }
     if (tm) HIPCHK(hipEventRecord(tm->ev[3], s));
     const bool fused_tried = fused;
@@ -253,6 +278,10 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     lh_ao_scratch *b = dirt ? &a->tile_dirt : env ? &a->tile_env : &a->tile_ao;
     const double eps = dirt ? dirt->eps : env ? env->eps : 1.0e-6;          /* the gather rays' offset along Ns */
     const lh_env_src_t esrc = env_source(a);
+    /* the sun-and-sky light (lh_sky.h): while one is set the gather reads it, not the environment; with LH_SKY_SUN every hit traces the sun's ray */
+    const lh_sky_src_t *sky = (env && a->sky_set) ? &a->sky : NULL;
+    sun_stage sunst = {sky ? sky->sky.sun_dir : NULL, &a->s_tile, NULL};
+    sun_stage *sun = (sky && (sky->sky.flags & LH_SKY_SUN)) ? &sunst : NULL;
     void *r_org, *r_dir, *r_prim, *r_t, *r_u, *r_v;          /* camera rays and their closest-hit records */
     if (dirt || env) {          /* one block of its own (org | dir | t | u | v | prim): lh_render_scratch keeps showing the last AO tile */
         lh_buf *rays = dirt ? &a->d_rays : &a->e_rays;
@@ -267,9 +296,10 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
     const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->tile_dirt_t};
     /* material textures (lh_tex.h): with at least one set, the resolve multiplies; with none, tex is NULL and the launch is the one it always was */
-    if (a->ntex && lh_tex_sync(a) != 0) return -1;
+    /* (the sun-and-sky gather has no texture fetch: ambientocclusion.c:369-375) */
+    if (a->ntex && !sky && lh_tex_sync(a) != 0) return -1;
     lh_tex_args_t tex_store;
-    const lh_tex_args_t *tex = lh_tex_args(a, r_prim, r_u, r_v, &tex_store);
+    const lh_tex_args_t *tex = sky ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &tex_store);
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
@@ -295,6 +325,13 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     if (tm) { HIPCHK(hipEventRecord(tm->ev[2], s)); opt.diag_clock += 3 * nwaves; }
     unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of k_ao_resolve's 64 counters */
     auto resolve = [&](bool from_counts) -> int {
+        if (sky) {
+            if (lh_render_launch_sky_resolve(w, h, band_rows, ps, ps, g.ntheta, g.nphi, seed, env->scale, sky, sunst.occ, (const uint32_t *)b->slot.p,
+                                             (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                                             from_counts ? NULL : (const double *)b->adir.p, (const uint8_t *)b->occ.p, (float *)d_rgb, a->d_total, s) != 0)
+                return fail("sun-and-sky resolve kernel launch failed");
+            return 0;
+        }
         if (env) {          /* from_counts: the stage ended fused -- no direction in memory, the resolve makes them again */
             if (lh_render_launch_env_resolve(w, h, band_rows, ps, ps, g.ntheta, g.nphi, seed, env->scale, &esrc, (const uint32_t *)b->slot.p,
                                              (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
@@ -328,8 +365,9 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         const bool fused = a->ao_fused && !d_uniforms;
         /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; it has no grouped order) */
         /* (so does the environment gather, a byte per ray) */
-        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && (dirt ? S * (size_t)g.N <= LH_DIRT_LATE_MAX : env ? S * (size_t)g.N <= LH_ENV_LATE_MAX : !a->dev.ao_group) && !getenv("LH_AO_SYNC");
-        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot) != 0) return -1;
+        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && (dirt ? S * (size_t)g.N <= LH_DIRT_LATE_MAX : env ? S * (size_t)g.N <= LH_ENV_LATE_MAX : !a->dev.ao_group) && !getenv("LH_AO_SYNC") &&
+                          !(sun && S > LH_SUN_LATE_MAX);
+        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot, sun) != 0) return -1;
     } else {          /* an empty scene: every sample is a miss */
         HIPCHK(hipMemsetAsync(b->slot.p, 0xFF, S * 4, s));
         HIPCHK(hipMemsetAsync(d_nhit, 0, sizeof(*d_nhit), s));
@@ -490,11 +528,19 @@ static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const
     lh_ao_scratch *b = dirt ? &a->batch_dirt : env ? &a->batch_env : &a->batch_ao;
     lh_buf *totals = dirt ? &a->d_tot : env ? &a->e_tot : &a->b_tot;
     const lh_env_src_t esrc = env_source(a);
+    /* the sun-and-sky light, as in ao_region */
+    const lh_sky_src_t *sky = (env && a->sky_set) ? &a->sky : NULL;
+    sun_stage sunst = {sky ? sky->sky.sun_dir : NULL, &a->s_batch, NULL};
+    sun_stage *sun = (sky && (sky->sky.flags & LH_SKY_SUN)) ? &sunst : NULL;
     if (ensure_buf(totals, sizeof(unsigned long long) * 65)) return -1;
     unsigned long long *d_nhit = (unsigned long long *)totals->p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
     const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->batch_dirt_t};
     /* 6. per-ray occlusion (dirt: bounded hits and value), scattered to the rays' own slots; slot NULL: an empty scene */
     auto resolve_with = [&](const uint32_t *slot, bool from_counts) -> int {
+        if (sky)
+            return lh_render_launch_sky_batch_resolve(L, n_rays, idx, cntp, g.ntheta, g.nphi, seed, env->scale, sky, sunst.occ, slot, (const double *)b->hitrec.p,
+                                                      (const unsigned long long *)b->key.p, from_counts ? NULL : (const double *)b->adir.p,
+                                                      (const uint8_t *)b->occ.p, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
         if (env)          /* from_counts: the stage ended fused -- no direction in memory, the resolve makes them again */
             return lh_render_launch_env_batch_resolve(L, n_rays, idx, cntp, g.ntheta, g.nphi, seed, env->scale, &esrc, slot, (const double *)b->hitrec.p,
                                                       (const unsigned long long *)b->key.p, from_counts ? NULL : (const double *)b->adir.p,
@@ -527,14 +573,14 @@ static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const
     /* 4-6.  A fused stage always leaves the count on the device; the grouped order (set_param "ao_group") needs it on the host: materialised */
     const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && (dirt || env || !a->dev.ao_group);
     /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; beyond that the count is read first) */
-    const bool late = fused && (!dirt || L * (size_t)g.N <= LH_DIRT_LATE_MAX) && (!env || L * (size_t)g.N <= LH_ENV_LATE_MAX);
+    const bool late = fused && (!dirt || L * (size_t)g.N <= LH_DIRT_LATE_MAX) && (!env || L * (size_t)g.N <= LH_ENV_LATE_MAX) && !(sun && L > LH_SUN_LATE_MAX);
     auto resolve = [&](bool from_counts) -> int {
         if (resolve_with((const uint32_t *)b->slot.p, from_counts) != 0) return fail("%s: resolve kernel launch failed", what);
         return 0;
     };
     ao_totals tot;
     if (ao_stage(a, dirt ? "lh_accel_dirt_device: " : env ? "lh_accel_env_device: " : "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt,
-                 lh_launch_opt(), NULL, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot) != 0)
+                 lh_launch_opt(), NULL, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot, sun) != 0)
         return -1;
     if (cnt) lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nocc, true);
     if (cnt && (dirt || env)) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
@@ -713,6 +759,57 @@ extern "C" int lh_accel_environment_host(lh_accel_t *a, size_t n, const double *
     double *d_dir = (double *)a->e_host.p; float *d_rgb = (float *)(d_dir + 3 * n);
     HIPCHK(hipMemcpyAsync(d_dir, dir, sizeof(double) * 3 * n, hipMemcpyHostToDevice, a->stream));
     if (lh_accel_environment_device(a, n, d_dir, d_rgb, a->stream) != 0) return -1;
+    HIPCHK(hipMemcpyAsync(rgb, d_rgb, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, a->stream));
+    HIPCHK(hipStreamSynchronize(a->stream));
+    return 0;
+}
+
+/* the sun-and-sky light (lh_sky.h): set after commit, as the environment; the struct is copied, its Perez denominators are made here; NULL removes it */
+extern "C" int lh_accel_set_sky(lh_accel_t *a, const lh_sky_t *sky)
+{
+    lh_guard guard(a);
+    if (sky && !lh_sky_ok(sky)) return fail("lh_accel_set_sky: bad sky parameters (every field finite, flags within LH_SKY_SUN)");
+    if (!a || !a->committed) return fail("lh_accel_set_sky: accel not committed");
+    if (!sky) { memset(&a->sky, 0, sizeof(a->sky)); a->sky_set = 0; return 0; }
+    a->sky.sky = *sky;
+    lh_sky_den(sky, a->sky.den);
+    a->sky_set = 1;
+    return 0;
+}
+
+/* the fetch alone: lh_sky_rgb of the accelerator's sky for n directions.  Asynchronous, nothing read back */
+extern "C" int lh_accel_sky_device(lh_accel_t *a, size_t n, const void *d_dir, void *d_rgb, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_sky_device";
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (!a->sky_set) return fail("%s: no sky is set (lh_accel_set_sky)", what);
+    if (n == 0) return 0;
+    if (!d_dir || !d_rgb) return fail("%s: NULL array", what);
+    if (((uintptr_t)d_dir & 7u) != 0) return fail("%s: directions are doubles: the pointer is not 8-byte aligned", what);
+    if (((uintptr_t)d_rgb & 3u) != 0) return fail("%s: the output holds floats: the pointer is not 4-byte aligned", what);
+    if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
+    HIPCHK(hipSetDevice(a->device));
+    if (lh_render_launch_sky_fetch(n, &a->sky, (const double *)d_dir, (float *)d_rgb, stream) != 0)
+        return fail("%s: kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+/* the same for HOST arrays: copies up, the device call on the accelerator's stream, copies down */
+extern "C" int lh_accel_sky_host(lh_accel_t *a, size_t n, const double *dir, float *rgb)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_sky_host";
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (!a->sky_set) return fail("%s: no sky is set (lh_accel_set_sky)", what);
+    if (n == 0) return 0;
+    if (!dir || !rgb) return fail("%s: NULL array", what);
+    if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
+    HIPCHK(hipSetDevice(a->device));
+    if (ensure_buf(&a->e_host, n * (3 * sizeof(double) + 3 * sizeof(float)))) return -1;
+    double *d_dir = (double *)a->e_host.p; float *d_rgb = (float *)(d_dir + 3 * n);
+    HIPCHK(hipMemcpyAsync(d_dir, dir, sizeof(double) * 3 * n, hipMemcpyHostToDevice, a->stream));
+    if (lh_accel_sky_device(a, n, d_dir, d_rgb, a->stream) != 0) return -1;
     HIPCHK(hipMemcpyAsync(rgb, d_rgb, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, a->stream));
     HIPCHK(hipStreamSynchronize(a->stream));
     return 0;
