@@ -129,11 +129,65 @@ int  lh_accel_commit(lh_accel_t *accel, int build_threads);
 #define LH_POS_F32 1      /* 3 floats per vertex at stride_bytes (>= 12, multiple of 4); vertex = (double)float */
 int  lh_accel_add_mesh_device(lh_accel_t *accel, uint32_t npositions, const void *d_positions, int position_format,
                               size_t stride_bytes, uint32_t nindices, const void *d_indices /* uint32_t */, void *stream);
+/* ---- updatable device meshes: new vertices, then a re-commit in place.  For a caller whose vertices move every step and who
+ * would otherwise destroy the accelerator and set every mesh, normal, attribute, material, texture, environment, sky and knob
+ * again -- and lose the streams, the fix-up queues, the pinned ring and every scratch buffer the old one had grown.
+ *   lh_accel_set_param(accel, "updatable", 1), before the commit, on an accelerator of device meshes.  The commit then KEEPS the
+ *     library's device copies of the positions, the index lists, the normals and the attributes -- the blocks lh_accel_add_mesh_device
+ *     and the set_*_device calls made, in the caller's format and stride -- and the per-stream events.  Memory: an updatable
+ *     accelerator holds the bytes the caller handed over for as long as it lives, beside the scene built from them.  Refused after
+ *     the commit ("before the commit") and on an accelerator that holds host meshes; lh_accel_add_mesh on an updatable accelerator
+ *     is refused the same way ("cannot be mixed").  An accelerator that never sets it behaves as it always did, in every call.
+ *   lh_accel_update_mesh_device, after the commit: new positions for mesh `mesh` (add order).  npositions must equal the mesh's;
+ *     the format and the stride may differ from those of the add.  The array is read by a copy enqueued on `stream` into the
+ *     library's block before the call returns, the stream's event recorded behind it: the caller may overwrite or free the array in
+ *     stream order afterwards.  An update only STAGES: no scene array and no tree is touched, and until lh_accel_recommit returns
+ *     every query answers from the old geometry.  A second update of a mesh replaces the first -- in stream order: two updates
+ *     of one mesh on different streams are not ordered by the library, the caller orders the streams; a mesh without triangles
+ *     accepts the call and does nothing.  Refused, -1 with lh_last_error, nothing enqueued, nothing changed: "accel is NULL"; "not
+ *     committed"; "not updatable" (the parameter was not set, or the commit fell back to the host builders -- the message says
+ *     which); "mesh M out of range"; "N positions given, the mesh has M"; and lh_accel_add_mesh_device's "unknown position format",
+ *     "bad stride", "positions not aligned", "NULL array", "not a device pointer", "extends past its allocation".
+ *   lh_accel_set_normals_device / lh_accel_set_attribute_device are accepted after the commit on such an accelerator, with the same
+ *     arguments and refusals, replacing and removing as before it; what they set is staged like a position update.
+ *   lh_accel_recommit: synchronous, like the commit.  Nothing staged: returns 0, no launch, no allocation.  Positions staged: waits
+ *     for the staged copies through their events, flattens every mesh into a NEW array of records and compares it with the resident
+ *     one; equal word for word, the trees stand; otherwise the traversal tree, lucille's own tree and the danger list are built
+ *     from the new records BESIDE the resident scene (the 8-wide nodes too when the scene had them or "wide8" is 1).  Positions or
+ *     attributes staged: the per-primitive normals and attributes are gathered again, into new arrays.  Then, and only when all of
+ *     that has succeeded, the call WAITS FOR THE DEVICE (hipDeviceSynchronize: a launch the caller enqueued earlier, on any stream,
+ *     may still read the old arrays), swaps the new arrays in, frees the old ones and sizes the grid again unless the caller set
+ *     it.  Memory: during a re-commit the scene's arrays exist twice.  After a successful return the accelerator is, for every entry
+ *     point, the one a caller would get from lh_accel_create, the same index lists with the new positions, the same settings and
+ *     lh_accel_commit; everything set on it survives.  *info (may be NULL) says what was redone.
+ *     Failure, -1 with lh_last_error: a NaN / infinite / > 1e30 coordinate of a referenced vertex (the commit's message), or a scene
+ *     whose trees the device builders cannot make ("the device builders cannot build the updated scene (...): it needs a new
+ *     accelerator" -- there is no host fallback here: it would release arrays an accelerator in use still holds).  Everything built
+ *     aside is freed, the accelerator stays committed and answers from the old geometry bit for bit, what was staged stays staged:
+ *     the caller may stage a repaired mesh and call again.
+ *   lh_accel_set_param(accel, "build_depth_cap", d) is for TESTS of the two paths above that no ordinary scene reaches any more: the levels
+ *     of a device-built traversal tree beyond which the device builders are given up (a commit falls back to the host builders, a
+ *     re-commit fails with "needs a new accelerator").  Default 86, what the walks' stacks take (3 d + 5 <= 264 rows); 1 .. 86; it
+ *     applies to every later commit AND re-commit of the accelerator.  A renderer has no reason to set it. */
+typedef struct lh_recommit_info {
+    int    flattened;        /* the meshes were flattened into new records (positions were staged) */
+    int    rebuilt_trees;    /* the records differed from the resident ones: both trees and the danger list were rebuilt */
+    int    regathered;       /* the per-primitive normals and attributes were gathered again */
+    double seconds;          /* the whole call */
+} lh_recommit_info_t;
+int  lh_accel_update_mesh_device(lh_accel_t *accel, uint32_t mesh, uint32_t npositions, const void *d_positions, int position_format,
+                                 size_t stride_bytes, void *stream);
+int  lh_accel_recommit(lh_accel_t *accel, lh_recommit_info_t *info /* may be NULL */);
 int  lh_accel_wait_exact(lh_accel_t *accel);
 /* lucille's own tree as the kernels read it, for inspection (tests compare the device-built tree with the host-built one):
  * *nnodes nodes of 128 bytes (lh_refbvh.h: two child boxes of 6 doubles, child[2], axis, is_leaf, first, count, parent, depth;
  * root = 0) and the ntriangles primitive ids in leaf order.  Either pointer may be NULL.  Fails if the tree is not attached. */
 int  lh_accel_ref_tree(lh_accel_t *accel, uint32_t *nnodes, void *nodes_out, uint32_t *leaf_prims_out);
+/* The danger list as the walks read it, for inspection too (tests compare a re-committed accelerator's with a fresh one's: the hit records
+ * cannot show a stale list, it only routes other rays to the reference's own walk).  *ndevice: 0 = every ray beyond the cap is routed, else
+ * the number of listed leaves behind the ONE box device_box[3] (lo | hi << 16 per axis on the scene's 16-bit grid; zeros with 0);
+ * *nhost / host_boxes (room for 16 x 6 doubles: bmin xyz, bmax xyz): the list the one-ray host walk reads.  Any pointer may be NULL. */
+int  lh_accel_danger_list(const lh_accel_t *accel, uint32_t *ndevice, uint32_t device_box[3], uint32_t *nhost, double *host_boxes);
 void lh_accel_destroy(lh_accel_t *accel);
 int  lh_accel_info(const lh_accel_t *accel, lh_accel_info_t *out);
 
@@ -758,7 +812,8 @@ int  lh_render_pt_bands(lh_accel_t *accel, const lh_camera_t *cam, int y0_first,
 #define LH_ATTR_TEXCOORD_UNSHARED 4
 #define LH_STATE_DOUBLES 24
 int  lh_accel_set_attribute(lh_accel_t *accel, uint32_t mesh, int kind, const double *data, size_t stride_bytes, uint32_t count);
-/* The same for meshes added with lh_accel_add_mesh_device, before commit; mesh = ordinal in add order.  d_normals / d_data are
+/* The same for meshes added with lh_accel_add_mesh_device, before commit (on an "updatable" accelerator after it as well: staged for
+ * lh_accel_recommit, above); mesh = ordinal in add order.  d_normals / d_data are
  * device memory of the accelerator's device: 3 components per vertex (normals, colours, tangents, binormals), 2 per vertex
  * (LH_ATTR_TEXCOORD) or 2 per index (LH_ATTR_TEXCOORD_UNSHARED), as doubles (LH_POS_F64: stride_bytes >= 8 x components and a
  * multiple of 8, pointer 8-byte aligned) or floats (LH_POS_F32: >= 4 x components, a multiple of 4, 4-byte aligned; a value IS
@@ -770,7 +825,7 @@ int  lh_accel_set_attribute(lh_accel_t *accel, uint32_t mesh, int kind, const do
  *     events of the mesh copies (no device-wide synchronise) and gathers every mesh and kind with one kernel into the
  *     per-primitive arrays the hit epilogue, the AO stage and the path tracer read; a mesh lacking a kind another mesh has is
  *     "absent" there exactly as on the host path.  Values are not validated (a NaN normal means "no normal").  The blocks are freed
- *     when the commit returns, however it ends, and by lh_accel_destroy.
+ *     when the commit returns, however it ends, and by lh_accel_destroy (an "updatable" accelerator keeps them until then).
  *   - Refused, -1 with lh_last_error, nothing enqueued, nothing changed: "accel is NULL"; "already committed"; an accelerator that
  *     holds host meshes or none ("for device meshes": the message names the host form); "mesh M out of range"; "unknown attribute
  *     kind"; "unknown format"; "bad stride"; "not aligned"; "NULL array" (with a non-zero count); "not a device pointer" /

@@ -51,6 +51,11 @@ class AccelInfo(C.Structure):
                 ("nnodes_traversal", C.c_uint32), ("ntriangles_in_tree", C.c_uint32)]
 
 
+class RecommitInfo(C.Structure):
+    """lh_recommit_info_t (include/lucille_hip.h): what lh_accel_recommit redid"""
+    _fields_ = [("flattened", C.c_int), ("rebuilt_trees", C.c_int), ("regathered", C.c_int), ("seconds", C.c_double)]
+
+
 class RasterPlane(C.Structure):
     """lh_raster_plane_t (include/lucille_hip.h)"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("frame", C.c_double * 9), ("eye", C.c_double * 3), ("fov", C.c_double)]
@@ -168,7 +173,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 
 # every symbol include/lucille_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
-    "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
+    "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_update_mesh_device", "lh_accel_recommit", "lh_accel_danger_list", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
     "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_intersect_device_tmax", "lh_accel_intersect_host_tmax", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes", "lh_accel_order_statistics",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
@@ -214,6 +219,10 @@ def lib():
     L.lh_accel_create.argtypes = [C.POINTER(vp), i32]
     L.lh_accel_add_mesh.argtypes = [vp, u32, vp, sz, u32, vp]
     L.lh_accel_add_mesh_device.argtypes = [vp, u32, vp, i32, sz, u32, vp, vp]
+    if hasattr(L, "lh_accel_recommit"):                  # an older library under LH_LIBRARY (A/B runs in tools/) has no updatable meshes
+        L.lh_accel_update_mesh_device.argtypes = [vp, u32, u32, vp, i32, sz, vp]
+        L.lh_accel_recommit.argtypes = [vp, C.POINTER(RecommitInfo)]
+        L.lh_accel_danger_list.argtypes = [vp, C.POINTER(u32), C.POINTER(u32 * 3), C.POINTER(u32), vp]
     L.lh_accel_commit.argtypes = [vp, i32]
     L.lh_accel_wait_exact.argtypes = [vp]
     L.lh_accel_ref_tree.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp]
@@ -584,6 +593,30 @@ class HipAccel:
             _check(self.L.lh_accel_set_attribute_device(self.h, int(mesh), int(kind), n, ptr, fmt, stride, self._stream_handle(stream)),
                    "lh_accel_set_attribute_device")
 
+    def update_mesh_device(self, mesh, positions, stream=None):
+        """lh_accel_update_mesh_device: new positions for device mesh `mesh` (add order) of a committed accelerator that set
+        set_param("updatable", 1) before its commit.  positions: as add_mesh_device takes them, one row per vertex of the mesh; the
+        dtype and the stride may differ from the add's.  Read by a copy enqueued on `stream` before this returns.  Only staged:
+        queries answer from the old geometry until recommit() returns."""
+        import torch
+        if positions is None:
+            raise ValueError("update_mesh_device: positions must be a CUDA torch tensor")
+        n, ptr, fmt, stride = self._device_rows("update_mesh_device", positions, 3)
+        with torch.cuda.device(self.device):
+            _check(self.L.lh_accel_update_mesh_device(self.h, int(mesh), n, ptr, fmt, stride, self._stream_handle(stream)),
+                   "lh_accel_update_mesh_device")
+
+    def recommit(self):
+        """lh_accel_recommit: rebuild, in place, from what update_mesh_device / set_normals_device / set_attribute_device staged since
+        the last (re-)commit -> info() plus "flattened", "rebuilt_trees", "regathered" (what was redone) and "recommit_seconds".
+        Synchronous; waits for the device before it swaps the new scene in.  On failure (LucilleHipError) the accelerator answers from
+        the old geometry and what was staged stays staged."""
+        r = RecommitInfo()
+        _check(self.L.lh_accel_recommit(self.h, C.byref(r)), "lh_accel_recommit")
+        out = self.info()
+        out.update(flattened=int(r.flattened), rebuilt_trees=int(r.rebuilt_trees), regathered=int(r.regathered), recommit_seconds=float(r.seconds))
+        return out
+
     def commit(self, build_threads=0, on_device=False, build=None):
         """build: "device" (= on_device: both trees on the GPU, LH_BUILD_ON_DEVICE), "host" (LH_BUILD_ON_HOST; a thread count
         in build_threads also means the host), None / "auto": the library chooses by the size of the scene"""
@@ -608,6 +641,13 @@ class HipAccel:
         prims = np.zeros(self.info()["ntriangles"], dtype=np.uint32)
         _check(self.L.lh_accel_ref_tree(self.h, C.byref(nn), nodes.ctypes.data_as(C.c_void_p), prims.ctypes.data_as(C.c_void_p)), "lh_accel_ref_tree")
         return nodes, prims
+
+    def danger_list(self):
+        """lh_accel_danger_list -> (leaves behind the device's box or 0 = every ray beyond the cap, the box's three words, the host list [n, 6])"""
+        nd, nh, w = C.c_uint32(), C.c_uint32(), (C.c_uint32 * 3)()
+        boxes = np.zeros((16, 6))
+        _check(self.L.lh_accel_danger_list(self.h, C.byref(nd), C.byref(w), C.byref(nh), boxes.ctypes.data), "lh_accel_danger_list")
+        return int(nd.value), tuple(int(x) for x in w), boxes[:nh.value].copy()
 
     def info(self):
         s = AccelInfo()

@@ -10,6 +10,7 @@
 #include "lh_internal.h"
 #include "lh_danger.h"
 #include "lh_plan.h"
+#include "lh_recommit.h"
 
 static thread_local char g_err[512] = "";
 
@@ -55,6 +56,7 @@ extern "C" int lh_accel_create(lh_accel_t **out, int device)
     { const char *e = getenv("LH_HOST_WALK"); if (e) a->host_walk = atoi(e) != 0; }
     a->ao_fused = 1;
     a->wide8 = -1;
+    a->build_depth_cap = LH_BUILD_DEPTH_MAX;
     { const char *e = getenv("LH_WIDE8"); if (e) a->wide8 = atoi(e); }
     { const char *e = getenv("LH_AO_FUSED"); if (e) a->ao_fused = atoi(e) != 0; }
     { const char *e = getenv("LH_FAST_START"); if (e) a->fast_start = atoi(e) != 0; }
@@ -100,7 +102,7 @@ extern "C" int lh_accel_add_mesh(lh_accel_t *a, uint32_t npos, const double *pos
     lh_guard guard(a);
     if (!a) return fail("lh_accel_add_mesh: accel is NULL");
     if (a->committed) return fail("lh_accel_add_mesh: accel already committed");
-    if (a->ndmeshes) return fail("lh_accel_add_mesh: host meshes and device meshes cannot be mixed on one accelerator");
+    if (a->ndmeshes || a->updatable) return fail("lh_accel_add_mesh: host meshes and device meshes cannot be mixed on one accelerator%s", a->updatable ? " (\"updatable\" is for device meshes)" : "");
     if ((npos && !pos) || (nidx && !idx)) return fail("lh_accel_add_mesh: NULL array");
     if (stride < 3 * sizeof(double) || (stride % sizeof(double)) != 0) return fail("lh_accel_add_mesh: bad stride %zu", stride);
     for (uint32_t i = 0; i < nidx - (nidx % 3); i++)
@@ -175,6 +177,7 @@ static void free_dmeshes(lh_accel_t *a)
 {
     for (uint32_t g = 0; g < a->ndmeshes; g++) {
         if (a->dmeshes[g].block) (void)hipFree(a->dmeshes[g].block);
+        if (a->dmeshes[g].pos_own) (void)hipFree(a->dmeshes[g].pos_own);
         for (int k = 0; k < LH_DATTR_SLOTS; k++) if (a->dmeshes[g].attr[k].block) (void)hipFree(a->dmeshes[g].attr[k].block);
     }
     free(a->dmeshes); a->dmeshes = NULL; a->ndmeshes = 0;
@@ -264,7 +267,7 @@ extern "C" int lh_accel_device_meshes(const lh_accel_t *a) { return a && (a->ndm
 static int set_dmesh_attr(lh_accel_t *a, const char *who, uint32_t mesh, int slot, uint32_t count, const void *d, int fmt, size_t stride,
                           const int *two_side, void *stream)
 {
-    if (a->committed || a->commit_failed) return fail("%s: accel already committed", who);
+    if (a->commit_failed || (a->committed && !(a->updatable && a->ndmeshes))) return fail("%s: accel already committed", who);      /* an updatable accelerator stages them for lh_accel_recommit */
     if (!a->ndmeshes) return fail("%s: for device meshes (lh_accel_add_mesh_device); host meshes take %s", who,
                                   slot == LH_DATTR_NORMAL ? "lh_accel_set_normals" : "lh_accel_set_attribute");
     if (mesh >= a->ndmeshes) return fail("%s: mesh %u out of range", who, mesh);
@@ -285,6 +288,21 @@ static int set_dmesh_attr(lh_accel_t *a, const char *who, uint32_t mesh, int slo
         if (count != need) return fail("%s: %u values given, the mesh needs %u (one per %s)", who, count, need,
                                        slot == LH_ATTR_TEXCOORD_UNSHARED ? "index" : "vertex");
     }
+    if (d && a->committed && m->attr[slot].block && m->attr[slot].fmt == fmt && m->attr[slot].stride == stride && bytes) {
+        /* staged after the commit in the format and stride of the block that is there (count == need: the same bytes): copied over it, as
+         * lh_accel_update_mesh_device does -- no allocation, and no hipFree, which waits for the device */
+        hipStream_t s = (hipStream_t)stream;
+        lh_dmesh_event *ev = dmesh_event_of(a, s);
+        if (!ev) return -1;
+        if (hipMemcpyAsync(m->attr[slot].block, d, bytes, hipMemcpyDeviceToDevice, s) != hipSuccess || hipEventRecord(ev->ev, s) != hipSuccess) {
+            const char *why = hipGetErrorString(hipGetLastError());
+            (void)hipStreamSynchronize(s);
+            return fail("%s: copying the array failed: %s", who, why);
+        }
+        if (two_side) m->two_side = *two_side;
+        a->staged_attr = 1;
+        return 0;
+    }
     lh_dmesh_attr n; memset(&n, 0, sizeof(n));
     if (d) {
         n.has = 1; n.fmt = fmt; n.stride = stride;
@@ -304,6 +322,7 @@ static int set_dmesh_attr(lh_accel_t *a, const char *who, uint32_t mesh, int slo
     if (m->attr[slot].block) { (void)hipSetDevice(a->device); (void)hipFree(m->attr[slot].block); }      /* replaced or removed */
     m->attr[slot] = n;
     if (two_side) m->two_side = *two_side;
+    if (a->committed) a->staged_attr = 1;
     return 0;
 }
 
@@ -348,12 +367,21 @@ static int dmesh_prim_tables(lh_host_scene *hs, const uint32_t *first, uint32_t 
 
 /* the staged device meshes -> a->d_tri64, on the accelerator's stream, behind the copies the adds enqueued (an event per caller
  * stream; no device-wide synchronise).  Returns once the kernel's status word is back: an index out of range fails the commit */
+static int flatten_device_meshes_into(lh_accel_t *a, const uint32_t *first, void **d_tri64, const char *who);
 static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first)
+{
+    const int rc = flatten_device_meshes_into(a, first, &a->d_tri64, "lh_accel_commit");
+    publish_scene(a);
+    return rc;
+}
+
+/* ... into an array of its own, *d_tri64 (the caller's to free, whatever is returned): the commit's is the scene's, a re-commit's
+ * stands beside the scene's until the swap */
+static int flatten_device_meshes_into(lh_accel_t *a, const uint32_t *first, void **d_tri64, const char *who)
 {
     const uint32_t nm = a->ndmeshes, nt = first[nm];
     const double t0 = now_s();
-    HIPCHK(hipMalloc(&a->d_tri64, sizeof(lh_tri64_t) * (size_t)nt));
-    publish_scene(a);
+    HIPCHK(hipMalloc(d_tri64, sizeof(lh_tri64_t) * (size_t)nt));
     for (uint32_t k = 0; k < a->ndmesh_events; k++) HIPCHK(hipStreamWaitEvent(a->stream, a->dmesh_events[k].ev, 0));
     /* one block: the descriptors, the first_prim table, the status words */
     const size_t desc_bytes = sizeof(lh_dmesh_desc_t) * (size_t)nm, first_bytes = (sizeof(uint32_t) * ((size_t)nm + 1) + 15) & ~(size_t)15;
@@ -364,13 +392,13 @@ static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first)
     char *d_tab = NULL; uint32_t status[4] = {0, 0, 0, 0};
     HIPCHK(hipMalloc((void **)&d_tab, h.size()));
     int rc = 0;
-    if (hipMemcpyAsync(d_tab, h.data(), h.size(), hipMemcpyHostToDevice, a->stream) != hipSuccess) rc = fail("lh_accel_commit: uploading the mesh table failed");
-    if (rc == 0) rc = lh_flatten_launch(nt, nm, (const lh_dmesh_desc_t *)d_tab, (const uint32_t *)(d_tab + desc_bytes), a->d_tri64, (uint32_t *)(d_tab + desc_bytes + first_bytes), a->stream);
-    if (rc == 0 && hipMemcpyAsync(status, d_tab + desc_bytes + first_bytes, sizeof(status), hipMemcpyDeviceToHost, a->stream) != hipSuccess) rc = fail("lh_accel_commit: reading the flatten status failed");
+    if (hipMemcpyAsync(d_tab, h.data(), h.size(), hipMemcpyHostToDevice, a->stream) != hipSuccess) rc = fail("%s: uploading the mesh table failed", who);
+    if (rc == 0) rc = lh_flatten_launch(nt, nm, (const lh_dmesh_desc_t *)d_tab, (const uint32_t *)(d_tab + desc_bytes), *d_tri64, (uint32_t *)(d_tab + desc_bytes + first_bytes), a->stream);
+    if (rc == 0 && hipMemcpyAsync(status, d_tab + desc_bytes + first_bytes, sizeof(status), hipMemcpyDeviceToHost, a->stream) != hipSuccess) rc = fail("%s: reading the flatten status failed", who);
     const hipError_t es = hipStreamSynchronize(a->stream);
     (void)hipFree(d_tab);
-    if (rc == 0 && es != hipSuccess) rc = fail("lh_accel_commit: flattening the device meshes failed: %s", hipGetErrorString(es));
-    if (rc == 0 && status[0]) rc = fail("lh_accel_commit: mesh %u: index %u out of range (npositions %u)", status[1], status[2], status[3]);
+    if (rc == 0 && es != hipSuccess) rc = fail("%s: flattening the device meshes failed: %s", who, hipGetErrorString(es));
+    if (rc == 0 && status[0]) rc = fail("%s: mesh %u: index %u out of range (npositions %u)", who, status[1], status[2], status[3]);
     if (rc == 0 && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device flatten (%u meshes, %.0f MB) %8.2f ms\n", nm, sizeof(lh_tri64_t) * (double)nt / 1e6, (now_s() - t0) * 1e3);
     return rc;
 }
@@ -379,8 +407,21 @@ static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first)
  * host scene uploads (device_upload): one kernel on the accelerator's stream.  Called behind flatten_device_meshes, which has
  * waited for the callers' copies and found every index in range; an array no mesh contributes to stays NULL, a scene without
  * any costs nothing here */
+static int gather_device_attributes_into(lh_accel_t *a, const uint32_t *first, lh_gather_out_t *o, const char *who);
 static int gather_device_attributes(lh_accel_t *a, const uint32_t *first)
 {
+    lh_gather_out_t o;
+    const int rc = gather_device_attributes_into(a, first, &o, "lh_accel_commit");
+    a->d_nrm9 = o.nrm9; a->d_st6 = o.st6; a->d_inside = o.inside;
+    for (int k = 0; k < 3; k++) a->d_attr9[k] = o.attr9[k];
+    publish_scene(a);
+    return rc;
+}
+
+/* ... into arrays of their own, *o (the caller's to free, whatever is returned; NULL: no mesh has it) */
+static int gather_device_attributes_into(lh_accel_t *a, const uint32_t *first, lh_gather_out_t *o, const char *who)
+{
+    memset(o, 0, sizeof(*o));
     const uint32_t nm = a->ndmeshes, nt = first[nm];
     bool any[LH_DATTR_SLOTS] = {false, false, false, false, false, false}, any_two = false, work = false;
     for (uint32_t g = 0; g < nm; g++) {
@@ -390,14 +431,11 @@ static int gather_device_attributes(lh_accel_t *a, const uint32_t *first)
     for (int k = 0; k < LH_DATTR_SLOTS; k++) work = work || any[k];
     if (nt == 0 || !(work || any_two)) return 0;
     const double t0 = now_s();
-    if (any[LH_DATTR_NORMAL]) HIPCHK(hipMalloc(&a->d_nrm9, sizeof(double) * 9 * (size_t)nt));
-    for (int k = 0; k < 3; k++) if (any[k]) HIPCHK(hipMalloc(&a->d_attr9[k], sizeof(double) * 9 * (size_t)nt));
-    if (any[LH_ATTR_TEXCOORD] || any[LH_ATTR_TEXCOORD_UNSHARED]) HIPCHK(hipMalloc(&a->d_st6, sizeof(double) * 6 * (size_t)nt));
-    if (any_two) HIPCHK(hipMalloc(&a->d_inside, (size_t)nt));
-    publish_scene(a);
-    lh_gather_out_t out;
-    out.nrm9 = (double *)a->d_nrm9; out.st6 = (double *)a->d_st6; out.inside = (uint8_t *)a->d_inside;
-    for (int k = 0; k < 3; k++) out.attr9[k] = (double *)a->d_attr9[k];
+    if (any[LH_DATTR_NORMAL]) HIPCHK(hipMalloc((void **)&o->nrm9, sizeof(double) * 9 * (size_t)nt));
+    for (int k = 0; k < 3; k++) if (any[k]) HIPCHK(hipMalloc((void **)&o->attr9[k], sizeof(double) * 9 * (size_t)nt));
+    if (any[LH_ATTR_TEXCOORD] || any[LH_ATTR_TEXCOORD_UNSHARED]) HIPCHK(hipMalloc((void **)&o->st6, sizeof(double) * 6 * (size_t)nt));
+    if (any_two) HIPCHK(hipMalloc((void **)&o->inside, (size_t)nt));
+    const lh_gather_out_t out = *o;
     /* one block: the index descriptors, the attribute descriptors, the first_prim table */
     const size_t desc_bytes = sizeof(lh_dmesh_desc_t) * (size_t)nm, attr_bytes = sizeof(lh_dmesh_attr_desc_t) * (size_t)nm;
     std::vector<char> h(desc_bytes + attr_bytes + sizeof(uint32_t) * ((size_t)nm + 1), 0);
@@ -416,12 +454,12 @@ static int gather_device_attributes(lh_accel_t *a, const uint32_t *first)
     char *d_tab = NULL;
     HIPCHK(hipMalloc((void **)&d_tab, h.size()));
     int rc = 0;
-    if (hipMemcpyAsync(d_tab, h.data(), h.size(), hipMemcpyHostToDevice, a->stream) != hipSuccess) rc = fail("lh_accel_commit: uploading the attribute table failed");
+    if (hipMemcpyAsync(d_tab, h.data(), h.size(), hipMemcpyHostToDevice, a->stream) != hipSuccess) rc = fail("%s: uploading the attribute table failed", who);
     if (rc == 0) rc = lh_gather_launch(nt, nm, (const lh_dmesh_desc_t *)d_tab, (const lh_dmesh_attr_desc_t *)(d_tab + desc_bytes),
                                        (const uint32_t *)(d_tab + desc_bytes + attr_bytes), out, a->stream);
     const hipError_t es = hipStreamSynchronize(a->stream);         /* the table is the host vector's until here */
     (void)hipFree(d_tab);
-    if (rc == 0 && es != hipSuccess) rc = fail("lh_accel_commit: gathering the device meshes' attributes failed: %s", hipGetErrorString(es));
+    if (rc == 0 && es != hipSuccess) rc = fail("%s: gathering the device meshes' attributes failed: %s", who, hipGetErrorString(es));
     if (rc == 0 && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device attribute gather      %8.2f ms\n", (now_s() - t0) * 1e3);
     return rc;
 }
@@ -806,43 +844,61 @@ __global__ __launch_bounds__(256) void k_danger_scan(uint32_t n, const double *_
     for (int q = 0; q < 6; q++) o[q] = nodes[parent].box[k][q];
 }
 
-static int lh_danger_scan(lh_accel_t *a)
+/* what a scan found: the list the one-ray host walk reads (nhost boxes; LH_DANGER_ALL: none, every ray beyond the cap) and the device's one box (ndev, words) */
+struct lh_danger_found { uint32_t nhost, ndev, words[3]; double boxes[6 * LH_DANGER_MAX]; };
+
+/* the scan over arrays that need not be the resident scene's (a re-commit's stand beside it): n triangle records, lucille's own tree over them and
+ * its box, the cap and the 16-bit grid of the traversal tree built from the same records.  a->d_danger is its scratch; nothing of the scene is written */
+static int danger_scan_arrays(lh_accel_t *a, uint32_t n, double deg_dcap, const void *tri64, const void *leafpos, const void *lca, const void *nodes,
+                              const double rbmin[3], const double rbmax[3], const float grid_lo[3], const float grid_step[3], lh_danger_found *o)
 {
-    lh_host_scene *hs = a->hs;
-    a->dev.ndanger = LH_DANGER_ALL;
-    if (!a->d_ref_nodes || !a->d_tri64 || hs->bvh.ntris == 0) return 0;
-    if (!(hs->bvh.deg_dcap < LH_DEG_DCAP_ALL)) return 0;              /* no zero-area triangle in the tree caps the directions: nothing to list */
+    o->nhost = o->ndev = LH_DANGER_ALL;
+    if (!nodes || !tri64 || n == 0) return 0;
+    if (!(deg_dcap < LH_DEG_DCAP_ALL)) return 0;              /* no zero-area triangle in the tree caps the directions: nothing to list */
     if (getenv("LH_DANGER_BOXES") && atoi(getenv("LH_DANGER_BOXES")) == 0) return 0;       /* A/B: round 5's rule (every ray beyond the cap) */
     HIPCHK(hipSetDevice(a->device));
     if (!a->d_danger) HIPCHK(hipMalloc(&a->d_danger, sizeof(double) * (8 + 6 * LH_DANGER_MAX)));
     HIPCHK(hipMemsetAsync(a->d_danger, 0, sizeof(double) * (8 + 6 * LH_DANGER_MAX), a->stream));
-    const uint32_t n = hs->bvh.ntris;
-    hipLaunchKernelGGL(k_danger_scan, dim3((n + 255u) / 256u), dim3(256), 0, a->stream, n, (const double *)a->d_tri64, (const uint2 *)a->d_prim_leafpos,
-                       (const int4 *)a->d_ref_lca, (const lh_refnode_t *)a->d_ref_nodes, a->dev.ref_bmin[0], a->dev.ref_bmin[1], a->dev.ref_bmin[2],
-                       a->dev.ref_bmax[0], a->dev.ref_bmax[1], a->dev.ref_bmax[2], (unsigned long long *)a->d_danger, (double *)a->d_danger + 8);
+    hipLaunchKernelGGL(k_danger_scan, dim3((n + 255u) / 256u), dim3(256), 0, a->stream, n, (const double *)tri64, (const uint2 *)leafpos,
+                       (const int4 *)lca, (const lh_refnode_t *)nodes, rbmin[0], rbmin[1], rbmin[2],
+                       rbmax[0], rbmax[1], rbmax[2], (unsigned long long *)a->d_danger, (double *)a->d_danger + 8);
     HIPCHK(hipGetLastError());
     double h[8 + 6 * LH_DANGER_MAX];
     HIPCHK(hipMemcpyAsync(h, a->d_danger, sizeof(h), hipMemcpyDeviceToHost, a->stream));
     HIPCHK(hipStreamSynchronize(a->stream));
     unsigned long long cnt; memcpy(&cnt, h, sizeof(cnt));
     if (cnt == 0 || cnt > LH_DANGER_MAX) return 0;                      /* none found (the cap came from somewhere else: keep round 5's rule) or too many */
+    memcpy(o->boxes, h + 8, sizeof(double) * 6 * (size_t)cnt);
+    o->nhost = (uint32_t)cnt;
+    /* the union of the listed boxes on the scene's 16-bit grid, a cell wider on every side (the nodes' own boxes are rounded outward
+     * the same way: lh_bvh.c).  A union that leaves the grid on any side (a leaf that also holds a triangle outside the traversal
+     * tree's bounds, however little outside): round 5's rule (lh_danger.h lh_danger_pack) */
+    double u[6] = {1.0e308, 1.0e308, 1.0e308, -1.0e308, -1.0e308, -1.0e308};
+    for (unsigned long long i = 0; i < cnt; i++)
+        for (int k = 0; k < 3; k++) { u[k] = fmin(u[k], h[8 + 6 * i + k]); u[3 + k] = fmax(u[3 + k], h[8 + 6 * i + 3 + k]); }
+    if (!lh_danger_pack(u, grid_lo, grid_step, o->words)) return 0;
+    o->ndev = (uint32_t)cnt;
+    return 0;
+}
+
+static int lh_danger_scan(lh_accel_t *a)
+{
+    lh_host_scene *hs = a->hs;
+    a->dev.ndanger = LH_DANGER_ALL;
+    lh_danger_found f;
+    /* the host scene's grid: a->dev's copy is set later in a device-built commit */
+    if (danger_scan_arrays(a, hs->bvh.ntris, hs->bvh.deg_dcap, a->d_tri64, a->d_prim_leafpos, a->d_ref_lca, a->d_ref_nodes, a->dev.ref_bmin, a->dev.ref_bmax,
+                           hs->bvh.grid_lo, hs->bvh.grid_step, &f) != 0) return -1;
+    if (f.nhost == LH_DANGER_ALL) return 0;
     pthread_mutex_lock(&g_scene_mu);
     if (hs->bvh.ndanger == LH_DANGER_ALL) {            /* the first replica of a shared host scene writes the list; the others found the same one */
-        memcpy(hs->bvh.danger, h + 8, sizeof(double) * 6 * (size_t)cnt);
-        __atomic_store_n(&hs->bvh.ndanger, (uint32_t)cnt, __ATOMIC_RELEASE);      /* the one-ray host walk reads it (lh_hostwalk.c) */
+        memcpy(hs->bvh.danger, f.boxes, sizeof(double) * 6 * (size_t)f.nhost);
+        __atomic_store_n(&hs->bvh.ndanger, f.nhost, __ATOMIC_RELEASE);      /* the one-ray host walk reads it (lh_hostwalk.c) */
     }
     pthread_mutex_unlock(&g_scene_mu);
-    {   /* the union of the listed boxes on the scene's 16-bit grid, a cell wider on every side (the nodes' own boxes are rounded outward
-         * the same way: lh_bvh.c).  A union that leaves the grid on any side (a leaf that also holds a triangle outside the traversal
-         * tree's bounds, however little outside): round 5's rule (lh_danger.h lh_danger_pack) */
-        double u[6] = {1.0e308, 1.0e308, 1.0e308, -1.0e308, -1.0e308, -1.0e308};
-        for (unsigned long long i = 0; i < cnt; i++)
-            for (int k = 0; k < 3; k++) { u[k] = fmin(u[k], h[8 + 6 * i + k]); u[3 + k] = fmax(u[3 + k], h[8 + 6 * i + 3 + k]); }
-        uint32_t w[3];
-        if (!lh_danger_pack(u, hs->bvh.grid_lo, hs->bvh.grid_step, w)) return 0;          /* the host scene's grid: a->dev's copy is set later in a device-built commit */
-        for (int k = 0; k < 3; k++) a->dev.danger[k] = w[k];
-    }
-    a->dev.ndanger = (uint32_t)cnt;
+    if (f.ndev == LH_DANGER_ALL) return 0;
+    for (int k = 0; k < 3; k++) a->dev.danger[k] = f.words[k];
+    a->dev.ndanger = f.ndev;
     return 0;
 }
 
@@ -994,7 +1050,7 @@ static int device_upload(lh_accel_t *a, const uint32_t *dmesh_first = NULL)
             for (int k = 0; k < 3; k++) { hs->bvh.bmin[k] = bmin[k]; hs->bvh.bmax[k] = bmax[k]; hs->bvh.grid_lo[k] = glo[k]; hs->bvh.grid_step[k] = gst[k]; }
             pthread_mutex_unlock(&g_scene_mu);
             publish_scene(a);
-            if (3 * d4 + 5 > 264) return -3;          /* deeper than k_overflow_fix's private stack: the caller falls back to the host builder */
+            if (d4 > (uint32_t)a->build_depth_cap) return -3;          /* deeper than k_overflow_fix's private stack (LH_BUILD_DEPTH_MAX: 3 d + 5 <= 264 rows; "build_depth_cap" lowers it): the caller falls back to the host builder */
             if (hs->have_ref && (hs->ref_on_device || hs->ref_state == 1) && device_ref_tree(a) < 0) {
                 if (!dmesh_first) return -1;
                 if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: %s: host builders\n", lh_last_error());
@@ -1068,9 +1124,9 @@ static int commit_device_meshes(lh_accel_t *a)
     a->build_auto = 0;
     int rc = dmesh_prim_tables(hs, first, nm);
     if (rc == 0) rc = device_upload(a, first);
-    if (rc == -3) rc = dmesh_host_fallback(a, first, nm);
+    if (rc == -3) { a->update_fellback = a->updatable; rc = dmesh_host_fallback(a, first, nm); }
     free(first);
-    free_dmeshes(a);
+    if (rc != 0 || !a->updatable || a->update_fellback) free_dmeshes(a);          /* an updatable accelerator keeps its blocks and events: freed by lh_accel_destroy */
     if (rc != 0) return -1;
     if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device meshes, %.2f ms in all\n", (now_s() - tc0) * 1e3);
     a->commit_failed = 0;
@@ -1162,6 +1218,194 @@ extern "C" int lh_accel_commit(lh_accel_t *a, int build_threads)
     return 0;
 }
 
+/* ---- updatable device meshes: new vertices, then a re-commit in place (include/lucille_hip.h) ------------------ */
+static int updatable_check(const lh_accel_t *a, const char *who)
+{
+    if (!a->committed) return fail("%s: accel not committed", who);
+    if (!a->updatable) return fail("%s: accel not updatable (lh_accel_set_param \"updatable\" = 1 comes before the commit)", who);
+    if (a->update_fellback) return fail("%s: accel not updatable: its commit fell back to the host builders, which keep no device meshes", who);
+    return 0;
+}
+
+extern "C" int lh_accel_update_mesh_device(lh_accel_t *a, uint32_t mesh, uint32_t npos, const void *d_pos, int fmt, size_t stride, void *stream)
+{
+    const char *who = "lh_accel_update_mesh_device";
+    lh_guard guard(a);
+    if (!a) return fail("%s: accel is NULL", who);
+    if (updatable_check(a, who) != 0) return -1;
+    if (mesh >= a->ndmeshes) return fail("%s: mesh %u out of range", who, mesh);
+    lh_dmesh *m = &a->dmeshes[mesh];
+    if (npos != m->npos) return fail("%s: %u positions given, the mesh has %u", who, npos, m->npos);
+    if (fmt != LH_POS_F64 && fmt != LH_POS_F32) return fail("%s: unknown position format %d", who, fmt);
+    const size_t elem = fmt == LH_POS_F32 ? sizeof(float) : sizeof(double);
+    if (stride < 3 * elem || (stride % elem) != 0) return fail("%s: bad stride %zu", who, stride);
+    if (npos && !d_pos) return fail("%s: NULL array", who);
+    if (((uintptr_t)d_pos % elem) != 0) return fail("%s: positions not aligned to %zu bytes", who, elem);
+    if (!m->ntris) return 0;                            /* never read: nothing is kept of it */
+    const size_t pos_bytes = (size_t)(npos - 1) * stride + 3 * elem;          /* ntris > 0: the add saw npos > 0 */
+    HIPCHK(hipSetDevice(a->device));
+    if (lh_device_array_ok(a, d_pos, pos_bytes, who, "positions") != 0) return -1;
+    hipStream_t s = (hipStream_t)stream;
+    lh_dmesh_event *ev = dmesh_event_of(a, s);
+    if (!ev) return -1;
+    /* into the library's own copy and nothing else.  The same format and stride as the copy's: in place; another: a block of its own, the one
+     * before it freed (hipFree waits for a copy that may still be writing it) */
+    const bool same = fmt == m->fmt && stride == m->stride;
+    void *own = NULL;
+    if (!same) HIPCHK(hipMalloc(&own, pos_bytes));
+    void *dst = same ? (void *)m->pos : own;
+    if (hipMemcpyAsync(dst, d_pos, pos_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess || hipEventRecord(ev->ev, s) != hipSuccess) {
+        const char *why = hipGetErrorString(hipGetLastError());
+        (void)hipStreamSynchronize(s);
+        if (own) (void)hipFree(own);
+        return fail("%s: copying the positions failed: %s", who, why);
+    }
+    if (!same) {
+        if (m->pos_own) (void)hipFree(m->pos_own);
+        m->pos_own = own; m->pos = own; m->fmt = fmt; m->stride = stride;
+    }
+    a->staged_pos = 1;
+    return 0;
+}
+
+/* a scene built beside the resident one: the arrays of scene_rows a re-commit replaces, and what device_upload writes into the headers for them */
+struct lh_side {
+    void *tri64, *tri32, *q4, *q8, *ref_nodes, *ref_leaf_prims, *ref_lca, *leafpos;
+    lh_gather_out_t attr;
+    uint32_t nq4, d4, st4, nq8, d8, nlive, ref_nnodes; double dcap, sc6[6], build_seconds, ref_seconds;
+    float bmin[3], bmax[3], glo[3], gst[3];
+    lh_danger_found danger;
+};
+
+static void side_free(lh_side *s)
+{
+    void *p[] = {s->tri64, s->tri32, s->q4, s->q8, s->ref_nodes, s->ref_leaf_prims, s->ref_lca, s->leafpos,
+                 s->attr.nrm9, s->attr.attr9[0], s->attr.attr9[1], s->attr.attr9[2], s->attr.st6, s->attr.inside};
+    for (size_t k = 0; k < sizeof(p) / sizeof(p[0]); k++) if (p[k]) (void)hipFree(p[k]);
+    memset(s, 0, sizeof(*s));
+}
+
+/* *diff: the two arrays of nwords words differ somewhere */
+static int words_differ(lh_accel_t *a, const void *x, const void *y, size_t nwords, bool *diff)
+{
+    int *flag = NULL, h_flag = 0;
+    HIPCHK(hipMalloc((void **)&flag, sizeof(int)));
+    int rc = 0;
+    if (hipMemsetAsync(flag, 0, sizeof(int), a->stream) != hipSuccess) rc = fail("lh_accel_recommit: comparing the triangle records failed");
+    if (rc == 0) {
+        hipLaunchKernelGGL(k_words_differ, dim3(2048), dim3(256), 0, a->stream, nwords, (const uint32_t *)x, (const uint32_t *)y, flag);
+        if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess)
+            rc = fail("lh_accel_recommit: comparing the triangle records failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    (void)hipFree(flag);
+    *diff = h_flag != 0;
+    return rc;
+}
+
+/* what device_upload builds from the records, from s->tri64 and beside the scene: the traversal tree and tri32, lucille's own tree, the danger list */
+static int side_build_trees(lh_accel_t *a, lh_side *s, uint32_t nt, int want_q8)
+{
+    static const char *cannot = "lh_accel_recommit: the device builders cannot build the updated scene (%s): it needs a new accelerator";
+    char err[256] = "";
+    const double tb = now_s();
+    s->nlive = nt; s->dcap = INFINITY;
+    s->danger.nhost = s->danger.ndev = LH_DANGER_ALL;          /* until a scan says otherwise (LH_REFTREE=0: none runs) */
+    const int rcb = lh_device_build(nt, (const double *)s->tri64, &s->q4, &s->nq4, &s->d4, &s->st4, want_q8, &s->q8, &s->nq8, &s->d8, &s->tri32, s->bmin, s->bmax, s->glo, s->gst,
+                                    &s->nlive, &s->dcap, (void *)a->stream, err, sizeof(err));
+    if (rcb == -2) return fail("lh_accel_recommit: a vertex coordinate is NaN, infinite or beyond 1e30");
+    if (rcb != 0) return fail(cannot, err);
+    s->build_seconds = now_s() - tb;
+    if (s->d4 > (uint32_t)a->build_depth_cap) { snprintf(err, sizeof(err), "a tree of %u levels, the walks' stacks take %d", s->d4, a->build_depth_cap); return fail(cannot, err); }
+    if ((uint64_t)s->nq4 * sizeof(lh_q4node_t) >= (1ull << 32)) return fail(cannot, "more 4-wide nodes than a 32-bit byte offset addresses");
+    if (!a->hs->have_ref) return 0;
+    const double tr = now_s(); uint32_t rdepth = 0;
+    if (lh_device_ref_build(nt, (const double *)s->tri64, &s->ref_nodes, &s->ref_nnodes, &rdepth, &s->ref_leaf_prims, &s->ref_lca, &s->leafpos, s->sc6,
+                            (void *)a->stream, err, sizeof(err)) != 0) {
+        s->ref_nodes = s->ref_leaf_prims = s->ref_lca = s->leafpos = NULL;
+        return fail(cannot, err);
+    }
+    s->ref_seconds = now_s() - tr;
+    return danger_scan_arrays(a, nt, s->dcap, s->tri64, s->leafpos, s->ref_lca, s->ref_nodes, s->sc6, s->sc6 + 3, s->glo, s->gst, &s->danger);
+}
+
+extern "C" int lh_accel_recommit(lh_accel_t *a, lh_recommit_info_t *info)
+{
+    const char *who = "lh_accel_recommit";
+    lh_guard guard(a);
+    if (info) memset(info, 0, sizeof(*info));
+    if (!a) return fail("%s: accel is NULL", who);
+    if (updatable_check(a, who) != 0) return -1;
+    if (!a->staged_pos && !a->staged_attr) return 0;
+    lh_host_scene *hs = a->hs;
+    const double t0 = now_s();
+    const bool timing = getenv("LH_BUILD_TIMING") != NULL;
+    HIPCHK(hipSetDevice(a->device));
+    /* the staged copies, through their events (the flatten waits for them again: an attribute-only re-commit does not flatten) */
+    for (uint32_t k = 0; k < a->ndmesh_events; k++) HIPCHK(hipStreamWaitEvent(a->stream, a->dmesh_events[k].ev, 0));
+    uint32_t *first = dmesh_first_prim(a);
+    if (!first) return fail("out of memory");
+    const uint32_t nt = first[a->ndmeshes];
+    const int had_q8 = a->d_q8nodes != NULL;
+    lh_recommit_plan_t plan = lh_recommit_plan(a->staged_pos, a->staged_attr, 1, had_q8, a->wide8);
+    lh_side s; memset(&s, 0, sizeof(s));
+    int rc = 0;
+    /* everything below is built aside: the accelerator's arrays and headers are read, never written, until the swap */
+    if (plan.flatten && nt) {
+        bool changed = false;
+        rc = flatten_device_meshes_into(a, first, &s.tri64, who);
+        if (rc == 0 && plan.compare) rc = words_differ(a, s.tri64, a->d_tri64, sizeof(lh_tri64_t) / 4 * (size_t)nt, &changed);
+        plan = lh_recommit_plan(a->staged_pos, a->staged_attr, changed, had_q8, a->wide8);
+        if (rc == 0 && !plan.trees) { (void)hipFree(s.tri64); s.tri64 = NULL; }          /* the resident records word for word: the trees stand */
+    } else
+        plan = lh_recommit_plan(a->staged_pos, a->staged_attr, 0, had_q8, a->wide8);          /* no triangles: nothing to build from */
+    const double t1 = now_s();
+    if (rc == 0 && plan.trees) rc = side_build_trees(a, &s, nt, plan.q8);
+    const double t2 = now_s();
+    if (rc == 0 && plan.gather) rc = gather_device_attributes_into(a, first, &s.attr, who);
+    const double tg = now_s();
+    free(first);
+    /* a launch a caller enqueued earlier, on any stream, may still read the old arrays through its own copy of the scene */
+    if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = fail("%s: waiting for the device failed: %s", who, hipGetErrorString(hipGetLastError()));
+    if (rc != 0) { side_free(&s); return -1; }          /* still committed, still the old scene; what was staged stays staged */
+    const double t3 = now_s();
+    void *old[14]; int nold = 0;
+    if (plan.trees) {
+        void **slot[] = {&a->d_tri64, &a->d_tri32, &a->d_q4nodes, &a->d_q8nodes, &a->d_ref_nodes, &a->d_ref_leaf_prims, &a->d_ref_lca, &a->d_prim_leafpos};
+        void *now[] = {s.tri64, s.tri32, s.q4, s.q8, s.ref_nodes, s.ref_leaf_prims, s.ref_lca, s.leafpos};
+        for (int k = 0; k < 8; k++) { old[nold++] = *slot[k]; *slot[k] = now[k]; }
+        pthread_mutex_lock(&g_scene_mu);
+        lh_bvh_t *b = &hs->bvh;
+        b->nq4nodes = s.nq4; b->q4_depth = s.d4; b->q4_stack = s.st4; b->nnodes = s.nq4; b->max_depth = s.d4; b->build_seconds = s.build_seconds;
+        b->nlive = s.nlive; b->deg_dcap = s.dcap;
+        b->nq8nodes = s.q8 ? s.nq8 : 0u; b->q8_depth = s.q8 ? s.d8 : 0u;
+        for (int k = 0; k < 3; k++) { b->bmin[k] = s.bmin[k]; b->bmax[k] = s.bmax[k]; b->grid_lo[k] = s.glo[k]; b->grid_step[k] = s.gst[k]; }
+        /* the danger list of the OLD geometry must not stay: lh_danger_scan writes the host list only over LH_DANGER_ALL */
+        memset(b->danger, 0, sizeof(b->danger));
+        if (s.danger.nhost != LH_DANGER_ALL) memcpy(b->danger, s.danger.boxes, sizeof(double) * 6 * (size_t)s.danger.nhost);
+        __atomic_store_n(&b->ndanger, s.danger.nhost, __ATOMIC_RELEASE);
+        hs->ref_build_seconds = s.ref_seconds;
+        pthread_mutex_unlock(&g_scene_mu);
+        a->dev.ndanger = s.danger.ndev;
+        for (int k = 0; k < 3; k++) a->dev.danger[k] = s.danger.ndev != LH_DANGER_ALL ? s.danger.words[k] : 0u;
+        if (hs->have_ref) publish_ref(a, s.ref_nnodes, 0, s.sc6, s.sc6 + 3);
+        a->hw_ns = 0.0; a->hw_gpu_left = 0;
+    }
+    if (plan.gather) {
+        void **slot[] = {&a->d_nrm9, &a->d_attr9[0], &a->d_attr9[1], &a->d_attr9[2], &a->d_st6, &a->d_inside};
+        void *now[] = {s.attr.nrm9, s.attr.attr9[0], s.attr.attr9[1], s.attr.attr9[2], s.attr.st6, s.attr.inside};
+        for (int k = 0; k < 6; k++) { old[nold++] = *slot[k]; *slot[k] = now[k]; }
+    }
+    publish_scene(a);
+    for (int k = 0; k < nold; k++) if (old[k]) (void)hipFree(old[k]);
+    if (plan.trees && !a->grid_user) (void)size_grid(a);          /* the new tree's stack rows (it asks the runtime for the device's CUs: the old grid stays a valid one) */
+    a->staged_pos = a->staged_attr = 0;
+    a->upload_seconds = now_s() - t0;
+    if (info) { info->flattened = plan.flatten; info->rebuilt_trees = plan.trees; info->regathered = plan.gather; info->seconds = a->upload_seconds; }
+    if (timing) fprintf(stderr, "[lucille_hip] recommit: flatten + compare %.2f ms, trees %.2f ms, gather %.2f ms, wait %.2f ms, swap %.2f ms: %.2f ms in all (%s)\n",
+                        (t1 - t0) * 1e3, (t2 - t1) * 1e3, (tg - t2) * 1e3, (t3 - tg) * 1e3, (now_s() - t3) * 1e3, a->upload_seconds * 1e3, plan.trees ? "trees rebuilt" : "trees kept");
+    return 0;
+}
+
 /* blocks until the reference-order tree of a device-built scene is attached: from then on exact-t ties and fragile
  * hits follow the reference's tree (before: ties fall back to "larger primitive id wins", as with LH_REFTREE=0) */
 extern "C" int lh_accel_wait_exact(lh_accel_t *a)
@@ -1204,6 +1448,18 @@ extern "C" int lh_accel_ref_tree(lh_accel_t *a, uint32_t *nnodes, void *nodes_ou
     if (nnodes) *nnodes = a->dev.ref_nnodes;
     if (nodes_out) HIPCHK(hipMemcpy(nodes_out, a->d_ref_nodes, sizeof(lh_refnode_t) * (size_t)a->dev.ref_nnodes, hipMemcpyDeviceToHost));
     if (leaf_prims_out) HIPCHK(hipMemcpy(leaf_prims_out, a->d_ref_leaf_prims, sizeof(uint32_t) * (size_t)a->hs->bvh.ntris, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int lh_accel_danger_list(const lh_accel_t *a, uint32_t *ndevice, uint32_t device_box[3], uint32_t *nhost, double *host_boxes)
+{
+    lh_guard guard(a);
+    if (!a || !a->committed) return fail("lh_accel_danger_list: accel not committed");
+    const uint32_t nd = a->dev.ndanger, nh = __atomic_load_n(&a->hs->bvh.ndanger, __ATOMIC_ACQUIRE);
+    if (ndevice) *ndevice = nd;
+    if (device_box) for (int k = 0; k < 3; k++) device_box[k] = nd != LH_DANGER_ALL ? a->dev.danger[k] : 0u;
+    if (nhost) *nhost = nh;
+    if (host_boxes && nh != LH_DANGER_ALL) memcpy(host_boxes, a->hs->bvh.danger, sizeof(double) * 6 * (size_t)nh);
     return 0;
 }
 
@@ -1269,7 +1525,10 @@ extern "C" int lh_accel_set_grid(lh_accel_t *a, int blocks)
  * "ao_fused", "wide8" (-1 auto / 0 / 1), "stack_cap" (tests of the overflow path),
  * "coop_patience" (10 ns ticks the pass beside a launch waits for progress; 0: half a second),
  * "dump_order" (1 / 0: large ray dumps are traced from a copy in bin order, lh_order.h), "dump_order_min" (rays of the smallest dump that is),
- * "dump_order_bits" (the key, 64 bins either way: 2 = the origin's cell at two bits per axis, 1 = one bit per axis under the direction octant), "dump_order_max_mb" (0: no cap; else a dump whose workspace would be larger is traced as given) */
+ * "dump_order_bits" (the key, 64 bins either way: 2 = the origin's cell at two bits per axis, 1 = one bit per axis under the direction octant), "dump_order_max_mb" (0: no cap; else a dump whose workspace would be larger is traced as given),
+ * "build_depth_cap" (levels of a device-built traversal tree beyond which the device builders are given up: LH_BUILD_DEPTH_MAX, what the walks' stacks take, or
+ * less -- tests of the host fallback and of a re-commit that cannot build),
+ * "updatable" (0 / 1, before the commit, device meshes only: the commit keeps the meshes for lh_accel_update_mesh_device / lh_accel_recommit) */
 extern "C" int lh_accel_set_param(lh_accel_t *a, const char *name, int value)
 {
     lh_guard guard(a);
@@ -1294,6 +1553,12 @@ extern "C" int lh_accel_set_param(lh_accel_t *a, const char *name, int value)
     else if (!strcmp(name, "dump_order_min") && value > 0) a->dump_order_min = (size_t)value;
     else if (!strcmp(name, "dump_order_bits") && (value == 1 || value == 2)) a->dump_order_bits = (uint32_t)value;
     else if (!strcmp(name, "dump_order_max_mb") && value >= 0) a->dump_order_max_mb = (size_t)value;
+    else if (!strcmp(name, "build_depth_cap") && value >= 1 && value <= LH_BUILD_DEPTH_MAX) a->build_depth_cap = value;
+    else if (!strcmp(name, "updatable") && (value == 0 || value == 1)) {
+        if (a->committed || a->commit_failed) return fail("lh_accel_set_param: \"updatable\" is set before the commit");
+        if (a->nmeshes) return fail("lh_accel_set_param: \"updatable\" is for device meshes: host meshes and device meshes cannot be mixed on one accelerator");
+        a->updatable = value;
+    }
     else if (!strcmp(name, "stack_cap") && (value == 0 || (value >= 8 && value <= 64 && value % 2 == 0))) a->dev.stack_cap = (uint32_t)value;
     else return fail("lh_accel_set_param: unknown parameter or bad value: %s = %d", name, value);
     return 0;

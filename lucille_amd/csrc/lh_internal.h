@@ -48,7 +48,9 @@ struct lh_dmesh_attr { void *block; size_t stride; int fmt, has; };          /* 
 #define LH_DATTR_NORMAL 5         /* slot of the normals behind the five LH_ATTR_* kinds */
 #define LH_DATTR_SLOTS 6
 struct lh_dmesh { void *block; const void *pos; const uint32_t *idx; size_t stride; uint32_t npos, ntris; int fmt;
-                  uint32_t nidx; int two_side; lh_dmesh_attr attr[LH_DATTR_SLOTS]; };      /* lh_accel_set_normals_device / _set_attribute_device: own copies, caller's format and stride */
+                  uint32_t nidx; int two_side;
+                  lh_dmesh_attr attr[LH_DATTR_SLOTS];      /* lh_accel_set_normals_device / _set_attribute_device: own copies, caller's format and stride */
+                  void *pos_own; };      /* the vertices an update handed over in another format or stride than block's (lh_accel_update_mesh_device); pos points into it then */
 typedef struct lh_dmesh_desc { const void *pos; const uint32_t *idx; unsigned long long stride; uint32_t npos, fmt; } lh_dmesh_desc_t;
 /* what k_gather_attributes reads of a mesh beside its lh_dmesh_desc_t: data[k] NULL = the mesh lacks slot k */
 typedef struct lh_dmesh_attr_desc { const void *data[LH_DATTR_SLOTS]; unsigned long long stride[LH_DATTR_SLOTS]; uint32_t f32_mask, two_side, nidx, pad; } lh_dmesh_attr_desc_t;
@@ -109,6 +111,10 @@ struct lh_accel {
     /* ... or staged device meshes (never both): device copies until the commit has flattened them */
     lh_dmesh *dmeshes; uint32_t ndmeshes; unsigned long long dmesh_tris;
     lh_dmesh_event *dmesh_events; uint32_t ndmesh_events;
+    /* "updatable" = 1: the commit keeps dmeshes and dmesh_events (ndmeshes stays non-zero on a committed accelerator: the only one), updates stage
+     * into them and lh_accel_recommit rebuilds from them.  update_fellback: the commit took dmesh_host_fallback, which needs the blocks gone */
+    int updatable, update_fellback, staged_pos, staged_attr;
+    int build_depth_cap;               /* 4-wide levels a device-built tree may have (device_upload returns -3 beyond: the host builders; a re-commit fails) */
     lh_host_scene *hs;        /* never NULL after create */
     void *d_ref_lca, *d_prim_leafpos, *d_ref_nodes, *d_ref_leaf_prims;   /* lucille's own tree: owned here, published in dev (lh_commit.hip publish_scene) */
     void *d_danger;                    /* 8 + LH_DANGER_MAX x 6 doubles: the count, then the boxes of lh_dev_scene_t.danger (lh_commit.hip lh_danger_scan) */
@@ -202,6 +208,7 @@ struct lh_accel {
 };
 
 #define LH_NCURSOR 64
+#define LH_BUILD_DEPTH_MAX 86     /* 3 d + 5 <= 264: the rows of k_overflow_fix's private stack */
 
 /* lucille calls accel->intersect from up to 16 render threads at once (render.c:1043-1105): every
  * entry point that touches the accelerator's buffers holds its lock */
