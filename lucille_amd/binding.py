@@ -884,9 +884,8 @@ class HipAccel:
                                              C.c_void_p(stream)), "lh_render_primary_rays")
         return org, dr
 
-    def render_ao_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed=1, uniforms=None, out=None,
-                       stream=None):
-        """-> (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict)"""
+    def _render_gather_tile(self, name, params, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream):
+        """render_ao_tile / _dirt_tile / _env_tile: the C function `name`; params: () for the AO tile, else (the caller's params or None,)"""
         import torch
         dev = torch.device("cuda", self.device)
         if out is None:
@@ -894,42 +893,27 @@ class HipAccel:
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         st = TileStats()
-        _check(self.L.lh_render_ao_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples, int(seed),
-                                        _dptr(uniforms), _dptr(out), C.byref(st), C.c_void_p(stream)),
-               "lh_render_ao_tile")
+        params = tuple(None if p is None else C.byref(p) for p in params)
+        _check(getattr(self.L, name)(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples, *params, int(seed),
+                                     _dptr(uniforms), _dptr(out), C.byref(st), C.c_void_p(stream)), name)
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def render_ao_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed=1, uniforms=None, out=None,
+                       stream=None):
+        """-> (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict)"""
+        return self._render_gather_tile("lh_render_ao_tile", (), cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
 
     def render_dirt_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, params=None, seed=1, uniforms=None, out=None,
                          stream=None):
         """lh_render_dirt_tile: the dirtmap transport's tile (params: a DirtParams, None: the defaults) ->
         (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x N, ao_occluded = the bounded hits)"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        st = TileStats()
-        _check(self.L.lh_render_dirt_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples,
-                                          None if params is None else C.byref(params), int(seed), _dptr(uniforms), _dptr(out),
-                                          C.byref(st), C.c_void_p(stream)), "lh_render_dirt_tile")
-        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+        return self._render_gather_tile("lh_render_dirt_tile", (params,), cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
 
     def render_env_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, params=None, seed=1, uniforms=None, out=None,
                         stream=None):
         """lh_render_env_tile: the environment-lit gather's tile (params: an EnvParams, None: the defaults) ->
         (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x N, ao_occluded = the occluded rays)"""
-        import torch
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        st = TileStats()
-        _check(self.L.lh_render_env_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples,
-                                         None if params is None else C.byref(params), int(seed), _dptr(uniforms), _dptr(out),
-                                         C.byref(st), C.c_void_p(stream)), "lh_render_env_tile")
-        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+        return self._render_gather_tile("lh_render_env_tile", (params,), cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
 
     def render_whitted_tile(self, cam, x0, y0, w, h, pixel_samples, params=None, out=None, stream=None):
         """lh_render_whitted_tile: the refraction chain's tile (params: a WhittedParams, None: the defaults) -- a camera miss sees the
@@ -1166,10 +1150,6 @@ class HipAccel:
         the far clip, AO_NO_HIT for a miss -- and the float32 tensor [n] of the mean weight (0 for a miss).  out: such a pair to
         fill (either member may be None, not both); with out=None the slots of rays that are not listed are UNSPECIFIED.
         Synchronous: the outputs are complete on return."""
-        if params is None:
-            params = DirtParams()
-        if not isinstance(params, DirtParams):
-            raise ValueError("dirt_device: params must be a DirtParams")
         return self._batch_stage_device("dirt_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
 
     def env_device(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None, index=None, count=None,
@@ -1180,21 +1160,27 @@ class HipAccel:
         gathered colour (zeros for a miss), the accelerator's environment (set_environment) seen by the rays that are not occluded.
         out: such a pair to fill (either member may be None, not both); with out=None the slots of rays that are not listed are
         UNSPECIFIED.  Synchronous: the outputs are complete on return."""
-        if params is None:
-            params = EnvParams()
-        if not isinstance(params, EnvParams):
-            raise ValueError("env_device: params must be an EnvParams")
         return self._batch_stage_device("env_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
 
-    def _batch_stage_device(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream):
-        """ao_device (dirt None) / dirt_device (dirt: its DirtParams) / env_device (dirt: its EnvParams; radiance [n, 3]): the checks and the call"""
+    # what -> (the C function, the type of params and how the refusal names it, the radiance is [n, 3])
+    _BATCH_STAGES = {"ao_device": ("lh_accel_ao_device", None, None, False),
+                     "dirt_device": ("lh_accel_dirt_device", DirtParams, "a DirtParams", False),
+                     "env_device": ("lh_accel_env_device", EnvParams, "an EnvParams", True)}
+
+    def _batch_stage_device(self, what, params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream):
+        """ao_device / dirt_device / env_device: the row of _BATCH_STAGES, the checks and the call (params None: the type's defaults)"""
         import torch
+        name, ptype, pname, env = self._BATCH_STAGES[what]
+        if ptype is not None:
+            if params is None:
+                params = ptype()
+            if not isinstance(params, ptype):
+                raise ValueError("%s: params must be %s" % (what, pname))
         n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
         dev = org.device
         ip, ni, cp = _list_args(index, count, what)
         if index is None and count is not None:
             ni = n
-        env = isinstance(dirt, EnvParams)
         if out is None:
             out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3) if env else n, dtype=torch.float32, device=dev))
         if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
@@ -1210,19 +1196,9 @@ class HipAccel:
         if stream is None:
             stream = torch.cuda.current_stream(dev)
         stream = getattr(stream, "cuda_stream", stream)
-        if env:
-            _check(self.L.lh_accel_env_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
-                                              C.byref(dirt), int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad),
-                                              C.c_void_p(stream)), "lh_accel_env_device")
-            return out
-        if dirt is not None:
-            _check(self.L.lh_accel_dirt_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
-                                               C.byref(dirt), int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad),
-                                               C.c_void_p(stream)), "lh_accel_dirt_device")
-            return out
-        _check(self.L.lh_accel_ao_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
-                                         int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad), C.c_void_p(stream)),
-               "lh_accel_ao_device")
+        pargs = () if ptype is None else (C.byref(params),)
+        _check(getattr(self.L, name)(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples), *pargs,
+                                     int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad), C.c_void_p(stream)), name)
         return out
 
     def ao_rays_device(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None, out=None, stream=None):

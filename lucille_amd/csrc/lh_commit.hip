@@ -552,14 +552,13 @@ static int upload_array(lh_accel_t *a, void **slot, const void *src, size_t byte
 
 static void release_device(lh_accel_t *a)
 {
-    lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_frame, &a->b_tot, &a->b_host,
+    lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_frame, &a->b_host,
                       &a->p_org2, &a->p_dir2, &a->p_path, &a->p_path2, &a->p_thr, &a->p_thr2, &a->p_rad, &a->p_counts};
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); i++) free_buf(bufs[i]);
-    for (lh_ao_scratch *sc : {&a->tile_ao, &a->batch_ao, &a->tile_dirt, &a->batch_dirt, &a->tile_env, &a->batch_env})
-        for (lh_buf *b : {&sc->slot, &sc->hitrec, &sc->key, &sc->occcount, &sc->aorg, &sc->adir, &sc->occ, &sc->blocks}) free_buf(b);
-    for (lh_dirt_scratch *sc : {&a->tile_dirt_t, &a->batch_dirt_t})
-        for (lh_buf *b : {&sc->t, &sc->bound, &sc->prim, &sc->uv}) free_buf(b);
-    for (lh_buf *b : {&a->d_tot, &a->d_rays, &a->e_tot, &a->e_rays, &a->e_host, &a->s_tile, &a->s_batch, &a->w_chain, &a->w_counts, &a->w_tile, &a->w_host}) free_buf(b);
+    /* the gather stage's scratch table: every entry is lh_buf after lh_buf */
+    static_assert(sizeof(a->gather) == sizeof(lh_buf) * LH_GATHER_BUFS * LH_GATHER_KINDS * 2, "lh_gather_scratch holds lh_buf members only");
+    for (size_t i = 0; i < sizeof(a->gather) / sizeof(lh_buf); i++) free_buf((lh_buf *)a->gather + i);
+    for (lh_buf *b : {&a->e_host, &a->w_chain, &a->w_counts, &a->w_tile, &a->w_host}) free_buf(b);
     if (a->d_total) (void)hipFree(a->d_total);
     scene_row rows[LH_SCENE_ROWS];
     scene_rows(a, NULL, rows);

@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/lucille_hip.h"     /* lh_camera_t, lh_material_t in the launcher signatures */
+#include "lh_gather.h"                     /* LH_GATHER_*: the kinds of gather stage */
 
 #define LH_BLOCK      256          /* 4 wavefronts of 64 lanes              */
 #define LH_MISS_PRIM  0xFFFFFFFFu
@@ -190,17 +191,21 @@ typedef struct lh_gather_src {
     uint32_t    budget_big;
 } lh_gather_src_t;
 
+/* what a fused stage leaves, by its kind (LH_GATHER_*, lh_gather.h), in the one array `out`:
+ *   AO    unsigned int per hit slot, the slot's occluded rays (zeroed by the launcher);
+ *   DIRT  double per gather ray, the t of ray (slot, r)'s closest hit under the one bound far_clip (lh_tmax.h) at element slot * N + r, 1e38 for a miss;
+ *   ENV   uint8_t per gather ray (lh_env.h): the AO stage's any-hit walk, the answer of ray (slot, r), 0 or 1, at element slot * N + r, written exactly
+ *         once (no memset, no atomic).
+ * Rays the persistent kernel does not finish go through the stream's fix-up queue: out of budget or stack rows to the cooperative walk, fragile hits (for
+ * DIRT the mark of a hit near the bound among them) to the reference's own walk; whoever finishes a ray stores the same word.  A queue overflow leaves
+ * DIRT and ENV words unwritten and AO counts short: the caller redoes the stage materialised */
+typedef struct lh_fused_out { int kind; void *out; double far_clip; } lh_fused_out_t;
+
 /* launchers implemented in lh_kernels.hip; their geometry: lh_plan.h */
 int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch, int variant, const lh_launch_ctx_t *ctx);
-/* the fused AO stage: occluded rays counted per slot in d_occ_count */
-int lh_launch_trace_ao(const lh_dev_scene_t *sc, const lh_gather_src_t *src, unsigned int *d_occ_count, unsigned long long *d_counters,
-                       const lh_launch_ctx_t *ctx);
-/* ... and the dirt stage's: closest hit under the one bound far_clip, the t of ray (slot, r)'s bounded record at element slot * N + r of d_t */
-int lh_launch_trace_dirt(const lh_dev_scene_t *sc, const lh_gather_src_t *src, double far_clip, double *d_t, unsigned long long *d_counters,
-                         const lh_launch_ctx_t *ctx);
-/* ... and the environment gather's (lh_env.h): the AO stage's any-hit walk, the answer of ray (slot, r) as a byte, 0 or 1, at element slot * N + r of d_occ */
-int lh_launch_trace_env(const lh_dev_scene_t *sc, const lh_gather_src_t *src, uint8_t *d_occ, unsigned long long *d_counters,
-                        const lh_launch_ctx_t *ctx);
+/* a fused gather stage: the rays of src made inside the persistent kernel, what they leave in out */
+int lh_launch_trace_gather(const lh_dev_scene_t *sc, const lh_gather_src_t *src, const lh_fused_out_t *out, unsigned long long *d_counters,
+                           const lh_launch_ctx_t *ctx);
 int lh_trace_formats_needed(int variant);
 int lh_trace_rows(const lh_dev_scene_t *sc);        /* LDS stack rows the default walk launches with on this scene (lh_plan.h) */
 

@@ -7,6 +7,8 @@
  *                   one way a batch of rays (lh_batch_t) reaches the kernels' launcher (lh_kernels.hip lh_launch_trace)
  *   lh_plan.h       the geometry of a persistent launch (rows, checked pushes, the top of the tree in LDS, workgroups per CU, the cooperative
  *                   walk beside it, the cursor chunk): plain C, read by the launchers, by size_grid and by tests/cpu_model/lh_plan_check.c
+ *   lh_gather.h     the kinds of gather stage (AO, dirt, environment) and its plan -- fused, late -- for a tile or a batch: plain C, read by
+ *                   lh_tile.hip and by tests/cpu_model/lh_gather_check.c
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
  *   lh_whitted.hip  the refraction chain (the reference's Whitted transport): its bounce kernel, its wavefront loop, its entry points
  */
@@ -69,12 +71,18 @@ struct lh_tex_block { int refs, width, height; float *host; void *dev; hipEvent_
 /* what a textured resolve and k_tex_batch read beside the per-sample slots: the closest-hit records by sample / ray id, the texture coordinates
  * per primitive (NULL: no mesh has any), the mesh ordinal per primitive, the per-mesh descriptor table */
 typedef struct lh_tex_args { const uint32_t *prim; const double *u, *v, *st6; const uint32_t *prim_mesh; const lh_tex_desc_t *table; } lh_tex_args_t;
-/* what the AO stage (lh_tile.hip ao_stage) owns for one kind of caller: slot of every sample / list entry, hit records, slot keys, per-slot
- * occlusion counts (fused), the materialised rays and their any-hit bytes, the compaction's block counts */
-struct lh_ao_scratch { lh_buf slot, hitrec, key, occcount, aorg, adir, occ, blocks; };
-/* ... and what the dirt stage adds for its gather rays (lh_dirt.h): the t of the bounded closest-hit records, and for a materialised stage the bounds and
- * the rest of the records (prim; u and v) */
-struct lh_dirt_scratch { lh_buf t, bound, prim, uv; };
+/* what the gather stage (lh_tile.hip ao_stage) owns for one transport (LH_GATHER_*, lh_gather.h) and one caller (the tile pipeline, a caller's batch):
+ * one entry of lh_accel::gather.  lh_buf members only (LH_GATHER_BUFS of them: the release is a loop).  Slot of every sample / list entry, hit
+ * records, slot keys, per-slot occlusion counts (fused AO), the materialised rays and the any-hit bytes (of a fused environment gather too), the
+ * compaction's block counts; */
+struct lh_gather_scratch {
+    lh_buf slot, hitrec, key, occcount, aorg, adir, occ, blocks;
+    lh_buf t, bound, prim, uv;          /* the dirt stage (lh_dirt.h): the t of its bounded closest-hit records; materialised, the bounds and the rest of the records */
+    lh_buf totals;                      /* a batch: the hits, then the resolve's 64 counters (a tile's are d_total) */
+    lh_buf rays;                        /* a dirt or environment tile: its camera rays and their records (org | dir | t | u | v | prim); the AO tile's are r_org ... r_v */
+    lh_buf sun;                         /* the sun's shadow rays and their any-hit bytes, per hit slot: org | dir | occ */
+};
+#define LH_GATHER_BUFS 15
 #define LH_AOQ_SLOTS 4
 #define LH_PIPE_DEPTH_MAX 8   /* staging blocks of a pipelined host batch (lh_query.hip) */
 
@@ -159,26 +167,14 @@ struct lh_accel {
     lh_buf r_diag;                     /* LH_STAGE_TIMING: wave start / exit clocks */
     lh_buf r_bands;                    /* lh_render_ao_bands: first line of every band */
     void *h_read;                      /* 1 KiB of pinned host memory: the read-backs at the end of an AO batch (occlusion totals, hit count, queue flags) */
-    /* tile-render scratch (lh_render_ao_tile): camera rays and closest-hit records, the frame of the host entry points, the AO stage's */
+    /* tile-render scratch (lh_render_ao_tile): camera rays and closest-hit records, the frame of the host entry points */
     lh_buf r_org, r_dir, r_prim, r_t, r_u, r_v, r_frame;
-    lh_ao_scratch tile_ao;
-    /* the AO stage's scratch for a caller's batch (lh_accel_ao_device / _ao_rays_device / _ao_host), apart from the tile's so that
-     * lh_render_scratch keeps showing the last tile call; the batch's totals (hits; 64 occlusion counters), lh_accel_ao_host's staging */
-    lh_ao_scratch batch_ao;
-    lh_buf b_tot, b_host;
-    /* the dirt stage (lh_render_dirt_tile, lh_accel_dirt_device / _host): scratch of its own for the tile and for a batch, so that lh_render_scratch
-     * keeps showing the last AO tile */
-    lh_ao_scratch tile_dirt, batch_dirt;
-    lh_dirt_scratch tile_dirt_t, batch_dirt_t;
-    lh_buf d_tot, d_rays;              /* a batch's totals; the tile's camera rays and their closest-hit records */
-    /* the environment gather (lh_render_env_tile, lh_accel_env_device / _host; lh_env.h): scratch of its own once more -- its any-hit bytes are the
-     * `occ` of these, fused or materialised -- a batch's totals, the tile's camera rays and records, lh_accel_environment_host's staging */
-    lh_ao_scratch tile_env, batch_env;
-    lh_buf e_tot, e_rays, e_host;
-    /* the sun-and-sky light (lh_accel_set_sky; lh_sky.h): sky_set 0 = none, the gather reads the environment; the sun's rays of a tile / a batch and
-     * their any-hit bytes (per hit slot: org | dir | occ) */
+    /* the gather stage's scratch, [LH_GATHER_*][LH_GATHER_TILE | LH_GATHER_BATCH]: every transport and either caller has a set of its own, so that
+     * lh_render_scratch keeps showing the last AO tile whatever ran since */
+    lh_gather_scratch gather[LH_GATHER_KINDS][2];
+    lh_buf b_host, e_host;             /* the staging of lh_accel_ao_host / _dirt_host / _env_host, and of lh_accel_environment_host / _sky_host */
+    /* the sun-and-sky light (lh_accel_set_sky; lh_sky.h): sky_set 0 = none, the gather reads the environment */
     lh_sky_src_t sky; int sky_set;
-    lh_buf s_tile, s_batch;
     /* the refraction chain (lh_whitted.hip; lh_whitted.h): the chain's compacted rays, ids and records, sized by list entries; its counts (one per depth);
      * the tile's camera rays, their records and the samples' colours; lh_accel_whitted_host's staging */
     lh_buf w_chain, w_counts, w_tile, w_host;
@@ -332,9 +328,6 @@ extern "C" int lh_render_launch_primary_region(const lh_camera_t *cam, int x0, i
 extern "C" int lh_render_launch_ao_rays(size_t nslots, int ntheta, int nphi, unsigned long long seed,
                                         const double *d_hitrec, const double *d_rnd,
                                         const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
-extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
-                                        const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
-                                        unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream);
 extern "C" int lh_render_launch_tex_batch(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count,
                                           const lh_tex_args_t *tex, uint32_t ntris, double *d_rgba, void *stream);
 extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
@@ -343,19 +336,10 @@ extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const do
                                               const unsigned long long *d_key, uint32_t *d_block_counts, uint32_t *d_slot_of_entry,
                                               double *d_hitrec, unsigned long long *d_slot_key, unsigned long long *d_total,
                                               uint32_t *d_nslots32, double eps, void *stream);
-extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
-                                              const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
-                                              uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream);
 extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigned long long *d_nslots, int ntheta, int nphi,
                                                 unsigned long long seed, const double *d_hitrec, const double *d_rnd,
                                                 const unsigned long long *d_slot_key, double *d_org, double *d_dir, void *stream);
 extern "C" int lh_render_launch_dirt_bounds(size_t n, double far_clip, double *d_bound, void *stream);
-extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
-                                             const uint32_t *d_slot_of_sample, const double *d_t, float *d_rgb,
-                                             unsigned long long *d_hit_total, const lh_tex_args_t *tex, void *stream);
-extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
-                                                   double near_clip, double far_clip, const uint32_t *d_slot_of_entry, const double *d_t,
-                                                   uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream);
 /* the accelerator's environment as the launchers take it (lh_accel_set_environment; never set: constant white) */
 typedef struct lh_env_src { float rgb[3]; const void *map; int w, h; } lh_env_src_t;
 /* ... as it stands now (never set: constant white; an explicit black environment stays black) */
@@ -366,26 +350,27 @@ static inline lh_env_src_t lh_env_source(const lh_accel_t *a)
     e.map = a->d_env_map; e.w = a->env.width; e.h = a->env.height;
     return e;
 }
-extern "C" int lh_render_launch_env_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
-                                            const lh_env_src_t *env, const uint32_t *d_slot_of_sample, const double *d_hitrec,
-                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
-                                            unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream);
-extern "C" int lh_render_launch_env_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
-                                                  unsigned long long seed, double scale, const lh_env_src_t *env, const uint32_t *d_slot_of_entry,
-                                                  const double *d_hitrec, const unsigned long long *d_slot_key, const double *d_adir,
-                                                  const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
-                                                  unsigned long long *d_occ_total, void *stream);
+/* the gather stage's resolves: what the stage left, and where its result goes -- a tile's pixels or a batch's per-ray outputs.
+ * lh_gather_left_t: the kind (LH_GATHER_*), the hemisphere's grid and the generator's seed; the per-slot counts of a fused AO stage (occ_count, or NULL:
+ * N any-hit bytes per slot at occ), the any-hit byte of every gather ray (occ: AO materialised, ENV either way), the dirt stage's t of every gather ray and
+ * its clips; for ENV the hit records and keys, the materialised directions (adir, or NULL: a fused stage, the resolve makes them again), the scale and the
+ * light -- the environment, or (sky != NULL) the sun-and-sky light with the sun's any-hit byte per slot (sun_occ, or NULL: no sun); total: 64 counters */
+typedef struct lh_gather_left {
+    int kind, ntheta, nphi; unsigned long long seed;
+    const unsigned int *occ_count; const uint8_t *occ; const double *t;
+    const double *hitrec; const unsigned long long *key; const double *adir;
+    double near_clip, far_clip, scale;
+    const lh_env_src_t *env; const lh_sky_src_t *sky; const uint8_t *sun_occ;
+    unsigned long long *total;
+} lh_gather_left_t;
+/* a region of w x h pixels (h = nbands * band_rows lines), xs * ys samples each, with the hit slot of every sample; tex or NULL: no mesh has a texture */
+typedef struct lh_resolve_tile { int w, h, band_rows, xs, ys; const uint32_t *slot_of_sample; float *rgb; const lh_tex_args_t *tex; } lh_resolve_tile_t;
+/* a list over n_rays rays (index, count: as lh_accel_intersect_device_indexed) with the hit slot of every entry (NULL: an empty scene, every traced ray
+ * is a miss); count_out[id] / value_out[id] (3 floats for ENV): either may be NULL */
+typedef struct lh_resolve_list { size_t n_list, n_rays; const uint32_t *index, *count, *slot_of_entry; uint32_t *count_out; float *value_out; } lh_resolve_list_t;
+extern "C" int lh_render_launch_tile_resolve(const lh_resolve_tile_t *to, const lh_gather_left_t *g, void *stream);
+extern "C" int lh_render_launch_list_resolve(const lh_resolve_list_t *to, const lh_gather_left_t *g, void *stream);
 extern "C" int lh_render_launch_env_fetch(size_t n, const lh_env_src_t *env, const double *d_dir, float *d_rgb, void *stream);
-/* ... under the sun-and-sky light (lh_sky_src_t, above) */
-extern "C" int lh_render_launch_sky_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
-                                            const lh_sky_src_t *sky, const uint8_t *d_sun_occ, const uint32_t *d_slot_of_sample, const double *d_hitrec,
-                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
-                                            unsigned long long *d_occ_total, void *stream);
-extern "C" int lh_render_launch_sky_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
-                                                  unsigned long long seed, double scale, const lh_sky_src_t *sky, const uint8_t *d_sun_occ,
-                                                  const uint32_t *d_slot_of_entry, const double *d_hitrec, const unsigned long long *d_slot_key,
-                                                  const double *d_adir, const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
-                                                  unsigned long long *d_occ_total, void *stream);
 extern "C" int lh_render_launch_sky_fetch(size_t n, const lh_sky_src_t *sky, const double *d_dir, float *d_rgb, void *stream);
 /* one ray per hit slot from the slot's hit record along sun_dir (d_nslots or NULL: the slot count on the device, nslots its upper bound) */
 extern "C" int lh_render_launch_sun_rays(size_t nslots, const unsigned long long *d_nslots, const double *d_hitrec, const double sun_dir[3],

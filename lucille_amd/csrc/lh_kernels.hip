@@ -835,7 +835,7 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_t
     trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
 }
 
-/* the persistent kernel of the fused dirt stage (lh_launch_trace_dirt): the gather rays of ao.nslots hits, made in the refill (SRC 1), walked to their
+/* the persistent kernel of the fused dirt stage (lh_launch_trace_gather, LH_GATHER_DIRT): the gather rays of ao.nslots hits, made in the refill (SRC 1), walked to their
  * CLOSEST hit under the launch's one bound ao.far_clip (TMAX); the retire stores the bounded record's t.  A kernel of its own once more */
 template <bool COUNT, int WALK>
 __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_dirt(
@@ -847,7 +847,7 @@ __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_dirt(
     trace_persist_lane<false, COUNT, WALK, 1, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
-/* the persistent kernel of the fused environment gather (lh_launch_trace_env): the AO stage's any-hit walk over the gather rays of ao.nslots hits
+/* the persistent kernel of the fused environment gather (lh_launch_trace_gather, LH_GATHER_ENV): the AO stage's any-hit walk over the gather rays of ao.nslots hits
  * (SRC 1), whose retire stores the ray's answer as a byte at occ[slot * N + r] (ENV).  A kernel of its own once more */
 template <bool COUNT, int WALK>
 __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_env(
@@ -1497,8 +1497,21 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-/* what the two fused stages differ in beside their kernels: the chunk before the clamp and the tail of AoSrc */
-struct FusedStage { bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; uint8_t *env_occ; };
+/* a fused stage's lh_fused_out_t (lh_device.h) as its kernels take it: the chunk before the clamp and the tail of AoSrc.  The AO rays of a slot are
+ * coherent: longer ranges per wave (LH_AO_CHUNK, latched on first use), and the grouped item order is the AO stage's experiment -- the dirt stage and
+ * the environment gather take the plain order (slot, sample) and LH_TILE_CHUNK */
+struct FusedStage {
+    bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; uint8_t *env_occ;
+    FusedStage(const lh_dev_scene_t *sc, const lh_fused_out_t &o)
+        : dirt(o.kind == LH_GATHER_DIRT), chunk(LH_TILE_CHUNK), occ_count(NULL), group(0), far_clip(dirt ? o.far_clip : 0.0),
+          dirt_t(dirt ? (double *)o.out : NULL), env_occ(o.kind == LH_GATHER_ENV ? (uint8_t *)o.out : NULL)
+    {
+        static uint32_t ao_chunk = 0;
+        if (o.kind != LH_GATHER_AO) return;
+        if (!ao_chunk) { const char *e = getenv("LH_AO_CHUNK"); ao_chunk = (e && atoi(e) >= 64 && atoi(e) <= 65536) ? (uint32_t)atoi(e) : LH_TILE_CHUNK; }
+        chunk = ao_chunk; occ_count = (unsigned int *)o.out; group = (int)sc->ao_group;
+    }
+};
 
 /* a fused stage: the gather rays of g.nslots hits, N = ntheta * nphi each, made inside the persistent kernel (SRC 1).  Rays that kernel does not
  * finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative walk) -- go through the stream's
@@ -1548,37 +1561,12 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
 
 } /* namespace */
 
-/* the AO stage of a tile with the rays generated inside the any-hit kernel (SRC 1 above): occluded rays counted per slot in d_occ_count (zeroed here) */
-extern "C" int lh_launch_trace_ao(const lh_dev_scene_t *sc, const lh_gather_src_t *src, unsigned int *d_occ_count, unsigned long long *d_counters,
-                                  const lh_launch_ctx_t *ctx)
+/* the fused gather stage of whatever kind (lh_fused_out_t, lh_device.h) */
+extern "C" int lh_launch_trace_gather(const lh_dev_scene_t *sc, const lh_gather_src_t *src, const lh_fused_out_t *out, unsigned long long *d_counters,
+                                      const lh_launch_ctx_t *ctx)
 {
-    static uint32_t ao_chunk = 0;
-    if (!ao_chunk) { const char *e = getenv("LH_AO_CHUNK"); ao_chunk = (e && atoi(e) >= 64 && atoi(e) <= 65536) ? (uint32_t)atoi(e) : LH_TILE_CHUNK; }
-    /* AO rays of a slot are coherent: longer ranges per wave (LH_AO_CHUNK) */
-    return launch_fused(sc, *src, FusedStage{false, ao_chunk, d_occ_count, (int)sc->ao_group, 0.0, NULL, NULL}, d_counters, *ctx);
-}
-
-/* the dirt stage (lh_dirt.h) the same way: the gather rays of nslots hits made inside a CLOSEST-hit kernel that walks them under the one bound
- * far_clip (lh_tmax.h) and stores the t of every ray's bounded record -- 1e38 for a miss -- at element slot * N + r of d_t; nothing else per ray
- * goes through HBM.  Rays the persistent kernel does not finish go through the queue as above: out of budget or stack rows to the cooperative walk,
- * fragile hits (the mark of a hit near the bound among them) to the reference's own walk, whose unbounded record is filtered by t < far_clip; both
- * store the same word.  A queue overflow leaves words unwritten: the caller redoes the stage materialised */
-extern "C" int lh_launch_trace_dirt(const lh_dev_scene_t *sc, const lh_gather_src_t *src, double far_clip, double *d_t, unsigned long long *d_counters,
-                                    const lh_launch_ctx_t *ctx)
-{
-    /* the gather rays of a slot are coherent, as AO rays are; the plain item order (slot, sample): the grouped order is the AO stage's experiment */
-    return launch_fused(sc, *src, FusedStage{true, LH_TILE_CHUNK, NULL, 0, far_clip, d_t, NULL}, d_counters, *ctx);
-}
-
-/* the environment gather (lh_env.h) the same way: the AO stage's rays and its any-hit walk, with the launch geometry of the AO stage (LH_PLAN_AO);
- * instead of a count per slot the answer of ray (slot, r), 0 or 1, is stored at byte slot * N + r of d_occ by whoever finishes the ray -- the lane
- * that retires it, the cooperative walk, the reference's own walk for a fragile hit.  Every byte of the first nslots * N is written exactly once
- * (no memset, no atomic) unless the queue overflows: the caller then redoes the stage materialised.  The plain item order (slot, sample) */
-extern "C" int lh_launch_trace_env(const lh_dev_scene_t *sc, const lh_gather_src_t *src, uint8_t *d_occ, unsigned long long *d_counters,
-                                   const lh_launch_ctx_t *ctx)
-{
-    if (!d_occ) return -1;
-    return launch_fused(sc, *src, FusedStage{false, LH_TILE_CHUNK, NULL, 0, 0.0, NULL, d_occ}, d_counters, *ctx);
+    if ((unsigned)out->kind >= LH_GATHER_KINDS || (out->kind == LH_GATHER_ENV && !out->out)) return -1;
+    return launch_fused(sc, *src, FusedStage(sc, *out), d_counters, *ctx);
 }
 
 extern "C" int lh_trace_rows(const lh_dev_scene_t *sc)

@@ -304,49 +304,88 @@ __device__ __forceinline__ bool tex_color(const TexArgs &tx, size_t i, double c[
     return true;
 }
 
-/* one thread per pixel: accumulates its sub-samples exactly like subsample()
- * (render.c:749-822) and bucket_write (:962-975): rgb[(h-1-ly)*w + lx].  TEX: radiance[k] *= texcol[k] where the hit's mesh has a
- * texture (ambientocclusion.c:393-401), accumulated per channel; false: the kernel the AO pipeline always ran */
-template <bool TEX>
-__device__ __forceinline__ void ao_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
-                                           const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
-                                           float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs *tx)
+/* a workgroup's count into one of the 64 counters at `total`: one atomic per WORKGROUP -- atomics on one address are served one after the other
+ * (~5 ns each); one per wave, 262 144 of them on a 4096^2 frame, were 1.2 of the 1.35 ms k_ao_resolve took */
+__device__ __forceinline__ void wg_total(unsigned int n, unsigned long long *__restrict__ total)
+{
+    __shared__ unsigned int wsum[4];
+    for (int off = 32; off > 0; off >>= 1) n += (unsigned int)__shfl_xor((int)n, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        if (tot) atomicAdd(total + (blockIdx.x & 63u), (unsigned long long)tot);
+    }
+}
+
+/* where pixel pix of a batch of h = nbands * band_rows lines goes in rgb: every band is flipped within itself, as a tile is (bucket_write,
+ * render.c:962-975: rgb[(h-1-ly)*w + lx]) */
+__device__ __forceinline__ float *pixel_out(float *__restrict__ rgb, size_t pix, int w, int band_rows)
+{
+    const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
+    return rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx);
+}
+
+/* what a hit slot is worth to the thread-per-pixel / thread-per-entry resolves, and the slot's count for the totals: the one expression in which the
+ * transports' resolves differ, and so their template parameter.  AO: (N - occluded) / N, from the per-slot count of a fused stage or the N any-hit
+ * bytes; dirt: lh_dirt_value over the N bounded t of the slot, in r order, and the bounded hits */
+struct AoValue {
+    int N; const uint8_t *__restrict__ occ; const unsigned int *__restrict__ occ_count;
+    __device__ __forceinline__ double operator()(uint32_t slot, unsigned int &c) const
+    {
+        if (occ_count) c = occ_count[slot];            /* fused AO stage: occluded rays were counted per slot */
+        else {
+            const uint8_t *o = occ + (size_t)slot * (size_t)N;
+            c = 0;
+            for (int r = 0; r < N; r++) if (o[r]) c++;
+        }
+        const double ns = (double)(uint32_t)N, occlusion = (double)c;
+        return 1.0 * (ns - occlusion) / ns;
+    }
+};
+struct DirtValue {
+    int N; double near_clip, far_clip; const double *__restrict__ tg;
+    __device__ __forceinline__ double operator()(uint32_t slot, unsigned int &c) const
+    {
+        uint32_t k;
+        const double val = lh_dirt_value(tg + (size_t)slot * (size_t)N, N, near_clip, far_clip, &k);
+        c = k;
+        return val;
+    }
+};
+
+/* one thread per pixel: accumulates its sub-samples exactly like subsample() (render.c:749-822) and writes like bucket_write (pixel_out); a miss
+ * gives 0, a hit its Value.  TEX: value[k] *= texcol[k] where the hit's mesh has a texture (ambientocclusion.c:393-401, dirtmap.c:273-281),
+ * accumulated per channel; false: one float to the three channels, the kernels the pipelines ran before textures.  Returns the thread's count */
+template <bool TEX, class Value>
+__device__ __forceinline__ unsigned int tile_resolve(int w, int h, int band_rows, int xs, int ys, const Value &value, const uint32_t *__restrict__ slot_of_sample,
+                                                     float *__restrict__ rgb, const TexArgs *tx)
 {
     LH_NC
     const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool inside = pix < (size_t)w * h;
-    /* h = all lines of the batch (nbands * band_rows); every band is flipped within itself, as a tile is */
-    const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
     double accum = 0.0, accum1 = 0.0, accum2 = 0.0;      /* (channels 1 and 2: TEX only) */
-    unsigned int nocc = 0;
+    unsigned int n = 0;
     const int S = inside ? xs * ys : 0;
     for (int s = 0; s < S; s++) {
         const uint32_t slot = slot_of_sample[pix * S + s];
-        double rad = 0.0;
+        double val = 0.0;
         if (slot != LH_MISS_PRIM) {
-            double occlusion = 0.0;
-            if (occ_count) {                       /* fused AO stage: occluded rays were counted per slot */
-                const unsigned int c = occ_count[slot];
-                occlusion = (double)c; nocc += c;
-            } else {
-                const uint8_t *o = occ + (size_t)slot * N;
-                for (int r = 0; r < N; r++) if (o[r]) { occlusion += 1.0; nocc++; }
-            }
-            const double ns = (double)(uint32_t)N;
-            rad = 1.0 * (ns - occlusion) / ns;
+            unsigned int c;
+            val = value(slot, c);
+            n += c;
         }
         if (TEX) {
             double c[4];
-            if (slot != LH_MISS_PRIM && tex_color(*tx, pix * S + s, c)) { accum = accum + rad * c[0]; accum1 = accum1 + rad * c[1]; accum2 = accum2 + rad * c[2]; }
-            else { accum = accum + rad; accum1 = accum1 + rad; accum2 = accum2 + rad; }
+            if (slot != LH_MISS_PRIM && tex_color(*tx, pix * S + s, c)) { accum = accum + val * c[0]; accum1 = accum1 + val * c[1]; accum2 = accum2 + val * c[2]; }
+            else { accum = accum + val; accum1 = accum1 + val; accum2 = accum2 + val; }
         } else
-        accum = accum + rad;
+        accum = accum + val;
     }
     if (inside) {
-        const double val = accum * ((double)1.0 / (xs * ys));
-        float f = (float)val;
+        float f = (float)(accum * ((double)1.0 / (xs * ys)));
         if (f < 0.0f) f = 0.0f;
-        float *o = rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx);
+        float *o = pixel_out(rgb, pix, w, band_rows);
         o[0] = f; o[1] = f; o[2] = f;
         if (TEX) {
             float f1 = (float)(accum1 * ((double)1.0 / (xs * ys))), f2 = (float)(accum2 * ((double)1.0 / (xs * ys)));
@@ -355,32 +394,23 @@ __device__ __forceinline__ void ao_resolve(int w, int h, int band_rows, int xs, 
             o[1] = f1; o[2] = f2;
         }
     }
-    if (occ_total) {
-        /* one atomic per WORKGROUP on one of 64 counters: atomics on one address are served one after the other (~5 ns each) --
-         * one per wave, 262 144 of them on a 4096^2 frame, were 1.2 of the 1.35 ms this kernel took */
-        __shared__ unsigned int wsum[4];
-        for (int off = 32; off > 0; off >>= 1) nocc += (unsigned int)__shfl_xor((int)nocc, off);
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nocc;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-            if (tot) atomicAdd(occ_total + (blockIdx.x & 63u), (unsigned long long)tot);
-        }
-    }
+    return n;
 }
 
 __global__ void k_ao_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
                              const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
                              float *__restrict__ rgb, unsigned long long *__restrict__ occ_total)
 {
-    ao_resolve<false>(w, h, band_rows, xs, ys, N, slot_of_sample, occ, occ_count, rgb, occ_total, NULL);
+    const unsigned int n = tile_resolve<false>(w, h, band_rows, xs, ys, AoValue{N, occ, occ_count}, slot_of_sample, rgb, NULL);
+    if (occ_total) wg_total(n, occ_total);
 }
 
 __global__ void k_ao_resolve_tex(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *__restrict__ slot_of_sample,
                                  const uint8_t *__restrict__ occ, const unsigned int *__restrict__ occ_count,
                                  float *__restrict__ rgb, unsigned long long *__restrict__ occ_total, const TexArgs tx)
 {
-    ao_resolve<true>(w, h, band_rows, xs, ys, N, slot_of_sample, occ, occ_count, rgb, occ_total, &tx);
+    const unsigned int n = tile_resolve<true>(w, h, band_rows, xs, ys, AoValue{N, occ, occ_count}, slot_of_sample, rgb, &tx);
+    if (occ_total) wg_total(n, occ_total);
 }
 
 /* ---- the AO stage for a caller's batch of hit records (lh_accel_ao_device / lh_accel_ao_rays_device) ----------------
@@ -448,44 +478,37 @@ __global__ void k_ao_batch_setup(const BatchList bl, const lh_dev_scene_t sc, co
     ao_hit_epilogue(sc.tri64, nrm9, org, dir, prim, t, u, v, (size_t)id, hitrec, slot_key, slot, EPS ? eps : 1.0e-6);
 }
 
-/* k_ao_resolve for a batch: one thread per list entry, the slot's occluded rays -> occluded_count[id] / radiance[id] (either may
- * be NULL); a traced miss gets LH_AO_NO_HIT / 0.  slot_of_entry NULL: an empty scene, every traced ray is a miss.  The batch's occluded
- * total goes to the 64 counters of occ_total, one atomic per workgroup */
+/* the resolve of a batch: one thread per list entry, the slot's Value and count -> count_out[id] / value_out[id] (either may be NULL); a traced miss
+ * gets LH_AO_NO_HIT / 0.  slot_of_entry NULL: an empty scene, every traced ray is a miss.  The batch's count goes to the 64 counters of total */
+template <class Value>
+__device__ __forceinline__ void batch_resolve(const BatchList &bl, const Value &value, const uint32_t *__restrict__ slot_of_entry,
+                                              uint32_t *__restrict__ count_out, float *__restrict__ value_out, unsigned long long *__restrict__ total)
+{
+    LH_NC
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    unsigned int n = 0;
+    if (batch_entry(bl, k, id)) {
+        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
+        uint32_t c = LH_AO_NO_HIT;
+        float val = 0.0f;
+        if (slot != LH_AO_NO_HIT) {
+            val = (float)value(slot, n);
+            c = n;
+        }
+        if (count_out) count_out[id] = c;
+        if (value_out) value_out[id] = val;
+    }
+    wg_total(n, total);
+}
+
+/* ... of the AO stage: occluded_count[id] / radiance[id] */
 __global__ void k_ao_batch_resolve(const BatchList bl, int N,
                                    const uint32_t *__restrict__ slot_of_entry, const uint8_t *__restrict__ occ,
                                    const unsigned int *__restrict__ occ_count, uint32_t *__restrict__ occluded_count,
                                    float *__restrict__ radiance, unsigned long long *__restrict__ occ_total)
 {
-    LH_NC
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    uint32_t id = 0;
-    unsigned int nocc = 0;
-    if (batch_entry(bl, k, id)) {
-        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
-        uint32_t c = LH_AO_NO_HIT;
-        float rad = 0.0f;
-        if (slot != LH_AO_NO_HIT) {
-            if (occ_count) c = occ_count[slot];            /* fused AO stage: occluded rays were counted per slot */
-            else {
-                const uint8_t *o = occ + (size_t)slot * (size_t)N;
-                c = 0;
-                for (int r = 0; r < N; r++) if (o[r]) c++;
-            }
-            nocc = c;
-            const double ns = (double)(uint32_t)N, occlusion = (double)c;
-            rad = (float)(1.0 * (ns - occlusion) / ns);          /* k_ao_resolve's expression */
-        }
-        if (occluded_count) occluded_count[id] = c;
-        if (radiance) radiance[id] = rad;
-    }
-    __shared__ unsigned int wsum[4];
-    for (int off = 32; off > 0; off >>= 1) nocc += (unsigned int)__shfl_xor((int)nocc, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nocc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (tot) atomicAdd(occ_total + (blockIdx.x & 63u), (unsigned long long)tot);
-    }
+    batch_resolve(bl, AoValue{N, occ, occ_count}, slot_of_entry, occluded_count, radiance, occ_total);
 }
 
 /* ---- the dirt stage (lh_dirt.h): the resolves read one double per gather ray -- the t of its bounded closest-hit record, at element
@@ -498,76 +521,19 @@ __global__ void k_dirt_bounds(size_t n, double far_clip, double *__restrict__ bo
     if (i < n) bound[i] = far_clip;
 }
 
-/* a workgroup's bounded hits into one of the 64 counters, one atomic per workgroup (k_ao_resolve has the numbers) */
-__device__ __forceinline__ void dirt_total(unsigned int nh, unsigned long long *__restrict__ total)
-{
-    __shared__ unsigned int wsum[4];
-    for (int off = 32; off > 0; off >>= 1) nh += (unsigned int)__shfl_xor((int)nh, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = nh;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned int tot = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        if (tot) atomicAdd(total + (blockIdx.x & 63u), (unsigned long long)tot);
-    }
-}
-
-/* k_ao_resolve for the dirt tile: a miss gives 0, a hit its value (ri_transport_dirtmap, dirtmap.c:234-292).  TEX: with the texture
- * multiply of :273-281, as ao_resolve; false: the kernel the dirt tile always ran */
-template <bool TEX>
-__device__ __forceinline__ void dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
-                                             const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
-                                             float *__restrict__ rgb, unsigned long long *__restrict__ hit_total, const TexArgs *tx)
-{
-    LH_NC
-    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool inside = pix < (size_t)w * h;
-    const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
-    double accum = 0.0, accum1 = 0.0, accum2 = 0.0;      /* (channels 1 and 2: TEX only) */
-    unsigned int nh = 0;
-    const int S = inside ? xs * ys : 0;
-    for (int s = 0; s < S; s++) {
-        const uint32_t slot = slot_of_sample[pix * S + s];
-        double val = 0.0;
-        if (slot != LH_MISS_PRIM) {
-            uint32_t c;
-            val = lh_dirt_value(tg + (size_t)slot * (size_t)N, N, near_clip, far_clip, &c);
-            nh += c;
-        }
-        if (TEX) {
-            double c[4];
-            if (slot != LH_MISS_PRIM && tex_color(*tx, pix * S + s, c)) { accum = accum + val * c[0]; accum1 = accum1 + val * c[1]; accum2 = accum2 + val * c[2]; }
-            else { accum = accum + val; accum1 = accum1 + val; accum2 = accum2 + val; }
-        } else
-        accum = accum + val;
-    }
-    if (inside) {
-        const double val = accum * ((double)1.0 / (xs * ys));
-        float f = (float)val;
-        if (f < 0.0f) f = 0.0f;
-        float *o = rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx);
-        o[0] = f; o[1] = f; o[2] = f;
-        if (TEX) {
-            float f1 = (float)(accum1 * ((double)1.0 / (xs * ys))), f2 = (float)(accum2 * ((double)1.0 / (xs * ys)));
-            if (f1 < 0.0f) f1 = 0.0f;
-            if (f2 < 0.0f) f2 = 0.0f;
-            o[1] = f1; o[2] = f2;
-        }
-    }
-    dirt_total(nh, hit_total);
-}
-
+/* k_ao_resolve for the dirt tile: a miss gives 0, a hit its value (ri_transport_dirtmap, dirtmap.c:234-292) */
 __global__ void k_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
                                const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
                                float *__restrict__ rgb, unsigned long long *__restrict__ hit_total)
 {
-    dirt_resolve<false>(w, h, band_rows, xs, ys, N, near_clip, far_clip, slot_of_sample, tg, rgb, hit_total, NULL);
+    wg_total(tile_resolve<false>(w, h, band_rows, xs, ys, DirtValue{N, near_clip, far_clip, tg}, slot_of_sample, rgb, NULL), hit_total);
 }
 
 __global__ void k_dirt_resolve_tex(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
                                    const uint32_t *__restrict__ slot_of_sample, const double *__restrict__ tg,
                                    float *__restrict__ rgb, unsigned long long *__restrict__ hit_total, const TexArgs tx)
 {
-    dirt_resolve<true>(w, h, band_rows, xs, ys, N, near_clip, far_clip, slot_of_sample, tg, rgb, hit_total, &tx);
+    wg_total(tile_resolve<true>(w, h, band_rows, xs, ys, DirtValue{N, near_clip, far_clip, tg}, slot_of_sample, rgb, &tx), hit_total);
 }
 
 /* the fetch alone for a batch of hit records (lh_accel_texture_device): one thread per list entry, 4 doubles at rgba[4 * id] -- texcol, or
@@ -586,28 +552,12 @@ __global__ void k_tex_batch(const BatchList bl, const TexArgs tx, uint32_t ntris
     o[0] = c[0]; o[1] = c[1]; o[2] = c[2]; o[3] = c[3];
 }
 
-/* k_ao_batch_resolve for the dirt stage: near_hits[id] / value[id] (either may be NULL); a traced miss gets LH_AO_NO_HIT / 0.
- * slot_of_entry NULL: an empty scene, every traced ray is a miss */
+/* k_ao_batch_resolve for the dirt stage: near_hits[id] / value[id] */
 __global__ void k_dirt_batch_resolve(const BatchList bl, int N, double near_clip, double far_clip,
                                      const uint32_t *__restrict__ slot_of_entry, const double *__restrict__ tg,
                                      uint32_t *__restrict__ near_hits, float *__restrict__ value, unsigned long long *__restrict__ hit_total)
 {
-    LH_NC
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    uint32_t id = 0;
-    unsigned int nh = 0;
-    if (batch_entry(bl, k, id)) {
-        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
-        uint32_t c = LH_AO_NO_HIT;
-        float val = 0.0f;
-        if (slot != LH_AO_NO_HIT) {
-            val = (float)lh_dirt_value(tg + (size_t)slot * (size_t)N, N, near_clip, far_clip, &c);
-            nh = c;
-        }
-        if (near_hits) near_hits[id] = c;
-        if (value) value[id] = val;
-    }
-    dirt_total(nh, hit_total);
+    batch_resolve(bl, DirtValue{N, near_clip, far_clip, tg}, slot_of_entry, near_hits, value, hit_total);
 }
 
 /* ---- the environment-lit gather (lh_env.h): the resolves read one byte per gather ray -- its any-hit answer, at element slot * N + r --
@@ -696,7 +646,6 @@ __device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs,
     const size_t pix = (size_t)blockIdx.x * (256 / LH_ENV_GROUP) + (threadIdx.x / LH_ENV_GROUP);
     const int gl = threadIdx.x & (LH_ENV_GROUP - 1);
     const bool inside = pix < (size_t)w * h;
-    const int lx = (int)(pix % w), line = (int)(pix / w), band = line / band_rows, ly = line % band_rows;
     const int S = xs * ys, N = gx.ntheta * gx.nphi;
     double accum = 0.0;          /* lanes 0-2: the pixel's channel */
     unsigned int nocc = 0;
@@ -718,9 +667,9 @@ __device__ __forceinline__ void env_resolve(int w, int h, int band_rows, int xs,
     if (inside && gl < 3) {
         float f = (float)(accum * ((double)1.0 / (xs * ys)));
         if (f < 0.0f) f = 0.0f;
-        rgb[3 * ((size_t)(band * band_rows + (band_rows - 1 - ly)) * w + lx) + gl] = f;
+        pixel_out(rgb, pix, w, band_rows)[gl] = f;
     }
-    dirt_total(nocc, occ_total);
+    wg_total(nocc, occ_total);
 }
 
 __global__ __launch_bounds__(256) void k_env_resolve(int w, int h, int band_rows, int xs, int ys, const EnvGather gx, const uint32_t *__restrict__ slot_of_sample,
@@ -766,7 +715,7 @@ __device__ __forceinline__ void env_batch_resolve(const BatchList &bl, const Env
         if (occluded_count && gl == 0) occluded_count[id] = hit ? c : LH_AO_NO_HIT;
         if (rgb && gl < 3) rgb[3 * (size_t)id + gl] = hit ? lh_env_finish(gx.scale, sum, gx.ntheta * gx.nphi) : 0.0f;
     }
-    dirt_total((hit && gl == 0) ? c : 0u, occ_total);
+    wg_total((hit && gl == 0) ? c : 0u, occ_total);
 }
 
 __global__ __launch_bounds__(256) void k_env_batch_resolve(const BatchList bl, const EnvGather gx, const uint32_t *__restrict__ slot_of_entry,
@@ -1230,19 +1179,69 @@ extern "C" int lh_render_launch_ao_rays_counted(size_t nslots_max, const unsigne
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-/* tex (or NULL: no mesh has a texture -- the kernel and the arguments of every frame before textures): the textured resolve */
-extern "C" int lh_render_launch_resolve(int w, int h, int band_rows, int xs, int ys, int N, const uint32_t *d_slot_of_sample,
-                                        const uint8_t *d_occ, const unsigned int *d_occ_count, float *d_rgb,
-                                        unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream)
+/* the environment gather's resolves -- a group of LH_ENV_GROUP lanes per pixel / list entry -- read the stage through an EnvGather.  adir: the
+ * materialised directions, or NULL: the fused stage (the directions are made again from the hit records and keys).  Under a sky the environment is none */
+static EnvGather env_gather(const lh_gather_left_t &g)
 {
-    const size_t total = (size_t)w * h;
+    const lh_env_src_t none = {{0.0f, 0.0f, 0.0f}, NULL, 0, 0};
+    EnvGather gx;
+    gx.ntheta = g.ntheta; gx.nphi = g.nphi; gx.seed = g.seed; gx.hitrec = g.hitrec; gx.slot_key = g.key; gx.adir = g.adir; gx.occ = g.occ;
+    gx.scale = g.scale; gx.env = env_of(g.sky ? none : *g.env);
+    return gx;
+}
+
+/* the resolve of a tile: what the stage left (g, by its kind and light) into the region's pixels (to).  to->tex NULL: no mesh has a texture -- the
+ * kernel and the arguments of every frame before textures; the sun-and-sky gather has no texture multiply (ambientocclusion.c:369-375) */
+extern "C" int lh_render_launch_tile_resolve(const lh_resolve_tile_t *to, const lh_gather_left_t *g, void *stream)
+{
+    const int w = to->w, h = to->h, band_rows = to->band_rows, xs = to->xs, ys = to->ys, N = g->ntheta * g->nphi;
+    const size_t total = (size_t)w * h, per = g->kind == LH_GATHER_ENV ? 256 / LH_ENV_GROUP : 256, nb = (total + per - 1) / per;
+    hipStream_t s = (hipStream_t)stream;
     if (total == 0) return 0;
-    if (tex)
-        hipLaunchKernelGGL(k_ao_resolve_tex, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           w, h, band_rows, xs, ys, N, d_slot_of_sample, d_occ, d_occ_count, d_rgb, d_occ_total, *tex);
-    else
-    hipLaunchKernelGGL(k_ao_resolve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, h, band_rows, xs, ys, N, d_slot_of_sample, d_occ, d_occ_count, d_rgb, d_occ_total);
+    if (nb > 0x7fffffffu) return -1;
+    const dim3 grid((unsigned)nb), block(256);
+    switch (g->kind) {
+    case LH_GATHER_AO:
+        if (to->tex) hipLaunchKernelGGL(k_ao_resolve_tex, grid, block, 0, s, w, h, band_rows, xs, ys, N, to->slot_of_sample, g->occ, g->occ_count, to->rgb, g->total, *to->tex);
+        else hipLaunchKernelGGL(k_ao_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, N, to->slot_of_sample, g->occ, g->occ_count, to->rgb, g->total);
+        break;
+    case LH_GATHER_DIRT:
+        if (to->tex) hipLaunchKernelGGL(k_dirt_resolve_tex, grid, block, 0, s, w, h, band_rows, xs, ys, N, g->near_clip, g->far_clip, to->slot_of_sample, g->t, to->rgb, g->total, *to->tex);
+        else hipLaunchKernelGGL(k_dirt_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, N, g->near_clip, g->far_clip, to->slot_of_sample, g->t, to->rgb, g->total);
+        break;
+    case LH_GATHER_ENV:
+        if (g->sky) hipLaunchKernelGGL(k_sky_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, env_gather(*g), *g->sky, g->sun_occ, to->slot_of_sample, to->rgb, g->total);
+        else if (to->tex) hipLaunchKernelGGL(k_env_resolve_tex, grid, block, 0, s, w, h, band_rows, xs, ys, env_gather(*g), to->slot_of_sample, to->rgb, g->total, *to->tex);
+        else hipLaunchKernelGGL(k_env_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, env_gather(*g), to->slot_of_sample, to->rgb, g->total);
+        break;
+    default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* ... and of a batch: into the two per-ray outputs of the list's rays (either may be NULL; slot_of_entry NULL: an empty scene) */
+extern "C" int lh_render_launch_list_resolve(const lh_resolve_list_t *to, const lh_gather_left_t *g, void *stream)
+{
+    if (to->n_list == 0) return 0;
+    if (to->n_list >= ((size_t)1 << 31) || to->n_rays >= ((size_t)1 << 31)) return -1;
+    const BatchList bl = {to->index, to->count, (uint32_t)to->n_list, (uint32_t)to->n_rays};
+    const size_t per = g->kind == LH_GATHER_ENV ? 256 / LH_ENV_GROUP : 256;
+    const dim3 grid((unsigned)((to->n_list + per - 1) / per)), block(256);
+    const int N = g->ntheta * g->nphi;
+    hipStream_t s = (hipStream_t)stream;
+    switch (g->kind) {
+    case LH_GATHER_AO:
+        hipLaunchKernelGGL(k_ao_batch_resolve, grid, block, 0, s, bl, N, to->slot_of_entry, g->occ, g->occ_count, to->count_out, to->value_out, g->total);
+        break;
+    case LH_GATHER_DIRT:
+        hipLaunchKernelGGL(k_dirt_batch_resolve, grid, block, 0, s, bl, N, g->near_clip, g->far_clip, to->slot_of_entry, g->t, to->count_out, to->value_out, g->total);
+        break;
+    case LH_GATHER_ENV:
+        if (g->sky) hipLaunchKernelGGL(k_sky_batch_resolve, grid, block, 0, s, bl, env_gather(*g), *g->sky, g->sun_occ, to->slot_of_entry, to->count_out, to->value_out, g->total);
+        else hipLaunchKernelGGL(k_env_batch_resolve, grid, block, 0, s, bl, env_gather(*g), to->slot_of_entry, to->count_out, to->value_out, g->total);
+        break;
+    default: return -1;
+    }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1257,7 +1256,7 @@ extern "C" int lh_render_launch_tex_batch(size_t n_list, size_t n_rays, const ui
 }
 
 /* the compaction of a batch's hits (list-aware k_hit_count, k_scan_blocks, k_ao_batch_setup); d_total: the number of hits (64 bits,
- * where lh_launch_trace_ao reads it); d_nslots32 (or NULL): the same as one uint32 */
+ * where lh_launch_trace_gather reads it); d_nslots32 (or NULL): the same as one uint32 */
 extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const double *d_nrm9, size_t n_list, size_t n_rays,
                                               const uint32_t *d_index, const uint32_t *d_count, const double *d_org, const double *d_dir,
                                               const uint32_t *d_prim, const double *d_t, const double *d_u, const double *d_v,
@@ -1276,127 +1275,12 @@ extern "C" int lh_render_launch_batch_compact(const lh_dev_scene_t *sc, const do
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-extern "C" int lh_render_launch_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
-                                              const uint32_t *d_slot_of_entry, const uint8_t *d_occ, const unsigned int *d_occ_count,
-                                              uint32_t *d_occluded_count, float *d_radiance, unsigned long long *d_occ_total, void *stream)
-{
-    if (n_list == 0) return 0;
-    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
-    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
-    hipLaunchKernelGGL(k_ao_batch_resolve, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       bl, N, d_slot_of_entry, d_occ, d_occ_count, d_occluded_count, d_radiance, d_occ_total);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-/* the dirt stage's launchers (kernels above): the bounds of a materialised stage, the two resolves */
+/* the bound array of a materialised dirt stage; the fetches alone of the sky and of the environment; the sun's rays */
 extern "C" int lh_render_launch_dirt_bounds(size_t n, double far_clip, double *d_bound, void *stream)
 {
     if (n == 0) return 0;
     if ((n + 255) / 256 > 0x7fffffffu) return -1;
     hipLaunchKernelGGL(k_dirt_bounds, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, far_clip, d_bound);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int lh_render_launch_dirt_resolve(int w, int h, int band_rows, int xs, int ys, int N, double near_clip, double far_clip,
-                                             const uint32_t *d_slot_of_sample, const double *d_t, float *d_rgb,
-                                             unsigned long long *d_hit_total, const lh_tex_args_t *tex, void *stream)
-{
-    const size_t total = (size_t)w * h;
-    if (total == 0) return 0;
-    if (tex)
-        hipLaunchKernelGGL(k_dirt_resolve_tex, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           w, h, band_rows, xs, ys, N, near_clip, far_clip, d_slot_of_sample, d_t, d_rgb, d_hit_total, *tex);
-    else
-    hipLaunchKernelGGL(k_dirt_resolve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       w, h, band_rows, xs, ys, N, near_clip, far_clip, d_slot_of_sample, d_t, d_rgb, d_hit_total);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int lh_render_launch_dirt_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int N,
-                                                   double near_clip, double far_clip, const uint32_t *d_slot_of_entry, const double *d_t,
-                                                   uint32_t *d_near_hits, float *d_value, unsigned long long *d_hit_total, void *stream)
-{
-    if (n_list == 0) return 0;
-    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
-    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
-    hipLaunchKernelGGL(k_dirt_batch_resolve, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       bl, N, near_clip, far_clip, d_slot_of_entry, d_t, d_near_hits, d_value, d_hit_total);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-/* the environment gather's launchers (kernels above): the two resolves -- a group of LH_ENV_GROUP lanes per pixel / list entry -- and the fetch alone.
- * d_adir: the materialised directions, or NULL: the fused stage (the directions are made again from the hit records and keys) */
-static EnvGather env_gather(int ntheta, int nphi, unsigned long long seed, double scale, const lh_env_src_t *env, const double *d_hitrec,
-                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ)
-{
-    EnvGather gx;
-    gx.ntheta = ntheta; gx.nphi = nphi; gx.seed = seed; gx.hitrec = d_hitrec; gx.slot_key = d_slot_key; gx.adir = d_adir; gx.occ = d_occ;
-    gx.scale = scale; gx.env = env_of(*env);
-    return gx;
-}
-
-extern "C" int lh_render_launch_env_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
-                                            const lh_env_src_t *env, const uint32_t *d_slot_of_sample, const double *d_hitrec,
-                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
-                                            unsigned long long *d_occ_total, const lh_tex_args_t *tex, void *stream)
-{
-    const size_t total = (size_t)w * h, per = 256 / LH_ENV_GROUP, nb = (total + per - 1) / per;
-    if (total == 0) return 0;
-    if (nb > 0x7fffffffu) return -1;
-    const EnvGather gx = env_gather(ntheta, nphi, seed, scale, env, d_hitrec, d_slot_key, d_adir, d_occ);
-    if (tex)
-        hipLaunchKernelGGL(k_env_resolve_tex, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, h, band_rows, xs, ys, gx, d_slot_of_sample, d_rgb,
-                           d_occ_total, *tex);
-    else
-        hipLaunchKernelGGL(k_env_resolve, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, h, band_rows, xs, ys, gx, d_slot_of_sample, d_rgb,
-                           d_occ_total);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int lh_render_launch_env_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
-                                                  unsigned long long seed, double scale, const lh_env_src_t *env, const uint32_t *d_slot_of_entry,
-                                                  const double *d_hitrec, const unsigned long long *d_slot_key, const double *d_adir,
-                                                  const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
-                                                  unsigned long long *d_occ_total, void *stream)
-{
-    if (n_list == 0) return 0;
-    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
-    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
-    const size_t per = 256 / LH_ENV_GROUP;
-    hipLaunchKernelGGL(k_env_batch_resolve, dim3((unsigned)((n_list + per - 1) / per)), dim3(256), 0, (hipStream_t)stream, bl,
-                       env_gather(ntheta, nphi, seed, scale, env, d_hitrec, d_slot_key, d_adir, d_occ), d_slot_of_entry, d_occluded_count, d_rgb, d_occ_total);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-/* ... and under the sun-and-sky light: the resolves' sky instantiations (d_sun_occ: a byte per slot, or NULL: no sun), the fetch alone, the sun's rays */
-extern "C" int lh_render_launch_sky_resolve(int w, int h, int band_rows, int xs, int ys, int ntheta, int nphi, unsigned long long seed, double scale,
-                                            const lh_sky_src_t *sky, const uint8_t *d_sun_occ, const uint32_t *d_slot_of_sample, const double *d_hitrec,
-                                            const unsigned long long *d_slot_key, const double *d_adir, const uint8_t *d_occ, float *d_rgb,
-                                            unsigned long long *d_occ_total, void *stream)
-{
-    const size_t total = (size_t)w * h, per = 256 / LH_ENV_GROUP, nb = (total + per - 1) / per;
-    const lh_env_src_t none = {{0.0f, 0.0f, 0.0f}, NULL, 0, 0};
-    if (total == 0) return 0;
-    if (nb > 0x7fffffffu) return -1;
-    hipLaunchKernelGGL(k_sky_resolve, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, w, h, band_rows, xs, ys,
-                       env_gather(ntheta, nphi, seed, scale, &none, d_hitrec, d_slot_key, d_adir, d_occ), *sky, d_sun_occ, d_slot_of_sample, d_rgb, d_occ_total);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-extern "C" int lh_render_launch_sky_batch_resolve(size_t n_list, size_t n_rays, const uint32_t *d_index, const uint32_t *d_count, int ntheta, int nphi,
-                                                  unsigned long long seed, double scale, const lh_sky_src_t *sky, const uint8_t *d_sun_occ,
-                                                  const uint32_t *d_slot_of_entry, const double *d_hitrec, const unsigned long long *d_slot_key,
-                                                  const double *d_adir, const uint8_t *d_occ, uint32_t *d_occluded_count, float *d_rgb,
-                                                  unsigned long long *d_occ_total, void *stream)
-{
-    if (n_list == 0) return 0;
-    if (n_list >= ((size_t)1 << 31) || n_rays >= ((size_t)1 << 31)) return -1;
-    const BatchList bl = {d_index, d_count, (uint32_t)n_list, (uint32_t)n_rays};
-    const lh_env_src_t none = {{0.0f, 0.0f, 0.0f}, NULL, 0, 0};
-    const size_t per = 256 / LH_ENV_GROUP;
-    hipLaunchKernelGGL(k_sky_batch_resolve, dim3((unsigned)((n_list + per - 1) / per)), dim3(256), 0, (hipStream_t)stream, bl,
-                       env_gather(ntheta, nphi, seed, scale, &none, d_hitrec, d_slot_key, d_adir, d_occ), *sky, d_sun_occ, d_slot_of_entry,
-                       d_occluded_count, d_rgb, d_occ_total);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

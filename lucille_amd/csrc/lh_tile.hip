@@ -74,44 +74,88 @@ static int stage_report(const stage_timer &tm, const void *d_clk, size_t nwaves,
     return 0;
 }
 
-/* The AO stage of the tile pipeline and of a caller's batch alike: from "the compaction has left hit records and keys (in b) and the hit count
- * (at d_nhit) on the device" to "occlusion totals, hit count and statistics words are on the host".  fused: the any-hit kernel generates ray
- * (slot, r) in its refill (lh_ao.h) and counts the occluded rays per slot -- nothing per AO ray goes through HBM.  Else, and as the second try
- * of a fused launch whose fix-up queue overflowed, materialised: AO rays in HBM (from d_uniforms if given: the parity replay), an any-hit batch.
- * late (with fused only): the count stays on the device -- the buffers are sized for the worst case (nmax slots: every sample / entry hits), the
- * kernels read it at d_nhit -- and the stage costs ONE host round trip, at its end (round 5: the two in the middle were ~0.25 ms of a rank's
- * 8.9 ms share of the config-5 frame).  Else the count is read first: it sizes the ray arrays and the launch.  resolve(from_counts) enqueues the
- * caller's radiance kernel (from the per-slot counts, or from the any-hit bytes), which adds the occluded rays into the 64 counters at d_nocc.
- * cnt: the LH_CNT_DEV counters or NULL; tm: stage timing or NULL (events 3-5: count known, any-hit done, resolved); prefix: of the messages */
-struct ao_totals { unsigned long long nhit, nocc, cnt[LH_CNT_DEV]; bool fused; };      /* cnt: the words at `cnt`; fused: the stage ended fused (no AO ray in HBM) */
-/* dirt (or NULL: ambient occlusion, the code above as it always ran): the stage of the dirtmap transport (lh_dirt.h) -- the hit records were built with
- * the dirt origin; what the stage leaves is the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), one double at
- * element slot * N + r of dirt->ts->t, for the caller's resolve: fused and materialised differ only in who wrote it.  fused: the closest-hit kernel
- * generates the ray in its refill and stores that word at its retire (lh_launch_trace_dirt).  Materialised: gather rays in HBM, ONE bounded
- * closest-hit launch through the ray dumps' kernels with a bound array filled with far_clip.  nocc then totals the bounded hits */
-struct dirt_stage { lh_dirt_params_t p; lh_dirt_scratch *ts; };
-/* env: the stage of the environment gather (lh_env.h) -- the AO stage's rays (the hit records were built with the gather's origin) and its any-hit
- * answers, but one per RAY: what the stage leaves is a byte, 0 or 1, at element slot * N + r of b->occ, for the caller's colour resolve; fused and
- * materialised differ only in who wrote it.  fused: the any-hit kernel stores the byte where the AO stage counts (lh_launch_trace_env).  Materialised:
- * the AO stage's own path, whose any-hit launch writes that array.  nocc totals the occluded rays, as for AO */
-/* sun (or NULL; with env only): the sun's shadow ray of the sun-and-sky light (lh_sky.h) -- one more ray per hit slot from the slot's origin along
- * the light's direction, written by k_sun_rays and answered by ONE plain any-hit launch, a ray dump as lh_accel_intersect_device traces it: no slot
- * key, so no self-primitive skip (a sun behind the surface is shadowed by the hit's own triangle).  What it leaves is a byte per slot at sun->occ,
- * for the caller's resolve, the same whether the N gather rays are then traced fused or materialised.  It runs BEFORE them: a launch resets the
- * stream's fix-up queue, whose words a late stage reads at its end.  late: the slot count is on the device, the launch is the identity list's with
- * its count there (lh_launch_opt::n_dev).  Not counted: cnt and the totals stay the gather rays' */
-struct sun_stage { const double *dir; lh_buf *buf; const uint8_t *occ; };
-#define LH_SUN_LATE_MAX ((size_t)1 << 30)        /* slots up to which the sun's launch can take its count from the device (a list holds 2^30 entries) */
-#define LH_ENV_LATE_MAX ((size_t)1 << 28)        /* gather rays (256 MiB of bytes) up to which a stage is sized for its worst case, the count left on the device */
-#define LH_DIRT_CHUNK ((size_t)1 << 30)          /* rays of one bounded launch at most (a list holds 2^30 entries) */
-#define LH_DIRT_LATE_MAX ((size_t)1 << 27)       /* gather rays (1 GiB of t) up to which a stage is sized for its worst case, the count left on the device */
+/* ---- the gather stage: one description of its transport ------------------------------------------------------------------------------------
+ * The kind (LH_GATHER_*, lh_gather.h) with its checked parameters, as the entry points hand it on: AO has none and offsets its rays by 1e-6 along Ns */
+struct gather_params { int kind; double eps; lh_dirt_params_t dirt; lh_env_params_t env; };
+/* ... and what ao_region / ao_batch_device make of it, once, at their top, for the stage and the resolves: the scratch entry of the kind and the caller
+ * (lh_accel::gather), the light of an environment gather -- the accelerator's environment, or while a sky is set (lh_sky.h) the sun-and-sky light, with
+ * LH_SKY_SUN the sun's direction: every hit then traces the sun's shadow ray -- the texture arguments of a tile's resolve (NULL: no mesh has a texture;
+ * the sun-and-sky gather has no texture fetch: ambientocclusion.c:369-375), and the prefix of the stage's messages */
+struct gather_desc {
+    gather_params p;
+    int where;                      /* LH_GATHER_TILE | LH_GATHER_BATCH */
+    lh_gather_scratch *b;
+    lh_env_src_t esrc; const lh_sky_src_t *sky; const double *sun_dir;
+    lh_tex_args_t tex_store; const lh_tex_args_t *tex;
+    const char *prefix;
+};
+static const char *const gather_device_name[LH_GATHER_KINDS] = {"lh_accel_ao_device", "lh_accel_dirt_device", "lh_accel_env_device"};
+static const char *const gather_prefix[LH_GATHER_KINDS] = {"lh_accel_ao_device: ", "lh_accel_dirt_device: ", "lh_accel_env_device: "};
+
+static void gather_describe(lh_accel_t *a, const gather_params &p, int where, gather_desc *d)
+{
+    d->p = p; d->where = where;
+    d->b = &a->gather[p.kind][where];
+    d->esrc = lh_env_source(a);
+    d->sky = (p.kind == LH_GATHER_ENV && a->sky_set) ? &a->sky : NULL;
+    d->sun_dir = (d->sky && (d->sky->sky.flags & LH_SKY_SUN)) ? d->sky->sky.sun_dir : NULL;
+    d->tex = NULL;
+    d->prefix = where == LH_GATHER_TILE ? "" : gather_prefix[p.kind];
+}
+
+/* what the stage left, as the resolves take it (lh_gather_left_t, lh_internal.h).  fused: the stage ended fused -- AO counted per slot, the environment
+ * gather has no direction in memory (the resolve makes them again); sun_occ: the sun's bytes (or NULL); total: the resolve's 64 counters */
+static lh_gather_left_t gather_left(const gather_desc &d, ao_grid g, uint64_t seed, bool fused, const uint8_t *sun_occ, unsigned long long *total)
+{
+    const lh_gather_scratch *b = d.b;
+    lh_gather_left_t l;
+    l.kind = d.p.kind; l.ntheta = g.ntheta; l.nphi = g.nphi; l.seed = seed;
+    l.occ_count = fused ? (const unsigned int *)b->occcount.p : NULL; l.occ = (const uint8_t *)b->occ.p; l.t = (const double *)b->t.p;
+    l.hitrec = (const double *)b->hitrec.p; l.key = (const unsigned long long *)b->key.p; l.adir = fused ? NULL : (const double *)b->adir.p;
+    l.near_clip = d.p.dirt.near_clip; l.far_clip = d.p.dirt.far_clip; l.scale = d.p.env.scale;
+    l.env = &d.esrc; l.sky = d.sky; l.sun_occ = sun_occ; l.total = total;
+    return l;
+}
+
+/* The gather stage of the tile pipeline and of a caller's batch alike: from "the compaction has left hit records and keys (in d.b) and the hit count
+ * (at d_nhit) on the device" to "totals, hit count and statistics words are on the host".  The hit records were built with the kind's origin (d.p.eps).
+ * What the stage leaves for the caller's resolve depends on its kind alone -- fused and materialised differ only in who wrote it:
+ *   AO    fused, the occluded rays of every slot counted in occcount; materialised, the any-hit byte of ray (slot, r) at element slot * N + r of occ;
+ *   ENV   (lh_env.h) that byte either way: the resolve needs the answer of every RAY;
+ *   DIRT  (lh_dirt.h) the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), a double at element slot * N + r of t.
+ * plan.fused: the kernel generates ray (slot, r) in its refill (lh_ao.h) -- nothing per gather ray goes through HBM but what is left
+ * (lh_launch_trace_gather).  Else, and as the second try of a fused launch whose fix-up queue overflowed, materialised: gather rays in HBM (from
+ * d_uniforms if given: the parity replay), then an any-hit batch, or for DIRT ONE bounded closest-hit launch per LH_DIRT_CHUNK rays through the ray
+ * dumps' kernels with a bound array filled with far_clip.
+ * plan.late (with fused only): the count stays on the device -- the buffers are sized for the worst case (nmax slots: every sample / entry hits), the
+ * kernels read it at d_nhit -- and the stage costs ONE host round trip, at its end (round 5: the two in the middle were ~0.25 ms of a rank's 8.9 ms
+ * share of the config-5 frame).  Else the count is read first: it sizes the ray arrays and the launch.
+ * d.sun_dir (or NULL): the sun's shadow ray of the sun-and-sky light -- one more ray per hit slot from the slot's origin along the light's direction,
+ * written by k_sun_rays and answered by ONE plain any-hit launch, a ray dump as lh_accel_intersect_device traces it: no slot key, so no self-primitive
+ * skip (a sun behind the surface is shadowed by the hit's own triangle).  It leaves a byte per slot, the same whether the N gather rays are then traced
+ * fused or materialised, and runs BEFORE them: a launch resets the stream's fix-up queue, whose words a late stage reads at its end.  late: the slot
+ * count is on the device, the launch is the identity list's with its count there (lh_launch_opt::n_dev).  Not counted: cnt and the totals stay the
+ * gather rays'.
+ * resolve(left) enqueues the caller's radiance kernel over what the stage left (gather_left), which adds its count -- occluded rays; DIRT: bounded
+ * hits -- into the 64 counters at d_nocc.  cnt: the LH_CNT_DEV counters or NULL; tm: stage timing or NULL (events 3-5: count known, rays traced, resolved) */
+struct ao_totals { unsigned long long nhit, nocc, cnt[LH_CNT_DEV]; bool fused; };      /* cnt: the words at `cnt`; fused: the stage ended fused (no gather ray in HBM) */
 template <class Resolve>
-static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t nmax, ao_grid g, uint64_t seed, const void *d_uniforms,
+static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g, uint64_t seed, const void *d_uniforms,
                     const unsigned long long *d_nhit, unsigned long long *d_nocc, unsigned long long *cnt, const lh_launch_opt &opt,
-                    stage_timer *tm, bool fused, bool late, Resolve resolve, const dirt_stage *dirt, bool env, hipStream_t s, ao_totals *out,
-                    sun_stage *sun = NULL)
+                    stage_timer *tm, lh_gather_plan_t plan, Resolve resolve, hipStream_t s, ao_totals *out)
 {
     const unsigned long long N = (unsigned long long)g.N;
+    lh_gather_scratch *b = d.b;
+    const char *prefix = d.prefix;
+    bool fused = plan.fused != 0;
+    const bool late = plan.late != 0;
+    /* what the stage leaves per hit slot: the buffer a fused stage sizes and its kernel fills, and the launch of a materialised one */
+    lh_buf *left; size_t slot_bytes; bool bounded = false; const char *fused_name;
+    switch (d.p.kind) {
+    case LH_GATHER_AO:  left = &b->occcount; slot_bytes = sizeof(unsigned int); fused_name = "fused AO"; break;                    /* a count per slot */
+    case LH_GATHER_ENV: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused environment-gather"; break;                    /* a byte per ray */
+    default:            left = &b->t; slot_bytes = (size_t)N * 8; fused_name = "fused dirt"; bounded = true; break;                /* DIRT: a double per ray */
+    }
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
     if (!a->h_read) HIPCHK(hipHostMalloc(&a->h_read, 1024, hipHostMallocDefault));
     unsigned long long *h_nocc64 = (unsigned long long *)a->h_read, *h_nhit = h_nocc64 + 64; uint32_t *h_qc = (uint32_t *)(h_nocc64 + 65);
@@ -123,19 +167,19 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
         /* the persistent kernel's ray index has 32 bits; nothing was hit: nothing to trace, the resolve sees misses only */
         if (nhit * N >= (1ull << 31) || nhit == 0) fused = false;
     }
-    if (sun) {
+    const uint8_t *sun_occ = NULL;
+    if (d.sun_dir) {
         const size_t ns = late ? nmax : (size_t)nhit;
-        sun->occ = NULL;
         if (ns) {
-            if (ensure_buf(sun->buf, ns * 49)) return -1;          /* org | dir | occ */
-            double *sorg = (double *)sun->buf->p, *sdir = sorg + 3 * ns;
+            if (ensure_buf(&b->sun, ns * 49)) return -1;          /* org | dir | occ */
+            double *sorg = (double *)b->sun.p, *sdir = sorg + 3 * ns;
             uint8_t *socc = (uint8_t *)(sdir + 3 * ns);
-            if (lh_render_launch_sun_rays(ns, late ? d_nhit : NULL, (const double *)b->hitrec.p, sun->dir, sorg, sdir, s) != 0)
+            if (lh_render_launch_sun_rays(ns, late ? d_nhit : NULL, (const double *)b->hitrec.p, d.sun_dir, sorg, sdir, s) != 0)
                 return fail("%ssun ray kernel launch failed", prefix);
             lh_launch_opt o;
             if (late) { o.indexed = true; o.index = NULL; o.idx_nrays = (uint32_t)ns; o.n_dev = (const uint32_t *)d_nhit; }          /* the count's low word: it is below 2^31 */
             if (lh_launch(a, lh_batch_t{ns, LH_MODE_ANY, sorg, sdir, NULL, NULL, NULL, NULL, socc, NULL}, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
-            sun->occ = socc;
+            sun_occ = socc;
         }
     }
     if (tm) HIPCHK(hipEventRecord(tm->ev[3], s));
@@ -153,7 +197,7 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
     };
     if (fused) {
         const size_t nslots = late ? nmax : (size_t)nhit;
-        if (dirt ? ensure_buf(&dirt->ts->t, nslots * (size_t)N * 8) : env ? ensure_buf(&b->occ, nslots * (size_t)N) : ensure_buf(&b->occcount, nslots * sizeof(unsigned int))) return -1;
+        if (ensure_buf(left, nslots * slot_bytes)) return -1;
         qslot = lh_aoq_slot(a, s);
         if (qslot < 0) return -1;
         lh_dev_scene_t sc = a->dev;          /* the launch's own scene: its visit budget, its clocks */
@@ -168,53 +212,45 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
         const lh_gather_src_t src = {nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
                                      late ? d_nhit : NULL, late ? big : 0u};
         const lh_launch_ctx_t ctx = {lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, (void *)s};
-        if (dirt) {
-            if (lh_launch_trace_dirt(&sc, &src, dirt->p.far_clip, (double *)dirt->ts->t.p, cnt, &ctx) != 0)
-                return fail("%sfused dirt launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
-        } else
-        if (env) {
-            if (lh_launch_trace_env(&sc, &src, (uint8_t *)b->occ.p, cnt, &ctx) != 0)
-                return fail("%sfused environment-gather launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
-        } else
-        if (lh_launch_trace_ao(&sc, &src, (unsigned int *)b->occcount.p, cnt, &ctx) != 0)
-            return fail("%sfused AO launch failed: %s", prefix, hipGetErrorString(hipGetLastError()));
+        const lh_fused_out_t fo = {d.p.kind, left->p, d.p.dirt.far_clip};
+        if (lh_launch_trace_gather(&sc, &src, &fo, cnt, &ctx) != 0)
+            return fail("%s%s launch failed: %s", prefix, fused_name, hipGetErrorString(hipGetLastError()));
         if (!late) {
             if (wait_queue() != 0) return -1;
-            fused = h_qc[1] == 0;             /* more than LH_AO_QCAP uncertain AO rays: redo the stage materialised */
+            fused = h_qc[1] == 0;             /* more than LH_AO_QCAP uncertain gather rays: redo the stage materialised */
         }
     }
-    /* stages 4-5 with the AO rays in HBM */
+    /* stages 4-5 with the gather rays in HBM */
     auto materialised = [&]() -> int {
         const size_t nao = (size_t)(nhit * N);
         if (!nao) return 0;
-        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!dirt && ensure_buf(&b->occ, nao))) return -1;
-        /* 4. AO rays */
+        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!bounded && ensure_buf(&b->occ, nao))) return -1;
+        /* 4. gather rays */
         if (lh_render_launch_ao_rays((size_t)nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
                                      (const unsigned long long *)b->key.p, (double *)b->aorg.p, (double *)b->adir.p, s) != 0)
             return fail("%sAO ray kernel launch failed", prefix);
         /* 5. any-hit.  The abandoned fused pass is not counted (nor is what the caller counted before the stage) */
         if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
-        if (dirt) {          /* 5. the dirt stage: closest hit under the bound far_clip, the records' t kept */
-            lh_dirt_scratch *ts = dirt->ts;
+        if (bounded) {          /* 5. the dirt stage: closest hit under the bound far_clip, the records' t kept */
             const size_t nb = nao < LH_DIRT_CHUNK ? nao : LH_DIRT_CHUNK;
-            if (ensure_buf(&ts->t, nao * 8) || ensure_buf(&ts->bound, nb * 8) || ensure_buf(&ts->prim, nb * 4) || ensure_buf(&ts->uv, nb * 16)) return -1;
-            if (lh_render_launch_dirt_bounds(nb, dirt->p.far_clip, (double *)ts->bound.p, s) != 0) return fail("%sbound kernel launch failed", prefix);
+            if (ensure_buf(&b->t, nao * 8) || ensure_buf(&b->bound, nb * 8) || ensure_buf(&b->prim, nb * 4) || ensure_buf(&b->uv, nb * 16)) return -1;
+            if (lh_render_launch_dirt_bounds(nb, d.p.dirt.far_clip, (double *)b->bound.p, s) != 0) return fail("%sbound kernel launch failed", prefix);
             for (size_t off = 0; off < nao; off += LH_DIRT_CHUNK) {
                 const size_t m = nao - off < LH_DIRT_CHUNK ? nao - off : LH_DIRT_CHUNK;
                 lh_launch_opt o = opt;
-                o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = ts->bound.p;
-                const lh_batch_t rays = {m, LH_MODE_CLOSEST, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, ts->prim.p,
-                                         (double *)ts->t.p + off, ts->uv.p, (double *)ts->uv.p + m, NULL, cnt};
+                o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = b->bound.p;
+                const lh_batch_t rays = {m, LH_MODE_CLOSEST, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, b->prim.p,
+                                         (double *)b->t.p + off, b->uv.p, (double *)b->uv.p + m, NULL, cnt};
                 if (lh_launch(a, rays, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
             }
             return 0;
         }
         return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, b->aorg.p, b->adir.p, NULL, NULL, NULL, NULL, b->occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
     };
-    /* 6. radiance, and its occlusion totals on their way to the host */
-    auto resolved = [&](bool from_counts) -> int {
+    /* 6. radiance, and its totals on their way to the host */
+    auto resolved = [&](bool from_fused) -> int {
         HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
-        if (resolve(from_counts) != 0) return -1;
+        if (resolve(gather_left(d, g, seed, from_fused, sun_occ, d_nocc)) != 0) return -1;
         HIPCHK(hipMemcpyAsync(h_nocc64, d_nocc, sizeof(unsigned long long) * 64, hipMemcpyDeviceToHost, s));
         return 0;
     };
@@ -223,9 +259,9 @@ static int ao_stage(lh_accel_t *a, const char *prefix, lh_ao_scratch *b, size_t 
     if (resolved(fused) != 0) return -1;
     if (tm) HIPCHK(hipEventRecord(tm->ev[5], s));
     if (late) {
-        /* the stage's one round trip: hit count, occlusion totals, the queue's overflow flag */
+        /* the stage's one round trip: hit count, totals, the queue's overflow flag */
         if (wait_queue() != 0) return -1;
-        if (h_qc[1] != 0) {                           /* more than LH_AO_QCAP uncertain AO rays: the stage once more, materialised */
+        if (h_qc[1] != 0) {                           /* more than LH_AO_QCAP uncertain gather rays: the stage once more, materialised */
             fused = false;
             if (materialised() != 0 || resolved(false) != 0) return -1;
             HIPCHK(hipStreamSynchronize(s));
@@ -258,13 +294,27 @@ static int env_params(const char *what, const lh_env_params_t *params, lh_env_pa
     return 0;
 }
 
-#define env_source lh_env_source          /* lh_internal.h */
+/* the kind of an entry point and its caller's parameters (NULL: the defaults; AO has none), checked */
+static int gather_check(const char *what, int kind, const void *params, gather_params *p)
+{
+    const lh_env_params_t env_def = LH_ENV_DEFAULTS;
+    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def};
+    if (kind == LH_GATHER_DIRT) {
+        if (dirt_params(what, (const lh_dirt_params_t *)params, &p->dirt) != 0) return -1;
+        p->eps = p->dirt.eps;
+    }
+    if (kind == LH_GATHER_ENV) {
+        if (env_params(what, (const lh_env_params_t *)params, &p->env) != 0) return -1;
+        p->eps = p->env.eps;
+    }
+    return 0;
+}
 
-/* one device batch of the AO pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands.  dirt (or NULL): the dirtmap
- * transport's tile -- the same pipeline with the dirt origin, the dirt stage and its resolve, in scratch of its own */
-static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0, int y0,
+/* one device batch of the gather pipeline over a Region (lh_render.hip): a rectangle, or nbands full-width bands.  p: the transport -- every kind runs
+ * the same pipeline with its own origin, stage and resolve, in scratch of its own */
+static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *cam, int x0, int w, int nbands, int band_rows, const int *d_band_y0, int y0,
                      uint64_t valid_pixels, int ps, int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb,
-                     lh_tile_stats_t *stats, void *stream, const lh_dirt_params_t *dirt = NULL, const lh_env_params_t *env = NULL)
+                     lh_tile_stats_t *stats, void *stream)
 {
     const int h = nbands * band_rows;              /* lines of the batch */
     HIPCHK(hipSetDevice(a->device));
@@ -275,31 +325,23 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
         return fail("AO pipeline: more than 2^34 samples in the frame (slot keys carry 34 bits)");
     if (S >= ((size_t)1 << 31)) return fail("AO pipeline: more than 2^31 samples in one batch; render the frame in tiles");     /* 32-bit sample indices on the device */
     const unsigned nb = (unsigned)((S + 255) / 256);
-    lh_ao_scratch *b = dirt ? &a->tile_dirt : env ? &a->tile_env : &a->tile_ao;
-    const double eps = dirt ? dirt->eps : env ? env->eps : 1.0e-6;          /* the gather rays' offset along Ns */
-    const lh_env_src_t esrc = env_source(a);
-    /* the sun-and-sky light (lh_sky.h): while one is set the gather reads it, not the environment; with LH_SKY_SUN every hit traces the sun's ray */
-    const lh_sky_src_t *sky = (env && a->sky_set) ? &a->sky : NULL;
-    sun_stage sunst = {sky ? sky->sky.sun_dir : NULL, &a->s_tile, NULL};
-    sun_stage *sun = (sky && (sky->sky.flags & LH_SKY_SUN)) ? &sunst : NULL;
+    gather_desc d;
+    gather_describe(a, p, LH_GATHER_TILE, &d);
+    lh_gather_scratch *b = d.b;
     void *r_org, *r_dir, *r_prim, *r_t, *r_u, *r_v;          /* camera rays and their closest-hit records */
-    if (dirt || env) {          /* one block of its own (org | dir | t | u | v | prim): lh_render_scratch keeps showing the last AO tile */
-        lh_buf *rays = dirt ? &a->d_rays : &a->e_rays;
-        if (ensure_buf(rays, S * 76)) return -1;
-        double *base = (double *)rays->p;
-        r_org = base; r_dir = base + 3 * S; r_t = base + 6 * S; r_u = base + 7 * S; r_v = base + 8 * S; r_prim = base + 9 * S;
-    } else {
+    if (p.kind == LH_GATHER_AO) {          /* the AO tile's own buffers: what lh_render_scratch shows */
         if (ensure_buf(&a->r_org, S * 24) || ensure_buf(&a->r_dir, S * 24) || ensure_buf(&a->r_prim, S * 4) ||
             ensure_buf(&a->r_t, S * 8) || ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8)) return -1;
         r_org = a->r_org.p; r_dir = a->r_dir.p; r_prim = a->r_prim.p; r_t = a->r_t.p; r_u = a->r_u.p; r_v = a->r_v.p;
+    } else {          /* one block of the kind's own (org | dir | t | u | v | prim): lh_render_scratch keeps showing the last AO tile */
+        if (ensure_buf(&b->rays, S * 76)) return -1;
+        double *base = (double *)b->rays.p;
+        r_org = base; r_dir = base + 3 * S; r_t = base + 6 * S; r_u = base + 7 * S; r_v = base + 8 * S; r_prim = base + 9 * S;
     }
     if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
-    const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->tile_dirt_t};
     /* material textures (lh_tex.h): with at least one set, the resolve multiplies; with none, tex is NULL and the launch is the one it always was */
-    /* (the sun-and-sky gather has no texture fetch: ambientocclusion.c:369-375) */
-    if (a->ntex && !sky && lh_tex_sync(a) != 0) return -1;
-    lh_tex_args_t tex_store;
-    const lh_tex_args_t *tex = sky ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &tex_store);
+    if (a->ntex && !d.sky && lh_tex_sync(a) != 0) return -1;
+    d.tex = d.sky ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &d.tex_store);
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
@@ -323,31 +365,12 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     if (lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, r_org, r_dir, r_prim, r_t, r_u, r_v, NULL, cnt},
                   LH_VARIANT_DEFAULT, s, false, opt) != 0) return -1;
     if (tm) { HIPCHK(hipEventRecord(tm->ev[2], s)); opt.diag_clock += 3 * nwaves; }
-    unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of k_ao_resolve's 64 counters */
-    auto resolve = [&](bool from_counts) -> int {
-        if (sky) {
-            if (lh_render_launch_sky_resolve(w, h, band_rows, ps, ps, g.ntheta, g.nphi, seed, env->scale, sky, sunst.occ, (const uint32_t *)b->slot.p,
-                                             (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                                             from_counts ? NULL : (const double *)b->adir.p, (const uint8_t *)b->occ.p, (float *)d_rgb, a->d_total, s) != 0)
-                return fail("sun-and-sky resolve kernel launch failed");
-            return 0;
-        }
-        if (env) {          /* from_counts: the stage ended fused -- no direction in memory, the resolve makes them again */
-            if (lh_render_launch_env_resolve(w, h, band_rows, ps, ps, g.ntheta, g.nphi, seed, env->scale, &esrc, (const uint32_t *)b->slot.p,
-                                             (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                                             from_counts ? NULL : (const double *)b->adir.p, (const uint8_t *)b->occ.p, (float *)d_rgb, a->d_total, tex, s) != 0)
-                return fail("environment-gather resolve kernel launch failed");
-            return 0;
-        }
-        if (dirt) {
-            if (lh_render_launch_dirt_resolve(w, h, band_rows, ps, ps, g.N, dirt->near_clip, dirt->far_clip, (const uint32_t *)b->slot.p,
-                                              (const double *)dstage.ts->t.p, (float *)d_rgb, a->d_total, tex, s) != 0)
-                return fail("dirt resolve kernel launch failed");
-            return 0;
-        }
-        if (lh_render_launch_resolve(w, h, band_rows, ps, ps, g.N, (const uint32_t *)b->slot.p, (const uint8_t *)b->occ.p,
-                                     from_counts ? (const unsigned int *)b->occcount.p : NULL, (float *)d_rgb, a->d_total, tex, s) != 0)
-            return fail("resolve kernel launch failed");
+    unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of the resolve's 64 counters */
+    /* 6. the samples' values into the pixels */
+    const lh_resolve_tile_t to = {w, h, band_rows, ps, ps, (const uint32_t *)b->slot.p, (float *)d_rgb, d.tex};
+    static const char *const resolve_name[LH_GATHER_KINDS] = {"resolve", "dirt resolve", "environment-gather resolve"};
+    auto resolve = [&](const lh_gather_left_t &left) -> int {
+        if (lh_render_launch_tile_resolve(&to, &left, s) != 0) return fail("%s kernel launch failed", d.sky ? "sun-and-sky resolve" : resolve_name[p.kind]);
         return 0;
     };
     ao_totals tot = {};
@@ -358,28 +381,25 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
                                      (const double *)r_dir, (const uint32_t *)r_prim, (const double *)r_t,
                                      (const double *)r_u, (const double *)r_v, (uint32_t *)b->blocks.p,
                                      (uint32_t *)b->slot.p, (double *)b->hitrec.p, (unsigned long long *)b->key.p,
-                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, eps, s) != 0)
+                                     x0, w, nbands, band_rows, d_band_y0, y0, ps * ps, cam->width, a->d_total, p.eps, s) != 0)
             return fail("compaction kernels failed: %s", hipGetErrorString(hipGetLastError()));
         HIPCHK(hipMemcpyAsync(d_nhit, a->d_total, sizeof(*d_nhit), hipMemcpyDeviceToDevice, s));
-        /* 4-6.  Late: the persistent kernel's 32-bit ray index covers the worst case; the grouped order ("ao_group") needs the count on the host */
-        const bool fused = a->ao_fused && !d_uniforms;
-        /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; it has no grouped order) */
-        /* (so does the environment gather, a byte per ray) */
-        const bool late = fused && S * (size_t)g.N < ((size_t)1 << 31) && (dirt ? S * (size_t)g.N <= LH_DIRT_LATE_MAX : env ? S * (size_t)g.N <= LH_ENV_LATE_MAX : !a->dev.ao_group) && !getenv("LH_AO_SYNC") &&
-                          !(sun && S > LH_SUN_LATE_MAX);
-        if (ao_stage(a, "", b, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot, sun) != 0) return -1;
+        /* 4-6.  Fused and late or not: lh_gather.h; LH_AO_SYNC is read per call */
+        const lh_gather_plan_t plan = lh_gather_plan(p.kind, LH_GATHER_TILE, S, (size_t)g.N, a->ao_fused, d_uniforms != NULL, (int)a->dev.ao_group,
+                                                     d.sun_dir != NULL, getenv("LH_AO_SYNC") != NULL);
+        if (ao_stage(a, d, S, g, seed, d_uniforms, d_nhit, a->d_total, cnt, opt, tm, plan, resolve, s, &tot) != 0) return -1;
     } else {          /* an empty scene: every sample is a miss */
         HIPCHK(hipMemsetAsync(b->slot.p, 0xFF, S * 4, s));
         HIPCHK(hipMemsetAsync(d_nhit, 0, sizeof(*d_nhit), s));
         if (tm) { HIPCHK(hipEventRecord(tm->ev[3], s)); HIPCHK(hipEventRecord(tm->ev[4], s)); }
         HIPCHK(hipMemsetAsync(a->d_total, 0, sizeof(unsigned long long) * 64, s));
-        if (resolve(false) != 0) return -1;
+        if (resolve(gather_left(d, g, seed, false, NULL, a->d_total)) != 0) return -1;
         if (tm) HIPCHK(hipEventRecord(tm->ev[5], s));
         HIPCHK(hipStreamSynchronize(s));
     }
     const size_t nao = (size_t)tot.nhit * g.N;
     if (tm && stage_report(*tm, a->r_diag.p, nwaves, S, tot.nhit, nao) != 0) return -1;
-    if (!dirt && !env) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
+    if (p.kind == LH_GATHER_AO) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
     if (cnt) {
         lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
@@ -395,44 +415,41 @@ static int ao_region(lh_accel_t *a, const lh_camera_t *cam, int x0, int w, int n
     return 0;
 }
 
+/* lh_render_ao_tile, lh_render_dirt_tile (ri_transport_dirtmap per camera sample, dirtmap.c:234-292: a miss gives 0, a hit its dirt value) and
+ * lh_render_env_tile (the environment-lit gather per camera sample -- gather_sunsky's loop with ri_texture_ibl_fetch as its sky,
+ * ambientocclusion.c:206-324,407-411: a miss gives 0, a hit the three floats of lh_env_value), each times the texture of the hit's mesh where it has
+ * one: the refusals, in their order -- the parameters before the accelerator -- and the region of one rectangle */
+static int gather_tile(const char *what, int kind, const void *params, lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps,
+                       int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb, lh_tile_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);
+    gather_params p;
+    if (gather_check(what, kind, params, &p) != 0) return -1;
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (!cam || !d_rgb) return fail("%s: NULL argument", what);
+    if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("%s: bad tile/sample counts", what);
+    return ao_region(a, p, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
+}
+
 extern "C" int lh_render_ao_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps,
                                  int gather_nsamples, uint64_t seed, const void *d_uniforms, void *d_rgb,
                                  lh_tile_stats_t *stats, void *stream)
 {
-    lh_guard guard(a);
-    if (!a || !a->committed) return fail("lh_render_ao_tile: accel not committed");
-    if (!cam || !d_rgb) return fail("lh_render_ao_tile: NULL argument");
-    if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_ao_tile: bad tile/sample counts");
-    return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
+    return gather_tile("lh_render_ao_tile", LH_GATHER_AO, NULL, a, cam, x0, y0, w, h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
 }
 
-/* ri_transport_dirtmap per camera sample (dirtmap.c:234-292): a miss gives 0, a hit its dirt value, times the texture of its mesh where it has one */
 extern "C" int lh_render_dirt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, int gather_nsamples,
                                    const lh_dirt_params_t *params, uint64_t seed, const void *d_uniforms, void *d_rgb,
                                    lh_tile_stats_t *stats, void *stream)
 {
-    lh_guard guard(a);
-    lh_dirt_params_t p;
-    if (dirt_params("lh_render_dirt_tile", params, &p) != 0) return -1;
-    if (!a || !a->committed) return fail("lh_render_dirt_tile: accel not committed");
-    if (!cam || !d_rgb) return fail("lh_render_dirt_tile: NULL argument");
-    if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_dirt_tile: bad tile/sample counts");
-    return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream, &p);
+    return gather_tile("lh_render_dirt_tile", LH_GATHER_DIRT, params, a, cam, x0, y0, w, h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
 }
 
-/* the environment-lit gather per camera sample (gather_sunsky's loop with ri_texture_ibl_fetch as its sky, ambientocclusion.c:206-324,407-411): a
- * miss gives 0, a hit the three floats of lh_env_value, times the texture of its mesh where it has one */
 extern "C" int lh_render_env_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, int gather_nsamples,
                                   const lh_env_params_t *params, uint64_t seed, const void *d_uniforms, void *d_rgb,
                                   lh_tile_stats_t *stats, void *stream)
 {
-    lh_guard guard(a);
-    lh_env_params_t p;
-    if (env_params("lh_render_env_tile", params, &p) != 0) return -1;
-    if (!a || !a->committed) return fail("lh_render_env_tile: accel not committed");
-    if (!cam || !d_rgb) return fail("lh_render_env_tile: NULL argument");
-    if (w <= 0 || h <= 0 || ps < 1 || gather_nsamples < 1) return fail("lh_render_env_tile: bad tile/sample counts");
-    return ao_region(a, cam, x0, w, 1, h, NULL, y0, (uint64_t)w * h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream, NULL, &p);
+    return gather_tile("lh_render_env_tile", LH_GATHER_ENV, params, a, cam, x0, y0, w, h, ps, gather_nsamples, seed, d_uniforms, d_rgb, stats, stream);
 }
 
 /* nbands full-width bands of band_rows lines (band b = frame lines band_y0[b] ...; a band that runs past the frame is
@@ -456,7 +473,9 @@ extern "C" int lh_render_ao_bands(lh_accel_t *a, const lh_camera_t *cam, int nba
     if (ensure_buf(&a->r_bands, sizeof(int) * (size_t)nbands)) return -1;
     HIPCHK(hipMemcpyAsync(a->r_bands.p, band_y0, sizeof(int) * (size_t)nbands, hipMemcpyHostToDevice, (hipStream_t)stream));
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));          /* band_y0 is the caller's memory */
-    return ao_region(a, cam, 0, cam->width, nbands, band_rows, (const int *)a->r_bands.p, 0, valid, ps, gather_nsamples, seed, NULL,
+    gather_params p;
+    if (gather_check("lh_render_ao_bands", LH_GATHER_AO, NULL, &p) != 0) return -1;
+    return ao_region(a, p, cam, 0, cam->width, nbands, band_rows, (const int *)a->r_bands.p, 0, valid, ps, gather_nsamples, seed, NULL,
                      d_rgb, stats, stream);
 }
 
@@ -507,12 +526,12 @@ static int ao_batch_args(const char *what, const lh_accel_t *a, size_t n_rays, b
     return 1;
 }
 
-/* lh_accel_ao_device, and with dirt (checked parameters) lh_accel_dirt_device: the same list, compaction and stage; the dirt call has the dirt
- * origin, scratch of its own and its resolve (d_occluded_count / d_radiance are then near_hits / value) */
-static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
-                           const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+/* lh_accel_ao_device / _dirt_device / _env_device behind their refusals: the same list, compaction and stage; the kind (p) has its origin, scratch of
+ * its own and its resolve (d_occluded_count / d_radiance are near_hits / value for DIRT, the count and float[3 n_rays] for ENV) */
+static int ao_batch_device(const char *what, lh_accel_t *a, const gather_params &p, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim,
+                           const void *d_t, const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
                            const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
-                           void *d_occluded_count, void *d_radiance, void *stream, const lh_dirt_params_t *dirt, const lh_env_params_t *env = NULL)
+                           void *d_occluded_count, void *d_radiance, void *stream)
 {
     const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, gather_nsamples, d_key, d_uniforms,
                                  d_index, n_index, d_count, d_occluded_count, d_radiance);
@@ -523,38 +542,17 @@ static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const
     HIPCHK(hipSetDevice(a->device));
     hipStream_t s = (hipStream_t)stream;
     const ao_grid g = ao_sample_grid(gather_nsamples);
-    const uint32_t *idx = (const uint32_t *)d_index, *cntp = (const uint32_t *)d_count;
-    /* env (checked parameters): lh_accel_env_device -- the environment gather's origin, scratch and resolve (d_radiance is then float[3 n_rays]) */
-    lh_ao_scratch *b = dirt ? &a->batch_dirt : env ? &a->batch_env : &a->batch_ao;
-    lh_buf *totals = dirt ? &a->d_tot : env ? &a->e_tot : &a->b_tot;
-    const lh_env_src_t esrc = env_source(a);
-    /* the sun-and-sky light, as in ao_region */
-    const lh_sky_src_t *sky = (env && a->sky_set) ? &a->sky : NULL;
-    sun_stage sunst = {sky ? sky->sky.sun_dir : NULL, &a->s_batch, NULL};
-    sun_stage *sun = (sky && (sky->sky.flags & LH_SKY_SUN)) ? &sunst : NULL;
-    if (ensure_buf(totals, sizeof(unsigned long long) * 65)) return -1;
-    unsigned long long *d_nhit = (unsigned long long *)totals->p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 occlusion counters */
-    const dirt_stage dstage = {dirt ? *dirt : lh_dirt_params_t{0.0, 0.0, 0.0}, &a->batch_dirt_t};
-    /* 6. per-ray occlusion (dirt: bounded hits and value), scattered to the rays' own slots; slot NULL: an empty scene */
-    auto resolve_with = [&](const uint32_t *slot, bool from_counts) -> int {
-        if (sky)
-            return lh_render_launch_sky_batch_resolve(L, n_rays, idx, cntp, g.ntheta, g.nphi, seed, env->scale, sky, sunst.occ, slot, (const double *)b->hitrec.p,
-                                                      (const unsigned long long *)b->key.p, from_counts ? NULL : (const double *)b->adir.p,
-                                                      (const uint8_t *)b->occ.p, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
-        if (env)          /* from_counts: the stage ended fused -- no direction in memory, the resolve makes them again */
-            return lh_render_launch_env_batch_resolve(L, n_rays, idx, cntp, g.ntheta, g.nphi, seed, env->scale, &esrc, slot, (const double *)b->hitrec.p,
-                                                      (const unsigned long long *)b->key.p, from_counts ? NULL : (const double *)b->adir.p,
-                                                      (const uint8_t *)b->occ.p, (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
-        if (dirt)
-            return lh_render_launch_dirt_batch_resolve(L, n_rays, idx, cntp, g.N, dirt->near_clip, dirt->far_clip, slot, (const double *)dstage.ts->t.p,
-                                                       (uint32_t *)d_occluded_count, (float *)d_radiance, d_nocc, s);
-        return lh_render_launch_batch_resolve(L, n_rays, idx, cntp, g.N, slot, slot ? (const uint8_t *)b->occ.p : NULL,
-                                              from_counts ? (const unsigned int *)b->occcount.p : NULL, (uint32_t *)d_occluded_count,
-                                              (float *)d_radiance, d_nocc, s);
-    };
+    gather_desc d;
+    gather_describe(a, p, LH_GATHER_BATCH, &d);
+    lh_gather_scratch *b = d.b;
+    if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)b->totals.p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 counters */
+    /* 6. per-ray count and value, scattered to the rays' own slots; slot_of_entry NULL: an empty scene */
+    lh_resolve_list_t to = {L, n_rays, (const uint32_t *)d_index, (const uint32_t *)d_count, NULL, (uint32_t *)d_occluded_count, (float *)d_radiance};
     if (a->hs->bvh.ntris == 0) {          /* an empty scene: every traced ray is a miss, no record array is read */
         HIPCHK(hipMemsetAsync(d_nocc, 0, sizeof(unsigned long long) * 64, s));
-        if (resolve_with(NULL, false) != 0)
+        const lh_gather_left_t left = gather_left(d, g, seed, false, NULL, d_nocc);
+        if (lh_render_launch_list_resolve(&to, &left, s) != 0)
             return fail("%s: resolve kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
@@ -562,29 +560,40 @@ static int ao_batch_device(const char *what, lh_accel_t *a, size_t n_rays, const
     const unsigned nb = (unsigned)((L + 255) / 256);
     if (ensure_buf(&b->blocks, (size_t)nb * 4) || ensure_buf(&b->slot, L * 4) || ensure_buf(&b->hitrec, L * 96) ||
         ensure_buf(&b->key, L * 8)) return -1;                     /* worst case: every entry hits */
-    unsigned long long *cnt = a->stat_on ? a->d_counters : NULL;          /* lh_accel_trace_statistics: as the tile pipelines' AO stage */
+    to.slot_of_entry = (const uint32_t *)b->slot.p;
+    unsigned long long *cnt = a->stat_on ? a->d_counters : NULL;          /* lh_accel_trace_statistics: as the tile pipelines' stage */
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
     /* 3. compaction: hits in list order, the count stays on the device */
-    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, L, n_rays, idx, cntp, (const double *)d_org, (const double *)d_dir,
+    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, L, n_rays, to.index, to.count, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
                                        (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)b->slot.p,
-                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, dirt ? dirt->eps : env ? env->eps : 1.0e-6, s) != 0)
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, NULL, p.eps, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    /* 4-6.  A fused stage always leaves the count on the device; the grouped order (set_param "ao_group") needs it on the host: materialised */
-    const bool fused = a->ao_fused && !d_uniforms && L * (size_t)g.N < ((size_t)1 << 31) && (dirt || env || !a->dev.ao_group);
-    /* (the dirt stage keeps a double per gather ray: the worst case is worth sizing for only while it is small; beyond that the count is read first) */
-    const bool late = fused && (!dirt || L * (size_t)g.N <= LH_DIRT_LATE_MAX) && (!env || L * (size_t)g.N <= LH_ENV_LATE_MAX) && !(sun && L > LH_SUN_LATE_MAX);
-    auto resolve = [&](bool from_counts) -> int {
-        if (resolve_with((const uint32_t *)b->slot.p, from_counts) != 0) return fail("%s: resolve kernel launch failed", what);
+    /* 4-6.  Fused and late or not: lh_gather.h (a batch is not asked to read the count first) */
+    const lh_gather_plan_t plan = lh_gather_plan(p.kind, LH_GATHER_BATCH, L, (size_t)g.N, a->ao_fused, d_uniforms != NULL, (int)a->dev.ao_group,
+                                                 d.sun_dir != NULL, 0);
+    auto resolve = [&](const lh_gather_left_t &left) -> int {
+        if (lh_render_launch_list_resolve(&to, &left, s) != 0) return fail("%s: resolve kernel launch failed", what);
         return 0;
     };
     ao_totals tot;
-    if (ao_stage(a, dirt ? "lh_accel_dirt_device: " : env ? "lh_accel_env_device: " : "lh_accel_ao_device: ", b, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt,
-                 lh_launch_opt(), NULL, fused, late, resolve, dirt ? &dstage : NULL, env != NULL, s, &tot, sun) != 0)
-        return -1;
+    if (ao_stage(a, d, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, plan, resolve, s, &tot) != 0) return -1;
     if (cnt) lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nocc, true);
-    if (cnt && (dirt || env)) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
+    if (cnt && p.kind != LH_GATHER_AO) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
     return 0;
+}
+
+/* the three device entry points: the parameters' refusal first, as ever */
+static int gather_batch_device(const char *what, int kind, const void *params, lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir,
+                               const void *d_prim, const void *d_t, const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+                               const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count, void *d_count_out, void *d_value_out,
+                               void *stream)
+{
+    lh_guard guard(a);
+    gather_params p;
+    if (gather_check(what, kind, params, &p) != 0) return -1;
+    return ao_batch_device(what, a, p, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
+                           d_count, d_count_out, d_value_out, stream);
 }
 
 extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
@@ -592,9 +601,8 @@ extern "C" int lh_accel_ao_device(lh_accel_t *a, size_t n_rays, const void *d_or
                                   const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
                                   void *d_occluded_count, void *d_radiance, void *stream)
 {
-    lh_guard guard(a);
-    return ao_batch_device("lh_accel_ao_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
-                           d_count, d_occluded_count, d_radiance, stream, NULL);
+    return gather_batch_device("lh_accel_ao_device", LH_GATHER_AO, NULL, a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key,
+                               d_uniforms, d_index, n_index, d_count, d_occluded_count, d_radiance, stream);
 }
 
 extern "C" int lh_accel_dirt_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
@@ -602,11 +610,8 @@ extern "C" int lh_accel_dirt_device(lh_accel_t *a, size_t n_rays, const void *d_
                                     const void *d_key, const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
                                     void *d_near_hits, void *d_value, void *stream)
 {
-    lh_guard guard(a);
-    lh_dirt_params_t p;
-    if (dirt_params("lh_accel_dirt_device", params, &p) != 0) return -1;
-    return ao_batch_device("lh_accel_dirt_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
-                           d_count, d_near_hits, d_value, stream, &p);
+    return gather_batch_device("lh_accel_dirt_device", LH_GATHER_DIRT, params, a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key,
+                               d_uniforms, d_index, n_index, d_count, d_near_hits, d_value, stream);
 }
 
 extern "C" int lh_accel_env_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
@@ -614,11 +619,8 @@ extern "C" int lh_accel_env_device(lh_accel_t *a, size_t n_rays, const void *d_o
                                    const void *d_key, const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
                                    void *d_occluded_count, void *d_rgb, void *stream)
 {
-    lh_guard guard(a);
-    lh_env_params_t p;
-    if (env_params("lh_accel_env_device", params, &p) != 0) return -1;
-    return ao_batch_device("lh_accel_env_device", a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_index, n_index,
-                           d_count, d_occluded_count, d_rgb, stream, NULL, &p);
+    return gather_batch_device("lh_accel_env_device", LH_GATHER_ENV, params, a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key,
+                               d_uniforms, d_index, n_index, d_count, d_occluded_count, d_rgb, stream);
 }
 
 extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
@@ -649,26 +651,30 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
         return 0;
     }
     const unsigned nb = (unsigned)((n_rays + 255) / 256);
-    if (ensure_buf(&a->b_tot, sizeof(unsigned long long) * 65) || ensure_buf(&a->batch_ao.blocks, (size_t)nb * 4) ||
-        ensure_buf(&a->batch_ao.hitrec, n_rays * 96) || ensure_buf(&a->batch_ao.key, n_rays * 8)) return -1;
-    unsigned long long *d_nhit = (unsigned long long *)a->b_tot.p;
+    lh_gather_scratch *b = &a->gather[LH_GATHER_AO][LH_GATHER_BATCH];
+    if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65) || ensure_buf(&b->blocks, (size_t)nb * 4) ||
+        ensure_buf(&b->hitrec, n_rays * 96) || ensure_buf(&b->key, n_rays * 8)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)b->totals.p;
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
-                                       (const unsigned long long *)d_key, (uint32_t *)a->batch_ao.blocks.p, (uint32_t *)d_slot_of_ray,
-                                       (double *)a->batch_ao.hitrec.p, (unsigned long long *)a->batch_ao.key.p, d_nhit, (uint32_t *)d_nslots, 1.0e-6, s) != 0)
+                                       (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)d_slot_of_ray,
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, 1.0e-6, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, g.ntheta, g.nphi, seed, (const double *)a->batch_ao.hitrec.p, (const double *)d_uniforms,
-                                         (const unsigned long long *)a->batch_ao.key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
+    if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
+                                         (const unsigned long long *)b->key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
         return fail("%s: AO ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
     return 0;
 }
 
-/* lh_accel_ao_host, and with dirt (checked parameters) lh_accel_dirt_host, with env lh_accel_env_host (radiance: 3 floats per ray) */
-static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
-                         const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
-                         const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance, const lh_dirt_params_t *dirt,
-                         const lh_env_params_t *env = NULL)
+/* lh_accel_ao_host / _dirt_host / _env_host (radiance: 3 floats per ray for ENV): the parameters' refusal first, then host arrays up, the device call
+ * on the accelerator's stream, the outputs down */
+static int gather_batch_host(const char *what, int kind, const void *params, lh_accel_t *a, size_t n_rays, const double *org, const double *dir,
+                             const uint32_t *prim, const double *t, const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
+                             const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance)
 {
+    lh_guard guard(a);
+    gather_params p;
+    if (gather_check(what, kind, params, &p) != 0) return -1;
     const int go = ao_batch_args(what, a, n_rays, org && dir && prim && t && u && v, gather_nsamples, NULL, NULL, NULL, 0, NULL, NULL, NULL);
     if (go <= 0) return go;
     if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
@@ -677,7 +683,7 @@ static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const d
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t nrad = env ? 3 * n : n;          /* floats of `radiance` */
+    const size_t nrad = kind == LH_GATHER_ENV ? 3 * n : n;          /* floats of `radiance` */
     if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 2 * sizeof(uint32_t) * n + sizeof(float) * nrad)) return -1;
     double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
     double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
@@ -691,8 +697,8 @@ static int ao_batch_host(const char *what, lh_accel_t *a, size_t n_rays, const d
     HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
     if (key) HIPCHK(hipMemcpyAsync(d_key, key, b_d, hipMemcpyHostToDevice, s));
     if (need) HIPCHK(hipMemcpyAsync(d_uni, uniforms, need * sizeof(double), hipMemcpyHostToDevice, s));
-    if (ao_batch_device(dirt ? "lh_accel_dirt_device" : env ? "lh_accel_env_device" : "lh_accel_ao_device", a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
-                        key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s, dirt, env) != 0) return -1;
+    if (ao_batch_device(gather_device_name[kind], a, p, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
+                        key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s) != 0) return -1;
     if (occluded_count) HIPCHK(hipMemcpyAsync(occluded_count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * nrad, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -703,28 +709,24 @@ extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org,
                                 const double *u, const double *v, int gather_nsamples, uint64_t seed, const uint64_t *key,
                                 const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *radiance)
 {
-    lh_guard guard(a);
-    return ao_batch_host("lh_accel_ao_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, occluded_count, radiance, NULL);
+    return gather_batch_host("lh_accel_ao_host", LH_GATHER_AO, NULL, a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms,
+                             occluded_count, radiance);
 }
 
 extern "C" int lh_accel_dirt_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
                                   const double *u, const double *v, int gather_nsamples, const lh_dirt_params_t *params, uint64_t seed,
                                   const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *near_hits, float *value)
 {
-    lh_guard guard(a);
-    lh_dirt_params_t p;
-    if (dirt_params("lh_accel_dirt_host", params, &p) != 0) return -1;
-    return ao_batch_host("lh_accel_dirt_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, near_hits, value, &p);
+    return gather_batch_host("lh_accel_dirt_host", LH_GATHER_DIRT, params, a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms,
+                             near_hits, value);
 }
 
 extern "C" int lh_accel_env_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
                                  const double *u, const double *v, int gather_nsamples, const lh_env_params_t *params, uint64_t seed,
                                  const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *occluded_count, float *rgb)
 {
-    lh_guard guard(a);
-    lh_env_params_t p;
-    if (env_params("lh_accel_env_host", params, &p) != 0) return -1;
-    return ao_batch_host("lh_accel_env_host", a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms, occluded_count, rgb, NULL, &p);
+    return gather_batch_host("lh_accel_env_host", LH_GATHER_ENV, params, a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms,
+                             occluded_count, rgb);
 }
 
 /* the fetch alone: ri_texture_ibl_fetch (env_fetch, lh_pt.h) of the accelerator's environment for n directions.  Asynchronous, nothing read back */
@@ -739,7 +741,7 @@ extern "C" int lh_accel_environment_device(lh_accel_t *a, size_t n, const void *
     if (((uintptr_t)d_rgb & 3u) != 0) return fail("%s: the output holds floats: the pointer is not 4-byte aligned", what);
     if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
     HIPCHK(hipSetDevice(a->device));
-    const lh_env_src_t esrc = env_source(a);
+    const lh_env_src_t esrc = lh_env_source(a);
     if (lh_render_launch_env_fetch(n, &esrc, (const double *)d_dir, (float *)d_rgb, stream) != 0)
         return fail("%s: kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
     return 0;
@@ -819,8 +821,8 @@ extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t 
 {
     lh_guard guard(a);
     if (!a || !a->committed || !d_ptr || !count) return fail("lh_render_scratch: bad argument");
-    lh_buf *b[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->tile_ao.slot, &a->tile_ao.hitrec,
-                   &a->tile_ao.aorg, &a->tile_ao.adir, &a->tile_ao.occ};
+    lh_gather_scratch *t = &a->gather[LH_GATHER_AO][LH_GATHER_TILE];          /* the last AO tile's */
+    lh_buf *b[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &t->slot, &t->hitrec, &t->aorg, &t->adir, &t->occ};
     if (which < 0 || which > 10) return fail("lh_render_scratch: unknown buffer %d", which);
     *d_ptr = b[which]->p;
     *count = which <= 6 ? a->r_nsamples : (which == 7 ? a->r_nslots : a->r_nao);
