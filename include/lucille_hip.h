@@ -651,6 +651,72 @@ int  lh_accel_set_sky(lh_accel_t *accel, const lh_sky_t *sky);
 int  lh_accel_sky_device(lh_accel_t *accel, size_t n, const void *d_dir_xyz, void *d_rgb_out, void *stream);
 int  lh_accel_sky_host(lh_accel_t *accel, size_t n, const double *dir_xyz, float *rgb_out);
 
+/* ---- direct light: shadow rays from a batch of hits to a short list of lights (contribution_from_sunlight,
+ *      src/transport/ambientocclusion.c:153-199, for the directional and point lights of ri_light_t, src/render/light.h:26-32; the rule:
+ *      lucille_amd/csrc/lh_lights.h) ----
+ * For every hit and every light of the list one plain any-hit ray from the gather stages' origin O = P + eps Ns (P and Ns as
+ * lh_accel_state_build_device gives them, Ns taken as it is): which lights the hit sees, and what they add.  Everything in fp64 in the
+ * order written, nothing contracted:
+ *   ray of light l:  directional (no LH_LIGHT_POINT): dir = v, the direction TOWARDS the light, unbounded.  Point: dir[k] = v[k] - O[k],
+ *     not normalised, bound tmax = 1.0: the ray is open iff the bounded any-hit contract of lh_accel_intersect_device_tmax answers 0
+ *     for (O, dir, 1.0) -- strict: an occluder exactly at the light does not shadow it.  No self-primitive skip (the semantics of
+ *     lh_accel_intersect_device): a light behind the surface is shadowed by the hit's own triangle, as the sky's sun.
+ *   weight:  w = 1; with LH_LIGHT_COSINE, nn = (Ns0 Ns0 + Ns1 Ns1) + Ns2 Ns2, dd the same sum of dir, nd = (Ns0 d0 + Ns1 d1) + Ns2 d2,
+ *     c = nd / sqrt(nn * dd), w = c > 0 ? c : 0 (a NaN gives 0); with LH_LIGHT_INVSQ, w = w / dd afterwards.
+ *   a ray whose direction is the zero vector or has a non-finite component is dark and is never traced; nor is a ray with !(w > 0).
+ *   bit l = (the ray is not dark && w > 0 && it is open);  value: sum_k = 0, for l = 0 .. L - 1 in list order: if (bit l)
+ *     sum_k = sum_k + w * rgb_l[k]; value_k = (float)sum_k.  The order is part of the contract.  With no flags this is the reference's
+ *     Lo[k] += light->col[k] per light.
+ *   parameters: eps finite and >= 0 (NULL: LH_LIGHTS_DEFAULTS); 1 <= nlights <= LH_LIGHTS_MAX; every v and rgb finite; a directional v
+ *     not the zero vector; flags within the three bits, reserved 0; LH_LIGHT_INVSQ only with LH_LIGHT_POINT.  Anything else is refused
+ *     ("bad lights") and nothing is enqueued.  A shadow ray with |dir.y| <= 1e-14 is outside the contract (reference UB, bvh.c:483-487).
+ *   LH_LIGHTS_MAX is 31, not 32: a traced miss is marked LH_AO_NO_HIT in d_visible, and a hit that saw 32 lights would carry the same
+ *     word.  `lights` is HOST memory and is copied: the table travels by value in the arguments of every kernel that reads it (1 736
+ *     bytes), so there is no device block whose release would have to wait for a launch.
+ * lh_accel_lights_device: as lh_accel_env_device, word for word -- list, count and id semantics, hit slots in list order, untouched
+ *   slots of rays that are not traced (4 bytes of d_visible, 12 of d_rgb), an id listed twice, synchronous on `stream`, the empty scene,
+ *   scratch of its own, its refusals; no keys, seed or uniforms: the stage draws nothing.  d_visible[id] (uint32, may be NULL) = the bit
+ *   mask, LH_AO_NO_HIT for a traced miss; d_rgb[3 id ..] (3 floats, may be NULL) = value, three 0.0f for a miss; not both NULL.  Fused
+ *   when "ao_fused" is on, the scene is not empty and list entries x nlights < 2^31: the persistent any-hit walk makes ray (slot, l) in
+ *   its refill from the hit record and the light table, walks it under its bound and stores its answer as one byte; else, and as the
+ *   second try of a fused launch whose queue overflowed, one kernel writes rays and bounds and one bounded any-hit launch answers
+ *   them.  Both give the same bytes.  With lh_accel_trace_statistics on, `rays` advances by hits x nlights (work items, traced or not)
+ *   and counters[4] by the items whose bit is clear.
+ * lh_accel_lights_host: the same for HOST arrays (copies up, the device call on the accelerator's stream, copies down).
+ * lh_accel_light_rays_device: the shadow rays alone, shaped like lh_accel_ao_rays_device: d_slot_of_ray, d_nslots, and ray (slot, l) at
+ *   element slot * nlights + l of d_org_out / d_dir_out (3 doubles each) and of d_tmax_out (doubles): +inf for a directional light, 1.0
+ *   for a point light, 0.0 for a ray that is not traced (dark, or !(w > 0)) -- its bit is clear whatever a launch answers for it.
+ *   lh_accel_intersect_device_tmax in any-hit mode on these arrays gives exactly the stage's bytes.  Asynchronous, nothing read back;
+ *   capacity_rays >= n_rays * nlights or it is refused.
+ * lh_render_lights_tile: per camera sample -- a miss gives 0, a hit its value_k (the float); sub-samples are widened, added per channel
+ *   in sample order, scaled, converted, clamped and written as lh_render_env_tile does; a frame does not depend on its tiling.
+ *   stats->ao_rays = hits x nlights, stats->ao_occluded = the items whose bit is clear.
+ * Not built: the texture multiply (the reference's sun branch fetches none, ambientocclusion.c:369-375), area lights, the sky's own sun
+ *   ray through this stage (lh_accel_set_sky keeps its launch), bands and the multi-device forms. */
+#define LH_LIGHT_POINT  1u   /* v is a position; without it v is the direction TOWARDS the light, as the reference's light->direction */
+#define LH_LIGHT_COSINE 2u   /* weight by the cosine between Ns and the ray */
+#define LH_LIGHT_INVSQ  4u   /* point lights only: divide by the squared distance */
+#define LH_LIGHTS_MAX  31
+typedef struct lh_light { double v[3]; double rgb[3]; uint32_t flags, reserved; } lh_light_t;   /* 56 bytes */
+typedef struct lh_lights_params { double eps; } lh_lights_params_t;
+#define LH_LIGHTS_DEFAULTS { 1.0e-5 }                                /* ambientocclusion.c:166 */
+int  lh_accel_lights_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                            const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                            const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                            const void *d_index, size_t n_index, const void *d_count,
+                            void *d_visible, void *d_rgb, void *stream);
+int  lh_accel_lights_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,
+                          const double *t, const double *u, const double *v, const lh_light_t *lights, int nlights,
+                          const lh_lights_params_t *params, uint32_t *visible, float *rgb);
+int  lh_accel_light_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                                const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                                const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                                void *d_slot_of_ray, void *d_nslots, void *d_org_out, void *d_dir_out, void *d_tmax_out,
+                                size_t capacity_rays, void *stream);
+int  lh_render_lights_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
+                           const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                           void *d_rgb, lh_tile_stats_t *stats, void *stream);
+
 /* ---- the refraction chain: the reference's Whitted transport (trace_whitted, src/transport/whitted.c:32-151; ri_refract and
  *      ri_reflect, src/render/reflection.c:26-128) ----
  * No random number anywhere: a hit sends ONE ray on -- the refraction of the incoming direction at the interpolated normal, or its

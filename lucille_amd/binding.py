@@ -156,6 +156,36 @@ class Sky(C.Structure):
         return s
 
 
+LIGHT_POINT, LIGHT_COSINE, LIGHT_INVSQ = 1, 2, 4      # LH_LIGHT_*: v is a position (else the direction towards the light); weight by the cosine; divide by the squared distance
+LIGHTS_MAX = 31                                        # LH_LIGHTS_MAX: a mask of 32 set bits would be AO_NO_HIT, the mark of a traced miss
+
+
+class Light(C.Structure):
+    """lh_light_t (56 bytes): a directional light (v: the direction TOWARDS it) or, with LIGHT_POINT, a point light (v: its position), its
+    colour and flags (LIGHT_COSINE, LIGHT_INVSQ -- the latter for point lights only); reserved must stay 0"""
+    _fields_ = [("v", C.c_double * 3), ("rgb", C.c_double * 3), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, v=(0.0, 1.0, 0.0), rgb=(1.0, 1.0, 1.0), flags=0, reserved=0):
+        super().__init__((C.c_double * 3)(*[float(x) for x in v]), (C.c_double * 3)(*[float(x) for x in rgb]), int(flags), int(reserved))
+
+
+class LightsParams(C.Structure):
+    """lh_lights_params_t: the origin offset of the shadow rays along Ns (default: LH_LIGHTS_DEFAULTS, contribution_from_sunlight's 1e-5)"""
+    _fields_ = [("eps", C.c_double)]
+
+    def __init__(self, eps=1.0e-5):
+        super().__init__(float(eps))
+
+
+def _light_array(what, lights):
+    """a sequence of Light -> (a ctypes array of them, or None for an empty one; its length): the C call refuses what the rule does not accept"""
+    lights = list(lights)
+    for x in lights:
+        if not isinstance(x, Light):
+            raise ValueError("%s: lights must be a sequence of Light" % what)
+    return ((Light * len(lights))(*lights) if lights else None), len(lights)
+
+
 class WhittedParams(C.Structure):
     """lh_whitted_params_t: origin offset, relative refractive index and depth limit of the refraction chain (defaults:
     LH_WHITTED_DEFAULTS, the constants of whitted.c); reserved must stay 0"""
@@ -186,6 +216,7 @@ ABI_SYMBOLS = [
     "lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile",
     "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
     "lh_sky_from_site", "lh_accel_set_sky", "lh_accel_sky_device", "lh_accel_sky_host",
+    "lh_accel_lights_device", "lh_accel_lights_host", "lh_accel_light_rays_device", "lh_render_lights_tile",
     "lh_accel_whitted_rays_device", "lh_accel_whitted_device", "lh_accel_whitted_host", "lh_render_whitted_tile",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
@@ -296,6 +327,12 @@ def lib():
         L.lh_accel_set_sky.argtypes = [vp, C.POINTER(Sky)]
         L.lh_accel_sky_device.argtypes = [vp, sz, vp, vp, vp]
         L.lh_accel_sky_host.argtypes = [vp, sz, vp, vp]
+    if hasattr(L, "lh_accel_lights_device"):             # an older library under LH_LIBRARY (A/B runs in tools/) has no light stage
+        lp, lpp = C.POINTER(Light), C.POINTER(LightsParams)
+        L.lh_accel_lights_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, sz, vp, vp, vp, vp]
+        L.lh_accel_lights_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, vp]
+        L.lh_accel_light_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, vp, vp, vp, vp, sz, vp]
+        L.lh_render_lights_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, lp, i32, lpp, vp, C.POINTER(TileStats), vp]
     if hasattr(L, "lh_accel_whitted_device"):            # an older library under LH_LIBRARY (A/B runs in tools/) has no refraction chain
         wpp = C.POINTER(WhittedParams)
         L.lh_accel_whitted_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, wpp, vp, sz, vp, vp, vp, vp]
@@ -1255,6 +1292,121 @@ class HipAccel:
         if not isinstance(params, EnvParams):
             raise ValueError("env_host: params must be an EnvParams")
         return self._batch_stage_host("env_host", params, org, dr, records, gather_nsamples, seed, key, uniforms)
+
+    # ---- direct light: shadow rays from a batch of hits to a list of lights (lh_lights.h) ----
+    @staticmethod
+    def _lights_params(what, params):
+        if params is None:
+            params = LightsParams()
+        if not isinstance(params, LightsParams):
+            raise ValueError("%s: params must be a LightsParams" % what)
+        return params
+
+    def lights_device(self, org, dr, records, lights, params=None, index=None, count=None, out=None, stream=None):
+        """lh_accel_lights_device: which of `lights` (a sequence of 1 .. LIGHTS_MAX Light) every hit of a batch of rays and their closest-hit
+        records sees, and what they add; org / dr / records / index / count as env_device, params: a LightsParams (None: eps 1e-5).  Returns
+        (visible, rgb): an int32 tensor [n] whose bits are uint32 -- bit l: the hit sees light l; AO_NO_HIT for a miss -- and the float32
+        tensor [n, 3] of the sum of the visible lights' weighted colours in list order (zeros for a miss).  out: such a pair to fill (either
+        member may be None, not both); with out=None the slots of rays that are not listed are UNSPECIFIED.  Synchronous."""
+        import torch
+        what = "lights_device"
+        params = self._lights_params(what, params)
+        arr, nl = _light_array(what, lights)
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, None, None)
+        dev = org.device
+        ip, ni, cp = _list_args(index, count, what)
+        if index is None and count is not None:
+            ni = n
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
+            raise ValueError("%s: out must be a (visible, rgb) pair, at least one of them a tensor" % what)
+        ov, orgb = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if ov is not None and not (ov.is_cuda and ov.dtype in words and ov.dim() == 1 and ov.shape[0] == n and ov.is_contiguous()):
+            raise ValueError("%s: the mask output must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if orgb is not None and not (orgb.is_cuda and orgb.dtype == torch.float32 and orgb.dim() == 2 and tuple(orgb.shape) == (n, 3) and orgb.is_contiguous()):
+            raise ValueError("%s: the colour output must be a contiguous float32 device tensor [n, 3]" % what)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_lights_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl, C.byref(params),
+                                             ip, ni, cp, _dptr(ov), _dptr(orgb), C.c_void_p(stream)), "lh_accel_lights_device")
+        return out
+
+    def lights_host(self, org, dr, records, lights, params=None):
+        """lh_accel_lights_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v)) -> (visible uint32 [n], rgb float32 [n, 3])"""
+        what = "lights_host"
+        params = self._lights_params(what, params)
+        arr, nl = _light_array(what, lights)
+        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
+        if d.shape[0] != n or len(records) != 4:
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
+        p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
+        u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
+        if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
+        vis = np.empty(n, np.uint32); rgb = np.empty((n, 3), np.float32)
+        _check(self.L.lh_accel_lights_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                           arr, nl, C.byref(params), vis.ctypes.data, rgb.ctypes.data), "lh_accel_lights_host")
+        return vis, rgb
+
+    def light_rays_device(self, org, dr, records, lights, params=None, out=None, stream=None):
+        """lh_accel_light_rays_device: only the shadow rays of the batch's hits, for a caller who traces them itself.  Returns (slot_of_ray
+        int32 [n] -- the hit slot of every ray, AO_NO_HIT (as uint32 bits) for a miss; nslots -- one-element int32 tensor, the number of hits;
+        org, dir -- float64 [n * L, 3]; tmax -- float64 [n * L]: ray (slot, l) at row slot * L + l, the first nslots * L rows written; tmax is
+        +inf for a directional light, 1 for a point light, 0 for a ray that is not traced: its bit is clear whatever a launch answers).
+        intersect_device(..., mode=MODE_ANY, tmax=tmax) on them gives the stage's bytes.  Everything stays on the device and nothing is read
+        back; out: such a 5-tuple to fill."""
+        import torch
+        what = "light_rays_device"
+        params = self._lights_params(what, params)
+        arr, nl = _light_array(what, lights)
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, None, None)
+        dev = org.device
+        if out is None:
+            m = n * max(nl, 1)
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+                   torch.empty((m, 3), dtype=torch.float64, device=dev), torch.empty((m, 3), dtype=torch.float64, device=dev),
+                   torch.empty(m, dtype=torch.float64, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 5:
+            raise ValueError("%s: out must be (slot_of_ray, nslots, org, dir, tmax)" % what)
+        so, ns, ro, rd, rt = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
+            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
+            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
+        for name, x in (("org", ro), ("dir", rd)):
+            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
+        if not (rt.is_cuda and rt.dtype == torch.float64 and rt.dim() == 1 and rt.is_contiguous()):
+            raise ValueError("%s: tmax must be a contiguous float64 device tensor [m]" % what)
+        cap = min(int(ro.shape[0]), int(rd.shape[0]), int(rt.shape[0]))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_light_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl, C.byref(params),
+                                                 _dptr(so), _dptr(ns), _dptr(ro), _dptr(rd), _dptr(rt), cap, C.c_void_p(stream)),
+               "lh_accel_light_rays_device")
+        return out
+
+    def render_lights_tile(self, cam, x0, y0, w, h, pixel_samples, lights, params=None, out=None, stream=None):
+        """lh_render_lights_tile: direct light per camera sample -- a miss gives 0, a hit the sum of the lights it sees -> (rgb float32
+        [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x lights, ao_occluded = the items whose bit is clear)"""
+        import torch
+        what = "render_lights_tile"
+        params = self._lights_params(what, params)
+        arr, nl = _light_array(what, lights)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = TileStats()
+        _check(self.L.lh_render_lights_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, arr, nl, C.byref(params), _dptr(out), C.byref(st),
+                                            C.c_void_p(stream)), "lh_render_lights_tile")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def environment_device(self, dirs, out=None, stream=None):
         """lh_accel_environment_device: the accelerator's environment (set_environment; constant white if none was set) seen in each of

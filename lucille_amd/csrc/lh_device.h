@@ -189,13 +189,15 @@ typedef struct lh_gather_src {
     const unsigned long long *d_slot_key;
     const unsigned long long *d_nslots;
     uint32_t    budget_big;
+    const struct lh_light *lights;      /* LH_GATHER_LIGHT: the HOST table of ntheta lights (nphi is 1), copied into the kernels' arguments; else NULL */
 } lh_gather_src_t;
 
 /* what a fused stage leaves, by its kind (LH_GATHER_*, lh_gather.h), in the one array `out`:
  *   AO    unsigned int per hit slot, the slot's occluded rays (zeroed by the launcher);
  *   DIRT  double per gather ray, the t of ray (slot, r)'s closest hit under the one bound far_clip (lh_tmax.h) at element slot * N + r, 1e38 for a miss;
  *   ENV   uint8_t per gather ray (lh_env.h): the AO stage's any-hit walk, the answer of ray (slot, r), 0 or 1, at element slot * N + r, written exactly
- *         once (no memset, no atomic).
+ *         once (no memset, no atomic);
+ *   LIGHT uint8_t per shadow ray (lh_lights.h): the bounded any-hit answer of item (slot, l) at element slot * L + l, 0 for an item that is not traced.
  * Rays the persistent kernel does not finish go through the stream's fix-up queue: out of budget or stack rows to the cooperative walk, fragile hits (for
  * DIRT the mark of a hit near the bound among them) to the reference's own walk; whoever finishes a ray stores the same word.  A queue overflow leaves
  * DIRT and ENV words unwritten and AO counts short: the caller redoes the stage materialised */

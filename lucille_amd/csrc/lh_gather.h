@@ -15,13 +15,15 @@
 enum { LH_GATHER_AO = 0,          /* ambient occlusion: a count of occluded rays per hit slot (fused), a byte per ray (materialised) */
        LH_GATHER_DIRT = 1,        /* the dirtmap transport (lh_dirt.h): a double per ray, the t of its bounded closest hit */
        LH_GATHER_ENV = 2,         /* the environment-lit gather (lh_env.h): a byte per ray */
-       LH_GATHER_KINDS = 3 };
+       LH_GATHER_LIGHT = 3,       /* direct light (lh_lights.h): N = the lights of the list, gather ray (slot, l) the shadow ray to light l; a byte per ray */
+       LH_GATHER_KINDS = 4 };
 /* who runs the stage: the tile pipeline (samples of a region) or a caller's batch of hit records (list entries) */
 enum { LH_GATHER_TILE = 0, LH_GATHER_BATCH = 1 };
 
 #define LH_SUN_LATE_MAX ((size_t)1 << 30)        /* slots up to which the sun's launch can take its count from the device (a list holds 2^30 entries) */
 #define LH_ENV_LATE_MAX ((size_t)1 << 28)        /* gather rays (256 MiB of bytes) up to which a stage is sized for its worst case, the count left on the device */
 #define LH_DIRT_CHUNK ((size_t)1 << 30)          /* rays of one bounded launch at most (a list holds 2^30 entries) */
+#define LH_LIGHT_LATE_MAX ((size_t)1 << 28)      /* shadow rays (256 MiB of bytes) up to which a stage is sized for its worst case: the environment gather's cap, for the same byte per ray */
 #define LH_DIRT_LATE_MAX ((size_t)1 << 27)       /* gather rays (1 GiB of t) up to which a stage is sized for its worst case, the count left on the device */
 
 typedef struct lh_gather_plan { int fused, late; } lh_gather_plan_t;
@@ -32,8 +34,14 @@ typedef struct lh_gather_plan { int fused, late; } lh_gather_plan_t;
 static inline lh_gather_plan_t lh_gather_plan(int kind, int where, size_t entries, size_t N, int ao_fused, int uniforms, int ao_group, int sun, int sync)
 {
     const unsigned long long rays = (unsigned long long)entries * (unsigned long long)N;          /* the worst case */
-    const int grouped = kind == LH_GATHER_AO && ao_group != 0;          /* the dirt and environment kernels have no grouped order */
+    const int grouped = kind == LH_GATHER_AO && ao_group != 0;          /* the dirt, environment and light kernels have no grouped order */
     lh_gather_plan_t p;
+    if (kind == LH_GATHER_LIGHT) {
+        /* no uniforms, no grouped order, no sun; a tile decides on the worst case as a batch does: entries x L < 2^31 (the 32-bit item index) */
+        p.fused = ao_fused && rays < (1ull << 31);
+        p.late = p.fused && rays <= LH_LIGHT_LATE_MAX && !(where == LH_GATHER_TILE && sync);
+        return p;
+    }
     p.fused = ao_fused && !uniforms;          /* replayed uniforms are read from memory by the ray kernel: materialised */
     if (where == LH_GATHER_BATCH) {
         /* a batch decides here, on the worst case; a tile that is not late reads the count and decides in the stage, on the hits it has */

@@ -7,7 +7,7 @@
  *                   one way a batch of rays (lh_batch_t) reaches the kernels' launcher (lh_kernels.hip lh_launch_trace)
  *   lh_plan.h       the geometry of a persistent launch (rows, checked pushes, the top of the tree in LDS, workgroups per CU, the cooperative
  *                   walk beside it, the cursor chunk): plain C, read by the launchers, by size_grid and by tests/cpu_model/lh_plan_check.c
- *   lh_gather.h     the kinds of gather stage (AO, dirt, environment) and its plan -- fused, late -- for a tile or a batch: plain C, read by
+ *   lh_gather.h     the kinds of gather stage (AO, dirt, environment, direct light) and its plan -- fused, late -- for a tile or a batch: plain C, read by
  *                   lh_tile.hip and by tests/cpu_model/lh_gather_check.c
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
  *   lh_whitted.hip  the refraction chain (the reference's Whitted transport): its bounce kernel, its wavefront loop, its entry points
@@ -361,6 +361,7 @@ typedef struct lh_gather_left {
     const double *hitrec; const unsigned long long *key; const double *adir;
     double near_clip, far_clip, scale;
     const lh_env_src_t *env; const lh_sky_src_t *sky; const uint8_t *sun_occ;
+    const lh_light_t *lights;          /* LH_GATHER_LIGHT: the HOST table of ntheta lights (nphi is 1); occ holds the byte of every item, hitrec the records */
     unsigned long long *total;
 } lh_gather_left_t;
 /* a region of w x h pixels (h = nbands * band_rows lines), xs * ys samples each, with the hit slot of every sample; tex or NULL: no mesh has a texture */
@@ -375,6 +376,8 @@ extern "C" int lh_render_launch_sky_fetch(size_t n, const lh_sky_src_t *sky, con
 /* one ray per hit slot from the slot's hit record along sun_dir (d_nslots or NULL: the slot count on the device, nslots its upper bound) */
 extern "C" int lh_render_launch_sun_rays(size_t nslots, const unsigned long long *d_nslots, const double *d_hitrec, const double sun_dir[3],
                                          double *d_org, double *d_dir, void *stream);
+extern "C" int lh_render_launch_light_rays(size_t nslots, const unsigned long long *d_nslots, const lh_light_t *lights, int n, const double *d_hitrec,
+                                           double *d_org, double *d_dir, double *d_tmax, void *stream);
 extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
                                             const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
                                             const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,

@@ -56,6 +56,7 @@
 #include "lh_reftrace.h"
 #include "lh_tmax.h"
 #include "lh_ao.h"
+#include "lh_lights.h"
 
 namespace {
 
@@ -503,6 +504,8 @@ __global__ __launch_bounds__(LH_BLOCK) void k_trace_direct(
  * record; an occluded ray adds one to its slot's counter, nothing per ray goes through HBM (round 1 wrote and
  * re-read 49 bytes per AO ray: 22 GB per 4096^2 x 64 frame).  A fragile hit (lh_reftrace.h; rare) is queued for
  * the reference's own walk.
+ * SRC 3 (any-hit, bounded): the work items are the shadow rays of a batch of hits to a list of lights (lh_lights.h) -- item i = (hit slot i / L, light
+ * i % L) -- made in the refill from the hit record and the light table; an item that is not traced stores its byte there and never starts a walk.
  * WALK 3: traverse_spec4 (the default); 8: the same with the stack check (trees whose worst case the LDS rows do not
  * cover); 7: traverse_spec8 (8-wide nodes). */
 struct AoSrc {
@@ -515,13 +518,32 @@ struct AoSrc {
     /* the dirt stage (closest hit, TMAX; lh_dirt.h): the bound of every ray of the launch, and where the t of ray (slot, r)'s bounded record goes --
      * element slot * N + r, 1e38 for a miss; no kernel of the AO stage looks at either */
     double far_clip; double *dirt_t;
+    /* the light stage (SRC 3; lh_lights.h): the table of ntheta lights (nphi is 1: item i = slot * ntheta + l, the plain order), in the arguments of the
+     * kernels of that stage; no other kernel looks at it */
+    const lh_light_t *lights;
 };
+/* ray sources whose rays are made from hit records (AoSrc): their count may live on the device, their answers go where the stage's kind says */
+#define LH_SRC_GATHER(SRC) ((SRC) == 1 || (SRC) == 3)
 
 /* the bound of ray `id` of a bounded launch: its element of sc.tmax -- or, for the rays a kernel makes itself (SRC 1: the dirt stage), the launch's one bound */
 template <int SRC>
 __device__ __forceinline__ double lane_tmax(const lh_dev_scene_t &sc, const AoSrc &ao, size_t id)
 {
+    if (SRC == 3) return (ao.lights[(uint32_t)id % (uint32_t)ao.ntheta].flags & LH_LIGHT_POINT) ? 1.0 : LH_LIGHT_TMAX_INF;      /* of a ray that is traced (lh_lights.h) */
     return SRC == 1 ? ao.far_clip : ray_tmax(sc, id);
+}
+
+/* work item i of the light stage: the shadow ray of hit slot i / L to light i % L from the slot's hit record (its origin, doubles 0-2, and Ns, doubles 9-11);
+ * returns the bound it is traced under, 0.0: it is not traced (lh_light_item) */
+__device__ __forceinline__ double light_src_item(const AoSrc &ao, uint32_t i, double &ox, double &oy, double &oz, double &dx, double &dy, double &dz)
+{
+    const uint32_t nl = (uint32_t)ao.ntheta, slot = i / nl, l = i - slot * nl;
+    const double *h = ao.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
+    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+    double d[3], w;
+    const double tmax = lh_light_item(O, Ns, ao.lights + l, d, &w);
+    ox = O[0]; oy = O[1]; oz = O[2]; dx = d[0]; dy = d[1]; dz = d[2];
+    return tmax;
 }
 
 /* the dirt stage's one store per gather ray: the t of its bounded record (no atomic; the ray and the rest of the record stay in registers) */
@@ -563,6 +585,8 @@ __device__ __forceinline__ void src_ray(const lh_dev_scene_t &sc, uint32_t i, co
         const unsigned long long key = ao.slot_key[slot];
         lh_ao_ray_builtin(ao.hitrec + LH_HITREC_DOUBLES * (size_t)slot, key, ao.seed, ao.ntheta, ao.nphi, (int)r, ox, oy, oz, dx, dy, dz);
         selfp = lh_slot_selfprim(key);            /* LH_SLOT_NOSELF matches no primitive id (ids < 2^29) */
+    } else if (SRC == 3) {
+        (void)light_src_item(ao, i, ox, oy, oz, dx, dy, dz);          /* (a queued ray: it was traced; no self primitive) */
     } else {
         double o[3], d[3];
         pt_camera_ray((const PtCamSrc *)sc.cam_src, i, o, d);
@@ -608,7 +632,7 @@ __device__ __forceinline__ void trace_persist_lane(
 #ifdef LH_DIAG_CLOCK      /* wave start / exit clocks (LH_STAGE_TIMING); off in the product: two SGPRs live across the whole kernel */
     if (sc.diag_clock && (tid & 63) == 0) sc.diag_clock[(size_t)blockIdx.x * (LH_BLOCK / 64) + (tid >> 6)] = wall_clock64();
 #endif
-    const uint32_t budget = (SRC == 1 && ao.budget_big && n >= (1u << 27)) ? ao.budget_big : sc.ray_budget;
+    const uint32_t budget = (LH_SRC_GATHER(SRC) && ao.budget_big && n >= (1u << 27)) ? ao.budget_big : sc.ray_budget;
     bool exhausted = false;          /* wave-uniform: every partition's cursor ran past its end */
     uint32_t wbase = 0, wend = 0;    /* wave-uniform: this wave's reserved ray range */
     uint32_t part, drained = 0;      /* wave-uniform: the partition this wave draws from, bit mask of the partitions known to be handed out */
@@ -644,7 +668,7 @@ __device__ __forceinline__ void trace_persist_lane(
                  * full queue, flags the slot -- with the flag WORD alone, so that no tentative t, u, v can land among the final record's stores */
                 if (!queued) { if (ANYHIT) occ[my] = (uint8_t)LH_OCC_RETRACE; else rec_prim<true>(sc, prim, my) = LH_PRIM_RETRACE; }
             } else
-            if (SRC != 1) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT, SRC == 0 && IO>(sc, my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
+            if (!LH_SRC_GATHER(SRC)) { if (__builtin_expect(!queued, 1)) write_out<ANYHIT, SRC == 0 && IO>(sc, my, L, best, prim, t, u, v, occ, sc.ref_nodes != NULL); }
             else if (!ANYHIT) { if (!L.over && !fragile) dirt_store(ao, my, best.t); }          /* the dirt stage: a queued ray's word is the consumer's to store */
             else if (ENV) { if (!L.over && !fragile) occ[my] = (uint8_t)((L.certain || best.prim != LH_MISS_PRIM) ? 1 : 0); }      /* the environment gather: so is its byte */
             else if (!L.over && !fragile && (L.certain || best.prim != LH_MISS_PRIM)) { uint32_t sl, rr; ao_item(ao, my, sl, rr); atomicAdd(&ao.occ_count[sl], 1u); }
@@ -683,7 +707,7 @@ __device__ __forceinline__ void trace_persist_lane(
                 if (__builtin_expect(wbase == wend, 0)) {
                     const uint32_t per = (n + LH_NPART - 1) / LH_NPART;
                     uint32_t chunk = sc.ray_chunk;
-                    if ((SRC != 1 && sc.n_dev) || (SRC == 1 && ao.nslots_dev)) {                   /* the host sized the chunk for its upper bound of n */
+                    if ((!LH_SRC_GATHER(SRC) && sc.n_dev) || (LH_SRC_GATHER(SRC) && ao.nslots_dev)) {                   /* the host sized the chunk for its upper bound of n */
                         const uint32_t c = n / (gridDim.x * (LH_BLOCK / 64) * 4u);
                         chunk = c < 64u ? 64u : (c < chunk ? c : chunk);
                     }
@@ -738,10 +762,17 @@ __device__ __forceinline__ void trace_persist_lane(
             if (sc.index) newray = sc.index[newray];
             if (newray >= sc.idx_nrays) newray = kNoRay;
         }
+        /* the light stage: an item that is not traced (dark, or without weight: lh_lights.h) leaves its byte here -- no occluder was found -- and its lane
+         * takes an item again at the next regroup, as the lane of a skipped id does; a walk never starts with a zero direction */
+        double ltmax = 0.0;
+        if (SRC == 3 && newray != kNoRay) {
+            ltmax = light_src_item(ao, newray, ox, oy, oz, dx, dy, dz);
+            if (!(ltmax > 0.0)) { occ[newray] = (uint8_t)0; newray = kNoRay; }
+        }
         if (newray != kNoRay) {
             const uint32_t i = newray;
             my = i;
-            src_ray<SRC, IO>(sc, i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
+            if (SRC != 3) src_ray<SRC, IO>(sc, i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
             lane_init(L, sc, ox, oy, oz, dx, dy, dz);
             best.t = LH_T_INF; best.u = 0.0; best.v = 0.0; best.prim = LH_MISS_PRIM; best.frag = 0u;
             stk[0][tid] = kDone;
@@ -749,15 +780,15 @@ __device__ __forceinline__ void trace_persist_lane(
              * dumps whenever it is finite; camera and AO rays (unit vectors) only where a zero-area triangle of |e1|_1 |e2|_1 > 1 stayed in the
              * tree: the bit is set from the DOUBLE cap (lh_danger.h lh_dcap_srcs): the float cap of such a scene may be 1.0f.  Every other scene skips the test whole */
             if (TMAX) {
-                const bool refw = (sc.cap_srcs & (1u << SRC)) != 0u && ray_needs_ref_walk(sc, L, dx, dy, dz);      /* asked under the unbounded 1e38f */
-                tmax_start(L, best, lane_tmax<SRC>(sc, ao, i));
+                const bool refw = (sc.cap_srcs & (1u << (SRC == 3 ? 0 : SRC))) != 0u && ray_needs_ref_walk(sc, L, dx, dy, dz);      /* asked under the unbounded 1e38f; a shadow ray is no unit vector: the arrays' bit */
+                tmax_start(L, best, SRC == 3 ? ltmax : lane_tmax<SRC>(sc, ao, i));
                 if (__builtin_expect(refw, 0)) LH_FORCE_REF_WALK(L, best);
             } else
             if ((sc.cap_srcs & (1u << SRC)) != 0u && __builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
             it0 = it;
         }
         const unsigned long long work = __ballot((L.cur != kDone) | (pend != 0));
-        if (work == 0ull && (!IDX || exhausted)) break;          /* (an indexed launch: a refill whose entries were all skipped leaves a wave without work, not without rays) */
+        if (work == 0ull && (!(IDX || SRC == 3) || exhausted)) break;          /* (an indexed launch, the light stage: a refill whose entries were all skipped leaves a wave without work, not without rays) */
         /* ---- walk until too few lanes remain active ---------------------- */
         const int thresh = exhausted ? 1 : min_active;
         if (WALK == 3)
@@ -857,6 +888,23 @@ __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_env(
     if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
     copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<true, COUNT, WALK, 1, false, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
+}
+
+/* the persistent kernel of the fused light stage (lh_launch_trace_gather, LH_GATHER_LIGHT; lh_lights.h): the shadow rays of ao.nslots hits to the ao.ntheta lights of
+ * `tab`, made in the refill (SRC 3), walked to ANY hit under the item's own bound (TMAX: a point light's ray ends at the light); the retire stores the answer as a byte
+ * at occ[slot * L + l], as the environment gather's does.  The first any-hit + bounded + byte-store instantiation: a kernel of its own once more.  The table travels
+ * by value in the kernel's arguments: nothing to allocate, nothing whose release would have to wait for the launch */
+template <bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_light(
+    lh_dev_scene_t sc, uint32_t n, uint8_t *__restrict__ occ, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao0, const FixQ fq,
+    const lh_light_tab_t tab)
+{
+    extern __shared__ int lh_stack_lds[];
+    AoSrc ao = ao0;
+    ao.lights = tab.l;
+    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
+    copy_tree_top(sc, lh_stack_lds);
+    trace_persist_lane<true, COUNT, WALK, 3, false, false, true, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
 /* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
@@ -1171,6 +1219,19 @@ __global__ __launch_bounds__(64) void k_coop_walk_env(lh_dev_scene_t sc, const d
     coop_walk_body<true, 1, false, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
 }
 
+/* the cooperative walk of the fused light stage (ray source 3, any hit, the item's own bound): the body of a bounded any-hit dump's -- every lane of a group starts
+ * with the ray's bound, the reference walk's record goes through the final accept, the group's answer goes to occ[i] as a byte -- with its rays made again from
+ * the item index, the hit records and the light table, which travels by value here too */
+__global__ __launch_bounds__(64) void k_coop_walk_light(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                                        uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                        double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao0, const FixQ fq,
+                                                        unsigned long long *counters, const uint32_t owner_groups, const lh_light_tab_t tab)
+{
+    AoSrc ao = ao0;
+    ao.lights = tab.l;
+    coop_walk_body<true, 3, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+}
+
 /* ------------------------------------------------------------------------ */
 /* one scan over the outputs of a ray dump: what is still flagged            */
 /* ------------------------------------------------------------------------ */
@@ -1458,21 +1519,34 @@ int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, const lh_plan_t &
     return b.counters ? launch(no, yes) : launch(no, no);
 }
 
+/* the kernel of a cooperative walk by its template arguments (the light stage's takes one argument more: its table) */
+template <bool ANYHIT, int SRC, bool TMAX, bool ENV>
+auto coop_kernel()
+{
+    constexpr bool DIRT = TMAX && SRC == 1 && !ANYHIT;          /* the fused dirt stage */
+    if constexpr (SRC == 3) return k_coop_walk_light;          /* the fused light stage */
+    else {
+        auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
+        if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
+        if (DIRT) kern = k_coop_walk_dirt;
+        if (ENV) kern = k_coop_walk_env;          /* the fused environment gather */
+        return kern;
+    }
+}
+
 /* the cooperative walk over the fix-up queue of the persistent launch just enqueued on s.  It runs on the queue's second
  * stream, CONCURRENTLY with that launch (a few small workgroups per CU next to the persistent ones: its low efficiency --
  * one ray per 16 lanes, restarted from the root -- is hidden behind the bulk of the frame), submitted AFTER it: if the two
  * streams share a hardware queue it simply runs afterwards. */
-template <bool ANYHIT, int SRC, bool TMAX = false, bool ENV = false>
-int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p, const lh_launch_ctx_t &c, hipStream_t s)
+/* extra: what a stage's kernel takes behind the common arguments (the light stage's table) */
+template <bool ANYHIT, int SRC, bool TMAX = false, bool ENV = false, class... Extra>
+int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p, const lh_launch_ctx_t &c, hipStream_t s,
+                const Extra &... extra)
 {
     /* the pass next to the producer (owner_groups 0) and the sweep behind it */
 #define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL(kern, dim3(GRID), dim3(64), p.coop_lds_bytes, STREAM, scl, LH_BATCH_ARRAYS(b), \
-                                                                      ao, fq, b.counters, OWNER_GROUPS)
-    constexpr bool DIRT = TMAX && SRC == 1 && !ANYHIT;          /* the fused dirt stage */
-    auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
-    if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
-    if (DIRT) kern = k_coop_walk_dirt;
-    if (ENV) kern = k_coop_walk_env;          /* the fused environment gather */
+                                                                      ao, fq, b.counters, OWNER_GROUPS, extra...)
+    auto *kern = coop_kernel<ANYHIT, SRC, TMAX, ENV>();
     lh_dev_scene_t scl = sc;
     scl.stack_rows = p.coop_rows;
     if (allow_lds((const void *)kern, p.coop_lds_bytes) != 0) return -1;
@@ -1502,9 +1576,11 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
  * the environment gather take the plain order (slot, sample) and LH_TILE_CHUNK */
 struct FusedStage {
     bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; uint8_t *env_occ;
+    bool light;          /* the light stage: env_occ is its byte per item */
     FusedStage(const lh_dev_scene_t *sc, const lh_fused_out_t &o)
         : dirt(o.kind == LH_GATHER_DIRT), chunk(LH_TILE_CHUNK), occ_count(NULL), group(0), far_clip(dirt ? o.far_clip : 0.0),
-          dirt_t(dirt ? (double *)o.out : NULL), env_occ(o.kind == LH_GATHER_ENV ? (uint8_t *)o.out : NULL)
+          dirt_t(dirt ? (double *)o.out : NULL), env_occ((o.kind == LH_GATHER_ENV || o.kind == LH_GATHER_LIGHT) ? (uint8_t *)o.out : NULL),
+          light(o.kind == LH_GATHER_LIGHT)
     {
         static uint32_t ao_chunk = 0;
         if (o.kind != LH_GATHER_AO) return;
@@ -1526,7 +1602,7 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
     lh_dev_scene_t scl = *sc;
     scl.ray_chunk = st.chunk;
     const lh_plan_t p = lh_plan_launch(&scl, n, st.dirt ? LH_PLAN_DIRT : LH_PLAN_AO, LH_VARIANT_SPEC, c.grid_blocks, 1);
-    const AoSrc ao = {g.d_hitrec, g.d_slot_key, st.occ_count, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, st.group, g.d_nslots, g.budget_big, st.far_clip, st.dirt_t};
+    const AoSrc ao = {g.d_hitrec, g.d_slot_key, st.occ_count, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, st.group, g.d_nslots, g.budget_big, st.far_clip, st.dirt_t, NULL};
     FixQ fq;
     if (apply_plan(scl, p) != 0) return -1;
     if (st.occ_count && hipMemsetAsync(st.occ_count, 0, sizeof(unsigned int) * g.nslots, s) != hipSuccess) return -1;      /* with the cursors' memset, before the stream's first kernel */
@@ -1550,6 +1626,18 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
         if (hipGetLastError() != hipSuccess) return -1;
         return launch_coop<false, 1, true>(scl, none, ao, fq, p, c, s);
     }
+    if (st.light) {          /* the light stage (lh_lights.h): ntheta lights of the host table g.lights, by value into both kernels */
+        if (!g.lights || g.ntheta < 1 || g.ntheta > LH_LIGHTS_MAX || g.nphi != 1) return -1;
+        lh_light_tab_t tab;
+        memset(&tab, 0, sizeof(tab));
+        memcpy(tab.l, g.lights, sizeof(lh_light_t) * (size_t)g.ntheta);
+        using light_t = decltype(&k_trace_persist_light<true, LH_WALK_Q4>);
+        const light_t lkern[2][2] = {{k_trace_persist_light<true, LH_WALK_Q4_CHECKED>, k_trace_persist_light<false, LH_WALK_Q4_CHECKED>},
+                                     {k_trace_persist_light<true, LH_WALK_Q4>, k_trace_persist_light<false, LH_WALK_Q4>}};
+        LH_LAUNCH_PERSIST(lkern[w][k], scl, (uint32_t)n, st.env_occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
+        if (hipGetLastError() != hipSuccess) return -1;
+        return launch_coop<true, 3, true>(scl, none, ao, fq, p, c, s, tab);
+    }
     /* the environment gather (named last: the kernels above keep their order) */
     using env_t = decltype(&k_trace_persist_env<true, LH_WALK_Q4>);
     const env_t ekern[2][2] = {{k_trace_persist_env<true, LH_WALK_Q4_CHECKED>, k_trace_persist_env<false, LH_WALK_Q4_CHECKED>},
@@ -1565,7 +1653,7 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
 extern "C" int lh_launch_trace_gather(const lh_dev_scene_t *sc, const lh_gather_src_t *src, const lh_fused_out_t *out, unsigned long long *d_counters,
                                       const lh_launch_ctx_t *ctx)
 {
-    if ((unsigned)out->kind >= LH_GATHER_KINDS || (out->kind == LH_GATHER_ENV && !out->out)) return -1;
+    if ((unsigned)out->kind >= LH_GATHER_KINDS || ((out->kind == LH_GATHER_ENV || out->kind == LH_GATHER_LIGHT) && !out->out)) return -1;
     return launch_fused(sc, *src, FusedStage(sc, *out), d_counters, *ctx);
 }
 

@@ -35,6 +35,7 @@
 #include "lh_dirt.h"
 #include "lh_env.h"
 #include "lh_sky.h"
+#include "lh_lights.h"
 #include "lh_tex.h"
 
 namespace {
@@ -767,6 +768,94 @@ __global__ void k_sun_rays(size_t nslots, const unsigned long long *__restrict__
     dir[3 * i] = sx; dir[3 * i + 1] = sy; dir[3 * i + 2] = sz;
 }
 
+/* ---- direct light (lh_lights.h): the resolves read one byte per shadow ray -- its bounded any-hit answer, at element slot * L + l -- make the
+ * item's ray and weight again from the hit record and the light table and add the visible lights in list order; whoever traced the rays wrote that
+ * array.  The table is a kernel argument by value: the resolves index it uniformly (scalar loads), the ray maker per thread ------------------------ */
+
+/* the shadow rays and bounds of a materialised stage, and of lh_accel_light_rays_device: one thread per item, ray (slot, l) at element slot * L + l;
+ * the bound of an item that is not traced is 0.0 (a dead bound: the bounded launch answers 0 for it, the byte a fused stage stores).  nslots_dev (or
+ * NULL): the slot count where it lives on the device, nslots then its upper bound */
+__global__ void k_light_rays(size_t nslots, const unsigned long long *__restrict__ nslots_dev, int L, const double *__restrict__ hitrec,
+                             double *__restrict__ org, double *__restrict__ dir, double *__restrict__ tmax, const lh_light_tab_t tab)
+{
+    LH_NC
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (nslots_dev && (size_t)*nslots_dev < nslots) nslots = (size_t)*nslots_dev;
+    if (id >= nslots * (size_t)L) return;
+    const size_t slot = id / (size_t)L; const int l = (int)(id - slot * (size_t)L);
+    const double *h = hitrec + LH_HITREC_DOUBLES * slot;
+    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+    double d[3], w;
+    const double tm = lh_light_item(O, Ns, tab.l + l, d, &w);
+    org[3 * id] = O[0]; org[3 * id + 1] = O[1]; org[3 * id + 2] = O[2];
+    dir[3 * id] = d[0]; dir[3 * id + 1] = d[1]; dir[3 * id + 2] = d[2];
+    tmax[id] = tm;
+}
+
+/* what the two resolves share: the list's length, the hit records, the bytes */
+struct LightGather { int L; const double *hitrec; const uint8_t *occ; };
+
+/* the mask and value of a hit slot, and how many of its L items have their bit clear */
+__device__ __forceinline__ uint32_t light_slot(const LightGather &g, const lh_light_tab_t &tab, uint32_t slot, float val[3], unsigned int &dark)
+{
+    LH_NC
+    const double *h = g.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
+    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+    const uint32_t mask = lh_lights_value(O, Ns, tab.l, g.L, g.occ + (size_t)slot * (size_t)g.L, val);
+    dark = (unsigned int)(g.L - __popc(mask));
+    return mask;
+}
+
+/* k_ao_resolve for the light tile, a thread per pixel: a miss gives 0, a hit the three floats of lh_lights_value; sub-samples are widened, added per
+ * channel in sample order and written as env_resolve does.  No texture multiply (the reference's sun branch fetches none) */
+__global__ __launch_bounds__(256) void k_light_resolve(int w, int h, int band_rows, int xs, int ys, const LightGather g, const uint32_t *__restrict__ slot_of_sample,
+                                                       float *__restrict__ rgb, unsigned long long *__restrict__ dark_total, const lh_light_tab_t tab)
+{
+    LH_NC
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool inside = pix < (size_t)w * h;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    unsigned int n = 0;
+    const int S = inside ? xs * ys : 0;
+    for (int s = 0; s < S; s++) {
+        const uint32_t slot = slot_of_sample[pix * S + s];
+        float val[3] = {0.0f, 0.0f, 0.0f};
+        if (slot != LH_MISS_PRIM) { unsigned int c; (void)light_slot(g, tab, slot, val, c); n += c; }
+        a0 = a0 + (double)val[0]; a1 = a1 + (double)val[1]; a2 = a2 + (double)val[2];
+    }
+    if (inside) {
+        const double inv = (double)1.0 / (xs * ys);
+        float f0 = (float)(a0 * inv), f1 = (float)(a1 * inv), f2 = (float)(a2 * inv);
+        if (f0 < 0.0f) f0 = 0.0f;
+        if (f1 < 0.0f) f1 = 0.0f;
+        if (f2 < 0.0f) f2 = 0.0f;
+        float *o = pixel_out(rgb, pix, w, band_rows);
+        o[0] = f0; o[1] = f1; o[2] = f2;
+    }
+    wg_total(n, dark_total);
+}
+
+/* k_ao_batch_resolve for the light stage, a thread per list entry: visible[id] / rgb[3 id ..] (either may be NULL); a traced miss gets LH_AO_NO_HIT and
+ * three zeros.  slot_of_entry NULL: an empty scene, every traced ray is a miss */
+__global__ __launch_bounds__(256) void k_light_batch_resolve(const BatchList bl, const LightGather g, const uint32_t *__restrict__ slot_of_entry,
+                                                             uint32_t *__restrict__ visible, float *__restrict__ rgb,
+                                                             unsigned long long *__restrict__ dark_total, const lh_light_tab_t tab)
+{
+    LH_NC
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    unsigned int n = 0;
+    if (batch_entry(bl, k, id)) {
+        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
+        uint32_t mask = LH_AO_NO_HIT;
+        float val[3] = {0.0f, 0.0f, 0.0f};
+        if (slot != LH_AO_NO_HIT) mask = light_slot(g, tab, slot, val, n);
+        if (visible) visible[id] = mask;
+        if (rgb) { rgb[3 * (size_t)id] = val[0]; rgb[3 * (size_t)id + 1] = val[1]; rgb[3 * (size_t)id + 2] = val[2]; }
+    }
+    wg_total(n, dark_total);
+}
+
 
 /* ---- the whole hit epilogue for a batch of hit records --------------------------------------
  * ri_intersection_state_build (intersection_state.c:99-248), every member a shader reads: P, Ng, Ns, tangent,
@@ -1190,6 +1279,15 @@ static EnvGather env_gather(const lh_gather_left_t &g)
     return gx;
 }
 
+/* a call's n lights (HOST memory) as the kernels take them; -1: no table, or a count outside 1 .. LH_LIGHTS_MAX */
+static int light_tab(const lh_light_t *lights, int n, lh_light_tab_t *tab)
+{
+    if (!lights || n < 1 || n > LH_LIGHTS_MAX) return -1;
+    memset(tab, 0, sizeof(*tab));
+    memcpy(tab->l, lights, sizeof(lh_light_t) * (size_t)n);
+    return 0;
+}
+
 /* the resolve of a tile: what the stage left (g, by its kind and light) into the region's pixels (to).  to->tex NULL: no mesh has a texture -- the
  * kernel and the arguments of every frame before textures; the sun-and-sky gather has no texture multiply (ambientocclusion.c:369-375) */
 extern "C" int lh_render_launch_tile_resolve(const lh_resolve_tile_t *to, const lh_gather_left_t *g, void *stream)
@@ -1197,6 +1295,7 @@ extern "C" int lh_render_launch_tile_resolve(const lh_resolve_tile_t *to, const 
     const int w = to->w, h = to->h, band_rows = to->band_rows, xs = to->xs, ys = to->ys, N = g->ntheta * g->nphi;
     const size_t total = (size_t)w * h, per = g->kind == LH_GATHER_ENV ? 256 / LH_ENV_GROUP : 256, nb = (total + per - 1) / per;
     hipStream_t s = (hipStream_t)stream;
+    lh_light_tab_t tab;
     if (total == 0) return 0;
     if (nb > 0x7fffffffu) return -1;
     const dim3 grid((unsigned)nb), block(256);
@@ -1214,6 +1313,10 @@ extern "C" int lh_render_launch_tile_resolve(const lh_resolve_tile_t *to, const 
         else if (to->tex) hipLaunchKernelGGL(k_env_resolve_tex, grid, block, 0, s, w, h, band_rows, xs, ys, env_gather(*g), to->slot_of_sample, to->rgb, g->total, *to->tex);
         else hipLaunchKernelGGL(k_env_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, env_gather(*g), to->slot_of_sample, to->rgb, g->total);
         break;
+    case LH_GATHER_LIGHT:
+        if (light_tab(g->lights, N, &tab) != 0) return -1;
+        hipLaunchKernelGGL(k_light_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, LightGather{N, g->hitrec, g->occ}, to->slot_of_sample, to->rgb, g->total, tab);
+        break;
     default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1229,6 +1332,7 @@ extern "C" int lh_render_launch_list_resolve(const lh_resolve_list_t *to, const 
     const dim3 grid((unsigned)((to->n_list + per - 1) / per)), block(256);
     const int N = g->ntheta * g->nphi;
     hipStream_t s = (hipStream_t)stream;
+    lh_light_tab_t tab;
     switch (g->kind) {
     case LH_GATHER_AO:
         hipLaunchKernelGGL(k_ao_batch_resolve, grid, block, 0, s, bl, N, to->slot_of_entry, g->occ, g->occ_count, to->count_out, to->value_out, g->total);
@@ -1239,6 +1343,10 @@ extern "C" int lh_render_launch_list_resolve(const lh_resolve_list_t *to, const 
     case LH_GATHER_ENV:
         if (g->sky) hipLaunchKernelGGL(k_sky_batch_resolve, grid, block, 0, s, bl, env_gather(*g), *g->sky, g->sun_occ, to->slot_of_entry, to->count_out, to->value_out, g->total);
         else hipLaunchKernelGGL(k_env_batch_resolve, grid, block, 0, s, bl, env_gather(*g), to->slot_of_entry, to->count_out, to->value_out, g->total);
+        break;
+    case LH_GATHER_LIGHT:
+        if (light_tab(g->lights, N, &tab) != 0) return -1;
+        hipLaunchKernelGGL(k_light_batch_resolve, grid, block, 0, s, bl, LightGather{N, g->hitrec, g->occ}, to->slot_of_entry, to->count_out, to->value_out, g->total, tab);
         break;
     default: return -1;
     }
@@ -1299,6 +1407,19 @@ extern "C" int lh_render_launch_sun_rays(size_t nslots, const unsigned long long
     if ((nslots + 255) / 256 > 0x7fffffffu) return -1;
     hipLaunchKernelGGL(k_sun_rays, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nslots, d_nslots, d_hitrec,
                        sun_dir[0], sun_dir[1], sun_dir[2], d_org, d_dir);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the shadow rays and bounds of nslots hit records to the n lights of a HOST table (d_nslots or NULL: the slot count on the device, nslots its upper bound) */
+extern "C" int lh_render_launch_light_rays(size_t nslots, const unsigned long long *d_nslots, const lh_light_t *lights, int n, const double *d_hitrec,
+                                           double *d_org, double *d_dir, double *d_tmax, void *stream)
+{
+    lh_light_tab_t tab;
+    if (nslots == 0) return 0;
+    if (light_tab(lights, n, &tab) != 0) return -1;
+    const size_t items = nslots * (size_t)n;
+    if ((items + 255) / 256 > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_light_rays, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nslots, d_nslots, n, d_hitrec, d_org, d_dir, d_tmax, tab);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -13,6 +13,7 @@
 #include "lh_dirt.h"
 #include "lh_env.h"
 #include "lh_sky.h"
+#include "lh_lights.h"
 
 #define ensure_buf lh_ensure_buf
 
@@ -76,7 +77,13 @@ static int stage_report(const stage_timer &tm, const void *d_clk, size_t nwaves,
 
 /* ---- the gather stage: one description of its transport ------------------------------------------------------------------------------------
  * The kind (LH_GATHER_*, lh_gather.h) with its checked parameters, as the entry points hand it on: AO has none and offsets its rays by 1e-6 along Ns */
-struct gather_params { int kind; double eps; lh_dirt_params_t dirt; lh_env_params_t env; };
+struct gather_params { int kind; double eps; lh_dirt_params_t dirt; lh_env_params_t env; const lh_light_t *lights; int nlights; };          /* lights: LH_GATHER_LIGHT, the caller's HOST table (lh_lights.h) */
+/* the sample grid of a stage: the hemisphere's -- or, for the light stage, one "sample" per light: ntheta = the lights, nphi = 1, so that work item
+ * slot * N + r is item (slot, l = r) in every kernel and buffer the stage shares with the gathers */
+static inline ao_grid gather_grid(const gather_params &p, int gather_nsamples)
+{
+    return p.kind == LH_GATHER_LIGHT ? ao_grid{1, p.nlights, p.nlights} : ao_sample_grid(gather_nsamples);
+}
 /* ... and what ao_region / ao_batch_device make of it, once, at their top, for the stage and the resolves: the scratch entry of the kind and the caller
  * (lh_accel::gather), the light of an environment gather -- the accelerator's environment, or while a sky is set (lh_sky.h) the sun-and-sky light, with
  * LH_SKY_SUN the sun's direction: every hit then traces the sun's shadow ray -- the texture arguments of a tile's resolve (NULL: no mesh has a texture;
@@ -89,8 +96,8 @@ struct gather_desc {
     lh_tex_args_t tex_store; const lh_tex_args_t *tex;
     const char *prefix;
 };
-static const char *const gather_device_name[LH_GATHER_KINDS] = {"lh_accel_ao_device", "lh_accel_dirt_device", "lh_accel_env_device"};
-static const char *const gather_prefix[LH_GATHER_KINDS] = {"lh_accel_ao_device: ", "lh_accel_dirt_device: ", "lh_accel_env_device: "};
+static const char *const gather_device_name[LH_GATHER_KINDS] = {"lh_accel_ao_device", "lh_accel_dirt_device", "lh_accel_env_device", "lh_accel_lights_device"};
+static const char *const gather_prefix[LH_GATHER_KINDS] = {"lh_accel_ao_device: ", "lh_accel_dirt_device: ", "lh_accel_env_device: ", "lh_accel_lights_device: "};
 
 static void gather_describe(lh_accel_t *a, const gather_params &p, int where, gather_desc *d)
 {
@@ -113,7 +120,7 @@ static lh_gather_left_t gather_left(const gather_desc &d, ao_grid g, uint64_t se
     l.occ_count = fused ? (const unsigned int *)b->occcount.p : NULL; l.occ = (const uint8_t *)b->occ.p; l.t = (const double *)b->t.p;
     l.hitrec = (const double *)b->hitrec.p; l.key = (const unsigned long long *)b->key.p; l.adir = fused ? NULL : (const double *)b->adir.p;
     l.near_clip = d.p.dirt.near_clip; l.far_clip = d.p.dirt.far_clip; l.scale = d.p.env.scale;
-    l.env = &d.esrc; l.sky = d.sky; l.sun_occ = sun_occ; l.total = total;
+    l.env = &d.esrc; l.sky = d.sky; l.sun_occ = sun_occ; l.lights = d.p.lights; l.total = total;
     return l;
 }
 
@@ -122,7 +129,10 @@ static lh_gather_left_t gather_left(const gather_desc &d, ao_grid g, uint64_t se
  * What the stage leaves for the caller's resolve depends on its kind alone -- fused and materialised differ only in who wrote it:
  *   AO    fused, the occluded rays of every slot counted in occcount; materialised, the any-hit byte of ray (slot, r) at element slot * N + r of occ;
  *   ENV   (lh_env.h) that byte either way: the resolve needs the answer of every RAY;
- *   DIRT  (lh_dirt.h) the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), a double at element slot * N + r of t.
+ *   DIRT  (lh_dirt.h) the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), a double at element slot * N + r of t;
+ *   LIGHT (lh_lights.h; N = the lights) the bounded any-hit byte of shadow ray (slot, l) at element slot * N + l of occ, 0 for an item that is not traced:
+ *         fused, the persistent walk makes the item in its refill; materialised, one kernel writes rays and bounds and one bounded any-hit launch per
+ *         LH_DIRT_CHUNK rays answers them.
  * plan.fused: the kernel generates ray (slot, r) in its refill (lh_ao.h) -- nothing per gather ray goes through HBM but what is left
  * (lh_launch_trace_gather).  Else, and as the second try of a fused launch whose fix-up queue overflowed, materialised: gather rays in HBM (from
  * d_uniforms if given: the parity replay), then an any-hit batch, or for DIRT ONE bounded closest-hit launch per LH_DIRT_CHUNK rays through the ray
@@ -154,6 +164,7 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
     switch (d.p.kind) {
     case LH_GATHER_AO:  left = &b->occcount; slot_bytes = sizeof(unsigned int); fused_name = "fused AO"; break;                    /* a count per slot */
     case LH_GATHER_ENV: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused environment-gather"; break;                    /* a byte per ray */
+    case LH_GATHER_LIGHT: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused light"; break;                               /* a byte per shadow ray */
     default:            left = &b->t; slot_bytes = (size_t)N * 8; fused_name = "fused dirt"; bounded = true; break;                /* DIRT: a double per ray */
     }
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
@@ -210,7 +221,7 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
         if (!late && big && nhit * N >= (1ull << 27)) sc.ray_budget = big;
         budget = sc.ray_budget;
         const lh_gather_src_t src = {nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                                     late ? d_nhit : NULL, late ? big : 0u};
+                                     late ? d_nhit : NULL, late ? big : 0u, d.p.lights};
         const lh_launch_ctx_t ctx = {lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, (void *)s};
         const lh_fused_out_t fo = {d.p.kind, left->p, d.p.dirt.far_clip};
         if (lh_launch_trace_gather(&sc, &src, &fo, cnt, &ctx) != 0)
@@ -225,6 +236,22 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
         const size_t nao = (size_t)(nhit * N);
         if (!nao) return 0;
         if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!bounded && ensure_buf(&b->occ, nao))) return -1;
+        if (d.p.kind == LH_GATHER_LIGHT) {          /* 4-5. the light stage: rays and a bound per ray, then bounded any-hit launches through the ray dumps' kernels */
+            if (ensure_buf(&b->bound, nao * 8)) return -1;
+            if (lh_render_launch_light_rays((size_t)nhit, NULL, d.p.lights, d.p.nlights, (const double *)b->hitrec.p, (double *)b->aorg.p, (double *)b->adir.p,
+                                            (double *)b->bound.p, s) != 0)
+                return fail("%slight ray kernel launch failed", prefix);
+            if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+            for (size_t off = 0; off < nao; off += LH_DIRT_CHUNK) {
+                const size_t m = nao - off < LH_DIRT_CHUNK ? nao - off : LH_DIRT_CHUNK;
+                lh_launch_opt o = opt;
+                o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = (const double *)b->bound.p + off;
+                const lh_batch_t rays = {m, LH_MODE_ANY, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, NULL, NULL, NULL, NULL,
+                                         (uint8_t *)b->occ.p + off, cnt};
+                if (lh_launch(a, rays, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
+            }
+            return 0;
+        }
         /* 4. gather rays */
         if (lh_render_launch_ao_rays((size_t)nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
                                      (const unsigned long long *)b->key.p, (double *)b->aorg.p, (double *)b->adir.p, s) != 0)
@@ -294,11 +321,14 @@ static int env_params(const char *what, const lh_env_params_t *params, lh_env_pa
     return 0;
 }
 
+/* what the light stage's entry points hand to gather_check as `params`: the caller's list and its parameters (NULL: LH_LIGHTS_DEFAULTS) */
+struct lights_in { const lh_light_t *lights; int nlights; const lh_lights_params_t *params; };
+
 /* the kind of an entry point and its caller's parameters (NULL: the defaults; AO has none), checked */
 static int gather_check(const char *what, int kind, const void *params, gather_params *p)
 {
     const lh_env_params_t env_def = LH_ENV_DEFAULTS;
-    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def};
+    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def, NULL, 0};
     if (kind == LH_GATHER_DIRT) {
         if (dirt_params(what, (const lh_dirt_params_t *)params, &p->dirt) != 0) return -1;
         p->eps = p->dirt.eps;
@@ -306,6 +336,15 @@ static int gather_check(const char *what, int kind, const void *params, gather_p
     if (kind == LH_GATHER_ENV) {
         if (env_params(what, (const lh_env_params_t *)params, &p->env) != 0) return -1;
         p->eps = p->env.eps;
+    }
+    if (kind == LH_GATHER_LIGHT) {
+        const lights_in *in = (const lights_in *)params;
+        const lh_lights_params_t def = LH_LIGHTS_DEFAULTS;
+        p->eps = in->params ? in->params->eps : def.eps;
+        if (!lh_lights_ok(in->lights, in->nlights, p->eps))
+            return fail("%s: bad lights (1 .. %d lights in host memory, every v and rgb finite, a directional v not zero, flags within POINT | COSINE | INVSQ, "
+                        "INVSQ only with POINT, reserved 0; eps %g finite and >= 0)", what, LH_LIGHTS_MAX, p->eps);
+        p->lights = in->lights; p->nlights = in->nlights;
     }
     return 0;
 }
@@ -319,7 +358,7 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     const int h = nbands * band_rows;              /* lines of the batch */
     HIPCHK(hipSetDevice(a->device));
     hipStream_t s = (hipStream_t)stream;
-    const ao_grid g = ao_sample_grid(gather_nsamples);
+    const ao_grid g = gather_grid(p, gather_nsamples);
     const size_t S = (size_t)w * h * ps * ps;
     if ((unsigned long long)cam->width * (unsigned long long)cam->height * (unsigned long long)(ps * ps) >= (1ull << 34))
         return fail("AO pipeline: more than 2^34 samples in the frame (slot keys carry 34 bits)");
@@ -340,8 +379,9 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     }
     if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
     /* material textures (lh_tex.h): with at least one set, the resolve multiplies; with none, tex is NULL and the launch is the one it always was */
-    if (a->ntex && !d.sky && lh_tex_sync(a) != 0) return -1;
-    d.tex = d.sky ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &d.tex_store);
+    const bool no_tex = d.sky || p.kind == LH_GATHER_LIGHT;          /* neither the sun-and-sky gather nor direct light fetches a texture */
+    if (a->ntex && !no_tex && lh_tex_sync(a) != 0) return -1;
+    d.tex = no_tex ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &d.tex_store);
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
@@ -368,7 +408,7 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of the resolve's 64 counters */
     /* 6. the samples' values into the pixels */
     const lh_resolve_tile_t to = {w, h, band_rows, ps, ps, (const uint32_t *)b->slot.p, (float *)d_rgb, d.tex};
-    static const char *const resolve_name[LH_GATHER_KINDS] = {"resolve", "dirt resolve", "environment-gather resolve"};
+    static const char *const resolve_name[LH_GATHER_KINDS] = {"resolve", "dirt resolve", "environment-gather resolve", "light resolve"};
     auto resolve = [&](const lh_gather_left_t &left) -> int {
         if (lh_render_launch_tile_resolve(&to, &left, s) != 0) return fail("%s kernel launch failed", d.sky ? "sun-and-sky resolve" : resolve_name[p.kind]);
         return 0;
@@ -401,7 +441,8 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     if (tm && stage_report(*tm, a->r_diag.p, nwaves, S, tot.nhit, nao) != 0) return -1;
     if (p.kind == LH_GATHER_AO) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
     if (cnt) {
-        lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
+        /* (the light stage counts its work items, traced or not: the camera rays and hits x lights) */
+        lh_stat_add(a, tot.cnt, p.kind == LH_GATHER_LIGHT ? (unsigned long long)S + nao : tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
             fprintf(stderr, "[lucille_hip] AO batch: rays by node visits (bucket b: [2^(b-1), 2^b)):");
             for (int k = 0; k < 24; k++) fprintf(stderr, " %llu", tot.cnt[LH_CNT_HIST + k]);
@@ -541,7 +582,7 @@ static int ao_batch_device(const char *what, lh_accel_t *a, const gather_params 
     if (L == 0) return 0;
     HIPCHK(hipSetDevice(a->device));
     hipStream_t s = (hipStream_t)stream;
-    const ao_grid g = ao_sample_grid(gather_nsamples);
+    const ao_grid g = gather_grid(p, gather_nsamples);
     gather_desc d;
     gather_describe(a, p, LH_GATHER_BATCH, &d);
     lh_gather_scratch *b = d.b;
@@ -578,7 +619,7 @@ static int ao_batch_device(const char *what, lh_accel_t *a, const gather_params 
     };
     ao_totals tot;
     if (ao_stage(a, d, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, plan, resolve, s, &tot) != 0) return -1;
-    if (cnt) lh_stat_add(a, tot.cnt, tot.cnt[LH_CNT_RAYS], tot.nocc, true);
+    if (cnt) lh_stat_add(a, tot.cnt, p.kind == LH_GATHER_LIGHT ? tot.nhit * (unsigned long long)g.N : tot.cnt[LH_CNT_RAYS], tot.nocc, true);      /* (the light stage counts its work items, traced or not) */
     if (cnt && p.kind != LH_GATHER_AO) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
     return 0;
 }
@@ -679,11 +720,11 @@ static int gather_batch_host(const char *what, int kind, const void *params, lh_
     if (go <= 0) return go;
     if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
     const size_t n = n_rays;
-    const size_t need = uniforms ? (size_t)2 * ao_sample_grid(gather_nsamples).N * n : 0;          /* worst case: every ray hits */
+    const size_t need = uniforms ? (size_t)2 * gather_grid(p, gather_nsamples).N * n : 0;          /* worst case: every ray hits */
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t nrad = kind == LH_GATHER_ENV ? 3 * n : n;          /* floats of `radiance` */
+    const size_t nrad = (kind == LH_GATHER_ENV || kind == LH_GATHER_LIGHT) ? 3 * n : n;          /* floats of `radiance` */
     if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 2 * sizeof(uint32_t) * n + sizeof(float) * nrad)) return -1;
     double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
     double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
@@ -727,6 +768,76 @@ extern "C" int lh_accel_env_host(lh_accel_t *a, size_t n_rays, const double *org
 {
     return gather_batch_host("lh_accel_env_host", LH_GATHER_ENV, params, a, n_rays, org, dir, prim, t, u, v, gather_nsamples, seed, key, uniforms, nuniforms,
                              occluded_count, rgb);
+}
+
+/* ---- direct light (lh_lights.h): the same list, compaction, stage and resolves with a light per "sample"; no keys, seed or uniforms ---- */
+extern "C" int lh_accel_lights_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                      const void *d_u, const void *d_v, const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                                      const void *d_index, size_t n_index, const void *d_count, void *d_visible, void *d_rgb, void *stream)
+{
+    const lights_in in = {lights, nlights, params};
+    return gather_batch_device("lh_accel_lights_device", LH_GATHER_LIGHT, &in, a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, 1, 0, NULL, NULL,
+                               d_index, n_index, d_count, d_visible, d_rgb, stream);
+}
+
+extern "C" int lh_accel_lights_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                                    const double *u, const double *v, const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                                    uint32_t *visible, float *rgb)
+{
+    const lights_in in = {lights, nlights, params};
+    return gather_batch_host("lh_accel_lights_host", LH_GATHER_LIGHT, &in, a, n_rays, org, dir, prim, t, u, v, 1, 0, NULL, NULL, 0, visible, rgb);
+}
+
+extern "C" int lh_render_lights_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, const lh_light_t *lights, int nlights,
+                                     const lh_lights_params_t *params, void *d_rgb, lh_tile_stats_t *stats, void *stream)
+{
+    const lights_in in = {lights, nlights, params};
+    return gather_tile("lh_render_lights_tile", LH_GATHER_LIGHT, &in, a, cam, x0, y0, w, h, ps, 1, 0, NULL, d_rgb, stats, stream);
+}
+
+/* the shadow rays alone, shaped like lh_accel_ao_rays_device: the compaction's slots and count, then ray (slot, l) and its bound at element slot * L + l.
+ * Asynchronous: the table travels in the ray kernel's arguments, nothing is read back */
+extern "C" int lh_accel_light_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                          const void *d_u, const void *d_v, const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                                          void *d_slot_of_ray, void *d_nslots, void *d_org_out, void *d_dir_out, void *d_tmax_out,
+                                          size_t capacity_rays, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_light_rays_device";
+    const lights_in in = {lights, nlights, params};
+    gather_params p;
+    if (gather_check(what, LH_GATHER_LIGHT, &in, &p) != 0) return -1;
+    if ((((uintptr_t)d_org_out | (uintptr_t)d_dir_out | (uintptr_t)d_tmax_out) & 7u) != 0) return fail("%s: the ray and bound arrays are doubles: a pointer is not 8-byte aligned", what);
+    const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, 1, NULL, NULL, NULL, 0, NULL, d_slot_of_ray, d_nslots);
+    if (go < 0) return go;
+    hipStream_t s = (hipStream_t)stream;
+    if (go == 0) {
+        if (d_nslots) { HIPCHK(hipSetDevice(a->device)); HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s)); }
+        return 0;
+    }
+    if (!d_slot_of_ray || !d_nslots || !d_org_out || !d_dir_out || !d_tmax_out) return fail("%s: NULL output array", what);
+    const size_t L = (size_t)p.nlights;
+    if (capacity_rays / L < n_rays) return fail("%s: capacity_rays %zu does not cover the worst case n_rays * nlights = %zu x %zu", what, capacity_rays, n_rays, L);
+    HIPCHK(hipSetDevice(a->device));
+    if (a->hs->bvh.ntris == 0) {
+        HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
+        HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s));
+        return 0;
+    }
+    const unsigned nb = (unsigned)((n_rays + 255) / 256);
+    lh_gather_scratch *b = &a->gather[LH_GATHER_LIGHT][LH_GATHER_BATCH];
+    if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65) || ensure_buf(&b->blocks, (size_t)nb * 4) ||
+        ensure_buf(&b->hitrec, n_rays * 96) || ensure_buf(&b->key, n_rays * 8)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)b->totals.p;
+    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
+                                       (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
+                                       NULL, (uint32_t *)b->blocks.p, (uint32_t *)d_slot_of_ray,
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, p.eps, s) != 0)
+        return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
+    if (lh_render_launch_light_rays(n_rays, d_nhit, p.lights, p.nlights, (const double *)b->hitrec.p, (double *)d_org_out, (double *)d_dir_out,
+                                    (double *)d_tmax_out, s) != 0)
+        return fail("%s: light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return 0;
 }
 
 /* the fetch alone: ri_texture_ibl_fetch (env_fetch, lh_pt.h) of the accelerator's environment for n directions.  Asynchronous, nothing read back */
