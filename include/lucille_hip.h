@@ -691,7 +691,7 @@ int  lh_accel_sky_host(lh_accel_t *accel, size_t n, const double *dir_xyz, float
  * lh_render_lights_tile: per camera sample -- a miss gives 0, a hit its value_k (the float); sub-samples are widened, added per channel
  *   in sample order, scaled, converted, clamped and written as lh_render_env_tile does; a frame does not depend on its tiling.
  *   stats->ao_rays = hits x nlights, stats->ao_occluded = the items whose bit is clear.
- * Not built: the texture multiply (the reference's sun branch fetches none, ambientocclusion.c:369-375), area lights, the sky's own sun
+ * Not built: the texture multiply (the reference's sun branch fetches none, ambientocclusion.c:369-375), the sky's own sun
  *   ray through this stage (lh_accel_set_sky keeps its launch), bands and the multi-device forms. */
 #define LH_LIGHT_POINT  1u   /* v is a position; without it v is the direction TOWARDS the light, as the reference's light->direction */
 #define LH_LIGHT_COSINE 2u   /* weight by the cosine between Ns and the ray */
@@ -716,6 +716,82 @@ int  lh_accel_light_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_
 int  lh_render_lights_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
                            const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
                            void *d_rgb, lh_tile_stats_t *stats, void *stream);
+
+/* ---- area lights: soft shadows from triangle emitters (the mesh an ri_light_t carries: light->geom, ri_light_attach_geom, src/render/light.c:107-111;
+ *      the point and normal drawn on it: ri_light_sample_pos_and_normal, light.c:113-147; the rule: lucille_amd/csrc/lh_area.h) ----
+ * For every hit, every light of the list and every sample s < S one any-hit ray from the gather stages' origin O = P + eps Ns to a point drawn on the
+ * light's emitter triangles: which lights the hit sees, and the mean of what their samples add.  Everything in fp64 in the order written:
+ *   emitters: lh_accel_set_emitters gives the accelerator a table of triangles (HOST memory, 9 doubles each: v0 v1 v2), after commit, at any time;
+ *     NULL / 0 removes it.  The library keeps one 128-byte record per triangle on the device (v0 v1 v2 n area: e1 = v1 - v0, e2 = v2 - v0, c = e1 x e2,
+ *     norm2 = (c0 c0 + c1 c1) + c2 c2, len = sqrt(norm2), n = c * (1.0 / len) where norm2 > (double)1.0e-17f, else n = c; area = 0.5 * len).  A
+ *     replaced or removed block is released behind a device-wide synchronise, as a texture's; the table is kept across lh_accel_recommit (emitters are
+ *     no scene geometry: a caller who wants them to occlude adds them as a mesh too).  Refused before anything touches a device: a non-finite vertex,
+ *     ntris >= 2^31 ("bad emitters").
+ *   light l is the run [first_tri, first_tri + ntris) of the table.  Sample (l, s) with uniforms (x0, x1, x2): j = (int)(x0 * (double)ntris) clamped to
+ *     [0, ntris - 1]; a NaN x0 makes the item dark; sq = sqrt(x1), t = x2, pos[k] = (double)(float)((v0[k] * (1.0 - sq) + v1[k] * (sq - t * sq)) +
+ *     (v2[k] * sq) * t) on triangle first_tri + j -- the reference's expression and its rounding to float -- and n that triangle's.
+ *   ray: dir = pos - O, not normalised, under the bound params.bound (0 < bound <= 1): open iff the bounded any-hit contract of
+ *     lh_accel_intersect_device_tmax answers 0 for (O, dir, bound).  No self-primitive skip.  The float-rounded pos lies off its triangle's plane: where
+ *     the emitter triangles are scene geometry too, at bound 1 an emitter may or may not shadow itself; pass a little less (1 - 1e-4).  A zero or
+ *     non-finite dir is dark.
+ *   weight: w = 1, dd = (d0 d0 + d1 d1) + d2 d2, then in this order: LH_AREA_COSINE, the surface cosine, LH_LIGHT_COSINE's expression;
+ *     LH_AREA_FACING, cl = -((n0 d0 + n1 d1) + n2 d2) / sqrt(dd), w = w * (cl > 0 ? cl : 0) (a one-sided emitter); LH_AREA_INVSQ, w = w / dd;
+ *     LH_AREA_PDF, w = w * ((double)ntris * area_j) (the pick is uniform by index: 1 / pdf).  A dark item and one with !(w > 0) is never traced.
+ *   value: sum_k = 0; for l in list order, for s = 0 .. S - 1: if item (l, s) is traced and open, sum_k = sum_k + w * rgb_l[k];
+ *     value_k = (float)(sum_k / (double)S); bit l of the mask: any sample of light l is open.  The order is part of the contract.
+ *   uniforms: d_uniforms (or NULL) replays 3 doubles per item in (hit slot, l, s) order, 3 * nlights * S * hits are consumed.  Built in (NULL):
+ *     c = ((key & (2^34 - 1)) * (uint64)(L S) + (uint64)(l S + s)) * 4, k = (seed * 0x9E3779B97F4A7C15) ^ c, x_j = (double)mix32(k + j) * 2^-32,
+ *     mix32 the AO stage's; the key of a hit is its entry of d_key, as lh_accel_ao_device takes it.  The built-in path is the replay rule fed by this
+ *     generator.
+ *   parameters: NULL is LH_AREA_DEFAULTS; eps finite and >= 0, bound finite with 0 < bound <= 1, 1 <= nsamples <= LH_AREA_SAMPLES_MAX, reserved 0;
+ *     1 <= nlights <= LH_AREA_LIGHTS_MAX (31, for LH_LIGHTS_MAX's reason); every rgb finite, flags within the four bits, reserved 0, ntris >= 1 and
+ *     first_tri + ntris <= the table's count.  Anything else is refused ("bad area lights") and nothing is enqueued.  `lights` is HOST memory and
+ *     travels by value in the kernels' arguments.  A ray with |dir.y| <= 1e-14 is outside the contract, as every shadow ray's.
+ * lh_accel_area_lights_device: as lh_accel_lights_device, word for word -- list, count and id semantics, hit slots in list order, untouched slots of
+ *   rays that are not traced, an id listed twice, synchronous on `stream`, the empty scene, scratch of its own, its refusals -- with seed, d_key and
+ *   d_uniforms as lh_accel_ao_device takes them.  Fused when "ao_fused" is on, no uniforms are replayed and list entries x nlights x S < 2^31: ray
+ *   source 4 of the persistent any-hit walk makes item (slot, l, s) in its refill -- the hit record, three uniforms, ONE gathered emitter record --
+ *   walks it under the bound and stores its answer as a byte.  Else, and as the second try after a queue overflow, one kernel writes rays, bounds and
+ *   weights and one bounded any-hit launch per 2^30 items answers them.  Both give the same bytes.  With lh_accel_trace_statistics on, `rays` advances
+ *   by hits x nlights x S and counters[4] by the items that are not open.
+ * lh_accel_area_lights_host: the same for HOST arrays; nuniforms >= 3 * nlights * S * n_rays where uniforms are given.
+ * lh_accel_area_light_rays_device: the rays alone, shaped like lh_accel_light_rays_device: item (slot, l, s) at element (slot * nlights + l) * S + s of
+ *   d_org_out / d_dir_out (3 doubles), d_tmax_out (the bound, 0.0 for an item that is not traced) and d_weight_out (doubles, may be NULL).
+ *   lh_accel_intersect_device_tmax in any-hit mode on these arrays gives exactly the stage's bytes.  Asynchronous, nothing read back;
+ *   capacity_rays >= n_rays * nlights * S or it is refused.
+ * lh_render_area_lights_tile: per camera sample, as lh_render_lights_tile; the built-in generator only, keyed by the absolute sample position: a frame
+ *   does not depend on its tiling.  stats->ao_rays = hits x nlights x S, stats->ao_occluded = the items that are not open.
+ * Not built: the device-pointer emitter table, the qmc sampler (ri_light_sample_pos_and_normal_qmc, light.c:149-194), a texture multiply, bands and
+ *   the multi-device forms, AreaLightSource in the RIB reader. */
+#define LH_AREA_COSINE 1u   /* weight by the cosine between Ns and the ray */
+#define LH_AREA_FACING 2u   /* weight by the cosine at the emitter, clamped at 0: one-sided */
+#define LH_AREA_INVSQ  4u   /* divide by the squared distance */
+#define LH_AREA_PDF    8u   /* multiply by ntris x the sampled triangle's area */
+#define LH_AREA_LIGHTS_MAX  31
+#define LH_AREA_SAMPLES_MAX 1024
+typedef struct lh_area_light { uint32_t first_tri, ntris; double rgb[3]; uint32_t flags, reserved; } lh_area_light_t;   /* 40 bytes */
+typedef struct lh_area_params { double eps, bound; int32_t nsamples; uint32_t reserved; } lh_area_params_t;              /* 24 bytes */
+#define LH_AREA_DEFAULTS { 1.0e-5, 1.0, 16, 0 }
+int  lh_accel_set_emitters(lh_accel_t *accel, const double *tri_xyz, size_t ntris);
+int  lh_accel_area_lights_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                                 const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                                 const lh_area_light_t *lights, int nlights, const lh_area_params_t *params,
+                                 uint64_t seed, const void *d_key, const void *d_uniforms,
+                                 const void *d_index, size_t n_index, const void *d_count,
+                                 void *d_visible, void *d_rgb, void *stream);
+int  lh_accel_area_lights_host(lh_accel_t *accel, size_t n_rays, const double *org_xyz, const double *dir_xyz, const uint32_t *prim,
+                               const double *t, const double *u, const double *v, const lh_area_light_t *lights, int nlights,
+                               const lh_area_params_t *params, uint64_t seed, const uint64_t *key, const double *uniforms, size_t nuniforms,
+                               uint32_t *visible, float *rgb);
+int  lh_accel_area_light_rays_device(lh_accel_t *accel, size_t n_rays, const void *d_org_xyz, const void *d_dir_xyz,
+                                     const void *d_prim, const void *d_t, const void *d_u, const void *d_v,
+                                     const lh_area_light_t *lights, int nlights, const lh_area_params_t *params,
+                                     uint64_t seed, const void *d_key, const void *d_uniforms,
+                                     void *d_slot_of_ray, void *d_nslots, void *d_org_out, void *d_dir_out, void *d_tmax_out, void *d_weight_out,
+                                     size_t capacity_rays, void *stream);
+int  lh_render_area_lights_tile(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h, int pixel_samples,
+                                const lh_area_light_t *lights, int nlights, const lh_area_params_t *params, uint64_t seed,
+                                void *d_rgb, lh_tile_stats_t *stats, void *stream);
 
 /* ---- the refraction chain: the reference's Whitted transport (trace_whitted, src/transport/whitted.c:32-151; ri_refract and
  *      ri_reflect, src/render/reflection.c:26-128) ----

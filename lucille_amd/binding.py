@@ -186,6 +186,37 @@ def _light_array(what, lights):
     return ((Light * len(lights))(*lights) if lights else None), len(lights)
 
 
+AREA_COSINE, AREA_FACING, AREA_INVSQ, AREA_PDF = 1, 2, 4, 8      # LH_AREA_*: the surface cosine; the emitter's cosine, one-sided; 1 / squared distance; ntris x the triangle's area
+AREA_LIGHTS_MAX, AREA_SAMPLES_MAX = 31, 1024                     # LH_AREA_LIGHTS_MAX, LH_AREA_SAMPLES_MAX
+
+
+class AreaLight(C.Structure):
+    """lh_area_light_t (40 bytes): the run [first_tri, first_tri + ntris) of the accelerator's emitter table (set_emitters), its colour and
+    flags (AREA_COSINE, AREA_FACING, AREA_INVSQ, AREA_PDF); reserved must stay 0"""
+    _fields_ = [("first_tri", C.c_uint32), ("ntris", C.c_uint32), ("rgb", C.c_double * 3), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, first_tri=0, ntris=1, rgb=(1.0, 1.0, 1.0), flags=0, reserved=0):
+        super().__init__(int(first_tri), int(ntris), (C.c_double * 3)(*[float(x) for x in rgb]), int(flags), int(reserved))
+
+
+class AreaParams(C.Structure):
+    """lh_area_params_t (24 bytes): the origin offset along Ns, the bound of a traced ray (0 < bound <= 1; a little below 1 where the emitters
+    are scene geometry too), the samples per light (defaults: LH_AREA_DEFAULTS); reserved must stay 0"""
+    _fields_ = [("eps", C.c_double), ("bound", C.c_double), ("nsamples", C.c_int32), ("reserved", C.c_uint32)]
+
+    def __init__(self, eps=1.0e-5, bound=1.0, nsamples=16, reserved=0):
+        super().__init__(float(eps), float(bound), int(nsamples), int(reserved))
+
+
+def _area_array(what, lights):
+    """a sequence of AreaLight -> (a ctypes array of them, or None for an empty one; its length): the C call refuses what the rule does not accept"""
+    lights = list(lights)
+    for x in lights:
+        if not isinstance(x, AreaLight):
+            raise ValueError("%s: lights must be a sequence of AreaLight" % what)
+    return ((AreaLight * len(lights))(*lights) if lights else None), len(lights)
+
+
 class WhittedParams(C.Structure):
     """lh_whitted_params_t: origin offset, relative refractive index and depth limit of the refraction chain (defaults:
     LH_WHITTED_DEFAULTS, the constants of whitted.c); reserved must stay 0"""
@@ -217,6 +248,7 @@ ABI_SYMBOLS = [
     "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
     "lh_sky_from_site", "lh_accel_set_sky", "lh_accel_sky_device", "lh_accel_sky_host",
     "lh_accel_lights_device", "lh_accel_lights_host", "lh_accel_light_rays_device", "lh_render_lights_tile",
+    "lh_accel_set_emitters", "lh_accel_area_lights_device", "lh_accel_area_lights_host", "lh_accel_area_light_rays_device", "lh_render_area_lights_tile",
     "lh_accel_whitted_rays_device", "lh_accel_whitted_device", "lh_accel_whitted_host", "lh_render_whitted_tile",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
     "lh_multi_create", "lh_multi_destroy", "lh_multi_ndevices", "lh_multi_accel", "lh_multi_add_mesh", "lh_multi_set_normals",
@@ -333,6 +365,13 @@ def lib():
         L.lh_accel_lights_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, vp]
         L.lh_accel_light_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, vp, vp, vp, vp, sz, vp]
         L.lh_render_lights_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, lp, i32, lpp, vp, C.POINTER(TileStats), vp]
+    if hasattr(L, "lh_accel_area_lights_device"):        # an older library under LH_LIBRARY (A/B runs in tools/) has no area-light stage
+        ap, app, u64 = C.POINTER(AreaLight), C.POINTER(AreaParams), C.c_uint64
+        L.lh_accel_set_emitters.argtypes = [vp, vp, sz]
+        L.lh_accel_area_lights_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, ap, i32, app, u64, vp, vp, vp, sz, vp, vp, vp, vp]
+        L.lh_accel_area_lights_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, ap, i32, app, u64, vp, vp, sz, vp, vp]
+        L.lh_accel_area_light_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, ap, i32, app, u64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.lh_render_area_lights_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, ap, i32, app, u64, vp, C.POINTER(TileStats), vp]
     if hasattr(L, "lh_accel_whitted_device"):            # an older library under LH_LIBRARY (A/B runs in tools/) has no refraction chain
         wpp = C.POINTER(WhittedParams)
         L.lh_accel_whitted_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, wpp, vp, sz, vp, vp, vp, vp]
@@ -1406,6 +1445,142 @@ class HipAccel:
         st = TileStats()
         _check(self.L.lh_render_lights_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, arr, nl, C.byref(params), _dptr(out), C.byref(st),
                                             C.c_void_p(stream)), "lh_render_lights_tile")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    # ---- area lights: soft shadows from triangle emitters (lh_area.h) ----
+    @staticmethod
+    def _area_params(what, params):
+        if params is None:
+            params = AreaParams()
+        if not isinstance(params, AreaParams):
+            raise ValueError("%s: params must be an AreaParams" % what)
+        return params
+
+    def set_emitters(self, tris):
+        """lh_accel_set_emitters: the table of emitter triangles the area lights' runs index -- host array [ntris, 3, 3] (or [ntris, 9]) of
+        float64 vertices; None (or an empty array) removes it.  After commit, at any time; kept across recommit."""
+        if tris is None:
+            _check(self.L.lh_accel_set_emitters(self.h, None, 0), "lh_accel_set_emitters")
+            return
+        t = _np(tris, np.float64).reshape(-1, 9)
+        if t.shape[0] == 0:
+            _check(self.L.lh_accel_set_emitters(self.h, None, 0), "lh_accel_set_emitters")
+            return
+        _check(self.L.lh_accel_set_emitters(self.h, t.ctypes.data, t.shape[0]), "lh_accel_set_emitters")
+
+    def area_lights_device(self, org, dr, records, lights, params=None, seed=1, key=None, uniforms=None, index=None, count=None, out=None, stream=None):
+        """lh_accel_area_lights_device: which of `lights` (a sequence of 1 .. AREA_LIGHTS_MAX AreaLight) every hit of a batch of rays and their
+        closest-hit records sees through params.nsamples samples each, and the mean of what the samples add; org / dr / records / index / count
+        as lights_device, seed / key / uniforms as ao_device (uniforms: 3 per item in (hit slot, l, s) order).  Returns (visible, rgb) as
+        lights_device does.  Synchronous."""
+        import torch
+        what = "area_lights_device"
+        params = self._area_params(what, params)
+        arr, nl = _area_array(what, lights)
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
+        dev = org.device
+        ip, ni, cp = _list_args(index, count, what)
+        if index is None and count is not None:
+            ni = n
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
+            raise ValueError("%s: out must be a (visible, rgb) pair, at least one of them a tensor" % what)
+        ov, orgb = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if ov is not None and not (ov.is_cuda and ov.dtype in words and ov.dim() == 1 and ov.shape[0] == n and ov.is_contiguous()):
+            raise ValueError("%s: the mask output must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if orgb is not None and not (orgb.is_cuda and orgb.dtype == torch.float32 and orgb.dim() == 2 and tuple(orgb.shape) == (n, 3) and orgb.is_contiguous()):
+            raise ValueError("%s: the colour output must be a contiguous float32 device tensor [n, 3]" % what)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_area_lights_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl, C.byref(params),
+                                                  int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(ov), _dptr(orgb), C.c_void_p(stream)),
+               "lh_accel_area_lights_device")
+        return out
+
+    def area_lights_host(self, org, dr, records, lights, params=None, seed=1, key=None, uniforms=None):
+        """lh_accel_area_lights_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v); key uint64 [n] or None; uniforms float64, 3 per
+        item, or None) -> (visible uint32 [n], rgb float32 [n, 3])"""
+        what = "area_lights_host"
+        params = self._area_params(what, params)
+        arr, nl = _area_array(what, lights)
+        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
+        if d.shape[0] != n or len(records) != 4:
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
+        p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
+        u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
+        if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
+            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
+        k = None if key is None else _np(key, np.uint64).reshape(-1)
+        if k is not None and k.shape[0] != n:
+            raise ValueError("%s: key must hold one word per ray" % what)
+        un = None if uniforms is None else _np(uniforms, np.float64).reshape(-1)
+        vis = np.empty(n, np.uint32); rgb = np.empty((n, 3), np.float32)
+        _check(self.L.lh_accel_area_lights_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
+                                                arr, nl, C.byref(params), int(seed), None if k is None else k.ctypes.data,
+                                                None if un is None else un.ctypes.data, 0 if un is None else un.shape[0],
+                                                vis.ctypes.data, rgb.ctypes.data), "lh_accel_area_lights_host")
+        return vis, rgb
+
+    def area_light_rays_device(self, org, dr, records, lights, params=None, seed=1, key=None, uniforms=None, out=None, stream=None):
+        """lh_accel_area_light_rays_device: only the rays of the batch's hits to the lights' samples.  Returns (slot_of_ray int32 [n], nslots --
+        one-element int32 tensor, org, dir -- float64 [n * L * S, 3], tmax, weight -- float64 [n * L * S]: item (slot, l, s) at row
+        (slot * L + l) * S + s, the first nslots * L * S rows written; tmax is params.bound, or 0 for an item that is not traced).
+        intersect_device(..., mode=MODE_ANY, tmax=tmax) on them gives the stage's bytes.  Nothing is read back; out: such a 6-tuple to fill."""
+        import torch
+        what = "area_light_rays_device"
+        params = self._area_params(what, params)
+        arr, nl = _area_array(what, lights)
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
+        dev = org.device
+        if out is None:
+            m = n * max(nl, 1) * max(int(params.nsamples), 1)
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
+                   torch.empty((m, 3), dtype=torch.float64, device=dev), torch.empty((m, 3), dtype=torch.float64, device=dev),
+                   torch.empty(m, dtype=torch.float64, device=dev), torch.empty(m, dtype=torch.float64, device=dev))
+        if not isinstance(out, (tuple, list)) or len(out) != 6:
+            raise ValueError("%s: out must be (slot_of_ray, nslots, org, dir, tmax, weight)" % what)
+        so, ns, ro, rd, rt, rw = out
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
+            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
+            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
+        for name, x in (("org", ro), ("dir", rd)):
+            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
+        for name, x in (("tmax", rt), ("weight", rw)):
+            if x is None and name == "weight":
+                continue
+            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 1 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [m]" % (what, name))
+        cap = min(int(ro.shape[0]), int(rd.shape[0]), int(rt.shape[0]), int(rt.shape[0]) if rw is None else int(rw.shape[0]))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_area_light_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl,
+                                                      C.byref(params), int(seed), _dptr(key), _dptr(uniforms), _dptr(so), _dptr(ns), _dptr(ro),
+                                                      _dptr(rd), _dptr(rt), _dptr(rw), cap, C.c_void_p(stream)), "lh_accel_area_light_rays_device")
+        return out
+
+    def render_area_lights_tile(self, cam, x0, y0, w, h, pixel_samples, lights, params=None, seed=1, out=None, stream=None):
+        """lh_render_area_lights_tile: area lights per camera sample -- a miss gives 0, a hit the mean over the samples of what its lights add ->
+        (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x lights x samples, ao_occluded = the items that are
+        not open).  The built-in generator, keyed by the absolute sample position: a frame does not depend on its tiling."""
+        import torch
+        what = "render_area_lights_tile"
+        params = self._area_params(what, params)
+        arr, nl = _area_array(what, lights)
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = TileStats()
+        _check(self.L.lh_render_area_lights_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, arr, nl, C.byref(params), int(seed), _dptr(out),
+                                                 C.byref(st), C.c_void_p(stream)), "lh_render_area_lights_tile")
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def environment_device(self, dirs, out=None, stream=None):

@@ -1466,6 +1466,7 @@ extern "C" void lh_accel_destroy(lh_accel_t *a)
 {
     if (!a) return;
     lh_tex_release(a);
+    if (a->d_emitters) { (void)hipSetDevice(a->device); (void)hipDeviceSynchronize(); (void)hipFree(a->d_emitters); a->d_emitters = NULL; a->nemit = 0; }      /* lh_accel_set_emitters */
     if (a->committed || a->commit_failed) { (void)hipSetDevice(a->device); lh_comb_destroy(a); release_device(a); }
     if (a->ndmeshes || a->ndmesh_events) { (void)hipSetDevice(a->device); free_dmeshes(a); }
     for (uint32_t g = 0; g < a->nmeshes; g++) {

@@ -190,6 +190,7 @@ typedef struct lh_gather_src {
     const unsigned long long *d_nslots;
     uint32_t    budget_big;
     const struct lh_light *lights;      /* LH_GATHER_LIGHT: the HOST table of ntheta lights (nphi is 1), copied into the kernels' arguments; else NULL */
+    const struct lh_area_tab *area;     /* LH_GATHER_AREA: the call's lights, emitter table and bound (lh_area.h; HOST memory; ntheta = its S, nphi = its L), copied likewise; else NULL */
 } lh_gather_src_t;
 
 /* what a fused stage leaves, by its kind (LH_GATHER_*, lh_gather.h), in the one array `out`:
@@ -197,7 +198,8 @@ typedef struct lh_gather_src {
  *   DIRT  double per gather ray, the t of ray (slot, r)'s closest hit under the one bound far_clip (lh_tmax.h) at element slot * N + r, 1e38 for a miss;
  *   ENV   uint8_t per gather ray (lh_env.h): the AO stage's any-hit walk, the answer of ray (slot, r), 0 or 1, at element slot * N + r, written exactly
  *         once (no memset, no atomic);
- *   LIGHT uint8_t per shadow ray (lh_lights.h): the bounded any-hit answer of item (slot, l) at element slot * L + l, 0 for an item that is not traced.
+ *   LIGHT uint8_t per shadow ray (lh_lights.h): the bounded any-hit answer of item (slot, l) at element slot * L + l, 0 for an item that is not traced;
+ *   AREA  the same byte (lh_area.h) for item (slot, l, s) at element (slot * L + l) * S + s.
  * Rays the persistent kernel does not finish go through the stream's fix-up queue: out of budget or stack rows to the cooperative walk, fragile hits (for
  * DIRT the mark of a hit near the bound among them) to the reference's own walk; whoever finishes a ray stores the same word.  A queue overflow leaves
  * DIRT and ENV words unwritten and AO counts short: the caller redoes the stage materialised */

@@ -16,7 +16,8 @@ enum { LH_GATHER_AO = 0,          /* ambient occlusion: a count of occluded rays
        LH_GATHER_DIRT = 1,        /* the dirtmap transport (lh_dirt.h): a double per ray, the t of its bounded closest hit */
        LH_GATHER_ENV = 2,         /* the environment-lit gather (lh_env.h): a byte per ray */
        LH_GATHER_LIGHT = 3,       /* direct light (lh_lights.h): N = the lights of the list, gather ray (slot, l) the shadow ray to light l; a byte per ray */
-       LH_GATHER_KINDS = 4 };
+       LH_GATHER_AREA = 4,        /* area lights (lh_area.h): N = lights x samples, gather ray (slot, l, s) the shadow ray to a point drawn on light l's emitters; a byte per ray */
+       LH_GATHER_KINDS = 5 };
 /* who runs the stage: the tile pipeline (samples of a region) or a caller's batch of hit records (list entries) */
 enum { LH_GATHER_TILE = 0, LH_GATHER_BATCH = 1 };
 
@@ -34,11 +35,12 @@ typedef struct lh_gather_plan { int fused, late; } lh_gather_plan_t;
 static inline lh_gather_plan_t lh_gather_plan(int kind, int where, size_t entries, size_t N, int ao_fused, int uniforms, int ao_group, int sun, int sync)
 {
     const unsigned long long rays = (unsigned long long)entries * (unsigned long long)N;          /* the worst case */
-    const int grouped = kind == LH_GATHER_AO && ao_group != 0;          /* the dirt, environment and light kernels have no grouped order */
+    const int grouped = kind == LH_GATHER_AO && ao_group != 0;          /* the dirt, environment, light and area kernels have no grouped order */
     lh_gather_plan_t p;
-    if (kind == LH_GATHER_LIGHT) {
-        /* no uniforms, no grouped order, no sun; a tile decides on the worst case as a batch does: entries x L < 2^31 (the 32-bit item index) */
-        p.fused = ao_fused && rays < (1ull << 31);
+    if (kind == LH_GATHER_LIGHT || kind == LH_GATHER_AREA) {
+        /* no grouped order, no sun; a tile decides on the worst case as a batch does: entries x L (x S) < 2^31 (the 32-bit item index).  The light stage
+         * draws nothing; replayed uniforms send the area stage to the ray kernel, which reads them from memory */
+        p.fused = ao_fused && rays < (1ull << 31) && !(kind == LH_GATHER_AREA && uniforms);
         p.late = p.fused && rays <= LH_LIGHT_LATE_MAX && !(where == LH_GATHER_TILE && sync);
         return p;
     }

@@ -7,7 +7,7 @@
  *                   one way a batch of rays (lh_batch_t) reaches the kernels' launcher (lh_kernels.hip lh_launch_trace)
  *   lh_plan.h       the geometry of a persistent launch (rows, checked pushes, the top of the tree in LDS, workgroups per CU, the cooperative
  *                   walk beside it, the cursor chunk): plain C, read by the launchers, by size_grid and by tests/cpu_model/lh_plan_check.c
- *   lh_gather.h     the kinds of gather stage (AO, dirt, environment, direct light) and its plan -- fused, late -- for a tile or a batch: plain C, read by
+ *   lh_gather.h     the kinds of gather stage (AO, dirt, environment, direct light, area lights) and its plan -- fused, late -- for a tile or a batch: plain C, read by
  *                   lh_tile.hip and by tests/cpu_model/lh_gather_check.c
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
  *   lh_whitted.hip  the refraction chain (the reference's Whitted transport): its bounce kernel, its wavefront loop, its entry points
@@ -175,6 +175,8 @@ struct lh_accel {
     lh_buf b_host, e_host;             /* the staging of lh_accel_ao_host / _dirt_host / _env_host, and of lh_accel_environment_host / _sky_host */
     /* the sun-and-sky light (lh_accel_set_sky; lh_sky.h): sky_set 0 = none, the gather reads the environment */
     lh_sky_src_t sky; int sky_set;
+    /* the emitter table of the area lights (lh_accel_set_emitters; lh_area.h): nemit records of 128 bytes on the device, NULL / 0 = none */
+    void *d_emitters; uint64_t nemit;
     /* the refraction chain (lh_whitted.hip; lh_whitted.h): the chain's compacted rays, ids and records, sized by list entries; its counts (one per depth);
      * the tile's camera rays, their records and the samples' colours; lh_accel_whitted_host's staging */
     lh_buf w_chain, w_counts, w_tile, w_host;
@@ -362,6 +364,7 @@ typedef struct lh_gather_left {
     double near_clip, far_clip, scale;
     const lh_env_src_t *env; const lh_sky_src_t *sky; const uint8_t *sun_occ;
     const lh_light_t *lights;          /* LH_GATHER_LIGHT: the HOST table of ntheta lights (nphi is 1); occ holds the byte of every item, hitrec the records */
+    const struct lh_area_tab *area;    /* LH_GATHER_AREA: the call's lights, emitter table, bound and replayed uniforms (lh_area.h; HOST memory; ntheta = its S, nphi = its L); occ, hitrec and key as above */
     unsigned long long *total;
 } lh_gather_left_t;
 /* a region of w x h pixels (h = nbands * band_rows lines), xs * ys samples each, with the hit slot of every sample; tex or NULL: no mesh has a texture */
@@ -378,6 +381,10 @@ extern "C" int lh_render_launch_sun_rays(size_t nslots, const unsigned long long
                                          double *d_org, double *d_dir, void *stream);
 extern "C" int lh_render_launch_light_rays(size_t nslots, const unsigned long long *d_nslots, const lh_light_t *lights, int n, const double *d_hitrec,
                                            double *d_org, double *d_dir, double *d_tmax, void *stream);
+/* the rays, bounds and (d_weight or NULL) weights of nslots hit records' area-light items (lh_area.h), item (slot, l, s) at element (slot * L + l) * S + s */
+extern "C" int lh_render_launch_area_rays(size_t nslots, const unsigned long long *d_nslots, const struct lh_area_tab *area, unsigned long long seed,
+                                          const double *d_hitrec, const unsigned long long *d_slot_key, double *d_org, double *d_dir, double *d_tmax,
+                                          double *d_weight, void *stream);
 extern "C" int lh_render_launch_state_build(size_t n, const lh_dev_scene_t *sc, const double *d_nrm9, const double *d_col9,
                                             const double *d_tan9, const double *d_bin9, const double *d_st6, const uint8_t *d_inside,
                                             const double *d_org, const double *d_dir, const uint32_t *d_prim, const double *d_t,

@@ -57,6 +57,7 @@
 #include "lh_tmax.h"
 #include "lh_ao.h"
 #include "lh_lights.h"
+#include "lh_area.h"
 
 namespace {
 
@@ -506,6 +507,8 @@ __global__ __launch_bounds__(LH_BLOCK) void k_trace_direct(
  * the reference's own walk.
  * SRC 3 (any-hit, bounded): the work items are the shadow rays of a batch of hits to a list of lights (lh_lights.h) -- item i = (hit slot i / L, light
  * i % L) -- made in the refill from the hit record and the light table; an item that is not traced stores its byte there and never starts a walk.
+ * SRC 4 (any-hit, bounded): the items of the area-light stage (lh_area.h) -- item i = (slot * L + l) * S + s -- made in the refill from the hit record, three
+ * uniforms of the keyed generator and ONE gathered emitter record (a dependent load: the record is one aligned 128-byte line); else as SRC 3.
  * WALK 3: traverse_spec4 (the default); 8: the same with the stack check (trees whose worst case the LDS rows do not
  * cover); 7: traverse_spec8 (8-wide nodes). */
 struct AoSrc {
@@ -521,15 +524,21 @@ struct AoSrc {
     /* the light stage (SRC 3; lh_lights.h): the table of ntheta lights (nphi is 1: item i = slot * ntheta + l, the plain order), in the arguments of the
      * kernels of that stage; no other kernel looks at it */
     const lh_light_t *lights;
+    /* the area-light stage (SRC 4; lh_area.h): the call's lights, emitter table, samples (ntheta = S, nphi = L: item i = (slot * L + l) * S + s) and bound, in the
+     * arguments of the kernels of that stage; no other kernel looks at it */
+    const lh_area_tab_t *area;
 };
 /* ray sources whose rays are made from hit records (AoSrc): their count may live on the device, their answers go where the stage's kind says */
-#define LH_SRC_GATHER(SRC) ((SRC) == 1 || (SRC) == 3)
+#define LH_SRC_GATHER(SRC) ((SRC) == 1 || (SRC) == 3 || (SRC) == 4)
+/* ... and those whose refill makes the whole item and may find that it is not traced (its byte is stored there) */
+#define LH_SRC_ITEM(SRC) ((SRC) == 3 || (SRC) == 4)
 
 /* the bound of ray `id` of a bounded launch: its element of sc.tmax -- or, for the rays a kernel makes itself (SRC 1: the dirt stage), the launch's one bound */
 template <int SRC>
 __device__ __forceinline__ double lane_tmax(const lh_dev_scene_t &sc, const AoSrc &ao, size_t id)
 {
     if (SRC == 3) return (ao.lights[(uint32_t)id % (uint32_t)ao.ntheta].flags & LH_LIGHT_POINT) ? 1.0 : LH_LIGHT_TMAX_INF;      /* of a ray that is traced (lh_lights.h) */
+    if (SRC == 4) return ao.area->bound;          /* of an item that is traced (lh_area.h): the call's one bound */
     return SRC == 1 ? ao.far_clip : ray_tmax(sc, id);
 }
 
@@ -542,6 +551,21 @@ __device__ __forceinline__ double light_src_item(const AoSrc &ao, uint32_t i, do
     const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
     double d[3], w;
     const double tmax = lh_light_item(O, Ns, ao.lights + l, d, &w);
+    ox = O[0]; oy = O[1]; oz = O[2]; dx = d[0]; dy = d[1]; dz = d[2];
+    return tmax;
+}
+
+/* work item i of the area-light stage: sample s of light l for hit slot `slot`, i = (slot * L + l) * S + s, from the slot's hit record and key, the built-in
+ * uniforms and the emitter record they pick; returns the bound it is traced under, 0.0: it is not traced (lh_area_item) */
+__device__ __forceinline__ double area_src_item(const AoSrc &ao, uint32_t i, double &ox, double &oy, double &oz, double &dx, double &dy, double &dz)
+{
+    const lh_area_tab_t *A = ao.area;
+    const uint32_t S = (uint32_t)A->S, LS = (uint32_t)A->L * S, slot = i / LS, r = i - slot * LS, l = r / S, s = r - l * S;
+    const double *h = ao.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
+    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+    double x[3], d[3], w;
+    lh_area_uniforms(ao.slot_key[slot], ao.seed, A->L, A->S, (int)l, (int)s, x);
+    const double tmax = lh_area_item(O, Ns, A->l + l, A->emitters, x, A->bound, d, &w);
     ox = O[0]; oy = O[1]; oz = O[2]; dx = d[0]; dy = d[1]; dz = d[2];
     return tmax;
 }
@@ -587,6 +611,8 @@ __device__ __forceinline__ void src_ray(const lh_dev_scene_t &sc, uint32_t i, co
         selfp = lh_slot_selfprim(key);            /* LH_SLOT_NOSELF matches no primitive id (ids < 2^29) */
     } else if (SRC == 3) {
         (void)light_src_item(ao, i, ox, oy, oz, dx, dy, dz);          /* (a queued ray: it was traced; no self primitive) */
+    } else if (SRC == 4) {
+        (void)area_src_item(ao, i, ox, oy, oz, dx, dy, dz);           /* (the same) */
     } else {
         double o[3], d[3];
         pt_camera_ray((const PtCamSrc *)sc.cam_src, i, o, d);
@@ -765,14 +791,14 @@ __device__ __forceinline__ void trace_persist_lane(
         /* the light stage: an item that is not traced (dark, or without weight: lh_lights.h) leaves its byte here -- no occluder was found -- and its lane
          * takes an item again at the next regroup, as the lane of a skipped id does; a walk never starts with a zero direction */
         double ltmax = 0.0;
-        if (SRC == 3 && newray != kNoRay) {
-            ltmax = light_src_item(ao, newray, ox, oy, oz, dx, dy, dz);
+        if (LH_SRC_ITEM(SRC) && newray != kNoRay) {
+            ltmax = SRC == 4 ? area_src_item(ao, newray, ox, oy, oz, dx, dy, dz) : light_src_item(ao, newray, ox, oy, oz, dx, dy, dz);
             if (!(ltmax > 0.0)) { occ[newray] = (uint8_t)0; newray = kNoRay; }
         }
         if (newray != kNoRay) {
             const uint32_t i = newray;
             my = i;
-            if (SRC != 3) src_ray<SRC, IO>(sc, i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
+            if (!LH_SRC_ITEM(SRC)) src_ray<SRC, IO>(sc, i, org, dir, ao, ox, oy, oz, dx, dy, dz, selfp);
             lane_init(L, sc, ox, oy, oz, dx, dy, dz);
             best.t = LH_T_INF; best.u = 0.0; best.v = 0.0; best.prim = LH_MISS_PRIM; best.frag = 0u;
             stk[0][tid] = kDone;
@@ -780,15 +806,15 @@ __device__ __forceinline__ void trace_persist_lane(
              * dumps whenever it is finite; camera and AO rays (unit vectors) only where a zero-area triangle of |e1|_1 |e2|_1 > 1 stayed in the
              * tree: the bit is set from the DOUBLE cap (lh_danger.h lh_dcap_srcs): the float cap of such a scene may be 1.0f.  Every other scene skips the test whole */
             if (TMAX) {
-                const bool refw = (sc.cap_srcs & (1u << (SRC == 3 ? 0 : SRC))) != 0u && ray_needs_ref_walk(sc, L, dx, dy, dz);      /* asked under the unbounded 1e38f; a shadow ray is no unit vector: the arrays' bit */
-                tmax_start(L, best, SRC == 3 ? ltmax : lane_tmax<SRC>(sc, ao, i));
+                const bool refw = (sc.cap_srcs & (1u << (LH_SRC_ITEM(SRC) ? 0 : SRC))) != 0u && ray_needs_ref_walk(sc, L, dx, dy, dz);      /* asked under the unbounded 1e38f; a shadow ray is no unit vector: the arrays' bit */
+                tmax_start(L, best, LH_SRC_ITEM(SRC) ? ltmax : lane_tmax<SRC>(sc, ao, i));
                 if (__builtin_expect(refw, 0)) LH_FORCE_REF_WALK(L, best);
             } else
             if ((sc.cap_srcs & (1u << SRC)) != 0u && __builtin_expect(ray_needs_ref_walk(sc, L, dx, dy, dz), 0)) LH_FORCE_REF_WALK(L, best);
             it0 = it;
         }
         const unsigned long long work = __ballot((L.cur != kDone) | (pend != 0));
-        if (work == 0ull && (!(IDX || SRC == 3) || exhausted)) break;          /* (an indexed launch, the light stage: a refill whose entries were all skipped leaves a wave without work, not without rays) */
+        if (work == 0ull && (!(IDX || LH_SRC_ITEM(SRC)) || exhausted)) break;          /* (an indexed launch, the light and area stages: a refill whose entries were all skipped leaves a wave without work, not without rays) */
         /* ---- walk until too few lanes remain active ---------------------- */
         const int thresh = exhausted ? 1 : min_active;
         if (WALK == 3)
@@ -905,6 +931,22 @@ __global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_light(
     if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
     copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<true, COUNT, WALK, 3, false, false, true, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
+}
+
+/* the persistent kernel of the fused area-light stage (lh_launch_trace_gather, LH_GATHER_AREA; lh_area.h): the light stage's kernel with ray source 4 -- item
+ * (slot, l, s) made in the refill, walked to ANY hit under the call's bound, its answer a byte at occ[(slot * L + l) * S + s].  The lights, the emitter table's
+ * address, S and the bound travel by value in the kernel's arguments; the table itself is a device block the accelerator owns (lh_accel_set_emitters) */
+template <bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_area(
+    lh_dev_scene_t sc, uint32_t n, uint8_t *__restrict__ occ, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao0, const FixQ fq,
+    const lh_area_tab_t tab)
+{
+    extern __shared__ int lh_stack_lds[];
+    AoSrc ao = ao0;
+    ao.area = &tab;
+    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
+    copy_tree_top(sc, lh_stack_lds);
+    trace_persist_lane<true, COUNT, WALK, 4, false, false, true, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
 /* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
@@ -1232,6 +1274,17 @@ __global__ __launch_bounds__(64) void k_coop_walk_light(lh_dev_scene_t sc, const
     coop_walk_body<true, 3, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
 }
 
+/* the cooperative walk of the fused area-light stage (ray source 4): the light stage's, its ray and bound made again from the item index */
+__global__ __launch_bounds__(64) void k_coop_walk_area(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+                                                       uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
+                                                       double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao0, const FixQ fq,
+                                                       unsigned long long *counters, const uint32_t owner_groups, const lh_area_tab_t tab)
+{
+    AoSrc ao = ao0;
+    ao.area = &tab;
+    coop_walk_body<true, 4, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+}
+
 /* ------------------------------------------------------------------------ */
 /* one scan over the outputs of a ray dump: what is still flagged            */
 /* ------------------------------------------------------------------------ */
@@ -1525,6 +1578,7 @@ auto coop_kernel()
 {
     constexpr bool DIRT = TMAX && SRC == 1 && !ANYHIT;          /* the fused dirt stage */
     if constexpr (SRC == 3) return k_coop_walk_light;          /* the fused light stage */
+    else if constexpr (SRC == 4) return k_coop_walk_area;      /* the fused area-light stage */
     else {
         auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
         if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
@@ -1577,10 +1631,11 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
 struct FusedStage {
     bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; uint8_t *env_occ;
     bool light;          /* the light stage: env_occ is its byte per item */
+    bool area;           /* the area-light stage: the same */
     FusedStage(const lh_dev_scene_t *sc, const lh_fused_out_t &o)
         : dirt(o.kind == LH_GATHER_DIRT), chunk(LH_TILE_CHUNK), occ_count(NULL), group(0), far_clip(dirt ? o.far_clip : 0.0),
-          dirt_t(dirt ? (double *)o.out : NULL), env_occ((o.kind == LH_GATHER_ENV || o.kind == LH_GATHER_LIGHT) ? (uint8_t *)o.out : NULL),
-          light(o.kind == LH_GATHER_LIGHT)
+          dirt_t(dirt ? (double *)o.out : NULL), env_occ((o.kind == LH_GATHER_ENV || o.kind == LH_GATHER_LIGHT || o.kind == LH_GATHER_AREA) ? (uint8_t *)o.out : NULL),
+          light(o.kind == LH_GATHER_LIGHT), area(o.kind == LH_GATHER_AREA)
     {
         static uint32_t ao_chunk = 0;
         if (o.kind != LH_GATHER_AO) return;
@@ -1602,7 +1657,7 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
     lh_dev_scene_t scl = *sc;
     scl.ray_chunk = st.chunk;
     const lh_plan_t p = lh_plan_launch(&scl, n, st.dirt ? LH_PLAN_DIRT : LH_PLAN_AO, LH_VARIANT_SPEC, c.grid_blocks, 1);
-    const AoSrc ao = {g.d_hitrec, g.d_slot_key, st.occ_count, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, st.group, g.d_nslots, g.budget_big, st.far_clip, st.dirt_t, NULL};
+    const AoSrc ao = {g.d_hitrec, g.d_slot_key, st.occ_count, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, st.group, g.d_nslots, g.budget_big, st.far_clip, st.dirt_t, NULL, NULL};
     FixQ fq;
     if (apply_plan(scl, p) != 0) return -1;
     if (st.occ_count && hipMemsetAsync(st.occ_count, 0, sizeof(unsigned int) * g.nslots, s) != hipSuccess) return -1;      /* with the cursors' memset, before the stream's first kernel */
@@ -1638,6 +1693,17 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
         if (hipGetLastError() != hipSuccess) return -1;
         return launch_coop<true, 3, true>(scl, none, ao, fq, p, c, s, tab);
     }
+    if (st.area) {          /* the area-light stage (lh_area.h): ntheta samples of each of nphi lights, the HOST table g.area by value into both kernels */
+        if (!g.area || g.area->L != g.nphi || g.area->S != g.ntheta || g.nphi < 1 || g.nphi > LH_AREA_LIGHTS_MAX || g.ntheta < 1 || !g.area->emitters ||
+            g.area->uniforms) return -1;          /* (replayed uniforms: the materialised stage's) */
+        const lh_area_tab_t tab = *g.area;
+        using area_t = decltype(&k_trace_persist_area<true, LH_WALK_Q4>);
+        const area_t akern[2][2] = {{k_trace_persist_area<true, LH_WALK_Q4_CHECKED>, k_trace_persist_area<false, LH_WALK_Q4_CHECKED>},
+                                    {k_trace_persist_area<true, LH_WALK_Q4>, k_trace_persist_area<false, LH_WALK_Q4>}};
+        LH_LAUNCH_PERSIST(akern[w][k], scl, (uint32_t)n, st.env_occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
+        if (hipGetLastError() != hipSuccess) return -1;
+        return launch_coop<true, 4, true>(scl, none, ao, fq, p, c, s, tab);
+    }
     /* the environment gather (named last: the kernels above keep their order) */
     using env_t = decltype(&k_trace_persist_env<true, LH_WALK_Q4>);
     const env_t ekern[2][2] = {{k_trace_persist_env<true, LH_WALK_Q4_CHECKED>, k_trace_persist_env<false, LH_WALK_Q4_CHECKED>},
@@ -1653,7 +1719,7 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
 extern "C" int lh_launch_trace_gather(const lh_dev_scene_t *sc, const lh_gather_src_t *src, const lh_fused_out_t *out, unsigned long long *d_counters,
                                       const lh_launch_ctx_t *ctx)
 {
-    if ((unsigned)out->kind >= LH_GATHER_KINDS || ((out->kind == LH_GATHER_ENV || out->kind == LH_GATHER_LIGHT) && !out->out)) return -1;
+    if ((unsigned)out->kind >= LH_GATHER_KINDS || ((out->kind == LH_GATHER_ENV || out->kind == LH_GATHER_LIGHT || out->kind == LH_GATHER_AREA) && !out->out)) return -1;
     return launch_fused(sc, *src, FusedStage(sc, *out), d_counters, *ctx);
 }
 

@@ -36,6 +36,7 @@
 #include "lh_env.h"
 #include "lh_sky.h"
 #include "lh_lights.h"
+#include "lh_area.h"
 #include "lh_tex.h"
 
 namespace {
@@ -856,6 +857,95 @@ __global__ __launch_bounds__(256) void k_light_batch_resolve(const BatchList bl,
     wg_total(n, dark_total);
 }
 
+/* ---- area lights (lh_area.h): the light stage's shape with S samples per light -- one byte per item at element (slot * L + l) * S + s; the resolves make every
+ * item's uniforms, sample and weight again (replayed uniforms: read again) and average over the samples.  The table of lights, the emitter table's address, S, the
+ * bound and the uniforms' address are a kernel argument by value ------------------------------------------------------------------------------------------ */
+
+/* the rays, bounds and weights of a materialised stage, and of lh_accel_area_light_rays_device: one thread per item; the bound of an item that is not traced is
+ * 0.0; weight (or NULL): the item's w.  nslots_dev (or NULL): the slot count where it lives on the device, nslots then its upper bound */
+__global__ void k_area_rays(size_t nslots, const unsigned long long *__restrict__ nslots_dev, unsigned long long seed, const double *__restrict__ hitrec,
+                            const unsigned long long *__restrict__ slot_key, double *__restrict__ org, double *__restrict__ dir, double *__restrict__ tmax,
+                            double *__restrict__ weight, const lh_area_tab_t tab)
+{
+    LH_NC
+    const size_t id = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t S = (size_t)tab.S, LS = (size_t)tab.L * S;
+    if (nslots_dev && (size_t)*nslots_dev < nslots) nslots = (size_t)*nslots_dev;
+    if (id >= nslots * LS) return;
+    const size_t slot = id / LS, r = id - slot * LS; const int l = (int)(r / S), sm = (int)(r - (size_t)l * S);
+    const double *h = hitrec + LH_HITREC_DOUBLES * slot;
+    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+    double x[3], d[3], w;
+    lh_area_item_uniforms(tab.uniforms ? tab.uniforms + 3 * LS * slot : NULL, slot_key[slot], seed, tab.L, tab.S, l, sm, x);
+    const double tm = lh_area_item(O, Ns, tab.l + l, tab.emitters, x, tab.bound, d, &w);
+    org[3 * id] = O[0]; org[3 * id + 1] = O[1]; org[3 * id + 2] = O[2];
+    dir[3 * id] = d[0]; dir[3 * id + 1] = d[1]; dir[3 * id + 2] = d[2];
+    tmax[id] = tm;
+    if (weight) weight[id] = w;
+}
+
+/* what the two resolves share: the hit records, the keys, the seed, the bytes */
+struct AreaGather { const double *hitrec; const unsigned long long *key; unsigned long long seed; const uint8_t *occ; };
+
+/* the mask and value of a hit slot, and how many of its L S items are not open */
+__device__ __forceinline__ uint32_t area_slot(const AreaGather &g, const lh_area_tab_t &tab, uint32_t slot, float val[3], unsigned int &closed)
+{
+    LH_NC
+    const size_t LS = (size_t)tab.L * (size_t)tab.S;
+    const double *h = g.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
+    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+    return lh_area_value(O, Ns, tab.l, tab.L, tab.S, tab.emitters, tab.bound, tab.uniforms ? tab.uniforms + 3 * LS * (size_t)slot : NULL, g.key[slot], g.seed,
+                         g.occ + (size_t)slot * LS, val, &closed);
+}
+
+/* k_light_resolve for the area-light tile, a thread per pixel */
+__global__ __launch_bounds__(256) void k_area_resolve(int w, int h, int band_rows, int xs, int ys, const AreaGather g, const uint32_t *__restrict__ slot_of_sample,
+                                                      float *__restrict__ rgb, unsigned long long *__restrict__ dark_total, const lh_area_tab_t tab)
+{
+    LH_NC
+    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool inside = pix < (size_t)w * h;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    unsigned int n = 0;
+    const int S = inside ? xs * ys : 0;
+    for (int s = 0; s < S; s++) {
+        const uint32_t slot = slot_of_sample[pix * S + s];
+        float val[3] = {0.0f, 0.0f, 0.0f};
+        if (slot != LH_MISS_PRIM) { unsigned int c; (void)area_slot(g, tab, slot, val, c); n += c; }
+        a0 = a0 + (double)val[0]; a1 = a1 + (double)val[1]; a2 = a2 + (double)val[2];
+    }
+    if (inside) {
+        const double inv = (double)1.0 / (xs * ys);
+        float f0 = (float)(a0 * inv), f1 = (float)(a1 * inv), f2 = (float)(a2 * inv);
+        if (f0 < 0.0f) f0 = 0.0f;
+        if (f1 < 0.0f) f1 = 0.0f;
+        if (f2 < 0.0f) f2 = 0.0f;
+        float *o = pixel_out(rgb, pix, w, band_rows);
+        o[0] = f0; o[1] = f1; o[2] = f2;
+    }
+    wg_total(n, dark_total);
+}
+
+/* k_light_batch_resolve for the area-light stage, a thread per list entry */
+__global__ __launch_bounds__(256) void k_area_batch_resolve(const BatchList bl, const AreaGather g, const uint32_t *__restrict__ slot_of_entry,
+                                                            uint32_t *__restrict__ visible, float *__restrict__ rgb,
+                                                            unsigned long long *__restrict__ dark_total, const lh_area_tab_t tab)
+{
+    LH_NC
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    uint32_t id = 0;
+    unsigned int n = 0;
+    if (batch_entry(bl, k, id)) {
+        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
+        uint32_t mask = LH_AO_NO_HIT;
+        float val[3] = {0.0f, 0.0f, 0.0f};
+        if (slot != LH_AO_NO_HIT) mask = area_slot(g, tab, slot, val, n);
+        if (visible) visible[id] = mask;
+        if (rgb) { rgb[3 * (size_t)id] = val[0]; rgb[3 * (size_t)id + 1] = val[1]; rgb[3 * (size_t)id + 2] = val[2]; }
+    }
+    wg_total(n, dark_total);
+}
+
 
 /* ---- the whole hit epilogue for a batch of hit records --------------------------------------
  * ri_intersection_state_build (intersection_state.c:99-248), every member a shader reads: P, Ng, Ns, tangent,
@@ -1317,6 +1407,11 @@ extern "C" int lh_render_launch_tile_resolve(const lh_resolve_tile_t *to, const 
         if (light_tab(g->lights, N, &tab) != 0) return -1;
         hipLaunchKernelGGL(k_light_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, LightGather{N, g->hitrec, g->occ}, to->slot_of_sample, to->rgb, g->total, tab);
         break;
+    case LH_GATHER_AREA:
+        if (!g->area || g->area->L != g->nphi || g->area->S != g->ntheta) return -1;
+        hipLaunchKernelGGL(k_area_resolve, grid, block, 0, s, w, h, band_rows, xs, ys, AreaGather{g->hitrec, g->key, g->seed, g->occ}, to->slot_of_sample, to->rgb,
+                           g->total, *g->area);
+        break;
     default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1347,6 +1442,11 @@ extern "C" int lh_render_launch_list_resolve(const lh_resolve_list_t *to, const 
     case LH_GATHER_LIGHT:
         if (light_tab(g->lights, N, &tab) != 0) return -1;
         hipLaunchKernelGGL(k_light_batch_resolve, grid, block, 0, s, bl, LightGather{N, g->hitrec, g->occ}, to->slot_of_entry, to->count_out, to->value_out, g->total, tab);
+        break;
+    case LH_GATHER_AREA:
+        if (!g->area || g->area->L != g->nphi || g->area->S != g->ntheta) return -1;
+        hipLaunchKernelGGL(k_area_batch_resolve, grid, block, 0, s, bl, AreaGather{g->hitrec, g->key, g->seed, g->occ}, to->slot_of_entry, to->count_out,
+                           to->value_out, g->total, *g->area);
         break;
     default: return -1;
     }
@@ -1420,6 +1520,20 @@ extern "C" int lh_render_launch_light_rays(size_t nslots, const unsigned long lo
     const size_t items = nslots * (size_t)n;
     if ((items + 255) / 256 > 0x7fffffffu) return -1;
     hipLaunchKernelGGL(k_light_rays, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nslots, d_nslots, n, d_hitrec, d_org, d_dir, d_tmax, tab);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the rays, bounds and weights (d_weight or NULL) of nslots hit records' area-light items (d_nslots or NULL: the slot count on the device, nslots its upper bound) */
+extern "C" int lh_render_launch_area_rays(size_t nslots, const unsigned long long *d_nslots, const lh_area_tab_t *area, unsigned long long seed,
+                                          const double *d_hitrec, const unsigned long long *d_slot_key, double *d_org, double *d_dir, double *d_tmax,
+                                          double *d_weight, void *stream)
+{
+    if (nslots == 0) return 0;
+    if (!area || area->L < 1 || area->L > LH_AREA_LIGHTS_MAX || area->S < 1 || area->S > LH_AREA_SAMPLES_MAX || !area->emitters) return -1;
+    const size_t items = nslots * (size_t)area->L * (size_t)area->S;
+    if ((items + 255) / 256 > 0x7fffffffu) return -1;
+    hipLaunchKernelGGL(k_area_rays, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nslots, d_nslots, seed, d_hitrec, d_slot_key,
+                       d_org, d_dir, d_tmax, d_weight, *area);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

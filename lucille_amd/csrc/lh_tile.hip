@@ -14,6 +14,7 @@
 #include "lh_env.h"
 #include "lh_sky.h"
 #include "lh_lights.h"
+#include "lh_area.h"
 
 #define ensure_buf lh_ensure_buf
 
@@ -77,11 +78,13 @@ static int stage_report(const stage_timer &tm, const void *d_clk, size_t nwaves,
 
 /* ---- the gather stage: one description of its transport ------------------------------------------------------------------------------------
  * The kind (LH_GATHER_*, lh_gather.h) with its checked parameters, as the entry points hand it on: AO has none and offsets its rays by 1e-6 along Ns */
-struct gather_params { int kind; double eps; lh_dirt_params_t dirt; lh_env_params_t env; const lh_light_t *lights; int nlights; };          /* lights: LH_GATHER_LIGHT, the caller's HOST table (lh_lights.h) */
+struct gather_params { int kind; double eps; lh_dirt_params_t dirt; lh_env_params_t env; const lh_light_t *lights; int nlights;          /* lights: LH_GATHER_LIGHT, the caller's HOST table (lh_lights.h) */
+                       lh_area_tab_t area; };          /* LH_GATHER_AREA: the caller's lights, the accelerator's emitter table, S, the bound (lh_area.h) */
 /* the sample grid of a stage: the hemisphere's -- or, for the light stage, one "sample" per light: ntheta = the lights, nphi = 1, so that work item
  * slot * N + r is item (slot, l = r) in every kernel and buffer the stage shares with the gathers */
 static inline ao_grid gather_grid(const gather_params &p, int gather_nsamples)
 {
+    if (p.kind == LH_GATHER_AREA) return ao_grid{p.area.L, p.area.S, p.area.L * p.area.S};          /* r = l * S + s: "nphi" lights of "ntheta" samples each */
     return p.kind == LH_GATHER_LIGHT ? ao_grid{1, p.nlights, p.nlights} : ao_sample_grid(gather_nsamples);
 }
 /* ... and what ao_region / ao_batch_device make of it, once, at their top, for the stage and the resolves: the scratch entry of the kind and the caller
@@ -96,8 +99,10 @@ struct gather_desc {
     lh_tex_args_t tex_store; const lh_tex_args_t *tex;
     const char *prefix;
 };
-static const char *const gather_device_name[LH_GATHER_KINDS] = {"lh_accel_ao_device", "lh_accel_dirt_device", "lh_accel_env_device", "lh_accel_lights_device"};
-static const char *const gather_prefix[LH_GATHER_KINDS] = {"lh_accel_ao_device: ", "lh_accel_dirt_device: ", "lh_accel_env_device: ", "lh_accel_lights_device: "};
+static const char *const gather_device_name[LH_GATHER_KINDS] = {"lh_accel_ao_device", "lh_accel_dirt_device", "lh_accel_env_device", "lh_accel_lights_device",
+                                                                   "lh_accel_area_lights_device"};
+static const char *const gather_prefix[LH_GATHER_KINDS] = {"lh_accel_ao_device: ", "lh_accel_dirt_device: ", "lh_accel_env_device: ", "lh_accel_lights_device: ",
+                                                              "lh_accel_area_lights_device: "};
 
 static void gather_describe(lh_accel_t *a, const gather_params &p, int where, gather_desc *d)
 {
@@ -120,7 +125,7 @@ static lh_gather_left_t gather_left(const gather_desc &d, ao_grid g, uint64_t se
     l.occ_count = fused ? (const unsigned int *)b->occcount.p : NULL; l.occ = (const uint8_t *)b->occ.p; l.t = (const double *)b->t.p;
     l.hitrec = (const double *)b->hitrec.p; l.key = (const unsigned long long *)b->key.p; l.adir = fused ? NULL : (const double *)b->adir.p;
     l.near_clip = d.p.dirt.near_clip; l.far_clip = d.p.dirt.far_clip; l.scale = d.p.env.scale;
-    l.env = &d.esrc; l.sky = d.sky; l.sun_occ = sun_occ; l.lights = d.p.lights; l.total = total;
+    l.env = &d.esrc; l.sky = d.sky; l.sun_occ = sun_occ; l.lights = d.p.lights; l.area = d.p.kind == LH_GATHER_AREA ? &d.p.area : NULL; l.total = total;
     return l;
 }
 
@@ -132,7 +137,9 @@ static lh_gather_left_t gather_left(const gather_desc &d, ao_grid g, uint64_t se
  *   DIRT  (lh_dirt.h) the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), a double at element slot * N + r of t;
  *   LIGHT (lh_lights.h; N = the lights) the bounded any-hit byte of shadow ray (slot, l) at element slot * N + l of occ, 0 for an item that is not traced:
  *         fused, the persistent walk makes the item in its refill; materialised, one kernel writes rays and bounds and one bounded any-hit launch per
- *         LH_DIRT_CHUNK rays answers them.
+ *         LH_DIRT_CHUNK rays answers them;
+ *   AREA  (lh_area.h; N = lights x samples) the same byte for item (slot, l, s) at element slot * N + l * S + s: fused, ray source 4 makes the item in the
+ *         refill; materialised -- also with replayed uniforms, which the ray kernel reads from memory -- the light stage's two steps.
  * plan.fused: the kernel generates ray (slot, r) in its refill (lh_ao.h) -- nothing per gather ray goes through HBM but what is left
  * (lh_launch_trace_gather).  Else, and as the second try of a fused launch whose fix-up queue overflowed, materialised: gather rays in HBM (from
  * d_uniforms if given: the parity replay), then an any-hit batch, or for DIRT ONE bounded closest-hit launch per LH_DIRT_CHUNK rays through the ray
@@ -165,6 +172,7 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
     case LH_GATHER_AO:  left = &b->occcount; slot_bytes = sizeof(unsigned int); fused_name = "fused AO"; break;                    /* a count per slot */
     case LH_GATHER_ENV: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused environment-gather"; break;                    /* a byte per ray */
     case LH_GATHER_LIGHT: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused light"; break;                               /* a byte per shadow ray */
+    case LH_GATHER_AREA: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused area-light"; break;                           /* the same, N = L x S */
     default:            left = &b->t; slot_bytes = (size_t)N * 8; fused_name = "fused dirt"; bounded = true; break;                /* DIRT: a double per ray */
     }
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
@@ -221,7 +229,7 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
         if (!late && big && nhit * N >= (1ull << 27)) sc.ray_budget = big;
         budget = sc.ray_budget;
         const lh_gather_src_t src = {nslots, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                                     late ? d_nhit : NULL, late ? big : 0u, d.p.lights};
+                                     late ? d_nhit : NULL, late ? big : 0u, d.p.lights, d.p.kind == LH_GATHER_AREA ? &d.p.area : NULL};
         const lh_launch_ctx_t ctx = {lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, (void *)s};
         const lh_fused_out_t fo = {d.p.kind, left->p, d.p.dirt.far_clip};
         if (lh_launch_trace_gather(&sc, &src, &fo, cnt, &ctx) != 0)
@@ -236,8 +244,13 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
         const size_t nao = (size_t)(nhit * N);
         if (!nao) return 0;
         if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!bounded && ensure_buf(&b->occ, nao))) return -1;
-        if (d.p.kind == LH_GATHER_LIGHT) {          /* 4-5. the light stage: rays and a bound per ray, then bounded any-hit launches through the ray dumps' kernels */
+        if (d.p.kind == LH_GATHER_LIGHT || d.p.kind == LH_GATHER_AREA) {          /* 4-5. the light and area stages: rays and a bound per ray, then bounded any-hit launches through the ray dumps' kernels */
             if (ensure_buf(&b->bound, nao * 8)) return -1;
+            if (d.p.kind == LH_GATHER_AREA) {
+                if (lh_render_launch_area_rays((size_t)nhit, NULL, &d.p.area, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                                               (double *)b->aorg.p, (double *)b->adir.p, (double *)b->bound.p, NULL, s) != 0)
+                    return fail("%sarea-light ray kernel launch failed", prefix);
+            } else
             if (lh_render_launch_light_rays((size_t)nhit, NULL, d.p.lights, d.p.nlights, (const double *)b->hitrec.p, (double *)b->aorg.p, (double *)b->adir.p,
                                             (double *)b->bound.p, s) != 0)
                 return fail("%slight ray kernel launch failed", prefix);
@@ -324,11 +337,15 @@ static int env_params(const char *what, const lh_env_params_t *params, lh_env_pa
 /* what the light stage's entry points hand to gather_check as `params`: the caller's list and its parameters (NULL: LH_LIGHTS_DEFAULTS) */
 struct lights_in { const lh_light_t *lights; int nlights; const lh_lights_params_t *params; };
 
+/* what the area-light stage's entry points hand to gather_check: the caller's list, its parameters (NULL: LH_AREA_DEFAULTS) and the accelerator whose
+ * emitter table the runs must lie in (NULL, or no table: none does) */
+struct area_in { const lh_area_light_t *lights; int nlights; const lh_area_params_t *params; const lh_accel_t *a; };
+
 /* the kind of an entry point and its caller's parameters (NULL: the defaults; AO has none), checked */
 static int gather_check(const char *what, int kind, const void *params, gather_params *p)
 {
     const lh_env_params_t env_def = LH_ENV_DEFAULTS;
-    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def, NULL, 0};
+    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def, NULL, 0, {}};
     if (kind == LH_GATHER_DIRT) {
         if (dirt_params(what, (const lh_dirt_params_t *)params, &p->dirt) != 0) return -1;
         p->eps = p->dirt.eps;
@@ -345,6 +362,20 @@ static int gather_check(const char *what, int kind, const void *params, gather_p
             return fail("%s: bad lights (1 .. %d lights in host memory, every v and rgb finite, a directional v not zero, flags within POINT | COSINE | INVSQ, "
                         "INVSQ only with POINT, reserved 0; eps %g finite and >= 0)", what, LH_LIGHTS_MAX, p->eps);
         p->lights = in->lights; p->nlights = in->nlights;
+    }
+    if (kind == LH_GATHER_AREA) {
+        const area_in *in = (const area_in *)params;
+        const lh_area_params_t def = LH_AREA_DEFAULTS, prm = in->params ? *in->params : def;
+        const uint64_t table = in->a ? in->a->nemit : 0;
+        if (!lh_area_lights_ok(in->lights, in->nlights, &prm, table))
+            return fail("%s: bad area lights (1 .. %d lights in host memory, every rgb finite, flags within COSINE | FACING | INVSQ | PDF, reserved 0, ntris >= 1 "
+                        "and first_tri + ntris within the %llu triangles of lh_accel_set_emitters; eps %g finite and >= 0, 0 < bound %g <= 1, nsamples %d in "
+                        "1 .. %d, reserved 0)", what, LH_AREA_LIGHTS_MAX, (unsigned long long)table, prm.eps, prm.bound, (int)prm.nsamples, LH_AREA_SAMPLES_MAX);
+        p->eps = prm.eps;
+        memset(&p->area, 0, sizeof(p->area));
+        memcpy(p->area.l, in->lights, sizeof(lh_area_light_t) * (size_t)in->nlights);
+        p->area.emitters = (const lh_emitter_t *)in->a->d_emitters; p->area.uniforms = NULL; p->area.bound = prm.bound;
+        p->area.L = in->nlights; p->area.S = prm.nsamples;
     }
     return 0;
 }
@@ -379,7 +410,7 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     }
     if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
     /* material textures (lh_tex.h): with at least one set, the resolve multiplies; with none, tex is NULL and the launch is the one it always was */
-    const bool no_tex = d.sky || p.kind == LH_GATHER_LIGHT;          /* neither the sun-and-sky gather nor direct light fetches a texture */
+    const bool no_tex = d.sky || p.kind == LH_GATHER_LIGHT || p.kind == LH_GATHER_AREA;          /* neither the sun-and-sky gather nor direct light fetches a texture */
     if (a->ntex && !no_tex && lh_tex_sync(a) != 0) return -1;
     d.tex = no_tex ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &d.tex_store);
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
@@ -408,7 +439,7 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of the resolve's 64 counters */
     /* 6. the samples' values into the pixels */
     const lh_resolve_tile_t to = {w, h, band_rows, ps, ps, (const uint32_t *)b->slot.p, (float *)d_rgb, d.tex};
-    static const char *const resolve_name[LH_GATHER_KINDS] = {"resolve", "dirt resolve", "environment-gather resolve", "light resolve"};
+    static const char *const resolve_name[LH_GATHER_KINDS] = {"resolve", "dirt resolve", "environment-gather resolve", "light resolve", "area-light resolve"};
     auto resolve = [&](const lh_gather_left_t &left) -> int {
         if (lh_render_launch_tile_resolve(&to, &left, s) != 0) return fail("%s kernel launch failed", d.sky ? "sun-and-sky resolve" : resolve_name[p.kind]);
         return 0;
@@ -442,7 +473,7 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     if (p.kind == LH_GATHER_AO) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
     if (cnt) {
         /* (the light stage counts its work items, traced or not: the camera rays and hits x lights) */
-        lh_stat_add(a, tot.cnt, p.kind == LH_GATHER_LIGHT ? (unsigned long long)S + nao : tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
+        lh_stat_add(a, tot.cnt, (p.kind == LH_GATHER_LIGHT || p.kind == LH_GATHER_AREA) ? (unsigned long long)S + nao : tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
             fprintf(stderr, "[lucille_hip] AO batch: rays by node visits (bucket b: [2^(b-1), 2^b)):");
             for (int k = 0; k < 24; k++) fprintf(stderr, " %llu", tot.cnt[LH_CNT_HIST + k]);
@@ -585,6 +616,7 @@ static int ao_batch_device(const char *what, lh_accel_t *a, const gather_params 
     const ao_grid g = gather_grid(p, gather_nsamples);
     gather_desc d;
     gather_describe(a, p, LH_GATHER_BATCH, &d);
+    if (p.kind == LH_GATHER_AREA) d.p.area.uniforms = (const double *)d_uniforms;          /* the ray kernel and the resolve read them: 3 per item */
     lh_gather_scratch *b = d.b;
     if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65)) return -1;
     unsigned long long *d_nhit = (unsigned long long *)b->totals.p, *d_nocc = d_nhit + 1;      /* the hits; the resolve's 64 counters */
@@ -619,7 +651,7 @@ static int ao_batch_device(const char *what, lh_accel_t *a, const gather_params 
     };
     ao_totals tot;
     if (ao_stage(a, d, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, plan, resolve, s, &tot) != 0) return -1;
-    if (cnt) lh_stat_add(a, tot.cnt, p.kind == LH_GATHER_LIGHT ? tot.nhit * (unsigned long long)g.N : tot.cnt[LH_CNT_RAYS], tot.nocc, true);      /* (the light stage counts its work items, traced or not) */
+    if (cnt) lh_stat_add(a, tot.cnt, (p.kind == LH_GATHER_LIGHT || p.kind == LH_GATHER_AREA) ? tot.nhit * (unsigned long long)g.N : tot.cnt[LH_CNT_RAYS], tot.nocc, true);      /* (the light stage counts its work items, traced or not) */
     if (cnt && p.kind != LH_GATHER_AO) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
     return 0;
 }
@@ -720,11 +752,11 @@ static int gather_batch_host(const char *what, int kind, const void *params, lh_
     if (go <= 0) return go;
     if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
     const size_t n = n_rays;
-    const size_t need = uniforms ? (size_t)2 * gather_grid(p, gather_nsamples).N * n : 0;          /* worst case: every ray hits */
+    const size_t need = uniforms ? (size_t)(kind == LH_GATHER_AREA ? 3 : 2) * gather_grid(p, gather_nsamples).N * n : 0;          /* worst case: every ray hits */
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t nrad = (kind == LH_GATHER_ENV || kind == LH_GATHER_LIGHT) ? 3 * n : n;          /* floats of `radiance` */
+    const size_t nrad = (kind == LH_GATHER_ENV || kind == LH_GATHER_LIGHT || kind == LH_GATHER_AREA) ? 3 * n : n;          /* floats of `radiance` */
     if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 2 * sizeof(uint32_t) * n + sizeof(float) * nrad)) return -1;
     double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
     double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
@@ -837,6 +869,115 @@ extern "C" int lh_accel_light_rays_device(lh_accel_t *a, size_t n_rays, const vo
     if (lh_render_launch_light_rays(n_rays, d_nhit, p.lights, p.nlights, (const double *)b->hitrec.p, (double *)d_org_out, (double *)d_dir_out,
                                     (double *)d_tmax_out, s) != 0)
         return fail("%s: light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+/* ---- area lights (lh_area.h): the light stage's pipeline with S samples per light, the AO stage's seed, keys and replayed uniforms ---- */
+
+/* the emitter table: records made on the host (lh_area_emitter), one block on the device that the accelerator owns.  A block that is replaced or removed
+ * is released behind a device-wide synchronise, as a texture's (lh_tex.hip): every launch enqueued earlier that may read it has finished.  Nothing of a
+ * commit or re-commit touches it */
+extern "C" int lh_accel_set_emitters(lh_accel_t *a, const double *tri_xyz, size_t ntris)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_set_emitters";
+    const bool remove = !tri_xyz && ntris == 0;
+    if (!remove) {          /* the array first: refused whatever the accelerator is, before anything touches a device */
+        if (!tri_xyz || ntris == 0) return fail("%s: bad emitters (a NULL array with a count, or an array of no triangles)", what);
+        if ((uint64_t)ntris >= LH_AREA_EMITTERS_MAX) return fail("%s: bad emitters (%zu triangles: fewer than 2^31)", what, ntris);
+        if (((uintptr_t)tri_xyz & 7u) != 0) return fail("%s: bad emitters (vertices are doubles: the pointer is not 8-byte aligned)", what);
+        for (size_t k = 0; k < 9 * ntris; k++)
+            if (!lh_area_fin(tri_xyz[k])) return fail("%s: bad emitters (triangle %zu has a vertex that is not finite)", what, k / 9);
+    }
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    HIPCHK(hipSetDevice(a->device));
+    void *d_new = NULL;
+    if (!remove) {
+        lh_emitter_t *rec = (lh_emitter_t *)malloc(sizeof(lh_emitter_t) * ntris);
+        if (!rec) return fail("%s: out of memory", what);
+        for (size_t k = 0; k < ntris; k++) lh_area_emitter(tri_xyz + 9 * k, rec + k);
+        hipError_t e = hipMalloc(&d_new, sizeof(lh_emitter_t) * ntris);          /* (256-byte aligned: every record is one line) */
+        if (e == hipSuccess) e = hipMemcpy(d_new, rec, sizeof(lh_emitter_t) * ntris, hipMemcpyHostToDevice);
+        free(rec);
+        if (e != hipSuccess) { (void)hipGetLastError(); if (d_new) (void)hipFree(d_new); return fail("%s: uploading the table failed: %s", what, hipGetErrorString(e)); }
+    }
+    if (a->d_emitters) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(a->d_emitters); }
+    a->d_emitters = d_new; a->nemit = remove ? 0 : (uint64_t)ntris;
+    return 0;
+}
+
+extern "C" int lh_accel_area_lights_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                           const void *d_u, const void *d_v, const lh_area_light_t *lights, int nlights, const lh_area_params_t *params,
+                                           uint64_t seed, const void *d_key, const void *d_uniforms, const void *d_index, size_t n_index, const void *d_count,
+                                           void *d_visible, void *d_rgb, void *stream)
+{
+    lh_guard guard(a);          /* (recursive: the table's count is read under the lock the stage then holds) */
+    const area_in in = {lights, nlights, params, a};
+    return gather_batch_device("lh_accel_area_lights_device", LH_GATHER_AREA, &in, a, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, 1, seed, d_key, d_uniforms,
+                               d_index, n_index, d_count, d_visible, d_rgb, stream);
+}
+
+extern "C" int lh_accel_area_lights_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
+                                         const double *u, const double *v, const lh_area_light_t *lights, int nlights, const lh_area_params_t *params,
+                                         uint64_t seed, const uint64_t *key, const double *uniforms, size_t nuniforms, uint32_t *visible, float *rgb)
+{
+    lh_guard guard(a);
+    const area_in in = {lights, nlights, params, a};
+    return gather_batch_host("lh_accel_area_lights_host", LH_GATHER_AREA, &in, a, n_rays, org, dir, prim, t, u, v, 1, seed, key, uniforms, nuniforms, visible, rgb);
+}
+
+extern "C" int lh_render_area_lights_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int ps, const lh_area_light_t *lights, int nlights,
+                                          const lh_area_params_t *params, uint64_t seed, void *d_rgb, lh_tile_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);
+    const area_in in = {lights, nlights, params, a};
+    return gather_tile("lh_render_area_lights_tile", LH_GATHER_AREA, &in, a, cam, x0, y0, w, h, ps, 1, seed, NULL, d_rgb, stats, stream);
+}
+
+/* the rays alone, shaped like lh_accel_light_rays_device: the compaction's slots and count, then item (slot, l, s) with its bound and weight at element
+ * (slot * L + l) * S + s.  Asynchronous: the lights travel in the ray kernel's arguments, nothing is read back */
+extern "C" int lh_accel_area_light_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                               const void *d_u, const void *d_v, const lh_area_light_t *lights, int nlights, const lh_area_params_t *params,
+                                               uint64_t seed, const void *d_key, const void *d_uniforms, void *d_slot_of_ray, void *d_nslots,
+                                               void *d_org_out, void *d_dir_out, void *d_tmax_out, void *d_weight_out, size_t capacity_rays, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_area_light_rays_device";
+    const area_in in = {lights, nlights, params, a};
+    gather_params p;
+    if (gather_check(what, LH_GATHER_AREA, &in, &p) != 0) return -1;
+    if ((((uintptr_t)d_org_out | (uintptr_t)d_dir_out | (uintptr_t)d_tmax_out | (uintptr_t)d_weight_out) & 7u) != 0)
+        return fail("%s: the ray, bound and weight arrays are doubles: a pointer is not 8-byte aligned", what);
+    const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, 1, d_key, d_uniforms, NULL, 0, NULL, d_slot_of_ray, d_nslots);
+    if (go < 0) return go;
+    hipStream_t s = (hipStream_t)stream;
+    if (go == 0) {
+        if (d_nslots) { HIPCHK(hipSetDevice(a->device)); HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s)); }
+        return 0;
+    }
+    if (!d_slot_of_ray || !d_nslots || !d_org_out || !d_dir_out || !d_tmax_out) return fail("%s: NULL output array", what);
+    const size_t LS = (size_t)p.area.L * (size_t)p.area.S;
+    if (capacity_rays / LS < n_rays) return fail("%s: capacity_rays %zu does not cover the worst case n_rays * nlights * nsamples = %zu x %zu", what, capacity_rays, n_rays, LS);
+    HIPCHK(hipSetDevice(a->device));
+    if (a->hs->bvh.ntris == 0) {
+        HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
+        HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s));
+        return 0;
+    }
+    const unsigned nb = (unsigned)((n_rays + 255) / 256);
+    lh_gather_scratch *b = &a->gather[LH_GATHER_AREA][LH_GATHER_BATCH];
+    if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65) || ensure_buf(&b->blocks, (size_t)nb * 4) ||
+        ensure_buf(&b->hitrec, n_rays * 96) || ensure_buf(&b->key, n_rays * 8)) return -1;
+    unsigned long long *d_nhit = (unsigned long long *)b->totals.p;
+    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
+                                       (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
+                                       (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)d_slot_of_ray,
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, p.eps, s) != 0)
+        return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
+    p.area.uniforms = (const double *)d_uniforms;
+    if (lh_render_launch_area_rays(n_rays, d_nhit, &p.area, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p, (double *)d_org_out,
+                                   (double *)d_dir_out, (double *)d_tmax_out, (double *)d_weight_out, s) != 0)
+        return fail("%s: area-light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
     return 0;
 }
 
