@@ -5,6 +5,7 @@ accel_intersect_func (lucille src/render/accel.h:24-34) -- see the header for
 the per-function mapping.  No compute happens in Python.
 """
 import atexit
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -960,36 +961,37 @@ class HipAccel:
                                              C.c_void_p(stream)), "lh_render_primary_rays")
         return org, dr
 
-    def _render_gather_tile(self, name, params, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream):
-        """render_ao_tile / _dirt_tile / _env_tile: the C function `name`; params: () for the AO tile, else (the caller's params or None,)"""
+    def _render_gather_tile(self, kind, params, lights, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream):
+        """the five tiles: the row of _BATCH_STAGES, its params and light list, and the call"""
         import torch
+        sg = self._BATCH_STAGES[kind]
+        params, pargs, _ = self._stage_args("render_%s_tile" % kind, sg, params, lights)
         dev = torch.device("cuda", self.device)
         if out is None:
             out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
         st = TileStats()
-        params = tuple(None if p is None else C.byref(p) for p in params)
-        _check(getattr(self.L, name)(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, gather_nsamples, *params, int(seed),
-                                     _dptr(uniforms), _dptr(out), C.byref(st), C.c_void_p(stream)), name)
+        mid = self._stage_mid(sg, gather_nsamples, pargs, (int(seed),)) + (() if sg.pack else (_dptr(uniforms),))
+        _check(getattr(self.L, sg.tile)(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, *mid, _dptr(out), C.byref(st), C.c_void_p(stream)), sg.tile)
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def render_ao_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed=1, uniforms=None, out=None,
                        stream=None):
         """-> (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict)"""
-        return self._render_gather_tile("lh_render_ao_tile", (), cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
+        return self._render_gather_tile("ao", None, None, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
 
     def render_dirt_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, params=None, seed=1, uniforms=None, out=None,
                          stream=None):
         """lh_render_dirt_tile: the dirtmap transport's tile (params: a DirtParams, None: the defaults) ->
         (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x N, ao_occluded = the bounded hits)"""
-        return self._render_gather_tile("lh_render_dirt_tile", (params,), cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
+        return self._render_gather_tile("dirt", params, None, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
 
     def render_env_tile(self, cam, x0, y0, w, h, pixel_samples, gather_nsamples, params=None, seed=1, uniforms=None, out=None,
                         stream=None):
         """lh_render_env_tile: the environment-lit gather's tile (params: an EnvParams, None: the defaults) ->
         (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x N, ao_occluded = the occluded rays)"""
-        return self._render_gather_tile("lh_render_env_tile", (params,), cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
+        return self._render_gather_tile("env", params, None, cam, x0, y0, w, h, pixel_samples, gather_nsamples, seed, uniforms, out, stream)
 
     def render_whitted_tile(self, cam, x0, y0, w, h, pixel_samples, params=None, out=None, stream=None):
         """lh_render_whitted_tile: the refraction chain's tile (params: a WhittedParams, None: the defaults) -- a camera miss sees the
@@ -1216,7 +1218,7 @@ class HipAccel:
         and the float32 tensor [n] of (N - count) / N (0 for a miss).  out: such a pair to fill (either member may be None, not
         both); with out=None both are allocated with torch.empty and the slots of rays that are not listed are UNSPECIFIED.
         Synchronous: the outputs are complete on return."""
-        return self._batch_stage_device("ao_device", None, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
+        return self._batch_stage_device("ao", None, None, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
 
     def dirt_device(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None, index=None, count=None,
                     out=None, stream=None):
@@ -1226,7 +1228,7 @@ class HipAccel:
         the far clip, AO_NO_HIT for a miss -- and the float32 tensor [n] of the mean weight (0 for a miss).  out: such a pair to
         fill (either member may be None, not both); with out=None the slots of rays that are not listed are UNSPECIFIED.
         Synchronous: the outputs are complete on return."""
-        return self._batch_stage_device("dirt_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
+        return self._batch_stage_device("dirt", params, None, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
 
     def env_device(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None, index=None, count=None,
                    out=None, stream=None):
@@ -1236,45 +1238,117 @@ class HipAccel:
         gathered colour (zeros for a miss), the accelerator's environment (set_environment) seen by the rays that are not occluded.
         out: such a pair to fill (either member may be None, not both); with out=None the slots of rays that are not listed are
         UNSPECIFIED.  Synchronous: the outputs are complete on return."""
-        return self._batch_stage_device("env_device", params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
+        return self._batch_stage_device("env", params, None, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream)
 
-    # what -> (the C function, the type of params and how the refusal names it, the radiance is [n, 3])
-    _BATCH_STAGES = {"ao_device": ("lh_accel_ao_device", None, None, False),
-                     "dirt_device": ("lh_accel_dirt_device", DirtParams, "a DirtParams", False),
-                     "env_device": ("lh_accel_env_device", EnvParams, "an EnvParams", True)}
+    # kind -> what differs between the kinds' forms.  device, host, tile, rays: the C functions (rays None: the kind has no rays-alone form); ptype, pname:
+    # the type of params and how a refusal names it; pack: how the light list is packed (None: a sampled kind, gather_nsamples goes to C instead);
+    # seeded: seed, key and uniforms go to C; rgb: the value is [n, 3]; word, pair: how the messages name the 32-bit output and the out pair; host_key:
+    # the host form's refusal of a key array of another length; rays_out: the names of the rays-alone form's double outputs, [m, 3] twice, then [m]
+    _Stage = collections.namedtuple("_Stage", "device host tile rays ptype pname pack seeded rgb word pair host_key rays_out")
+    _BATCH_STAGES = {
+        "ao": _Stage("lh_accel_ao_device", "lh_accel_ao_host", "lh_render_ao_tile", "lh_accel_ao_rays_device", None, None, None, True, False,
+                     "count", "(count, radiance)", "one key per ray", ("ao_org", "ao_dir")),
+        "dirt": _Stage("lh_accel_dirt_device", "lh_accel_dirt_host", "lh_render_dirt_tile", None, DirtParams, "a DirtParams", None, True, False,
+                       "count", "(count, radiance)", "one key per ray", None),
+        "env": _Stage("lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", None, EnvParams, "an EnvParams", None, True, True,
+                      "count", "(count, radiance)", "one key per ray", None),
+        "lights": _Stage("lh_accel_lights_device", "lh_accel_lights_host", "lh_render_lights_tile", "lh_accel_light_rays_device", LightsParams,
+                         "a LightsParams", _light_array, False, True, "mask", "(visible, rgb)", None, ("org", "dir", "tmax")),
+        "area_lights": _Stage("lh_accel_area_lights_device", "lh_accel_area_lights_host", "lh_render_area_lights_tile", "lh_accel_area_light_rays_device",
+                              AreaParams, "an AreaParams", _area_array, True, True, "mask", "(visible, rgb)", "key must hold one word per ray",
+                              ("org", "dir", "tmax", "weight"))}
 
-    def _batch_stage_device(self, what, params, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream):
-        """ao_device / dirt_device / env_device: the row of _BATCH_STAGES, the checks and the call (params None: the type's defaults)"""
-        import torch
-        name, ptype, pname, env = self._BATCH_STAGES[what]
-        if ptype is not None:
+    @staticmethod
+    def _stage_args(what, sg, params, lights):
+        """-> (the row's params: the caller's, or for None the type's defaults; params and the packed light list as the C call takes them; the lights)"""
+        if sg.ptype is not None:
             if params is None:
-                params = ptype()
-            if not isinstance(params, ptype):
-                raise ValueError("%s: params must be %s" % (what, pname))
+                params = sg.ptype()
+            if not isinstance(params, sg.ptype):
+                raise ValueError("%s: params must be %s" % (what, sg.pname))
+        pargs = () if sg.ptype is None else (C.byref(params),)
+        if sg.pack is None:
+            return params, pargs, 0
+        arr, nl = sg.pack(what, lights)
+        return params, (arr, nl) + pargs, nl
+
+    @staticmethod
+    def _stage_mid(sg, gather_nsamples, pargs, seeded):
+        """what a C call takes between the records and its outputs: gather_nsamples (a sampled kind), params, `seeded` (a seeded kind)"""
+        return (() if sg.pack else (int(gather_nsamples),)) + pargs + (seeded if sg.seeded else ())
+
+    def _batch_stage_device(self, kind, params, lights, org, dr, records, gather_nsamples, seed, key, uniforms, index, count, out, stream):
+        """the five device forms: the row of _BATCH_STAGES, the checks and the call (params None: the type's defaults)"""
+        import torch
+        sg = self._BATCH_STAGES[kind]
+        what = kind + "_device"
+        params, pargs, _ = self._stage_args(what, sg, params, lights)
         n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
         dev = org.device
         ip, ni, cp = _list_args(index, count, what)
         if index is None and count is not None:
             ni = n
         if out is None:
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3) if env else n, dtype=torch.float32, device=dev))
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3) if sg.rgb else n, dtype=torch.float32, device=dev))
         if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
-            raise ValueError("%s: out must be a (count, radiance) pair, at least one of them a tensor" % what)
+            raise ValueError("%s: out must be a %s pair, at least one of them a tensor" % (what, sg.pair))
         oc, orad = out
         words = (torch.int32, getattr(torch, "uint32", torch.int32))
         if oc is not None and not (oc.is_cuda and oc.dtype in words and oc.dim() == 1 and oc.shape[0] == n and oc.is_contiguous()):
-            raise ValueError("%s: the count output must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if env and orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 2 and tuple(orad.shape) == (n, 3) and orad.is_contiguous()):
+            raise ValueError("%s: the %s output must be a contiguous int32 / uint32 device tensor [n]" % (what, sg.word))
+        if sg.rgb and orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 2 and tuple(orad.shape) == (n, 3) and orad.is_contiguous()):
             raise ValueError("%s: the colour output must be a contiguous float32 device tensor [n, 3]" % what)
-        if not env and orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 1 and orad.shape[0] == n and orad.is_contiguous()):
+        if not sg.rgb and orad is not None and not (orad.is_cuda and orad.dtype == torch.float32 and orad.dim() == 1 and orad.shape[0] == n and orad.is_contiguous()):
             raise ValueError("%s: the radiance output must be a contiguous float32 device tensor [n]" % what)
         if stream is None:
             stream = torch.cuda.current_stream(dev)
         stream = getattr(stream, "cuda_stream", stream)
-        pargs = () if ptype is None else (C.byref(params),)
-        _check(getattr(self.L, name)(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples), *pargs,
-                                     int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(oc), _dptr(orad), C.c_void_p(stream)), name)
+        mid = self._stage_mid(sg, gather_nsamples, pargs, (int(seed), _dptr(key), _dptr(uniforms)))
+        _check(getattr(self.L, sg.device)(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), *mid, ip, ni, cp, _dptr(oc), _dptr(orad),
+                                          C.c_void_p(stream)), sg.device)
+        return out
+
+    def _rays_device(self, kind, params, lights, org, dr, records, gather_nsamples, seed, key, uniforms, out, stream):
+        """the three rays-alone forms: the row of _BATCH_STAGES, the checks and the call.  out: (slot_of_ray, nslots) and the row's rays_out; a last member
+        "weight" may be None; the capacity handed to C is the shortest of the double outputs that are given"""
+        import torch
+        sg = self._BATCH_STAGES[kind]
+        what = sg.rays[len("lh_accel_"):]
+        params, pargs, nl = self._stage_args(what, sg, params, lights)
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
+        dev = org.device
+        if sg.pack is None:
+            if int(gather_nsamples) < 1:
+                raise ValueError("%s: gather_nsamples must be at least 1" % what)
+            m = n * int(int(gather_nsamples) ** 0.5) ** 2
+        else:
+            m = n * max(nl, 1) * max(int(getattr(params, "nsamples", 1)), 1)
+        names = ("slot_of_ray", "nslots") + sg.rays_out
+        if out is None:
+            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)) + tuple(
+                torch.empty((m, 3) if k < 2 else m, dtype=torch.float64, device=dev) for k in range(len(sg.rays_out)))
+        if not isinstance(out, (tuple, list)) or len(out) != len(names):
+            raise ValueError("%s: out must be (%s)" % (what, ", ".join(names)))
+        so, ns = out[:2]
+        words = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
+            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
+        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
+            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
+        for k, (name, x) in enumerate(zip(sg.rays_out, out[2:])):
+            if x is None and name == "weight":
+                continue
+            if k < 2 and not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
+            if k >= 2 and not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 1 and x.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous float64 device tensor [m]" % (what, name))
+        cap = min(int(x.shape[0]) for x in out[2:] if x is not None)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        stream = getattr(stream, "cuda_stream", stream)
+        mid = self._stage_mid(sg, gather_nsamples, pargs, (int(seed), _dptr(key), _dptr(uniforms)))
+        _check(getattr(self.L, sg.rays)(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), *mid, _dptr(so), _dptr(ns),
+                                        *[_dptr(x) for x in out[2:]], cap, C.c_void_p(stream)), sg.rays)
         return out
 
     def ao_rays_device(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None, out=None, stream=None):
@@ -1282,113 +1356,32 @@ class HipAccel:
         (slot_of_ray int32 [n] -- the hit slot of every ray, AO_NO_HIT (as uint32 bits) for a miss; nslots -- one-element int32
         tensor, the number of hits; ao_org, ao_dir -- float64 [n * N, 3], ray (slot, r) at row slot * N + r, the first
         nslots * N rows written).  Everything stays on the device and nothing is read back; out: such a 4-tuple to fill."""
-        import torch
-        what = "ao_rays_device"
-        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
-        dev = org.device
-        if int(gather_nsamples) < 1:
-            raise ValueError("%s: gather_nsamples must be at least 1" % what)
-        N = int(int(gather_nsamples) ** 0.5) ** 2
-        if out is None:
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
-                   torch.empty((n * N, 3), dtype=torch.float64, device=dev), torch.empty((n * N, 3), dtype=torch.float64, device=dev))
-        if not isinstance(out, (tuple, list)) or len(out) != 4:
-            raise ValueError("%s: out must be (slot_of_ray, nslots, ao_org, ao_dir)" % what)
-        so, ns, ao, ad = out
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
-            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
-            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
-        for name, x in (("ao_org", ao), ("ao_dir", ad)):
-            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
-                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
-        cap = min(int(ao.shape[0]), int(ad.shape[0]))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        stream = getattr(stream, "cuda_stream", stream)
-        _check(self.L.lh_accel_ao_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), int(gather_nsamples),
-                                              int(seed), _dptr(key), _dptr(uniforms), _dptr(so), _dptr(ns), _dptr(ao), _dptr(ad), cap,
-                                              C.c_void_p(stream)), "lh_accel_ao_rays_device")
-        return out
+        return self._rays_device("ao", None, None, org, dr, records, gather_nsamples, seed, key, uniforms, out, stream)
 
     def ao_host(self, org, dr, records, gather_nsamples, seed=1, key=None, uniforms=None):
         """lh_accel_ao_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v)) -> (count uint32 [n], radiance float32 [n])"""
-        return self._batch_stage_host("ao_host", None, org, dr, records, gather_nsamples, seed, key, uniforms)
+        return self._batch_stage_host("ao", None, None, org, dr, records, gather_nsamples, seed, key, uniforms)
 
     def dirt_host(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None):
         """lh_accel_dirt_host: host arrays as ao_host, params as dirt_device -> (near_hits uint32 [n], value float32 [n])"""
-        if params is None:
-            params = DirtParams()
-        if not isinstance(params, DirtParams):
-            raise ValueError("dirt_host: params must be a DirtParams")
-        return self._batch_stage_host("dirt_host", params, org, dr, records, gather_nsamples, seed, key, uniforms)
+        return self._batch_stage_host("dirt", params, None, org, dr, records, gather_nsamples, seed, key, uniforms)
 
     def env_host(self, org, dr, records, gather_nsamples, params=None, seed=1, key=None, uniforms=None):
         """lh_accel_env_host: host arrays as ao_host, params as env_device -> (count uint32 [n], rgb float32 [n, 3])"""
-        if params is None:
-            params = EnvParams()
-        if not isinstance(params, EnvParams):
-            raise ValueError("env_host: params must be an EnvParams")
-        return self._batch_stage_host("env_host", params, org, dr, records, gather_nsamples, seed, key, uniforms)
+        return self._batch_stage_host("env", params, None, org, dr, records, gather_nsamples, seed, key, uniforms)
 
     # ---- direct light: shadow rays from a batch of hits to a list of lights (lh_lights.h) ----
-    @staticmethod
-    def _lights_params(what, params):
-        if params is None:
-            params = LightsParams()
-        if not isinstance(params, LightsParams):
-            raise ValueError("%s: params must be a LightsParams" % what)
-        return params
-
     def lights_device(self, org, dr, records, lights, params=None, index=None, count=None, out=None, stream=None):
         """lh_accel_lights_device: which of `lights` (a sequence of 1 .. LIGHTS_MAX Light) every hit of a batch of rays and their closest-hit
         records sees, and what they add; org / dr / records / index / count as env_device, params: a LightsParams (None: eps 1e-5).  Returns
         (visible, rgb): an int32 tensor [n] whose bits are uint32 -- bit l: the hit sees light l; AO_NO_HIT for a miss -- and the float32
         tensor [n, 3] of the sum of the visible lights' weighted colours in list order (zeros for a miss).  out: such a pair to fill (either
         member may be None, not both); with out=None the slots of rays that are not listed are UNSPECIFIED.  Synchronous."""
-        import torch
-        what = "lights_device"
-        params = self._lights_params(what, params)
-        arr, nl = _light_array(what, lights)
-        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, None, None)
-        dev = org.device
-        ip, ni, cp = _list_args(index, count, what)
-        if index is None and count is not None:
-            ni = n
-        if out is None:
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
-        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
-            raise ValueError("%s: out must be a (visible, rgb) pair, at least one of them a tensor" % what)
-        ov, orgb = out
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if ov is not None and not (ov.is_cuda and ov.dtype in words and ov.dim() == 1 and ov.shape[0] == n and ov.is_contiguous()):
-            raise ValueError("%s: the mask output must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if orgb is not None and not (orgb.is_cuda and orgb.dtype == torch.float32 and orgb.dim() == 2 and tuple(orgb.shape) == (n, 3) and orgb.is_contiguous()):
-            raise ValueError("%s: the colour output must be a contiguous float32 device tensor [n, 3]" % what)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        stream = getattr(stream, "cuda_stream", stream)
-        _check(self.L.lh_accel_lights_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl, C.byref(params),
-                                             ip, ni, cp, _dptr(ov), _dptr(orgb), C.c_void_p(stream)), "lh_accel_lights_device")
-        return out
+        return self._batch_stage_device("lights", params, lights, org, dr, records, None, 0, None, None, index, count, out, stream)
 
     def lights_host(self, org, dr, records, lights, params=None):
         """lh_accel_lights_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v)) -> (visible uint32 [n], rgb float32 [n, 3])"""
-        what = "lights_host"
-        params = self._lights_params(what, params)
-        arr, nl = _light_array(what, lights)
-        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
-        if d.shape[0] != n or len(records) != 4:
-            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
-        p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
-        u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
-        if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
-            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
-        vis = np.empty(n, np.uint32); rgb = np.empty((n, 3), np.float32)
-        _check(self.L.lh_accel_lights_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
-                                           arr, nl, C.byref(params), vis.ctypes.data, rgb.ctypes.data), "lh_accel_lights_host")
-        return vis, rgb
+        return self._batch_stage_host("lights", params, lights, org, dr, records, None, 0, None, None)
 
     def light_rays_device(self, org, dr, records, lights, params=None, out=None, stream=None):
         """lh_accel_light_rays_device: only the shadow rays of the batch's hits, for a caller who traces them itself.  Returns (slot_of_ray
@@ -1397,65 +1390,14 @@ class HipAccel:
         +inf for a directional light, 1 for a point light, 0 for a ray that is not traced: its bit is clear whatever a launch answers).
         intersect_device(..., mode=MODE_ANY, tmax=tmax) on them gives the stage's bytes.  Everything stays on the device and nothing is read
         back; out: such a 5-tuple to fill."""
-        import torch
-        what = "light_rays_device"
-        params = self._lights_params(what, params)
-        arr, nl = _light_array(what, lights)
-        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, None, None)
-        dev = org.device
-        if out is None:
-            m = n * max(nl, 1)
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
-                   torch.empty((m, 3), dtype=torch.float64, device=dev), torch.empty((m, 3), dtype=torch.float64, device=dev),
-                   torch.empty(m, dtype=torch.float64, device=dev))
-        if not isinstance(out, (tuple, list)) or len(out) != 5:
-            raise ValueError("%s: out must be (slot_of_ray, nslots, org, dir, tmax)" % what)
-        so, ns, ro, rd, rt = out
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
-            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
-            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
-        for name, x in (("org", ro), ("dir", rd)):
-            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
-                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
-        if not (rt.is_cuda and rt.dtype == torch.float64 and rt.dim() == 1 and rt.is_contiguous()):
-            raise ValueError("%s: tmax must be a contiguous float64 device tensor [m]" % what)
-        cap = min(int(ro.shape[0]), int(rd.shape[0]), int(rt.shape[0]))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        stream = getattr(stream, "cuda_stream", stream)
-        _check(self.L.lh_accel_light_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl, C.byref(params),
-                                                 _dptr(so), _dptr(ns), _dptr(ro), _dptr(rd), _dptr(rt), cap, C.c_void_p(stream)),
-               "lh_accel_light_rays_device")
-        return out
+        return self._rays_device("lights", params, lights, org, dr, records, None, 0, None, None, out, stream)
 
     def render_lights_tile(self, cam, x0, y0, w, h, pixel_samples, lights, params=None, out=None, stream=None):
         """lh_render_lights_tile: direct light per camera sample -- a miss gives 0, a hit the sum of the lights it sees -> (rgb float32
         [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x lights, ao_occluded = the items whose bit is clear)"""
-        import torch
-        what = "render_lights_tile"
-        params = self._lights_params(what, params)
-        arr, nl = _light_array(what, lights)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        st = TileStats()
-        _check(self.L.lh_render_lights_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, arr, nl, C.byref(params), _dptr(out), C.byref(st),
-                                            C.c_void_p(stream)), "lh_render_lights_tile")
-        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+        return self._render_gather_tile("lights", params, lights, cam, x0, y0, w, h, pixel_samples, None, 0, None, out, stream)
 
     # ---- area lights: soft shadows from triangle emitters (lh_area.h) ----
-    @staticmethod
-    def _area_params(what, params):
-        if params is None:
-            params = AreaParams()
-        if not isinstance(params, AreaParams):
-            raise ValueError("%s: params must be an AreaParams" % what)
-        return params
-
     def set_emitters(self, tris):
         """lh_accel_set_emitters: the table of emitter triangles the area lights' runs index -- host array [ntris, 3, 3] (or [ntris, 9]) of
         float64 vertices; None (or an empty array) removes it.  After commit, at any time; kept across recommit."""
@@ -1473,115 +1415,25 @@ class HipAccel:
         closest-hit records sees through params.nsamples samples each, and the mean of what the samples add; org / dr / records / index / count
         as lights_device, seed / key / uniforms as ao_device (uniforms: 3 per item in (hit slot, l, s) order).  Returns (visible, rgb) as
         lights_device does.  Synchronous."""
-        import torch
-        what = "area_lights_device"
-        params = self._area_params(what, params)
-        arr, nl = _area_array(what, lights)
-        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
-        dev = org.device
-        ip, ni, cp = _list_args(index, count, what)
-        if index is None and count is not None:
-            ni = n
-        if out is None:
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev))
-        if not isinstance(out, (tuple, list)) or len(out) != 2 or (out[0] is None and out[1] is None):
-            raise ValueError("%s: out must be a (visible, rgb) pair, at least one of them a tensor" % what)
-        ov, orgb = out
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if ov is not None and not (ov.is_cuda and ov.dtype in words and ov.dim() == 1 and ov.shape[0] == n and ov.is_contiguous()):
-            raise ValueError("%s: the mask output must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if orgb is not None and not (orgb.is_cuda and orgb.dtype == torch.float32 and orgb.dim() == 2 and tuple(orgb.shape) == (n, 3) and orgb.is_contiguous()):
-            raise ValueError("%s: the colour output must be a contiguous float32 device tensor [n, 3]" % what)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        stream = getattr(stream, "cuda_stream", stream)
-        _check(self.L.lh_accel_area_lights_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl, C.byref(params),
-                                                  int(seed), _dptr(key), _dptr(uniforms), ip, ni, cp, _dptr(ov), _dptr(orgb), C.c_void_p(stream)),
-               "lh_accel_area_lights_device")
-        return out
+        return self._batch_stage_device("area_lights", params, lights, org, dr, records, None, seed, key, uniforms, index, count, out, stream)
 
     def area_lights_host(self, org, dr, records, lights, params=None, seed=1, key=None, uniforms=None):
         """lh_accel_area_lights_host: host arrays (org, dr [n, 3]; records = (prim, t, u, v); key uint64 [n] or None; uniforms float64, 3 per
         item, or None) -> (visible uint32 [n], rgb float32 [n, 3])"""
-        what = "area_lights_host"
-        params = self._area_params(what, params)
-        arr, nl = _area_array(what, lights)
-        o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
-        if d.shape[0] != n or len(records) != 4:
-            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
-        p = _np(records[0], np.uint32).reshape(-1); t = _np(records[1], np.float64).reshape(-1)
-        u = _np(records[2], np.float64).reshape(-1); v = _np(records[3], np.float64).reshape(-1)
-        if not (p.shape[0] == t.shape[0] == u.shape[0] == v.shape[0] == n):
-            raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
-        k = None if key is None else _np(key, np.uint64).reshape(-1)
-        if k is not None and k.shape[0] != n:
-            raise ValueError("%s: key must hold one word per ray" % what)
-        un = None if uniforms is None else _np(uniforms, np.float64).reshape(-1)
-        vis = np.empty(n, np.uint32); rgb = np.empty((n, 3), np.float32)
-        _check(self.L.lh_accel_area_lights_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
-                                                arr, nl, C.byref(params), int(seed), None if k is None else k.ctypes.data,
-                                                None if un is None else un.ctypes.data, 0 if un is None else un.shape[0],
-                                                vis.ctypes.data, rgb.ctypes.data), "lh_accel_area_lights_host")
-        return vis, rgb
+        return self._batch_stage_host("area_lights", params, lights, org, dr, records, None, seed, key, uniforms)
 
     def area_light_rays_device(self, org, dr, records, lights, params=None, seed=1, key=None, uniforms=None, out=None, stream=None):
         """lh_accel_area_light_rays_device: only the rays of the batch's hits to the lights' samples.  Returns (slot_of_ray int32 [n], nslots --
         one-element int32 tensor, org, dir -- float64 [n * L * S, 3], tmax, weight -- float64 [n * L * S]: item (slot, l, s) at row
         (slot * L + l) * S + s, the first nslots * L * S rows written; tmax is params.bound, or 0 for an item that is not traced).
         intersect_device(..., mode=MODE_ANY, tmax=tmax) on them gives the stage's bytes.  Nothing is read back; out: such a 6-tuple to fill."""
-        import torch
-        what = "area_light_rays_device"
-        params = self._area_params(what, params)
-        arr, nl = _area_array(what, lights)
-        n, prim, t, u, v = self._ao_batch_in(what, org, dr, records, key, uniforms)
-        dev = org.device
-        if out is None:
-            m = n * max(nl, 1) * max(int(params.nsamples), 1)
-            out = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev),
-                   torch.empty((m, 3), dtype=torch.float64, device=dev), torch.empty((m, 3), dtype=torch.float64, device=dev),
-                   torch.empty(m, dtype=torch.float64, device=dev), torch.empty(m, dtype=torch.float64, device=dev))
-        if not isinstance(out, (tuple, list)) or len(out) != 6:
-            raise ValueError("%s: out must be (slot_of_ray, nslots, org, dir, tmax, weight)" % what)
-        so, ns, ro, rd, rt, rw = out
-        words = (torch.int32, getattr(torch, "uint32", torch.int32))
-        if not (so.is_cuda and so.dtype in words and so.dim() == 1 and so.shape[0] == n and so.is_contiguous()):
-            raise ValueError("%s: slot_of_ray must be a contiguous int32 / uint32 device tensor [n]" % what)
-        if not (ns.is_cuda and ns.dtype in words and ns.numel() == 1):
-            raise ValueError("%s: nslots must be a one-element int32 / uint32 device tensor" % what)
-        for name, x in (("org", ro), ("dir", rd)):
-            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 2 and x.shape[1] == 3 and x.is_contiguous()):
-                raise ValueError("%s: %s must be a contiguous float64 device tensor [m, 3]" % (what, name))
-        for name, x in (("tmax", rt), ("weight", rw)):
-            if x is None and name == "weight":
-                continue
-            if not (x.is_cuda and x.dtype == torch.float64 and x.dim() == 1 and x.is_contiguous()):
-                raise ValueError("%s: %s must be a contiguous float64 device tensor [m]" % (what, name))
-        cap = min(int(ro.shape[0]), int(rd.shape[0]), int(rt.shape[0]), int(rt.shape[0]) if rw is None else int(rw.shape[0]))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        stream = getattr(stream, "cuda_stream", stream)
-        _check(self.L.lh_accel_area_light_rays_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), arr, nl,
-                                                      C.byref(params), int(seed), _dptr(key), _dptr(uniforms), _dptr(so), _dptr(ns), _dptr(ro),
-                                                      _dptr(rd), _dptr(rt), _dptr(rw), cap, C.c_void_p(stream)), "lh_accel_area_light_rays_device")
-        return out
+        return self._rays_device("area_lights", params, lights, org, dr, records, None, seed, key, uniforms, out, stream)
 
     def render_area_lights_tile(self, cam, x0, y0, w, h, pixel_samples, lights, params=None, seed=1, out=None, stream=None):
         """lh_render_area_lights_tile: area lights per camera sample -- a miss gives 0, a hit the mean over the samples of what its lights add ->
         (rgb float32 [h,w,3] CUDA tensor in image orientation, stats dict: ao_rays = hits x lights x samples, ao_occluded = the items that are
         not open).  The built-in generator, keyed by the absolute sample position: a frame does not depend on its tiling."""
-        import torch
-        what = "render_area_lights_tile"
-        params = self._area_params(what, params)
-        arr, nl = _area_array(what, lights)
-        dev = torch.device("cuda", self.device)
-        if out is None:
-            out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        st = TileStats()
-        _check(self.L.lh_render_area_lights_tile(self.h, C.byref(cam), x0, y0, w, h, pixel_samples, arr, nl, C.byref(params), int(seed), _dptr(out),
-                                                 C.byref(st), C.c_void_p(stream)), "lh_render_area_lights_tile")
-        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+        return self._render_gather_tile("area_lights", params, lights, cam, x0, y0, w, h, pixel_samples, None, seed, None, out, stream)
 
     def environment_device(self, dirs, out=None, stream=None):
         """lh_accel_environment_device: the accelerator's environment (set_environment; constant white if none was set) seen in each of
@@ -1735,7 +1587,11 @@ class HipAccel:
             raise ValueError("%s: params must be a WhittedParams" % what)
         return params
 
-    def _batch_stage_host(self, what, dirt, org, dr, records, gather_nsamples, seed, key, uniforms):
+    def _batch_stage_host(self, kind, params, lights, org, dr, records, gather_nsamples, seed, key, uniforms):
+        """the five host forms: the row of _BATCH_STAGES, the checks and the call (params None: the type's defaults)"""
+        sg = self._BATCH_STAGES[kind]
+        what = kind + "_host"
+        params, pargs, _ = self._stage_args(what, sg, params, lights)
         o = _np(org, np.float64).reshape(-1, 3); d = _np(dr, np.float64).reshape(-1, 3); n = o.shape[0]
         if d.shape[0] != n or len(records) != 4:
             raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
@@ -1745,26 +1601,13 @@ class HipAccel:
             raise ValueError("%s: org, dr and the (prim, t, u, v) records must describe the same rays" % what)
         k = None if key is None else _np(key, np.uint64).reshape(-1)
         if k is not None and k.shape[0] != n:
-            raise ValueError("%s: one key per ray" % what)
+            raise ValueError("%s: %s" % (what, sg.host_key))
         un = None if uniforms is None else _np(uniforms, np.float64).reshape(-1)
-        cnt = np.empty(n, np.uint32); rad = np.empty(n, np.float32)
-        if isinstance(dirt, EnvParams):
-            rad = np.empty((n, 3), np.float32)
-            _check(self.L.lh_accel_env_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
-                                            int(gather_nsamples), C.byref(dirt), int(seed), None if k is None else k.ctypes.data,
-                                            None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,
-                                            rad.ctypes.data), "lh_accel_env_host")
-            return cnt, rad
-        if dirt is not None:
-            _check(self.L.lh_accel_dirt_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
-                                             int(gather_nsamples), C.byref(dirt), int(seed), None if k is None else k.ctypes.data,
-                                             None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,
-                                             rad.ctypes.data), "lh_accel_dirt_host")
-            return cnt, rad
-        _check(self.L.lh_accel_ao_host(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data,
-                                       int(gather_nsamples), int(seed), None if k is None else k.ctypes.data,
-                                       None if un is None else un.ctypes.data, 0 if un is None else un.shape[0], cnt.ctypes.data,
-                                       rad.ctypes.data), "lh_accel_ao_host")
+        cnt = np.empty(n, np.uint32); rad = np.empty((n, 3) if sg.rgb else n, np.float32)
+        mid = self._stage_mid(sg, gather_nsamples, pargs, (int(seed), None if k is None else k.ctypes.data, None if un is None else un.ctypes.data,
+                                                           0 if un is None else un.shape[0]))
+        _check(getattr(self.L, sg.host)(self.h, n, o.ctypes.data, d.ctypes.data, p.ctypes.data, t.ctypes.data, u.ctypes.data, v.ctypes.data, *mid,
+                                        cnt.ctypes.data, rad.ctypes.data), sg.host)
         return cnt, rad
 
     def scratch(self, which, dtype, width):

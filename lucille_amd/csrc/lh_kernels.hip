@@ -1644,6 +1644,17 @@ struct FusedStage {
     }
 };
 
+/* what the fused item kinds (lh_lights.h, lh_area.h) share: the persistent kernel `kern` over the items of `none` -- its bytes at none.occ -- and the
+ * cooperative pass of ray source SRC behind it, the kind's table by value into both */
+template <int SRC, class Kern, class Tab>
+int launch_fused_items(Kern kern, const Tab &tab, const lh_dev_scene_t &scl, const lh_batch_t &none, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p,
+                       const lh_launch_ctx_t &c, hipStream_t s)
+{
+    LH_LAUNCH_PERSIST(kern, scl, (uint32_t)none.n, (uint8_t *)none.occ, none.counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
+    if (hipGetLastError() != hipSuccess) return -1;
+    return launch_coop<true, SRC, true>(scl, none, ao, fq, p, c, s, tab);
+}
+
 /* a fused stage: the gather rays of g.nslots hits, N = ntheta * nphi each, made inside the persistent kernel (SRC 1).  Rays that kernel does not
  * finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative walk) -- go through the stream's
  * fix-up queue (2 words per entry, count + overflow flag in qcount[0..1]) to k_coop_walk */
@@ -1689,9 +1700,7 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
         using light_t = decltype(&k_trace_persist_light<true, LH_WALK_Q4>);
         const light_t lkern[2][2] = {{k_trace_persist_light<true, LH_WALK_Q4_CHECKED>, k_trace_persist_light<false, LH_WALK_Q4_CHECKED>},
                                      {k_trace_persist_light<true, LH_WALK_Q4>, k_trace_persist_light<false, LH_WALK_Q4>}};
-        LH_LAUNCH_PERSIST(lkern[w][k], scl, (uint32_t)n, st.env_occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
-        if (hipGetLastError() != hipSuccess) return -1;
-        return launch_coop<true, 3, true>(scl, none, ao, fq, p, c, s, tab);
+        return launch_fused_items<3>(lkern[w][k], tab, scl, none, ao, fq, p, c, s);
     }
     if (st.area) {          /* the area-light stage (lh_area.h): ntheta samples of each of nphi lights, the HOST table g.area by value into both kernels */
         if (!g.area || g.area->L != g.nphi || g.area->S != g.ntheta || g.nphi < 1 || g.nphi > LH_AREA_LIGHTS_MAX || g.ntheta < 1 || !g.area->emitters ||
@@ -1700,9 +1709,7 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
         using area_t = decltype(&k_trace_persist_area<true, LH_WALK_Q4>);
         const area_t akern[2][2] = {{k_trace_persist_area<true, LH_WALK_Q4_CHECKED>, k_trace_persist_area<false, LH_WALK_Q4_CHECKED>},
                                     {k_trace_persist_area<true, LH_WALK_Q4>, k_trace_persist_area<false, LH_WALK_Q4>}};
-        LH_LAUNCH_PERSIST(akern[w][k], scl, (uint32_t)n, st.env_occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
-        if (hipGetLastError() != hipSuccess) return -1;
-        return launch_coop<true, 4, true>(scl, none, ao, fq, p, c, s, tab);
+        return launch_fused_items<4>(akern[w][k], tab, scl, none, ao, fq, p, c, s);
     }
     /* the environment gather (named last: the kernels above keep their order) */
     using env_t = decltype(&k_trace_persist_env<true, LH_WALK_Q4>);

@@ -797,20 +797,26 @@ __global__ void k_light_rays(size_t nslots, const unsigned long long *__restrict
 struct LightGather { int L; const double *hitrec; const uint8_t *occ; };
 
 /* the mask and value of a hit slot, and how many of its L items have their bit clear */
-__device__ __forceinline__ uint32_t light_slot(const LightGather &g, const lh_light_tab_t &tab, uint32_t slot, float val[3], unsigned int &dark)
-{
-    LH_NC
-    const double *h = g.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
-    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
-    const uint32_t mask = lh_lights_value(O, Ns, tab.l, g.L, g.occ + (size_t)slot * (size_t)g.L, val);
-    dark = (unsigned int)(g.L - __popc(mask));
-    return mask;
-}
+struct light_slot {
+    const LightGather &g; const lh_light_tab_t &tab;
+    __device__ __forceinline__ uint32_t operator()(uint32_t slot, float val[3], unsigned int &dark) const
+    {
+        LH_NC
+        const double *h = g.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
+        const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+        const uint32_t mask = lh_lights_value(O, Ns, tab.l, g.L, g.occ + (size_t)slot * (size_t)g.L, val);
+        dark = (unsigned int)(g.L - __popc(mask));
+        return mask;
+    }
+};
 
-/* k_ao_resolve for the light tile, a thread per pixel: a miss gives 0, a hit the three floats of lh_lights_value; sub-samples are widened, added per
+/* the resolves of an item kind.  Slot: "mask, value and closed count of a hit slot" over the kind's gather and its table, which stay the kernel's
+ * by-value arguments (light_slot, area_slot).
+ * k_ao_resolve for an item kind's tile, a thread per pixel: a miss gives 0, a hit the three floats of its slot; sub-samples are widened, added per
  * channel in sample order and written as env_resolve does.  No texture multiply (the reference's sun branch fetches none) */
-__global__ __launch_bounds__(256) void k_light_resolve(int w, int h, int band_rows, int xs, int ys, const LightGather g, const uint32_t *__restrict__ slot_of_sample,
-                                                       float *__restrict__ rgb, unsigned long long *__restrict__ dark_total, const lh_light_tab_t tab)
+template <class Slot>
+__device__ __forceinline__ void item_resolve(int w, int h, int band_rows, int xs, int ys, const Slot &at, const uint32_t *__restrict__ slot_of_sample,
+                                             float *__restrict__ rgb, unsigned long long *__restrict__ dark_total)
 {
     LH_NC
     const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -821,7 +827,7 @@ __global__ __launch_bounds__(256) void k_light_resolve(int w, int h, int band_ro
     for (int s = 0; s < S; s++) {
         const uint32_t slot = slot_of_sample[pix * S + s];
         float val[3] = {0.0f, 0.0f, 0.0f};
-        if (slot != LH_MISS_PRIM) { unsigned int c; (void)light_slot(g, tab, slot, val, c); n += c; }
+        if (slot != LH_MISS_PRIM) { unsigned int c; (void)at(slot, val, c); n += c; }
         a0 = a0 + (double)val[0]; a1 = a1 + (double)val[1]; a2 = a2 + (double)val[2];
     }
     if (inside) {
@@ -836,11 +842,11 @@ __global__ __launch_bounds__(256) void k_light_resolve(int w, int h, int band_ro
     wg_total(n, dark_total);
 }
 
-/* k_ao_batch_resolve for the light stage, a thread per list entry: visible[id] / rgb[3 id ..] (either may be NULL); a traced miss gets LH_AO_NO_HIT and
+/* k_ao_batch_resolve for an item kind, a thread per list entry: visible[id] / rgb[3 id ..] (either may be NULL); a traced miss gets LH_AO_NO_HIT and
  * three zeros.  slot_of_entry NULL: an empty scene, every traced ray is a miss */
-__global__ __launch_bounds__(256) void k_light_batch_resolve(const BatchList bl, const LightGather g, const uint32_t *__restrict__ slot_of_entry,
-                                                             uint32_t *__restrict__ visible, float *__restrict__ rgb,
-                                                             unsigned long long *__restrict__ dark_total, const lh_light_tab_t tab)
+template <class Slot>
+__device__ __forceinline__ void item_batch_resolve(const BatchList &bl, const Slot &at, const uint32_t *__restrict__ slot_of_entry, uint32_t *__restrict__ visible,
+                                                   float *__restrict__ rgb, unsigned long long *__restrict__ dark_total)
 {
     LH_NC
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
@@ -850,11 +856,24 @@ __global__ __launch_bounds__(256) void k_light_batch_resolve(const BatchList bl,
         const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
         uint32_t mask = LH_AO_NO_HIT;
         float val[3] = {0.0f, 0.0f, 0.0f};
-        if (slot != LH_AO_NO_HIT) mask = light_slot(g, tab, slot, val, n);
+        if (slot != LH_AO_NO_HIT) mask = at(slot, val, n);
         if (visible) visible[id] = mask;
         if (rgb) { rgb[3 * (size_t)id] = val[0]; rgb[3 * (size_t)id + 1] = val[1]; rgb[3 * (size_t)id + 2] = val[2]; }
     }
     wg_total(n, dark_total);
+}
+
+__global__ __launch_bounds__(256) void k_light_resolve(int w, int h, int band_rows, int xs, int ys, const LightGather g, const uint32_t *__restrict__ slot_of_sample,
+                                                       float *__restrict__ rgb, unsigned long long *__restrict__ dark_total, const lh_light_tab_t tab)
+{
+    item_resolve(w, h, band_rows, xs, ys, light_slot{g, tab}, slot_of_sample, rgb, dark_total);
+}
+
+__global__ __launch_bounds__(256) void k_light_batch_resolve(const BatchList bl, const LightGather g, const uint32_t *__restrict__ slot_of_entry,
+                                                             uint32_t *__restrict__ visible, float *__restrict__ rgb,
+                                                             unsigned long long *__restrict__ dark_total, const lh_light_tab_t tab)
+{
+    item_batch_resolve(bl, light_slot{g, tab}, slot_of_entry, visible, rgb, dark_total);
 }
 
 /* ---- area lights (lh_area.h): the light stage's shape with S samples per light -- one byte per item at element (slot * L + l) * S + s; the resolves make every
@@ -888,62 +907,30 @@ __global__ void k_area_rays(size_t nslots, const unsigned long long *__restrict_
 struct AreaGather { const double *hitrec; const unsigned long long *key; unsigned long long seed; const uint8_t *occ; };
 
 /* the mask and value of a hit slot, and how many of its L S items are not open */
-__device__ __forceinline__ uint32_t area_slot(const AreaGather &g, const lh_area_tab_t &tab, uint32_t slot, float val[3], unsigned int &closed)
-{
-    LH_NC
-    const size_t LS = (size_t)tab.L * (size_t)tab.S;
-    const double *h = g.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
-    const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
-    return lh_area_value(O, Ns, tab.l, tab.L, tab.S, tab.emitters, tab.bound, tab.uniforms ? tab.uniforms + 3 * LS * (size_t)slot : NULL, g.key[slot], g.seed,
-                         g.occ + (size_t)slot * LS, val, &closed);
-}
+struct area_slot {
+    const AreaGather &g; const lh_area_tab_t &tab;
+    __device__ __forceinline__ uint32_t operator()(uint32_t slot, float val[3], unsigned int &closed) const
+    {
+        LH_NC
+        const size_t LS = (size_t)tab.L * (size_t)tab.S;
+        const double *h = g.hitrec + LH_HITREC_DOUBLES * (size_t)slot;
+        const double O[3] = {h[0], h[1], h[2]}, Ns[3] = {h[9], h[10], h[11]};
+        return lh_area_value(O, Ns, tab.l, tab.L, tab.S, tab.emitters, tab.bound, tab.uniforms ? tab.uniforms + 3 * LS * (size_t)slot : NULL, g.key[slot], g.seed,
+                             g.occ + (size_t)slot * LS, val, &closed);
+    }
+};
 
-/* k_light_resolve for the area-light tile, a thread per pixel */
 __global__ __launch_bounds__(256) void k_area_resolve(int w, int h, int band_rows, int xs, int ys, const AreaGather g, const uint32_t *__restrict__ slot_of_sample,
                                                       float *__restrict__ rgb, unsigned long long *__restrict__ dark_total, const lh_area_tab_t tab)
 {
-    LH_NC
-    const size_t pix = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool inside = pix < (size_t)w * h;
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    unsigned int n = 0;
-    const int S = inside ? xs * ys : 0;
-    for (int s = 0; s < S; s++) {
-        const uint32_t slot = slot_of_sample[pix * S + s];
-        float val[3] = {0.0f, 0.0f, 0.0f};
-        if (slot != LH_MISS_PRIM) { unsigned int c; (void)area_slot(g, tab, slot, val, c); n += c; }
-        a0 = a0 + (double)val[0]; a1 = a1 + (double)val[1]; a2 = a2 + (double)val[2];
-    }
-    if (inside) {
-        const double inv = (double)1.0 / (xs * ys);
-        float f0 = (float)(a0 * inv), f1 = (float)(a1 * inv), f2 = (float)(a2 * inv);
-        if (f0 < 0.0f) f0 = 0.0f;
-        if (f1 < 0.0f) f1 = 0.0f;
-        if (f2 < 0.0f) f2 = 0.0f;
-        float *o = pixel_out(rgb, pix, w, band_rows);
-        o[0] = f0; o[1] = f1; o[2] = f2;
-    }
-    wg_total(n, dark_total);
+    item_resolve(w, h, band_rows, xs, ys, area_slot{g, tab}, slot_of_sample, rgb, dark_total);
 }
 
-/* k_light_batch_resolve for the area-light stage, a thread per list entry */
 __global__ __launch_bounds__(256) void k_area_batch_resolve(const BatchList bl, const AreaGather g, const uint32_t *__restrict__ slot_of_entry,
                                                             uint32_t *__restrict__ visible, float *__restrict__ rgb,
                                                             unsigned long long *__restrict__ dark_total, const lh_area_tab_t tab)
 {
-    LH_NC
-    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
-    uint32_t id = 0;
-    unsigned int n = 0;
-    if (batch_entry(bl, k, id)) {
-        const uint32_t slot = slot_of_entry ? slot_of_entry[k] : LH_AO_NO_HIT;
-        uint32_t mask = LH_AO_NO_HIT;
-        float val[3] = {0.0f, 0.0f, 0.0f};
-        if (slot != LH_AO_NO_HIT) mask = area_slot(g, tab, slot, val, n);
-        if (visible) visible[id] = mask;
-        if (rgb) { rgb[3 * (size_t)id] = val[0]; rgb[3 * (size_t)id + 1] = val[1]; rgb[3 * (size_t)id + 2] = val[2]; }
-    }
-    wg_total(n, dark_total);
+    item_batch_resolve(bl, area_slot{g, tab}, slot_of_entry, visible, rgb, dark_total);
 }
 
 

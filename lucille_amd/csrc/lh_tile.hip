@@ -79,13 +79,33 @@ static int stage_report(const stage_timer &tm, const void *d_clk, size_t nwaves,
 /* ---- the gather stage: one description of its transport ------------------------------------------------------------------------------------
  * The kind (LH_GATHER_*, lh_gather.h) with its checked parameters, as the entry points hand it on: AO has none and offsets its rays by 1e-6 along Ns */
 struct gather_params { int kind; double eps; lh_dirt_params_t dirt; lh_env_params_t env; const lh_light_t *lights; int nlights;          /* lights: LH_GATHER_LIGHT, the caller's HOST table (lh_lights.h) */
-                       lh_area_tab_t area; };          /* LH_GATHER_AREA: the caller's lights, the accelerator's emitter table, S, the bound (lh_area.h) */
-/* the sample grid of a stage: the hemisphere's -- or, for the light stage, one "sample" per light: ntheta = the lights, nphi = 1, so that work item
- * slot * N + r is item (slot, l = r) in every kernel and buffer the stage shares with the gathers */
+                       lh_area_tab_t area;             /* LH_GATHER_AREA: the caller's lights, the accelerator's emitter table, S, the bound (lh_area.h) */
+                       ao_grid items; };               /* an item kind's grid (gather_check): LIGHT nphi = 1, ntheta = the lights; AREA r = l * S + s, "nphi" lights of "ntheta" samples */
+
+/* what the code around the stage reads of a kind, one row per LH_GATHER_* -- a new kind is a row here, its case in gather_check and its resolve.
+ * An item kind has one work item per (slot, light[, sample]) instead of a hemisphere sample: its ray kernel writes a bound per ray, the statistics count
+ * its work items, traced or not, and its resolve fetches no texture */
+struct gather_kind {
+    const char *device_name, *prefix;          /* the device entry point (a host form's messages carry it), and the prefix of a batch stage's messages */
+    const char *fused_name, *resolve_name;     /* in "... launch failed" */
+    lh_buf lh_gather_scratch::*left;           /* what the stage leaves per hit slot: the buffer a fused stage sizes and its kernel fills ... */
+    size_t slot_bytes, slot_bytes_n;           /* ... of slot_bytes + slot_bytes_n * N bytes per slot */
+    bool bounded; int mode;                    /* materialised: bounded launches of LH_DIRT_CHUNK rays through the ray dumps' kernels, or one plain launch; closest or any hit */
+    bool item;
+    int uniforms_per_item, radiance_floats;    /* replayed uniforms per gather ray; floats of `radiance` per ray */
+};
+static const gather_kind gather_kinds[LH_GATHER_KINDS] = {
+    {"lh_accel_ao_device", "lh_accel_ao_device: ", "fused AO", "resolve", &lh_gather_scratch::occcount, sizeof(unsigned int), 0, false, LH_MODE_ANY, false, 2, 1},          /* a count per slot */
+    {"lh_accel_dirt_device", "lh_accel_dirt_device: ", "fused dirt", "dirt resolve", &lh_gather_scratch::t, 0, 8, true, LH_MODE_CLOSEST, false, 2, 1},                     /* a double per ray */
+    {"lh_accel_env_device", "lh_accel_env_device: ", "fused environment-gather", "environment-gather resolve", &lh_gather_scratch::occ, 0, 1, false, LH_MODE_ANY, false, 2, 3},          /* a byte per ray */
+    {"lh_accel_lights_device", "lh_accel_lights_device: ", "fused light", "light resolve", &lh_gather_scratch::occ, 0, 1, true, LH_MODE_ANY, true, 2, 3},                  /* a byte per shadow ray */
+    {"lh_accel_area_lights_device", "lh_accel_area_lights_device: ", "fused area-light", "area-light resolve", &lh_gather_scratch::occ, 0, 1, true, LH_MODE_ANY, true, 3, 3},          /* the same, N = L x S */
+};
+
+/* the sample grid of a stage: the hemisphere's, or an item kind's own -- work item slot * N + r is item (slot, r) in every kernel and buffer the kinds share */
 static inline ao_grid gather_grid(const gather_params &p, int gather_nsamples)
 {
-    if (p.kind == LH_GATHER_AREA) return ao_grid{p.area.L, p.area.S, p.area.L * p.area.S};          /* r = l * S + s: "nphi" lights of "ntheta" samples each */
-    return p.kind == LH_GATHER_LIGHT ? ao_grid{1, p.nlights, p.nlights} : ao_sample_grid(gather_nsamples);
+    return gather_kinds[p.kind].item ? p.items : ao_sample_grid(gather_nsamples);
 }
 /* ... and what ao_region / ao_batch_device make of it, once, at their top, for the stage and the resolves: the scratch entry of the kind and the caller
  * (lh_accel::gather), the light of an environment gather -- the accelerator's environment, or while a sky is set (lh_sky.h) the sun-and-sky light, with
@@ -99,11 +119,6 @@ struct gather_desc {
     lh_tex_args_t tex_store; const lh_tex_args_t *tex;
     const char *prefix;
 };
-static const char *const gather_device_name[LH_GATHER_KINDS] = {"lh_accel_ao_device", "lh_accel_dirt_device", "lh_accel_env_device", "lh_accel_lights_device",
-                                                                   "lh_accel_area_lights_device"};
-static const char *const gather_prefix[LH_GATHER_KINDS] = {"lh_accel_ao_device: ", "lh_accel_dirt_device: ", "lh_accel_env_device: ", "lh_accel_lights_device: ",
-                                                              "lh_accel_area_lights_device: "};
-
 static void gather_describe(lh_accel_t *a, const gather_params &p, int where, gather_desc *d)
 {
     d->p = p; d->where = where;
@@ -112,7 +127,7 @@ static void gather_describe(lh_accel_t *a, const gather_params &p, int where, ga
     d->sky = (p.kind == LH_GATHER_ENV && a->sky_set) ? &a->sky : NULL;
     d->sun_dir = (d->sky && (d->sky->sky.flags & LH_SKY_SUN)) ? d->sky->sky.sun_dir : NULL;
     d->tex = NULL;
-    d->prefix = where == LH_GATHER_TILE ? "" : gather_prefix[p.kind];
+    d->prefix = where == LH_GATHER_TILE ? "" : gather_kinds[p.kind].prefix;
 }
 
 /* what the stage left, as the resolves take it (lh_gather_left_t, lh_internal.h).  fused: the stage ended fused -- AO counted per slot, the environment
@@ -135,15 +150,14 @@ static lh_gather_left_t gather_left(const gather_desc &d, ao_grid g, uint64_t se
  *   AO    fused, the occluded rays of every slot counted in occcount; materialised, the any-hit byte of ray (slot, r) at element slot * N + r of occ;
  *   ENV   (lh_env.h) that byte either way: the resolve needs the answer of every RAY;
  *   DIRT  (lh_dirt.h) the t of every gather ray's bounded closest-hit record (lh_tmax.h, every bound far_clip), a double at element slot * N + r of t;
- *   LIGHT (lh_lights.h; N = the lights) the bounded any-hit byte of shadow ray (slot, l) at element slot * N + l of occ, 0 for an item that is not traced:
- *         fused, the persistent walk makes the item in its refill; materialised, one kernel writes rays and bounds and one bounded any-hit launch per
- *         LH_DIRT_CHUNK rays answers them;
- *   AREA  (lh_area.h; N = lights x samples) the same byte for item (slot, l, s) at element slot * N + l * S + s: fused, ray source 4 makes the item in the
- *         refill; materialised -- also with replayed uniforms, which the ray kernel reads from memory -- the light stage's two steps.
- * plan.fused: the kernel generates ray (slot, r) in its refill (lh_ao.h) -- nothing per gather ray goes through HBM but what is left
- * (lh_launch_trace_gather).  Else, and as the second try of a fused launch whose fix-up queue overflowed, materialised: gather rays in HBM (from
- * d_uniforms if given: the parity replay), then an any-hit batch, or for DIRT ONE bounded closest-hit launch per LH_DIRT_CHUNK rays through the ray
- * dumps' kernels with a bound array filled with far_clip.
+ *   LIGHT (lh_lights.h; N = the lights) the bounded any-hit byte of shadow ray (slot, l) at element slot * N + l of occ, 0 for an item that is not traced;
+ *   AREA  (lh_area.h; N = lights x samples) the same byte for item (slot, l, s) at element slot * N + l * S + s.
+ * The row of gather_kinds says which buffer that is and how a materialised stage launches.
+ * plan.fused: the kernel generates ray (slot, r) in its refill (lh_ao.h; an item kind: the item) -- nothing per gather ray goes through HBM but what
+ * is left (lh_launch_trace_gather).  Else, and as the second try of a fused launch whose fix-up queue overflowed, materialised: the kind's ray kernel
+ * writes the gather rays to HBM (from d_uniforms if given: the parity replay; the area kind reads its own from d.p.area), then one any-hit batch -- or,
+ * for a bounded kind, ONE bounded launch per LH_DIRT_CHUNK rays through the ray dumps' kernels: DIRT closest hit under a bound array filled with
+ * far_clip, the records' t kept; an item kind any hit under the bound its ray kernel wrote beside every ray, a byte kept.
  * plan.late (with fused only): the count stays on the device -- the buffers are sized for the worst case (nmax slots: every sample / entry hits), the
  * kernels read it at d_nhit -- and the stage costs ONE host round trip, at its end (round 5: the two in the middle were ~0.25 ms of a rank's 8.9 ms
  * share of the config-5 frame).  Else the count is read first: it sizes the ray arrays and the launch.
@@ -166,15 +180,9 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
     const char *prefix = d.prefix;
     bool fused = plan.fused != 0;
     const bool late = plan.late != 0;
-    /* what the stage leaves per hit slot: the buffer a fused stage sizes and its kernel fills, and the launch of a materialised one */
-    lh_buf *left; size_t slot_bytes; bool bounded = false; const char *fused_name;
-    switch (d.p.kind) {
-    case LH_GATHER_AO:  left = &b->occcount; slot_bytes = sizeof(unsigned int); fused_name = "fused AO"; break;                    /* a count per slot */
-    case LH_GATHER_ENV: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused environment-gather"; break;                    /* a byte per ray */
-    case LH_GATHER_LIGHT: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused light"; break;                               /* a byte per shadow ray */
-    case LH_GATHER_AREA: left = &b->occ; slot_bytes = (size_t)N; fused_name = "fused area-light"; break;                           /* the same, N = L x S */
-    default:            left = &b->t; slot_bytes = (size_t)N * 8; fused_name = "fused dirt"; bounded = true; break;                /* DIRT: a double per ray */
-    }
+    const gather_kind &K = gather_kinds[d.p.kind];
+    lh_buf *left = &(b->*K.left);
+    const size_t slot_bytes = K.slot_bytes + K.slot_bytes_n * (size_t)N;
     /* the stage's read-backs land in 1 KiB of pinned memory: 64 occlusion totals, the hit count, the queue's appends and overflow flag */
     if (!a->h_read) HIPCHK(hipHostMalloc(&a->h_read, 1024, hipHostMallocDefault));
     unsigned long long *h_nocc64 = (unsigned long long *)a->h_read, *h_nhit = h_nocc64 + 64; uint32_t *h_qc = (uint32_t *)(h_nocc64 + 65);
@@ -233,7 +241,7 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
         const lh_launch_ctx_t ctx = {lh_next_cursor(a), a->grid_blocks, a->min_active, a->tri_batch, &a->aoq[qslot].q, a->ncus, (void *)s};
         const lh_fused_out_t fo = {d.p.kind, left->p, d.p.dirt.far_clip};
         if (lh_launch_trace_gather(&sc, &src, &fo, cnt, &ctx) != 0)
-            return fail("%s%s launch failed: %s", prefix, fused_name, hipGetErrorString(hipGetLastError()));
+            return fail("%s%s launch failed: %s", prefix, K.fused_name, hipGetErrorString(hipGetLastError()));
         if (!late) {
             if (wait_queue() != 0) return -1;
             fused = h_qc[1] == 0;             /* more than LH_AO_QCAP uncertain gather rays: redo the stage materialised */
@@ -243,49 +251,45 @@ static int ao_stage(lh_accel_t *a, const gather_desc &d, size_t nmax, ao_grid g,
     auto materialised = [&]() -> int {
         const size_t nao = (size_t)(nhit * N);
         if (!nao) return 0;
-        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!bounded && ensure_buf(&b->occ, nao))) return -1;
-        if (d.p.kind == LH_GATHER_LIGHT || d.p.kind == LH_GATHER_AREA) {          /* 4-5. the light and area stages: rays and a bound per ray, then bounded any-hit launches through the ray dumps' kernels */
-            if (ensure_buf(&b->bound, nao * 8)) return -1;
-            if (d.p.kind == LH_GATHER_AREA) {
-                if (lh_render_launch_area_rays((size_t)nhit, NULL, &d.p.area, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
-                                               (double *)b->aorg.p, (double *)b->adir.p, (double *)b->bound.p, NULL, s) != 0)
-                    return fail("%sarea-light ray kernel launch failed", prefix);
-            } else
+        const bool closest = K.mode == LH_MODE_CLOSEST;          /* the records' t kept; else a byte per ray */
+        if (ensure_buf(&b->aorg, nao * 24) || ensure_buf(&b->adir, nao * 24) || (!closest && ensure_buf(&b->occ, nao)) ||
+            (K.item && ensure_buf(&b->bound, nao * 8))) return -1;
+        /* 4. gather rays; an item kind's kernel writes the bound of every ray beside it */
+        switch (d.p.kind) {
+        case LH_GATHER_LIGHT:
             if (lh_render_launch_light_rays((size_t)nhit, NULL, d.p.lights, d.p.nlights, (const double *)b->hitrec.p, (double *)b->aorg.p, (double *)b->adir.p,
                                             (double *)b->bound.p, s) != 0)
                 return fail("%slight ray kernel launch failed", prefix);
-            if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
-            for (size_t off = 0; off < nao; off += LH_DIRT_CHUNK) {
-                const size_t m = nao - off < LH_DIRT_CHUNK ? nao - off : LH_DIRT_CHUNK;
-                lh_launch_opt o = opt;
-                o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = (const double *)b->bound.p + off;
-                const lh_batch_t rays = {m, LH_MODE_ANY, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, NULL, NULL, NULL, NULL,
-                                         (uint8_t *)b->occ.p + off, cnt};
-                if (lh_launch(a, rays, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
-            }
-            return 0;
+            break;
+        case LH_GATHER_AREA:
+            if (lh_render_launch_area_rays((size_t)nhit, NULL, &d.p.area, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p,
+                                           (double *)b->aorg.p, (double *)b->adir.p, (double *)b->bound.p, NULL, s) != 0)
+                return fail("%sarea-light ray kernel launch failed", prefix);
+            break;
+        default:
+            if (lh_render_launch_ao_rays((size_t)nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
+                                         (const unsigned long long *)b->key.p, (double *)b->aorg.p, (double *)b->adir.p, s) != 0)
+                return fail("%sAO ray kernel launch failed", prefix);
         }
-        /* 4. gather rays */
-        if (lh_render_launch_ao_rays((size_t)nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
-                                     (const unsigned long long *)b->key.p, (double *)b->aorg.p, (double *)b->adir.p, s) != 0)
-            return fail("%sAO ray kernel launch failed", prefix);
-        /* 5. any-hit.  The abandoned fused pass is not counted (nor is what the caller counted before the stage) */
+        /* 5. the launch.  The abandoned fused pass is not counted (nor is what the caller counted before the stage) */
         if (cnt && fused_tried) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
-        if (bounded) {          /* 5. the dirt stage: closest hit under the bound far_clip, the records' t kept */
+        if (!K.bounded)
+            return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, b->aorg.p, b->adir.p, NULL, NULL, NULL, NULL, b->occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
+        if (!K.item) {          /* the dirt stage: one bound array of far_clip serves every chunk, as do the records' other members */
             const size_t nb = nao < LH_DIRT_CHUNK ? nao : LH_DIRT_CHUNK;
             if (ensure_buf(&b->t, nao * 8) || ensure_buf(&b->bound, nb * 8) || ensure_buf(&b->prim, nb * 4) || ensure_buf(&b->uv, nb * 16)) return -1;
             if (lh_render_launch_dirt_bounds(nb, d.p.dirt.far_clip, (double *)b->bound.p, s) != 0) return fail("%sbound kernel launch failed", prefix);
-            for (size_t off = 0; off < nao; off += LH_DIRT_CHUNK) {
-                const size_t m = nao - off < LH_DIRT_CHUNK ? nao - off : LH_DIRT_CHUNK;
-                lh_launch_opt o = opt;
-                o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = b->bound.p;
-                const lh_batch_t rays = {m, LH_MODE_CLOSEST, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, b->prim.p,
-                                         (double *)b->t.p + off, b->uv.p, (double *)b->uv.p + m, NULL, cnt};
-                if (lh_launch(a, rays, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
-            }
-            return 0;
         }
-        return lh_launch(a, lh_batch_t{nao, LH_MODE_ANY, b->aorg.p, b->adir.p, NULL, NULL, NULL, NULL, b->occ.p, cnt}, LH_VARIANT_DEFAULT, s, false, opt);
+        for (size_t off = 0; off < nao; off += LH_DIRT_CHUNK) {
+            const size_t m = nao - off < LH_DIRT_CHUNK ? nao - off : LH_DIRT_CHUNK;
+            lh_launch_opt o = opt;
+            o.indexed = true; o.idx_nrays = (uint32_t)m; o.tmax = (const double *)b->bound.p + (K.item ? off : 0);
+            lh_batch_t rays = {m, K.mode, (const double *)b->aorg.p + 3 * off, (const double *)b->adir.p + 3 * off, NULL, NULL, NULL, NULL, NULL, cnt};
+            if (closest) { rays.prim = b->prim.p; rays.t = (double *)b->t.p + off; rays.u = b->uv.p; rays.v = (double *)b->uv.p + m; }
+            else rays.occ = (uint8_t *)b->occ.p + off;
+            if (lh_launch(a, rays, LH_VARIANT_DEFAULT, s, true, o) != 0) return -1;
+        }
+        return 0;
     };
     /* 6. radiance, and its totals on their way to the host */
     auto resolved = [&](bool from_fused) -> int {
@@ -345,7 +349,7 @@ struct area_in { const lh_area_light_t *lights; int nlights; const lh_area_param
 static int gather_check(const char *what, int kind, const void *params, gather_params *p)
 {
     const lh_env_params_t env_def = LH_ENV_DEFAULTS;
-    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def, NULL, 0, {}};
+    *p = gather_params{kind, 1.0e-6, lh_dirt_params_t{0.0, 0.0, 0.0}, env_def, NULL, 0, {}, {}};
     if (kind == LH_GATHER_DIRT) {
         if (dirt_params(what, (const lh_dirt_params_t *)params, &p->dirt) != 0) return -1;
         p->eps = p->dirt.eps;
@@ -362,6 +366,7 @@ static int gather_check(const char *what, int kind, const void *params, gather_p
             return fail("%s: bad lights (1 .. %d lights in host memory, every v and rgb finite, a directional v not zero, flags within POINT | COSINE | INVSQ, "
                         "INVSQ only with POINT, reserved 0; eps %g finite and >= 0)", what, LH_LIGHTS_MAX, p->eps);
         p->lights = in->lights; p->nlights = in->nlights;
+        p->items = ao_grid{1, in->nlights, in->nlights};
     }
     if (kind == LH_GATHER_AREA) {
         const area_in *in = (const area_in *)params;
@@ -376,6 +381,7 @@ static int gather_check(const char *what, int kind, const void *params, gather_p
         memcpy(p->area.l, in->lights, sizeof(lh_area_light_t) * (size_t)in->nlights);
         p->area.emitters = (const lh_emitter_t *)in->a->d_emitters; p->area.uniforms = NULL; p->area.bound = prm.bound;
         p->area.L = in->nlights; p->area.S = prm.nsamples;
+        p->items = ao_grid{p->area.L, p->area.S, p->area.L * p->area.S};
     }
     return 0;
 }
@@ -410,7 +416,8 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     }
     if (ensure_buf(&b->slot, S * 4) || ensure_buf(&b->blocks, (size_t)nb * 4)) return -1;
     /* material textures (lh_tex.h): with at least one set, the resolve multiplies; with none, tex is NULL and the launch is the one it always was */
-    const bool no_tex = d.sky || p.kind == LH_GATHER_LIGHT || p.kind == LH_GATHER_AREA;          /* neither the sun-and-sky gather nor direct light fetches a texture */
+    const gather_kind &K = gather_kinds[p.kind];
+    const bool no_tex = d.sky || K.item;          /* neither the sun-and-sky gather nor direct light fetches a texture */
     if (a->ntex && !no_tex && lh_tex_sync(a) != 0) return -1;
     d.tex = no_tex ? NULL : lh_tex_args(a, r_prim, r_u, r_v, &d.tex_store);
     /* lh_accel_trace_statistics: the counting instantiations of the same kernels, accumulated over the batch */
@@ -439,9 +446,8 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     unsigned long long *d_nhit = a->d_total + 64;          /* the compaction's total, kept clear of the resolve's 64 counters */
     /* 6. the samples' values into the pixels */
     const lh_resolve_tile_t to = {w, h, band_rows, ps, ps, (const uint32_t *)b->slot.p, (float *)d_rgb, d.tex};
-    static const char *const resolve_name[LH_GATHER_KINDS] = {"resolve", "dirt resolve", "environment-gather resolve", "light resolve", "area-light resolve"};
     auto resolve = [&](const lh_gather_left_t &left) -> int {
-        if (lh_render_launch_tile_resolve(&to, &left, s) != 0) return fail("%s kernel launch failed", d.sky ? "sun-and-sky resolve" : resolve_name[p.kind]);
+        if (lh_render_launch_tile_resolve(&to, &left, s) != 0) return fail("%s kernel launch failed", d.sky ? "sun-and-sky resolve" : K.resolve_name);
         return 0;
     };
     ao_totals tot = {};
@@ -472,8 +478,8 @@ static int ao_region(lh_accel_t *a, const gather_params &p, const lh_camera_t *c
     if (tm && stage_report(*tm, a->r_diag.p, nwaves, S, tot.nhit, nao) != 0) return -1;
     if (p.kind == LH_GATHER_AO) { a->r_nsamples = S; a->r_nslots = (size_t)tot.nhit; a->r_nao = tot.fused ? 0 : nao; }
     if (cnt) {
-        /* (the light stage counts its work items, traced or not: the camera rays and hits x lights) */
-        lh_stat_add(a, tot.cnt, (p.kind == LH_GATHER_LIGHT || p.kind == LH_GATHER_AREA) ? (unsigned long long)S + nao : tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
+        /* (an item kind counts its work items, traced or not: the camera rays and hits x N) */
+        lh_stat_add(a, tot.cnt, K.item ? (unsigned long long)S + nao : tot.cnt[LH_CNT_RAYS], tot.nhit + tot.nocc, true);
         if (getenv("LH_DEBUG_COUNTERS")) {
             fprintf(stderr, "[lucille_hip] AO batch: rays by node visits (bucket b: [2^(b-1), 2^b)):");
             for (int k = 0; k < 24; k++) fprintf(stderr, " %llu", tot.cnt[LH_CNT_HIST + k]);
@@ -651,7 +657,7 @@ static int ao_batch_device(const char *what, lh_accel_t *a, const gather_params 
     };
     ao_totals tot;
     if (ao_stage(a, d, L, g, seed, d_uniforms, d_nhit, d_nocc, cnt, lh_launch_opt(), NULL, plan, resolve, s, &tot) != 0) return -1;
-    if (cnt) lh_stat_add(a, tot.cnt, (p.kind == LH_GATHER_LIGHT || p.kind == LH_GATHER_AREA) ? tot.nhit * (unsigned long long)g.N : tot.cnt[LH_CNT_RAYS], tot.nocc, true);      /* (the light stage counts its work items, traced or not) */
+    if (cnt) lh_stat_add(a, tot.cnt, gather_kinds[p.kind].item ? tot.nhit * (unsigned long long)g.N : tot.cnt[LH_CNT_RAYS], tot.nocc, true);      /* (an item kind counts its work items, traced or not) */
     if (cnt && p.kind != LH_GATHER_AO) a->last_retraced = tot.cnt[LH_CNT_RETRACED];          /* the gather rays that went through the fix-up queue (lh_accel_last_retraced) */
     return 0;
 }
@@ -696,14 +702,18 @@ extern "C" int lh_accel_env_device(lh_accel_t *a, size_t n_rays, const void *d_o
                                d_uniforms, d_index, n_index, d_count, d_occluded_count, d_rgb, stream);
 }
 
-extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
-                                       const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
-                                       const void *d_uniforms, void *d_slot_of_ray, void *d_nslots, void *d_ao_org, void *d_ao_dir,
-                                       size_t capacity_rays, void *stream)
+/* lh_accel_ao_rays_device / _light_rays_device / _area_light_rays_device behind the refusal of their parameters (p: from gather_check; AO has none): only
+ * the gather rays of the batch's hits, for a caller who traces them itself -- the compaction's slots and count, then the kind's ray kernel with the count
+ * read on the device.  doubles: how the alignment refusal names the double outputs; d_tmax_out: an item kind's bounds, d_weight_out (or NULL): the area
+ * kind's weights.  Asynchronous: a table of lights travels in the ray kernel's arguments, nothing is read back */
+static int gather_rays_device(const char *what, lh_accel_t *a, gather_params p, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim,
+                              const void *d_t, const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key, const void *d_uniforms,
+                              void *d_slot_of_ray, void *d_nslots, void *d_org_out, void *d_dir_out, void *d_tmax_out, void *d_weight_out, const char *doubles,
+                              size_t capacity_rays, void *stream)
 {
-    lh_guard guard(a);
-    const char *what = "lh_accel_ao_rays_device";
-    if ((((uintptr_t)d_ao_org | (uintptr_t)d_ao_dir) & 7u) != 0) return fail("%s: the ray arrays are doubles: a pointer is not 8-byte aligned", what);
+    const bool item = gather_kinds[p.kind].item;
+    if ((((uintptr_t)d_org_out | (uintptr_t)d_dir_out | (uintptr_t)d_tmax_out | (uintptr_t)d_weight_out) & 7u) != 0)
+        return fail("%s: the %s arrays are doubles: a pointer is not 8-byte aligned", what, doubles);
     const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, gather_nsamples, d_key, d_uniforms,
                                  NULL, 0, NULL, d_slot_of_ray, d_nslots);
     if (go < 0) return go;
@@ -712,11 +722,13 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
         if (d_nslots) { HIPCHK(hipSetDevice(a->device)); HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s)); }
         return 0;
     }
-    if (!d_slot_of_ray || !d_nslots || !d_ao_org || !d_ao_dir) return fail("%s: NULL output array", what);
-    const ao_grid g = ao_sample_grid(gather_nsamples);
-    if (capacity_rays / (size_t)g.N < n_rays || capacity_rays < n_rays * (size_t)g.N)
-        return fail("%s: capacity_rays %zu does not cover the worst case n_rays * N = %zu x %d", what, capacity_rays, n_rays, g.N);
-    if ((n_rays * (size_t)g.N + 255) / 256 > 0x7fffffffu) return fail("%s: more than 2^39 AO rays in one call", what);
+    if (!d_slot_of_ray || !d_nslots || !d_org_out || !d_dir_out || (item && !d_tmax_out)) return fail("%s: NULL output array", what);
+    const ao_grid g = gather_grid(p, gather_nsamples);
+    const size_t N = (size_t)g.N;
+    if (capacity_rays / N < n_rays || (!item && capacity_rays < n_rays * N))
+        return fail("%s: capacity_rays %zu does not cover the worst case n_rays * %s = %zu x %zu", what, capacity_rays,
+                    p.kind == LH_GATHER_AO ? "N" : p.kind == LH_GATHER_LIGHT ? "nlights" : "nlights * nsamples", n_rays, N);
+    if (!item && (n_rays * N + 255) / 256 > 0x7fffffffu) return fail("%s: more than 2^39 AO rays in one call", what);
     HIPCHK(hipSetDevice(a->device));
     if (a->hs->bvh.ntris == 0) {
         HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
@@ -724,19 +736,46 @@ extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void 
         return 0;
     }
     const unsigned nb = (unsigned)((n_rays + 255) / 256);
-    lh_gather_scratch *b = &a->gather[LH_GATHER_AO][LH_GATHER_BATCH];
+    lh_gather_scratch *b = &a->gather[p.kind][LH_GATHER_BATCH];
     if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65) || ensure_buf(&b->blocks, (size_t)nb * 4) ||
         ensure_buf(&b->hitrec, n_rays * 96) || ensure_buf(&b->key, n_rays * 8)) return -1;
     unsigned long long *d_nhit = (unsigned long long *)b->totals.p;
     if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
                                        (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
                                        (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)d_slot_of_ray,
-                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, 1.0e-6, s) != 0)
+                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, p.eps, s) != 0)
         return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
-                                         (const unsigned long long *)b->key.p, (double *)d_ao_org, (double *)d_ao_dir, s) != 0)
-        return fail("%s: AO ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
-    return 0;
+    switch (p.kind) {
+    case LH_GATHER_LIGHT:
+        if (lh_render_launch_light_rays(n_rays, d_nhit, p.lights, p.nlights, (const double *)b->hitrec.p, (double *)d_org_out, (double *)d_dir_out,
+                                        (double *)d_tmax_out, s) != 0)
+            return fail("%s: light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return 0;
+    case LH_GATHER_AREA:
+        p.area.uniforms = (const double *)d_uniforms;
+        if (lh_render_launch_area_rays(n_rays, d_nhit, &p.area, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p, (double *)d_org_out,
+                                       (double *)d_dir_out, (double *)d_tmax_out, (double *)d_weight_out, s) != 0)
+            return fail("%s: area-light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return 0;
+    default:
+        if (lh_render_launch_ao_rays_counted(n_rays, d_nhit, g.ntheta, g.nphi, seed, (const double *)b->hitrec.p, (const double *)d_uniforms,
+                                             (const unsigned long long *)b->key.p, (double *)d_org_out, (double *)d_dir_out, s) != 0)
+            return fail("%s: AO ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
+        return 0;
+    }
+}
+
+extern "C" int lh_accel_ao_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
+                                       const void *d_u, const void *d_v, int gather_nsamples, uint64_t seed, const void *d_key,
+                                       const void *d_uniforms, void *d_slot_of_ray, void *d_nslots, void *d_ao_org, void *d_ao_dir,
+                                       size_t capacity_rays, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_accel_ao_rays_device";
+    gather_params p;
+    if (gather_check(what, LH_GATHER_AO, NULL, &p) != 0) return -1;          /* (no parameters: the double outputs' alignment is its first refusal) */
+    return gather_rays_device(what, a, p, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed, d_key, d_uniforms, d_slot_of_ray, d_nslots,
+                              d_ao_org, d_ao_dir, NULL, NULL, "ray", capacity_rays, stream);
 }
 
 /* lh_accel_ao_host / _dirt_host / _env_host (radiance: 3 floats per ray for ENV): the parameters' refusal first, then host arrays up, the device call
@@ -752,11 +791,12 @@ static int gather_batch_host(const char *what, int kind, const void *params, lh_
     if (go <= 0) return go;
     if (!occluded_count && !radiance) return fail("%s: both outputs are NULL", what);
     const size_t n = n_rays;
-    const size_t need = uniforms ? (size_t)(kind == LH_GATHER_AREA ? 3 : 2) * gather_grid(p, gather_nsamples).N * n : 0;          /* worst case: every ray hits */
+    const gather_kind &K = gather_kinds[kind];
+    const size_t need = uniforms ? (size_t)K.uniforms_per_item * gather_grid(p, gather_nsamples).N * n : 0;          /* worst case: every ray hits */
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t nrad = (kind == LH_GATHER_ENV || kind == LH_GATHER_LIGHT || kind == LH_GATHER_AREA) ? 3 * n : n;          /* floats of `radiance` */
+    const size_t nrad = (size_t)K.radiance_floats * n;          /* floats of `radiance` */
     if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 2 * sizeof(uint32_t) * n + sizeof(float) * nrad)) return -1;
     double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
     double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
@@ -770,7 +810,7 @@ static int gather_batch_host(const char *what, int kind, const void *params, lh_
     HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
     if (key) HIPCHK(hipMemcpyAsync(d_key, key, b_d, hipMemcpyHostToDevice, s));
     if (need) HIPCHK(hipMemcpyAsync(d_uni, uniforms, need * sizeof(double), hipMemcpyHostToDevice, s));
-    if (ao_batch_device(gather_device_name[kind], a, p, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
+    if (ao_batch_device(K.device_name, a, p, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
                         key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s) != 0) return -1;
     if (occluded_count) HIPCHK(hipMemcpyAsync(occluded_count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
     if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * nrad, hipMemcpyDeviceToHost, s));
@@ -827,8 +867,7 @@ extern "C" int lh_render_lights_tile(lh_accel_t *a, const lh_camera_t *cam, int 
     return gather_tile("lh_render_lights_tile", LH_GATHER_LIGHT, &in, a, cam, x0, y0, w, h, ps, 1, 0, NULL, d_rgb, stats, stream);
 }
 
-/* the shadow rays alone, shaped like lh_accel_ao_rays_device: the compaction's slots and count, then ray (slot, l) and its bound at element slot * L + l.
- * Asynchronous: the table travels in the ray kernel's arguments, nothing is read back */
+/* the shadow rays alone (gather_rays_device): ray (slot, l) and its bound at element slot * L + l */
 extern "C" int lh_accel_light_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
                                           const void *d_u, const void *d_v, const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
                                           void *d_slot_of_ray, void *d_nslots, void *d_org_out, void *d_dir_out, void *d_tmax_out,
@@ -839,37 +878,8 @@ extern "C" int lh_accel_light_rays_device(lh_accel_t *a, size_t n_rays, const vo
     const lights_in in = {lights, nlights, params};
     gather_params p;
     if (gather_check(what, LH_GATHER_LIGHT, &in, &p) != 0) return -1;
-    if ((((uintptr_t)d_org_out | (uintptr_t)d_dir_out | (uintptr_t)d_tmax_out) & 7u) != 0) return fail("%s: the ray and bound arrays are doubles: a pointer is not 8-byte aligned", what);
-    const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, 1, NULL, NULL, NULL, 0, NULL, d_slot_of_ray, d_nslots);
-    if (go < 0) return go;
-    hipStream_t s = (hipStream_t)stream;
-    if (go == 0) {
-        if (d_nslots) { HIPCHK(hipSetDevice(a->device)); HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s)); }
-        return 0;
-    }
-    if (!d_slot_of_ray || !d_nslots || !d_org_out || !d_dir_out || !d_tmax_out) return fail("%s: NULL output array", what);
-    const size_t L = (size_t)p.nlights;
-    if (capacity_rays / L < n_rays) return fail("%s: capacity_rays %zu does not cover the worst case n_rays * nlights = %zu x %zu", what, capacity_rays, n_rays, L);
-    HIPCHK(hipSetDevice(a->device));
-    if (a->hs->bvh.ntris == 0) {
-        HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
-        HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s));
-        return 0;
-    }
-    const unsigned nb = (unsigned)((n_rays + 255) / 256);
-    lh_gather_scratch *b = &a->gather[LH_GATHER_LIGHT][LH_GATHER_BATCH];
-    if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65) || ensure_buf(&b->blocks, (size_t)nb * 4) ||
-        ensure_buf(&b->hitrec, n_rays * 96) || ensure_buf(&b->key, n_rays * 8)) return -1;
-    unsigned long long *d_nhit = (unsigned long long *)b->totals.p;
-    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
-                                       (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
-                                       NULL, (uint32_t *)b->blocks.p, (uint32_t *)d_slot_of_ray,
-                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, p.eps, s) != 0)
-        return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    if (lh_render_launch_light_rays(n_rays, d_nhit, p.lights, p.nlights, (const double *)b->hitrec.p, (double *)d_org_out, (double *)d_dir_out,
-                                    (double *)d_tmax_out, s) != 0)
-        return fail("%s: light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
-    return 0;
+    return gather_rays_device(what, a, p, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, 1, 0, NULL, NULL, d_slot_of_ray, d_nslots, d_org_out, d_dir_out,
+                              d_tmax_out, NULL, "ray and bound", capacity_rays, stream);
 }
 
 /* ---- area lights (lh_area.h): the light stage's pipeline with S samples per light, the AO stage's seed, keys and replayed uniforms ---- */
@@ -934,8 +944,7 @@ extern "C" int lh_render_area_lights_tile(lh_accel_t *a, const lh_camera_t *cam,
     return gather_tile("lh_render_area_lights_tile", LH_GATHER_AREA, &in, a, cam, x0, y0, w, h, ps, 1, seed, NULL, d_rgb, stats, stream);
 }
 
-/* the rays alone, shaped like lh_accel_light_rays_device: the compaction's slots and count, then item (slot, l, s) with its bound and weight at element
- * (slot * L + l) * S + s.  Asynchronous: the lights travel in the ray kernel's arguments, nothing is read back */
+/* the rays alone (gather_rays_device): item (slot, l, s) with its bound and weight (d_weight_out may be NULL) at element (slot * L + l) * S + s */
 extern "C" int lh_accel_area_light_rays_device(lh_accel_t *a, size_t n_rays, const void *d_org, const void *d_dir, const void *d_prim, const void *d_t,
                                                const void *d_u, const void *d_v, const lh_area_light_t *lights, int nlights, const lh_area_params_t *params,
                                                uint64_t seed, const void *d_key, const void *d_uniforms, void *d_slot_of_ray, void *d_nslots,
@@ -946,39 +955,8 @@ extern "C" int lh_accel_area_light_rays_device(lh_accel_t *a, size_t n_rays, con
     const area_in in = {lights, nlights, params, a};
     gather_params p;
     if (gather_check(what, LH_GATHER_AREA, &in, &p) != 0) return -1;
-    if ((((uintptr_t)d_org_out | (uintptr_t)d_dir_out | (uintptr_t)d_tmax_out | (uintptr_t)d_weight_out) & 7u) != 0)
-        return fail("%s: the ray, bound and weight arrays are doubles: a pointer is not 8-byte aligned", what);
-    const int go = ao_batch_args(what, a, n_rays, d_org && d_dir && d_prim && d_t && d_u && d_v, 1, d_key, d_uniforms, NULL, 0, NULL, d_slot_of_ray, d_nslots);
-    if (go < 0) return go;
-    hipStream_t s = (hipStream_t)stream;
-    if (go == 0) {
-        if (d_nslots) { HIPCHK(hipSetDevice(a->device)); HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s)); }
-        return 0;
-    }
-    if (!d_slot_of_ray || !d_nslots || !d_org_out || !d_dir_out || !d_tmax_out) return fail("%s: NULL output array", what);
-    const size_t LS = (size_t)p.area.L * (size_t)p.area.S;
-    if (capacity_rays / LS < n_rays) return fail("%s: capacity_rays %zu does not cover the worst case n_rays * nlights * nsamples = %zu x %zu", what, capacity_rays, n_rays, LS);
-    HIPCHK(hipSetDevice(a->device));
-    if (a->hs->bvh.ntris == 0) {
-        HIPCHK(hipMemsetAsync(d_slot_of_ray, 0xFF, n_rays * 4, s));
-        HIPCHK(hipMemsetAsync(d_nslots, 0, sizeof(uint32_t), s));
-        return 0;
-    }
-    const unsigned nb = (unsigned)((n_rays + 255) / 256);
-    lh_gather_scratch *b = &a->gather[LH_GATHER_AREA][LH_GATHER_BATCH];
-    if (ensure_buf(&b->totals, sizeof(unsigned long long) * 65) || ensure_buf(&b->blocks, (size_t)nb * 4) ||
-        ensure_buf(&b->hitrec, n_rays * 96) || ensure_buf(&b->key, n_rays * 8)) return -1;
-    unsigned long long *d_nhit = (unsigned long long *)b->totals.p;
-    if (lh_render_launch_batch_compact(&a->dev, (const double *)a->d_nrm9, n_rays, n_rays, NULL, NULL, (const double *)d_org, (const double *)d_dir,
-                                       (const uint32_t *)d_prim, (const double *)d_t, (const double *)d_u, (const double *)d_v,
-                                       (const unsigned long long *)d_key, (uint32_t *)b->blocks.p, (uint32_t *)d_slot_of_ray,
-                                       (double *)b->hitrec.p, (unsigned long long *)b->key.p, d_nhit, (uint32_t *)d_nslots, p.eps, s) != 0)
-        return fail("%s: compaction kernels failed: %s", what, hipGetErrorString(hipGetLastError()));
-    p.area.uniforms = (const double *)d_uniforms;
-    if (lh_render_launch_area_rays(n_rays, d_nhit, &p.area, seed, (const double *)b->hitrec.p, (const unsigned long long *)b->key.p, (double *)d_org_out,
-                                   (double *)d_dir_out, (double *)d_tmax_out, (double *)d_weight_out, s) != 0)
-        return fail("%s: area-light ray kernel launch failed: %s", what, hipGetErrorString(hipGetLastError()));
-    return 0;
+    return gather_rays_device(what, a, p, n_rays, d_org, d_dir, d_prim, d_t, d_u, d_v, 1, seed, d_key, d_uniforms, d_slot_of_ray, d_nslots, d_org_out, d_dir_out,
+                              d_tmax_out, d_weight_out, "ray, bound and weight", capacity_rays, stream);
 }
 
 /* the fetch alone: ri_texture_ibl_fetch (env_fetch, lh_pt.h) of the accelerator's environment for n directions.  Asynchronous, nothing read back */
