@@ -940,6 +940,47 @@ class HipAccel:
                "lh_accel_beam_visibility_host")
         return res
 
+    def _beam_tensor(self, what, name, T, dtypes, count):
+        import torch
+        if not (isinstance(T, torch.Tensor) and T.is_cuda and T.device.index == self.device and T.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous CUDA tensor on the accelerator's device %d" % (what, name, self.device))
+        if T.dtype not in dtypes or T.numel() < count:
+            raise ValueError("%s: %s must hold at least %d elements of %s" % (what, name, count, " / ".join(str(d) for d in dtypes)))
+        return _dptr(T)
+
+    def beam_visibility_device(self, d_org, d_dirs, d_result, stream=None):
+        """lh_accel_beam_visibility_device on the caller's tensors: d_org [n,3] and d_dirs [n,4,3] float64, d_result int32 with at
+        least n elements (the first n are written).  Enqueued on `stream` (a torch.cuda.Stream, a raw handle, or None: torch's
+        current stream); nothing is allocated or copied and the call does not wait for the device."""
+        import torch
+        what = "beam_visibility_device"
+        n = int(d_org.numel()) // 3
+        po = self._beam_tensor(what, "d_org", d_org, (torch.float64,), 3 * n)
+        pd = self._beam_tensor(what, "d_dirs", d_dirs, (torch.float64,), 12 * n)
+        pr = self._beam_tensor(what, "d_result", d_result, (torch.int32,), n)
+        with torch.cuda.device(self.device):
+            _check(self.L.lh_accel_beam_visibility_device(self.h, n, po, pd, pr, self._stream_handle(stream)), "lh_accel_beam_visibility_device")
+
+    def beam_raster_device(self, d_org, d_dirs, d_corners, width, height, frame, eye, fov, d_t, d_status, d_flags, stream=None):
+        """lh_accel_beam_raster_device on the caller's tensors: d_org [n,3], d_dirs [n,4,3], d_corners [n,3] float64; d_t float64
+        with at least n * height * width elements (planes that are not traced keep their contents), d_status int32 (n), d_flags
+        int64 / uint64 (4 n) or None.  Enqueued on `stream` as beam_visibility_device; nothing is allocated or copied."""
+        import torch
+        what = "beam_raster_device"
+        n = int(d_org.numel()) // 3
+        words = (torch.int64, getattr(torch, "uint64", torch.int64))
+        po = self._beam_tensor(what, "d_org", d_org, (torch.float64,), 3 * n)
+        pd = self._beam_tensor(what, "d_dirs", d_dirs, (torch.float64,), 12 * n)
+        pc = self._beam_tensor(what, "d_corners", d_corners, (torch.float64,), 3 * n)
+        pt = self._beam_tensor(what, "d_t", d_t, (torch.float64,), n * int(width) * int(height))
+        ps = self._beam_tensor(what, "d_status", d_status, (torch.int32,), n)
+        pf = None if d_flags is None else self._beam_tensor(what, "d_flags", d_flags, words, 4 * n)
+        pl = RasterPlane(int(width), int(height), (C.c_double * 9)(*np.asarray(frame, np.float64).reshape(-1)),
+                         (C.c_double * 3)(*np.asarray(eye, np.float64).reshape(-1)), float(fov))
+        with torch.cuda.device(self.device):
+            _check(self.L.lh_accel_beam_raster_device(self.h, n, po, pd, pc, C.addressof(pl), pt, ps, pf, self._stream_handle(stream)),
+                   "lh_accel_beam_raster_device")
+
     def beam_visibility_set(self, beams):
         """ri_bvh_intersect_beam_visibility for n beams a caller's ri_beam_set has ALREADY set up: beams = a structured array of
         BEAM_SET_DTYPE (lh_beam_set_t: org, dir[4], normal[4], dominant_axis, dirsign[3]) -> int32 [n]"""

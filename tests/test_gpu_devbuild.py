@@ -78,7 +78,13 @@ def test_device_built_scene_renders_the_same_frames_and_builds_fast():
     assert idv["ntriangles"] == ih["ntriangles"] == 322 * 4 ** 5
     assert idv["build_seconds"] < ih["build_seconds"]
     # beams need lucille's own tree: the call waits for the background build
-    bg = load_golden("beams_300")
+    # (the tessellated scene has no golden: the beams_300 soup, built on the device right here and asked at once)
+    from tests.test_beam import golden_case
+    bP, bidx, cases = golden_case("beams_300")
+    bdev, _ = dev_accel(bP, bidx)
+    for borg, bd, exp in cases:
+        assert np.array_equal(bdev.beam_visibility(borg, bd), exp)
+    bdev.close()
     host.close(); dev.close()
 
 
