@@ -477,6 +477,38 @@ int lh_ensure_buf(lh_buf *b, size_t bytes)
     return 0;
 }
 
+int lh_stage_carve(lh_buf *block, lh_field_t *f, int nf)
+{
+    size_t total = 0;
+    if (lh_stage_layout(f, nf, &total) != 0) return fail("a staging block of %d fields does not fit size_t", nf);
+    if (lh_ensure_buf(block, total) != 0) return -1;
+    lh_stage_place(f, nf, block->p);
+    return 0;
+}
+
+/* the copies of one direction; a failure is reported (the first one of the call: lh_stage_down passes a failed device form through) and waited behind */
+static int stage_copies(lh_accel_t *a, const lh_field_t *f, int nf, bool up, int rc)
+{
+    for (int k = 0; k < nf && rc == 0; k++) {
+        if (!f[k].bytes || !(up ? f[k].up != NULL : f[k].down != NULL)) continue;
+        const hipError_t e = up ? hipMemcpyAsync(f[k].dev, f[k].up, f[k].bytes, hipMemcpyHostToDevice, a->stream)
+                                : hipMemcpyAsync(f[k].down, f[k].dev, f[k].bytes, hipMemcpyDeviceToHost, a->stream);
+        if (e != hipSuccess) rc = fail("staging copy %s of field %d (%zu bytes) failed: %s", up ? "up" : "down", k, f[k].bytes, hipGetErrorString(e));
+    }
+    if (up && rc == 0) return 0;
+    const hipError_t e = hipStreamSynchronize(a->stream);
+    if (rc == 0 && e != hipSuccess) rc = fail("hipStreamSynchronize(a->stream) failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+int lh_stage_up(lh_accel_t *a, lh_field_t *f, int nf)
+{
+    if (lh_stage_carve(&a->stage, f, nf) != 0) return -1;
+    return stage_copies(a, f, nf, true, 0);
+}
+
+int lh_stage_down(lh_accel_t *a, const lh_field_t *f, int nf, int rc) { return stage_copies(a, f, nf, false, rc); }
+
 /* the scene's device arrays, a row each: the slot of the accelerator that owns the array, its size, and whether it is there
  * -- as the image's header h says (a receiver, before it has allocated), else as the slot says.  The first LH_IMAGE_ROWS rows,
  * in this order, are the scene image: a wire format between ranks (lh_dist.hip) */
@@ -552,13 +584,13 @@ static int upload_array(lh_accel_t *a, void **slot, const void *src, size_t byte
 
 static void release_device(lh_accel_t *a)
 {
-    lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->r_frame, &a->b_host,
+    lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->stage, &a->diag_drop,
                       &a->p_org2, &a->p_dir2, &a->p_path, &a->p_path2, &a->p_thr, &a->p_thr2, &a->p_rad, &a->p_counts};
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); i++) free_buf(bufs[i]);
     /* the gather stage's scratch table: every entry is lh_buf after lh_buf */
     static_assert(sizeof(a->gather) == sizeof(lh_buf) * LH_GATHER_BUFS * LH_GATHER_KINDS * 2, "lh_gather_scratch holds lh_buf members only");
     for (size_t i = 0; i < sizeof(a->gather) / sizeof(lh_buf); i++) free_buf((lh_buf *)a->gather + i);
-    for (lh_buf *b : {&a->e_host, &a->w_chain, &a->w_counts, &a->w_tile, &a->w_host}) free_buf(b);
+    for (lh_buf *b : {&a->w_chain, &a->w_counts, &a->w_tile}) free_buf(b);
     if (a->d_total) (void)hipFree(a->d_total);
     scene_row rows[LH_SCENE_ROWS];
     scene_rows(a, NULL, rows);
@@ -568,7 +600,7 @@ static void release_device(lh_accel_t *a)
     if (a->d_materials) (void)hipFree(a->d_materials);
     if (a->d_env_map) (void)hipFree(a->d_env_map);
     a->d_prim_mesh = a->d_materials = a->d_env_map = NULL;
-    free_buf(&a->r_state); free_buf(&a->r_uni); free_buf(&a->r_bands); free_buf(&a->r_diag);
+    free_buf(&a->r_bands); free_buf(&a->r_diag);
     if (a->h_read) { (void)hipHostFree(a->h_read); a->h_read = NULL; }
     a->d_total = NULL;
     if (a->d_danger) (void)hipFree(a->d_danger);
@@ -593,10 +625,9 @@ static void release_device(lh_accel_t *a)
         for (int b = 0; b < 3; b++) (void)hipStreamDestroy(a->pipe.s[b]);
         a->pipe.ready = 0;
     }
-    if (a->d_stage) (void)hipFree(a->d_stage);
     if (a->stream) (void)hipStreamDestroy(a->stream);
     a->d_cursor = a->d_counters = NULL;
-    a->d_stage = NULL; a->stage_bytes = 0; a->stream = NULL;
+    a->stream = NULL;
 }
 
 static void free_trash(lh_host_scene *hs)

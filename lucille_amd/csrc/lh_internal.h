@@ -7,6 +7,8 @@
  *                   one way a batch of rays (lh_batch_t) reaches the kernels' launcher (lh_kernels.hip lh_launch_trace)
  *   lh_plan.h       the geometry of a persistent launch (rows, checked pushes, the top of the tree in LDS, workgroups per CU, the cooperative
  *                   walk beside it, the cursor chunk): plain C, read by the launchers, by size_grid and by tests/cpu_model/lh_plan_check.c
+ *   lh_stage.h      the layout of a host form's staging block (fields in order, each on a 16-byte boundary): plain C, read by lh_stage_carve below and by
+ *                   tests/cpu_model/lh_stage_check.c
  *   lh_gather.h     the kinds of gather stage (AO, dirt, environment, direct light, area lights) and its plan -- fused, late -- for a tile or a batch: plain C, read by
  *                   lh_tile.hip and by tests/cpu_model/lh_gather_check.c
  *   lh_tile.hip     the callers on either side: AO tiles / bands / frames, hit epilogue, path-traced tiles
@@ -32,6 +34,7 @@
 #include "lh_device.h"
 #include "lh_order.h"
 #include "lh_tex.h"
+#include "lh_stage.h"
 
 /* lh_last_error() of the calling thread; lh_fail formats it and returns -1 */
 int lh_fail(const char *fmt, ...);
@@ -150,8 +153,10 @@ struct lh_accel {
     int default_variant;
     /* per-stream fix-up queues of the persistent launches (rays out of visit budget / stack rows, fragile AO hits) */
     struct { hipStream_t stream; int used; lh_fixq_t q; lh_buf order_ws; } aoq[LH_AOQ_SLOTS];      /* order_ws: the stream's workspace for dumps traced in bin order (lh_order.h) */
-    /* staging for host batches */
-    void *d_stage; size_t stage_bytes;
+    /* THE staging block of every entry point that takes host arrays (lh_stage_up / lh_stage_down below; the ray batches' host_chunk carves it itself):
+     * such a call holds the lock, runs on `stream` and synchronises before it returns, so one block serves them all, at the largest size any asked for */
+    lh_buf stage;
+    lh_buf diag_drop;                  /* lh_accel_intersect_diag_device: the hit records it throws away.  Its own block: it alone writes scratch on a CALLER's stream and returns unsynchronised */
     /* pipelined host batches: a ring of pinned in/out staging blocks and their device twins; rays up on s[0]; trace + records down alternate between s[1] and s[2] */
     struct { void *h_in[LH_PIPE_DEPTH_MAX], *h_out[LH_PIPE_DEPTH_MAX], *d_in[LH_PIPE_DEPTH_MAX], *d_out[LH_PIPE_DEPTH_MAX]; hipStream_t s[3];
              hipEvent_t in_done[LH_PIPE_DEPTH_MAX], done[LH_PIPE_DEPTH_MAX]; size_t cap; int depth, ready; } pipe;
@@ -162,24 +167,21 @@ struct lh_accel {
     lh_tex_block **tex; uint32_t ntex_slots, ntex;      /* per mesh (NULL: none), and how many meshes have one: > 0 makes the AO and dirt tiles multiply */
     void *d_tex_table; uint32_t tex_table_n; int tex_dirty;     /* lh_tex_desc_t per mesh on the device, rebuilt by lh_tex_sync after a setter */
     lh_environment_t env; void *d_env_map; int env_set;      /* env_set: lh_accel_set_environment was called (else the path tracer's environment is constant white) */
-    lh_buf r_state;                    /* lh_accel_state_build_host staging */
-    lh_buf r_uni;                      /* lh_render_ao_tile_host: caller uniforms on the device */
     lh_buf r_diag;                     /* LH_STAGE_TIMING: wave start / exit clocks */
     lh_buf r_bands;                    /* lh_render_ao_bands: first line of every band */
     void *h_read;                      /* 1 KiB of pinned host memory: the read-backs at the end of an AO batch (occlusion totals, hit count, queue flags) */
-    /* tile-render scratch (lh_render_ao_tile): camera rays and closest-hit records, the frame of the host entry points */
-    lh_buf r_org, r_dir, r_prim, r_t, r_u, r_v, r_frame;
+    /* tile-render scratch (lh_render_ao_tile): camera rays and closest-hit records */
+    lh_buf r_org, r_dir, r_prim, r_t, r_u, r_v;
     /* the gather stage's scratch, [LH_GATHER_*][LH_GATHER_TILE | LH_GATHER_BATCH]: every transport and either caller has a set of its own, so that
      * lh_render_scratch keeps showing the last AO tile whatever ran since */
     lh_gather_scratch gather[LH_GATHER_KINDS][2];
-    lh_buf b_host, e_host;             /* the staging of lh_accel_ao_host / _dirt_host / _env_host, and of lh_accel_environment_host / _sky_host */
     /* the sun-and-sky light (lh_accel_set_sky; lh_sky.h): sky_set 0 = none, the gather reads the environment */
     lh_sky_src_t sky; int sky_set;
     /* the emitter table of the area lights (lh_accel_set_emitters; lh_area.h): nemit records of 128 bytes on the device, NULL / 0 = none */
     void *d_emitters; uint64_t nemit;
     /* the refraction chain (lh_whitted.hip; lh_whitted.h): the chain's compacted rays, ids and records, sized by list entries; its counts (one per depth);
-     * the tile's camera rays, their records and the samples' colours; lh_accel_whitted_host's staging */
-    lh_buf w_chain, w_counts, w_tile, w_host;
+     * the tile's camera rays, their records and the samples' colours */
+    lh_buf w_chain, w_counts, w_tile;
     uint64_t last_retraced;            /* rays the last counted launch finished outside the main kernel */
     int ao_fused;                      /* AO rays generated inside the any-hit kernel (default); 0: materialised in HBM */
     uint32_t ao_budget;                /* visit budget of the fused AO stage (0: dev.ray_budget) */
@@ -237,6 +239,18 @@ enum { LH_FMT_F32 = 1, LH_FMT_Q16X4 = 4, LH_FMT_Q8 = 32 };
 int  lh_ensure_formats(lh_accel_t *a, int mask);
 int  lh_sync_ref(lh_accel_t *a, bool wait);          /* attach the background-built reference-order tree (wait: block for it) */
 int  lh_ensure_buf(lh_buf *b, size_t bytes);
+/* A host form is: fields, up, device form, down.
+ *     lh_field_t f[] = {lh_field_up(dir, 24 * n), lh_field_down(rgb, 12 * n)};          -- the block's layout, in order (lh_stage.h)
+ *     if (lh_stage_up(a, f, 2) != 0) return -1;
+ *     return lh_stage_down(a, f, 2, lh_accel_environment_device(a, n, f[0].dev, f[1].dev, a->stream));
+ * lh_stage_carve: lays the fields out (lh_stage.h), grows `block` to hold them and sets every f[k].dev (NULL for an absent field).
+ * lh_stage_up: carves a->stage, then enqueues a copy up on a->stream for every field that has one.
+ * lh_stage_down: rc is the device form's answer; if it is 0, enqueues a copy down for every field that has one; synchronises a->stream and returns rc,
+ * or -1 for a copy that failed.  Both synchronise before they return a failure, so that no copy from the caller's arrays is still in flight then, and
+ * leave lh_last_error at what failed FIRST.  The caller holds the accelerator's lock and has set the device */
+int  lh_stage_carve(lh_buf *block, lh_field_t *f, int nf);
+int  lh_stage_up(lh_accel_t *a, lh_field_t *f, int nf);
+int  lh_stage_down(lh_accel_t *a, const lh_field_t *f, int nf, int rc);
 int  lh_device_array_ok(const lh_accel_t *a, const void *p, size_t bytes, const char *who, const char *what);      /* `bytes` at p are memory of the accelerator's device: asked of the runtime */
 /* lh_tex.hip */
 void lh_tex_release(lh_accel_t *a);                  /* every texture block and the table (lh_accel_destroy) */
@@ -312,7 +326,6 @@ static inline void lh_stat_add(lh_accel_t *a, const unsigned long long *h, unsig
     a->stat[3] += rays; a->stat[4] += hits;
     if (slots) { a->stat_slots[0] += h[LH_CNT_NODE_SLOTS]; a->stat_slots[1] += h[LH_CNT_TRI_SLOTS]; a->stat_slots[2] += h[LH_CNT_REGROUP_SLOTS]; }
 }
-int  lh_ensure_stage(lh_accel_t *a, size_t bytes);
 
 /* lh_render.hip: the launchers lh_tile.hip calls (stream is a hipStream_t).  lh_render.hip includes this file too, so a prototype that drifts
  * from its definition does not compile -- under extern "C" it would still link */

@@ -303,15 +303,6 @@ extern "C" int lh_accel_order_statistics(lh_accel_t *a, uint64_t out[2], int cle
     return 0;
 }
 
-int lh_ensure_stage(lh_accel_t *a, size_t bytes)
-{
-    if (a->stage_bytes >= bytes) return 0;
-    if (a->d_stage) { (void)hipFree(a->d_stage); a->d_stage = NULL; a->stage_bytes = 0; }
-    HIPCHK(hipMalloc(&a->d_stage, bytes));
-    a->stage_bytes = bytes;
-    return 0;
-}
-
 /* ---- large host batches: chunks pipelined through pinned staging -----------------------------------
  * A pageable hipMemcpy moves ~12 GB/s; the link does ~50.  Rays are cut into chunks of `cap` rays; chunk k is copied into pinned
  * block k % depth by a pool of host threads, sent, traced and brought back on stream k & 1 while the host stages the next chunks
@@ -515,8 +506,8 @@ struct lh_staged { char *org, *dir, *tmax; double *t, *u, *v; uint32_t *prim, *d
 static int staged_block(lh_accel_t *a, size_t m, size_t el, bool rec16, bool bounded, bool diag, lh_staged *d)
 {
     const size_t b_ray = el * 3 * m, b_out = (2 * b_ray + (bounded ? el * m : 0) + 15) & ~(size_t)15, b_diag = diag ? sizeof(uint32_t) * 4 * m : 0;
-    if (lh_ensure_stage(a, b_out + 3 * sizeof(double) * m + sizeof(uint32_t) * m + b_diag + m + 64) != 0) return -1;
-    char *base = (char *)a->d_stage;
+    if (lh_ensure_buf(&a->stage, b_out + 3 * sizeof(double) * m + sizeof(uint32_t) * m + b_diag + m + 64) != 0) return -1;
+    char *base = (char *)a->stage.p;
     d->org = base; d->dir = base + b_ray; d->tmax = bounded ? base + 2 * b_ray : NULL;
     d->t = (double *)(base + b_out); d->u = d->t + m; d->v = d->u + m;
     d->prim = (uint32_t *)(d->v + m); d->diag = diag ? d->prim + m : NULL;
@@ -997,7 +988,7 @@ extern "C" int lh_accel_intersect_diag_host(lh_accel_t *a, size_t n, const doubl
 }
 
 /* the same for rays resident on the device, closest- or any-hit: d_diag n x 4 u32 (see lh_accel_intersect_diag_host); the hit
- * records go to the accelerator's staging block and are dropped.  What a cost map of a frame is made of (tools/ao_cost_map.py). */
+ * records go to a block of their own (diag_drop: this call writes it on the CALLER's stream and does not wait) and are dropped.  What a cost map of a frame is made of (tools/ao_cost_map.py). */
 extern "C" int lh_accel_intersect_diag_device(lh_accel_t *a, size_t n, const void *d_org, const void *d_dir, int mode, void *d_diag, void *stream)
 {
     lh_guard guard(a);
@@ -1008,11 +999,10 @@ extern "C" int lh_accel_intersect_diag_device(lh_accel_t *a, size_t n, const voi
     hipStream_t s = (hipStream_t)stream;
     if (a->hs->bvh.ntris == 0) { HIPCHK(hipMemsetAsync(d_diag, 0, sizeof(uint32_t) * 4 * n, s)); return 0; }
     const size_t b_d = sizeof(double) * n;
-    if (lh_ensure_stage(a, 3 * b_d + sizeof(uint32_t) * n + n + 64) != 0) return -1;
-    double *d_t = (double *)a->d_stage, *d_u = d_t + n, *d_v = d_u + n;
-    uint32_t *d_prim = (uint32_t *)(d_v + n); uint8_t *d_occ = (uint8_t *)(d_prim + n);
+    lh_field_t f[] = {lh_field_scratch(b_d), lh_field_scratch(b_d), lh_field_scratch(b_d), lh_field_scratch(sizeof(uint32_t) * n), lh_field_scratch(n)};      /* t | u | v | prim | occ */
+    if (lh_stage_carve(&a->diag_drop, f, 5) != 0) return -1;
     lh_launch_opt opt; opt.diag_out = (uint32_t *)d_diag;
-    return lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, d_prim, d_t, d_u, d_v, d_occ, NULL}, LH_VARIANT_SPEC, s, true, opt);
+    return lh_launch(a, lh_batch_t{n, mode, d_org, d_dir, f[3].dev, f[0].dev, f[1].dev, f[2].dev, f[4].dev, NULL}, LH_VARIANT_SPEC, s, true, opt);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1051,40 +1041,29 @@ static int beam_visibility_launch(lh_accel_t *a, size_t n, const void *d_org, co
     return 0;
 }
 
-extern "C" int lh_accel_beam_visibility_host(lh_accel_t *a, size_t n, const double *org, const double *dirs, int32_t *result)
+/* both host forms: the beams' own arrays (org | dirs) or the caller's preset beams, whichever the entry point has; the absent ones are absent fields */
+static int beam_visibility_host(lh_accel_t *a, size_t n, bool have_beams, const double *org, const double *dirs, const lh_beam_set_t *beams, int32_t *result)
 {
     lh_guard guard(a);
     if (!a || !a->committed) return fail("beam_visibility: accel not committed");
     if (n == 0) return 0;
-    if (!org || !dirs || !result) return fail("beam_visibility: NULL argument");
+    if (!have_beams || !result) return fail("beam_visibility: NULL argument");
     HIPCHK(hipSetDevice(a->device));
-    const size_t bo = sizeof(double) * 3 * n, bd = sizeof(double) * 12 * n, br = sizeof(int32_t) * n;
-    if (lh_ensure_stage(a, bo + bd + br + 64) != 0) return -1;
-    char *base = (char *)a->d_stage;
-    HIPCHK(hipMemcpyAsync(base, org, bo, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(base + bo, dirs, bd, hipMemcpyHostToDevice, a->stream));
-    if (lh_accel_beam_visibility_device(a, n, base, base + bo, base + bo + bd, a->stream) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(result, base + bo + bd, br, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    lh_field_t f[] = {lh_field_up(org, sizeof(double) * 3 * n), lh_field_up(dirs, sizeof(double) * 12 * n), lh_field_up(beams, sizeof(lh_beam_set_t) * n),
+                      lh_field_down(result, sizeof(int32_t) * n)};
+    if (lh_stage_up(a, f, 4) != 0) return -1;
+    return lh_stage_down(a, f, 4, beam_visibility_launch(a, n, f[0].dev, f[1].dev, f[3].dev, a->stream, (const lh_beam_set_t *)f[2].dev));
+}
+
+extern "C" int lh_accel_beam_visibility_host(lh_accel_t *a, size_t n, const double *org, const double *dirs, int32_t *result)
+{
+    return beam_visibility_host(a, n, org && dirs, org, dirs, NULL, result);
 }
 
 /* beams the caller's own ri_beam_set has set up (lh_beam_set_t: ri_bvh_intersect_beam_visibility's argument, bvh.h:208-221) */
 extern "C" int lh_accel_beam_visibility_set_host(lh_accel_t *a, size_t n, const lh_beam_set_t *beams, int32_t *result)
 {
-    lh_guard guard(a);
-    if (!a || !a->committed) return fail("beam_visibility: accel not committed");
-    if (n == 0) return 0;
-    if (!beams || !result) return fail("beam_visibility: NULL argument");
-    HIPCHK(hipSetDevice(a->device));
-    const size_t bb = sizeof(lh_beam_set_t) * n, br = sizeof(int32_t) * n;
-    if (lh_ensure_stage(a, bb + br + 64) != 0) return -1;
-    char *base = (char *)a->d_stage;
-    HIPCHK(hipMemcpyAsync(base, beams, bb, hipMemcpyHostToDevice, a->stream));
-    if (beam_visibility_launch(a, n, NULL, NULL, base + bb, a->stream, (const lh_beam_set_t *)base) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(result, base + bb, br, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    return beam_visibility_host(a, n, beams != NULL, NULL, NULL, beams, result);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1125,56 +1104,32 @@ static int beam_raster_launch(lh_accel_t *a, size_t n, const void *d_org, const 
     return 0;
 }
 
-extern "C" int lh_accel_beam_raster_host(lh_accel_t *a, size_t n, const double *org, const double *dirs, const double *corner,
-                                         const lh_raster_plane_t *plane, double *t_out, int32_t *status, uint64_t *flags)
+/* both host forms, as beam_visibility_host.  t_out goes up AND down: planes that are not traced keep the caller's contents */
+static int beam_raster_host(lh_accel_t *a, size_t n, bool have_beams, const double *org, const double *dirs, const lh_beam_set_t *beams, const double *corner,
+                            const lh_raster_plane_t *plane, double *t_out, int32_t *status, uint64_t *flags)
 {
     lh_guard guard(a);
     if (!a || !a->committed) return fail("beam_raster: accel not committed");
     if (n == 0) return 0;
-    if (!org || !dirs || !corner || !plane || !t_out || !status) return fail("beam_raster: NULL argument");
+    if (!have_beams || !corner || !plane || !t_out || !status) return fail("beam_raster: NULL argument");
     if (plane->width <= 0 || plane->height <= 0) return fail("beam_raster: the raster window is %d x %d", plane->width, plane->height);
     HIPCHK(hipSetDevice(a->device));
     const size_t px = (size_t)plane->width * (size_t)plane->height;
-    const size_t bo = sizeof(double) * 3 * n, bd = sizeof(double) * 12 * n, bt = sizeof(double) * px * n, bs = (sizeof(int32_t) * n + 7) & ~(size_t)7,
-                 bf = sizeof(uint64_t) * 4 * n;
-    if (lh_ensure_stage(a, 2 * bo + bd + bt + bs + bf + 64) != 0) return -1;
-    char *base = (char *)a->d_stage;
-    char *d_org = base, *d_dirs = base + bo, *d_corner = d_dirs + bd, *d_t = d_corner + bo, *d_st = d_t + bt, *d_fl = d_st + bs;
-    HIPCHK(hipMemcpyAsync(d_org, org, bo, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_dirs, dirs, bd, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_corner, corner, bo, hipMemcpyHostToDevice, a->stream));
-    /* planes that are not traced keep the caller's contents: the staging copy starts as the caller's */
-    HIPCHK(hipMemcpyAsync(d_t, t_out, bt, hipMemcpyHostToDevice, a->stream));
-    if (lh_accel_beam_raster_device(a, n, d_org, d_dirs, d_corner, plane, d_t, d_st, d_fl, a->stream) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(t_out, d_t, bt, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * n, hipMemcpyDeviceToHost, a->stream));
-    if (flags) HIPCHK(hipMemcpyAsync(flags, d_fl, bf, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    lh_field_t f[] = {lh_field_up(org, sizeof(double) * 3 * n), lh_field_up(dirs, sizeof(double) * 12 * n), lh_field_up(beams, sizeof(lh_beam_set_t) * n),
+                      lh_field_up(corner, sizeof(double) * 3 * n), lh_field_both(t_out, sizeof(double) * px * n), lh_field_down(status, sizeof(int32_t) * n),
+                      lh_field_down(flags, sizeof(uint64_t) * 4 * n)};
+    if (lh_stage_up(a, f, 7) != 0) return -1;
+    return lh_stage_down(a, f, 7, beam_raster_launch(a, n, f[0].dev, f[1].dev, f[3].dev, plane, f[4].dev, f[5].dev, f[6].dev, a->stream, (const lh_beam_set_t *)f[2].dev));
+}
+
+extern "C" int lh_accel_beam_raster_host(lh_accel_t *a, size_t n, const double *org, const double *dirs, const double *corner,
+                                         const lh_raster_plane_t *plane, double *t_out, int32_t *status, uint64_t *flags)
+{
+    return beam_raster_host(a, n, org && dirs, org, dirs, NULL, corner, plane, t_out, status, flags);
 }
 
 extern "C" int lh_accel_beam_raster_set_host(lh_accel_t *a, size_t n, const lh_beam_set_t *beams, const double *corner,
                                              const lh_raster_plane_t *plane, double *t_out, int32_t *status, uint64_t *flags)
 {
-    lh_guard guard(a);
-    if (!a || !a->committed) return fail("beam_raster: accel not committed");
-    if (n == 0) return 0;
-    if (!beams || !corner || !plane || !t_out || !status) return fail("beam_raster: NULL argument");
-    if (plane->width <= 0 || plane->height <= 0) return fail("beam_raster: the raster window is %d x %d", plane->width, plane->height);
-    HIPCHK(hipSetDevice(a->device));
-    const size_t px = (size_t)plane->width * (size_t)plane->height;
-    const size_t bb = (sizeof(lh_beam_set_t) * n + 15) & ~(size_t)15, bo = sizeof(double) * 3 * n, bt = sizeof(double) * px * n,
-                 bs = (sizeof(int32_t) * n + 7) & ~(size_t)7, bf = sizeof(uint64_t) * 4 * n;
-    if (lh_ensure_stage(a, bb + bo + bt + bs + bf + 64) != 0) return -1;
-    char *base = (char *)a->d_stage;
-    char *d_beams = base, *d_corner = base + bb, *d_t = d_corner + bo, *d_st = d_t + bt, *d_fl = d_st + bs;
-    HIPCHK(hipMemcpyAsync(d_beams, beams, sizeof(lh_beam_set_t) * n, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_corner, corner, bo, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_t, t_out, bt, hipMemcpyHostToDevice, a->stream));         /* planes that are not traced keep the caller's contents */
-    if (beam_raster_launch(a, n, NULL, NULL, d_corner, plane, d_t, d_st, d_fl, a->stream, (const lh_beam_set_t *)d_beams) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(t_out, d_t, bt, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipMemcpyAsync(status, d_st, sizeof(int32_t) * n, hipMemcpyDeviceToHost, a->stream));
-    if (flags) HIPCHK(hipMemcpyAsync(flags, d_fl, bf, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    return beam_raster_host(a, n, beams != NULL, NULL, NULL, beams, corner, plane, t_out, status, flags);
 }

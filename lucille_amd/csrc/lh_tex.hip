@@ -192,15 +192,7 @@ extern "C" int lh_accel_texture_host(lh_accel_t *a, size_t n_rays, const uint32_
     if (!rgba_out) return fail("%s: the output is NULL", what);
     HIPCHK(hipSetDevice(a->device));
     const size_t n = n_rays, b_d = sizeof(double) * n;
-    if (lh_ensure_buf(&a->r_state, 6 * b_d + sizeof(uint32_t) * n)) return -1;          /* out (4) | u | v | prim: the hit epilogue's staging */
-    double *d_out = (double *)a->r_state.p, *d_u = d_out + 4 * n, *d_v = d_u + n;
-    uint32_t *d_prim = (uint32_t *)(d_v + n);
-    hipStream_t s = a->stream;
-    HIPCHK(hipMemcpyAsync(d_u, u, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_v, v, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    if (lh_accel_texture_device(a, n, d_prim, d_u, d_v, NULL, 0, NULL, d_out, s) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(rgba_out, d_out, 4 * b_d, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    lh_field_t f[] = {lh_field_down(rgba_out, 4 * b_d), lh_field_up(u, b_d), lh_field_up(v, b_d), lh_field_up(prim, sizeof(uint32_t) * n)};
+    if (lh_stage_up(a, f, 4) != 0) return -1;
+    return lh_stage_down(a, f, 4, lh_accel_texture_device(a, n, f[3].dev, f[1].dev, f[2].dev, NULL, 0, NULL, f[0].dev, a->stream));
 }

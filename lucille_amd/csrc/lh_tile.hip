@@ -567,20 +567,11 @@ extern "C" int lh_render_ao_tile_host(lh_accel_t *a, const lh_camera_t *cam, int
     if (!cam || !rgb) return fail("lh_render_ao_tile_host: NULL argument");
     if (w <= 0 || h <= 0) return fail("lh_render_ao_tile_host: bad tile");
     HIPCHK(hipSetDevice(a->device));
-    const size_t fb = (size_t)w * h * 3 * sizeof(float);
-    if (ensure_buf(&a->r_frame, fb)) return -1;
-    void *d_uni = NULL;
-    if (uniforms) {
-        const size_t need = (size_t)2 * ao_sample_grid(gather_nsamples).N * w * h * ps * ps;       /* worst case: every sample hits */
-        if (nuniforms < need) return fail("lh_render_ao_tile_host: %zu uniforms given, the tile may consume %zu", nuniforms, need);
-        if (ensure_buf(&a->r_uni, need * sizeof(double))) return -1;
-        HIPCHK(hipMemcpyAsync(a->r_uni.p, uniforms, need * sizeof(double), hipMemcpyHostToDevice, a->stream));
-        d_uni = a->r_uni.p;
-    }
-    if (lh_render_ao_tile(a, cam, x0, y0, w, h, ps, gather_nsamples, seed, d_uni, a->r_frame.p, stats, a->stream) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(rgb, a->r_frame.p, fb, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    const size_t need = uniforms ? (size_t)2 * ao_sample_grid(gather_nsamples).N * w * h * ps * ps : 0;       /* worst case: every sample hits */
+    if (nuniforms < need) return fail("lh_render_ao_tile_host: %zu uniforms given, the tile may consume %zu", nuniforms, need);
+    lh_field_t f[] = {lh_field_up(uniforms, need * sizeof(double)), lh_field_down(rgb, (size_t)w * h * 3 * sizeof(float))};
+    if (lh_stage_up(a, f, 2) != 0) return -1;
+    return lh_stage_down(a, f, 2, lh_render_ao_tile(a, cam, x0, y0, w, h, ps, gather_nsamples, seed, f[0].dev, f[1].dev, stats, a->stream));
 }
 
 /* ------------------------------------------------------------------------ */
@@ -795,27 +786,14 @@ static int gather_batch_host(const char *what, int kind, const void *params, lh_
     const size_t need = uniforms ? (size_t)K.uniforms_per_item * gather_grid(p, gather_nsamples).N * n : 0;          /* worst case: every ray hits */
     if (nuniforms < need) return fail("%s: %zu uniforms given, the batch may consume %zu", what, nuniforms, need);
     HIPCHK(hipSetDevice(a->device));
-    const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    const size_t nrad = (size_t)K.radiance_floats * n;          /* floats of `radiance` */
-    if (ensure_buf(&a->b_host, 2 * b_ray + 3 * b_d + (key ? b_d : 0) + need * sizeof(double) + 2 * sizeof(uint32_t) * n + sizeof(float) * nrad)) return -1;
-    double *d_org = (double *)a->b_host.p, *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
-    double *d_key = d_v + n, *d_uni = d_key + (key ? n : 0);
-    uint32_t *d_prim = (uint32_t *)(d_uni + need), *d_cnt = d_prim + n; float *d_rad = (float *)(d_cnt + n);
-    hipStream_t s = a->stream;
-    HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_t, t, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_u, u, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_v, v, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    if (key) HIPCHK(hipMemcpyAsync(d_key, key, b_d, hipMemcpyHostToDevice, s));
-    if (need) HIPCHK(hipMemcpyAsync(d_uni, uniforms, need * sizeof(double), hipMemcpyHostToDevice, s));
-    if (ao_batch_device(K.device_name, a, p, n, d_org, d_dir, d_prim, d_t, d_u, d_v, gather_nsamples, seed,
-                        key ? d_key : NULL, need ? d_uni : NULL, NULL, 0, NULL, occluded_count ? d_cnt : NULL, radiance ? d_rad : NULL, s) != 0) return -1;
-    if (occluded_count) HIPCHK(hipMemcpyAsync(occluded_count, d_cnt, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (radiance) HIPCHK(hipMemcpyAsync(radiance, d_rad, sizeof(float) * nrad, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n, b_u32 = sizeof(uint32_t) * n;
+    enum { ORG, DIR, T, U, V, PRIM, KEY, UNI, CNT, RAD, NF };
+    lh_field_t f[NF] = {lh_field_up(org, b_ray), lh_field_up(dir, b_ray), lh_field_up(t, b_d), lh_field_up(u, b_d), lh_field_up(v, b_d), lh_field_up(prim, b_u32),
+                        lh_field_up(key, sizeof(uint64_t) * n), lh_field_up(uniforms, need * sizeof(double)),
+                        lh_field_down(occluded_count, b_u32), lh_field_down(radiance, sizeof(float) * K.radiance_floats * n)};
+    if (lh_stage_up(a, f, NF) != 0) return -1;
+    return lh_stage_down(a, f, NF, ao_batch_device(K.device_name, a, p, n, f[ORG].dev, f[DIR].dev, f[PRIM].dev, f[T].dev, f[U].dev, f[V].dev, gather_nsamples, seed,
+                                                   f[KEY].dev, f[UNI].dev, NULL, 0, NULL, f[CNT].dev, f[RAD].dev, a->stream));
 }
 
 extern "C" int lh_accel_ao_host(lh_accel_t *a, size_t n_rays, const double *org, const double *dir, const uint32_t *prim, const double *t,
@@ -987,13 +965,9 @@ extern "C" int lh_accel_environment_host(lh_accel_t *a, size_t n, const double *
     if (!dir || !rgb) return fail("%s: NULL array", what);
     if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
     HIPCHK(hipSetDevice(a->device));
-    if (ensure_buf(&a->e_host, n * (3 * sizeof(double) + 3 * sizeof(float)))) return -1;
-    double *d_dir = (double *)a->e_host.p; float *d_rgb = (float *)(d_dir + 3 * n);
-    HIPCHK(hipMemcpyAsync(d_dir, dir, sizeof(double) * 3 * n, hipMemcpyHostToDevice, a->stream));
-    if (lh_accel_environment_device(a, n, d_dir, d_rgb, a->stream) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    lh_field_t f[] = {lh_field_up(dir, sizeof(double) * 3 * n), lh_field_down(rgb, sizeof(float) * 3 * n)};
+    if (lh_stage_up(a, f, 2) != 0) return -1;
+    return lh_stage_down(a, f, 2, lh_accel_environment_device(a, n, f[0].dev, f[1].dev, a->stream));
 }
 
 /* the sun-and-sky light (lh_sky.h): set after commit, as the environment; the struct is copied, its Perez denominators are made here; NULL removes it */
@@ -1038,13 +1012,9 @@ extern "C" int lh_accel_sky_host(lh_accel_t *a, size_t n, const double *dir, flo
     if (!dir || !rgb) return fail("%s: NULL array", what);
     if (n >= ((size_t)1 << 39)) return fail("%s: more than 2^39 directions in one call", what);
     HIPCHK(hipSetDevice(a->device));
-    if (ensure_buf(&a->e_host, n * (3 * sizeof(double) + 3 * sizeof(float)))) return -1;
-    double *d_dir = (double *)a->e_host.p; float *d_rgb = (float *)(d_dir + 3 * n);
-    HIPCHK(hipMemcpyAsync(d_dir, dir, sizeof(double) * 3 * n, hipMemcpyHostToDevice, a->stream));
-    if (lh_accel_sky_device(a, n, d_dir, d_rgb, a->stream) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(rgb, d_rgb, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    lh_field_t f[] = {lh_field_up(dir, sizeof(double) * 3 * n), lh_field_down(rgb, sizeof(float) * 3 * n)};
+    if (lh_stage_up(a, f, 2) != 0) return -1;
+    return lh_stage_down(a, f, 2, lh_accel_sky_device(a, n, f[0].dev, f[1].dev, a->stream));
 }
 
 extern "C" int lh_render_scratch(lh_accel_t *a, int which, void **d_ptr, size_t *count)
@@ -1088,21 +1058,13 @@ extern "C" int lh_accel_state_build_host(lh_accel_t *a, size_t n, const double *
     if (!org || !dir || !prim || !t || !u || !v || !state) return fail("lh_accel_state_build_host: NULL argument");
     HIPCHK(hipSetDevice(a->device));
     const size_t b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n, b_state = sizeof(double) * LH_STATE_DOUBLES * n;
-    if (ensure_buf(&a->r_state, 2 * b_ray + 3 * b_d + sizeof(uint32_t) * n + 8 + b_state)) return -1;
-    char *base = (char *)a->r_state.p;
-    double *d_state = (double *)base, *d_org = (double *)(base + b_state), *d_dir = d_org + 3 * n, *d_t = d_dir + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
-    uint32_t *d_prim = (uint32_t *)(d_v + n);
-    HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_t, t, b_d, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_u, u, b_d, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_v, v, b_d, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, a->stream));
-    HIPCHK(hipMemsetAsync(d_state, 0, b_state, a->stream));
-    if (lh_accel_state_build_device(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, d_state, a->stream) != 0) return -1;
-    HIPCHK(hipMemcpyAsync(state, d_state, b_state, hipMemcpyDeviceToHost, a->stream));
-    HIPCHK(hipStreamSynchronize(a->stream));
-    return 0;
+    enum { STATE, ORG, DIR, T, U, V, PRIM, NF };
+    lh_field_t f[NF] = {lh_field_down(state, b_state), lh_field_up(org, b_ray), lh_field_up(dir, b_ray), lh_field_up(t, b_d), lh_field_up(u, b_d), lh_field_up(v, b_d),
+                        lh_field_up(prim, sizeof(uint32_t) * n)};
+    if (lh_stage_up(a, f, NF) != 0) return -1;
+    const hipError_t e = hipMemsetAsync(f[STATE].dev, 0, b_state, a->stream);          /* a miss's state, and every state of an empty scene, is zeros */
+    return lh_stage_down(a, f, NF, e != hipSuccess ? fail("hipMemsetAsync of the states failed: %s", hipGetErrorString(e))
+                                                   : lh_accel_state_build_device(a, n, f[ORG].dev, f[DIR].dev, f[PRIM].dev, f[T].dev, f[U].dev, f[V].dev, f[STATE].dev, a->stream));
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1337,16 +1299,15 @@ extern "C" int lh_render_ao_frame_host(lh_accel_t *a, const lh_camera_t *cam, in
     }
     HIPCHK(hipSetDevice(a->device));
     const int W = cam->width, H = cam->height;
-    if (ensure_buf(&a->r_frame, (size_t)tile * tile * 3 * sizeof(float))) return -1;
     std::vector<float> host((size_t)tile * tile * 3);
     lh_tile_stats_t tot = {0, 0, 0, 0};
     for (int y0 = 0; y0 < H; y0 += tile)
         for (int x0 = 0; x0 < W; x0 += tile) {
             const int w = (x0 + tile <= W) ? tile : W - x0, h = (y0 + tile <= H) ? tile : H - y0;
             lh_tile_stats_t st;
-            if (lh_render_ao_tile(a, cam, x0, y0, w, h, ps, gather_nsamples, seed, NULL, a->r_frame.p, &st, a->stream) != 0) return -1;
-            HIPCHK(hipMemcpyAsync(host.data(), a->r_frame.p, (size_t)w * h * 3 * sizeof(float), hipMemcpyDeviceToHost, a->stream));
-            HIPCHK(hipStreamSynchronize(a->stream));
+            lh_field_t f[] = {lh_field_down(host.data(), (size_t)w * h * 3 * sizeof(float))};          /* the device tile is the staging block: the first tile is the largest */
+            if (lh_stage_up(a, f, 1) != 0) return -1;
+            if (lh_stage_down(a, f, 1, lh_render_ao_tile(a, cam, x0, y0, w, h, ps, gather_nsamples, seed, NULL, f[0].dev, &st, a->stream)) != 0) return -1;
             /* the tile comes back with its rows already flipped (row 0 = pixel row y0+h-1) */
             for (int r = 0; r < h; r++)
                 memcpy(rgb + ((size_t)(H - (y0 + h) + r) * W + x0) * 3, host.data() + (size_t)r * w * 3, (size_t)w * 3 * sizeof(float));

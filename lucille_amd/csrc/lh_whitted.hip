@@ -292,27 +292,14 @@ extern "C" int lh_accel_whitted_host(lh_accel_t *a, size_t n_rays, const double 
     const int go = whitted_args(what, a, n_rays, org, dir, prim, t, u, v, NULL, 0, NULL, end_org, end_dir, bounces, rgb);
     if (go <= 0) return go;
     HIPCHK(hipSetDevice(a->device));
-    const size_t n = n_rays, b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n;
-    if (ensure_buf(&a->w_host, 4 * b_ray + 3 * b_d + sizeof(uint32_t) * 2 * n + sizeof(float) * 3 * n)) return -1;
-    double *d_org = (double *)a->w_host.p, *d_dir = d_org + 3 * n, *d_eo = d_dir + 3 * n, *d_ed = d_eo + 3 * n, *d_t = d_ed + 3 * n, *d_u = d_t + n, *d_v = d_u + n;
-    uint32_t *d_prim = (uint32_t *)(d_v + n), *d_b = d_prim + n; float *d_rgb = (float *)(d_b + n);
-    hipStream_t s = a->stream;
-    HIPCHK(hipMemcpyAsync(d_org, org, b_ray, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_dir, dir, b_ray, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_t, t, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_u, u, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_v, v, b_d, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_prim, prim, sizeof(uint32_t) * n, hipMemcpyHostToDevice, s));
-    if (end_org) HIPCHK(hipMemcpyAsync(d_eo, end_org, b_ray, hipMemcpyHostToDevice, s));
-    if (end_dir) HIPCHK(hipMemcpyAsync(d_ed, end_dir, b_ray, hipMemcpyHostToDevice, s));
-    if (lh_accel_whitted_device(a, n, d_org, d_dir, d_prim, d_t, d_u, d_v, &p, NULL, 0, NULL, bounces ? d_b : NULL, end_org ? d_eo : NULL,
-                                end_dir ? d_ed : NULL, rgb ? d_rgb : NULL, s) != 0) return -1;
-    if (bounces) HIPCHK(hipMemcpyAsync(bounces, d_b, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
-    if (end_org) HIPCHK(hipMemcpyAsync(end_org, d_eo, b_ray, hipMemcpyDeviceToHost, s));
-    if (end_dir) HIPCHK(hipMemcpyAsync(end_dir, d_ed, b_ray, hipMemcpyDeviceToHost, s));
-    if (rgb) HIPCHK(hipMemcpyAsync(rgb, d_rgb, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    return 0;
+    const size_t n = n_rays, b_ray = sizeof(double) * 3 * n, b_d = sizeof(double) * n, b_u32 = sizeof(uint32_t) * n;
+    enum { ORG, DIR, END_ORG, END_DIR, T, U, V, PRIM, BOUNCES, RGB, NF };
+    lh_field_t f[NF] = {lh_field_up(org, b_ray), lh_field_up(dir, b_ray), lh_field_both(end_org, b_ray), lh_field_both(end_dir, b_ray),
+                        lh_field_up(t, b_d), lh_field_up(u, b_d), lh_field_up(v, b_d), lh_field_up(prim, b_u32),
+                        lh_field_down(bounces, b_u32), lh_field_down(rgb, sizeof(float) * 3 * n)};
+    if (lh_stage_up(a, f, NF) != 0) return -1;
+    return lh_stage_down(a, f, NF, lh_accel_whitted_device(a, n, f[ORG].dev, f[DIR].dev, f[PRIM].dev, f[T].dev, f[U].dev, f[V].dev, &p, NULL, 0, NULL,
+                                                           f[BOUNCES].dev, f[END_ORG].dev, f[END_DIR].dev, f[RGB].dev, a->stream));
 }
 
 /* ri_transport_whitted per camera sample: the camera rays of lh_render_primary_rays, their closest hits, the chain over every sample (a
