@@ -69,8 +69,8 @@ typedef struct lh_dev_scene {
                                   record stores carry from there on; never read in the node step or the triangle pass.
                                   Work item k is ray index[k] (or k), ids >= idx_nrays are skipped */
     const void *tmax;          /* NULL, or: a bounded launch (lh_accel_intersect_device_tmax; always an indexed one) -- idx_nrays bounds by ray id, doubles, or floats
-                                  with LH_IO_RAYS_F32 (lh_tmax.h).  Read where a ray is loaded and where it retires, by the kernels of their own that such a
-                                  launch runs (k_trace_persist_tmax, k_coop_walk_tmax, k_fixups_tmax, k_trace_small_tmax): no other kernel looks at it */
+                                  with LH_IO_RAYS_F32 (lh_tmax.h).  Read where a ray is loaded and where it retires, by the TMAX = true instantiations that such a
+                                  launch runs (k_trace_persist_indexed, k_coop_walk, k_fixups, k_trace_small): no other kernel looks at it */
 } lh_dev_scene_t;
 
 /* traversal statistics accumulated by the COUNT variants (u64 each) */

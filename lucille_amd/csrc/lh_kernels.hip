@@ -848,6 +848,7 @@ __device__ __forceinline__ void copy_tree_top(const lh_dev_scene_t &sc, int *lh_
     }
 }
 
+/* the persistent kernel of the ray sources that have no hit records behind them: a ray dump's arrays (SRC 0), a path-traced pass's camera rays (SRC 2) */
 template <bool ANYHIT, bool COUNT, int WALK, int SRC, bool IO = false>
 __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_lane(
     lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
@@ -856,15 +857,17 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_l
     uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao, const FixQ fq)
 {
     extern __shared__ int lh_stack_lds[];          /* [stack entries][LH_BLOCK], sized at launch; then the top of the tree (sc.top_nodes x 64 bytes) */
-    if (SRC != 1 && sc.n_dev) n = *sc.n_dev;       /* the path tracer's bounce chain: the count the previous shading pass left */
-    if (SRC == 1 && ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* the fused AO stage behind a compaction nobody read back (<= the host's bound < 2^31) */
+    static_assert(!LH_SRC_GATHER(SRC), "the gather stages' kernel is k_trace_persist_stage");
+    if (sc.n_dev) n = *sc.n_dev;       /* the path tracer's bounce chain: the count the previous shading pass left */
     if (WALK != 7) copy_tree_top(sc, lh_stack_lds);
     trace_persist_lane<ANYHIT, COUNT, WALK, SRC, IO>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
 /* the persistent kernel of an indexed ray dump (lh_accel_intersect_device_indexed): n list entries at most, sc.n_dev (or NULL) the
- * number of them to trace.  A kernel of its own, so that the kernels above keep their names, registers and instruction streams */
-template <bool ANYHIT, bool COUNT, int WALK>
+ * number of them to trace.  A kernel of its own, so that the kernels above keep their names, registers and instruction streams.
+ * TMAX: a bounded ray dump (lh_accel_intersect_device_tmax) -- an indexed launch, a dense call being the identity list over its rays, whose rays carry a
+ * bound each (sc.tmax); every launch without bounds runs the TMAX = false instantiations */
+template <bool ANYHIT, bool COUNT, int WALK, bool TMAX = false>
 __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_indexed(
     lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
@@ -874,79 +877,95 @@ __global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_i
     extern __shared__ int lh_stack_lds[];
     if (sc.n_dev) { const uint32_t c = *sc.n_dev; if (c < n) n = c; }      /* min(*d_count, n_index) */
     if (WALK != 7) copy_tree_top(sc, lh_stack_lds);
-    trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
+    trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true, TMAX>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
 }
 
-/* the persistent kernel of a bounded ray dump (lh_accel_intersect_device_tmax): an indexed launch -- a dense call is the identity list over its rays --
- * whose rays carry a bound each (sc.tmax).  Again a kernel of its own: every launch without bounds runs the kernels above, unchanged */
-template <bool ANYHIT, bool COUNT, int WALK>
-__global__ __launch_bounds__(LH_BLOCK, WALK == 7 ? 3 : 4) void k_trace_persist_tmax(
-    lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
-    uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-    double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters,
-    uint32_t *cursor, int min_active, int tri_batch, const FixQ fq)
-{
-    extern __shared__ int lh_stack_lds[];
-    if (sc.n_dev) { const uint32_t c = *sc.n_dev; if (c < n) n = c; }      /* min(*d_count, n_index) */
-    if (WALK != 7) copy_tree_top(sc, lh_stack_lds);
-    trace_persist_lane<ANYHIT, COUNT, WALK, 0, true, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters, cursor, min_active, tri_batch, AoSrc{}, fq, lh_stack_lds);
-}
+/* ---- the fused gather stages (lh_launch_trace_gather): a row per kind (LH_GATHER_*, lh_gather.h) -- all that the kinds' kernels and launches differ in ---- */
+/* ANYHIT, SRC, TMAX, ENV: the template arguments of the persistent body, whose IO and IDX are a ray dump's (false), and -- with COOP_ENV for ENV: ray sources 3
+ * and 4 store their byte whatever it says, the rows keep the value their kernels were written with -- of the cooperative body.  PLAN: the kind for lh_plan_launch.
+ * Tab: what travels BY VALUE in the arguments of the kind's kernels (nothing to allocate, nothing whose release would have to wait for the launch); bind: the
+ * AoSrc a kernel walks with -- its own argument where there is no table (a copy with nothing bound into it moved the prologue's scalar loads and registers:
+ * profiles/stage_kernels.md), else a copy that points at the table; table: the host's checks of the caller's table and the copy (false: refused).  answer: where the stage leaves its answers
+ * (lh_fused_out_t, lh_device.h) -- the output fields of AoSrc, or the byte per item at `occ` (false: refused).  chunk: the rays a wave reserves, before the clamp.
+ * A new kind is a row here and its case in lh_launch_trace_gather. */
+struct NoTab {};
+struct StageRow {          /* what most rows say: the AO stage's any-hit walk over ray source 1, no table, the plain item order */
+    static constexpr bool ANYHIT = true, TMAX = false, ENV = false, COOP_ENV = false;
+    static constexpr int SRC = 1, PLAN = LH_PLAN_AO;
+    using Tab = NoTab;
+    static __device__ __forceinline__ const AoSrc &bind(const AoSrc &ao, const NoTab &) { return ao; }
+    static bool table(NoTab &, const lh_gather_src_t &) { return true; }
+    static uint32_t chunk() { return LH_TILE_CHUNK; }
+};
+struct ByteRow : StageRow {          /* the kinds that leave a byte per item: written exactly once, by whoever finishes the item */
+    static constexpr bool ENV = true;
+    static bool answer(AoSrc &, uint8_t *&occ, const lh_dev_scene_t &, const lh_fused_out_t &o) { occ = (uint8_t *)o.out; return occ != NULL; }
+};
+template <int KIND> struct Stage;
+/* ambient occlusion: occluded rays counted per slot (zeroed before the launch).  A slot's AO rays are coherent: longer ranges per wave (LH_AO_CHUNK, latched on
+ * first use), and the grouped item order (sc.ao_group) is this stage's experiment */
+template <> struct Stage<LH_GATHER_AO> : StageRow {
+    static bool answer(AoSrc &ao, uint8_t *&, const lh_dev_scene_t &sc, const lh_fused_out_t &o) { ao.occ_count = (unsigned int *)o.out; ao.group = (int)sc.ao_group; return true; }
+    static uint32_t chunk()
+    {
+        static uint32_t ao_chunk = 0;
+        if (!ao_chunk) { const char *e = getenv("LH_AO_CHUNK"); ao_chunk = (e && atoi(e) >= 64 && atoi(e) <= 65536) ? (uint32_t)atoi(e) : LH_TILE_CHUNK; }
+        return ao_chunk;
+    }
+};
+/* the dirtmap transport (lh_dirt.h): the same rays walked to their CLOSEST hit under the launch's one bound; the retire stores the bounded record's t */
+template <> struct Stage<LH_GATHER_DIRT> : StageRow {
+    static constexpr bool ANYHIT = false, TMAX = true;
+    static constexpr int PLAN = LH_PLAN_DIRT;
+    static bool answer(AoSrc &ao, uint8_t *&, const lh_dev_scene_t &, const lh_fused_out_t &o) { ao.far_clip = o.far_clip; ao.dirt_t = (double *)o.out; return ao.dirt_t != NULL; }
+};
+/* the environment gather (lh_env.h): the AO stage's walk, the ray's answer a byte at occ[slot * N + r] -- the resolve needs to know WHICH rays were occluded */
+template <> struct Stage<LH_GATHER_ENV> : ByteRow {
+    static constexpr bool COOP_ENV = true;
+};
+/* direct light (lh_lights.h): the shadow rays of the hits to the ntheta lights of the table (nphi is 1), made in the refill (SRC 3), walked to ANY hit under the
+ * item's own bound (a point light's ray ends at the light); a byte at occ[slot * L + l] */
+template <> struct Stage<LH_GATHER_LIGHT> : ByteRow {
+    static constexpr bool TMAX = true;
+    static constexpr int SRC = 3;
+    using Tab = lh_light_tab_t;
+    static __device__ __forceinline__ AoSrc bind(AoSrc ao, const Tab &tab) { ao.lights = tab.l; return ao; }
+    static bool table(Tab &tab, const lh_gather_src_t &g)
+    {
+        if (!g.lights || g.ntheta < 1 || g.ntheta > LH_LIGHTS_MAX || g.nphi != 1) return false;
+        memset(&tab, 0, sizeof(tab));
+        memcpy(tab.l, g.lights, sizeof(lh_light_t) * (size_t)g.ntheta);
+        return true;
+    }
+};
+/* area lights (lh_area.h): the light stage with ray source 4 -- item (slot, l, s), ntheta samples of each of nphi lights, its byte at occ[(slot * L + l) * S + s].
+ * The lights, the emitter table's address, S and the bound travel; the table itself is a device block the accelerator owns (lh_accel_set_emitters) */
+template <> struct Stage<LH_GATHER_AREA> : ByteRow {
+    static constexpr bool TMAX = true;
+    static constexpr int SRC = 4;
+    using Tab = lh_area_tab_t;
+    static __device__ __forceinline__ AoSrc bind(AoSrc ao, const Tab &tab) { ao.area = &tab; return ao; }
+    static bool table(Tab &tab, const lh_gather_src_t &g)
+    {
+        if (!g.area || g.area->L != g.nphi || g.area->S != g.ntheta || g.nphi < 1 || g.nphi > LH_AREA_LIGHTS_MAX || g.ntheta < 1 || !g.area->emitters ||
+            g.area->uniforms) return false;          /* (replayed uniforms: the materialised stage's) */
+        tab = *g.area;
+        return true;
+    }
+};
 
-/* the persistent kernel of the fused dirt stage (lh_launch_trace_gather, LH_GATHER_DIRT): the gather rays of ao.nslots hits, made in the refill (SRC 1), walked to their
- * CLOSEST hit under the launch's one bound ao.far_clip (TMAX); the retire stores the bounded record's t.  A kernel of its own once more */
-template <bool COUNT, int WALK>
-__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_dirt(
-    lh_dev_scene_t sc, uint32_t n, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao, const FixQ fq)
-{
-    extern __shared__ int lh_stack_lds[];
-    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
-    copy_tree_top(sc, lh_stack_lds);
-    trace_persist_lane<false, COUNT, WALK, 1, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, NULL, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
-}
-
-/* the persistent kernel of the fused environment gather (lh_launch_trace_gather, LH_GATHER_ENV): the AO stage's any-hit walk over the gather rays of ao.nslots hits
- * (SRC 1), whose retire stores the ray's answer as a byte at occ[slot * N + r] (ENV).  A kernel of its own once more */
-template <bool COUNT, int WALK>
-__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_env(
-    lh_dev_scene_t sc, uint32_t n, uint8_t *__restrict__ occ, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao, const FixQ fq)
-{
-    extern __shared__ int lh_stack_lds[];
-    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
-    copy_tree_top(sc, lh_stack_lds);
-    trace_persist_lane<true, COUNT, WALK, 1, false, false, false, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
-}
-
-/* the persistent kernel of the fused light stage (lh_launch_trace_gather, LH_GATHER_LIGHT; lh_lights.h): the shadow rays of ao.nslots hits to the ao.ntheta lights of
- * `tab`, made in the refill (SRC 3), walked to ANY hit under the item's own bound (TMAX: a point light's ray ends at the light); the retire stores the answer as a byte
- * at occ[slot * L + l], as the environment gather's does.  The first any-hit + bounded + byte-store instantiation: a kernel of its own once more.  The table travels
- * by value in the kernel's arguments: nothing to allocate, nothing whose release would have to wait for the launch */
-template <bool COUNT, int WALK>
-__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_light(
+/* the persistent kernel of a fused stage: the gather rays of ao.nslots hits, made in the refill by the kind's ray source, walked and retired as its row says */
+template <int KIND, bool COUNT, int WALK>
+__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_stage(
     lh_dev_scene_t sc, uint32_t n, uint8_t *__restrict__ occ, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao0, const FixQ fq,
-    const lh_light_tab_t tab)
+    const typename Stage<KIND>::Tab tab)
 {
+    using K = Stage<KIND>;
     extern __shared__ int lh_stack_lds[];
-    AoSrc ao = ao0;
-    ao.lights = tab.l;
+    const AoSrc &ao = K::bind(ao0, tab);
     if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
     copy_tree_top(sc, lh_stack_lds);
-    trace_persist_lane<true, COUNT, WALK, 3, false, false, true, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
-}
-
-/* the persistent kernel of the fused area-light stage (lh_launch_trace_gather, LH_GATHER_AREA; lh_area.h): the light stage's kernel with ray source 4 -- item
- * (slot, l, s) made in the refill, walked to ANY hit under the call's bound, its answer a byte at occ[(slot * L + l) * S + s].  The lights, the emitter table's
- * address, S and the bound travel by value in the kernel's arguments; the table itself is a device block the accelerator owns (lh_accel_set_emitters) */
-template <bool COUNT, int WALK>
-__global__ __launch_bounds__(LH_BLOCK, 4) void k_trace_persist_area(
-    lh_dev_scene_t sc, uint32_t n, uint8_t *__restrict__ occ, unsigned long long *counters, uint32_t *cursor, int min_active, int tri_batch, const AoSrc ao0, const FixQ fq,
-    const lh_area_tab_t tab)
-{
-    extern __shared__ int lh_stack_lds[];
-    AoSrc ao = ao0;
-    ao.area = &tab;
-    if (ao.nslots_dev) n = (uint32_t)*ao.nslots_dev * (uint32_t)(ao.ntheta * ao.nphi);      /* behind a compaction nobody read back (<= the host's bound < 2^31) */
-    copy_tree_top(sc, lh_stack_lds);
-    trace_persist_lane<true, COUNT, WALK, 4, false, false, true, true>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
+    trace_persist_lane<K::ANYHIT, COUNT, WALK, K::SRC, false, false, K::TMAX, K::ENV>(sc, n, NULL, NULL, NULL, NULL, NULL, NULL, occ, counters, cursor, min_active, tri_batch, ao, fq, lh_stack_lds);
 }
 
 /* work item k of a launch -> the ray it stands for: k itself, or entry k of an indexed launch's list (false: an id beyond the
@@ -1006,8 +1025,8 @@ __device__ __noinline__ RefHit ref_trace_one(const lh_dev_scene_t &sc, double ox
  * SRC 1: AO rays regenerated from (slot, sample), occluded rays counted per slot; LH_Q_REF entries (and fragile results)
  * are decided by the reference's own walk, by the group's first lane. */
 /* TMAX: the rays of a bounded launch (sc.tmax, lh_tmax.h) -- every lane of a group starts with the ray's bound, the group's merged best retires like a
- * lane's (tmax_retire), the reference walk's records go through the final accept.  The body is shared; the kernels are k_coop_walk (every launch without
- * bounds: TMAX = false, the code it always was) and k_coop_walk_tmax */
+ * lane's (tmax_retire), the reference walk's records go through the final accept.  The body is shared; the kernels are k_coop_walk<ANYHIT, SRC, TMAX> (a launch
+ * without bounds: TMAX = false, the code it always was) and k_coop_walk_stage<KIND> (a fused stage, by its kind's row) */
 /* ENV (any hit, ray source 1): the environment gather's rays -- the group's answer goes to occ[i] as a byte, 0 or 1, instead of into the slot's count */
 template <bool ANYHIT, int SRC, bool TMAX, bool ENV = false>
 __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const double *__restrict__ org, const double *__restrict__ dir,
@@ -1224,65 +1243,28 @@ __device__ __forceinline__ void coop_walk_body(const lh_dev_scene_t &sc, const d
     if (owner_groups == 0u && (lane & 15) == 0) fq.heads[gid] = e;          /* where the sweep goes on */
 }
 
-template <bool ANYHIT, int SRC>
+/* the cooperative walk of a ray dump (SRC 0; TMAX: a bounded one) or of a path-traced pass's camera rays (SRC 2) */
+template <bool ANYHIT, int SRC, bool TMAX = false>
 __global__ __launch_bounds__(64) void k_coop_walk(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
                                                   uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
                                                   double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
                                                   unsigned long long *counters, const uint32_t owner_groups)
 {
-    coop_walk_body<ANYHIT, SRC, false>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+    static_assert(!LH_SRC_GATHER(SRC), "the gather stages' kernel is k_coop_walk_stage");
+    coop_walk_body<ANYHIT, SRC, TMAX>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
 }
 
-/* the cooperative walk of a bounded ray dump (ray source 0) */
-template <bool ANYHIT>
-__global__ __launch_bounds__(64) void k_coop_walk_tmax(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
-                                                       uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                       double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
-                                                       unsigned long long *counters, const uint32_t owner_groups)
-{
-    coop_walk_body<ANYHIT, 0, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
-}
-
-/* the cooperative walk of the fused dirt stage (ray source 1, closest hit, the launch's one bound) */
-__global__ __launch_bounds__(64) void k_coop_walk_dirt(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
-                                                       uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                       double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
-                                                       unsigned long long *counters, const uint32_t owner_groups)
-{
-    coop_walk_body<false, 1, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
-}
-
-/* the cooperative walk of the fused environment gather (ray source 1, any hit, a byte per ray) */
-__global__ __launch_bounds__(64) void k_coop_walk_env(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
-                                                      uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                      double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao, const FixQ fq,
-                                                      unsigned long long *counters, const uint32_t owner_groups)
-{
-    coop_walk_body<true, 1, false, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
-}
-
-/* the cooperative walk of the fused light stage (ray source 3, any hit, the item's own bound): the body of a bounded any-hit dump's -- every lane of a group starts
- * with the ray's bound, the reference walk's record goes through the final accept, the group's answer goes to occ[i] as a byte -- with its rays made again from
- * the item index, the hit records and the light table, which travels by value here too */
-__global__ __launch_bounds__(64) void k_coop_walk_light(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
+/* the cooperative walk of a fused stage: the body as the kind's row says, its rays (and bounds) made again from the item index, the hit records and the kind's
+ * table, which travels by value here too.  k_coop_walk's arguments, the table behind them: one launch site serves both (launch_coop) */
+template <int KIND>
+__global__ __launch_bounds__(64) void k_coop_walk_stage(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
                                                         uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
                                                         double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao0, const FixQ fq,
-                                                        unsigned long long *counters, const uint32_t owner_groups, const lh_light_tab_t tab)
+                                                        unsigned long long *counters, const uint32_t owner_groups, const typename Stage<KIND>::Tab tab)
 {
-    AoSrc ao = ao0;
-    ao.lights = tab.l;
-    coop_walk_body<true, 3, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
-}
-
-/* the cooperative walk of the fused area-light stage (ray source 4): the light stage's, its ray and bound made again from the item index */
-__global__ __launch_bounds__(64) void k_coop_walk_area(lh_dev_scene_t sc, const double *__restrict__ org, const double *__restrict__ dir,
-                                                       uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                       double *__restrict__ v, uint8_t *__restrict__ occ, const AoSrc ao0, const FixQ fq,
-                                                       unsigned long long *counters, const uint32_t owner_groups, const lh_area_tab_t tab)
-{
-    AoSrc ao = ao0;
-    ao.area = &tab;
-    coop_walk_body<true, 4, true>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
+    using K = Stage<KIND>;
+    const AoSrc &ao = K::bind(ao0, tab);
+    coop_walk_body<K::ANYHIT, K::SRC, K::TMAX, K::COOP_ENV>(sc, org, dir, prim, t, u, v, occ, ao, fq, counters, owner_groups);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1406,23 +1388,15 @@ __device__ __forceinline__ void fixups_body(const lh_dev_scene_t &sc, size_t n, 
     }
 }
 
+/* TMAX: the same scan behind a bounded launch (sc.tmax) */
+template <bool TMAX>
 __global__ __launch_bounds__(256) void k_fixups(lh_dev_scene_t sc, size_t n, const double *__restrict__ org,
                                                 const double *__restrict__ dir, uint32_t *__restrict__ prim,
                                                 double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
                                                 uint8_t *__restrict__ occ, int anyhit, unsigned long long *counters,
                                                 const uint32_t *qcount, int force)
 {
-    fixups_body<false>(sc, n, org, dir, prim, t, u, v, occ, anyhit, counters, qcount, force);
-}
-
-/* the same scan behind a bounded launch (sc.tmax) */
-__global__ __launch_bounds__(256) void k_fixups_tmax(lh_dev_scene_t sc, size_t n, const double *__restrict__ org,
-                                                     const double *__restrict__ dir, uint32_t *__restrict__ prim,
-                                                     double *__restrict__ t, double *__restrict__ u, double *__restrict__ v,
-                                                     uint8_t *__restrict__ occ, int anyhit, unsigned long long *counters,
-                                                     const uint32_t *qcount, int force)
-{
-    fixups_body<true>(sc, n, org, dir, prim, t, u, v, occ, anyhit, counters, qcount, force);
+    fixups_body<TMAX>(sc, n, org, dir, prim, t, u, v, occ, anyhit, counters, qcount, force);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -1465,21 +1439,13 @@ __device__ __forceinline__ void trace_small_body(const lh_dev_scene_t &sc, uint3
     if (counters) atomicAdd(&counters[LH_CNT_RETRACED], 1ull);
 }
 
-template <bool ANYHIT, bool PER_WAVE>
+/* TMAX: a handful of rays of a bounded call (sc.tmax; a wave per ray) */
+template <bool ANYHIT, bool PER_WAVE, bool TMAX = false>
 __global__ __launch_bounds__(64) void k_trace_small(lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
                                                     uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
                                                     double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters)
 {
-    trace_small_body<ANYHIT, PER_WAVE, false>(sc, n, org, dir, prim, t, u, v, occ, counters);
-}
-
-/* a handful of rays of a bounded call (sc.tmax; a wave per ray) */
-template <bool ANYHIT>
-__global__ __launch_bounds__(64) void k_trace_small_tmax(lh_dev_scene_t sc, uint32_t n, const double *__restrict__ org, const double *__restrict__ dir,
-                                                         uint32_t *__restrict__ prim, double *__restrict__ t, double *__restrict__ u,
-                                                         double *__restrict__ v, uint8_t *__restrict__ occ, unsigned long long *counters)
-{
-    trace_small_body<ANYHIT, true, true>(sc, n, org, dir, prim, t, u, v, occ, counters);
+    trace_small_body<ANYHIT, PER_WAVE, TMAX>(sc, n, org, dir, prim, t, u, v, occ, counters);
 }
 
 /* ---- launchers: what is launched with how many rows, how much of the tree's top, which chunk is lh_plan.h's to say ---------------- */
@@ -1555,7 +1521,7 @@ int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, const lh_plan_t &
             const lane_t f64[3] = {k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q8, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4_CHECKED, 0, false>, k_trace_persist_lane<ANYHIT, COUNT, LH_WALK_Q4, 0, false>};
             uint32_t *cursor = (uint32_t *)c.d_cursor;
             if (sc.tmax) {                       /* a bounded ray dump: an indexed launch whose rays carry a bound each (named last: the kernels above keep their order) */
-                const indexed_t bounded[3] = {k_trace_persist_tmax<ANYHIT, COUNT, LH_WALK_Q8>, k_trace_persist_tmax<ANYHIT, COUNT, LH_WALK_Q4_CHECKED>, k_trace_persist_tmax<ANYHIT, COUNT, LH_WALK_Q4>};
+                const indexed_t bounded[3] = {k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q8, true>, k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q4_CHECKED, true>, k_trace_persist_indexed<ANYHIT, COUNT, LH_WALK_Q4, true>};
                 if (!sc.idx_nrays || sc.cam_src) return -1;
                 LH_LAUNCH_PERSIST(bounded[w], sc, (uint32_t)b.n, LH_BATCH_ARRAYS(b), b.counters, cursor, c.min_active, c.tri_batch, fq);
             } else
@@ -1572,35 +1538,18 @@ int launch_walk(const lh_dev_scene_t &sc, const lh_batch_t &b, const lh_plan_t &
     return b.counters ? launch(no, yes) : launch(no, no);
 }
 
-/* the kernel of a cooperative walk by its template arguments (the light stage's takes one argument more: its table) */
-template <bool ANYHIT, int SRC, bool TMAX, bool ENV>
-auto coop_kernel()
-{
-    constexpr bool DIRT = TMAX && SRC == 1 && !ANYHIT;          /* the fused dirt stage */
-    if constexpr (SRC == 3) return k_coop_walk_light;          /* the fused light stage */
-    else if constexpr (SRC == 4) return k_coop_walk_area;      /* the fused area-light stage */
-    else {
-        auto *kern = k_coop_walk<ANYHIT, DIRT ? 0 : SRC>;
-        if (TMAX) kern = k_coop_walk_tmax<ANYHIT>;
-        if (DIRT) kern = k_coop_walk_dirt;
-        if (ENV) kern = k_coop_walk_env;          /* the fused environment gather */
-        return kern;
-    }
-}
-
 /* the cooperative walk over the fix-up queue of the persistent launch just enqueued on s.  It runs on the queue's second
  * stream, CONCURRENTLY with that launch (a few small workgroups per CU next to the persistent ones: its low efficiency --
  * one ray per 16 lanes, restarted from the root -- is hidden behind the bulk of the frame), submitted AFTER it: if the two
  * streams share a hardware queue it simply runs afterwards. */
-/* extra: what a stage's kernel takes behind the common arguments (the light stage's table) */
-template <bool ANYHIT, int SRC, bool TMAX = false, bool ENV = false, class... Extra>
-int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p, const lh_launch_ctx_t &c, hipStream_t s,
-                const Extra &... extra)
+/* kern: k_coop_walk<...> or k_coop_walk_stage<KIND>; tab: what a stage's kernel takes behind the common arguments (its kind's table) */
+template <class Kern, class... Tab>
+int launch_coop(Kern kern, const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p, const lh_launch_ctx_t &c, hipStream_t s,
+                const Tab &... tab)
 {
     /* the pass next to the producer (owner_groups 0) and the sweep behind it */
 #define LH_LAUNCH_COOP(GRID, STREAM, OWNER_GROUPS) hipLaunchKernelGGL(kern, dim3(GRID), dim3(64), p.coop_lds_bytes, STREAM, scl, LH_BATCH_ARRAYS(b), \
-                                                                      ao, fq, b.counters, OWNER_GROUPS, extra...)
-    auto *kern = coop_kernel<ANYHIT, SRC, TMAX, ENV>();
+                                                                      ao, fq, b.counters, OWNER_GROUPS, tab...)
     lh_dev_scene_t scl = sc;
     scl.stack_rows = p.coop_rows;
     if (allow_lds((const void *)kern, p.coop_lds_bytes) != 0) return -1;
@@ -1625,100 +1574,38 @@ int launch_coop(const lh_dev_scene_t &sc, const lh_batch_t &b, const AoSrc &ao, 
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-/* a fused stage's lh_fused_out_t (lh_device.h) as its kernels take it: the chunk before the clamp and the tail of AoSrc.  The AO rays of a slot are
- * coherent: longer ranges per wave (LH_AO_CHUNK, latched on first use), and the grouped item order is the AO stage's experiment -- the dirt stage and
- * the environment gather take the plain order (slot, sample) and LH_TILE_CHUNK */
-struct FusedStage {
-    bool dirt; uint32_t chunk; unsigned int *occ_count; int group; double far_clip; double *dirt_t; uint8_t *env_occ;
-    bool light;          /* the light stage: env_occ is its byte per item */
-    bool area;           /* the area-light stage: the same */
-    FusedStage(const lh_dev_scene_t *sc, const lh_fused_out_t &o)
-        : dirt(o.kind == LH_GATHER_DIRT), chunk(LH_TILE_CHUNK), occ_count(NULL), group(0), far_clip(dirt ? o.far_clip : 0.0),
-          dirt_t(dirt ? (double *)o.out : NULL), env_occ((o.kind == LH_GATHER_ENV || o.kind == LH_GATHER_LIGHT || o.kind == LH_GATHER_AREA) ? (uint8_t *)o.out : NULL),
-          light(o.kind == LH_GATHER_LIGHT), area(o.kind == LH_GATHER_AREA)
-    {
-        static uint32_t ao_chunk = 0;
-        if (o.kind != LH_GATHER_AO) return;
-        if (!ao_chunk) { const char *e = getenv("LH_AO_CHUNK"); ao_chunk = (e && atoi(e) >= 64 && atoi(e) <= 65536) ? (uint32_t)atoi(e) : LH_TILE_CHUNK; }
-        chunk = ao_chunk; occ_count = (unsigned int *)o.out; group = (int)sc->ao_group;
-    }
-};
-
-/* what the fused item kinds (lh_lights.h, lh_area.h) share: the persistent kernel `kern` over the items of `none` -- its bytes at none.occ -- and the
- * cooperative pass of ray source SRC behind it, the kind's table by value into both */
-template <int SRC, class Kern, class Tab>
-int launch_fused_items(Kern kern, const Tab &tab, const lh_dev_scene_t &scl, const lh_batch_t &none, const AoSrc &ao, const FixQ &fq, const lh_plan_t &p,
-                       const lh_launch_ctx_t &c, hipStream_t s)
+/* a fused stage of kind KIND (its row: Stage<KIND> above): the gather rays of g.nslots hits, N = ntheta * nphi each, made inside the persistent kernel.  Rays
+ * that kernel does not finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative walk) -- go through the
+ * stream's fix-up queue (2 words per entry, count + overflow flag in qcount[0..1]) to k_coop_walk_stage */
+template <int KIND>
+int launch_stage(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const lh_fused_out_t &o, unsigned long long *d_counters, const lh_launch_ctx_t &c)
 {
-    LH_LAUNCH_PERSIST(kern, scl, (uint32_t)none.n, (uint8_t *)none.occ, none.counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
-    if (hipGetLastError() != hipSuccess) return -1;
-    return launch_coop<true, SRC, true>(scl, none, ao, fq, p, c, s, tab);
-}
-
-/* a fused stage: the gather rays of g.nslots hits, N = ntheta * nphi each, made inside the persistent kernel (SRC 1).  Rays that kernel does not
- * finish -- fragile hits (the reference's own walk decides), rays out of visit budget or LDS rows (the cooperative walk) -- go through the stream's
- * fix-up queue (2 words per entry, count + overflow flag in qcount[0..1]) to k_coop_walk */
-int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const FusedStage &st, unsigned long long *d_counters, const lh_launch_ctx_t &c)
-{
+    using K = Stage<KIND>;
     hipStream_t s = (hipStream_t)c.stream;
     const size_t n = g.nslots * (size_t)(g.ntheta * g.nphi);
     if (n == 0) return 0;
-    if (n >= ((size_t)1 << 31) || (st.dirt && !st.dirt_t)) return -1;
-    if (g.d_nslots && st.group) return -1;            /* the grouped order needs the exact count on the host */
+    /* the rays are made in the kernel; where their answers go is the row's to say */
+    AoSrc ao = {g.d_hitrec, g.d_slot_key, NULL, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, 0, g.d_nslots, g.budget_big, 0.0, NULL, NULL, NULL};
+    uint8_t *occ = NULL;
+    typename K::Tab tab;
+    if (n >= ((size_t)1 << 31) || !K::answer(ao, occ, *sc, o) || !K::table(tab, g)) return -1;
+    if (g.d_nslots && ao.group) return -1;            /* the grouped order needs the exact count on the host */
     lh_dev_scene_t scl = *sc;
-    scl.ray_chunk = st.chunk;
-    const lh_plan_t p = lh_plan_launch(&scl, n, st.dirt ? LH_PLAN_DIRT : LH_PLAN_AO, LH_VARIANT_SPEC, c.grid_blocks, 1);
-    const AoSrc ao = {g.d_hitrec, g.d_slot_key, st.occ_count, g.seed, g.ntheta, g.nphi, (uint32_t)g.nslots, st.group, g.d_nslots, g.budget_big, st.far_clip, st.dirt_t, NULL, NULL};
+    scl.ray_chunk = K::chunk();
+    const lh_plan_t p = lh_plan_launch(&scl, n, K::PLAN, LH_VARIANT_SPEC, c.grid_blocks, 1);
     FixQ fq;
     if (apply_plan(scl, p) != 0) return -1;
-    if (st.occ_count && hipMemsetAsync(st.occ_count, 0, sizeof(unsigned int) * g.nslots, s) != hipSuccess) return -1;      /* with the cursors' memset, before the stream's first kernel */
+    if (ao.occ_count && hipMemsetAsync(ao.occ_count, 0, sizeof(unsigned int) * g.nslots, s) != hipSuccess) return -1;      /* with the cursors' memset, before the stream's first kernel */
     if (persist_begin(c, true, &fq, s) != 0) return -1;
-    /* the rays are made in the kernel; the answers counted per slot (AO), their t stored through ao (dirt), a byte per ray at `occ` (the environment gather) */
-    const lh_batch_t none = {n, st.dirt ? LH_MODE_CLOSEST : LH_MODE_ANY, NULL, NULL, NULL, NULL, NULL, NULL, st.env_occ, d_counters};
-    const int w = p.guard ? 0 : 1, k = d_counters ? 0 : 1;          /* the kernels below: checked pushes first, counted first */
-    if (!st.dirt && !st.env_occ) {
-        using ao_t = decltype(&k_trace_persist_lane<true, true, LH_WALK_Q4, 1>);
-        const ao_t kern[2][2] = {{k_trace_persist_lane<true, true, LH_WALK_Q4_CHECKED, 1>, k_trace_persist_lane<true, false, LH_WALK_Q4_CHECKED, 1>},
-                                 {k_trace_persist_lane<true, true, LH_WALK_Q4, 1>, k_trace_persist_lane<true, false, LH_WALK_Q4, 1>}};
-        LH_LAUNCH_PERSIST(kern[w][k], scl, (uint32_t)n, LH_BATCH_ARRAYS(none), d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
-        if (hipGetLastError() != hipSuccess) return -1;
-        return launch_coop<true, 1>(scl, none, ao, fq, p, c, s);
-    }
-    using dirt_t = decltype(&k_trace_persist_dirt<true, LH_WALK_Q4>);
-    const dirt_t kern[2][2] = {{k_trace_persist_dirt<true, LH_WALK_Q4_CHECKED>, k_trace_persist_dirt<false, LH_WALK_Q4_CHECKED>},
-                               {k_trace_persist_dirt<true, LH_WALK_Q4>, k_trace_persist_dirt<false, LH_WALK_Q4>}};
-    if (st.dirt) {
-        LH_LAUNCH_PERSIST(kern[w][k], scl, (uint32_t)n, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
-        if (hipGetLastError() != hipSuccess) return -1;
-        return launch_coop<false, 1, true>(scl, none, ao, fq, p, c, s);
-    }
-    if (st.light) {          /* the light stage (lh_lights.h): ntheta lights of the host table g.lights, by value into both kernels */
-        if (!g.lights || g.ntheta < 1 || g.ntheta > LH_LIGHTS_MAX || g.nphi != 1) return -1;
-        lh_light_tab_t tab;
-        memset(&tab, 0, sizeof(tab));
-        memcpy(tab.l, g.lights, sizeof(lh_light_t) * (size_t)g.ntheta);
-        using light_t = decltype(&k_trace_persist_light<true, LH_WALK_Q4>);
-        const light_t lkern[2][2] = {{k_trace_persist_light<true, LH_WALK_Q4_CHECKED>, k_trace_persist_light<false, LH_WALK_Q4_CHECKED>},
-                                     {k_trace_persist_light<true, LH_WALK_Q4>, k_trace_persist_light<false, LH_WALK_Q4>}};
-        return launch_fused_items<3>(lkern[w][k], tab, scl, none, ao, fq, p, c, s);
-    }
-    if (st.area) {          /* the area-light stage (lh_area.h): ntheta samples of each of nphi lights, the HOST table g.area by value into both kernels */
-        if (!g.area || g.area->L != g.nphi || g.area->S != g.ntheta || g.nphi < 1 || g.nphi > LH_AREA_LIGHTS_MAX || g.ntheta < 1 || !g.area->emitters ||
-            g.area->uniforms) return -1;          /* (replayed uniforms: the materialised stage's) */
-        const lh_area_tab_t tab = *g.area;
-        using area_t = decltype(&k_trace_persist_area<true, LH_WALK_Q4>);
-        const area_t akern[2][2] = {{k_trace_persist_area<true, LH_WALK_Q4_CHECKED>, k_trace_persist_area<false, LH_WALK_Q4_CHECKED>},
-                                    {k_trace_persist_area<true, LH_WALK_Q4>, k_trace_persist_area<false, LH_WALK_Q4>}};
-        return launch_fused_items<4>(akern[w][k], tab, scl, none, ao, fq, p, c, s);
-    }
-    /* the environment gather (named last: the kernels above keep their order) */
-    using env_t = decltype(&k_trace_persist_env<true, LH_WALK_Q4>);
-    const env_t ekern[2][2] = {{k_trace_persist_env<true, LH_WALK_Q4_CHECKED>, k_trace_persist_env<false, LH_WALK_Q4_CHECKED>},
-                               {k_trace_persist_env<true, LH_WALK_Q4>, k_trace_persist_env<false, LH_WALK_Q4>}};
-    LH_LAUNCH_PERSIST(ekern[w][k], scl, (uint32_t)n, st.env_occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq);
+    const lh_batch_t none = {n, K::ANYHIT ? LH_MODE_ANY : LH_MODE_CLOSEST, NULL, NULL, NULL, NULL, NULL, NULL, occ, d_counters};
+    using stage_t = decltype(&k_trace_persist_stage<KIND, true, LH_WALK_Q4>);
+    const stage_t kern[2][2] = {{k_trace_persist_stage<KIND, true, LH_WALK_Q4_CHECKED>, k_trace_persist_stage<KIND, false, LH_WALK_Q4_CHECKED>},          /* checked pushes first, */
+                                {k_trace_persist_stage<KIND, true, LH_WALK_Q4>, k_trace_persist_stage<KIND, false, LH_WALK_Q4>}};                          /* counted first */
+    LH_LAUNCH_PERSIST(kern[p.guard ? 0 : 1][d_counters ? 0 : 1], scl, (uint32_t)n, occ, d_counters, (uint32_t *)c.d_cursor, c.min_active, c.tri_batch, ao, fq, tab);
     if (hipGetLastError() != hipSuccess) return -1;
-    return launch_coop<true, 1, false, true>(scl, none, ao, fq, p, c, s);
+    return launch_coop(k_coop_walk_stage<KIND>, scl, none, ao, fq, p, c, s, tab);
 }
+
 
 } /* namespace */
 
@@ -1726,8 +1613,14 @@ int launch_fused(const lh_dev_scene_t *sc, const lh_gather_src_t &g, const Fused
 extern "C" int lh_launch_trace_gather(const lh_dev_scene_t *sc, const lh_gather_src_t *src, const lh_fused_out_t *out, unsigned long long *d_counters,
                                       const lh_launch_ctx_t *ctx)
 {
-    if ((unsigned)out->kind >= LH_GATHER_KINDS || ((out->kind == LH_GATHER_ENV || out->kind == LH_GATHER_LIGHT || out->kind == LH_GATHER_AREA) && !out->out)) return -1;
-    return launch_fused(sc, *src, FusedStage(sc, *out), d_counters, *ctx);
+    switch (out->kind) {
+    case LH_GATHER_AO:    return launch_stage<LH_GATHER_AO>(sc, *src, *out, d_counters, *ctx);
+    case LH_GATHER_DIRT:  return launch_stage<LH_GATHER_DIRT>(sc, *src, *out, d_counters, *ctx);
+    case LH_GATHER_ENV:   return launch_stage<LH_GATHER_ENV>(sc, *src, *out, d_counters, *ctx);
+    case LH_GATHER_LIGHT: return launch_stage<LH_GATHER_LIGHT>(sc, *src, *out, d_counters, *ctx);
+    case LH_GATHER_AREA:  return launch_stage<LH_GATHER_AREA>(sc, *src, *out, d_counters, *ctx);
+    }
+    return -1;
 }
 
 extern "C" int lh_trace_rows(const lh_dev_scene_t *sc)
@@ -1753,6 +1646,8 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
     const lh_batch_t &b = *batch;
     const size_t n = b.n;
     const bool anyhit = b.mode == LH_MODE_ANY;
+    auto *const fixups = !sc->tmax ? k_fixups<false> : k_fixups<true>;          /* the scan behind the launch.  Named here, before k_trace_small: a template is emitted where it is first named,
+                                                                                            * and behind overflow_walk's other callers this kernel's registers come out differently (profiles/stage_kernels.md) */
     if (n == 0) return 0;
     /* the persistent kernel indexes rays with 32 bits: a larger batch is a sequence of launches */
     const size_t kMaxLaunch = (size_t)1 << 30;
@@ -1775,7 +1670,7 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
          * Per-ray diagnostics (diag_out): the same walk for a batch of any size, a lane per ray */
         const bool per_wave = n <= LH_SMALL_BATCH;
         auto *k = per_wave ? (anyhit ? k_trace_small<true, true> : k_trace_small<false, true>) : (anyhit ? k_trace_small<true, false> : k_trace_small<false, false>);
-        if (sc->tmax) { if (!per_wave) return -1; k = anyhit ? k_trace_small_tmax<true> : k_trace_small_tmax<false>; }
+        if (sc->tmax) { if (!per_wave) return -1; k = anyhit ? k_trace_small<true, true, true> : k_trace_small<false, true, true>; }
         hipLaunchKernelGGL(k, dim3((unsigned)(per_wave ? n : (n + 63) / 64)), dim3(64), 0, s, scl, (uint32_t)n, LH_BATCH_ARRAYS(b), b.counters);
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
@@ -1789,16 +1684,15 @@ extern "C" int lh_launch_trace(const lh_dev_scene_t *sc, const lh_batch_t *batch
     int rc = launch_walk(scl, b, p, *ctx, fq, s);
     if (rc != 0) return rc;
     if (p.coop) {
-        rc = sc->tmax ? (anyhit ? launch_coop<true, 0, true>(scl, b, AoSrc{}, fq, p, *ctx, s) : launch_coop<false, 0, true>(scl, b, AoSrc{}, fq, p, *ctx, s))
-             : anyhit ? launch_coop<true, 0>(scl, b, AoSrc{}, fq, p, *ctx, s)
-             : sc->cam_src ? launch_coop<false, 2>(scl, b, AoSrc{}, fq, p, *ctx, s)
-                    : launch_coop<false, 0>(scl, b, AoSrc{}, fq, p, *ctx, s);
+        auto *kern = sc->tmax ? (anyhit ? k_coop_walk<true, 0, true> : k_coop_walk<false, 0, true>)
+                     : anyhit ? k_coop_walk<true, 0> : sc->cam_src ? k_coop_walk<false, 2> : k_coop_walk<false, 0>;
+        rc = launch_coop(kern, scl, b, AoSrc{}, fq, p, *ctx, s);
         if (rc != 0) return rc;
     }
     /* what is still flagged: fragile hits (the reference's own walk), and out-of-budget rays the queue had no room for */
     {
         const size_t blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(sc->tmax ? k_fixups_tmax : k_fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, LH_BATCH_ARRAYS(b),
+        hipLaunchKernelGGL(fixups, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, scl, n, LH_BATCH_ARRAYS(b),
                            anyhit ? 1 : 0, b.counters, q ? q->qcount : NULL, (p.walk == LH_WALK_DIRECT || q == NULL) ? 1 : 0);
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
