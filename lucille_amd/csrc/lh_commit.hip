@@ -11,6 +11,7 @@
 #include "lh_danger.h"
 #include "lh_plan.h"
 #include "lh_recommit.h"
+#include "lh_route.h"
 
 static thread_local char g_err[512] = "";
 
@@ -172,7 +173,6 @@ extern "C" int lh_accel_set_attribute(lh_accel_t *a, uint32_t mesh, int kind, co
 }
 
 /* ---- meshes handed over as device arrays ----------------------------------------------------- */
-static void publish_scene(lh_accel_t *a);
 static void free_dmeshes(lh_accel_t *a)
 {
     for (uint32_t g = 0; g < a->ndmeshes; g++) {
@@ -365,19 +365,10 @@ static int dmesh_prim_tables(lh_host_scene *hs, const uint32_t *first, uint32_t 
     return 0;
 }
 
-/* the staged device meshes -> a->d_tri64, on the accelerator's stream, behind the copies the adds enqueued (an event per caller
- * stream; no device-wide synchronise).  Returns once the kernel's status word is back: an index out of range fails the commit */
-static int flatten_device_meshes_into(lh_accel_t *a, const uint32_t *first, void **d_tri64, const char *who);
-static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first)
-{
-    const int rc = flatten_device_meshes_into(a, first, &a->d_tri64, "lh_accel_commit");
-    publish_scene(a);
-    return rc;
-}
-
-/* ... into an array of its own, *d_tri64 (the caller's to free, whatever is returned): the commit's is the scene's, a re-commit's
- * stands beside the scene's until the swap */
-static int flatten_device_meshes_into(lh_accel_t *a, const uint32_t *first, void **d_tri64, const char *who)
+/* the staged device meshes -> an array of triangle records of its own, *d_tri64 (a side's: the caller's to free, whatever is
+ * returned), on the accelerator's stream, behind the copies the adds enqueued (an event per caller stream; no device-wide
+ * synchronise).  Returns once the kernel's status word is back: an index out of range fails the commit */
+static int flatten_device_meshes(lh_accel_t *a, const uint32_t *first, void **d_tri64, const char *who)
 {
     const uint32_t nm = a->ndmeshes, nt = first[nm];
     const double t0 = now_s();
@@ -403,23 +394,11 @@ static int flatten_device_meshes_into(lh_accel_t *a, const uint32_t *first, void
     return rc;
 }
 
-/* the per-vertex normals and attributes of the staged device meshes -> a->d_nrm9, a->d_attr9[], a->d_st6, a->d_inside, the arrays a
- * host scene uploads (device_upload): one kernel on the accelerator's stream.  Called behind flatten_device_meshes, which has
- * waited for the callers' copies and found every index in range; an array no mesh contributes to stays NULL, a scene without
- * any costs nothing here */
-static int gather_device_attributes_into(lh_accel_t *a, const uint32_t *first, lh_gather_out_t *o, const char *who);
-static int gather_device_attributes(lh_accel_t *a, const uint32_t *first)
-{
-    lh_gather_out_t o;
-    const int rc = gather_device_attributes_into(a, first, &o, "lh_accel_commit");
-    a->d_nrm9 = o.nrm9; a->d_st6 = o.st6; a->d_inside = o.inside;
-    for (int k = 0; k < 3; k++) a->d_attr9[k] = o.attr9[k];
-    publish_scene(a);
-    return rc;
-}
-
-/* ... into arrays of their own, *o (the caller's to free, whatever is returned; NULL: no mesh has it) */
-static int gather_device_attributes_into(lh_accel_t *a, const uint32_t *first, lh_gather_out_t *o, const char *who)
+/* the per-vertex normals and attributes of the staged device meshes -> arrays of their own, *o (a side's: the caller's to free,
+ * whatever is returned), laid out as the nrm9 / attr9[] / st6 / inside a host scene uploads (device_upload): one kernel on the
+ * accelerator's stream.  Called behind flatten_device_meshes, which has waited for the callers' copies and found every index in
+ * range; an array no mesh contributes to stays NULL, a scene without any costs nothing here */
+static int gather_device_attributes(lh_accel_t *a, const uint32_t *first, lh_gather_out_t *o, const char *who)
 {
     memset(o, 0, sizeof(*o));
     const uint32_t nm = a->ndmeshes, nt = first[nm];
@@ -800,50 +779,26 @@ __global__ void k_words_differ(size_t nwords, const uint32_t *__restrict__ x, co
     if (__ballot(diff) != 0ull && (threadIdx.x & 63) == 0) atomicExch(flag, 1);
 }
 
-/* the 8-wide nodes of a scene whose tree was built on this device without them: the build is run once more (it is
- * deterministic: stable sort, stable partitions, a layout of the top that does not depend on its threads) and only its 8-wide
- * collapse is kept.  The leaves of those nodes index the resident triangle records, so the second run's records must be the
- * resident ones word for word -- checked, not assumed */
-static int device_rebuild_q8(lh_accel_t *a)
+/* *diff: the two arrays of nwords words differ somewhere (what: the comparison, for the error text) */
+static int words_differ(lh_accel_t *a, const void *x, const void *y, size_t nwords, bool *diff, const char *what)
 {
-    lh_host_scene *hs = a->hs;
-    char berr[256] = "";
-    void *q4 = NULL, *q8 = NULL, *t32 = NULL; int *flag = NULL, h_flag = 0;
-    uint32_t nq4 = 0, d4 = 0, st4 = 0, nq8 = 0, d8 = 0; float bmin[3], bmax[3], glo[3], gst[3];
-    const int rcb = lh_device_build(hs->bvh.ntris, (const double *)a->d_tri64, &q4, &nq4, &d4, &st4, 1, &q8, &nq8, &d8, &t32, bmin, bmax, glo, gst,
-                                    NULL, NULL, (void *)a->stream, berr, sizeof(berr));
-    if (rcb != 0) return fail("building the 8-wide nodes on the device failed: %s", berr);
+    int *flag = NULL, h_flag = 0;
+    HIPCHK(hipMalloc((void **)&flag, sizeof(int)));
     int rc = 0;
-    if (q8) {
-        const size_t nwords = sizeof(lh_tri32_t) / 4 * (size_t)hs->bvh.ntris;
-        if (hipMalloc((void **)&flag, sizeof(int)) != hipSuccess || hipMemsetAsync(flag, 0, sizeof(int), a->stream) != hipSuccess) rc = fail("out of device memory");
-        if (rc == 0) {
-            hipLaunchKernelGGL(k_words_differ, dim3(2048), dim3(256), 0, a->stream, nwords, (const uint32_t *)t32, (const uint32_t *)a->d_tri32, flag);
-            if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess)
-                rc = fail("comparing the rebuilt triangle order failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-        if (rc == 0 && (h_flag || nq4 != hs->bvh.nq4nodes))
-            rc = fail("the device build did not repeat itself (%u nodes, then %u): the 8-wide nodes are not usable; set \"wide8\" = 1 before the commit", hs->bvh.nq4nodes, nq4);
+    if (hipMemsetAsync(flag, 0, sizeof(int), a->stream) != hipSuccess) rc = fail("%s failed", what);
+    if (rc == 0) {
+        hipLaunchKernelGGL(k_words_differ, dim3(2048), dim3(256), 0, a->stream, nwords, (const uint32_t *)x, (const uint32_t *)y, flag);
+        if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess)
+            rc = fail("%s failed: %s", what, hipGetErrorString(hipGetLastError()));
     }
-    if (flag) (void)hipFree(flag);
-    if (q4) (void)hipFree(q4);
-    if (t32) (void)hipFree(t32);
-    if (rc != 0) { if (q8) (void)hipFree(q8); return -1; }
-    if (q8) {
-        pthread_mutex_lock(&g_scene_mu);
-        hs->bvh.nq8nodes = nq8; hs->bvh.q8_depth = d8;
-        pthread_mutex_unlock(&g_scene_mu);
-        a->d_q8nodes = q8;
-        publish_scene(a);
-    }
-    return 0;
+    (void)hipFree(flag);
+    *diff = h_flag != 0;
+    return rc;
 }
 
 extern "C" int lh_device_ref_build(uint32_t ntris, const double *d_tri64, void **d_nodes, uint32_t *nnodes, uint32_t *max_depth,
                                    void **d_leaf_prims, void **d_lca, void **d_leafpos, double scene6[6], void *stream, char *err, size_t errlen);   /* lh_refbuild.hip */
 
-/* lucille's own tree of a device-built scene, on this device (LH_REF_BUILD=host: the background host thread instead).
- * 0: attached; 1: not built here (the host thread will); -1: error */
 /* ---- the leaves of lucille's own tree that hold a zero-area triangle (round 6; lh_bvh.h ndanger / danger, lh_walk.h danger_hit) ----
  * A numerically collinear triangle that stays in the traversal tree caps the directions the tree can vouch for at 1 / s2 (lh_bvh.c
  * tri_zero_area_s2) -- below 1 as soon as |e1|_1 |e2|_1 > 1, i.e. for ANY such sliver in a scene modelled in small units -- and every
@@ -911,46 +866,123 @@ static int danger_scan_arrays(lh_accel_t *a, uint32_t n, double deg_dcap, const 
     return 0;
 }
 
-static int lh_danger_scan(lh_accel_t *a)
+/* a danger list becomes the accelerator's: the one a side brings (side_install), or -- none brought -- the one a scan of the resident scene finds
+ * now that lucille's own tree has arrived from somewhere else: the host thread (attach_ref), another rank (lh_scene_image_finish).  The host list
+ * is written only over LH_DANGER_ALL: the first replica of a shared host scene writes it, the others found the same one */
+static int lh_danger_scan(lh_accel_t *a, const lh_danger_found *brought = NULL)
 {
-    lh_host_scene *hs = a->hs;
-    a->dev.ndanger = LH_DANGER_ALL;
-    lh_danger_found f;
-    /* the host scene's grid: a->dev's copy is set later in a device-built commit */
-    if (danger_scan_arrays(a, hs->bvh.ntris, hs->bvh.deg_dcap, a->d_tri64, a->d_prim_leafpos, a->d_ref_lca, a->d_ref_nodes, a->dev.ref_bmin, a->dev.ref_bmax,
-                           hs->bvh.grid_lo, hs->bvh.grid_step, &f) != 0) return -1;
-    if (f.nhost == LH_DANGER_ALL) return 0;
+    lh_bvh_t *b = &a->hs->bvh; lh_danger_found f; int rc = 0;
+    if (brought) f = *brought;          /* (a scan that fails finds LH_DANGER_ALL) */
+    else rc = danger_scan_arrays(a, b->ntris, b->deg_dcap, a->d_tri64, a->d_prim_leafpos, a->d_ref_lca, a->d_ref_nodes, a->dev.ref_bmin, a->dev.ref_bmax, b->grid_lo, b->grid_step, &f);
     pthread_mutex_lock(&g_scene_mu);
-    if (hs->bvh.ndanger == LH_DANGER_ALL) {            /* the first replica of a shared host scene writes the list; the others found the same one */
-        memcpy(hs->bvh.danger, f.boxes, sizeof(double) * 6 * (size_t)f.nhost);
-        __atomic_store_n(&hs->bvh.ndanger, f.nhost, __ATOMIC_RELEASE);      /* the one-ray host walk reads it (lh_hostwalk.c) */
+    if (b->ndanger == LH_DANGER_ALL && f.nhost != LH_DANGER_ALL) {
+        memcpy(b->danger, f.boxes, sizeof(double) * 6 * (size_t)f.nhost);
+        __atomic_store_n(&b->ndanger, f.nhost, __ATOMIC_RELEASE);      /* the one-ray host walk reads it (lh_hostwalk.c) */
     }
     pthread_mutex_unlock(&g_scene_mu);
-    if (f.ndev == LH_DANGER_ALL) return 0;
-    for (int k = 0; k < 3; k++) a->dev.danger[k] = f.words[k];
     a->dev.ndanger = f.ndev;
-    return 0;
+    for (int k = 0; k < 3; k++) a->dev.danger[k] = f.ndev != LH_DANGER_ALL ? f.words[k] : 0u;
+    return rc;
 }
 
-static int device_ref_tree(lh_accel_t *a)
+/* a side: everything the device builders make of a scene, owned by nobody until side_install makes it the accelerator's -- the arrays of scene_rows
+ * a device build fills and what goes into the headers for them.  A first commit's stands beside an empty scene, a re-commit's beside the resident one */
+struct lh_side {
+    void *tri64, *tri32, *q4, *q8, *ref_nodes, *ref_leaf_prims, *ref_lca, *leafpos;
+    lh_gather_out_t attr; int gathered;          /* gathered: attr is what the meshes have now, its NULLs included */
+    uint32_t nq4, d4, st4, nq8, d8, nlive, ref_nnodes; double dcap, sc6[6], build_seconds, ref_seconds;
+    float bmin[3], bmax[3], glo[3], gst[3];
+    lh_danger_found danger;
+};
+
+static void side_free(lh_side *s)
+{
+    void *p[] = {s->tri64, s->tri32, s->q4, s->q8, s->ref_nodes, s->ref_leaf_prims, s->ref_lca, s->leafpos,
+                 s->attr.nrm9, s->attr.attr9[0], s->attr.attr9[1], s->attr.attr9[2], s->attr.st6, s->attr.inside};
+    for (size_t k = 0; k < sizeof(p) / sizeof(p[0]); k++) if (p[k]) (void)hipFree(p[k]);
+    memset(s, 0, sizeof(*s));
+}
+
+/* the one run of the device builders: from nt > 0 triangle records (the side's own, or resident ones) the traversal tree and tri32 (lh_build.hip), with
+ * the 8-wide nodes if want_q8, then -- own_tree -- lucille's own tree (lh_refbuild.hip) and the danger list.  Nothing of the accelerator is written but
+ * its scratch; whatever the outcome the side (zeroed by its owner: no danger list is LH_DANGER_ALL) owns what was allocated, and err says what a builder said (a failed scan: lh_last_error()).  What follows: lh_route.h */
+static lh_side_outcome_t side_build(lh_accel_t *a, lh_side *s, const void *tri64, uint32_t nt, int want_q8, bool own_tree, char *err, size_t errlen)
+{
+    const double tb = now_s();
+    const int rcb = lh_device_build(nt, (const double *)tri64, &s->q4, &s->nq4, &s->d4, &s->st4, want_q8, &s->q8, &s->nq8, &s->d8, &s->tri32, s->bmin, s->bmax, s->glo, s->gst,
+                                    &s->nlive, &s->dcap, (void *)a->stream, err, errlen);
+    if (rcb != 0) return rcb == -2 ? LH_SIDE_BAD_VERTEX : LH_SIDE_BUILDER_FAILED;
+    s->build_seconds = now_s() - tb;
+    /* deeper than k_overflow_fix's private stack (LH_BUILD_DEPTH_MAX: 3 d + 5 <= 264 rows; "build_depth_cap" lowers it) */
+    if (s->d4 > (uint32_t)a->build_depth_cap) { snprintf(err, errlen, "a tree of %u levels, the walks' stacks take %d", s->d4, a->build_depth_cap); return LH_SIDE_TOO_DEEP; }
+    if ((uint64_t)s->nq4 * sizeof(lh_q4node_t) >= (1ull << 32)) { snprintf(err, errlen, "more 4-wide nodes than a 32-bit byte offset addresses"); return LH_SIDE_TOO_MANY_NODES; }
+    if (!own_tree) return LH_SIDE_BUILT;
+    const double tr = now_s(); uint32_t rdepth = 0;
+    if (lh_device_ref_build(nt, (const double *)tri64, &s->ref_nodes, &s->ref_nnodes, &rdepth, &s->ref_leaf_prims, &s->ref_lca, &s->leafpos, s->sc6,
+                            (void *)a->stream, err, errlen) != 0) {
+        s->ref_nodes = s->ref_leaf_prims = s->ref_lca = s->leafpos = NULL;          /* the builder freed them */
+        return LH_SIDE_REF_FAILED;
+    }
+    s->ref_seconds = now_s() - tr;
+    if (danger_scan_arrays(a, nt, s->dcap, tri64, s->leafpos, s->ref_lca, s->ref_nodes, s->sc6, s->sc6 + 3, s->glo, s->gst, &s->danger) != 0) return LH_SIDE_SCAN_FAILED;
+    return LH_SIDE_BUILT;
+}
+
+/* the side becomes the scene: whichever of its parts it holds -- the triangle records; the trees (tri32, the 4-wide nodes, lucille's own tree and the
+ * danger list, if they were built); the 8-wide nodes; the gathered attribute arrays -- change places with the accelerator's, their header fields are
+ * written, the scene is published, and what was displaced is freed with the side.  Nothing else writes the header fields a device build produces.
+ * The caller has made sure no launch reads what is displaced (a first commit displaces nothing) */
+static void side_install(lh_accel_t *a, lh_side *s)
+{
+    lh_host_scene *hs = a->hs; lh_bvh_t *b = &hs->bvh;
+    auto put = [](void **slot, void **p) { void *was = *slot; *slot = *p; *p = was; };
+    const bool trees = s->q4 != NULL, own_tree = s->ref_nodes != NULL;
+    if (s->tri64) put(&a->d_tri64, &s->tri64);
+    pthread_mutex_lock(&g_scene_mu);
+    if (trees) {
+        b->nq4nodes = s->nq4; b->q4_depth = s->d4; b->q4_stack = s->st4; b->nnodes = s->nq4; b->max_depth = s->d4; b->build_seconds = s->build_seconds;
+        b->nlive = s->nlive; b->deg_dcap = s->dcap;
+        for (int k = 0; k < 3; k++) { b->bmin[k] = s->bmin[k]; b->bmax[k] = s->bmax[k]; b->grid_lo[k] = s->glo[k]; b->grid_step[k] = s->gst[k]; }
+        put(&a->d_tri32, &s->tri32); put(&a->d_q4nodes, &s->q4);
+        put(&a->d_ref_nodes, &s->ref_nodes); put(&a->d_ref_leaf_prims, &s->ref_leaf_prims); put(&a->d_ref_lca, &s->ref_lca); put(&a->d_prim_leafpos, &s->leafpos);
+        a->hw_ns = 0.0; a->hw_gpu_left = 0;
+    }
+    if (s->q8 || (trees && a->d_q8nodes)) { b->nq8nodes = s->q8 ? s->nq8 : 0u; b->q8_depth = s->q8 ? s->d8 : 0u; }          /* none made, none displaced: the fields stay, the host scene's may be another replica's */
+    if (own_tree) { hs->ref_on_device = 1; hs->ref_build_seconds = s->ref_seconds; }
+    pthread_mutex_unlock(&g_scene_mu);
+    if (trees) (void)lh_danger_scan(a, &s->danger);
+    if (own_tree) publish_ref(a, s->ref_nnodes, 0, s->sc6, s->sc6 + 3);
+    if (trees || s->q8) put(&a->d_q8nodes, &s->q8);
+    if (s->gathered) {
+        put(&a->d_nrm9, (void **)&s->attr.nrm9); put(&a->d_st6, (void **)&s->attr.st6); put(&a->d_inside, (void **)&s->attr.inside);
+        for (int k = 0; k < 3; k++) put(&a->d_attr9[k], (void **)&s->attr.attr9[k]);
+    }
+    publish_scene(a);
+    side_free(s);
+}
+
+/* the 8-wide nodes of a scene whose tree was built on this device without them: the build is run once more (it is
+ * deterministic: stable sort, stable partitions, a layout of the top that does not depend on its threads) and only its 8-wide
+ * collapse is kept.  The leaves of those nodes index the resident triangle records, so the second run's records must be the
+ * resident ones word for word -- checked, not assumed */
+static int device_rebuild_q8(lh_accel_t *a)
 {
     lh_host_scene *hs = a->hs;
-    const char *e = getenv("LH_REF_BUILD");
-    if (e && strcmp(e, "host") == 0 && !hs->ref_on_device) return 1;
-    char rerr[256] = ""; uint32_t rn = 0, rdepth = 0; double sc6[6];
-    const double t0 = now_s();
-    if (lh_device_ref_build(hs->bvh.ntris, (const double *)a->d_tri64, &a->d_ref_nodes, &rn, &rdepth, &a->d_ref_leaf_prims, &a->d_ref_lca,
-                            &a->d_prim_leafpos, sc6, (void *)a->stream, rerr, sizeof(rerr)) != 0) {
-        a->d_ref_nodes = a->d_ref_leaf_prims = a->d_ref_lca = a->d_prim_leafpos = NULL;
-        if (hs->ref_on_device) return fail("building lucille's own tree on the device failed: %s", rerr);       /* a replica: there is no host copy to fall back on */
-        if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: lucille's own tree not built on the device (%s): host thread\n", rerr);
-        return 1;
+    char err[256] = "";
+    lh_side s; memset(&s, 0, sizeof(s));
+    const lh_side_outcome_t o = side_build(a, &s, a->d_tri64, hs->bvh.ntris, 1, false, err, sizeof(err));
+    /* too deep: as deep as the resident tree, which a commit accepted ("build_depth_cap" may have been lowered since) */
+    if (o != LH_SIDE_BUILT && o != LH_SIDE_TOO_DEEP) { side_free(&s); return fail("building the 8-wide nodes on the device failed: %s", err); }
+    int rc = 0; bool diff = false;
+    if (s.q8) {
+        rc = words_differ(a, s.tri32, a->d_tri32, sizeof(lh_tri32_t) / 4 * (size_t)hs->bvh.ntris, &diff, "comparing the rebuilt triangle order");
+        if (rc == 0 && (diff || s.nq4 != hs->bvh.nq4nodes))
+            rc = fail("the device build did not repeat itself (%u nodes, then %u): the 8-wide nodes are not usable; set \"wide8\" = 1 before the commit", hs->bvh.nq4nodes, s.nq4);
     }
-    publish_ref(a, rn, 0, sc6, sc6 + 3);
-    pthread_mutex_lock(&g_scene_mu);
-    hs->ref_on_device = 1; hs->ref_build_seconds = now_s() - t0;
-    pthread_mutex_unlock(&g_scene_mu);
-    return lh_danger_scan(a);
+    (void)hipFree(s.q4); (void)hipFree(s.tri32); s.q4 = s.tri32 = NULL;          /* only the 8-wide nodes are kept */
+    if (rc != 0) { side_free(&s); return -1; }
+    side_install(a, &s);
+    return 0;
 }
 
 int lh_ensure_formats(lh_accel_t *a, int mask)
@@ -1038,87 +1070,90 @@ static int device_begin(lh_accel_t *a)
 }
 
 /* ---- device replica of the host scene (once per GPU) ---------------------------------------- */
-static int device_upload(lh_accel_t *a, const uint32_t *dmesh_first = NULL)
+static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm, lh_side *s);
+/* LH_ROUTE_INSTALL: committed.  LH_ROUTE_HOST_BUILDERS: the device builders were given up and the caller builds from its host arrays; device
+ * meshes (dmesh_first: their first_prim table) have none and take dmesh_host_fallback from here, with the side */
+static lh_route_t device_upload(lh_accel_t *a, lh_side_builder_t who, const uint32_t *dmesh_first = NULL)
 {
     lh_host_scene *hs = a->hs;
     const double t0 = now_s();
-    if (device_begin(a) != 0) return -1;
+    if (device_begin(a) != 0) return LH_ROUTE_ERROR;
     const size_t nt = hs->bvh.ntris;
-    if (hs->nrm9 && upload_array(a, &a->d_nrm9, hs->nrm9, sizeof(double) * 9 * nt) != 0) return -1;
+    if (hs->nrm9 && upload_array(a, &a->d_nrm9, hs->nrm9, sizeof(double) * 9 * nt) != 0) return LH_ROUTE_ERROR;
     for (int kind = 0; kind < 3; kind++)
-        if (hs->attr9[kind] && upload_array(a, &a->d_attr9[kind], hs->attr9[kind], sizeof(double) * 9 * nt) != 0) return -1;
-    if (hs->st6 && upload_array(a, &a->d_st6, hs->st6, sizeof(double) * 6 * nt) != 0) return -1;
-    if (hs->inside && upload_array(a, &a->d_inside, hs->inside, nt) != 0) return -1;
+        if (hs->attr9[kind] && upload_array(a, &a->d_attr9[kind], hs->attr9[kind], sizeof(double) * 9 * nt) != 0) return LH_ROUTE_ERROR;
+    if (hs->st6 && upload_array(a, &a->d_st6, hs->st6, sizeof(double) * 6 * nt) != 0) return LH_ROUTE_ERROR;
+    if (hs->inside && upload_array(a, &a->d_inside, hs->inside, nt) != 0) return LH_ROUTE_ERROR;
     if (hs->bvh.ntris) {
+        lh_side s; memset(&s, 0, sizeof(s));          /* a device-built scene is made aside: installed whole, or freed */
+        const bool timing = getenv("LH_BUILD_TIMING") != NULL;
         const size_t t64 = sizeof(lh_tri64_t) * nt;
         const double tu = now_s();
-        if (dmesh_first) { if (flatten_device_meshes(a, dmesh_first) != 0 || gather_device_attributes(a, dmesh_first) != 0) return -1; }      /* device meshes: the records are made here, nothing crosses the link */
-        else if (upload_array(a, &a->d_tri64, hs->bvh.tri64, t64) != 0) return -1;
-        if (!dmesh_first && getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 upload (%.0f MB)      %8.2f ms\n", t64 / 1e6, (now_s() - tu) * 1e3);
-        if (hs->device_built) {
-            /* the traversal tree is built here, on this device (lh_build.hip): LBVH -> the same 4-wide nodes */
-            char berr[256] = "";
-            uint32_t nq4 = 0, d4 = 0, st4 = 0, nq8 = 0, d8 = 0; float bmin[3], bmax[3], glo[3], gst[3];
-            /* "wide8" = 1: the 8-wide nodes of ray dumps are collapsed from the same binary tree now.  Left to itself (-1) a scene
-             * gets them when its first dump asks (lh_ensure_formats: the build is run again, ~40 ms per 10 M triangles) -- a renderer
-             * that re-commits every frame and never dumps does not pay for them */
-            const int want_q8 = a->wide8 == 1;
-            const double tb = now_s();
-            uint32_t nlive = hs->bvh.ntris; double dcap = INFINITY;
-            const int rcb = lh_device_build(hs->bvh.ntris, (const double *)a->d_tri64, &a->d_q4nodes, &nq4, &d4, &st4, want_q8, &a->d_q8nodes, &nq8, &d8, &a->d_tri32, bmin, bmax, glo, gst,
-                                            &nlive, &dcap, (void *)a->stream, berr, sizeof(berr));
-            if (rcb == -2) return fail("lh_accel_commit: a vertex coordinate is NaN, infinite or beyond 1e30");
-            if (rcb != 0 && ((a->build_auto && !hs->ref_on_device) || dmesh_first)) {
-                if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: device build failed (%s): host builders\n", berr);
-                return -3;                              /* nobody asked for the device: the caller builds on the host */
-            }
-            if (rcb != 0) return fail("device BVH build failed: %s", berr);
-            pthread_mutex_lock(&g_scene_mu);
-            hs->bvh.nq4nodes = nq4; hs->bvh.q4_depth = d4; hs->bvh.q4_stack = st4; hs->bvh.nnodes = nq4; hs->bvh.max_depth = d4; hs->bvh.build_seconds = now_s() - tb;
-            hs->bvh.nlive = nlive; hs->bvh.deg_dcap = dcap;
-            if (a->d_q8nodes) { hs->bvh.nq8nodes = nq8; hs->bvh.q8_depth = d8; }
-            for (int k = 0; k < 3; k++) { hs->bvh.bmin[k] = bmin[k]; hs->bvh.bmax[k] = bmax[k]; hs->bvh.grid_lo[k] = glo[k]; hs->bvh.grid_step[k] = gst[k]; }
-            pthread_mutex_unlock(&g_scene_mu);
-            publish_scene(a);
-            if (d4 > (uint32_t)a->build_depth_cap) return -3;          /* deeper than k_overflow_fix's private stack (LH_BUILD_DEPTH_MAX: 3 d + 5 <= 264 rows; "build_depth_cap" lowers it): the caller falls back to the host builder */
-            if (hs->have_ref && (hs->ref_on_device || hs->ref_state == 1) && device_ref_tree(a) < 0) {
-                if (!dmesh_first) return -1;
-                if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: %s: host builders\n", lh_last_error());
-                return -3;                              /* device meshes: the flattened triangles are copied out and both trees built on the host */
-            }
-        } else if (upload_array(a, &a->d_tri32, hs->bvh.tri32, sizeof(lh_tri32_t) * nt, 64) != 0) return -1;
-        if (hs->have_ref && __atomic_load_n(&hs->ref_state, __ATOMIC_ACQUIRE) == 2 && attach_ref(a) != 0) return -1;
+        lh_route_t r = LH_ROUTE_INSTALL;
+        if (who == LH_FOR_DEVICE_MESHES) {          /* the records are made here, nothing crosses the link */
+            if (flatten_device_meshes(a, dmesh_first, &s.tri64, "lh_accel_commit") != 0 || gather_device_attributes(a, dmesh_first, &s.attr, "lh_accel_commit") != 0) r = LH_ROUTE_ERROR;
+            s.gathered = 1;
+        } else if (upload_array(a, hs->device_built ? &s.tri64 : &a->d_tri64, hs->bvh.tri64, t64) != 0) r = LH_ROUTE_ERROR;
+        else if (timing) fprintf(stderr, "[lucille_hip] commit: tri64 upload (%.0f MB)      %8.2f ms\n", t64 / 1e6, (now_s() - tu) * 1e3);
+        if (r == LH_ROUTE_INSTALL && hs->device_built) {
+            /* the trees are built here, on this device (lh_build.hip: LBVH -> the same 4-wide nodes).  "wide8" = 1: the 8-wide nodes of ray dumps are
+             * collapsed from the same binary tree now.  Left to itself (-1) a scene gets them when its first dump asks (lh_ensure_formats: the build is
+             * run again, ~40 ms per 10 M triangles) -- a renderer that re-commits every frame and never dumps does not pay for them.  Lucille's own tree
+             * belongs to this build where its home is the device already (device meshes, a replica of such a scene) or the host thread is held back
+             * for it (ref_state 1) -- unless LH_REF_BUILD=host leaves a tree that need not be here to that thread */
+            const char *e = getenv("LH_REF_BUILD");
+            const bool own_tree = hs->have_ref && (hs->ref_on_device || (hs->ref_state == 1 && !(e && strcmp(e, "host") == 0)));
+            char err[256] = "";
+            const lh_side_outcome_t o = side_build(a, &s, s.tri64, hs->bvh.ntris, a->wide8 == 1, own_tree, err, sizeof(err));
+            const bool tree_failed = o == LH_SIDE_BUILDER_FAILED || o == LH_SIDE_TOO_MANY_NODES;
+            r = lh_side_route(who, o, a->build_auto, hs->ref_on_device);
+            if (r == LH_ROUTE_ERROR && o == LH_SIDE_BAD_VERTEX) (void)fail("lh_accel_commit: a vertex coordinate is NaN, infinite or beyond 1e30");
+            if (r == LH_ROUTE_ERROR && tree_failed) (void)fail("device BVH build failed: %s", err);
+            if (r == LH_ROUTE_ERROR && o == LH_SIDE_TOO_DEEP) (void)fail("lh_accel_commit_replica: the device-built tree is deeper than the traversal kernels' stacks (the source fell back to the host builder?)");
+            if (r == LH_ROUTE_ERROR && o == LH_SIDE_REF_FAILED) (void)fail("building lucille's own tree on the device failed: %s", err);          /* (a failed scan has left its own text) */
+            if (timing && r == LH_ROUTE_HOST_BUILDERS && tree_failed) fprintf(stderr, "[lucille_hip] commit: device build failed (%s): host builders\n", err);
+            if (timing && r == LH_ROUTE_HOST_BUILDERS && o == LH_SIDE_REF_FAILED) fprintf(stderr, "[lucille_hip] commit: building lucille's own tree on the device failed: %s: host builders\n", err);
+            if (timing && r == LH_ROUTE_HOST_BUILDERS && o == LH_SIDE_SCAN_FAILED) fprintf(stderr, "[lucille_hip] commit: %s: host builders\n", lh_last_error());
+            if (timing && r == LH_ROUTE_REF_HOST_THREAD) fprintf(stderr, "[lucille_hip] commit: lucille's own tree not built on the device (%s): host thread\n", err);
+            if (r == LH_ROUTE_INSTALL || r == LH_ROUTE_REF_HOST_THREAD) side_install(a, &s);          /* the latter: side_build has left the side without that tree */
+        }
+        const bool fell_back = r == LH_ROUTE_HOST_BUILDERS && who == LH_FOR_DEVICE_MESHES;          /* the fallback's own device_upload commits the scene */
+        if (fell_back) r = dmesh_host_fallback(a, dmesh_first, a->ndmeshes, &s) == 0 ? LH_ROUTE_INSTALL : LH_ROUTE_ERROR;
+        if (fell_back || r == LH_ROUTE_ERROR || r == LH_ROUTE_HOST_BUILDERS) { side_free(&s); return r; }
+        if (!hs->device_built && upload_array(a, &a->d_tri32, hs->bvh.tri32, sizeof(lh_tri32_t) * nt, 64) != 0) return LH_ROUTE_ERROR;
+        if (hs->have_ref && __atomic_load_n(&hs->ref_state, __ATOMIC_ACQUIRE) == 2 && attach_ref(a) != 0) return LH_ROUTE_ERROR;
         /* resident from the start: what the default kernel reads (everything else on first use) */
-        if (lh_ensure_formats(a, LH_FMT_Q16X4) != 0) return -1;
+        if (lh_ensure_formats(a, LH_FMT_Q16X4) != 0) return LH_ROUTE_ERROR;
     }
     a->upload_seconds = now_s() - t0;
-    if (size_grid(a) != 0) return -1;
+    if (size_grid(a) != 0) return LH_ROUTE_ERROR;
     a->committed = 1;
-    return 0;
+    return LH_ROUTE_INSTALL;
 }
 
 /* a device-mesh scene whose trees the device builders could not make (an LBVH deeper than the walks' stacks, memory): the one case
  * in which its triangles are copied to the host -- once, as flattened by the kernel -- and both trees are built there from that
  * copy, handed to the host builders as ONE mesh of 3 n vertices with the identity index list; the scene goes on as a host-built one */
-static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm)
+static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm, lh_side *s)
 {
     lh_host_scene *hs = a->hs;
+    a->update_fellback = a->updatable;
     const size_t nt = first[nm];
     double *tri = (double *)malloc(sizeof(lh_tri64_t) * nt);
     uint32_t *ident = (uint32_t *)malloc(sizeof(uint32_t) * 3 * nt);
     lh_mesh_copy *mc = (lh_mesh_copy *)calloc(1, sizeof(lh_mesh_copy));
     if (!tri || !ident || !mc) { free(tri); free(ident); free(mc); return fail("out of memory"); }
     const double t0 = now_s();
-    const hipError_t e = hipMemcpy(tri, a->d_tri64, sizeof(lh_tri64_t) * nt, hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy(tri, s->tri64, sizeof(lh_tri64_t) * nt, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { free(tri); free(ident); free(mc); return fail("lh_accel_commit: copying the flattened triangles to the host failed: %s", hipGetErrorString(e)); }
     if (getenv("LH_BUILD_TIMING")) fprintf(stderr, "[lucille_hip] commit: tri64 to the host (%.0f MB)   %8.2f ms\n", sizeof(lh_tri64_t) * (double)nt / 1e6, (now_s() - t0) * 1e3);
     for (size_t i = 0; i < 3 * nt; i++) ident[i] = (uint32_t)i;
     /* the per-primitive attribute arrays the gather made cross the release with the triangles: into the host scene, in the layout
      * device_upload carries back (host_build below sees one mesh without attributes and leaves them alone) */
     struct { void *dev; void **host; size_t bytes; } carry[] = {
-        {a->d_nrm9, (void **)&hs->nrm9, sizeof(double) * 9 * nt}, {a->d_attr9[0], (void **)&hs->attr9[0], sizeof(double) * 9 * nt},
-        {a->d_attr9[1], (void **)&hs->attr9[1], sizeof(double) * 9 * nt}, {a->d_attr9[2], (void **)&hs->attr9[2], sizeof(double) * 9 * nt},
-        {a->d_st6, (void **)&hs->st6, sizeof(double) * 6 * nt}, {a->d_inside, (void **)&hs->inside, nt}};
+        {s->attr.nrm9, (void **)&hs->nrm9, sizeof(double) * 9 * nt}, {s->attr.attr9[0], (void **)&hs->attr9[0], sizeof(double) * 9 * nt},
+        {s->attr.attr9[1], (void **)&hs->attr9[1], sizeof(double) * 9 * nt}, {s->attr.attr9[2], (void **)&hs->attr9[2], sizeof(double) * 9 * nt},
+        {s->attr.st6, (void **)&hs->st6, sizeof(double) * 6 * nt}, {s->attr.inside, (void **)&hs->inside, nt}};
     for (size_t k = 0; k < sizeof(carry) / sizeof(carry[0]); k++) {
         if (!carry[k].dev) continue;
         free(*carry[k].host);
@@ -1127,6 +1162,7 @@ static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm
         if (ec != hipSuccess) { free(tri); free(ident); free(mc); return fail("lh_accel_commit: copying the gathered attributes to the host failed: %s", hipGetErrorString(ec)); }
     }
     free_dmeshes(a);
+    side_free(s);
     release_device(a);
     lh_bvh_release(&hs->bvh); lh_refbvh_release(&hs->ref); hs->ref_state = 0; hs->ref_on_device = 0;
     mc->npos = mc->nidx = (uint32_t)(3 * nt); mc->pos = tri; mc->idx = ident;
@@ -1134,7 +1170,7 @@ static int dmesh_host_fallback(lh_accel_t *a, const uint32_t *first, uint32_t nm
     if (host_build(a, 0, false, false) != 0) return -1;
     hs->nmeshes = nm;
     if (dmesh_prim_tables(hs, first, nm) != 0) return -1;
-    return device_upload(a) == 0 ? 0 : -1;
+    return device_upload(a, LH_FOR_HOST_MESHES) == LH_ROUTE_INSTALL ? 0 : -1;
 }
 
 /* lh_accel_commit of an accelerator that holds device meshes: always the device path, no host copy of the triangles */
@@ -1153,8 +1189,7 @@ static int commit_device_meshes(lh_accel_t *a)
     hs->ref_on_device = 1;                      /* lucille's own tree is built on the device too: there are no host triangles for a host thread */
     a->build_auto = 0;
     int rc = dmesh_prim_tables(hs, first, nm);
-    if (rc == 0) rc = device_upload(a, first);
-    if (rc == -3) { a->update_fellback = a->updatable; rc = dmesh_host_fallback(a, first, nm); }
+    if (rc == 0) rc = device_upload(a, LH_FOR_DEVICE_MESHES, first) == LH_ROUTE_INSTALL ? 0 : -1;
     free(first);
     if (rc != 0 || !a->updatable || a->update_fellback) free_dmeshes(a);          /* an updatable accelerator keeps its blocks and events: freed by lh_accel_destroy */
     if (rc != 0) return -1;
@@ -1197,14 +1232,14 @@ extern "C" int lh_accel_commit(lh_accel_t *a, int build_threads)
         const double tc0 = now_s();
         if (host_build(a, build_threads, true, true) != 0) return -1;
         const double tc1 = now_s();
-        const int rc = device_upload(a);
+        const lh_route_t next = device_upload(a, LH_FOR_HOST_MESHES);
         if (timing) fprintf(stderr, "[lucille_hip] commit: host side %.2f ms, device side %.2f ms\n", (tc1 - tc0) * 1e3, (now_s() - tc1) * 1e3);
         {
             lh_host_scene *hs = a->hs;
-            if (hs->ref_state == 1 && !hs->ref_thread_live && rc != 0) hs->ref_state = 0;      /* the device side failed (or the tree is too deep: -3): no background
+            if (hs->ref_state == 1 && !hs->ref_thread_live && next != LH_ROUTE_INSTALL) hs->ref_state = 0;      /* the device side failed, or was given up for the host builders: no background
                                                                                                   * build of lucille's tree for a scene that is about to be rebuilt on the host, or dropped */
             if (hs->ref_state == 1 && !hs->ref_thread_live) {
-                if (rc == 0 && a->nmeshes) {
+                if (next == LH_ROUTE_INSTALL && a->nmeshes) {
                     /* the mesh copies are no longer needed: the background thread returns them to the system */
                     hs->trash = (void **)calloc((size_t)a->nmeshes * 8, sizeof(void *));
                     if (hs->trash) {
@@ -1220,8 +1255,8 @@ extern "C" int lh_accel_commit(lh_accel_t *a, int build_threads)
                 hs->ref_thread_live = 1;
             }
         }
-        if (rc == -3) {
-            /* an LBVH deeper than the kernel's stack bound (degenerate distributions): build on the host after all */
+        if (next == LH_ROUTE_HOST_BUILDERS) {
+            /* an LBVH deeper than the kernel's stack bound (degenerate distributions), or one nobody asked for that failed: build on the host after all */
             (void)hipSetDevice(a->device); release_device(a);
             lh_host_scene *hs = a->hs;
             pthread_mutex_lock(&g_scene_mu);
@@ -1237,13 +1272,13 @@ extern "C" int lh_accel_commit(lh_accel_t *a, int build_threads)
                 for (int k = 0; k < 5; k++) free(a->meshes[g].attr[k]);
             }
             free(a->meshes); a->meshes = NULL; a->nmeshes = 0;
-            if (rc != 0) return -1;
+            if (next != LH_ROUTE_INSTALL) return -1;
             a->commit_failed = 0;
             return 0;
         }
     }
     if (host_build(a, build_threads, false, false) != 0) return -1;
-    if (device_upload(a) != 0) return -1;
+    if (device_upload(a, LH_FOR_HOST_MESHES) != LH_ROUTE_INSTALL) return -1;
     a->commit_failed = 0;
     return 0;
 }
@@ -1298,66 +1333,6 @@ extern "C" int lh_accel_update_mesh_device(lh_accel_t *a, uint32_t mesh, uint32_
     return 0;
 }
 
-/* a scene built beside the resident one: the arrays of scene_rows a re-commit replaces, and what device_upload writes into the headers for them */
-struct lh_side {
-    void *tri64, *tri32, *q4, *q8, *ref_nodes, *ref_leaf_prims, *ref_lca, *leafpos;
-    lh_gather_out_t attr;
-    uint32_t nq4, d4, st4, nq8, d8, nlive, ref_nnodes; double dcap, sc6[6], build_seconds, ref_seconds;
-    float bmin[3], bmax[3], glo[3], gst[3];
-    lh_danger_found danger;
-};
-
-static void side_free(lh_side *s)
-{
-    void *p[] = {s->tri64, s->tri32, s->q4, s->q8, s->ref_nodes, s->ref_leaf_prims, s->ref_lca, s->leafpos,
-                 s->attr.nrm9, s->attr.attr9[0], s->attr.attr9[1], s->attr.attr9[2], s->attr.st6, s->attr.inside};
-    for (size_t k = 0; k < sizeof(p) / sizeof(p[0]); k++) if (p[k]) (void)hipFree(p[k]);
-    memset(s, 0, sizeof(*s));
-}
-
-/* *diff: the two arrays of nwords words differ somewhere */
-static int words_differ(lh_accel_t *a, const void *x, const void *y, size_t nwords, bool *diff)
-{
-    int *flag = NULL, h_flag = 0;
-    HIPCHK(hipMalloc((void **)&flag, sizeof(int)));
-    int rc = 0;
-    if (hipMemsetAsync(flag, 0, sizeof(int), a->stream) != hipSuccess) rc = fail("lh_accel_recommit: comparing the triangle records failed");
-    if (rc == 0) {
-        hipLaunchKernelGGL(k_words_differ, dim3(2048), dim3(256), 0, a->stream, nwords, (const uint32_t *)x, (const uint32_t *)y, flag);
-        if (hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, a->stream) != hipSuccess || hipStreamSynchronize(a->stream) != hipSuccess)
-            rc = fail("lh_accel_recommit: comparing the triangle records failed: %s", hipGetErrorString(hipGetLastError()));
-    }
-    (void)hipFree(flag);
-    *diff = h_flag != 0;
-    return rc;
-}
-
-/* what device_upload builds from the records, from s->tri64 and beside the scene: the traversal tree and tri32, lucille's own tree, the danger list */
-static int side_build_trees(lh_accel_t *a, lh_side *s, uint32_t nt, int want_q8)
-{
-    static const char *cannot = "lh_accel_recommit: the device builders cannot build the updated scene (%s): it needs a new accelerator";
-    char err[256] = "";
-    const double tb = now_s();
-    s->nlive = nt; s->dcap = INFINITY;
-    s->danger.nhost = s->danger.ndev = LH_DANGER_ALL;          /* until a scan says otherwise (LH_REFTREE=0: none runs) */
-    const int rcb = lh_device_build(nt, (const double *)s->tri64, &s->q4, &s->nq4, &s->d4, &s->st4, want_q8, &s->q8, &s->nq8, &s->d8, &s->tri32, s->bmin, s->bmax, s->glo, s->gst,
-                                    &s->nlive, &s->dcap, (void *)a->stream, err, sizeof(err));
-    if (rcb == -2) return fail("lh_accel_recommit: a vertex coordinate is NaN, infinite or beyond 1e30");
-    if (rcb != 0) return fail(cannot, err);
-    s->build_seconds = now_s() - tb;
-    if (s->d4 > (uint32_t)a->build_depth_cap) { snprintf(err, sizeof(err), "a tree of %u levels, the walks' stacks take %d", s->d4, a->build_depth_cap); return fail(cannot, err); }
-    if ((uint64_t)s->nq4 * sizeof(lh_q4node_t) >= (1ull << 32)) return fail(cannot, "more 4-wide nodes than a 32-bit byte offset addresses");
-    if (!a->hs->have_ref) return 0;
-    const double tr = now_s(); uint32_t rdepth = 0;
-    if (lh_device_ref_build(nt, (const double *)s->tri64, &s->ref_nodes, &s->ref_nnodes, &rdepth, &s->ref_leaf_prims, &s->ref_lca, &s->leafpos, s->sc6,
-                            (void *)a->stream, err, sizeof(err)) != 0) {
-        s->ref_nodes = s->ref_leaf_prims = s->ref_lca = s->leafpos = NULL;
-        return fail(cannot, err);
-    }
-    s->ref_seconds = now_s() - tr;
-    return danger_scan_arrays(a, nt, s->dcap, s->tri64, s->leafpos, s->ref_lca, s->ref_nodes, s->sc6, s->sc6 + 3, s->glo, s->gst, &s->danger);
-}
-
 extern "C" int lh_accel_recommit(lh_accel_t *a, lh_recommit_info_t *info)
 {
     const char *who = "lh_accel_recommit";
@@ -1379,54 +1354,35 @@ extern "C" int lh_accel_recommit(lh_accel_t *a, lh_recommit_info_t *info)
     lh_recommit_plan_t plan = lh_recommit_plan(a->staged_pos, a->staged_attr, 1, had_q8, a->wide8);
     lh_side s; memset(&s, 0, sizeof(s));
     int rc = 0;
-    /* everything below is built aside: the accelerator's arrays and headers are read, never written, until the swap */
+    /* everything below is built aside: the accelerator's arrays and headers are read, never written, until the install */
     if (plan.flatten && nt) {
         bool changed = false;
-        rc = flatten_device_meshes_into(a, first, &s.tri64, who);
-        if (rc == 0 && plan.compare) rc = words_differ(a, s.tri64, a->d_tri64, sizeof(lh_tri64_t) / 4 * (size_t)nt, &changed);
+        rc = flatten_device_meshes(a, first, &s.tri64, who);
+        if (rc == 0 && plan.compare) rc = words_differ(a, s.tri64, a->d_tri64, sizeof(lh_tri64_t) / 4 * (size_t)nt, &changed, "lh_accel_recommit: comparing the triangle records");
         plan = lh_recommit_plan(a->staged_pos, a->staged_attr, changed, had_q8, a->wide8);
         if (rc == 0 && !plan.trees) { (void)hipFree(s.tri64); s.tri64 = NULL; }          /* the resident records word for word: the trees stand */
     } else
         plan = lh_recommit_plan(a->staged_pos, a->staged_attr, 0, had_q8, a->wide8);          /* no triangles: nothing to build from */
     const double t1 = now_s();
-    if (rc == 0 && plan.trees) rc = side_build_trees(a, &s, nt, plan.q8);
+    if (rc == 0 && plan.trees) {
+        char err[256] = "";
+        const lh_side_outcome_t o = side_build(a, &s, s.tri64, nt, plan.q8, hs->have_ref != 0, err, sizeof(err));
+        if (lh_side_route(LH_FOR_RECOMMIT, o, 0, hs->ref_on_device) != LH_ROUTE_INSTALL)
+            rc = o == LH_SIDE_BAD_VERTEX ? fail("%s: a vertex coordinate is NaN, infinite or beyond 1e30", who) : o == LH_SIDE_SCAN_FAILED ? -1 /* the scan's own text */
+                                         : fail("%s: the device builders cannot build the updated scene (%s): it needs a new accelerator", who, err);
+    }
     const double t2 = now_s();
-    if (rc == 0 && plan.gather) rc = gather_device_attributes_into(a, first, &s.attr, who);
+    if (rc == 0 && plan.gather) { rc = gather_device_attributes(a, first, &s.attr, who); s.gathered = 1; }
     const double tg = now_s();
     free(first);
     /* a launch a caller enqueued earlier, on any stream, may still read the old arrays through its own copy of the scene */
     if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = fail("%s: waiting for the device failed: %s", who, hipGetErrorString(hipGetLastError()));
     if (rc != 0) { side_free(&s); return -1; }          /* still committed, still the old scene; what was staged stays staged */
     const double t3 = now_s();
-    void *old[14]; int nold = 0;
-    if (plan.trees) {
-        void **slot[] = {&a->d_tri64, &a->d_tri32, &a->d_q4nodes, &a->d_q8nodes, &a->d_ref_nodes, &a->d_ref_leaf_prims, &a->d_ref_lca, &a->d_prim_leafpos};
-        void *now[] = {s.tri64, s.tri32, s.q4, s.q8, s.ref_nodes, s.ref_leaf_prims, s.ref_lca, s.leafpos};
-        for (int k = 0; k < 8; k++) { old[nold++] = *slot[k]; *slot[k] = now[k]; }
-        pthread_mutex_lock(&g_scene_mu);
-        lh_bvh_t *b = &hs->bvh;
-        b->nq4nodes = s.nq4; b->q4_depth = s.d4; b->q4_stack = s.st4; b->nnodes = s.nq4; b->max_depth = s.d4; b->build_seconds = s.build_seconds;
-        b->nlive = s.nlive; b->deg_dcap = s.dcap;
-        b->nq8nodes = s.q8 ? s.nq8 : 0u; b->q8_depth = s.q8 ? s.d8 : 0u;
-        for (int k = 0; k < 3; k++) { b->bmin[k] = s.bmin[k]; b->bmax[k] = s.bmax[k]; b->grid_lo[k] = s.glo[k]; b->grid_step[k] = s.gst[k]; }
-        /* the danger list of the OLD geometry must not stay: lh_danger_scan writes the host list only over LH_DANGER_ALL */
-        memset(b->danger, 0, sizeof(b->danger));
-        if (s.danger.nhost != LH_DANGER_ALL) memcpy(b->danger, s.danger.boxes, sizeof(double) * 6 * (size_t)s.danger.nhost);
-        __atomic_store_n(&b->ndanger, s.danger.nhost, __ATOMIC_RELEASE);
-        hs->ref_build_seconds = s.ref_seconds;
-        pthread_mutex_unlock(&g_scene_mu);
-        a->dev.ndanger = s.danger.ndev;
-        for (int k = 0; k < 3; k++) a->dev.danger[k] = s.danger.ndev != LH_DANGER_ALL ? s.danger.words[k] : 0u;
-        if (hs->have_ref) publish_ref(a, s.ref_nnodes, 0, s.sc6, s.sc6 + 3);
-        a->hw_ns = 0.0; a->hw_gpu_left = 0;
+    if (plan.trees) {          /* the danger list of the OLD geometry must not stay: an install writes the host list only over LH_DANGER_ALL */
+        pthread_mutex_lock(&g_scene_mu); __atomic_store_n(&hs->bvh.ndanger, LH_DANGER_ALL, __ATOMIC_RELEASE); pthread_mutex_unlock(&g_scene_mu);
     }
-    if (plan.gather) {
-        void **slot[] = {&a->d_nrm9, &a->d_attr9[0], &a->d_attr9[1], &a->d_attr9[2], &a->d_st6, &a->d_inside};
-        void *now[] = {s.attr.nrm9, s.attr.attr9[0], s.attr.attr9[1], s.attr.attr9[2], s.attr.st6, s.attr.inside};
-        for (int k = 0; k < 6; k++) { old[nold++] = *slot[k]; *slot[k] = now[k]; }
-    }
-    publish_scene(a);
-    for (int k = 0; k < nold; k++) if (old[k]) (void)hipFree(old[k]);
+    side_install(a, &s);
     if (plan.trees && !a->grid_user) (void)size_grid(a);          /* the new tree's stack rows (it asks the runtime for the device's CUs: the old grid stays a valid one) */
     a->staged_pos = a->staged_attr = 0;
     a->upload_seconds = now_s() - t0;
@@ -1459,11 +1415,7 @@ extern "C" int lh_accel_commit_replica(lh_accel_t *dst, lh_accel_t *src)
     pthread_mutex_unlock(&g_scene_mu);
     free(old);                                  /* a fresh accelerator's scene holds nothing */
     dst->commit_failed = 1;
-    {
-        const int rc = device_upload(dst);              /* a device-built scene is built again on this replica's device */
-        if (rc == -3) return fail("lh_accel_commit_replica: the device-built tree is deeper than the traversal kernels' stacks (the source fell back to the host builder?)");
-        if (rc != 0) return -1;
-    }
+    if (device_upload(dst, LH_FOR_REPLICA) != LH_ROUTE_INSTALL) return -1;              /* a device-built scene is built again on this replica's device */
     dst->commit_failed = 0;
     return 0;
 }

@@ -125,7 +125,7 @@ struct lh_accel {
     /* "updatable" = 1: the commit keeps dmeshes and dmesh_events (ndmeshes stays non-zero on a committed accelerator: the only one), updates stage
      * into them and lh_accel_recommit rebuilds from them.  update_fellback: the commit took dmesh_host_fallback, which needs the blocks gone */
     int updatable, update_fellback, staged_pos, staged_attr;
-    int build_depth_cap;               /* 4-wide levels a device-built tree may have (device_upload returns -3 beyond: the host builders; a re-commit fails) */
+    int build_depth_cap;               /* 4-wide levels a device-built tree may have (beyond: the outcome LH_SIDE_TOO_DEEP of lh_route.h -- the host builders; a replica and a re-commit fail) */
     lh_host_scene *hs;        /* never NULL after create */
     void *d_ref_lca, *d_prim_leafpos, *d_ref_nodes, *d_ref_leaf_prims;   /* lucille's own tree: owned here, published in dev (lh_commit.hip publish_scene) */
     void *d_danger;                    /* 8 + LH_DANGER_MAX x 6 doubles: the count, then the boxes of lh_dev_scene_t.danger (lh_commit.hip lh_danger_scan) */
