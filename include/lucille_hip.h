@@ -183,6 +183,18 @@ int  lh_accel_wait_exact(lh_accel_t *accel);
  * *nnodes nodes of 128 bytes (lh_refbvh.h: two child boxes of 6 doubles, child[2], axis, is_leaf, first, count, parent, depth;
  * root = 0) and the ntriangles primitive ids in leaf order.  Either pointer may be NULL.  Fails if the tree is not attached. */
 int  lh_accel_ref_tree(lh_accel_t *accel, uint32_t *nnodes, void *nodes_out, uint32_t *leaf_prims_out);
+/* The traversal trees as the walks read them, for inspection too (tests check every node, box and stack figure of a tree the device built: hit
+ * records show a box one grid code too tight, or a stack count one row short, on next to no ray).  A read-only image: the DEVICE arrays, copied back,
+ * never a host copy; nothing is built and no kernel runs.  info: the figures the launches use -- ntris records of 48 bytes (leaf order; the first
+ * nlive are in the leaves) and of 72 bytes (primitive-id order), nq4 4-wide nodes of 64 bytes (12 words lo | hi << 16 on the 16-bit grid, 4 child
+ * references), their levels and the stack rows the builder counted (0: 3 x q4_depth + 5 rows), nq8 8-wide nodes of 128 bytes and their levels
+ * (both 0 while the 8-wide nodes are not resident), whether the device built the trees, the scene box, the grid and the radius the rays' set-up is
+ * given.  Every pointer may be NULL; an array is written only up to the counts info reports (call once for the counts, once for the arrays). */
+typedef struct lh_tree_image {
+    uint32_t ntris, nlive, nq4, q4_depth, q4_stack, nq8, q8_depth, device_built;
+    float    bmin[3], bmax[3], grid_lo[3], grid_step[3], scene_r;
+} lh_tree_image_t;
+int  lh_accel_tree_image(lh_accel_t *accel, lh_tree_image_t *info, void *q4nodes, void *q8nodes, void *tri32, void *tri64);
 /* The danger list as the walks read it, for inspection too (tests compare a re-committed accelerator's with a fresh one's: the hit records
  * cannot show a stale list, it only routes other rays to the reference's own walk).  *ndevice: 0 = every ray beyond the cap is routed, else
  * the number of listed leaves behind the ONE box device_box[3] (lo | hi << 16 per axis on the scene's 16-bit grid; zeros with 0);

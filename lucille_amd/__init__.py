@@ -16,7 +16,7 @@ include/lucille_accel.h, lh_host.c) is C and is exercised by the C program in te
 There is no CPU fallback: loading fails loudly when the library is missing and
 every query fails loudly when no HIP device is visible.
 """
-from .binding import (Camera, HipAccel, LucilleHipError, RecommitInfo, MISS, MODE_ANY, MODE_CLOSEST, RAYS_F64, RAYS_F32, REC_F64, REC16,  # noqa: F401
+from .binding import (Camera, HipAccel, LucilleHipError, RecommitInfo, TreeImage, MISS, MODE_ANY, MODE_CLOSEST, RAYS_F64, RAYS_F32, REC_F64, REC16,  # noqa: F401
                       SELECT_HIT, SELECT_MISS, SELECT_OCCLUDED, SELECT_UNOCCLUDED, compact, POS_F64, POS_F32, AO_NO_HIT,
                       VARIANT_DEFAULT, VARIANT_DIRECT,
                       VARIANT_SPEC, build_library, device_count, library_path,

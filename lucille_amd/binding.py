@@ -57,6 +57,13 @@ class RecommitInfo(C.Structure):
     _fields_ = [("flattened", C.c_int), ("rebuilt_trees", C.c_int), ("regathered", C.c_int), ("seconds", C.c_double)]
 
 
+class TreeImage(C.Structure):
+    """lh_tree_image_t (include/lucille_hip.h): the figures of the resident traversal trees"""
+    _fields_ = [("ntris", C.c_uint32), ("nlive", C.c_uint32), ("nq4", C.c_uint32), ("q4_depth", C.c_uint32), ("q4_stack", C.c_uint32),
+                ("nq8", C.c_uint32), ("q8_depth", C.c_uint32), ("device_built", C.c_uint32),
+                ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("grid_lo", C.c_float * 3), ("grid_step", C.c_float * 3), ("scene_r", C.c_float)]
+
+
 class RasterPlane(C.Structure):
     """lh_raster_plane_t (include/lucille_hip.h)"""
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("frame", C.c_double * 9), ("eye", C.c_double * 3), ("fov", C.c_double)]
@@ -235,7 +242,7 @@ BEAM_SET_DTYPE = np.dtype([("org", np.float64, (3,)), ("dir", np.float64, (4, 3)
 
 # every symbol include/lucille_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [
-    "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_update_mesh_device", "lh_accel_recommit", "lh_accel_danger_list", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree",
+    "lh_device_count", "lh_last_error", "lh_accel_create", "lh_accel_add_mesh", "lh_accel_add_mesh_device", "lh_accel_update_mesh_device", "lh_accel_recommit", "lh_accel_danger_list", "lh_accel_commit", "lh_accel_wait_exact", "lh_accel_ref_tree", "lh_accel_tree_image",
     "lh_accel_destroy", "lh_accel_info", "lh_accel_prim_lookup", "lh_accel_intersect1", "lh_accel_combine_statistics", "lh_accel_intersect_diag_host", "lh_accel_intersect_diag_device",
     "lh_accel_intersect_host", "lh_accel_intersect_device", "lh_accel_intersect_host_ex", "lh_accel_intersect_device_ex", "lh_accel_intersect_device_indexed", "lh_accel_intersect_device_tmax", "lh_accel_intersect_host_tmax", "lh_accel_compact_device", "lh_accel_intersect_device_counted", "lh_accel_last_retraced", "lh_accel_dump_node_bytes", "lh_accel_order_statistics",
     "lh_accel_set_grid", "lh_accel_set_param", "lh_accel_export", "lh_accel_set_normals", "lh_render_primary_rays",
@@ -290,6 +297,8 @@ def lib():
     L.lh_accel_commit.argtypes = [vp, i32]
     L.lh_accel_wait_exact.argtypes = [vp]
     L.lh_accel_ref_tree.argtypes = [vp, C.POINTER(C.c_uint32), vp, vp]
+    if hasattr(L, "lh_accel_tree_image"):                # (an older library under LH_LIBRARY has no tree image)
+        L.lh_accel_tree_image.argtypes = [vp, C.POINTER(TreeImage), vp, vp, vp, vp]
     L.lh_accel_destroy.argtypes = [vp]
     L.lh_accel_destroy.restype = None
     L.lh_accel_info.argtypes = [vp, C.POINTER(AccelInfo)]
@@ -718,6 +727,31 @@ class HipAccel:
         prims = np.zeros(self.info()["ntriangles"], dtype=np.uint32)
         _check(self.L.lh_accel_ref_tree(self.h, C.byref(nn), nodes.ctypes.data_as(C.c_void_p), prims.ctypes.data_as(C.c_void_p)), "lh_accel_ref_tree")
         return nodes, prims
+
+    # the record layouts of lh_q4node_t / lh_q8node_t / lh_tri32_t (lh_bvh.h); lh_tri64_t is 9 doubles
+    Q4_NODE = np.dtype([("w", "<u4", (4, 3)), ("ref", "<i4", (4,))])
+    Q8_NODE = np.dtype([("w", "<u4", (8, 3)), ("ref", "<i4", (8,))])
+    TRI32 = np.dtype([("v0", "<f4", (3,)), ("e1", "<f4", (3,)), ("e2", "<f4", (3,)), ("prim", "<u4"), ("ne1", "<f4"), ("ne2", "<f4")])
+
+    def tree_image(self):
+        """lh_accel_tree_image: the traversal trees the device holds, read back -> dict of the figures of lh_tree_image_t (scalars; bmin, bmax,
+        grid_lo, grid_step as float32 [3]) and the arrays q4nodes (Q4_NODE [nq4]), q8nodes (Q8_NODE [nq8], empty while not resident),
+        tri32 (TRI32 [ntris], leaf order) and tri64 (float64 [ntris, 3, 3], primitive-id order)"""
+        t = TreeImage()
+        _check(self.L.lh_accel_tree_image(self.h, C.byref(t), None, None, None, None), "lh_accel_tree_image")
+        q4 = np.zeros(t.nq4, self.Q4_NODE); q8 = np.zeros(t.nq8, self.Q8_NODE)
+        t32 = np.zeros(t.ntris, self.TRI32); t64 = np.zeros((t.ntris, 3, 3), np.float64)
+        u = TreeImage()
+        _check(self.L.lh_accel_tree_image(self.h, C.byref(u), q4.ctypes.data_as(C.c_void_p), q8.ctypes.data_as(C.c_void_p),
+                                          t32.ctypes.data_as(C.c_void_p), t64.ctypes.data_as(C.c_void_p)), "lh_accel_tree_image")
+        if bytes(u) != bytes(t):
+            raise LucilleHipError("lh_accel_tree_image: the scene changed between the two calls")
+        out = {k: int(getattr(t, k)) for k in ("ntris", "nlive", "nq4", "q4_depth", "q4_stack", "nq8", "q8_depth", "device_built")}
+        for k in ("bmin", "bmax", "grid_lo", "grid_step"):
+            out[k] = np.array(list(getattr(t, k)), np.float32)
+        out["scene_r"] = np.float32(t.scene_r)
+        out.update(q4nodes=q4, q8nodes=q8, tri32=t32, tri64=t64)
+        return out
 
     def danger_list(self):
         """lh_accel_danger_list -> (leaves behind the device's box or 0 = every ray beyond the cap, the box's three words, the host list [n, 6])"""

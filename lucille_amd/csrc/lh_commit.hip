@@ -1433,6 +1433,31 @@ extern "C" int lh_accel_ref_tree(lh_accel_t *a, uint32_t *nnodes, void *nodes_ou
     return 0;
 }
 
+/* the resident traversal trees as the walks read them: the device arrays, and the figures of a->dev the launch plan and the rays' set-up are given */
+extern "C" int lh_accel_tree_image(lh_accel_t *a, lh_tree_image_t *info, void *q4nodes, void *q8nodes, void *tri32, void *tri64)
+{
+    lh_guard guard(a);
+    if (!a || !a->committed) return fail("lh_accel_tree_image: accel not committed");
+    HIPCHK(hipSetDevice(a->device));
+    const lh_bvh_t *b = &a->hs->bvh; const lh_dev_scene_t *d = &a->dev;
+    const size_t nt = d->ntris, n4 = a->d_q4nodes ? d->nq4nodes : 0u, n8 = a->d_q8nodes ? d->nq8nodes : 0u;
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->ntris = d->ntris; info->nlive = nt ? b->nlive : 0u;
+        info->nq4 = (uint32_t)n4; info->q4_depth = d->q4_depth; info->q4_stack = d->q4_stack;
+        info->nq8 = (uint32_t)n8; info->q8_depth = n8 ? d->q8_depth : 0u;
+        info->device_built = a->hs->device_built ? 1u : 0u;
+        for (int k = 0; k < 3; k++) { info->bmin[k] = b->bmin[k]; info->bmax[k] = b->bmax[k]; info->grid_lo[k] = d->grid_lo[k]; info->grid_step[k] = d->grid_step[k]; }
+        info->scene_r = d->scene_r;
+    }
+    HIPCHK(hipStreamSynchronize(a->stream));          /* 8-wide nodes made on first use are written on the accelerator's stream */
+    if (q4nodes && n4) HIPCHK(hipMemcpy(q4nodes, a->d_q4nodes, sizeof(lh_q4node_t) * n4, hipMemcpyDeviceToHost));
+    if (q8nodes && n8) HIPCHK(hipMemcpy(q8nodes, a->d_q8nodes, sizeof(lh_q8node_t) * n8, hipMemcpyDeviceToHost));
+    if (tri32 && nt && a->d_tri32) HIPCHK(hipMemcpy(tri32, a->d_tri32, sizeof(lh_tri32_t) * nt, hipMemcpyDeviceToHost));
+    if (tri64 && nt && a->d_tri64) HIPCHK(hipMemcpy(tri64, a->d_tri64, sizeof(lh_tri64_t) * nt, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int lh_accel_danger_list(const lh_accel_t *a, uint32_t *ndevice, uint32_t device_box[3], uint32_t *nhost, double *host_boxes)
 {
     lh_guard guard(a);
