@@ -1255,6 +1255,26 @@ class HipAccel:
                                                 uu.ctypes.data, vv.ctypes.data, st.ctypes.data), "lh_accel_state_build_host")
         return st
 
+    def state_build_device(self, org, dr, prim, t, u, v, out=None, stream=None):
+        """lh_accel_state_build_device: float64 device tensors org, dr [n, 3], t, u, v [n] and the int32 / uint32 prim [n] of a batch's hit
+        records -> the float64 device tensor [n, 24] of their ri_intersection_state_build records, in stream order (nothing is read back).
+        The record of a miss (prim AO_NO_HIT's bits, LH_MISS_PRIM) is NOT written, and no record at all on an empty scene: out -- such a tensor
+        to fill -- keeps what it held there; with out=None it is allocated with torch.empty and those records are UNSPECIFIED."""
+        import torch
+        what = "state_build_device"
+        n, prim, t, u, v = self._ao_batch_in(what, org, dr, (prim, t, u, v), None, None)
+        if out is None:
+            out = torch.empty((n, STATE_DOUBLES), dtype=torch.float64, device=org.device)
+        if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float64 and out.dim() == 2 and tuple(out.shape) == (n, STATE_DOUBLES)
+                and out.is_contiguous()):
+            raise ValueError("%s: out must be a contiguous float64 device tensor [n, %d]" % (what, STATE_DOUBLES))
+        if stream is None:
+            stream = torch.cuda.current_stream(org.device)
+        stream = getattr(stream, "cuda_stream", stream)
+        _check(self.L.lh_accel_state_build_device(self.h, n, _dptr(org), _dptr(dr), _dptr(prim), _dptr(t), _dptr(u), _dptr(v), _dptr(out), C.c_void_p(stream)),
+               "lh_accel_state_build_device")
+        return out
+
     # ---- the AO stage for a caller's batch of hit records -------------------------------
     @staticmethod
     def _ao_batch_in(what, org, dr, records, key, uniforms):

@@ -265,6 +265,18 @@ void lo_state_batch(const lo_scene_t *s, size_t n, const double *org, const doub
     }
 }
 
+/* full state of n caller-made hit records (no ray is traced: prim, t, u, v are taken as they are); a miss slot
+ * (prim 0xFFFFFFFF) gives zeros.  Every other prim must be a primitive of the scene */
+void lo_state_records(const lo_scene_t *s, size_t n, const double *org, const double *dir, const uint32_t *prim,
+                      const double *t, const double *u, const double *v, double *state24)
+{
+    size_t i;
+    for (i = 0; i < n; i++) {
+        memset(state24 + 24 * i, 0, 24 * sizeof(double));
+        if (prim[i] != 0xFFFFFFFFu) lo_state_build_full(s, prim[i], t[i], u[i], v[i], org + 3 * i, dir + 3 * i, state24 + 24 * i);
+    }
+}
+
 /* AO rays of one shading point (calculate_occlusion, ambientocclusion.c:42-151).
  * rnd = 2*ntheta*nphi numbers in consumption order (z0 then z1, i fastest). */
 void lo_ao_rays(const double P[3], const double Ns[3], uint32_t ntheta, uint32_t nphi,

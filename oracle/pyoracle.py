@@ -115,6 +115,7 @@ def lib():
                                    C.POINTER(C.c_float), _dp, _dp, _u32p, _dp, _dp, _dp, C.c_size_t]
         L.lo_scene_set_attribute.argtypes = [C.c_void_p, C.c_uint32, C.c_int, _dp]
         L.lo_state_batch.argtypes = [C.c_void_p, C.c_size_t, _dp, _dp, _u32p, _dp]
+        L.lo_state_records.argtypes = [C.c_void_p, C.c_size_t, _dp, _dp, _u32p, _dp, _dp, _dp, _dp]
         L.lo_render_pt.restype = C.c_uint64
         L.lo_render_pt.argtypes = [C.c_void_p, C.POINTER(Camera)] + [C.c_int] * 8 + [_u32p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_uint64,
@@ -179,6 +180,18 @@ class Oracle:
         prim = np.empty(org.shape[0], np.uint32); st = np.zeros((org.shape[0], 24))
         self.L.lo_state_batch(self.h, org.shape[0], _p(org, _dp), _p(dr, _dp), _p(prim, _u32p), _p(st, _dp))
         return prim, st
+
+    def state_records(self, org, dr, prim, t, u, v):
+        """the whole record of caller-made hit records, no ray traced (lo_state_records): [n, 24], zeros for a MISS slot.  Every other
+        prim must be a primitive of the scene"""
+        org = _c(org, np.float64).reshape(-1, 3); dr = _c(dr, np.float64).reshape(-1, 3)
+        prim = _c(prim, np.uint32).reshape(-1); t, u, v = (_c(x, np.float64).reshape(-1) for x in (t, u, v))
+        n = org.shape[0]
+        assert dr.shape[0] == n and all(x.shape[0] == n for x in (prim, t, u, v))
+        assert (prim[prim != MISS] < self.ntriangles).all()
+        st = np.zeros((n, 24))
+        self.L.lo_state_records(self.h, n, _p(org, _dp), _p(dr, _dp), _p(prim, _u32p), _p(t, _dp), _p(u, _dp), _p(v, _dp), _p(st, _dp))
+        return st
 
     def build(self):
         self.L.lo_scene_build(self.h)

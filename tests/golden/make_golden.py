@@ -95,6 +95,21 @@ def state_fixture(name="state_attr"):
     print(name, "hits", int((prim != po.MISS).sum()), "of", org.shape[0], "inside", int(st[:, 23].sum()))
 
 
+def state_edges_fixture(name="state_edges", seed=7):
+    """the compiled reference's records of tests/state_edges.py's edge scene (tiny unnormalised triangles, normals on the ortho basis's
+    thresholds, attribute combinations, odd two-sided meshes): the seed, prim + 24 doubles per ray.  Recorded results only"""
+    from tests import state_edges as se
+    meshes, org, dr = se.edge_scene(seed)
+    ref = po.RefLib(); apply_state_scene(ref, meshes, True); ref.build()
+    prim, st = ref.state_batch(org, dr)
+    o = po.Oracle(); apply_state_scene(o, meshes, False); o.build()
+    op, ost = o.state_batch(org, dr)
+    assert np.array_equal(op, prim) and ost.tobytes() == st.tobytes(), "oracle restatement != compiled reference"
+    per_family = se.assert_coverage(meshes, prim, st)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), seed=seed, prim=prim, state=st)
+    print(name, "hits", int((prim != po.MISS).sum()), "of", org.shape[0], "per family", dict(zip(se.FAMILIES, per_family.tolist())))
+
+
 def ao_fixture(name, rib, width, height, gather_nsamples, pixel_samples=1):
     """The reference's own AO render of one of its example scenes (single thread, Ri C API
     driven by oracle/ref_rib.py): the triangles it actually traced (after its RIB ingest),
@@ -219,6 +234,8 @@ if __name__ == "__main__":
         rib_fixture(); hdr_fixture(); sys.exit(0)
     if "--state" in sys.argv:
         state_fixture(); sys.exit(0)
+    if "--state-edges" in sys.argv:
+        state_edges_fixture(); sys.exit(0)
     if "--beam-raster" in sys.argv:
         beam_raster_fixture(); sys.exit(0)
     if not po.ref_available(stat=True):
@@ -235,6 +252,7 @@ if __name__ == "__main__":
     rib_fixture()
     hdr_fixture()
     state_fixture()
+    state_edges_fixture()
     beam_raster_fixture()
     # check values of the full S-soup-1M are pinned in
     # tests/test_oracle_vs_ref.py against the live reference, not stored here.
