@@ -152,6 +152,20 @@ uint64_t lo_render_pt(const lo_scene_t *scene, const lo_camera_t *cam, int x0, i
                       const float env_rgb[3], const float *env_map, int env_w, int env_h, int ref_weights, uint64_t seed,
                       float *rgb, uint16_t *path_rays, uint64_t *max_rays_on_a_path);
 
+/* lo_render_pt with two more outputs (either may be NULL): path_rad = float [pixel][sample][3], every path's radiance as the device
+ * adds it to its pixel (pixel = ly * w + lx, bottom frame line first); counters = LO_PT_NCOUNTERS words, added to.
+ * Counted at every path vertex that scatters (a hit the path survives -- where the vertex arithmetic runs): the lobe taken (MIRROR
+ * is the drawn one; a refraction that turns into a reflection counts as TIR alone), the hit facing away (Ns . D > 0), the hit of a
+ * path that is inside glass, ri_ortho_basis's axis (diffuse vertices only), a flat hit whose |e1 x e2|^2 <= 1e-17f leaves Ng
+ * unnormalised, a hit on a mesh with normals / with colours.  Counted once per path: how it ended. */
+enum { LO_PT_LOBE_DIFFUSE, LO_PT_LOBE_MIRROR, LO_PT_LOBE_REFRACTED, LO_PT_TIR, LO_PT_HIT_BACK, LO_PT_HIT_INTERIOR, LO_PT_AXIS0, LO_PT_AXIS1,
+       LO_PT_AXIS2, LO_PT_FLAT_UNNORMALISED, LO_PT_HIT_NORMALS, LO_PT_HIT_COLOURS, LO_PT_END_MISS_FIRST, LO_PT_END_MISS_LATER,
+       LO_PT_END_ROULETTE, LO_PT_END_LIMIT, LO_PT_NCOUNTERS };
+uint64_t lo_render_pt_detail(const lo_scene_t *scene, const lo_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total,
+                             int max_vertices, const uint32_t *prim_mesh, const float *materials10, const float *override10,
+                             const float env_rgb[3], const float *env_map, int env_w, int env_h, int ref_weights, uint64_t seed,
+                             float *rgb, uint16_t *path_rays, uint64_t *max_rays_on_a_path, float *path_rad, uint64_t *counters);
+
 /* src/transport/pathtrace.c AS WRITTEN (lucille_oracle_ptref.c: restated from the reference's text alone, its own MT19937 in
  * the text's call order, the connect step, BRDF values without cosine / pdf, no roulette compensation): the tile (x0, y0, w, h)
  * of the frame, nsamples paths per pixel, rgb[h][w][3] floats top row first.  Transport parity-UNPINNED (the file is dead code);

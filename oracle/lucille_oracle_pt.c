@@ -27,6 +27,9 @@
  *       in the direction it left (light_sample's extra visibility ray, :354-382, is that ray);
  *   (3) weights: flag 0 = the unbiased estimator of this sampling scheme (divide by P(type) x survival), flag 1 =
  *       the reference's own factors (1/pi on 'D', nothing else).
+ * lo_render_pt_detail is lo_render_pt with two more outputs: every path's radiance as one_path returns it (what the device's pixel sums
+ * are made of: tests/pt_cases.py pixel_from_paths predicts a pixel from them exactly) and LO_PT_NCOUNTERS branch counters (lucille_oracle.h), which
+ * say on the ORACLE alone which branches of the vertex arithmetic an input reaches (tests/test_pt_cases.py).
  * Every operation is a single IEEE operation on both sides (no contraction: oracle/Makefile builds with -ffp-contract=off;
  * the cosine lobe's sin / cos are the product's own polynomial, lobe_f32); only the light probe's acos comes from libm.
  */
@@ -123,10 +126,11 @@ static void env_lookup(const float rgb[3], const float *map, int w, int h, const
  * prim_mesh[prim] = ordinal of the mesh (ri_geom_t) the primitive belongs to; materials[mesh]; override != NULL: one
  * material for every mesh.
  */
+#define CNT(name) do { if (cnt) cnt[LO_PT_##name]++; } while (0)
 static uint32_t one_path(const lo_scene_t *s, const lo_camera_t *cam, int px, int py, int sample, int max_vertices,
                          const uint32_t *prim_mesh, const pt_material_t *materials, const pt_material_t *override,
                          const float env_rgb[3], const float *env_map, int env_w, int env_h, int ref_weights, uint64_t seed,
-                         float radiance[3])
+                         float radiance[3], uint64_t *cnt /* LO_PT_NCOUNTERS branch counters, or NULL */)
 {
     const uint64_t key0 = path_key(seed, px, py, cam->width, sample);
     double org[3], dir[3];
@@ -150,13 +154,15 @@ static uint32_t one_path(const lo_scene_t *s, const lo_camera_t *cam, int px, in
             float e[3];
             env_lookup(env_rgb, env_map, env_w, env_h, dir, e);
             for (k = 0; k < 3; k++) radiance[k] = G[k] * e[k];
+            if (depth == 0) CNT(END_MISS_FIRST); else CNT(END_MISS_LATER);
             break;
         }
         M = override ? override : &materials[prim_mesh[prim]];
         kd_ = ave3(M->kd); ks_ = ave3(M->ks); kt_ = ave3(M->kt);
         /* trace_path's vertex limit (the camera vertex and this one count) and russian_roulette */
         ksum = ((double)M->kd[0] + M->kd[1] + M->kd[2] + M->ks[0] + M->ks[1] + M->ks[2] + M->kt[0] + M->kt[1] + M->kt[2]) / 3.0;
-        if (depth + 2 >= max_vertices || !(ksum > 0.0) || lo_pt_rnd(key) > ksum) break;      /* absorbed: contributes nothing */
+        if (depth + 2 >= max_vertices) { CNT(END_LIMIT); break; }                            /* absorbed: contributes nothing */
+        if (!(ksum > 0.0) || lo_pt_rnd(key) > ksum) { CNT(END_ROULETTE); break; }
         ksum = kd_ + ks_ + kt_;
 
         /* ri_intersection_state_build's P, Ng, Ns, colour (intersection_state.c:99-248) */
@@ -164,7 +170,12 @@ static uint32_t one_path(const lo_scene_t *s, const lo_camera_t *cam, int px, in
         lo_priv_prim_attributes(s, prim, attr);
         wgt = 1.0 - u - v;
         for (k = 0; k < 3; k++) { P[k] = org[k] + dir[k] * t; e01[k] = v1[k] - v0[k]; e02[k] = v2[k] - v0[k]; }
-        cross3(Ng, e01, e02); normalize3(Ng);
+        cross3(Ng, e01, e02);
+        if (!n0 && !(Ng[0] * Ng[0] + Ng[1] * Ng[1] + Ng[2] * Ng[2] > (double)1.0e-17f)) CNT(FLAT_UNNORMALISED);
+        normalize3(Ng);
+        if (n0) CNT(HIT_NORMALS);
+        if (attr[0][0]) CNT(HIT_COLOURS);
+        if (interior) CNT(HIT_INTERIOR);
         if (n0) {
             for (k = 0; k < 3; k++) { const double a = n0[k] * wgt, b = n1[k] * u, c = n2[k] * v; Ns[k] = (a + b) + c; }
             normalize3(Ns);
@@ -173,6 +184,7 @@ static uint32_t one_path(const lo_scene_t *s, const lo_camera_t *cam, int px, in
             for (k = 0; k < 3; k++) { const double a = attr[0][0][k] * wgt, b = attr[0][1][k] * u, c = attr[0][2][k] * v; col[k] = (float)((a + b) + c); }
         back = Ns[0] * dir[0] + Ns[1] * dir[1] + Ns[2] * dir[2] > 0.0;         /* the normal facing the incoming ray */
         for (k = 0; k < 3; k++) N[k] = back ? -Ns[k] : Ns[k];
+        if (back) CNT(HIT_BACK);
 
         rt = lo_pt_rnd(key + 3) * ksum;                                         /* sample_reflection_type */
         type = rt < kd_ ? 'D' : (rt < kd_ + ks_ ? 'S' : 'T');
@@ -182,20 +194,25 @@ static uint32_t one_path(const lo_scene_t *s, const lo_camera_t *cam, int px, in
             e = interior ? (double)M->ior : 1.0 / (double)M->ior;
             cos1 = -(in[0] * N[0] + in[1] * N[1] + in[2] * N[2]);
             coeff = 1.0 - (e * e) * (1.0 - cos1 * cos1);
-            if (coeff <= 0.0) type = 'S';                                       /* total internal reflection */
+            if (coeff <= 0.0) { type = 'S'; CNT(TIR); }                         /* total internal reflection */
             else {
                 const double c2 = e * cos1 - sqrt(coeff);
                 for (k = 0; k < 3; k++) O[k] = c2 * N[k] + e * in[k];
                 normalize3(O);
                 side = -1.0; interior = !interior;
+                CNT(LOBE_REFRACTED);
             }
-        }
+        } else if (type == 'S') CNT(LOBE_MIRROR);
         if (type == 'S') {                                                      /* ri_reflect: r = in - 2 n (in . n) */
             const double dn = dir[0] * N[0] + dir[1] * N[1] + dir[2] * N[2];
             for (k = 0; k < 3; k++) O[k] = dir[k] - 2.0 * dn * N[k];
         } else if (type == 'D') {                                               /* sample_cosweight about ri_ortho_basis(N) */
             double basis[3][3]; float d0, d1, d2;
+            int ax;
             lo_ortho_basis(basis, N);
+            for (ax = 0; ax < 3; ax++) if (N[ax] < 0.6 && N[ax] > -0.6) break;   /* ri_ortho_basis's choice, restated for the counter alone */
+            CNT(LOBE_DIFFUSE);
+            if (cnt) cnt[LO_PT_AXIS0 + (ax >= 3 ? 0 : ax)]++;
             lobe_f32((float)lo_pt_rnd(key + 1), (float)lo_pt_rnd(key + 2), &d0, &d1, &d2);     /* v.f[] = (float)(...), pathtrace.c:519-521 */
             for (k = 0; k < 3; k++) O[k] = (double)d0 * basis[0][k] + (double)d1 * basis[1][k] + (double)d2 * N[k];
         }
@@ -211,15 +228,19 @@ static uint32_t one_path(const lo_scene_t *s, const lo_camera_t *cam, int px, in
     return nrays;
 }
 
+#undef CNT
+
 /*
  * spp samples (s0 .. s0 + spp - 1 of spp_total) of every pixel of the tile (x0, y0, w, h): rgb[h][w][3] (float, top row
  * first, as lh_render_pt_tile writes it) += the mean, accumulated per pixel in sample order in fp32.  path_rays (may be
  * NULL): rays of each path, [pixel][sample].  Returns the number of rays traced; *max_rays_on_a_path = the longest path.
+ * path_rad (may be NULL): float [pixel][sample][3], the radiance one_path returned; counters (may be NULL): LO_PT_NCOUNTERS
+ * words, ADDED to.  Pixels in tile order, bottom frame line first (pixel = ly * w + lx).
  */
-uint64_t lo_render_pt(const lo_scene_t *s, const lo_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total,
-                      int max_vertices, const uint32_t *prim_mesh, const float *materials10, const float *override10,
-                      const float env_rgb[3], const float *env_map, int env_w, int env_h, int ref_weights, uint64_t seed,
-                      float *rgb, uint16_t *path_rays, uint64_t *max_rays_on_a_path)
+uint64_t lo_render_pt_detail(const lo_scene_t *s, const lo_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total,
+                             int max_vertices, const uint32_t *prim_mesh, const float *materials10, const float *override10,
+                             const float env_rgb[3], const float *env_map, int env_w, int env_h, int ref_weights, uint64_t seed,
+                             float *rgb, uint16_t *path_rays, uint64_t *max_rays_on_a_path, float *path_rad, uint64_t *counters)
 {
     uint64_t rays = 0, longest = 0;
     const float inv = 1.0f / (float)spp_total;
@@ -229,14 +250,25 @@ uint64_t lo_render_pt(const lo_scene_t *s, const lo_camera_t *cam, int x0, int y
             float sr = 0.0f, sg = 0.0f, sb = 0.0f, *o = rgb + 3 * ((size_t)(h - 1 - ly) * w + lx);
             for (sm = 0; sm < spp; sm++) {
                 float rad[3];
+                const size_t slot = ((size_t)ly * w + lx) * spp + sm;
                 const uint32_t n = one_path(s, cam, x0 + lx, y0 + ly, s0 + sm, max_vertices, prim_mesh, (const pt_material_t *)materials10,
-                                            (const pt_material_t *)override10, env_rgb, env_map, env_w, env_h, ref_weights, seed, rad);
+                                            (const pt_material_t *)override10, env_rgb, env_map, env_w, env_h, ref_weights, seed, rad, counters);
                 sr += rad[0]; sg += rad[1]; sb += rad[2];
                 rays += n; if (n > longest) longest = n;
-                if (path_rays) path_rays[((size_t)ly * w + lx) * spp + sm] = (uint16_t)(n > 65535 ? 65535 : n);
+                if (path_rays) path_rays[slot] = (uint16_t)(n > 65535 ? 65535 : n);
+                if (path_rad) { path_rad[3 * slot] = rad[0]; path_rad[3 * slot + 1] = rad[1]; path_rad[3 * slot + 2] = rad[2]; }
             }
             o[0] += sr * inv; o[1] += sg * inv; o[2] += sb * inv;
         }
     if (max_rays_on_a_path) *max_rays_on_a_path = longest;
     return rays;
+}
+
+uint64_t lo_render_pt(const lo_scene_t *s, const lo_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total,
+                      int max_vertices, const uint32_t *prim_mesh, const float *materials10, const float *override10,
+                      const float env_rgb[3], const float *env_map, int env_w, int env_h, int ref_weights, uint64_t seed,
+                      float *rgb, uint16_t *path_rays, uint64_t *max_rays_on_a_path)
+{
+    return lo_render_pt_detail(s, cam, x0, y0, w, h, s0, spp, spp_total, max_vertices, prim_mesh, materials10, override10, env_rgb, env_map,
+                               env_w, env_h, ref_weights, seed, rgb, path_rays, max_rays_on_a_path, NULL, NULL);
 }

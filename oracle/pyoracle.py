@@ -120,6 +120,8 @@ def lib():
         L.lo_render_pt.argtypes = [C.c_void_p, C.POINTER(Camera)] + [C.c_int] * 8 + [_u32p, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                    C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_uint64,
                                    C.POINTER(C.c_float), C.POINTER(C.c_uint16), _u64p]
+        L.lo_render_pt_detail.restype = C.c_uint64
+        L.lo_render_pt_detail.argtypes = L.lo_render_pt.argtypes + [C.POINTER(C.c_float), _u64p]
         L.lo_soup_triangles.argtypes = [_u64p, C.c_uint32, C.c_double, _dp, _u32p]
         L.lo_soup_rays.argtypes = [_u64p, C.c_size_t, _dp, _dp]
         _lib = L
@@ -127,6 +129,9 @@ def lib():
 
 
 SOUP_SEED = 88172645463325252
+# lo_render_pt_detail's counters, in the order of the LO_PT_* enum (lucille_oracle.h)
+PT_COUNTERS = ("diffuse", "mirror", "refracted", "tir", "back", "interior", "axis0", "axis1", "axis2", "flat_unnormalised", "normals",
+               "colours", "miss_first", "miss_later", "roulette", "limit")
 
 
 def soup(ntri, nrays, half_extent=0.005, seed=SOUP_SEED):
@@ -214,10 +219,12 @@ class Oracle:
         return img, {"org": ro[:n], "dir": rd[:n], "prim": rp[:n], "t": rt[:n], "u": ru[:n], "v": rv[:n]}
 
     def render_pt(self, cam, x0, y0, w, h, s0, spp, spp_total, max_vertices=8, materials=None, override=None,
-                  env_rgb=(1.0, 1.0, 1.0), env_map=None, ref_weights=0, seed=1, out=None):
+                  env_rgb=(1.0, 1.0, 1.0), env_map=None, ref_weights=0, seed=1, out=None, detail=False):
         """lo_render_pt (lucille_oracle_pt.c): the path-traced tile, one path at a time.  materials: [nmesh, 10] float32
         (kd, ks, kt, ior) or override: 10 floats for every mesh.  -> (rgb [h, w, 3] float32 (accumulated into `out`),
-        {"rays", "max_depth_reached", "paths"}, rays per path [h * w, spp] uint16)"""
+        {"rays", "max_depth_reached", "paths"}, rays per path [h * w, spp] uint16).  detail=True (lo_render_pt_detail): two more,
+        every path's radiance [h * w, spp, 3] float32 (pixel = ly * w + lx, bottom frame line first) and the branch counters
+        {name of PT_COUNTERS: count}"""
         fp = C.POINTER(C.c_float)
         rgb = np.zeros((h, w, 3), np.float32) if out is None else out
         _, g, _ = self.triangles()
@@ -230,12 +237,18 @@ class Oracle:
         env = _c(env_rgb, np.float32).reshape(3)
         em = None if env_map is None else _c(env_map, np.float32)
         per = np.zeros((h * w, spp), np.uint16); longest = C.c_uint64(0)
-        rays = self.L.lo_render_pt(self.h, C.byref(cam), x0, y0, w, h, s0, spp, spp_total, max_vertices, _p(g, _u32p),
-                                   None if mats is None else mats.ctypes.data_as(fp), None if ov is None else ov.ctypes.data_as(fp),
-                                   env.ctypes.data_as(fp), None if em is None else em.ctypes.data_as(fp),
-                                   0 if em is None else em.shape[1], 0 if em is None else em.shape[0], int(ref_weights), int(seed),
-                                   rgb.ctypes.data_as(fp), per.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(longest))
-        return rgb, {"paths": w * h * spp, "rays": int(rays), "max_depth_reached": int(longest.value)}, per
+        args = (self.h, C.byref(cam), x0, y0, w, h, s0, spp, spp_total, max_vertices, _p(g, _u32p),
+                None if mats is None else mats.ctypes.data_as(fp), None if ov is None else ov.ctypes.data_as(fp),
+                env.ctypes.data_as(fp), None if em is None else em.ctypes.data_as(fp),
+                0 if em is None else em.shape[1], 0 if em is None else em.shape[0], int(ref_weights), int(seed),
+                rgb.ctypes.data_as(fp), per.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(longest))
+        if not detail:
+            rays = self.L.lo_render_pt(*args)
+            return rgb, {"paths": w * h * spp, "rays": int(rays), "max_depth_reached": int(longest.value)}, per
+        rad = np.zeros((h * w, spp, 3), np.float32); cnt = np.zeros(len(PT_COUNTERS), np.uint64)
+        rays = self.L.lo_render_pt_detail(*args, rad.ctypes.data_as(fp), _p(cnt, _u64p))
+        return (rgb, {"paths": w * h * spp, "rays": int(rays), "max_depth_reached": int(longest.value)}, per, rad,
+                dict(zip(PT_COUNTERS, map(int, cnt))))
 
     def render_ptref(self, cam, x0, y0, w, h, nsamples, max_vertices=0, materials=None, override=None, env_rgb=(1.0, 1.0, 1.0),
                      env_map=None, mt_seed=4357):

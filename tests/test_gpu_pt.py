@@ -9,6 +9,7 @@ import lucille_amd as la
 from oracle import pyoracle as po
 from tests.helpers import load_golden
 from tests.test_gpu_ao import load_case
+from tests.test_gpu_pt_oracle import mat10
 
 pytestmark = pytest.mark.gpu
 
@@ -159,12 +160,22 @@ def test_mirror_and_glass_conserve_energy_and_roulette_is_unbiased(ps):
     acc.set_material(la.ALL_MESHES, la.Material.make(kd=(0, 0, 0), ks=(1, 1, 1)))
     img, _ = render2(acc, cam, 8, max_vertices=200)
     assert img.max() <= 1.0 + 1e-6 and img.mean() > 0.97
-    # glass sphere over a diffuse plane: mesh materials differ; energy stays below the white furnace
     g = ps["g"]
     nm = int(g["ngeoms"])
+    assert nm == 2 and g["idx0"].shape[0] == 3 * 1984 and g["idx1"].shape[0] == 6           # mesh 0 the sphere, mesh 1 the plane
+    glass_mat, diffuse_mat = la.Material.make(kd=(0.2, 0.2, 0.2), ks=(0.1, 0.1, 0.1), kt=(0.7, 0.7, 0.7), ior=1.5), la.Material.make(kd=(0.7, 0.6, 0.5))
+    # a glass SPHERE over a diffuse plane: paths travel inside the glass and are reflected back in (the oracle's counters say so, on the
+    # same input); energy stays below the white furnace, the frame is deterministic
+    acc.set_material(0, glass_mat); acc.set_material(1, diffuse_mat)
+    _, _, _, _, cnt = ps["oracle"].render_pt(ps["ocam"], 0, 0, cam.width, cam.height, 0, 4, 4, materials=[mat10(glass_mat), mat10(diffuse_mat)],
+                                             seed=1, detail=True)
+    assert cnt["tir"] > 0 and cnt["interior"] > 0, cnt
+    s1, ss1 = render2(acc, cam, 64, seed=1); s2, _ = render2(acc, cam, 64, seed=2); s1b, _ = render2(acc, cam, 64, seed=1)
+    assert s1.max() <= 1.25 and 0.2 < s1.mean() < 1.0 and ss1["rays"] > 1.3 * ss1["paths"]
+    assert abs(s1.mean() - s2.mean()) < 0.01 and not np.array_equal(s1, s2) and np.array_equal(s1, s1b)
+    # a glass PLANE under a diffuse sphere (this test's input from the start, once described as the glass sphere): mesh materials differ
     for k in range(nm):
-        acc.set_material(k, la.Material.make(kd=(0.2, 0.2, 0.2), ks=(0.1, 0.1, 0.1), kt=(0.7, 0.7, 0.7), ior=1.5) if k == nm - 1
-                         else la.Material.make(kd=(0.7, 0.6, 0.5)))
+        acc.set_material(k, glass_mat if k == nm - 1 else diffuse_mat)
     a, sa = render2(acc, cam, 64, seed=1); b, sb = render2(acc, cam, 64, seed=2)
     # (roulette runs on the channel AVERAGE: a coloured reflectance weighs single channels by kd_c / mean(kd), so a
     # 64-sample pixel mean may sit a little above 1; the frame may not)
