@@ -953,6 +953,56 @@ int  lh_render_pt_bands(lh_accel_t *accel, const lh_camera_t *cam, int y0_first,
                         int spp_begin, int spp_count, int spp_total, int max_path_vertices, int flags,
                         const lh_material_t *override_material, uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream);
 
+/* ---- the path tracer with direct light from a light list, and a path-vertex sink (the rule: lucille_amd/csrc/lh_ptl.h) ----
+ * lh_render_pt_tile_lit / lh_render_pt_bands_lit: lh_render_pt_tile2 / lh_render_pt_bands, word for word, plus
+ *   lights   `lights` / nlights / params as lh_accel_lights_device takes them (HOST memory, copied; nlights == 0: none, `lights` may be NULL
+ *     then; else refused as that call refuses them -- "bad lights" -- with nothing enqueued).  Bounce d (0-based) of a pass traces the ray that
+ *     arrives at path vertex d + 2.  Every hit of a bounce -- its path may go on, be ended by the roulette or end at the vertex limit -- adds
+ *       r_k = ((G_k * kd_k) * col_k) * value_k          float32, three IEEE multiplies in this order
+ *     to its path's pixel: G the throughput the arriving ray carries (1, 1, 1 for camera rays), kd the diffuse reflectance of the hit's
+ *     material, col the interpolated vertex colour (1 where the mesh has none), value the three floats lh_accel_lights_device gives for this
+ *     hit record, list and eps (origin P + eps Ns, one bounded any-hit shadow ray per light, no self-primitive skip).  r goes into the
+ *     pixel's fixed-point sums as a path's radiance does: a channel that is NaN or 0 adds nothing, a term is clamped to +-2^18, and the frame
+ *     stays the same bit for bit under tiling, banding and slot order.  No 1 / pi is applied (fold it into the lights' colours); no specular
+ *     or transmissive lobe is lit.  The environment is collected as before: the list's lights are delta lights no sampled direction finds.
+ *     The stage runs once per bounce over the bounce's entries, fused or materialised as for any caller (entries x nlights >= 2^31:
+ *     materialised), synchronous; with lh_accel_trace_statistics on, its items are counted as lh_accel_lights_device counts them, on top of
+ *     the closest-hit rays.  lh_pt_stats_t is unchanged.
+ *     Limits and cost of a pass with lights: every entry of every bounce may add a term to its pixel's sums, so spp_count x
+ *     (max_path_vertices - 1) <= 4096 or the call is refused (without lights: spp_count <= 4096, as before).  The stage compacts a
+ *     bounce into the scratch of lh_accel_lights_device, sized for the worst case of every path hitting: about 120 + nlights bytes per
+ *     path of the pass (a 96-byte hit record, key, slot, 12 bytes of value, a byte per shadow ray; 56 more per shadow ray when the stage
+ *     runs materialised) on top of the pass's own ~164, allocated at the first lit call and kept by the accelerator until it is destroyed
+ *     -- 2 GB at 2^24 paths and one light.
+ *   sink     NULL, or device arrays that receive every entry of every bounce, misses included: bounce d's block starts at record
+ *     counts[0] + .. + counts[d - 1] and holds the bounce's entries in its slot order (from bounce 1 on that order depends on scheduling;
+ *     the set of records does not).  Each array may be NULL (skipped).  A record at a position >= capacity is not written and nothing
+ *     beyond capacity is touched; d_counts always holds the true counts (max_path_vertices words: the entries of every bounce, then
+ *     zeros); the call returns 0 and the caller compares their sum with its capacity.  Refused (-1, nothing enqueued): a d_org / d_dir /
+ *     d_t / d_u / d_v pointer that is not 8-byte aligned, any other pointer that is not 4-byte aligned.
+ *   With nlights == 0 and no sink the calls enqueue exactly what lh_render_pt_tile2 / lh_render_pt_bands enqueue.
+ * Not built: area lights and the sky's sun at path vertices, the texture multiply, the multi-device and distributed frames, LightSource in
+ *   the RIB reader, lsh_hip options. */
+typedef struct lh_pt_sink {            /* device arrays, each may be NULL (skipped); capacity in records */
+    void *d_path;    /* uint32: pixel_of_pass * spp + sample, interior bit cleared */
+    void *d_depth;   /* uint32: bounce d */
+    void *d_org, *d_dir;               /* 3 doubles each */
+    void *d_prim, *d_t, *d_u, *d_v;    /* the bounce's hit record, LH_MISS_PRIM for a miss */
+    void *d_thr;     /* 3 floats: G of the arriving ray */
+    void *d_direct;  /* 3 floats: r of the rule; 0 for a miss or without lights */
+    void *d_counts;  /* uint32 [max_vertices]: entries per bounce, then zeros */
+    size_t capacity;
+} lh_pt_sink_t;
+int  lh_render_pt_tile_lit(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h,
+                           int spp_begin, int spp_count, int spp_total, int max_path_vertices, int flags,
+                           const lh_light_t *lights, int nlights, const lh_lights_params_t *params, const lh_pt_sink_t *sink,
+                           uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream);
+int  lh_render_pt_bands_lit(lh_accel_t *accel, const lh_camera_t *cam, int y0_first, int band_rows, int band_stride, int nbands,
+                            int spp_begin, int spp_count, int spp_total, int max_path_vertices, int flags,
+                            const lh_material_t *override_material, const lh_light_t *lights, int nlights,
+                            const lh_lights_params_t *params, const lh_pt_sink_t *sink, uint64_t seed, void *d_rgb,
+                            lh_pt_stats_t *stats, void *stream);
+
 /* ---- the whole hit epilogue: ri_intersection_state_build (src/render/intersection_state.c:99-248) ----
  * Optional per-vertex attributes of mesh `mesh`, before commit (geom.h:34-48): colours, tangents, binormals
  * (xyz, `count` = vertices), texture coordinates (s, t per vertex) or texcoords_unshared (s, t per INDEX: `count` =

@@ -194,6 +194,56 @@ def _light_array(what, lights):
     return ((Light * len(lights))(*lights) if lights else None), len(lights)
 
 
+class PtSinkStruct(C.Structure):
+    """lh_pt_sink_t (96 bytes): ten record arrays and the counts on the device, each may be NULL, and the capacity in records"""
+    _fields_ = [(k, C.c_void_p) for k in ("d_path", "d_depth", "d_org", "d_dir", "d_prim", "d_t", "d_u", "d_v", "d_thr", "d_direct", "d_counts")] + \
+               [("capacity", C.c_size_t)]
+
+
+class PtSink:
+    """the path-vertex sink of render_pt_tile_lit / render_pt_bands_lit: torch tensors for `capacity` records and the counts of `max_vertices`
+    bounces on `device` -- path, depth, prim: int32 (uint32 bits); org, dir: float64 [capacity, 3]; t, u, v: float64; thr, direct: float32
+    [capacity, 3]; counts: int32 [max_vertices].  fields: the record arrays to allocate (default: all); an absent one is None and is skipped.
+    After a call, total() is the number of records the pass had, written or not (the caller compares it with the capacity) and records()
+    the written ones as numpy arrays."""
+    FIELDS = ("path", "depth", "org", "dir", "prim", "t", "u", "v", "thr", "direct")
+
+    def __init__(self, capacity, max_vertices, device=0, fields=None):
+        import torch
+        dev = torch.device("cuda", device)
+        self.capacity, self.max_vertices = int(capacity), int(max_vertices)
+        want = self.FIELDS if fields is None else tuple(fields)
+        n = self.capacity
+        shapes = {"path": ((n,), torch.int32), "depth": ((n,), torch.int32), "prim": ((n,), torch.int32), "org": ((n, 3), torch.float64),
+                  "dir": ((n, 3), torch.float64), "t": ((n,), torch.float64), "u": ((n,), torch.float64), "v": ((n,), torch.float64),
+                  "thr": ((n, 3), torch.float32), "direct": ((n, 3), torch.float32)}
+        for k in self.FIELDS:
+            setattr(self, k, torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) if k in want else None)
+        self.counts = torch.zeros((self.max_vertices,), dtype=torch.int32, device=dev)
+
+    def struct(self):
+        s = PtSinkStruct()
+        for k in self.FIELDS + ("counts",):
+            t = getattr(self, k)
+            setattr(s, "d_" + k, None if t is None else t.data_ptr())
+        s.capacity = self.capacity
+        return s
+
+    def total(self):
+        return int(self.counts.cpu().numpy().view(np.uint32).astype(np.int64).sum())
+
+    def records(self):
+        """-> dict of numpy arrays over the min(total, capacity) written records (path, depth, prim as uint32), plus "counts" (uint32)"""
+        n = min(self.total(), self.capacity)
+        out = {"counts": self.counts.cpu().numpy().view(np.uint32)}
+        for k in self.FIELDS:
+            t = getattr(self, k)
+            if t is not None:
+                a = t[:n].cpu().numpy()
+                out[k] = a.view(np.uint32) if a.dtype == np.int32 else a
+        return out
+
+
 AREA_COSINE, AREA_FACING, AREA_INVSQ, AREA_PDF = 1, 2, 4, 8      # LH_AREA_*: the surface cosine; the emitter's cosine, one-sided; 1 / squared distance; ntris x the triangle's area
 AREA_LIGHTS_MAX, AREA_SAMPLES_MAX = 31, 1024                     # LH_AREA_LIGHTS_MAX, LH_AREA_SAMPLES_MAX
 
@@ -256,6 +306,7 @@ ABI_SYMBOLS = [
     "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
     "lh_sky_from_site", "lh_accel_set_sky", "lh_accel_sky_device", "lh_accel_sky_host",
     "lh_accel_lights_device", "lh_accel_lights_host", "lh_accel_light_rays_device", "lh_render_lights_tile",
+    "lh_render_pt_tile_lit", "lh_render_pt_bands_lit",
     "lh_accel_set_emitters", "lh_accel_area_lights_device", "lh_accel_area_lights_host", "lh_accel_area_light_rays_device", "lh_render_area_lights_tile",
     "lh_accel_whitted_rays_device", "lh_accel_whitted_device", "lh_accel_whitted_host", "lh_render_whitted_tile",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
@@ -375,6 +426,12 @@ def lib():
         L.lh_accel_lights_host.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, vp]
         L.lh_accel_light_rays_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, lp, i32, lpp, vp, vp, vp, vp, vp, sz, vp]
         L.lh_render_lights_tile.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, lp, i32, lpp, vp, C.POINTER(TileStats), vp]
+    if hasattr(L, "lh_render_pt_tile_lit"):              # an older library under LH_LIBRARY (A/B runs in tools/) has no lit path tracer
+        lp, lpp, skp = C.POINTER(Light), C.POINTER(LightsParams), C.POINTER(PtSinkStruct)
+        L.lh_render_pt_tile_lit.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, i32, i32, lp, i32, lpp, skp, C.c_uint64, vp,
+                                            C.POINTER(PtStats), vp]
+        L.lh_render_pt_bands_lit.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(Material), lp, i32, lpp, skp,
+                                             C.c_uint64, vp, C.POINTER(PtStats), vp]
     if hasattr(L, "lh_accel_area_lights_device"):        # an older library under LH_LIBRARY (A/B runs in tools/) has no area-light stage
         ap, app, u64 = C.POINTER(AreaLight), C.POINTER(AreaParams), C.c_uint64
         L.lh_accel_set_emitters.argtypes = [vp, vp, sz]
@@ -1152,6 +1209,49 @@ class HipAccel:
                                          int(spp_count), int(spp_total), int(max_vertices), int(flags),
                                          C.byref(override) if override is not None else None, int(seed), _dptr(out), C.byref(st),
                                          C.c_void_p(stream)), "lh_render_pt_bands")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def _lit_args(self, what, lights, params, sink):
+        arr, n = _light_array(what, lights or ())
+        if params is not None and not isinstance(params, LightsParams):
+            raise ValueError("%s: params must be a LightsParams" % what)
+        if sink is not None and not isinstance(sink, (PtSink, PtSinkStruct)):
+            raise ValueError("%s: sink must be a PtSink" % what)
+        sk = sink.struct() if isinstance(sink, PtSink) else sink
+        return arr, n, (C.byref(params) if params is not None else None), (C.byref(sk) if sk is not None else None), sk
+
+    def render_pt_tile_lit(self, cam, x0, y0, w, h, spp_begin, spp_count, spp_total, max_vertices=8, flags=0, lights=(), params=None, sink=None,
+                           seed=1, out=None, stream=None):
+        """lh_render_pt_tile_lit: render_pt_tile2 with direct light from `lights` (a sequence of 0 .. LIGHTS_MAX Light; params: a LightsParams,
+        None: eps 1e-5) at every path vertex -- r = ((G kd) col) value per hit, no 1 / pi -- and a path-vertex sink (a PtSink or None) that
+        receives every entry of every bounce -> (out, stats)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        arr, n, pp, skp, _keep = self._lit_args("lh_render_pt_tile_lit", lights, params, sink)
+        st = PtStats()
+        _check(self.L.lh_render_pt_tile_lit(self.h, C.byref(cam), x0, y0, w, h, spp_begin, spp_count, spp_total, max_vertices, int(flags),
+                                            arr, n, pp, skp, int(seed), _dptr(out), C.byref(st), C.c_void_p(stream)), "lh_render_pt_tile_lit")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def render_pt_bands_lit(self, cam, y0_first, band_rows, band_stride, nbands, spp_begin, spp_count, spp_total, max_vertices=8, flags=0,
+                            override=None, lights=(), params=None, sink=None, seed=1, out=None, stream=None):
+        """lh_render_pt_bands_lit: render_pt_bands with the lights, params and sink of render_pt_tile_lit -> (out, stats)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.zeros((nbands, band_rows, cam.width, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        arr, n, pp, skp, _keep = self._lit_args("lh_render_pt_bands_lit", lights, params, sink)
+        st = PtStats()
+        _check(self.L.lh_render_pt_bands_lit(self.h, C.byref(cam), int(y0_first), int(band_rows), int(band_stride), int(nbands), int(spp_begin),
+                                             int(spp_count), int(spp_total), int(max_vertices), int(flags),
+                                             C.byref(override) if override is not None else None, arr, n, pp, skp, int(seed), _dptr(out),
+                                             C.byref(st), C.c_void_p(stream)), "lh_render_pt_bands_lit")
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def set_material(self, mesh, material):

@@ -196,6 +196,7 @@ struct lh_accel {
                                           writes shows up as a wrong record instead of as whatever the buffer held (the lost any-hit rays of r05 hid behind recycled buffers) */
     int fast_start;                    /* device-built scenes: launch before lucille's own tree is attached (ties by primitive id until then) */
     lh_buf p_org2, p_dir2, p_path, p_path2, p_thr, p_thr2, p_rad, p_counts;   /* path tracer */
+    lh_buf p_value;                    /* ... with lights (lh_ptl.h): 12 bytes per entry of a bounce, the light stage's value, then the hit's direct light */
     unsigned long long *d_total;
     size_t r_nsamples, r_nslots, r_nao;
     struct lh_combiner *comb;          /* lh_accel_intersect1: concurrent single-ray callers coalesced into one launch (lh_query.hip) */
@@ -416,5 +417,14 @@ extern "C" int lh_pt_launch_shade(size_t n_max, const lh_dev_scene_t *sc, const 
                                   const float *d_thr, unsigned long long *d_accum, double *d_org2, double *d_dir2, uint32_t *d_path_of2,
                                   float *d_thr2, int ncus, void *stream);
 extern "C" int lh_pt_launch_resolve(int w, int h, int band_rows, float inv_total_spp, unsigned long long *d_accum, float *d_rgb, void *stream);
+/* the lit pass (lh_ptl.h): the camera rays into memory, a bounce's direct light from the light stage's values, a bounce's entries into the caller's sink */
+extern "C" int lh_pt_launch_camera_rays(size_t n, const void *d_cam, double *d_org, double *d_dir, int ncus, void *stream);
+extern "C" int lh_pt_launch_direct(size_t n_max, const double *d_col9, const uint32_t *d_prim_mesh, const void *d_materials,
+                                   const lh_material_t *override_mat, int depth, int spp, const uint32_t *d_counts, const uint32_t *d_prim,
+                                   const double *d_u, const double *d_v, const uint32_t *d_path_of, const float *d_thr, float *d_value, int keep,
+                                   unsigned long long *d_accum, int ncus, void *stream);
+extern "C" int lh_pt_launch_sink(size_t n_max, int depth, const uint32_t *d_counts, const double *d_org, const double *d_dir, const uint32_t *d_prim,
+                                 const double *d_t, const double *d_u, const double *d_v, const uint32_t *d_path_of, const float *d_thr,
+                                 const float *d_direct, const lh_pt_sink_t *sink, int ncus, void *stream);
 
 #endif

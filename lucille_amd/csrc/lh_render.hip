@@ -36,6 +36,7 @@
 #include "lh_env.h"
 #include "lh_sky.h"
 #include "lh_lights.h"
+#include "lh_ptl.h"
 #include "lh_area.h"
 #include "lh_tex.h"
 
@@ -1048,7 +1049,7 @@ struct PtPass {
 #define LH_PT_ROUNDS 4
 
 /* A path's radiance goes into its pixel's accumulator where the path ends -- three 64-bit FIXED-POINT sums per pixel of the pass
- * (32 fraction bits; a sample clamped to +-2^18: the 2^12 samples of a pixel that lh_tile.hip allows in one pass stay below 2^62) -- instead of into a 12-byte record per path that a resolve pass sums afterwards (rounds 2-4): those records
+ * (32 fraction bits; a term clamped to +-2^18: the 2^12 terms of a pixel that lh_tile.hip allows in one pass -- its samples; in a lit pass, lh_ptl.h, its samples x the bounces, each entry of which may add a term -- stay below 2^62) -- instead of into a 12-byte record per path that a resolve pass sums afterwards (rounds 2-4): those records
  * were written where the paths ended, a few of every 128-byte line per bounce (6.7 + 5.6 + ... GB of partial-line writes and
  * 12.9 GB read back per 2^30-path pass, 12.9 GB of HBM held).  Integer sums do not depend on the order of their terms: a pixel
  * is the same whatever the slot order, tiling or sharding, bit for bit, as before.  Lanes of a wave hold consecutive slots,
@@ -1269,6 +1270,107 @@ __global__ __launch_bounds__(256) void k_pt_resolve(int w, int h, int band_rows,
     const int lx = (int)(pix % w), ly = (int)(pix / w), band = ly / band_rows;
     float *o = rgb + 3 * ((size_t)(band * band_rows + (band_rows - 1 - (ly - band * band_rows))) * w + lx);
     o[0] += sum[0] * inv_total_spp; o[1] += sum[1] * inv_total_spp; o[2] += sum[2] * inv_total_spp;
+}
+
+/* ---- direct light at the path vertices (lh_ptl.h) and the path-vertex sink --------------------------------------------------------------
+ * Between the closest-hit launch of bounce `depth` and its shading pass, for a caller with lights or a sink (lh_tile.hip pt_tile): the light
+ * stage of a caller's batch answers `value` for the bounce's entries, k_pt_direct turns it into the hits' r and adds that to their pixels,
+ * k_pt_sink hands the entries out.  Bounce 0 has no ray in memory (the closest-hit walk makes the camera rays in its refill): the stage and
+ * the sink read them from the arrays k_pt_camera_rays fills. */
+
+/* the pass's camera rays, pt_camera_ray per path id */
+__global__ __launch_bounds__(256) void k_pt_camera_rays(uint32_t n, const PtCamSrc *__restrict__ cam, double *__restrict__ org, double *__restrict__ dir)
+{
+    LH_NC
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        double o[3], d[3];
+        pt_camera_ray(cam, i, o, d);
+        for (int c = 0; c < 3; c++) { org[3 * (size_t)i + c] = o[c]; dir[3 * (size_t)i + c] = d[c]; }
+    }
+}
+
+/* what the two kernels read of a pass */
+struct PtLit { float okd[3]; int use_override, depth; LhDiv spp; };
+
+/* one streaming pass over the first counts[depth] entries: r of every hit by the rule into its pixel's sums; with `keep` r goes back into
+ * `value` (three zeros for a miss) for the sink to hand out.  pt_accumulate is wave-wide: the loop's bounds are the workgroup's, every lane
+ * reaches it in every iteration, an entry beyond the count or a miss with ends = false */
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_pt_direct(const PtLit ps, const double *__restrict__ col9, const uint32_t *__restrict__ prim_mesh,
+                                                   const DevMaterial *__restrict__ materials, const uint32_t *__restrict__ counts,
+                                                   const uint32_t *__restrict__ prim, const double *__restrict__ u, const double *__restrict__ v,
+                                                   const uint32_t *__restrict__ path_of, const float *__restrict__ thr, float *__restrict__ value,
+                                                   int keep, unsigned long long *__restrict__ accum)
+{
+    LH_NC
+    const uint32_t n = counts[ps.depth];
+    const int lane = threadIdx.x & 63;
+    for (uint32_t base = blockIdx.x * 256u; base < n; base += gridDim.x * 256u) {      /* n <= 2^30: no wrap */
+        const uint32_t i = base + threadIdx.x;
+        const bool in = i < n;
+        const uint32_t p = in ? prim[i] : LH_MISS_PRIM;
+        const uint32_t path = (FIRST ? i : (in ? path_of[i] : 0u)) & ~LH_PT_INTERIOR;
+        const bool hit = p != LH_MISS_PRIM;
+        float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f;
+        if (hit) {
+            float G0 = 1.0f, G1 = 1.0f, G2 = 1.0f;
+            if (!FIRST) { G0 = thr[3 * (size_t)i]; G1 = thr[3 * (size_t)i + 1]; G2 = thr[3 * (size_t)i + 2]; }
+            float k0 = ps.okd[0], k1 = ps.okd[1], k2 = ps.okd[2];
+            if (!ps.use_override) { const DevMaterial *mp = materials + prim_mesh[p]; k0 = mp->kd[0]; k1 = mp->kd[1]; k2 = mp->kd[2]; }
+            float c0 = 1.0f, c1 = 1.0f, c2 = 1.0f;
+            if (col9) {
+                const double *cc = col9 + 9 * (size_t)p;
+                if (cc[0] == cc[0]) {
+                    const double uu = u[i], vv = v[i], wgt = 1.0 - uu - vv;
+                    c0 = lh_ptl_colour(cc[0], cc[3], cc[6], wgt, uu, vv);
+                    c1 = lh_ptl_colour(cc[1], cc[4], cc[7], wgt, uu, vv);
+                    c2 = lh_ptl_colour(cc[2], cc[5], cc[8], wgt, uu, vv);
+                }
+            }
+            r0 = lh_ptl_direct(G0, k0, c0, value[3 * (size_t)i]);
+            r1 = lh_ptl_direct(G1, k1, c1, value[3 * (size_t)i + 1]);
+            r2 = lh_ptl_direct(G2, k2, c2, value[3 * (size_t)i + 2]);
+        }
+        if (keep && in) { value[3 * (size_t)i] = r0; value[3 * (size_t)i + 1] = r1; value[3 * (size_t)i + 2] = r2; }
+        pt_accumulate(accum, lh_div(path, ps.spp), hit, r0, r1, r2, lane);
+    }
+}
+
+/* the caller's arrays (lh_pt_sink_t), each may be NULL */
+struct PtSinkOut { uint32_t *path, *depth; double *org, *dir; uint32_t *prim; double *t, *u, *v; float *thr, *direct; unsigned long long capacity; };
+
+/* bounce `depth`'s entries, misses included, behind those of the bounces before it: entry i at record counts[0] + .. + counts[depth - 1] + i,
+ * the slot order of the bounce; a record at or beyond the capacity is not written.  direct (or NULL: no lights): what k_pt_direct kept */
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_pt_sink(int depth, const uint32_t *__restrict__ counts, const double *__restrict__ org, const double *__restrict__ dir,
+                                                 const uint32_t *__restrict__ prim, const double *__restrict__ t, const double *__restrict__ u,
+                                                 const double *__restrict__ v, const uint32_t *__restrict__ path_of, const float *__restrict__ thr,
+                                                 const float *__restrict__ direct, const PtSinkOut o)
+{
+    __shared__ unsigned long long sfirst;
+    if (threadIdx.x < 64) {          /* the block's own sum of the earlier bounces' counts, by its first wave */
+        unsigned long long sum = 0ull;
+        for (int k = (int)threadIdx.x; k < depth; k += 64) sum += counts[k];
+        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        if (threadIdx.x == 0) sfirst = sum;
+    }
+    __syncthreads();
+    const unsigned long long first = sfirst;
+    const uint32_t n = counts[depth];
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const unsigned long long r = first + i;
+        if (r >= o.capacity) continue;
+        if (o.path) o.path[r] = (FIRST ? i : path_of[i]) & ~LH_PT_INTERIOR;
+        if (o.depth) o.depth[r] = (uint32_t)depth;
+        if (o.org) for (int c = 0; c < 3; c++) o.org[3 * r + c] = org[3 * (size_t)i + c];
+        if (o.dir) for (int c = 0; c < 3; c++) o.dir[3 * r + c] = dir[3 * (size_t)i + c];
+        if (o.prim) o.prim[r] = prim[i];
+        if (o.t) o.t[r] = t[i];
+        if (o.u) o.u[r] = u[i];
+        if (o.v) o.v[r] = v[i];
+        if (o.thr) for (int c = 0; c < 3; c++) o.thr[3 * r + c] = FIRST ? 1.0f : thr[3 * (size_t)i + c];
+        if (o.direct) for (int c = 0; c < 3; c++) o.direct[3 * r + c] = (direct && prim[i] != LH_MISS_PRIM) ? direct[3 * (size_t)i + c] : 0.0f;
+    }
 }
 
 } /* namespace */
@@ -1608,6 +1710,60 @@ extern "C" int lh_pt_launch_shade(size_t n_max, const lh_dev_scene_t *sc, const 
         hipLaunchKernelGGL((k_pt_scatter<false>), dim3(ns), dim3(256), 0, s, ps, *sc, d_nrm9, d_col9, d_prim_mesh, (const DevMaterial *)d_materials,
                            (const uint32_t *)d_counts, d_org, d_dir, d_prim, d_t, d_u, d_v, d_path_of, d_thr, d_org2, d_dir2, d_path_of2, d_thr2);
     }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* streaming grids of the lit pass's kernels: a workgroup per 256 entries of the upper bound, at most 16 per compute unit */
+static unsigned pt_lit_grid(size_t n_max, int ncus)
+{
+    const size_t blocks = (n_max + 255) / 256, cus = (size_t)(ncus > 0 ? ncus : 256);
+    return (unsigned)(blocks < cus * 16 ? blocks : cus * 16);
+}
+
+/* the camera rays of the pass (d_cam: what lh_pt_launch_begin wrote) into d_org / d_dir */
+extern "C" int lh_pt_launch_camera_rays(size_t n, const void *d_cam, double *d_org, double *d_dir, int ncus, void *stream)
+{
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_pt_camera_rays, dim3(pt_lit_grid(n, ncus)), dim3(256), 0, (hipStream_t)stream, (uint32_t)n, (const PtCamSrc *)d_cam, d_org, d_dir);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the direct light of bounce `depth` (lh_ptl.h) over counts[depth] entries (at most n_max): d_value holds the light stage's answer per entry and,
+ * with keep, r afterwards */
+extern "C" int lh_pt_launch_direct(size_t n_max, const double *d_col9, const uint32_t *d_prim_mesh, const void *d_materials,
+                                   const lh_material_t *override_mat, int depth, int spp, const uint32_t *d_counts, const uint32_t *d_prim,
+                                   const double *d_u, const double *d_v, const uint32_t *d_path_of, const float *d_thr, float *d_value, int keep,
+                                   unsigned long long *d_accum, int ncus, void *stream)
+{
+    if (n_max == 0) return 0;
+    PtLit ps;
+    memset(&ps, 0, sizeof(ps));
+    if (override_mat) for (int k = 0; k < 3; k++) ps.okd[k] = override_mat->kd[k];
+    ps.use_override = override_mat != NULL; ps.depth = depth; ps.spp = lh_div_make((uint32_t)spp);
+    const dim3 grid(pt_lit_grid(n_max, ncus));
+    if (depth == 0)
+        hipLaunchKernelGGL((k_pt_direct<true>), grid, dim3(256), 0, (hipStream_t)stream, ps, d_col9, d_prim_mesh, (const DevMaterial *)d_materials, d_counts,
+                           d_prim, d_u, d_v, d_path_of, d_thr, d_value, keep, d_accum);
+    else
+        hipLaunchKernelGGL((k_pt_direct<false>), grid, dim3(256), 0, (hipStream_t)stream, ps, d_col9, d_prim_mesh, (const DevMaterial *)d_materials, d_counts,
+                           d_prim, d_u, d_v, d_path_of, d_thr, d_value, keep, d_accum);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* bounce `depth`'s entries into the caller's sink; d_direct: what lh_pt_launch_direct kept, or NULL (no lights) */
+extern "C" int lh_pt_launch_sink(size_t n_max, int depth, const uint32_t *d_counts, const double *d_org, const double *d_dir, const uint32_t *d_prim,
+                                 const double *d_t, const double *d_u, const double *d_v, const uint32_t *d_path_of, const float *d_thr,
+                                 const float *d_direct, const lh_pt_sink_t *sink, int ncus, void *stream)
+{
+    if (n_max == 0) return 0;
+    const PtSinkOut o = {(uint32_t *)sink->d_path, (uint32_t *)sink->d_depth, (double *)sink->d_org, (double *)sink->d_dir, (uint32_t *)sink->d_prim,
+                         (double *)sink->d_t, (double *)sink->d_u, (double *)sink->d_v, (float *)sink->d_thr, (float *)sink->d_direct,
+                         (unsigned long long)sink->capacity};
+    const dim3 grid(pt_lit_grid(n_max, ncus));
+    if (depth == 0)
+        hipLaunchKernelGGL((k_pt_sink<true>), grid, dim3(256), 0, (hipStream_t)stream, depth, d_counts, d_org, d_dir, d_prim, d_t, d_u, d_v, d_path_of, d_thr, d_direct, o);
+    else
+        hipLaunchKernelGGL((k_pt_sink<false>), grid, dim3(256), 0, (hipStream_t)stream, depth, d_counts, d_org, d_dir, d_prim, d_t, d_u, d_v, d_path_of, d_thr, d_direct, o);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -1153,11 +1153,61 @@ int lh_ensure_prim_mesh(lh_accel_t *a)
 /* wavefront path tracer (kernels: lh_render.hip, arithmetic: lh_pt.h)       */
 /* ------------------------------------------------------------------------ */
 
+/* what the _lit entry points add to a pass (lh_ptl.h; both NULL: the pass as it ever was): the checked light list as the light stage takes it, and
+ * the caller's path-vertex sink */
+struct pt_lit { const char *what; const gather_params *lights; const lh_pt_sink_t *sink; };
+static const pt_lit pt_unlit = {NULL, NULL, NULL};
+
+/* the sink's refusals: its double arrays 8-byte aligned, the others 4-byte */
+static int pt_sink_ok(const char *what, const lh_pt_sink_t *k)
+{
+    if ((((uintptr_t)k->d_org | (uintptr_t)k->d_dir | (uintptr_t)k->d_t | (uintptr_t)k->d_u | (uintptr_t)k->d_v) & 7u) != 0)
+        return fail("%s: the sink's org, dir, t, u and v arrays are doubles: a pointer is not 8-byte aligned", what);
+    if ((((uintptr_t)k->d_path | (uintptr_t)k->d_depth | (uintptr_t)k->d_prim | (uintptr_t)k->d_thr | (uintptr_t)k->d_direct | (uintptr_t)k->d_counts) & 3u) != 0)
+        return fail("%s: the sink's path, depth, prim, thr, direct and counts arrays are 32-bit words: a pointer is not 4-byte aligned", what);
+    return 0;
+}
+
+/* what a lit pass does between the closest-hit launch of bounce `depth` and its shading pass: the light stage over the bounce's entries and their
+ * direct light into the pixels (with lights), the entries into the sink (with one).  org / dir / path / thr: the bounce's own sets (NULL at bounce 0);
+ * value: p_value or NULL; cnt: the statistics words or NULL, closest_cnt: where the closest-hit launches' words are kept while the stage counts */
+static int pt_lit_bounce(lh_accel_t *a, const pt_lit &lit, size_t S, int depth, int spp, const lh_material_t *override_mat, const void *d_cam,
+                         const uint32_t *counts, const double *org, const double *dir, const uint32_t *path, const float *thr, float *value,
+                         unsigned long long *cnt, unsigned long long *closest_cnt, hipStream_t s)
+{
+    /* bounce 0 has no ray in memory: the light stage and the sink read the camera rays from the second ray set, free until the swap after bounce 0 */
+    if (depth == 0) {
+        if (lh_pt_launch_camera_rays(S, d_cam, (double *)a->p_org2.p, (double *)a->p_dir2.p, a->ncus, s) != 0) return fail("pt camera ray launch failed");
+        org = (const double *)a->p_org2.p; dir = (const double *)a->p_dir2.p;
+    }
+    if (lit.lights) {
+        /* the light stage of a caller's batch over the bounce's entries, behind the guard this call holds: the identity list with its count on
+         * the device.  It resets and counts the statistics words for itself */
+        if (cnt) {
+            unsigned long long hc[LH_CNT_N];
+            HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (int k = 0; k < LH_CNT_N; k++) closest_cnt[k] += hc[k];
+        }
+        if (ao_batch_device(lit.what, a, *lit.lights, S, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, 1, 0, NULL, NULL, NULL, S, counts + depth,
+                            NULL, value, s) != 0) return -1;
+        if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+        if (lh_pt_launch_direct(S, (const double *)a->d_attr9[0], (const uint32_t *)a->d_prim_mesh, a->d_materials, override_mat, depth, spp, counts,
+                                (const uint32_t *)a->r_prim.p, (const double *)a->r_u.p, (const double *)a->r_v.p, path, thr, value,
+                                lit.sink && lit.sink->d_direct, (unsigned long long *)a->p_rad.p, a->ncus, s) != 0)
+            return fail("pt direct light launch failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (lit.sink && lh_pt_launch_sink(S, depth, counts, org, dir, (const uint32_t *)a->r_prim.p, (const double *)a->r_t.p, (const double *)a->r_u.p,
+                                      (const double *)a->r_v.p, path, thr, value, lit.sink, a->ncus, s) != 0)
+        return fail("pt sink launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
 /* the pass over a w-wide region of h lines = full bands of band_rows lines, band k starting at frame line y0 + k * band_stride
  * (an ordinary tile: band_rows = h) */
 static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int band_rows, int band_stride, int s0, int spp, int spp_total, int max_vertices,
                    const lh_material_t *override_mat, const float env_rgb[3], const void *d_env_map, int env_w, int env_h, int flags,
-                   uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream)
+                   uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream, const pt_lit &lit)
 {
     if (w <= 0 || h <= 0 || spp < 1 || spp_total < spp || max_vertices < 2 || max_vertices > 65536 || band_rows < 1 || h % band_rows != 0)
         return fail("lh_render_pt_tile: bad arguments");
@@ -1167,6 +1217,10 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
     const size_t S = (size_t)w * h * spp;
     if (S > ((size_t)1 << 30)) return fail("lh_render_pt_tile: more than 2^30 paths in one pass; lower spp_count or the tile size");
     if (spp > 4096) return fail("lh_render_pt_tile: more than 4096 samples of a pixel in one pass (the pixels' fixed-point sums); lower spp_count");
+    /* with lights every entry of every bounce may add a term to its pixel (a hit its direct light, a miss the environment): a path up to max_vertices - 1 */
+    if (lit.lights && (size_t)spp * (size_t)(max_vertices - 1) > 4096)
+        return fail("%s: with lights spp_count x (max_path_vertices - 1) = %d x %d exceeds 4096 terms of a pixel in one pass (the pixels' fixed-point sums); "
+                    "lower spp_count", lit.what, spp, max_vertices - 1);
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;      /* lh_accel_trace_statistics */
     if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
     const int nbounce = max_vertices - 1;                  /* bounce d traces the ray to path vertex d + 2; the last vertex scatters nothing */
@@ -1175,6 +1229,10 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
         ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8) || ensure_buf(&a->p_path, S * 4) ||
         ensure_buf(&a->p_path2, S * 4) || ensure_buf(&a->p_thr, S * 12) || ensure_buf(&a->p_thr2, S * 12) ||
         ensure_buf(&a->p_rad, (size_t)w * h * 24) || ensure_buf(&a->p_counts, ((size_t)nbounce + 2) * 4 + 64 + lh_pt_cam_bytes())) return -1;
+    const bool lit_pass = lit.lights || lit.sink;          /* lh_ptl.h; neither: not one launch or buffer more than before */
+    if (lit.lights && ensure_buf(&a->p_value, S * 12)) return -1;
+    float *value = lit.lights ? (float *)a->p_value.p : NULL;
+    unsigned long long closest_cnt[LH_CNT_N] = {0};       /* with lights: the closest-hit launches' words, taken before the light stage resets them */
     /* the chain's ray / path-word / throughput records alternate between two sets; bounce 0 reads none (its rays are the camera
      * rays, generated inside the closest-hit kernel and again by the shading pass for the paths that go on) */
     double *org = NULL, *dir = NULL, *org2 = (double *)a->r_org.p, *dir2 = (double *)a->r_dir.p;
@@ -1193,6 +1251,10 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
         lh_launch_opt opt; opt.n_dev = counts + depth; opt.cam_src = depth == 0 ? d_cam : NULL;
         rc = lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt}, LH_VARIANT_SPEC, s, false, opt);
         if (rc != 0) break;
+        if (lit_pass) {
+            rc = pt_lit_bounce(a, lit, S, depth, spp, override_mat, d_cam, counts, org, dir, path, thr, value, cnt, closest_cnt, s);
+            if (rc != 0) break;
+        }
         if (lh_pt_launch_shade(S, &a->dev, (const double *)a->d_nrm9, (const double *)a->d_attr9[0], (const uint32_t *)a->d_prim_mesh,
                                a->d_materials, override_mat, env_rgb, d_env_map, env_w, env_h, (flags & LH_PT_REFERENCE_WEIGHTS) != 0,
                                depth, max_vertices, seed, s0, spp, x0, y0, w, band_rows, band_stride, cam->width, d_cam, counts, org, dir, (const uint32_t *)a->r_prim.p,
@@ -1216,12 +1278,16 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
     if (rc != 0) return -1;
     if (lh_pt_launch_resolve(w, h, band_rows, 1.0f / (float)spp_total, (unsigned long long *)a->p_rad.p, (float *)d_rgb, s) != 0)
         return fail("pt resolve launch failed");
+    /* the sink's counts: the entries of every bounce, then zeros (a chain that ended early; the last vertex scatters nothing) */
+    if (lit.sink && lit.sink->d_counts)
+        HIPCHK(hipMemcpyAsync(lit.sink->d_counts, counts, sizeof(uint32_t) * (size_t)max_vertices, hipMemcpyDeviceToDevice, s));
     std::vector<uint32_t> hcounts((size_t)nbounce + 1);
     HIPCHK(hipMemcpyAsync(hcounts.data(), counts, hcounts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (cnt) {
         unsigned long long hc[LH_CNT_N];
         HIPCHK(hipMemcpy(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost));
+        for (int k = 0; k < LH_CNT_N; k++) hc[k] += closest_cnt[k];
         lh_stat_add(a, hc, hc[LH_CNT_RAYS], 0);
     }
     if (stats) {
@@ -1242,7 +1308,7 @@ extern "C" int lh_render_pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, 
     if (!cam || !d_rgb || !env) return fail("lh_render_pt_tile: NULL argument");
     if (!(kd > 0.0f) || kd > 1.0f) return fail("lh_render_pt_tile: bad arguments");
     lh_material_t m; memset(&m, 0, sizeof(m)); m.kd[0] = m.kd[1] = m.kd[2] = kd; m.ior = 1.0f;
-    return pt_tile(a, cam, x0, y0, w, h, h, 0, s0, spp, spp_total, max_vertices, &m, env, NULL, 0, 0, 0, seed, d_rgb, stats, stream);
+    return pt_tile(a, cam, x0, y0, w, h, h, 0, s0, spp, spp_total, max_vertices, &m, env, NULL, 0, 0, 0, seed, d_rgb, stats, stream, pt_unlit);
 }
 
 /* per-mesh materials (lh_accel_set_material) and the accelerator's environment (lh_accel_set_environment) */
@@ -1255,7 +1321,38 @@ extern "C" int lh_render_pt_tile2(lh_accel_t *a, const lh_camera_t *cam, int x0,
     float one[3] = {1.0f, 1.0f, 1.0f};
     const float *rgb = a->env_set ? a->env.rgb : one;          /* never set: constant white; an explicit black environment stays black */
     return pt_tile(a, cam, x0, y0, w, h, h, 0, s0, spp, spp_total, max_vertices, NULL, rgb, a->d_env_map, a->env.width, a->env.height, flags,
-                   seed, d_rgb, stats, stream);
+                   seed, d_rgb, stats, stream, pt_unlit);
+}
+
+/* the _lit forms' own refusals, before anything is enqueued: the list as the light stage refuses it (nlights == 0: none), the sink's pointers.
+ * p: the checked list; out: what pt_tile takes */
+static int pt_lit_check(const char *what, const lh_light_t *lights, int nlights, const lh_lights_params_t *params, const lh_pt_sink_t *sink,
+                        gather_params *p, pt_lit *out)
+{
+    *out = pt_lit{what, NULL, sink};
+    if (nlights != 0) {
+        const lights_in in = {lights, nlights, params};
+        if (gather_check(what, LH_GATHER_LIGHT, &in, p) != 0) return -1;
+        out->lights = p;
+    }
+    return sink ? pt_sink_ok(what, sink) : 0;
+}
+
+/* lh_render_pt_tile2 with direct light from a light list at every path vertex and a path-vertex sink (lh_ptl.h) */
+extern "C" int lh_render_pt_tile_lit(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total,
+                                     int max_vertices, int flags, const lh_light_t *lights, int nlights, const lh_lights_params_t *params,
+                                     const lh_pt_sink_t *sink, uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_render_pt_tile_lit";
+    gather_params p; pt_lit lit;
+    if (pt_lit_check(what, lights, nlights, params, sink, &p, &lit) != 0) return -1;
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (!cam || !d_rgb) return fail("%s: NULL argument", what);
+    float one[3] = {1.0f, 1.0f, 1.0f};
+    const float *rgb = a->env_set ? a->env.rgb : one;
+    return pt_tile(a, cam, x0, y0, w, h, h, 0, s0, spp, spp_total, max_vertices, NULL, rgb, a->d_env_map, a->env.width, a->env.height, flags,
+                   seed, d_rgb, stats, stream, lit);
 }
 
 /* a rank's interleaved full-width bands of a sharded frame as ONE pass: nbands bands of band_rows lines, band k starting at
@@ -1274,7 +1371,28 @@ extern "C" int lh_render_pt_bands(lh_accel_t *a, const lh_camera_t *cam, int y0_
     float one[3] = {1.0f, 1.0f, 1.0f};
     const float *rgb = a->env_set ? a->env.rgb : one;          /* never set: constant white; an explicit black environment stays black */
     return pt_tile(a, cam, 0, y0_first, cam->width, nbands * band_rows, band_rows, band_stride, s0, spp, spp_total, max_vertices, override_mat, rgb,
-                   a->d_env_map, a->env.width, a->env.height, flags, seed, d_rgb, stats, stream);
+                   a->d_env_map, a->env.width, a->env.height, flags, seed, d_rgb, stats, stream, pt_unlit);
+}
+
+/* lh_render_pt_bands with the light list and the sink of lh_render_pt_tile_lit */
+extern "C" int lh_render_pt_bands_lit(lh_accel_t *a, const lh_camera_t *cam, int y0_first, int band_rows, int band_stride, int nbands,
+                                      int s0, int spp, int spp_total, int max_vertices, int flags, const lh_material_t *override_mat,
+                                      const lh_light_t *lights, int nlights, const lh_lights_params_t *params, const lh_pt_sink_t *sink,
+                                      uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);
+    const char *what = "lh_render_pt_bands_lit";
+    gather_params p; pt_lit lit;
+    if (pt_lit_check(what, lights, nlights, params, sink, &p, &lit) != 0) return -1;
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (!cam || !d_rgb) return fail("%s: NULL argument", what);
+    if (nbands < 1 || band_rows < 1 || y0_first < 0 || (nbands > 1 && band_stride < band_rows) ||
+        (long long)y0_first + (long long)(nbands - 1) * band_stride + band_rows > cam->height)
+        return fail("%s: bands must be disjoint and inside the frame", what);
+    float one[3] = {1.0f, 1.0f, 1.0f};
+    const float *rgb = a->env_set ? a->env.rgb : one;
+    return pt_tile(a, cam, 0, y0_first, cam->width, nbands * band_rows, band_rows, band_stride, s0, spp, spp_total, max_vertices, override_mat, rgb,
+                   a->d_env_map, a->env.width, a->env.height, flags, seed, d_rgb, stats, stream, lit);
 }
 
 /* ------------------------------------------------------------------------ */
