@@ -33,12 +33,17 @@ __device__ __forceinline__ uint32_t lh_mix32(uint64_t x)
 #define LH_HITREC_DOUBLES 12
 
 /* slot key: low 34 bits = absolute sample position (frame pixel x sub-sample; keys the built-in generator), high 30 bits =
- * the primitive the AO rays of this slot start on WHEN that primitive cannot occlude them -- a flat-shaded hit: Ns = Ng, the
- * origin lies 1e-6 off the triangle's plane on the side every direction of the hemisphere points to (d . Ns = sqrt(1 - z0) >=
- * 2.4e-4), so the reference's own test of that triangle (bvh.c:730-791) ends at t < 0, ten orders of magnitude away from fp64
- * rounding -- or LH_SLOT_NOSELF when it can (interpolated normals may tilt the hemisphere below the plane).  The any-hit
- * kernel skips that one triangle instead of sending it through the fp64 test (1.0 fp64 re-tests per AO ray on BASELINE
- * config 5 without this). */
+ * the primitive the AO rays of this slot start on WHEN that primitive cannot occlude them (a flat-shaded hit), or
+ * LH_SLOT_NOSELF when it can (interpolated normals may tilt the hemisphere below the plane).  The any-hit kernel skips that
+ * one triangle instead of sending it through the fp64 test (1.0 fp64 re-tests per AO ray on BASELINE config 5 without this).
+ *
+ * Why a flat-shaded hit's triangle cannot occlude: Ns = Ng, the origin lies 1e-6 off the triangle's plane, and no direction
+ * of the hemisphere points back at the plane: d . Ns = sqrt(max(1 - z0, 0)) >= 0.  With d . Ns > 0 the reference's own test
+ * of that triangle (bvh.c:730-791) ends at t < 0.  Equality happens: z0 = (i + r0) / ntheta is rounded in fp32, for i >= 1
+ * the sum i + r0 can round up to i + 1, and in the last stratum z0 then is 1.0 and d . Ns == 0 -- about once in 2^24 rays of
+ * that stratum.  Such a ray runs parallel to its triangle at height 1e-6 and fails triangle_isect's determinant test
+ * (fabs(a) > 1e-14) or its u range, so the skip holds for it too:
+ * tests/test_gpu_ao_sampler.py::test_edges_through_the_stages checks that on the oracle. */
 #define LH_SLOTKEY_BITS 34
 #define LH_SLOTKEY_MASK ((1ull << LH_SLOTKEY_BITS) - 1ull)
 #define LH_SLOT_NOSELF  0x3FFFFFFFu

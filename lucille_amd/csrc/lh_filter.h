@@ -57,9 +57,12 @@ typedef struct lh_ray32 {
     int   ngx, ngy, ngz;              /* dir_k < 0                           */
 } lh_ray32_t;
 
+/* the sign is that of the comparison d < 0 -- the one ngx / ngy / ngz take (lh_ray_setup) and the reference takes both its dir_sign and its
+ * +-DBL_MAX from (bvh.c:473-497): a -0.0 counts as +0.0.  With copysign a -0.0 got a negative inverse next to ng = 0, the slab test took its planes
+ * in the wrong order and the ray missed every box whose planes of that axis it starts between (tests/test_gpu_signed_zero.py) */
 LH_HD float lh_safe_dir(float d)
 {
-    return (fabsf(d) < 1e-30f) ? copysignf(1e-30f, d) : d;
+    return (fabsf(d) < 1e-30f) ? ((d < 0.0f) ? -1e-30f : 1e-30f) : d;
 }
 
 typedef struct lh_grid { float lo[3], step[3]; } lh_grid_t;
