@@ -981,8 +981,8 @@ int  lh_render_pt_bands(lh_accel_t *accel, const lh_camera_t *cam, int y0_first,
  *     zeros); the call returns 0 and the caller compares their sum with its capacity.  Refused (-1, nothing enqueued): a d_org / d_dir /
  *     d_t / d_u / d_v pointer that is not 8-byte aligned, any other pointer that is not 4-byte aligned.
  *   With nlights == 0 and no sink the calls enqueue exactly what lh_render_pt_tile2 / lh_render_pt_bands enqueue.
- * Not built: area lights and the sky's sun at path vertices, the texture multiply, the multi-device and distributed frames, LightSource in
- *   the RIB reader, lsh_hip options. */
+ * Area lights at the path vertices are the _lights forms below; the sky's sun is a directional light: a caller puts it into the list.
+ * Not built: the texture multiply, the multi-device and distributed frames, LightSource in the RIB reader, lsh_hip options. */
 typedef struct lh_pt_sink {            /* device arrays, each may be NULL (skipped); capacity in records */
     void *d_path;    /* uint32: pixel_of_pass * spp + sample, interior bit cleared */
     void *d_depth;   /* uint32: bounce d */
@@ -1002,6 +1002,49 @@ int  lh_render_pt_bands_lit(lh_accel_t *accel, const lh_camera_t *cam, int y0_fi
                             const lh_material_t *override_material, const lh_light_t *lights, int nlights,
                             const lh_lights_params_t *params, const lh_pt_sink_t *sink, uint64_t seed, void *d_rgb,
                             lh_pt_stats_t *stats, void *stream);
+
+/* ---- the path tracer with soft shadows: area lights at every path vertex (the rule: lucille_amd/csrc/lh_ptl.h) ----
+ * lh_render_pt_tile_lights / lh_render_pt_bands_lights: the _lit forms, word for word, with the two lists in one lh_pt_lights_t:
+ *   lights / nlights / params          the delta lights, as the _lit forms take them (nlights == 0: none);
+ *   area / narea / area_params         area lights over the accelerator's emitter table (lh_accel_set_emitters), as lh_accel_area_lights_device
+ *     takes them (HOST memory, copied; narea == 0: none, `area` may be NULL then; else refused as that call refuses them -- "bad area lights",
+ *     which includes no emitter table -- with nothing enqueued).  `lights` NULL is no lights at all; with narea == 0 the call is the _lit call:
+ *     the same launches, buffers and bytes.
+ *   The area value of a hit of bounce d is exactly what lh_accel_area_lights_device answers for that hit record, `area`, area_params, the seed
+ *     seed + (uint64)(d + 1) * 0xD1B54A32D192ED03 (modulo 2^64), the entry's key and no replayed uniforms: origin P + eps Ns, area_params.nsamples
+ *     samples per light, the bound, no self-primitive skip, lights and samples in order.  The key of an entry is that of its path, sample s of the
+ *     pass at frame pixel (px, py): ((uint64)py * cam->width + px) * spp_total + (spp_begin + s) -- frame coordinates, so a frame does not
+ *     depend on its tiling, banding or passes over the samples.  The bounce is in the seed because the generator reads 34 bits of a key; the
+ *     path's own draws use `seed` itself.
+ *   A hit still adds ONE term r_k = ((G_k * kd_k) * col_k) * value_k: with one kind of light value is that stage's three floats, with both
+ *     value_k = delta_k + area_k, one float32 add.  The sink's d_direct receives r; lh_pt_sink_t is unchanged.  No 1 / pi is applied, no specular
+ *     or transmissive lobe is lit, and an emitter is seen by no sampled direction: emitters are no scene geometry (a caller who wants them to
+ *     occlude adds them as a mesh and passes a bound a little below 1), so nothing is counted twice.
+ *   Refused (-1, nothing enqueued or written): everything the _lit forms refuse; the area list and parameters; a non-zero reserved word;
+ *     cam->width x cam->height x spp_total > 2^34 with area lights (the keys' 34 bits); spp_count x (max_path_vertices - 1) > 4096 with
+ *     either kind of light (one term per entry of every bounce).
+ *   Per bounce: the delta stage (if any), a kernel that writes the keys, the area stage over the bounce's entries -- fused or materialised as
+ *     for any caller (entries x narea x S >= 2^31: materialised), synchronous -- a kernel that folds the two values where there are both, the
+ *     direct-light kernel, the sink.  With lh_accel_trace_statistics on `rays` advances by the closest-hit rays + hits x nlights + hits x
+ *     narea x S.
+ *   Memory a pass with area lights costs on top of the _lit forms', allocated at the first such call and kept by the accelerator: 8 bytes a
+ *     path of keys, 12 of value, and the scratch of lh_accel_area_lights_device sized for every path hitting -- about 108 bytes a path (a
+ *     96-byte hit record, key, slot) plus one byte per path, light and sample (56 more per shadow ray when the stage runs materialised):
+ *     2.4 GB at 2^24 paths, one light and 16 samples.  The two stages compact a bounce each for itself; sharing that is a later change.
+ * Not built: a texture multiply, the sky as the path tracer's environment, the multi-device and distributed frames, AreaLightSource /
+ *   LightSource in the RIB reader, lsh_hip options, the qmc sampler. */
+typedef struct lh_pt_lights {          /* 48 bytes */
+    const lh_light_t *lights;   int32_t nlights; uint32_t reserved0; const lh_lights_params_t *params;       /* as the _lit forms take them */
+    const lh_area_light_t *area; int32_t narea;  uint32_t reserved1; const lh_area_params_t *area_params;    /* as lh_accel_area_lights_device takes them */
+} lh_pt_lights_t;
+int  lh_render_pt_tile_lights(lh_accel_t *accel, const lh_camera_t *cam, int x0, int y0, int w, int h,
+                              int spp_begin, int spp_count, int spp_total, int max_path_vertices, int flags,
+                              const lh_pt_lights_t *lights, const lh_pt_sink_t *sink, uint64_t seed, void *d_rgb,
+                              lh_pt_stats_t *stats, void *stream);
+int  lh_render_pt_bands_lights(lh_accel_t *accel, const lh_camera_t *cam, int y0_first, int band_rows, int band_stride, int nbands,
+                               int spp_begin, int spp_count, int spp_total, int max_path_vertices, int flags,
+                               const lh_material_t *override_material, const lh_pt_lights_t *lights, const lh_pt_sink_t *sink,
+                               uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream);
 
 /* ---- the whole hit epilogue: ri_intersection_state_build (src/render/intersection_state.c:99-248) ----
  * Optional per-vertex attributes of mesh `mesh`, before commit (geom.h:34-48): colours, tangents, binormals

@@ -23,4 +23,4 @@ from .binding import (Camera, HipAccel, LucilleHipError, RecommitInfo, TreeImage
                       HipMulti, HipDist, DIST_RCCL, DIST_SHM, Material, Environment, ALL_MESHES, PT_REFERENCE_WEIGHTS, ATTR_COLOR, ATTR_TANGENT, ATTR_BINORMAL,
                       ATTR_TEXCOORD, ATTR_TEXCOORD_UNSHARED, STATE_DOUBLES, DirtParams, EnvParams, WhittedParams, WHITTED_CUT, Sky, SKY_SUN,
                       Light, LightsParams, LIGHT_POINT, LIGHT_COSINE, LIGHT_INVSQ, LIGHTS_MAX, PtSink, PtSinkStruct,
-                      AreaLight, AreaParams, AREA_COSINE, AREA_FACING, AREA_INVSQ, AREA_PDF, AREA_LIGHTS_MAX, AREA_SAMPLES_MAX)
+                      AreaLight, AreaParams, AREA_COSINE, AREA_FACING, AREA_INVSQ, AREA_PDF, AREA_LIGHTS_MAX, AREA_SAMPLES_MAX, PtLights)

@@ -275,6 +275,14 @@ def _area_array(what, lights):
     return ((AreaLight * len(lights))(*lights) if lights else None), len(lights)
 
 
+class PtLights(C.Structure):
+    """lh_pt_lights_t (48 bytes): the delta lights of render_pt_tile_lit (lights, nlights, params) and the area lights of area_lights_device (area,
+    narea, area_params) for render_pt_tile_lights / render_pt_bands_lights; the reserved words must stay 0.  Holds pointers only: the arrays
+    they point to must outlive the call (HipAccel._lights_args keeps them)"""
+    _fields_ = [("lights", C.POINTER(Light)), ("nlights", C.c_int32), ("reserved0", C.c_uint32), ("params", C.POINTER(LightsParams)),
+                ("area", C.POINTER(AreaLight)), ("narea", C.c_int32), ("reserved1", C.c_uint32), ("area_params", C.POINTER(AreaParams))]
+
+
 class WhittedParams(C.Structure):
     """lh_whitted_params_t: origin offset, relative refractive index and depth limit of the refraction chain (defaults:
     LH_WHITTED_DEFAULTS, the constants of whitted.c); reserved must stay 0"""
@@ -306,7 +314,7 @@ ABI_SYMBOLS = [
     "lh_accel_env_device", "lh_accel_env_host", "lh_render_env_tile", "lh_accel_environment_device", "lh_accel_environment_host",
     "lh_sky_from_site", "lh_accel_set_sky", "lh_accel_sky_device", "lh_accel_sky_host",
     "lh_accel_lights_device", "lh_accel_lights_host", "lh_accel_light_rays_device", "lh_render_lights_tile",
-    "lh_render_pt_tile_lit", "lh_render_pt_bands_lit",
+    "lh_render_pt_tile_lit", "lh_render_pt_bands_lit", "lh_render_pt_tile_lights", "lh_render_pt_bands_lights",
     "lh_accel_set_emitters", "lh_accel_area_lights_device", "lh_accel_area_lights_host", "lh_accel_area_light_rays_device", "lh_render_area_lights_tile",
     "lh_accel_whitted_rays_device", "lh_accel_whitted_device", "lh_accel_whitted_host", "lh_render_whitted_tile",
     "lh_accel_set_texture", "lh_accel_set_texture_device", "lh_accel_texture_device", "lh_accel_texture_host", "lh_multi_set_texture",
@@ -432,7 +440,13 @@ def lib():
                                             C.POINTER(PtStats), vp]
         L.lh_render_pt_bands_lit.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(Material), lp, i32, lpp, skp,
                                              C.c_uint64, vp, C.POINTER(PtStats), vp]
-    if hasattr(L, "lh_accel_area_lights_device"):        # an older library under LH_LIBRARY (A/B runs in tools/) has no area-light stage
+    if hasattr(L, "lh_render_pt_tile_lights"):           # an older library under LH_LIBRARY (A/B runs in tools/) has no area lights at path vertices
+        plp, skp = C.POINTER(PtLights), C.POINTER(PtSinkStruct)
+        L.lh_render_pt_tile_lights.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, i32, i32, plp, skp, C.c_uint64, vp,
+                                               C.POINTER(PtStats), vp]
+        L.lh_render_pt_bands_lights.argtypes = [vp, C.POINTER(Camera), i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(Material), plp, skp,
+                                                C.c_uint64, vp, C.POINTER(PtStats), vp]
+    if hasattr(L, "lh_accel_area_lights_device"):       # an older library under LH_LIBRARY (A/B runs in tools/) has no area-light stage
         ap, app, u64 = C.POINTER(AreaLight), C.POINTER(AreaParams), C.c_uint64
         L.lh_accel_set_emitters.argtypes = [vp, vp, sz]
         L.lh_accel_area_lights_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, ap, i32, app, u64, vp, vp, vp, sz, vp, vp, vp, vp]
@@ -1252,6 +1266,56 @@ class HipAccel:
                                              int(spp_count), int(spp_total), int(max_vertices), int(flags),
                                              C.byref(override) if override is not None else None, arr, n, pp, skp, int(seed), _dptr(out),
                                              C.byref(st), C.c_void_p(stream)), "lh_render_pt_bands_lit")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def _lights_args(self, what, lights, params, area, area_params, sink):
+        """-> (byref of a PtLights, byref of the sink or None, what both point to: kept alive by the caller until the call has returned)"""
+        arr, n, _pp, skp, sk = self._lit_args(what, lights, params, sink)
+        aarr, na = _area_array(what, area or ())
+        if area_params is not None and not isinstance(area_params, AreaParams):
+            raise ValueError("%s: area_params must be an AreaParams" % what)
+        pl = PtLights()
+        pl.lights = arr if arr is not None else None
+        pl.nlights = n
+        pl.params = C.pointer(params) if params is not None else None
+        pl.area = aarr if aarr is not None else None
+        pl.narea = na
+        pl.area_params = C.pointer(area_params) if area_params is not None else None
+        return C.byref(pl), skp, (pl, arr, aarr, params, area_params, sk)
+
+    def render_pt_tile_lights(self, cam, x0, y0, w, h, spp_begin, spp_count, spp_total, max_vertices=8, flags=0, lights=(), params=None, area=(),
+                              area_params=None, sink=None, seed=1, out=None, stream=None):
+        """lh_render_pt_tile_lights: render_pt_tile_lit with soft shadows -- `area` (a sequence of 0 .. AREA_LIGHTS_MAX AreaLight over the emitter
+        table of set_emitters; area_params: an AreaParams, None: eps 1e-5, bound 1, 16 samples) lights every path vertex beside, or instead
+        of, `lights`: the area value of a hit of bounce d is area_lights_device's for the key of its path's (frame pixel, sample) and the
+        bounce's seed; with both kinds a hit's value is the float32 sum of the two -> (out, stats)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        plp, skp, _keep = self._lights_args("lh_render_pt_tile_lights", lights, params, area, area_params, sink)
+        st = PtStats()
+        _check(self.L.lh_render_pt_tile_lights(self.h, C.byref(cam), x0, y0, w, h, spp_begin, spp_count, spp_total, max_vertices, int(flags),
+                                               plp, skp, int(seed), _dptr(out), C.byref(st), C.c_void_p(stream)), "lh_render_pt_tile_lights")
+        return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def render_pt_bands_lights(self, cam, y0_first, band_rows, band_stride, nbands, spp_begin, spp_count, spp_total, max_vertices=8, flags=0,
+                               override=None, lights=(), params=None, area=(), area_params=None, sink=None, seed=1, out=None, stream=None):
+        """lh_render_pt_bands_lights: render_pt_bands_lit with the area lights of render_pt_tile_lights -> (out, stats)"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.zeros((nbands, band_rows, cam.width, 3), dtype=torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        plp, skp, _keep = self._lights_args("lh_render_pt_bands_lights", lights, params, area, area_params, sink)
+        st = PtStats()
+        _check(self.L.lh_render_pt_bands_lights(self.h, C.byref(cam), int(y0_first), int(band_rows), int(band_stride), int(nbands), int(spp_begin),
+                                                int(spp_count), int(spp_total), int(max_vertices), int(flags),
+                                                C.byref(override) if override is not None else None, plp, skp, int(seed), _dptr(out),
+                                                C.byref(st), C.c_void_p(stream)), "lh_render_pt_bands_lights")
         return out, {k: int(getattr(st, k)) for k, _ in st._fields_}
 
     def set_material(self, mesh, material):

@@ -564,7 +564,8 @@ static int upload_array(lh_accel_t *a, void **slot, const void *src, size_t byte
 static void release_device(lh_accel_t *a)
 {
     lh_buf *bufs[] = {&a->r_org, &a->r_dir, &a->r_prim, &a->r_t, &a->r_u, &a->r_v, &a->stage, &a->diag_drop,
-                      &a->p_org2, &a->p_dir2, &a->p_path, &a->p_path2, &a->p_thr, &a->p_thr2, &a->p_rad, &a->p_counts, &a->p_value};
+                      &a->p_org2, &a->p_dir2, &a->p_path, &a->p_path2, &a->p_thr, &a->p_thr2, &a->p_rad, &a->p_counts, &a->p_value,
+                      &a->p_value2, &a->p_key};
     for (size_t i = 0; i < sizeof(bufs) / sizeof(bufs[0]); i++) free_buf(bufs[i]);
     /* the gather stage's scratch table: every entry is lh_buf after lh_buf */
     static_assert(sizeof(a->gather) == sizeof(lh_buf) * LH_GATHER_BUFS * LH_GATHER_KINDS * 2, "lh_gather_scratch holds lh_buf members only");

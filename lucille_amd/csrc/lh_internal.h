@@ -197,6 +197,7 @@ struct lh_accel {
     int fast_start;                    /* device-built scenes: launch before lucille's own tree is attached (ties by primitive id until then) */
     lh_buf p_org2, p_dir2, p_path, p_path2, p_thr, p_thr2, p_rad, p_counts;   /* path tracer */
     lh_buf p_value;                    /* ... with lights (lh_ptl.h): 12 bytes per entry of a bounce, the light stage's value, then the hit's direct light */
+    lh_buf p_value2, p_key;            /* ... with area lights: 12 bytes per entry, the area stage's value, and the entry's 8-byte key for its generator */
     unsigned long long *d_total;
     size_t r_nsamples, r_nslots, r_nao;
     struct lh_combiner *comb;          /* lh_accel_intersect1: concurrent single-ray callers coalesced into one launch (lh_query.hip) */
@@ -423,6 +424,10 @@ extern "C" int lh_pt_launch_direct(size_t n_max, const double *d_col9, const uin
                                    const lh_material_t *override_mat, int depth, int spp, const uint32_t *d_counts, const uint32_t *d_prim,
                                    const double *d_u, const double *d_v, const uint32_t *d_path_of, const float *d_thr, float *d_value, int keep,
                                    unsigned long long *d_accum, int ncus, void *stream);
+/* ... with area lights: a bounce's keys for the area stage's generator, and the two stages' values folded into one */
+extern "C" int lh_pt_launch_area_keys(size_t n_max, int depth, int spp_total, const void *d_cam, const uint32_t *d_counts, const uint32_t *d_path_of,
+                                      unsigned long long *d_key, int ncus, void *stream);
+extern "C" int lh_pt_launch_value_add(size_t n_max, int depth, const uint32_t *d_counts, float *d_value, const float *d_area, int ncus, void *stream);
 extern "C" int lh_pt_launch_sink(size_t n_max, int depth, const uint32_t *d_counts, const double *d_org, const double *d_dir, const uint32_t *d_prim,
                                  const double *d_t, const double *d_u, const double *d_v, const uint32_t *d_path_of, const float *d_thr,
                                  const float *d_direct, const lh_pt_sink_t *sink, int ncus, void *stream);

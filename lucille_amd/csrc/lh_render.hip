@@ -1276,7 +1276,8 @@ __global__ __launch_bounds__(256) void k_pt_resolve(int w, int h, int band_rows,
  * Between the closest-hit launch of bounce `depth` and its shading pass, for a caller with lights or a sink (lh_tile.hip pt_tile): the light
  * stage of a caller's batch answers `value` for the bounce's entries, k_pt_direct turns it into the hits' r and adds that to their pixels,
  * k_pt_sink hands the entries out.  Bounce 0 has no ray in memory (the closest-hit walk makes the camera rays in its refill): the stage and
- * the sink read them from the arrays k_pt_camera_rays fills. */
+ * the sink read them from the arrays k_pt_camera_rays fills.  With area lights the area stage answers a second `value`, keyed per entry by
+ * k_pt_area_keys; k_pt_value_add folds the two where a pass has both kinds. */
 
 /* the pass's camera rays, pt_camera_ray per path id */
 __global__ __launch_bounds__(256) void k_pt_camera_rays(uint32_t n, const PtCamSrc *__restrict__ cam, double *__restrict__ org, double *__restrict__ dir)
@@ -1333,6 +1334,33 @@ __global__ __launch_bounds__(256) void k_pt_direct(const PtLit ps, const double 
         }
         if (keep && in) { value[3 * (size_t)i] = r0; value[3 * (size_t)i + 1] = r1; value[3 * (size_t)i + 2] = r2; }
         pt_accumulate(accum, lh_div(path, ps.spp), hit, r0, r1, r2, lane);
+    }
+}
+
+/* a pass with both kinds of light (lh_ptl.h): `value` holds the delta stage's answer per entry, `area` the area stage's; value_k = delta_k + area_k
+ * becomes the entry's one value, in place, before k_pt_direct reads it.  One streaming pass over counts[depth] entries, three floats each; a miss's
+ * slots hold what the stages left there and nobody reads them */
+__global__ __launch_bounds__(256) void k_pt_value_add(int depth, const uint32_t *__restrict__ counts, float *__restrict__ value, const float *__restrict__ area)
+{
+    LH_NC
+    const uint32_t n = counts[depth];
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u)
+        for (int c = 0; c < 3; c++) value[3 * (size_t)i + c] = lh_ptl_value(value[3 * (size_t)i + c], area[3 * (size_t)i + c]);
+}
+
+/* the keys of bounce `depth`'s entries for the area stage's generator (lh_ptl.h): one streaming pass over counts[depth] entries, path word ->
+ * (pixel of the pass, sample) -> frame pixel (pt_pixel) -> lh_ptl_area_key, one 8-byte store per entry.  cam: the pass as k_pt_begin wrote it */
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_pt_area_keys(int depth, int spp_total, const PtCamSrc *__restrict__ cam, const uint32_t *__restrict__ counts,
+                                                      const uint32_t *__restrict__ path_of, unsigned long long *__restrict__ key)
+{
+    const uint32_t n = counts[depth];
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+        const uint32_t path = (FIRST ? i : path_of[i]) & ~LH_PT_INTERIOR;
+        const uint32_t pix = lh_div(path, cam->dv.spp);
+        int px, py;
+        pt_pixel(pix, cam->x0, cam->y0, cam->w, cam->band_rows, cam->band_stride, cam->dv, px, py);
+        key[i] = lh_ptl_area_key(px, py, cam->cam.width, spp_total, cam->s0, (int)(path - pix * (uint32_t)cam->spp));
     }
 }
 
@@ -1747,6 +1775,27 @@ extern "C" int lh_pt_launch_direct(size_t n_max, const double *d_col9, const uin
     else
         hipLaunchKernelGGL((k_pt_direct<false>), grid, dim3(256), 0, (hipStream_t)stream, ps, d_col9, d_prim_mesh, (const DevMaterial *)d_materials, d_counts,
                            d_prim, d_u, d_v, d_path_of, d_thr, d_value, keep, d_accum);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* the area stage's keys of bounce `depth` (lh_ptl.h) for counts[depth] entries (at most n_max) into d_key; d_cam: what lh_pt_launch_begin wrote */
+extern "C" int lh_pt_launch_area_keys(size_t n_max, int depth, int spp_total, const void *d_cam, const uint32_t *d_counts, const uint32_t *d_path_of,
+                                      unsigned long long *d_key, int ncus, void *stream)
+{
+    if (n_max == 0) return 0;
+    const dim3 grid(pt_lit_grid(n_max, ncus));
+    if (depth == 0)
+        hipLaunchKernelGGL((k_pt_area_keys<true>), grid, dim3(256), 0, (hipStream_t)stream, depth, spp_total, (const PtCamSrc *)d_cam, d_counts, d_path_of, d_key);
+    else
+        hipLaunchKernelGGL((k_pt_area_keys<false>), grid, dim3(256), 0, (hipStream_t)stream, depth, spp_total, (const PtCamSrc *)d_cam, d_counts, d_path_of, d_key);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+/* both kinds of light: d_value (the delta stage's answer) += d_area (the area stage's) over counts[depth] entries, before lh_pt_launch_direct */
+extern "C" int lh_pt_launch_value_add(size_t n_max, int depth, const uint32_t *d_counts, float *d_value, const float *d_area, int ncus, void *stream)
+{
+    if (n_max == 0) return 0;
+    hipLaunchKernelGGL(k_pt_value_add, dim3(pt_lit_grid(n_max, ncus)), dim3(256), 0, (hipStream_t)stream, depth, d_counts, d_value, d_area);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -15,6 +15,7 @@
 #include "lh_sky.h"
 #include "lh_lights.h"
 #include "lh_area.h"
+#include "lh_ptl.h"
 
 #define ensure_buf lh_ensure_buf
 
@@ -1153,10 +1154,10 @@ int lh_ensure_prim_mesh(lh_accel_t *a)
 /* wavefront path tracer (kernels: lh_render.hip, arithmetic: lh_pt.h)       */
 /* ------------------------------------------------------------------------ */
 
-/* what the _lit entry points add to a pass (lh_ptl.h; both NULL: the pass as it ever was): the checked light list as the light stage takes it, and
- * the caller's path-vertex sink */
-struct pt_lit { const char *what; const gather_params *lights; const lh_pt_sink_t *sink; };
-static const pt_lit pt_unlit = {NULL, NULL, NULL};
+/* what the _lit and _lights entry points add to a pass (lh_ptl.h; all NULL: the pass as it ever was): the checked light list as the light stage
+ * takes it, the checked area list as the area stage takes it, and the caller's path-vertex sink */
+struct pt_lit { const char *what; const gather_params *lights; const lh_pt_sink_t *sink; const gather_params *area; };
+static const pt_lit pt_unlit = {NULL, NULL, NULL, NULL};
 
 /* the sink's refusals: its double arrays 8-byte aligned, the others 4-byte */
 static int pt_sink_ok(const char *what, const lh_pt_sink_t *k)
@@ -1168,12 +1169,23 @@ static int pt_sink_ok(const char *what, const lh_pt_sink_t *k)
     return 0;
 }
 
-/* what a lit pass does between the closest-hit launch of bounce `depth` and its shading pass: the light stage over the bounce's entries and their
+/* the statistics words of the launches so far, off the device before a stage of a lit bounce resets and counts them for itself */
+static int pt_take_counters(const unsigned long long *cnt, unsigned long long *closest_cnt, hipStream_t s)
+{
+    unsigned long long hc[LH_CNT_N];
+    HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < LH_CNT_N; k++) closest_cnt[k] += hc[k];
+    return 0;
+}
+
+/* what a lit pass does between the closest-hit launch of bounce `depth` and its shading pass: the light stages over the bounce's entries and their
  * direct light into the pixels (with lights), the entries into the sink (with one).  org / dir / path / thr: the bounce's own sets (NULL at bounce 0);
- * value: p_value or NULL; cnt: the statistics words or NULL, closest_cnt: where the closest-hit launches' words are kept while the stage counts */
-static int pt_lit_bounce(lh_accel_t *a, const pt_lit &lit, size_t S, int depth, int spp, const lh_material_t *override_mat, const void *d_cam,
-                         const uint32_t *counts, const double *org, const double *dir, const uint32_t *path, const float *thr, float *value,
-                         unsigned long long *cnt, unsigned long long *closest_cnt, hipStream_t s)
+ * value: where the hits' one value and then r stand (p_value; p_value2 with area lights alone) or NULL; spp_total, seed: the pass's, for the area
+ * stage's keys and seed; cnt: the statistics words or NULL, closest_cnt: where the closest-hit launches' words are kept while a stage counts */
+static int pt_lit_bounce(lh_accel_t *a, const pt_lit &lit, size_t S, int depth, int spp, int spp_total, uint64_t seed, const lh_material_t *override_mat,
+                         const void *d_cam, const uint32_t *counts, const double *org, const double *dir, const uint32_t *path, const float *thr,
+                         float *value, unsigned long long *cnt, unsigned long long *closest_cnt, hipStream_t s)
 {
     /* bounce 0 has no ray in memory: the light stage and the sink read the camera rays from the second ray set, free until the swap after bounce 0 */
     if (depth == 0) {
@@ -1183,15 +1195,25 @@ static int pt_lit_bounce(lh_accel_t *a, const pt_lit &lit, size_t S, int depth, 
     if (lit.lights) {
         /* the light stage of a caller's batch over the bounce's entries, behind the guard this call holds: the identity list with its count on
          * the device.  It resets and counts the statistics words for itself */
-        if (cnt) {
-            unsigned long long hc[LH_CNT_N];
-            HIPCHK(hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            for (int k = 0; k < LH_CNT_N; k++) closest_cnt[k] += hc[k];
-        }
+        if (cnt && pt_take_counters(cnt, closest_cnt, s) != 0) return -1;
         if (ao_batch_device(lit.what, a, *lit.lights, S, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, 1, 0, NULL, NULL, NULL, S, counts + depth,
                             NULL, value, s) != 0) return -1;
         if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+    }
+    if (lit.area) {
+        /* the area stage likewise, keyed per entry by (frame pixel, sample) and seeded per bounce (lh_ptl.h), no uniforms replayed; with delta lights
+         * too its answer goes beside theirs and the two are folded into the hits' one value */
+        float *area_value = lit.lights ? (float *)a->p_value2.p : value;
+        if (lh_pt_launch_area_keys(S, depth, spp_total, d_cam, counts, path, (unsigned long long *)a->p_key.p, a->ncus, s) != 0)
+            return fail("pt area key launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if (cnt && pt_take_counters(cnt, closest_cnt, s) != 0) return -1;
+        if (ao_batch_device(lit.what, a, *lit.area, S, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, 1, lh_ptl_area_seed(seed, depth), a->p_key.p, NULL,
+                            NULL, S, counts + depth, NULL, area_value, s) != 0) return -1;
+        if (cnt) HIPCHK(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * LH_CNT_DEV, s));
+        if (lit.lights && lh_pt_launch_value_add(S, depth, counts, value, area_value, a->ncus, s) != 0)
+            return fail("pt value fold launch failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (lit.lights || lit.area) {
         if (lh_pt_launch_direct(S, (const double *)a->d_attr9[0], (const uint32_t *)a->d_prim_mesh, a->d_materials, override_mat, depth, spp, counts,
                                 (const uint32_t *)a->r_prim.p, (const double *)a->r_u.p, (const double *)a->r_v.p, path, thr, value,
                                 lit.sink && lit.sink->d_direct, (unsigned long long *)a->p_rad.p, a->ncus, s) != 0)
@@ -1211,6 +1233,10 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
 {
     if (w <= 0 || h <= 0 || spp < 1 || spp_total < spp || max_vertices < 2 || max_vertices > 65536 || band_rows < 1 || h % band_rows != 0)
         return fail("lh_render_pt_tile: bad arguments");
+    /* with area lights an entry's key is (frame pixel, sample) and the stage's generator reads 34 bits of it (lh_ptl.h) */
+    if (lit.area && !lh_ptl_area_keys_ok(cam->width, cam->height, spp_total))
+        return fail("%s: with area lights width x height x spp_total = %d x %d x %d exceeds the 2^34 keys of the area stage's generator", lit.what,
+                    cam->width, cam->height, spp_total);
     HIPCHK(hipSetDevice(a->device));
     if (sync_materials(a) != 0) return -1;
     hipStream_t s = (hipStream_t)stream;
@@ -1218,7 +1244,7 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
     if (S > ((size_t)1 << 30)) return fail("lh_render_pt_tile: more than 2^30 paths in one pass; lower spp_count or the tile size");
     if (spp > 4096) return fail("lh_render_pt_tile: more than 4096 samples of a pixel in one pass (the pixels' fixed-point sums); lower spp_count");
     /* with lights every entry of every bounce may add a term to its pixel (a hit its direct light, a miss the environment): a path up to max_vertices - 1 */
-    if (lit.lights && (size_t)spp * (size_t)(max_vertices - 1) > 4096)
+    if ((lit.lights || lit.area) && (size_t)spp * (size_t)(max_vertices - 1) > 4096)
         return fail("%s: with lights spp_count x (max_path_vertices - 1) = %d x %d exceeds 4096 terms of a pixel in one pass (the pixels' fixed-point sums); "
                     "lower spp_count", lit.what, spp, max_vertices - 1);
     unsigned long long *cnt = (a->stat_on && a->hs->bvh.ntris) ? a->d_counters : NULL;      /* lh_accel_trace_statistics */
@@ -1229,9 +1255,10 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
         ensure_buf(&a->r_u, S * 8) || ensure_buf(&a->r_v, S * 8) || ensure_buf(&a->p_path, S * 4) ||
         ensure_buf(&a->p_path2, S * 4) || ensure_buf(&a->p_thr, S * 12) || ensure_buf(&a->p_thr2, S * 12) ||
         ensure_buf(&a->p_rad, (size_t)w * h * 24) || ensure_buf(&a->p_counts, ((size_t)nbounce + 2) * 4 + 64 + lh_pt_cam_bytes())) return -1;
-    const bool lit_pass = lit.lights || lit.sink;          /* lh_ptl.h; neither: not one launch or buffer more than before */
+    const bool lit_pass = lit.lights || lit.area || lit.sink;          /* lh_ptl.h; none: not one launch or buffer more than before */
     if (lit.lights && ensure_buf(&a->p_value, S * 12)) return -1;
-    float *value = lit.lights ? (float *)a->p_value.p : NULL;
+    if (lit.area && (ensure_buf(&a->p_value2, S * 12) || ensure_buf(&a->p_key, S * 8))) return -1;
+    float *value = lit.lights ? (float *)a->p_value.p : (lit.area ? (float *)a->p_value2.p : NULL);
     unsigned long long closest_cnt[LH_CNT_N] = {0};       /* with lights: the closest-hit launches' words, taken before the light stage resets them */
     /* the chain's ray / path-word / throughput records alternate between two sets; bounce 0 reads none (its rays are the camera
      * rays, generated inside the closest-hit kernel and again by the shading pass for the paths that go on) */
@@ -1252,7 +1279,7 @@ static int pt_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w,
         rc = lh_launch(a, lh_batch_t{S, LH_MODE_CLOSEST, org, dir, a->r_prim.p, a->r_t.p, a->r_u.p, a->r_v.p, NULL, cnt}, LH_VARIANT_SPEC, s, false, opt);
         if (rc != 0) break;
         if (lit_pass) {
-            rc = pt_lit_bounce(a, lit, S, depth, spp, override_mat, d_cam, counts, org, dir, path, thr, value, cnt, closest_cnt, s);
+            rc = pt_lit_bounce(a, lit, S, depth, spp, spp_total, seed, override_mat, d_cam, counts, org, dir, path, thr, value, cnt, closest_cnt, s);
             if (rc != 0) break;
         }
         if (lh_pt_launch_shade(S, &a->dev, (const double *)a->d_nrm9, (const double *)a->d_attr9[0], (const uint32_t *)a->d_prim_mesh,
@@ -1325,17 +1352,62 @@ extern "C" int lh_render_pt_tile2(lh_accel_t *a, const lh_camera_t *cam, int x0,
 }
 
 /* the _lit forms' own refusals, before anything is enqueued: the list as the light stage refuses it (nlights == 0: none), the sink's pointers.
- * p: the checked list; out: what pt_tile takes */
-static int pt_lit_check(const char *what, const lh_light_t *lights, int nlights, const lh_lights_params_t *params, const lh_pt_sink_t *sink,
-                        gather_params *p, pt_lit *out)
+ * The _lights forms' area list likewise, as the area stage refuses it (area NULL or nlights == 0: none).  p, pa: the checked lists; out: what pt_tile
+ * takes */
+static int pt_lit_check(const char *what, const lh_light_t *lights, int nlights, const lh_lights_params_t *params, const area_in *area,
+                        const lh_pt_sink_t *sink, gather_params *p, gather_params *pa, pt_lit *out)
 {
-    *out = pt_lit{what, NULL, sink};
+    *out = pt_lit{what, NULL, sink, NULL};
     if (nlights != 0) {
         const lights_in in = {lights, nlights, params};
         if (gather_check(what, LH_GATHER_LIGHT, &in, p) != 0) return -1;
         out->lights = p;
     }
+    if (area && area->nlights != 0) {
+        if (gather_check(what, LH_GATHER_AREA, area, pa) != 0) return -1;
+        out->area = pa;
+    }
     return sink ? pt_sink_ok(what, sink) : 0;
+}
+
+/* the _lights forms' lh_pt_lights_t (NULL: no lights at all): its reserved words, then both lists through pt_lit_check; the area list's runs must lie
+ * in a's emitter table (none, or no accelerator: "bad area lights") */
+static int pt_lights_check(const char *what, const lh_accel_t *a, const lh_pt_lights_t *l, const lh_pt_sink_t *sink, gather_params *p, gather_params *pa,
+                           pt_lit *out)
+{
+    static const lh_pt_lights_t none = {NULL, 0, 0, NULL, NULL, 0, 0, NULL};
+    if (!l) l = &none;
+    if (l->reserved0 != 0 || l->reserved1 != 0) return fail("%s: the reserved words of lh_pt_lights_t must be 0", what);
+    const area_in area = {l->area, l->narea, l->area_params, a};
+    return pt_lit_check(what, l->lights, l->nlights, l->params, &area, sink, p, pa, out);
+}
+
+/* the lit forms behind their lists' and sink's refusals: lh_render_pt_tile2 / lh_render_pt_bands with what `lit` adds */
+static int pt_lit_tile(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total, int max_vertices, int flags,
+                       uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream, const pt_lit &lit)
+{
+    if (!a || !a->committed) return fail("%s: accel not committed", lit.what);
+    if (!cam || !d_rgb) return fail("%s: NULL argument", lit.what);
+    float one[3] = {1.0f, 1.0f, 1.0f};
+    const float *rgb = a->env_set ? a->env.rgb : one;
+    return pt_tile(a, cam, x0, y0, w, h, h, 0, s0, spp, spp_total, max_vertices, NULL, rgb, a->d_env_map, a->env.width, a->env.height, flags,
+                   seed, d_rgb, stats, stream, lit);
+}
+
+static int pt_lit_bands(lh_accel_t *a, const lh_camera_t *cam, int y0_first, int band_rows, int band_stride, int nbands, int s0, int spp, int spp_total,
+                        int max_vertices, int flags, const lh_material_t *override_mat, uint64_t seed, void *d_rgb, lh_pt_stats_t *stats, void *stream,
+                        const pt_lit &lit)
+{
+    const char *what = lit.what;
+    if (!a || !a->committed) return fail("%s: accel not committed", what);
+    if (!cam || !d_rgb) return fail("%s: NULL argument", what);
+    if (nbands < 1 || band_rows < 1 || y0_first < 0 || (nbands > 1 && band_stride < band_rows) ||
+        (long long)y0_first + (long long)(nbands - 1) * band_stride + band_rows > cam->height)
+        return fail("%s: bands must be disjoint and inside the frame", what);
+    float one[3] = {1.0f, 1.0f, 1.0f};
+    const float *rgb = a->env_set ? a->env.rgb : one;
+    return pt_tile(a, cam, 0, y0_first, cam->width, nbands * band_rows, band_rows, band_stride, s0, spp, spp_total, max_vertices, override_mat, rgb,
+                   a->d_env_map, a->env.width, a->env.height, flags, seed, d_rgb, stats, stream, lit);
 }
 
 /* lh_render_pt_tile2 with direct light from a light list at every path vertex and a path-vertex sink (lh_ptl.h) */
@@ -1346,13 +1418,19 @@ extern "C" int lh_render_pt_tile_lit(lh_accel_t *a, const lh_camera_t *cam, int 
     lh_guard guard(a);
     const char *what = "lh_render_pt_tile_lit";
     gather_params p; pt_lit lit;
-    if (pt_lit_check(what, lights, nlights, params, sink, &p, &lit) != 0) return -1;
-    if (!a || !a->committed) return fail("%s: accel not committed", what);
-    if (!cam || !d_rgb) return fail("%s: NULL argument", what);
-    float one[3] = {1.0f, 1.0f, 1.0f};
-    const float *rgb = a->env_set ? a->env.rgb : one;
-    return pt_tile(a, cam, x0, y0, w, h, h, 0, s0, spp, spp_total, max_vertices, NULL, rgb, a->d_env_map, a->env.width, a->env.height, flags,
-                   seed, d_rgb, stats, stream, lit);
+    if (pt_lit_check(what, lights, nlights, params, NULL, sink, &p, NULL, &lit) != 0) return -1;
+    return pt_lit_tile(a, cam, x0, y0, w, h, s0, spp, spp_total, max_vertices, flags, seed, d_rgb, stats, stream, lit);
+}
+
+/* lh_render_pt_tile_lit with area lights beside, or instead of, the delta lights (lh_ptl.h) */
+extern "C" int lh_render_pt_tile_lights(lh_accel_t *a, const lh_camera_t *cam, int x0, int y0, int w, int h, int s0, int spp, int spp_total,
+                                        int max_vertices, int flags, const lh_pt_lights_t *lights, const lh_pt_sink_t *sink, uint64_t seed,
+                                        void *d_rgb, lh_pt_stats_t *stats, void *stream)
+{
+    lh_guard guard(a);          /* (held from here on: the emitter table's count is read under the lock the stages then hold) */
+    gather_params p, pa; pt_lit lit;
+    if (pt_lights_check("lh_render_pt_tile_lights", a, lights, sink, &p, &pa, &lit) != 0) return -1;
+    return pt_lit_tile(a, cam, x0, y0, w, h, s0, spp, spp_total, max_vertices, flags, seed, d_rgb, stats, stream, lit);
 }
 
 /* a rank's interleaved full-width bands of a sharded frame as ONE pass: nbands bands of band_rows lines, band k starting at
@@ -1383,16 +1461,20 @@ extern "C" int lh_render_pt_bands_lit(lh_accel_t *a, const lh_camera_t *cam, int
     lh_guard guard(a);
     const char *what = "lh_render_pt_bands_lit";
     gather_params p; pt_lit lit;
-    if (pt_lit_check(what, lights, nlights, params, sink, &p, &lit) != 0) return -1;
-    if (!a || !a->committed) return fail("%s: accel not committed", what);
-    if (!cam || !d_rgb) return fail("%s: NULL argument", what);
-    if (nbands < 1 || band_rows < 1 || y0_first < 0 || (nbands > 1 && band_stride < band_rows) ||
-        (long long)y0_first + (long long)(nbands - 1) * band_stride + band_rows > cam->height)
-        return fail("%s: bands must be disjoint and inside the frame", what);
-    float one[3] = {1.0f, 1.0f, 1.0f};
-    const float *rgb = a->env_set ? a->env.rgb : one;
-    return pt_tile(a, cam, 0, y0_first, cam->width, nbands * band_rows, band_rows, band_stride, s0, spp, spp_total, max_vertices, override_mat, rgb,
-                   a->d_env_map, a->env.width, a->env.height, flags, seed, d_rgb, stats, stream, lit);
+    if (pt_lit_check(what, lights, nlights, params, NULL, sink, &p, NULL, &lit) != 0) return -1;
+    return pt_lit_bands(a, cam, y0_first, band_rows, band_stride, nbands, s0, spp, spp_total, max_vertices, flags, override_mat, seed, d_rgb, stats, stream, lit);
+}
+
+/* lh_render_pt_bands_lit with the lights of lh_render_pt_tile_lights */
+extern "C" int lh_render_pt_bands_lights(lh_accel_t *a, const lh_camera_t *cam, int y0_first, int band_rows, int band_stride, int nbands,
+                                         int s0, int spp, int spp_total, int max_vertices, int flags, const lh_material_t *override_mat,
+                                         const lh_pt_lights_t *lights, const lh_pt_sink_t *sink, uint64_t seed, void *d_rgb, lh_pt_stats_t *stats,
+                                         void *stream)
+{
+    lh_guard guard(a);
+    gather_params p, pa; pt_lit lit;
+    if (pt_lights_check("lh_render_pt_bands_lights", a, lights, sink, &p, &pa, &lit) != 0) return -1;
+    return pt_lit_bands(a, cam, y0_first, band_rows, band_stride, nbands, s0, spp, spp_total, max_vertices, flags, override_mat, seed, d_rgb, stats, stream, lit);
 }
 
 /* ------------------------------------------------------------------------ */
